@@ -9,10 +9,13 @@ owns `--pairs` pairs (weak scaling), no data-path collective except that gather.
 
     python bench.py [--gpus N --steps K --warmup W] [--pairs P] [--candidates dense|c2f|dso] [--arith fused|exact]
                     [--rows R --cols C --levels L --huber D]     (config 5: --rows 960 --cols 1280 --levels 7 --huber 10 --pairs 512)
+                    [--dump-outputs DIR] [--full]
 
 N > 1 is launched by the driver as: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
-Rank 0 prints ONE JSON line.  The CPU oracle (oracle/) is used here only for the `cpu_baseline` / `parity` leg (it is the
-checker and the baseline, never the thing measured); everything timed on the GPU goes through libvors_hip.so alone.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the stage
+times and roofline of those steps); everything else — live PMC passes, other batch sizes / candidate modes / arithmetics / shapes, throughput
+mode, sequences, CPU baselines, oracle parity — runs only with --full. The CPU oracle (oracle/) is used here only for the `cpu_baseline` /
+`parity` legs (it is the checker and the baseline, never the thing measured); everything timed on the GPU goes through libvors_hip.so alone.
 
 Byte model (refined as VERDICT r01 asks): per point-evaluation 9 B dense / 13 B sparse (coordinates 4 when stored,
 inverse depth 4, template 1, four taps 4) for every energy evaluation, + 4 B (gx, gy) for the evaluations whose g and H the reference
@@ -77,6 +80,13 @@ def parse():
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                    help="process-group backend for N > 1: nccl (= RCCL over xGMI, the measured configuration) or gloo (control-plane test of "
                         "the N > 1 code path on a box with fewer GPUs than ranks: ranks then share devices round-robin)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline (the --no-* options above trim it): live rocprofv3 PMC passes, the 256 / 512-pair batches, "
+                        "the other candidate modes, throughput mode (rings), the REFERENCE block, sequences, config 5, CPU baselines, oracle parity "
+                        "and parity_pinned; N > 1: the rings and the other scaling reading. Off: only the headline")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the timed path computed in its last step (poses, status, per-pair stats; rank 0's, and the gathered table "
+                        "for N > 1) as DIR/<name>.npy in float32; the inputs are seeded, identical from run to run")
     return p.parse_args()
 
 
@@ -171,6 +181,38 @@ def live_counters(args, candidates=None):
         out["source"] = (f"measured in this run: rocprofv3 --pmc passes of this command (2 steps each, {time.perf_counter() - t0:.0f} s); "
                          "FETCH_SIZE KiB x 2 + WRITE_SIZE KiB per MI355X_MICROARCH.md")
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(V, work, gathered=None):
+    """What the timed path hands its caller after a step, on the host: poses, status and the per-pair diagnostics (vors_pair_stats), plus
+    the gathered [world * P, 8] table for N > 1 — all float32 (the integer fields are exact in it). Beyond DUMP_LIMIT_BYTES in all, a fixed
+    seeded sample of the pairs is kept (the same rows of every array, and of every rank's block of the gathered table; `sample_pairs`)."""
+    st = V.decode_stats(work.stats)
+    arrays = {"poses": work.poses.cpu().numpy(), "status": work.status.cpu().numpy()}
+    for name in st.dtype.names:
+        arrays["stats_" + name] = st[name]
+    if gathered is not None:
+        arrays["gathered"] = gathered.cpu().numpy()
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = work.n
+        k = max(1, int(n * DUMP_LIMIT_BYTES / (total + 4 * n) * 0.95))
+        keep = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        for name, a in arrays.items():
+            rows = keep if name != "gathered" else (np.arange(len(a) // n)[:, None] * n + keep[None, :]).ravel()
+            arrays[name] = np.ascontiguousarray(a[rows])
+        arrays["sample_pairs"] = keep.astype(np.float32)
+    return arrays
+
+
+def write_outputs(arrays, d):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def arith_id(V, name):
@@ -783,15 +825,17 @@ def main():
     ring = min(max(args.steps, 1), 4096)
     if args.graph:
         main_w.capture()
-        dt = timed_run(main_w, args.steps, args.warmup, world, packed, gathered)
+    else:
+        main_w.batch.enable_kernel_timing(ring)
+    dt = timed_run(main_w, args.steps, args.warmup, world, packed, gathered)
+    if args.dump_outputs and rank == 0:   # the last timed step's results, before anything below runs the workload again
+        write_outputs(output_arrays(V, main_w, gathered), args.dump_outputs)
+    if args.graph:
         main_w.graph = None
         main_w.batch.enable_kernel_timing(ring)   # kernel durations from a few eager steps after the timed region
         for _ in range(min(args.steps, 5)):
             main_w.step()
         torch.cuda.synchronize()
-    else:
-        main_w.batch.enable_kernel_timing(ring)
-        dt = timed_run(main_w, args.steps, args.warmup, world, packed, gathered)
     lm_ms = main_w.batch.kernel_times("lm")[-args.steps:]
     kf_ms = main_w.batch.kernel_times("keyframe")[-args.steps:]
     pyr_ms = main_w.batch.kernel_times("pyramid_keyframe")[-args.steps:] + main_w.batch.kernel_times("pyramid_current")[-args.steps:]
@@ -807,7 +851,7 @@ def main():
     job_gbps = (b_io + b_lm) * world * args.steps / dt / 1e9
     gt_err = np.abs(stats["lm_model"] - main_w.gt.cpu().numpy()).max(axis=1)
     cnt = {}
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc:
         cnt = live_counters(args)
     if "traffic_bytes" not in cnt:
         cnt = lm_counters(args) or cnt
@@ -952,21 +996,24 @@ def main():
             del r
             return {"ring": 3, "value": round(total * args.steps / dt_p, 2), "unit": "frame-pairs/s", "ms_per_step": round(dt_p / args.steps * 1e3, 4),
                     "note": "vors_pipeline_* ring of 3 handles per rank + the per-step all-gather; not `value`"}
-        out[args.scaling]["pipelined"] = pipelined_scaling(args, args.scaling)
-        other = "strong" if args.scaling == "weak" else "weak"
-        import copy
-        a2 = copy.copy(args)
-        a2.pairs = -(-args.total_pairs // world) if other == "strong" else pairs_weak
-        w2 = Workload(V, a2, args.candidates, device, 0x5EED0000 + rank * a2.pairs)
-        packed2 = torch.zeros((a2.pairs, 8), dtype=torch.float32, device=device)
-        gathered2 = torch.zeros((world * a2.pairs, 8), dtype=torch.float32, device=device)
-        dt_o = timed_run(w2, args.steps, args.warmup, world, packed2, gathered2)
-        out[other] = scaling_block(other, w2, dt_o, multi_gpu_self_check(a2, w2, packed2, gathered2, rank, world))
-        del w2
-        w2 = None
-        out[other]["pipelined"] = pipelined_scaling(a2, other)
-        out["config"]["value_is"] = f"`{args.scaling}` (see the `weak` and `strong` blocks; `strong` is BASELINE configs[3] as written)"
-        del packed2, gathered2
+        out["config"]["value_is"] = f"`{args.scaling}` (--full adds the rings and the other reading)"
+        if args.full:
+            out[args.scaling]["pipelined"] = pipelined_scaling(args, args.scaling)
+            other = "strong" if args.scaling == "weak" else "weak"
+            import copy
+            a2 = copy.copy(args)
+            a2.pairs = -(-args.total_pairs // world) if other == "strong" else pairs_weak
+            w2 = Workload(V, a2, args.candidates, device, 0x5EED0000 + rank * a2.pairs)
+            packed2 = torch.zeros((a2.pairs, 8), dtype=torch.float32, device=device)
+            gathered2 = torch.zeros((world * a2.pairs, 8), dtype=torch.float32, device=device)
+            dt_o = timed_run(w2, args.steps, args.warmup, world, packed2, gathered2)
+            out[other] = scaling_block(other, w2, dt_o, multi_gpu_self_check(a2, w2, packed2, gathered2, rank, world))
+            del w2
+            w2 = None
+            out[other]["pipelined"] = pipelined_scaling(a2, other)
+            out["config"]["value_is"] = f"`{args.scaling}` (see the `weak` and `strong` blocks; `strong` is BASELINE configs[3] as written)"
+            del packed2, gathered2
+
     def guarded(key, fn):
         # Everything after the headline is an EXTRA measurement: one that fails (a box with less memory, a missing tool) is recorded in
         # `errors` — loudly, in the line — instead of taking the line, and with it `value`, `roofline` and the other blocks, down.
@@ -979,7 +1026,7 @@ def main():
             except Exception:  # noqa: BLE001
                 pass
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         try:
             if not args.no_secondary:
                 # ---- SURVEY §8d batch size: 256 pairs (one per CU) of the same workload, and BASELINE config 4's per-GPU share on 8 GPUs (512)
@@ -1087,11 +1134,12 @@ def main():
             if parity_secondary is not None:
                 out["parity_secondary"] = parity_secondary
     if rank == 0:
-        # "bit-identical to the oracle" is NOT "bit-identical to vors" until a document produced by the Rust reference says so
-        from oracle.rust_pin import parity_pinned
-        pinned, detail = parity_pinned()
-        out["parity_pinned"] = pinned
-        out["parity_pinned_detail"] = detail
+        if args.full:
+            # "bit-identical to the oracle" is NOT "bit-identical to vors" until a document produced by the Rust reference says so
+            from oracle.rust_pin import parity_pinned
+            pinned, detail = parity_pinned()
+            out["parity_pinned"] = pinned
+            out["parity_pinned_detail"] = detail
         print(json.dumps(out))
     if world > 1:
         import torch.distributed as dist

@@ -153,7 +153,7 @@ def test_bench_two_ranks_code_path_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--pairs", "64", "--total-pairs", "96", "--candidates", "c2f", "--backend", "gloo"]
+           "--pairs", "64", "--total-pairs", "96", "--candidates", "c2f", "--backend", "gloo", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -185,7 +185,7 @@ def test_bench_two_ranks_strong_scaling_of_a_fixed_batch():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--steps", "3", "--warmup", "1", "--candidates", "c2f", "--scaling", "strong", "--total-pairs", "96", "--pairs", "32", "--no-secondary", "--no-pmc",
-              "--no-sequences", "--cpu-pairs", "0", "--parity-pairs", "0"]
+              "--no-sequences", "--cpu-pairs", "0", "--parity-pairs", "0", "--full"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo"] + common
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
@@ -213,7 +213,7 @@ def test_bench_single_rank_json_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--pairs", "64", "--steps", "3", "--warmup", "1", "--cpu-pairs", "4",
-                        "--parity-pairs", "16", "--no-sequences", "--no-pmc"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--parity-pairs", "16", "--no-sequences", "--no-pmc", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1
@@ -236,3 +236,46 @@ def test_bench_single_rank_json_contract():
     assert d["pipelined"]["ring"] == 3 and d["pipelined"]["value"] > 0 and d["parity_pinned"] in (True, False)
     assert d["config5"]["fused"]["value"] > 0 and d["config5"]["reference"]["parity_sample"]["n_poses_bit_identical"] == d["config5"]["reference"]["parity_sample"]["sample_pairs"]
     assert d["parity"]["status_equal"] and d["parity"]["n_beyond_tol"] <= d["parity"]["n_beyond_tol_oracle_f32_vs_f64_accumulation"] + 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py` (no --full) prints the headline alone; --dump-outputs writes what the timed path computed in its last
+    step, the same from run to run and the same as a batch of the same seeded pairs run here."""
+    import json
+    import subprocess
+    import sys
+    import vors_amd as V
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--pairs", "64", "--steps", "4", "--warmup", "1",
+                            "--candidates", "c2f", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines += [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 2
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "stages_ms"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["unit"] == "frame-pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 64 * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 1e-3
+    for k in ("cpu_baseline", "parity", "pipelined", "reference", "sequences_64", "config5", "batch_256", "secondary", "parity_pinned", "errors"):
+        assert k not in d, k
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert "poses.npy" in names and "status.npy" in names and "stats_nb_iter.npy" in names
+    assert sum((tmp_path / "a" / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and a.shape[0] == 64, n
+        assert (a.view(np.uint32) == b.view(np.uint32)).all(), n
+    # the same 64 pairs (bench.py's seeds) through a batch of this process: the dumped poses are those bits
+    intr = V.scaled_intrinsics(480, 640)
+    cfg = V.Config(nb_levels=6, intrinsics=V.Intrinsics(intr[:2], intr[2:4], intr[4]), candidates_mode=V.CANDIDATES_COARSE_TO_FINE,
+                   arithmetic=V.ARITH_FUSED)
+    kg, kd, cg, _, _ = V.synth_render_pairs(0x5EED0000, 64, 480, 640, intr, device="cuda")
+    poses = torch.zeros((64, 7), dtype=torch.float32, device="cuda")
+    status = torch.zeros(64, dtype=torch.int32, device="cuda")
+    V.Batch(cfg, 64, 480, 640).track_pairs(kg, kd, cg, poses, status)
+    torch.cuda.synchronize()
+    assert (np.load(tmp_path / "a" / "poses.npy").view(np.uint32) == poses.cpu().numpy().view(np.uint32)).all()
+    assert (np.load(tmp_path / "a" / "status.npy") == status.cpu().numpy()).all()

@@ -1,7 +1,11 @@
-# full GPU suite + the default bench line (what the driver runs at round end)
-cd /root/repo
-mkdir -p gpurun_out/r06
-( time python -m pytest tests -m gpu -x -q ) > gpurun_out/r06/gputest.log 2>&1
-( time python bench.py ) > gpurun_out/r06/bench_default.log 2>&1
-python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r06/smoke.log 2>&1
-tail -n 6 gpurun_out/r06/gputest.log; tail -c 1500 gpurun_out/r06/bench_default.log; tail -n 3 gpurun_out/r06/smoke.log
+# full GPU suite + the complete (--full) bench line + smoke(), from the repository root; logs under $1 (default validate_out/).
+# Stops at the first step that fails.
+cd "$(dirname "$0")/.." || exit 1
+OUT=${1:-validate_out}
+mkdir -p "$OUT"
+( time python -m pytest tests -m gpu -x -q ) > "$OUT/gputest.log" 2>&1 &&
+( time python bench.py --full ) > "$OUT/bench_full.log" 2>&1 &&
+python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
+rc=$?
+tail -n 6 "$OUT/gputest.log"; tail -c 1500 "$OUT/bench_full.log" 2>/dev/null; tail -n 3 "$OUT/smoke.log" 2>/dev/null
+exit $rc
