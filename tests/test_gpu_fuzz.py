@@ -28,7 +28,7 @@ def _cases():
     return out
 
 
-@pytest.mark.parametrize("arith", [V.ARITH_EXACT, V.ARITH_FUSED], ids=["exact", "fused"])
+@pytest.mark.parametrize("arith", [V.ARITH_REFERENCE, V.ARITH_EXACT, V.ARITH_FUSED], ids=["reference", "exact", "fused"])
 @pytest.mark.parametrize("i,rows,cols,L,mode,huber", _cases(), ids=lambda v: str(v))
 def test_random_shapes_vs_oracle(i, rows, cols, L, mode, huber, arith):
     import torch
@@ -61,6 +61,10 @@ def test_random_shapes_vs_oracle(i, rows, cols, L, mode, huber, arith):
     same_path = (st["nb_iter"][:, :L] == ref["nb_iter"]).all(axis=1)
     assert (err[ok] < POSE_TOL).all(), f"pose error {err} (rows={rows} cols={cols} L={L} mode={mode})"
     assert (p[~ok] == ref["poses"][~ok]).all()
+    if arith == V.ARITH_REFERENCE:  # the reference's own summation order: the same LM path and the same bits, not a tolerance
+        assert (st["nb_iter"][:, :L] == ref["nb_iter"]).all(), f"iteration counts {st['nb_iter'][:, :L]} vs {ref['nb_iter']}"
+        for got, want in ((p, ref["poses"]), (st["lm_model"], ref["models"]), (st["optical_flow"], ref["flow"])):
+            assert (np.ascontiguousarray(got, np.float32).view(np.uint32) == want.view(np.uint32)).all()
     if (ok & ~same_path).any():
         # an accept / reject comparison within rounding of a tie: iteration counts differ, the poses still agree
         print(f"[fuzz {i}] {int((ok & ~same_path).sum())} pair(s) took another accept/reject path; pose diff {err[ok & ~same_path]}")

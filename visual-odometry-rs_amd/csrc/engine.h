@@ -94,6 +94,7 @@ struct RefDensePlanes {
 // state instead and queues its pair; a second launch gives each queued pair a whole workgroup (the same chains, bit for bit).
 struct RefResume {  // the state of optimizer::State::iterative_solve between two evaluations (lm_reference.hip RefLm) + the level
     float cur_model[7], cand[7];
+    float entry[7];  // the model the level started from: lm_model stays it if the level fails (inverse_compositional.rs:195-199)
     float kept[28];
     float cur_energy, lm_coef;
     int nb_iter, n_full, lvl;

@@ -759,12 +759,13 @@ __device__ __forceinline__ int ref_lm_advance(RefLm& s, float acc, int cnt, cons
 
 // One level by one wavefront. G2: two points per lane (refw_eval2; FAST: the level's focal lengths are verified fast divisors).
 // The LM state between two evaluations <-> memory (engine.h RefResume): the hand-over of a straggler pair to a workgroup.
-__device__ __forceinline__ void ref_lm_save(const RefLm& s, int lvl, RefResume* r) {
+__device__ __forceinline__ void ref_lm_save(const RefLm& s, const Iso& entry, int lvl, RefResume* r) {
     const int lane = threadIdx.x & 63;
     if (lane < RW_NSUM) r->kept[lane] = s.kept;
     if (lane == 0) {
         iso_store(s.cur_model, r->cur_model);
         iso_store(s.cand, r->cand);
+        iso_store(entry, r->entry);
         r->cur_energy = s.cur_energy;
         r->lm_coef = s.lm_coef;
         r->nb_iter = s.nb_iter;
@@ -805,7 +806,7 @@ __device__ int refw_solve_level(const Src& src, int n, const RefImg& c, Iso* mod
         else acc = refw_eval<HUBER>(src, n, c, s.cand, lds, &cnt);
         cmd = ref_lm_advance(s, acc, cnt);
         if (ho_after > 0 && cmd == REF_LM_EVAL && __builtin_amdgcn_readfirstlane(finished) >= ho_after) {
-            ref_lm_save(s, lvl, ho.state + pair);
+            ref_lm_save(s, *model, lvl, ho.state + pair);  // (*model: the level's entry, written only when the level is done)
             if (lane == 0) ho.list[atomicAdd(&ho.counters[0], 1)] = pair;
             return 2;
         }
@@ -1149,8 +1150,10 @@ __global__ __launch_bounds__(512) void lm_ref_track_coop_kernel(Geom g, const ui
         const RefImg c = ref_level_img<SRC>(g, cur0, curu, rec, pair, lvl);
         RefLm s;
         ref_lm_begin(s, lm_model);
+        Iso entry = lm_model;  // lm_model if the level fails: Tracker::track breaks out before `lm_model = ...` (inverse_compositional.rs:195-199)
         if (resume && lvl == first_lvl) {  // pick the level up where the one-wavefront launch left it: `cand` is the next model to evaluate
             ref_lm_restore(s, saved);
+            entry = ref_iso_uniform(iso_load(saved->entry));
             lm_model = s.cand;
         }
         int cmd = REF_LM_EVAL;
@@ -1173,10 +1176,11 @@ __global__ __launch_bounds__(512) void lm_ref_track_coop_kernel(Geom g, const ui
                 cmd = __builtin_amdgcn_readfirstlane(sh.cmd);
                 eval_model = ref_iso_uniform(iso_load(sh.model));
             } while (cmd == REF_LM_EVAL);
-            lm_model = eval_model;  // REF_LM_DONE: the level's result; REF_LM_FAIL: the last kept model (not used any further)
+            lm_model = eval_model;  // REF_LM_DONE: the level's result (REF_LM_FAIL: the last kept model, replaced below)
         });
         const bool ok = cmd == REF_LM_DONE;
-        if (wave == 0) lm_model = ok ? s.cur_model : lm_model;
+        if (!ok) lm_model = entry;  // the level's progress is discarded: the keyframe test warps with the model the level started from
+        else if (wave == 0) lm_model = s.cur_model;
         if (out_stats && threadIdx.x == 0) {
             out_stats[pair].nb_iter[lvl] = ok ? s.nb_iter : 0;
             out_stats[pair].nb_grad_evals[lvl] = ok ? s.n_full : 0;
