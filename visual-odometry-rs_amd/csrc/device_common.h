@@ -1,4 +1,4 @@
-// Device helpers shared by kernels.hip and lm_kernels.hip.
+// Device helpers shared by kernels.hip, lm_kernels.hip and lm_reference.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,56 @@ namespace vors {
 __device__ __forceinline__ int select_pair(const Geom& g, int k) {
     if (!g.sel_list) return k;
     return k < *g.sel_count ? g.sel_list[k] : -1;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Tracker::track bookkeeping shared by every kernel form (uniform control code; each is called by ONE lane, which the caller picks)
+// ------------------------------------------------------------------------------------------------------------
+// Start of track() (inverse_compositional.rs:177): the two poses (null = identity) and the model the coarsest level starts from.
+struct TrackEntry {
+    Iso prev_pose, kf_pose, lm_model;
+};
+__device__ __forceinline__ TrackEntry track_entry(const float* prev_poses7, const float* kf_poses7, int pair) {
+    TrackEntry e;
+    e.prev_pose = prev_poses7 ? iso_load(prev_poses7 + 7 * pair) : iso_identity();
+    e.kf_pose = kf_poses7 ? iso_load(kf_poses7 + 7 * pair) : iso_identity();
+    e.lm_model = iso_mul(iso_inverse(e.prev_pose), e.kf_pose);
+    return e;
+}
+// End of track() (inverse_compositional.rs:206-224): the pose, the status, and the keyframe decision from the mean optical flow.
+__device__ __forceinline__ void store_track_result(int pair, bool went_well, const Iso& lm_model, const Iso& prev_pose, const Iso& kf_pose,
+                                                   float optical_flow, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats) {
+    const Iso pose = went_well ? iso_mul(kf_pose, iso_inverse(lm_model)) : prev_pose;  // inverse_compositional.rs:206-208
+    iso_store(pose, out_poses7 + 7 * pair);
+    out_status[pair] = went_well ? VORS_TRACK_OK : VORS_TRACK_OPTIMIZER_FAILED_POSE_KEPT;
+    if (out_stats) {
+        iso_store(lm_model, out_stats[pair].lm_model);
+        out_stats[pair].optical_flow = optical_flow;
+        out_stats[pair].change_keyframe = (optical_flow >= 1.0f) ? 1 : 0;
+    }
+}
+// Statistics of one level; zero when the level failed (its progress is discarded: inverse_compositional.rs:195-199).
+__device__ __forceinline__ void store_level_stats(vors_pair_stats* out_stats, int pair, int lvl, bool ok, int nb_iter, int n_full, float energy) {
+    out_stats[pair].nb_iter[lvl] = ok ? nb_iter : 0;
+    out_stats[pair].nb_grad_evals[lvl] = ok ? n_full : 0;
+    out_stats[pair].energy[lvl] = ok ? energy : 0.f;
+}
+// After a failure: levels [0, lvl) are never run.
+__device__ __forceinline__ void zero_level_stats_below(vors_pair_stats* out_stats, int pair, int lvl) {
+    for (int l2 = lvl - 1; l2 >= 0; --l2) {
+        out_stats[pair].nb_iter[l2] = 0;
+        out_stats[pair].nb_grad_evals[l2] = 0;
+        out_stats[pair].energy[l2] = 0.f;
+    }
+}
+// Levels [L, VORS_MAX_LEVELS) do not exist for this geometry.
+__device__ __forceinline__ void zero_unused_level_stats(vors_pair_stats* out_stats, int pair, int L) {
+    for (int lvl = L; lvl < VORS_MAX_LEVELS; ++lvl) {
+        out_stats[pair].nb_iter[lvl] = 0;
+        out_stats[pair].nb_grad_evals[lvl] = 0;
+        out_stats[pair].n_points[lvl] = 0;
+        out_stats[pair].energy[lvl] = 0.f;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -199,6 +199,28 @@ VORS_HD bool lm_step(const float* h36, const float* g6, const Iso& model, float 
     return true;
 }
 
+// What one evaluated candidate means for the level: eval()'s accept test (lm_optimizer.rs:140-149) + stop_criterion
+// (lm_optimizer.rs:156-192), and stop_criterion's update of lm_coef. `energy`: the candidate's; `cur_energy`: the kept state's;
+// `nb_iter`: step() calls of the level so far, this candidate's included. The comparisons are written as the reference
+// writes them (a NaN energy is accepted and stops the level), and 0.1f * lm_coef keeps its operand order.
+enum LmVerdict { LM_REJECTED_GO_ON = 0, LM_REJECTED_STOP = 1, LM_ACCEPTED_GO_ON = 2, LM_ACCEPTED_STOP = 3 };
+VORS_HD bool lm_too_many_iterations(int nb_iter) { return nb_iter > 20; }
+VORS_HD LmVerdict lm_verdict(float energy, float cur_energy, int nb_iter, float& lm_coef) {
+    const bool too_many_iterations = lm_too_many_iterations(nb_iter);
+    if (energy > cur_energy) {  // Err(energy)
+        if (too_many_iterations) return LM_REJECTED_STOP;
+        lm_coef *= 10.0f;
+        return LM_REJECTED_GO_ON;
+    }
+    const float d_energy = cur_energy - energy;
+    if (too_many_iterations) return LM_ACCEPTED_STOP;
+    lm_coef = 0.1f * lm_coef;
+    if (!(d_energy > 1.0f)) return LM_ACCEPTED_STOP;
+    return LM_ACCEPTED_GO_ON;
+}
+VORS_HD bool lm_accepted(LmVerdict v) { return v >= LM_ACCEPTED_GO_ON; }
+VORS_HD bool lm_stops(LmVerdict v) { return (v & 1) != 0; }
+
 // Per-level pinhole intrinsics; reference: src/core/camera.rs:84-140.
 struct Intr {
     float cu, cv, fu, fv, skew;

@@ -1293,6 +1293,8 @@ __device__ __forceinline__ void solve_step_lane0(LmShared& s, int cur, const Iso
 // (lm_optimizer.rs:113-192). All control values are workgroup-uniform (read from LDS). Returns false when step() fails
 // (Cholesky); *model is then left untouched: the level's progress is discarded like the reference's `Err(err) => break`
 // (inverse_compositional.rs:195-199).
+// The two verdict blocks below are lm_verdict (lie.h) written out: calling it here moves the spills of the dense FUSED
+// instantiations of lm_track_kernel (VGPR spills 47 -> 49, scratch 128 -> 124 and the like), so this one site keeps its own text.
 template <int BLOCK, bool HUBER, class Src>
 __device__ bool solve_level(const Src& src, int n_slots, const ImgCtx& c, Iso* model, int* nb_iter_out, float* energy_out,
                             float* lm_coef_out, LmShared& s, const LmSplitState* resume = nullptr, int* n_full_out = nullptr, long long* ph = nullptr) {
@@ -1519,6 +1521,19 @@ __device__ __forceinline__ void with_level_source(const Geom& g, int lvl, int pa
     }
 }
 
+// The current image of a level and the level's constants (the FUSED exact_* choices are the caller's).
+__device__ __forceinline__ ImgCtx level_ctx(const Geom& g, const uint8_t* cur0, const uint8_t* curu, int pair, int lvl) {
+    ImgCtx c;
+    c.img = level_ptr(g, cur0, curu, pair, lvl);
+    c.rows = g.lv[lvl].rows;
+    c.cols = g.lv[lvl].cols;
+    c.k = g.lv[lvl].k;
+    c.huber = g.huber_delta;
+    c.inv_fu_d = g.lv[lvl].inv_fu_d; c.inv_fv_d = g.lv[lvl].inv_fv_d;
+    c.inv_fu = g.lv[lvl].inv_fu; c.inv_fv = g.lv[lvl].inv_fv; c.s_fuv = g.lv[lvl].s_fuv;
+    return c;
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // Tracker::track for a batch: one workgroup per frame pair, all levels, all LM iterations, keyframe test.
 // ------------------------------------------------------------------------------------------------------------
@@ -1551,9 +1566,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
         if ((int)blockIdx.x >= split.count[SPLIT_SIDE_COUNT]) return;
         pair = __builtin_amdgcn_readfirstlane(split.side_list[blockIdx.x]);
     }
-    const Iso prev_pose = prev_poses7 ? iso_load(prev_poses7 + 7 * pair) : iso_identity();
-    const Iso kf_pose = kf_poses7 ? iso_load(kf_poses7 + 7 * pair) : iso_identity();
-    Iso lm_model = iso_uniform(iso_mul(iso_inverse(prev_pose), kf_pose));  // inverse_compositional.rs:177
+    const TrackEntry track = track_entry(prev_poses7, kf_poses7, pair);
+    const Iso prev_pose = track.prev_pose, kf_pose = track.kf_pose;
+    Iso lm_model = iso_uniform(track.lm_model);
     bool went_well = true;
     int start_lvl = g.L - 1;
     const LmSplitState* resume = nullptr;
@@ -1570,14 +1585,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
         }
     }
     for (int lvl = start_lvl; lvl >= (mode == 1 ? split.n_split : (mode == 4 ? 1 : 0)); --lvl) {
-        ImgCtx c;
-        c.img = level_ptr(g, cur0, curu, pair, lvl);
-        c.rows = g.lv[lvl].rows;
-        c.cols = g.lv[lvl].cols;
-        c.k = g.lv[lvl].k;
-        c.huber = g.huber_delta;
-        c.inv_fu_d = g.lv[lvl].inv_fu_d; c.inv_fv_d = g.lv[lvl].inv_fv_d;
-        c.inv_fu = g.lv[lvl].inv_fu; c.inv_fv = g.lv[lvl].inv_fv; c.s_fuv = g.lv[lvl].s_fuv;
+        ImgCtx c = level_ctx(g, cur0, curu, pair, lvl);
         if constexpr (FUSED) {
             // Levels of FEW points run in the EXACT arithmetic (Geom::fused_exact_points): the energy of a few hundred points
             // carries the per-point rounding of the fused warp (~1 ulp of u, v) at 3-10x the reference's own summation noise, enough to
@@ -1614,9 +1622,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
 #endif
         });
         if (out_stats && threadIdx.x == 0) {
-            out_stats[pair].nb_iter[lvl] = ok ? nb_iter : 0;
-            out_stats[pair].nb_grad_evals[lvl] = ok ? n_full : 0;
-            out_stats[pair].energy[lvl] = ok ? energy : 0.f;
+            store_level_stats(out_stats, pair, lvl, ok, nb_iter, n_full, energy);
 #ifdef VORS_PROFILE_LEVELS
             out_stats[pair].energy[lvl] = (float)(wall_clock64() - t_level0) * 0.01f;  // 100 MHz ticks -> microseconds
 #ifdef VORS_PROFILE_CLOCK
@@ -1626,7 +1632,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
         }
         if (!ok) {
             went_well = false;
-            if (out_stats && threadIdx.x == 0)
+            if (out_stats && threadIdx.x == 0)  // (zero_level_stats_below written out: the call moves the spills of the dense instantiations)
                 for (int l2 = lvl - 1; l2 >= 0; --l2) {
                     out_stats[pair].nb_iter[l2] = 0;
                     out_stats[pair].nb_grad_evals[l2] = 0;
@@ -1715,17 +1721,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
         }
         block_sum2<BLOCK>(flow_sum, flow_n, s);
     }
-    if (threadIdx.x == 0) {
-        const float optical_flow = flow_sum / flow_n;
-        const Iso pose = went_well ? iso_mul(kf_pose, iso_inverse(lm_model)) : prev_pose;  // inverse_compositional.rs:206-208
-        iso_store(pose, out_poses7 + 7 * pair);
-        out_status[pair] = went_well ? VORS_TRACK_OK : VORS_TRACK_OPTIMIZER_FAILED_POSE_KEPT;
-        if (out_stats) {
-            iso_store(lm_model, out_stats[pair].lm_model);
-            out_stats[pair].optical_flow = optical_flow;
-            out_stats[pair].change_keyframe = (optical_flow >= 1.0f) ? 1 : 0;
-        }
-    }
+    if (threadIdx.x == 0) store_track_result(pair, went_well, lm_model, prev_pose, kf_pose, flow_sum / flow_n, out_poses7, out_status, out_stats);
     // usable candidates per level (diagnostics for the byte model)
     if (out_stats) {
         for (int lvl = 0; lvl < g.L; ++lvl) {
@@ -1761,13 +1757,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
             if (threadIdx.x == 0) out_stats[pair].n_points[lvl] = (int)n;
         }
 #ifndef VORS_PROFILE_PHASES
-        if (threadIdx.x == 0)
-            for (int lvl = g.L; lvl < VORS_MAX_LEVELS; ++lvl) {
-                out_stats[pair].nb_iter[lvl] = 0;
-                out_stats[pair].nb_grad_evals[lvl] = 0;
-                out_stats[pair].n_points[lvl] = 0;
-                out_stats[pair].energy[lvl] = 0.f;
-            }
+        if (threadIdx.x == 0) zero_unused_level_stats(out_stats, pair, g.L);
 #endif
 #ifdef VORS_PROFILE_LEVELS
         if (threadIdx.x == 0 && g.L <= VORS_MAX_LEVELS - 2) {
@@ -1784,17 +1774,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
 // order: thread -> wavefront -> workgroup -> chunks in index order), so results are deterministic.
 // ------------------------------------------------------------------------------------------------------------
 #define SPLIT_BLOCK 256
-__device__ __forceinline__ ImgCtx level_ctx(const Geom& g, const uint8_t* cur0, const uint8_t* curu, int pair, int lvl) {
-    ImgCtx c;
-    c.img = level_ptr(g, cur0, curu, pair, lvl);
-    c.rows = g.lv[lvl].rows;
-    c.cols = g.lv[lvl].cols;
-    c.k = g.lv[lvl].k;
-    c.huber = g.huber_delta;
-    c.inv_fu_d = g.lv[lvl].inv_fu_d; c.inv_fv_d = g.lv[lvl].inv_fv_d;
-    c.inv_fu = g.lv[lvl].inv_fu; c.inv_fv = g.lv[lvl].inv_fv; c.s_fuv = g.lv[lvl].s_fuv;
-    return c;
-}
 #ifndef VORS_SPLIT_WAVES
 #define VORS_SPLIT_WAVES 5
 #endif
@@ -1918,32 +1897,19 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
             } else if (phase == 4) {  // g, H of the candidate accepted one round ago (now the kept model): on to its step()
                 take = true;
             } else {
-                const bool too_many_iterations = nb_iter > 20;  // stop_criterion: lm_optimizer.rs:156-192
-                if (energy > cur_energy) {                      // Err(energy)
-                    if (too_many_iterations) done = true;
-                    else lm_coef *= 10.0f;
-                } else {
-                    const float d_energy = cur_energy - energy;
+                const LmVerdict v = lm_verdict(energy, cur_energy, nb_iter, lm_coef);  // eval()'s verdict + stop_criterion (lie.h)
+                if (lm_accepted(v)) {
                     n_full += 1;  // accepted: the reference forms its g and H (lm_optimizer.rs:147)
                     cur_energy = energy;
                     cur_model = iso_load(st->cand);
-                    if (too_many_iterations) {
-                        done = true;
-                    } else {
-                        lm_coef = 0.1f * lm_coef;
-                        if (!(d_energy > 1.0f)) done = true;
-                        else if (have_full) take = true;  // the level goes on from this candidate, its g and H are at hand
-                        else need_gh = true;              // ... or are the business of the next round
-                    }
                 }
+                if (lm_stops(v)) done = true;
+                else if (lm_accepted(v) && have_full) take = true;  // the level goes on from this candidate, its g and H are at hand
+                else if (lm_accepted(v)) need_gh = true;            // ... or are the business of the next round
             }
             bool again = false;
             if (done) {  // level finished
-                if (out_stats) {
-                    out_stats[pair].nb_iter[lvl] = nb_iter;
-                    out_stats[pair].nb_grad_evals[lvl] = n_full;
-                    out_stats[pair].energy[lvl] = cur_energy;
-                }
+                if (out_stats) store_level_stats(out_stats, pair, lvl, true, nb_iter, n_full, cur_energy);
                 iso_store(cur_model, st->model);
                 if (lvl > 0) {
                     iso_store(cur_model, st->entry);
@@ -1988,12 +1954,7 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
                     for (int q = 0; q < 7; ++q) st->model[q] = st->entry[q];
                     st->went_well = 0;
                     st->phase = 2;
-                    if (out_stats)
-                        for (int l2 = lvl; l2 >= 0; --l2) {
-                            out_stats[pair].nb_iter[l2] = 0;
-                            out_stats[pair].nb_grad_evals[l2] = 0;
-                            out_stats[pair].energy[l2] = 0.f;
-                        }
+                    if (out_stats) zero_level_stats_below(out_stats, pair, lvl + 1);  // this level and every finer one
                 }
             }
             st->nb_iter = nb_iter;

@@ -709,7 +709,7 @@ struct RefLmAhead {
     bool ok, valid;
 };
 __device__ __forceinline__ bool ref_lm_ahead_valid(const RefLm& s) {
-    return s.started && !(s.nb_iter > 20);  // (a rejected evaluation with too many iterations stops the level instead)
+    return s.started && !lm_too_many_iterations(s.nb_iter);  // (a rejected evaluation with too many iterations stops the level instead)
 }
 __device__ __forceinline__ RefLmAhead ref_lm_step_ahead(const RefLm& s) {
     RefLmAhead a;
@@ -726,25 +726,19 @@ __device__ __forceinline__ int ref_lm_advance(RefLm& s, float acc, int cnt, cons
         s.kept = acc;
         s.cur_energy = energy;
         s.n_full = 1;
-    } else {  // eval() + stop_criterion: lm_optimizer.rs:140-192
-        const bool too_many_iterations = s.nb_iter > 20;
-        if (energy > s.cur_energy) {  // Err(energy)
-            if (too_many_iterations) return REF_LM_DONE;
-            s.lm_coef *= 10.0f;
-            if (ahead && ahead->valid) {  // step() of exactly this state was computed while the evaluation ran
-                s.nb_iter += 1;
-                s.cand = ahead->cand;
-                return ahead->ok ? REF_LM_EVAL : REF_LM_FAIL;
-            }
-        } else {
-            const float d_energy = s.cur_energy - energy;
+    } else {
+        const LmVerdict v = lm_verdict(energy, s.cur_energy, s.nb_iter, s.lm_coef);  // eval() + stop_criterion (lie.h)
+        if (lm_accepted(v)) {
             s.n_full += 1;
             s.kept = acc;
             s.cur_energy = energy;
             s.cur_model = s.cand;
-            if (too_many_iterations) return REF_LM_DONE;
-            s.lm_coef = 0.1f * s.lm_coef;
-            if (!(d_energy > 1.0f)) return REF_LM_DONE;
+        }
+        if (lm_stops(v)) return REF_LM_DONE;
+        if (!lm_accepted(v) && ahead && ahead->valid) {  // step() of exactly this state was computed while the evaluation ran
+            s.nb_iter += 1;
+            s.cand = ahead->cand;
+            return ahead->ok ? REF_LM_EVAL : REF_LM_FAIL;
         }
     }
     s.nb_iter += 1;
@@ -757,7 +751,6 @@ __device__ __forceinline__ int ref_lm_advance(RefLm& s, float acc, int cnt, cons
     return ok ? REF_LM_EVAL : REF_LM_FAIL;
 }
 
-// One level by one wavefront. G2: two points per lane (refw_eval2; FAST: the level's focal lengths are verified fast divisors).
 // The LM state between two evaluations <-> memory (engine.h RefResume): the hand-over of a straggler pair to a workgroup.
 __device__ __forceinline__ void ref_lm_save(const RefLm& s, const Iso& entry, int lvl, RefResume* r) {
     const int lane = threadIdx.x & 63;
@@ -897,17 +890,7 @@ __device__ __forceinline__ void ref_finish_pair(const Geom& g, int pair, const u
             }
         });
     }
-    if (lane == 0) {
-        const float optical_flow = flow_sum / (float)flow_n;
-        const Iso pose = went_well ? iso_mul(kf_pose, iso_inverse(lm_model)) : prev_pose;  // inverse_compositional.rs:206-208
-        iso_store(pose, out_poses7 + 7 * pair);
-        out_status[pair] = went_well ? VORS_TRACK_OK : VORS_TRACK_OPTIMIZER_FAILED_POSE_KEPT;
-        if (out_stats) {
-            iso_store(lm_model, out_stats[pair].lm_model);
-            out_stats[pair].optical_flow = optical_flow;
-            out_stats[pair].change_keyframe = (optical_flow >= 1.0f) ? 1 : 0;
-        }
-    }
+    if (lane == 0) store_track_result(pair, went_well, lm_model, prev_pose, kf_pose, flow_sum / (float)flow_n, out_poses7, out_status, out_stats);
     if (out_stats) {  // usable candidates per level (diagnostics)
         for (int lvl = 0; lvl < g.L; ++lvl) {
             if constexpr (SRC == REF_SRC_DENSE_T) {
@@ -930,13 +913,7 @@ __device__ __forceinline__ void ref_finish_pair(const Geom& g, int pair, const u
                 if (lane == 0) out_stats[pair].n_points[lvl] = rec.n_used[(size_t)pair * VORS_MAX_LEVELS + lvl];
             }
         }
-        if (lane == 0)
-            for (int lvl = g.L; lvl < VORS_MAX_LEVELS; ++lvl) {
-                out_stats[pair].nb_iter[lvl] = 0;
-                out_stats[pair].nb_grad_evals[lvl] = 0;
-                out_stats[pair].n_points[lvl] = 0;
-                out_stats[pair].energy[lvl] = 0.f;
-            }
+        if (lane == 0) zero_unused_level_stats(out_stats, pair, g.L);
     }
 }
 
@@ -956,9 +933,8 @@ __global__ __launch_bounds__(64 * RW_WPB, 4) void lm_ref_track_kernel(Geom g, co
     float* lds = lds_all + wave * RW_WORDS;
     REFW_INIT();
     REFW_T0(t_kernel);
-    const Iso prev_pose = prev_poses7 ? iso_load(prev_poses7 + 7 * pair) : iso_identity();
-    const Iso kf_pose = kf_poses7 ? iso_load(kf_poses7 + 7 * pair) : iso_identity();
-    Iso lm_model = ref_iso_uniform(iso_mul(iso_inverse(prev_pose), kf_pose));  // inverse_compositional.rs:177
+    const TrackEntry track = track_entry(prev_poses7, kf_poses7, pair);
+    Iso lm_model = ref_iso_uniform(track.lm_model);
     bool went_well = true;
     for (int lvl = g.L - 1; lvl >= 0; --lvl) {
         const RefImg c = ref_level_img<SRC>(g, cur0, curu, rec, pair, lvl);
@@ -972,14 +948,10 @@ __global__ __launch_bounds__(64 * RW_WPB, 4) void lm_ref_track_kernel(Geom g, co
         });
         if (how == 2) return;  // handed over: the workgroup kernel finishes this pair (levels done so far have their statistics already)
         const bool ok = how == 1;
-        if (out_stats && lane == 0) {
-            out_stats[pair].nb_iter[lvl] = ok ? nb_iter : 0;
-            out_stats[pair].nb_grad_evals[lvl] = ok ? n_full : 0;
-            out_stats[pair].energy[lvl] = ok ? energy : 0.f;
-        }
+        if (out_stats && lane == 0) store_level_stats(out_stats, pair, lvl, ok, nb_iter, n_full, energy);
         if (!ok) {
             went_well = false;
-            if (out_stats && lane == 0)
+            if (out_stats && lane == 0)  // (zero_level_stats_below written out: the call costs this kernel a VGPR)
                 for (int l2 = lvl - 1; l2 >= 0; --l2) {
                     out_stats[pair].nb_iter[l2] = 0;
                     out_stats[pair].nb_grad_evals[l2] = 0;
@@ -995,7 +967,7 @@ __global__ __launch_bounds__(64 * RW_WPB, 4) void lm_ref_track_kernel(Geom g, co
 #endif
     REFW_FLUSH();
     if (ho_after > 0 && lane == 0) atomicAdd(&rec.handoff.counters[1], 1);  // one pair fewer to wait for (before the epilogue: the stragglers may go now)
-    ref_finish_pair<SRC>(g, pair, kf0, kfu, kf_depth, rec, lm_model, went_well, prev_pose, kf_pose, lds, out_poses7, out_status, out_stats);
+    ref_finish_pair<SRC>(g, pair, kf0, kfu, kf_depth, rec, lm_model, went_well, track.prev_pose, track.kf_pose, lds, out_poses7, out_status, out_stats);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1141,9 +1113,8 @@ __global__ __launch_bounds__(512) void lm_ref_track_coop_kernel(Geom g, const ui
     }
     __syncthreads();
     unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const Iso prev_pose = prev_poses7 ? iso_load(prev_poses7 + 7 * pair) : iso_identity();
-    const Iso kf_pose = kf_poses7 ? iso_load(kf_poses7 + 7 * pair) : iso_identity();
-    Iso lm_model = ref_iso_uniform(iso_mul(iso_inverse(prev_pose), kf_pose));  // inverse_compositional.rs:177 (every wavefront alike)
+    const TrackEntry track = track_entry(prev_poses7, kf_poses7, pair);  // (every wavefront alike)
+    Iso lm_model = ref_iso_uniform(track.lm_model);
     bool went_well = true;
     int parity = 0;
     for (int lvl = first_lvl; lvl >= 0; --lvl) {
@@ -1181,14 +1152,10 @@ __global__ __launch_bounds__(512) void lm_ref_track_coop_kernel(Geom g, const ui
         const bool ok = cmd == REF_LM_DONE;
         if (!ok) lm_model = entry;  // the level's progress is discarded: the keyframe test warps with the model the level started from
         else if (wave == 0) lm_model = s.cur_model;
-        if (out_stats && threadIdx.x == 0) {
-            out_stats[pair].nb_iter[lvl] = ok ? s.nb_iter : 0;
-            out_stats[pair].nb_grad_evals[lvl] = ok ? s.n_full : 0;
-            out_stats[pair].energy[lvl] = ok ? s.cur_energy : 0.f;
-        }
+        if (out_stats && threadIdx.x == 0) store_level_stats(out_stats, pair, lvl, ok, s.nb_iter, s.n_full, s.cur_energy);
         if (!ok) {
             went_well = false;
-            if (out_stats && threadIdx.x == 0)
+            if (out_stats && threadIdx.x == 0)  // (written out like lm_ref_track_kernel's: the call changes the register count)
                 for (int l2 = lvl - 1; l2 >= 0; --l2) {
                     out_stats[pair].nb_iter[l2] = 0;
                     out_stats[pair].nb_grad_evals[l2] = 0;
@@ -1208,7 +1175,7 @@ __global__ __launch_bounds__(512) void lm_ref_track_coop_kernel(Geom g, const ui
 #endif
     (void)prof;
     if (wave != 0) return;  // (no barrier below)
-    ref_finish_pair<SRC>(g, pair, kf0, kfu, kf_depth, rec, lm_model, went_well, prev_pose, kf_pose, slots, out_poses7, out_status, out_stats);
+    ref_finish_pair<SRC>(g, pair, kf0, kfu, kf_depth, rec, lm_model, went_well, track.prev_pose, track.kf_pose, slots, out_poses7, out_status, out_stats);
 }
 
 // Wavefronts per workgroup of the one-wavefront-per-pair kernel: four pairs to a workgroup (one wavefront per SIMD: single-wavefront
