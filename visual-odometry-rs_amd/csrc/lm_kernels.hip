@@ -627,17 +627,21 @@ struct FUnit {
 //  * not latency: a software-pipelined loop (stage B of unit k+1 and the raw words of unit k+2 requested before stage C of unit k waits
 //    for its taps, two units per basic block) left the energy-only round at 1760-1800 us (1759 as is) and the full round at 3303 (3339);
 //  * the tap gathers, in the energy-only round: every tap load issued twice -> +66 % (full round +24 %), 16 extra FMAs per point -> +1 %
-//    (full +5 %). A 16-bit (or 8-bit, or unaligned 32-bit) gather costs the CU ~19 cycles per wavefront instruction however well the
-//    lanes' addresses line up, an aligned dword 12.7, 8 unaligned bytes 33;
+//    (full +5 %). A 16-bit (or 8-bit, or unaligned 32-bit) gather cost the CU ~19 cycles per wavefront instruction in that probe, an aligned
+//    dword 12.7, 8 unaligned bytes 33; what a gather costs does depend on the address pattern, though: on a warped quad row a 16-bit gather
+//    takes 7.9 cycles, an unaligned 32-bit one 15.3, a 64-bit one 28.4 (round 7, tools/ubench/quad_tap_gathers.hip);
 //  * and VALU issue right behind: the current-image band of a workgroup staged in LDS (sampled bounding rows, 16-byte copies, taps as
 //    ds_read2_b32 + v_alignbyte; every tap served from LDS in the bench) was SLOWER — 1927 / 3359 us: +60 VALU instructions per quad for
 //    the LDS addressing, 4 instead of 8 workgroups per CU, and two barriers plus two memory latencies before a 19-iteration sweep.
 // So the loop stays as simple as it is.
 template <int G>
 struct FusedStage {
+    // a quad's tap words may come out of 32-bit loads shared by two pixels (energy-only evaluations, fused_stage_b): bytes 0, 1 are the
+    // taps, whatever the upper bytes hold
+    using TapWord = typename std::conditional<G == 4, uint32_t, uint16_t>::type;
     float fa[G], fb[G];  // fractional parts of (u, v)
     bool inside[G];      // candidate && inside the strict window of lm_optimizer.rs:227-231
-    uint16_t top[G], bot[G];  // tap words (t00 | t01 << 8), (t10 | t11 << 8), as loaded: 16 bits (widened where they are consumed)
+    TapWord top[G], bot[G];  // tap words (t00 | t01 << 8), (t10 | t11 << 8) in bytes 0, 1, as loaded (only those bytes are ever converted)
     uint32_t tmw;
     float a[G], b[G], iz[G], gu[G], gv[G];
 };
@@ -729,11 +733,57 @@ __device__ __forceinline__ void fused_stage_b(const FUnit<G>& p, const ImgCtx& c
         st.inside[g] = p.valid[g] && ((unsigned)iu[g] < wlim) && ((unsigned)iv[g] < hlim);
 #pragma unroll
     for (int g = 0; g < G; ++g) off[g] = (iv[g] * c.cols + iu[g]) & (st.inside[g] ? -1 : 0);
+    if constexpr (G == 4 && !XW && ENERGY_ONLY) {
+        // A quad's pixels land on neighbouring bytes of ONE row of the current image for nearly every model the tracker meets (h00 ~ 1,
+        // h10 ~ 0), so the pixels (0, 1) and (2, 3) share their tap loads: one unaligned 32-bit gather per row at the first pixel's
+        // position holds the taps of the second one too whenever both are inside, on the same row, and 0 <= iu' - iu <= 2 — the second
+        // pixel's tap word is the first one's shifted down by iu' - iu bytes. Same bytes, same floats; half the gathers.
+        // The 4-byte reads stay inside the level: an inside pixel has iu <= cols - 3 and iv <= rows - 3, so bytes iu .. iu + 3 of the tap
+        // rows iv, iv + 1 <= rows - 2 end at most on the FIRST byte of the next row <= rows - 1, which exists; an outside first pixel reads
+        // offset 0 (bytes 0 .. 3 of row 0 and of row 1; a quad level has cols >= 4, and a level of ONE row — nothing inside — reads row 0 twice).
+        // A second pixel that is inside but cannot share (row crossing, first pixel outside, extreme scale) takes its own two 16-bit
+        // gathers under a wavefront-level branch: a gather costs the same with few lanes active, so the branch must be skipped to pay.
+        // Energy-only evaluations alone: their round is bound by the gathers (-11 % per launch); the full evaluation is bound by VALU issue,
+        // and the predicates, shifts and branches made it 2 % SLOWER (profiles/r07_experiments/README.md): it keeps one gather per point.
+        uint32_t wt[2], wb[2];
+        unsigned sh[2];
+        bool own[2];
+        const unsigned below = c.rows > 1 ? (unsigned)c.cols : 0u;  // (uniform)
 #pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const Taps t = load_taps_at(c, off[g]);
-        st.top[g] = t.top;
-        st.bot[g] = t.bot;
+        for (int h = 0; h < 2; ++h) {
+            const unsigned o = (unsigned)off[2 * h];
+            __builtin_memcpy(&wt[h], c.img + o, 4);
+            __builtin_memcpy(&wb[h], c.img + (o + below), 4);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned d = (unsigned)iu[2 * h + 1] - (unsigned)iu[2 * h];  // (saturated coordinates: wraps, no overflow)
+            const bool share = st.inside[2 * h] && iv[2 * h + 1] == iv[2 * h] && d <= 2u;
+            own[h] = st.inside[2 * h + 1] && !share;  // (an outside second pixel contributes nothing: whatever word it gets)
+            sh[h] = (8u * d) & 31u;
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint32_t t1 = wt[h] >> sh[h], b1 = wb[h] >> sh[h];
+            if (__any(own[h])) {
+                if (own[h]) {
+                    const Taps t = load_taps_at(c, off[2 * h + 1]);
+                    t1 = t.top;
+                    b1 = t.bot;
+                }
+            }
+            st.top[2 * h] = wt[h];
+            st.bot[2 * h] = wb[h];
+            st.top[2 * h + 1] = t1;
+            st.bot[2 * h + 1] = b1;
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const Taps t = load_taps_at(c, off[g]);
+            st.top[g] = t.top;
+            st.bot[g] = t.bot;
+        }
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) st.fa[g] = __builtin_amdgcn_fractf(u[g]);
@@ -754,7 +804,7 @@ __device__ __forceinline__ void fused_stage_b(const FUnit<G>& p, const ImgCtx& c
 // Stage C: lerp-form bilinear interpolation, residual, Jacobian, the 29 sums (`cnt` = the lane's integer count of inside points).
 template <bool HUBER, bool ENERGY_ONLY, int G>
 __device__ __forceinline__ void fused_stage_c(const ImgCtx& c, const JacK& k, const FusedStage<G>& st, float acc[NACC], int& cnt) {
-    uint16_t top[G], bot[G];
+    typename FusedStage<G>::TapWord top[G], bot[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         top[g] = st.top[g];
