@@ -1,7 +1,10 @@
-// Internal interface between the HIP kernels (kernels_*.hip) and the host engine / C ABI (capi.cpp).
+// Internal interface between the HIP kernels and their launch functions (kernels.hip, lm_kernels.hip, lm_reference.hip, dso_kernels.hip)
+// and the host engine / C ABI (host_common.h; batch.cpp, trackers.cpp, pipeline.cpp, operators.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "../../include/vors_hip.h"
 #include "lie.h"
@@ -228,14 +231,59 @@ void launch_keyframe_dso(const Geom& g, Pyramid kf, const uint16_t* depth, DsoWs
 void launch_slim_materialize(const Geom& g, int l, int pair, Records rec, int n, Records out, hipStream_t s);
 void launch_dense_materialize(const Geom& g, int l, int pair, Pyramid kf, const uint16_t* depth, Records rec, Records out,
                               hipStream_t s);
-// `kf` and `kf_depth` are read only in dense mode (points are recomputed from the keyframe image + depth on the fly).
-void launch_lm_track(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7, const float* kf_poses7,
-                     float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs, int block, LmSplitWs split, hipStream_t s);
+// What every LM kernel reads: the two pyramids and the keyframe's records. `kf` and `kf_depth` are read only in dense mode (points are
+// recomputed from the keyframe image + depth on the fly).
+struct LmScene {
+    Pyramid cur, kf;
+    const uint16_t* kf_depth;
+    Records rec;
+};
+// One track launch (host side only: the kernels keep their flat argument lists, launch_track below unpacks the record).
+struct TrackCall : LmScene {
+    const float *prev_poses7, *kf_poses7;
+    float* out_poses7;
+    int32_t* out_status;
+    vors_pair_stats* out_stats;
+    int n_pairs;
+};
+// One evaluation of one level of one pair of a prepared batch at an explicit model -> 29 sums.
+struct EvalCall : LmScene {
+    int pair, lvl;
+    const float* model7;
+    float* out29;
+};
+// THE place where the records become kernel arguments: K(g, scene..., extra...), K(g, scene..., poses and outputs..., extra...).
+template <class K, class... Extra>
+void launch_on_scene(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Geom& g, const LmScene& c, Extra... extra) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, g, c.cur.level0, c.cur.upper, c.kf.level0, c.kf.upper, c.kf_depth, c.rec, extra...);
+}
+template <class K, class... Extra>
+void launch_track(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Geom& g, const TrackCall& c, Extra... extra) {
+    launch_on_scene(kernel, grid, block, lds, s, g, c, c.prev_poses7, c.kf_poses7, c.out_poses7, c.out_status, c.out_stats, extra...);
+}
+template <class K>
+void launch_eval(K kernel, dim3 block, hipStream_t s, const Geom& g, const EvalCall& c) {
+    launch_on_scene(kernel, dim3(1), block, 0, s, g, c, c.pair, c.lvl, c.model7, c.out29);
+}
+// Run-time value -> template argument: f receives a std::integral_constant, `decltype(x)::value` is the compile-time constant.
+//   with_bool(huber, [&](auto h) { launch(kernel<decltype(h)::value>); });
+template <class F>
+void with_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+// ... the first of the candidates (descending) that v reaches, the last one otherwise
+template <int First, int... Rest, class F>
+void with_largest_reached(int v, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, First>{});
+    else if (v >= First) f(std::integral_constant<int, First>{});
+    else with_largest_reached<Rest...>(v, f);
+}
+
+void launch_lm_track(const Geom& g, const TrackCall& call, int block, LmSplitWs split, hipStream_t s);
 // the two arithmetic modes of the above (lm_kernels.hip compiled with VORS_FUSED = 0 / 1)
-void launch_lm_track_exact(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7, const float* kf_poses7,
-                           float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs, int block, LmSplitWs split, hipStream_t s);
-void launch_lm_track_fused(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7, const float* kf_poses7,
-                           float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs, int block, LmSplitWs split, hipStream_t s);
+void launch_lm_track_exact(const Geom& g, const TrackCall& call, int block, LmSplitWs split, hipStream_t s);
+void launch_lm_track_fused(const Geom& g, const TrackCall& call, int block, LmSplitWs split, hipStream_t s);
 // REFERENCE arithmetic (lm_reference.hip): the candidate lists of n_pairs pairs into extract_z's column-major order (no-op in dense mode;
 // honours Geom::sel_list), and the tracker with the reference's sequential sums.
 void launch_sort_colmajor(const Geom& g, Records rec, int n_pairs, hipStream_t s);
@@ -244,19 +292,22 @@ bool ref_rank_from_regions(const Geom& g, const Records& rec);  // coarse-to-fin
 // of the current frame's pyramid -> rec.dense_t
 void launch_ref_dense_planes_keyframe(const Geom& g, Pyramid kf, const uint16_t* depth, Records rec, int n_pairs, hipStream_t s);
 void launch_ref_dense_planes_current(const Geom& g, Pyramid cur, Records rec, int n_pairs, hipStream_t s);
-void launch_lm_track_reference(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7,
-                               const float* kf_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs, hipStream_t s);
-void launch_lm_eval_level_reference(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, int pair, int lvl,
-                                    const float* model7, float* out29, hipStream_t s);
+// What the handle's device offers the workgroup-per-pair kernel: compute units and LDS per CU (MI355X: 256 CUs, 160 KB). Resolved once per
+// handle, on its device, when it is created (a process may hold handles on devices of different sizes); host side only.
+struct RefDevice {
+    int cus = 256;
+    size_t lds_per_cu = 64 * 1024;
+};
+RefDevice query_ref_device(int device);
+void launch_lm_track_reference(const Geom& g, const TrackCall& call, const RefDevice& dev, hipStream_t s);
+void launch_lm_eval_level_reference(const Geom& g, const EvalCall& call, hipStream_t s);
 void launch_lm_eval_obs_reference(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta, const float* model7,
                                   float* out_energy_n_g_h, float* residuals, hipStream_t s);
 void launch_lm_solve_obs_reference(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta, const float* model7,
                                    float* out, hipStream_t s);
 // One evaluation of one level of one pair of a prepared batch at an explicit model, per arithmetic mode -> 29 sums.
-void launch_lm_eval_level_exact(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, int pair, int lvl,
-                                const float* model7, float* out29, hipStream_t s);
-void launch_lm_eval_level_fused(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, int pair, int lvl,
-                                const float* model7, float* out29, hipStream_t s);
+void launch_lm_eval_level_exact(const Geom& g, const EvalCall& call, hipStream_t s);
+void launch_lm_eval_level_fused(const Geom& g, const EvalCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

@@ -1,0 +1,166 @@
+// What the host sources of libvors_hip.so share (batch.cpp, trackers.cpp, pipeline.cpp, operators.cpp): error plumbing, device and buffer
+// guards, and the batch handle every other handle is built on. None of them contains a kernel; no CPU compute path exists here: every
+// compute entry point needs a HIP device and fails loudly (VORS_ERR_NO_DEVICE) without one.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "engine.h"
+
+// ---------------------------------------------------------------------------------------------------------------
+// error plumbing
+// ---------------------------------------------------------------------------------------------------------------
+vors_status vors_set_last_error(vors_status st, const std::string& msg);  // operators.cpp (also used by multi.cpp)
+inline vors_status fail(vors_status st, const std::string& msg) { return vors_set_last_error(st, msg); }
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t _e = (expr);                                                                                \
+        if (_e != hipSuccess)                                                                                  \
+            return fail(VORS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                      \
+    } while (0)
+
+inline vors_status require_device() {
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        return fail(VORS_ERR_NO_DEVICE, "vors_hip: no HIP device available (this library has no CPU fallback)");
+    }
+    return VORS_OK;
+}
+
+// Entry points run on the handle's device whatever the caller's current device is, and restore the caller's on exit.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int device) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// Short-lived and per-tracker buffers.
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    template <class T>
+    T* as() { return static_cast<T*>(p); }
+};
+struct PinnedBuf {
+    void* p = nullptr;
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 16, hipHostMallocDefault); }
+    template <class T>
+    T* as() { return static_cast<T*>(p); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// device-resident batch engine
+// ---------------------------------------------------------------------------------------------------------------
+// Owner of what a batch handle creates on its device: one hipMalloc per buffer (the caller-visible pointers keep their own alignment,
+// `bytes` is what vors_batch_workspace_bytes reports), streams and events. The first error sticks and turns the later calls into no-ops,
+// so the creation code is straight-line statements followed by ONE check of `err`; the destructor releases whatever was created. A new
+// workspace buffer is one alloc() line and nothing else.
+struct DeviceResources {
+    std::vector<void*> buffers;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+    uint64_t bytes = 0;
+    hipError_t err = hipSuccess;
+    DeviceResources() = default;
+    DeviceResources(const DeviceResources&) = delete;
+    DeviceResources& operator=(const DeviceResources&) = delete;
+    ~DeviceResources() {
+        for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (void* p : buffers) (void)hipFree(p);
+    }
+    template <class T>
+    void alloc(T** p, size_t n) {
+        if (err != hipSuccess) return;
+        if ((err = hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T))) != hipSuccess) return;
+        buffers.push_back(*p);
+        bytes += n * sizeof(T);
+    }
+    void stream(hipStream_t* s, unsigned flags) {
+        if (err == hipSuccess && (err = hipStreamCreateWithFlags(s, flags)) == hipSuccess) streams.push_back(*s);
+    }
+    void event(hipEvent_t* e, unsigned flags) {
+        if (err == hipSuccess && (err = hipEventCreateWithFlags(e, flags)) == hipSuccess) events.push_back(*e);
+    }
+};
+
+// Per-stage HIP-event ring (stage: 0 keyframe pyramid, 1 keyframe precompute, 2 current pyramid, 3 LM kernel).
+// Events are only RECORDED on the caller's stream during a step (non-blocking); elapsed times are read afterwards.
+struct StageTimers {
+    int ring = 0;
+    std::vector<hipEvent_t> ev0[4], ev1[4];
+    long count[4] = {0, 0, 0, 0};
+    StageTimers() = default;
+    StageTimers(const StageTimers&) = delete;
+    StageTimers& operator=(const StageTimers&) = delete;
+    ~StageTimers() { clear(); }
+    void clear() {  // ring -> 0: no stage is timed
+        ring = 0;
+        for (int st = 0; st < 4; ++st) {
+            for (auto* ring_events : {&ev0[st], &ev1[st]}) {
+                for (hipEvent_t e : *ring_events)
+                    if (e) (void)hipEventDestroy(e);
+                ring_events->clear();
+            }
+            count[st] = 0;
+        }
+    }
+};
+#define STAGE_BEGIN(b, st, s) \
+    do {                      \
+        if ((b)->timers.ring > 0) HIP_TRY(hipEventRecord((b)->timers.ev0[st][(b)->timers.count[st] % (b)->timers.ring], s)); \
+    } while (0)
+#define STAGE_END(b, st, s)   \
+    do {                      \
+        if ((b)->timers.ring > 0) {  \
+            HIP_TRY(hipEventRecord((b)->timers.ev1[st][(b)->timers.count[st] % (b)->timers.ring], s)); \
+            (b)->timers.count[st] += 1; \
+        }                     \
+    } while (0)
+
+struct vors_batch {
+    vors_config cfg;
+    vors::Geom g;
+    int max_pairs = 0;
+    int device = 0;          // HIP device the workspaces live on (vors_batch_create_on); every entry point switches to it
+    int prepared_pairs = 0;  // n_pairs of the last prepare_keyframes: track_current may not ask for more
+    int current_pairs = 0;   // n_pairs of the last track_current: the current-frame pyramid slots that hold an image
+    uint8_t* kf_upper = nullptr;
+    uint8_t* cur_upper = nullptr;
+    const uint8_t* kf_level0 = nullptr;   // caller's buffer of the last prepare_keyframes
+    const uint8_t* cur_level0 = nullptr;  // caller's buffer of the last track_current
+    const uint16_t* kf_depth = nullptr;   // caller's depth buffer of the last prepare_keyframes (read by the dense LM kernel)
+    vors::Records rec{};
+    vors::LmSplitWs split{};
+    int lm_block = 256;  // threads per frame pair in the LM kernel (256 / 512 / 1024)
+    vors::RefDevice ref_device;  // REFERENCE arithmetic: what the device offers the workgroup-per-pair kernel
+    // generic-mask (DSO) mode workspaces
+    vors::DsoWs dso{};
+    vors::PixelPlanes pp{};
+    uint8_t* mask0 = nullptr;
+    StageTimers timers;
+    DeviceResources own;  // every device pointer, stream and event above that the handle created (destroy on the handle's device)
+};
+
+// The stream work is enqueued on must belong to the handle's device (a stream of another device would silently run nothing useful).
+vors_status check_stream(const vors_batch* b, hipStream_t s);
+// Tracker::track up to the keyframe test for the prepared keyframes of `b`, with the keyframe poses on the device (batch.cpp;
+// vors_batch_track_current is the kf_poses7 = NULL case)
+vors_status batch_track_current(vors_batch* b, int n_pairs, const uint8_t* d_cur_gray, const float* d_prev_poses7, const float* d_kf_poses7,
+                                float* d_out_poses7, int32_t* d_out_status, vors_pair_stats* d_out_stats, hipStream_t s);

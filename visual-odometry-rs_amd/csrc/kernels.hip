@@ -903,7 +903,7 @@ void launch_zero_ints(const Geom& g, int* base, int stride, int n_pairs, hipStre
     else hipLaunchKernelGGL(zero_ints_kernel, dim3(n_pairs), dim3(64), 0, s, g, base, stride);
 }
 
-// Region geometry of the coarse-to-fine keyframe kernel (read by capi.cpp when it sizes the handle): roots per wavefront, and
+// Region geometry of the coarse-to-fine keyframe kernel (read by batch.cpp when it sizes the handle): roots per wavefront, and
 // wavefront regions per pair.
 static int keyframe_roots_per_wave(const Geom& g) {
     static int kf_r = getenv("VORS_KF_R") ? atoi(getenv("VORS_KF_R")) : 4;  // roots per wavefront (tuning knob)
@@ -943,7 +943,7 @@ void launch_keyframe(const Geom& g, Pyramid kf, const uint16_t* depth, Records r
         for (int l = next; l < g.L; ++l)
             hipLaunchKernelGGL(dense_idepth_halve_kernel, dim3((g.lv[l].n_slots + 255) / 256, n_pairs), dim3(256), 0, s, g, l, rec);
     } else {
-        // the region geometry the handle was sized for (keyframe_region_geometry at create(), capi.cpp) is the single source of truth
+        // the region geometry the handle was sized for (keyframe_region_geometry at create(), batch.cpp) is the single source of truth
         const int r = rec.kf_r;
         dim3 grid(rec.n_regions / KF_WAVES, n_pairs);
         const size_t lds = (size_t)KF_WAVES * r * kf_nodes(g.L) * 16;
@@ -1111,7 +1111,7 @@ void launch_trackers_advance(int n_seq, int* frame_counter, const float* out_pos
     hipLaunchKernelGGL(trackers_advance_kernel, dim3(1), dim3(256), 0, s, n_seq, frame_counter, out_poses7, stats, cur_poses7, kf_poses7, kf_frame,
                        promo_list, promo_count);
 }
-// Results of sequence 0 of a lock-step handle as ONE packed record (pose7, status, keyframe index, vors_pair_stats; capi.cpp TrackerOut),
+// Results of sequence 0 of a lock-step handle as ONE packed record (pose7, status, keyframe index, vors_pair_stats; trackers.cpp TrackerOut),
 // stored by the device straight into the caller's pinned host memory: the single-sequence tracker reads its frame back without a copy call.
 __global__ __launch_bounds__(64) void tracker_pack_out_kernel(const float* __restrict__ pose7, const int32_t* __restrict__ status,
                                                               const int32_t* __restrict__ kf_frame, const vors_pair_stats* __restrict__ stats,

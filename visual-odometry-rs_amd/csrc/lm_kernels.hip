@@ -1587,6 +1587,14 @@ __device__ __forceinline__ ImgCtx level_ctx(const Geom& g, const uint8_t* cur0, 
 // ------------------------------------------------------------------------------------------------------------
 // Tracker::track for a batch: one workgroup per frame pair, all levels, all LM iterations, keyframe test.
 // ------------------------------------------------------------------------------------------------------------
+// What a launch of lm_track_kernel does (its `mode` argument). Everything but LM_WHOLE_TRACK belongs to the split path (dense).
+enum LmTrackMode : int {
+    LM_WHOLE_TRACK = 0,    // the whole track() of the pair: every level, pose, keyframe test, statistics
+    LM_COARSE_LEVELS = 1,  // levels L-1 .. split.n_split, then hands the model over to the evaluation rounds through split.state
+    LM_EPILOGUE = 2,       // takes the rounds' results back: pose + keyframe test + statistics (and finishes whatever LM_STRAGGLERS could not take)
+    LM_STRAGGLERS = 3,     // workgroup a finishes the a-th pair still iterating after the last round (a big workgroup each, all in parallel)
+    LM_SIDE_LANE = 4,      // workgroup k finishes the levels above 0 of the k-th pair on the side lane (engine.h LmSplitWs), back to the rounds
+};
 template <int BLOCK, bool HUBER, bool DENSE, bool FUSED>
 // Register budget: with 256-thread workgroups more resident workgroups per CU hide the latency-bound coarse levels of their
 // neighbours (measured at 4096 pairs: dense 5 waves/SIMD = 96 VGPRs +3.7 %, 6 spills; sparse 6 waves/SIMD +4 %).
@@ -1599,20 +1607,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
                                                           const float* __restrict__ prev_poses7, const float* __restrict__ kf_poses7,
                                                           float* __restrict__ out_poses7, int32_t* __restrict__ out_status,
                                                           vors_pair_stats* __restrict__ out_stats, int mode, LmSplitWs split) {
-    // mode 0: the whole track() of the pair. Split path (dense): mode 1 = levels L-1 .. split.n_split, hands the model over
-    // through split.state; mode 3 = workgroup a finishes the a-th pair still iterating after the last evaluation round (a big
-    // workgroup each, all of them in parallel); mode 2 = takes the results back: pose + keyframe test + statistics (and
-    // finishes whatever mode 3 could not take).
+    // mode: an LmTrackMode (an int here: the kernel's signature is part of its symbol)
     __shared__ LmShared s;
 #ifdef VORS_PROFILE_LEVELS
     const long long t_kernel0 = wall_clock64();
 #endif
     int pair = blockIdx.x;
-    if (mode == 3) {
+    if (mode == LM_STRAGGLERS) {
         if ((int)blockIdx.x >= split_n_active(split, split.rounds)) return;
         pair = __builtin_amdgcn_readfirstlane(split_active(split, split.rounds, blockIdx.x));
     }
-    if (mode == 4) {  // side lane (engine.h LmSplitWs): workgroup k finishes the levels above 0 of the k-th pair handed over by the step kernel
+    if (mode == LM_SIDE_LANE) {  // side lane (engine.h LmSplitWs): workgroup k finishes the levels above 0 of the k-th pair handed over by the step kernel
         if ((int)blockIdx.x >= split.count[SPLIT_SIDE_COUNT]) return;
         pair = __builtin_amdgcn_readfirstlane(split.side_list[blockIdx.x]);
     }
@@ -1622,7 +1627,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
     bool went_well = true;
     int start_lvl = g.L - 1;
     const LmSplitState* resume = nullptr;
-    if (mode >= 2) {  // the finest levels have been solved by the evaluation rounds — or are finished here (stragglers)
+    if (mode >= LM_EPILOGUE) {  // the finest levels have been solved by the evaluation rounds — or are finished here (stragglers)
         const LmSplitState* st = split.state + pair;
         went_well = st->went_well != 0;
         start_lvl = -1;
@@ -1634,7 +1639,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
             lm_model = iso_uniform(iso_load(st->model));
         }
     }
-    for (int lvl = start_lvl; lvl >= (mode == 1 ? split.n_split : (mode == 4 ? 1 : 0)); --lvl) {
+    for (int lvl = start_lvl; lvl >= (mode == LM_COARSE_LEVELS ? split.n_split : (mode == LM_SIDE_LANE ? 1 : 0)); --lvl) {
         ImgCtx c = level_ctx(g, cur0, curu, pair, lvl);
         if constexpr (FUSED) {
             // Levels of FEW points run in the EXACT arithmetic (Geom::fused_exact_points): the energy of a few hundred points
@@ -1691,7 +1696,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
             break;
         }
     }
-    if (mode == 4) {  // level 0 is the rounds' again: hand the pair over like mode 1 does
+    if (mode == LM_SIDE_LANE) {  // level 0 is the rounds' again: hand the pair over like LM_COARSE_LEVELS does
         if (threadIdx.x == 0) {
             LmSplitState* st = split.state + pair;
             iso_store(lm_model, st->model);
@@ -1710,7 +1715,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
         }
         return;
     }
-    if (mode == 3) {  // hand the finished pair back to the bookkeeping of mode 2
+    if (mode == LM_STRAGGLERS) {  // hand the finished pair back to the bookkeeping of LM_EPILOGUE
         if (threadIdx.x == 0) {
             LmSplitState* st = split.state + pair;
             iso_store(lm_model, st->model);
@@ -1719,7 +1724,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(VORS_LM_W
         }
         return;
     }
-    if (mode == 1) {
+    if (mode == LM_COARSE_LEVELS) {
         if (threadIdx.x == 0) {
             LmSplitState* st = split.state + pair;
             iso_store(lm_model, st->model);
@@ -2057,34 +2062,17 @@ void launch_lm_split_merge(LmSplitWs ws, int round, hipStream_t s);
 void launch_lm_split_step(const Geom& g, LmSplitWs ws, vors_pair_stats* out_stats, int round, int late, int next_late, int grid, hipStream_t s);
 #endif
 
-#define VORS_LM_KARGS g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats
-template <int BLOCK, bool DENSE>
-static void launch_lm_track_block(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7,
-                                  const float* kf_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats,
-                                  int n_pairs, int mode, LmSplitWs split, hipStream_t s) {
-    if (g.huber_delta > 0.f)
-        hipLaunchKernelGGL((lm_track_kernel<BLOCK, true, DENSE, kFused>), dim3(n_pairs), dim3(BLOCK), 0, s, VORS_LM_KARGS, mode, split);
-    else
-        hipLaunchKernelGGL((lm_track_kernel<BLOCK, false, DENSE, kFused>), dim3(n_pairs), dim3(BLOCK), 0, s, VORS_LM_KARGS, mode, split);
-}
-static void launch_lm_track_mode(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7,
-                                 const float* kf_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs,
-                                 int block, int mode, LmSplitWs split, hipStream_t s) {
-#define VORS_LM_ARGS g, cur, kf, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats, n_pairs, mode, split, s
-    if (g.mode == VORS_CANDIDATES_DENSE) {
-        if (block >= 1024) launch_lm_track_block<1024, true>(VORS_LM_ARGS);
-        else if (block >= 512) launch_lm_track_block<512, true>(VORS_LM_ARGS);
-        else if (block >= 256) launch_lm_track_block<256, true>(VORS_LM_ARGS);
-        else if (block >= 128) launch_lm_track_block<128, true>(VORS_LM_ARGS);
-        else launch_lm_track_block<64, true>(VORS_LM_ARGS);
-    } else {
-        if (block >= 1024) launch_lm_track_block<1024, false>(VORS_LM_ARGS);
-        else if (block >= 512) launch_lm_track_block<512, false>(VORS_LM_ARGS);
-        else if (block >= 256) launch_lm_track_block<256, false>(VORS_LM_ARGS);
-        else if (block >= 128) launch_lm_track_block<128, false>(VORS_LM_ARGS);
-        else launch_lm_track_block<64, false>(VORS_LM_ARGS);
-    }
-#undef VORS_LM_ARGS
+// `n_groups` workgroups of `block` threads (rounded down to 1024 / 512 / 256 / 128 / 64) of the per-pair kernel
+static void launch_lm_track_mode(const Geom& g, const TrackCall& call, int n_groups, int block, LmTrackMode mode, const LmSplitWs& split, hipStream_t s) {
+    with_bool(g.mode == VORS_CANDIDATES_DENSE, [&](auto dense) {
+        with_bool(g.huber_delta > 0.f, [&](auto huber) {
+            with_largest_reached<1024, 512, 256, 128, 64>(block, [&](auto b) {
+                constexpr int BLOCK = decltype(b)::value;
+                launch_track(lm_track_kernel<BLOCK, decltype(huber)::value, decltype(dense)::value, kFused>, dim3(n_groups), dim3(BLOCK), 0, s, g, call,
+                             (int)mode, split);
+            });
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -2112,17 +2100,18 @@ __global__ __launch_bounds__(256) void lm_eval_level_kernel(Geom g, const uint8_
 #else
 #define VORS_LAUNCH_LM_EVAL_LEVEL launch_lm_eval_level_exact
 #endif
-void VORS_LAUNCH_LM_EVAL_LEVEL(const Geom& g_in, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, int pair, int lvl,
-                               const float* model7, float* out29, hipStream_t s) {
+// the caller's buffers are 16-byte aligned: the dense quad source may use wide loads (Geom::wide_loads_ok)
+static int wide_loads_ok(const LmScene& c) {
+    return (((uintptr_t)c.kf.level0 | (uintptr_t)c.kf.upper | (uintptr_t)c.kf_depth | (uintptr_t)c.rec.IZ) % 16 == 0) ? 1 : 0;
+}
+void VORS_LAUNCH_LM_EVAL_LEVEL(const Geom& g_in, const EvalCall& call, hipStream_t s) {
     Geom g = g_in;
-    g.wide_loads_ok = (((uintptr_t)kf.level0 | (uintptr_t)kf.upper | (uintptr_t)kf_depth | (uintptr_t)rec.IZ) % 16 == 0) ? 1 : 0;
-#define VORS_EL_ARGS dim3(1), dim3(256), 0, s, g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, pair, lvl, model7, out29
-    const bool dense = g.mode == VORS_CANDIDATES_DENSE, huber = g.huber_delta > 0.f;
-    if (dense && huber) hipLaunchKernelGGL((lm_eval_level_kernel<true, true, kFused>), VORS_EL_ARGS);
-    else if (dense) hipLaunchKernelGGL((lm_eval_level_kernel<false, true, kFused>), VORS_EL_ARGS);
-    else if (huber) hipLaunchKernelGGL((lm_eval_level_kernel<true, false, kFused>), VORS_EL_ARGS);
-    else hipLaunchKernelGGL((lm_eval_level_kernel<false, false, kFused>), VORS_EL_ARGS);
-#undef VORS_EL_ARGS
+    g.wide_loads_ok = wide_loads_ok(call);
+    with_bool(g.mode == VORS_CANDIDATES_DENSE, [&](auto dense) {
+        with_bool(g.huber_delta > 0.f, [&](auto huber) {
+            launch_eval(lm_eval_level_kernel<decltype(huber)::value, decltype(dense)::value, kFused>, dim3(256), s, g, call);
+        });
+    });
 }
 
 #if VORS_FUSED
@@ -2130,14 +2119,12 @@ void VORS_LAUNCH_LM_EVAL_LEVEL(const Geom& g_in, Pyramid cur, Pyramid kf, const 
 #else
 #define VORS_LAUNCH_LM_TRACK launch_lm_track_exact
 #endif
-void VORS_LAUNCH_LM_TRACK(const Geom& g_in, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7,
-                          const float* kf_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs, int block,
-                          LmSplitWs split, hipStream_t s) {
+void VORS_LAUNCH_LM_TRACK(const Geom& g_in, const TrackCall& call, int block, LmSplitWs split, hipStream_t s) {
     Geom g = g_in;
-    g.wide_loads_ok = (((uintptr_t)kf.level0 | (uintptr_t)kf.upper | (uintptr_t)kf_depth | (uintptr_t)rec.IZ) % 16 == 0) ? 1 : 0;
-#define VORS_LM_MARGS g, cur, kf, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats, n_pairs, block
+    g.wide_loads_ok = wide_loads_ok(call);
+    const int n_pairs = call.n_pairs;
     if (g.mode != VORS_CANDIDATES_DENSE || split.chunks <= 0) {
-        launch_lm_track_mode(VORS_LM_MARGS, 0, split, s);
+        launch_lm_track_mode(g, call, n_pairs, block, LM_WHOLE_TRACK, split, s);
         return;
     }
     // coarse levels per pair, then the evaluation rounds on the finest levels, then the per-pair epilogue (which also finishes
@@ -2146,7 +2133,7 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, Pyramid cur, Pyramid kf, const uint1
     split.rounds = std::max(1, std::min(split.rounds, VORS_SPLIT_MAX_ROUNDS));
     (void)hipMemsetAsync(split.count, 0, SPLIT_COUNT_INTS * sizeof(int), s);
     const int join_round = split.side_round >= 0 ? std::min(split.side_round + 3, split.rounds) : -1;
-    launch_lm_track_mode(VORS_LM_MARGS, 1, split, s);
+    launch_lm_track_mode(g, call, n_pairs, block, LM_COARSE_LEVELS, split, s);
     const int base_chunks = std::max(1, split.chunks / 4);
     for (int r = 0; r < split.rounds; ++r) {
         // every pair needs at least two evaluations per level: full grids. Later rounds concern fewer and fewer pairs, finally a
@@ -2168,21 +2155,16 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, Pyramid cur, Pyramid kf, const uint1
         // that goes on) dominate the even rounds, candidates' energies the odd ones; the other kind gets a small grid.
         const int minor = std::max(std::min(full, 256), grid / 8);
         const int grid_full = late ? grid : ((r & 1) ? minor : grid), grid_energy = (r & 1) ? grid : minor;
-#define VORS_SPLIT_KARGS g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, split, r
-        if (g.huber_delta > 0.f) {
-            hipLaunchKernelGGL((lm_split_eval_kernel<true, false, kFused>), dim3(grid_full), dim3(SPLIT_BLOCK), 0, s, VORS_SPLIT_KARGS);
-            if (!late && r > 0) hipLaunchKernelGGL((lm_split_eval_kernel<true, true, kFused>), dim3(grid_energy), dim3(SPLIT_BLOCK), 0, s, VORS_SPLIT_KARGS);
-        } else {
-            hipLaunchKernelGGL((lm_split_eval_kernel<false, false, kFused>), dim3(grid_full), dim3(SPLIT_BLOCK), 0, s, VORS_SPLIT_KARGS);
-            if (!late && r > 0) hipLaunchKernelGGL((lm_split_eval_kernel<false, true, kFused>), dim3(grid_energy), dim3(SPLIT_BLOCK), 0, s, VORS_SPLIT_KARGS);
-        }
-#undef VORS_SPLIT_KARGS
-        launch_lm_split_step(g, split, out_stats, r, late, next_late, std::max(1, n_pairs / shrink), s);
+        with_bool(g.huber_delta > 0.f, [&](auto huber) {
+            constexpr bool HUBER = decltype(huber)::value;
+            launch_on_scene(lm_split_eval_kernel<HUBER, false, kFused>, dim3(grid_full), dim3(SPLIT_BLOCK), 0, s, g, call, split, r);
+            if (!late && r > 0) launch_on_scene(lm_split_eval_kernel<HUBER, true, kFused>, dim3(grid_energy), dim3(SPLIT_BLOCK), 0, s, g, call, split, r);
+        });
+        launch_lm_split_step(g, split, call.out_stats, r, late, next_late, std::max(1, n_pairs / shrink), s);
         if (r == split.side_round) {  // fork: the pairs still above level 0 finish those levels on the side stream, one workgroup each
             (void)hipEventRecord(split.ev_fork, s);
             (void)hipStreamWaitEvent(split.side_stream, split.ev_fork, 0);
-            launch_lm_track_mode(g, cur, kf, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats, n_pairs, 1024, 4, split,
-                                 split.side_stream);
+            launch_lm_track_mode(g, call, n_pairs, 1024, LM_SIDE_LANE, split, split.side_stream);
             (void)hipEventRecord(split.ev_join, split.side_stream);
         }
     }
@@ -2192,20 +2174,14 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, Pyramid cur, Pyramid kf, const uint1
     }
     // the pairs still iterating (a handful, each with a long serial tail) finish in parallel, one 1024-thread workgroup each (the grid grows with
     // the batch: a hard batch may leave more than 256 of them, and a workgroup beyond the active list returns at once)
-    launch_lm_track_mode(g, cur, kf, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats, std::min(n_pairs, std::max(256, n_pairs / 8)), 1024, 3,
-                         split, s);
-    launch_lm_track_mode(VORS_LM_MARGS, 2, split, s);
-#undef VORS_LM_MARGS
+    launch_lm_track_mode(g, call, std::min(n_pairs, std::max(256, n_pairs / 8)), 1024, LM_STRAGGLERS, split, s);
+    launch_lm_track_mode(g, call, n_pairs, block, LM_EPILOGUE, split, s);
 }
 
 #if !VORS_FUSED
-void launch_lm_track(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7,
-                     const float* kf_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs, int block,
-                     LmSplitWs split, hipStream_t s) {
-    if (g.arith == VORS_ARITH_FUSED)
-        launch_lm_track_fused(g, cur, kf, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats, n_pairs, block, split, s);
-    else
-        launch_lm_track_exact(g, cur, kf, kf_depth, rec, prev_poses7, kf_poses7, out_poses7, out_status, out_stats, n_pairs, block, split, s);
+void launch_lm_track(const Geom& g, const TrackCall& call, int block, LmSplitWs split, hipStream_t s) {
+    if (g.arith == VORS_ARITH_FUSED) launch_lm_track_fused(g, call, block, split, s);
+    else launch_lm_track_exact(g, call, block, split, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -1195,26 +1195,19 @@ static int refw_waves_per_block(int n_pairs) {
 // (per CU: 16 wavefronts, 160 KB of LDS at 2 (W - 1) blocks of 7.6 KB per workgroup — MI355X: 256 pairs with 8, 512 with 5, 768 with 4,
 // 1280 with 3); a batch that needs a second round of workgroups is slower than a thinner workgroup for everyone (tools/coop_sweep.py: 320
 // pairs 0.83 ms per step with 8 wavefronts, 0.65 with 5; 1024 pairs 1.52 with 5, 1.22 with 3). Beyond that: one wavefront per pair.
-// What the CURRENT device offers a workgroup kernel: compute units and LDS per CU (queried per call — cheap, cached by the runtime — because a
-// process may hold handles on devices of different sizes; MI355X: 256 CUs, 160 KB).
-struct RefcDevice {
-    int cus;
-    size_t lds_per_cu;
-};
-static RefcDevice refc_device() {
-    int dev = 0, cus = 0, lds = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || lds <= 0) lds = 64 * 1024;
-    int lds_cu = 0;  // (some runtimes report the 64 KB default per block and the real size per multiprocessor: a workgroup may take all of it)
-    if (hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && lds_cu > lds) lds = lds_cu;
-    (void)hipGetLastError();
-    return RefcDevice{cus, (size_t)lds};
+// What the device offers a workgroup kernel (engine.h RefDevice) is resolved when the handle is created, not here.
+RefDevice query_ref_device(int device) {
+    RefDevice d;  // (the defaults stand where an attribute cannot be read)
+    int cus = 0, lds = 0, lds_cu = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) d.cus = cus;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds > 0) d.lds_per_cu = (size_t)lds;
+    // (some runtimes report the 64 KB default per block and the real size per multiprocessor: a workgroup may take all of it)
+    if (hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) == hipSuccess && (size_t)lds_cu > d.lds_per_cu)
+        d.lds_per_cu = (size_t)lds_cu;
+    return d;
 }
 static size_t refc_lds_bytes(int waves) { return (size_t)2 * (waves - 1) * RW_WORDS * sizeof(float) + sizeof(RefcShared); }
-static int refc_waves_per_pair(int n_pairs, bool dense, int n_launch = -1) {  // n_pairs: pairs resident together; n_launch: pairs of this launch
-    if (n_launch < 0) n_launch = n_pairs;
-    const RefcDevice d = refc_device();
+static int refc_waves_per_pair(const RefDevice& d, int n_pairs, bool dense, int n_launch) {  // n_pairs: pairs resident together; n_launch: pairs of this launch
     int w = 0;
     for (int cand : {8, 5, 4, 3}) {
         const size_t lds = refc_lds_bytes(cand);
@@ -1235,57 +1228,46 @@ static int refc_waves_per_pair(int n_pairs, bool dense, int n_launch = -1) {  //
     return w;
 }
 
-void launch_lm_track_reference(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, const float* prev_poses7,
-                               const float* kf_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats, int n_pairs,
-                               hipStream_t s) {
-    const bool huber = g.huber_delta > 0.f;
-    // dense mode: the column-major planes (capi.cpp allocates and fills them for every REFERENCE handle); without them, the gathering source
-    const int src = g.mode != VORS_CANDIDATES_DENSE ? REF_SRC_SLIM : (rec.dense_t.recs ? REF_SRC_DENSE_T : REF_SRC_DENSE_ROWMAJOR);
+// Where the points of a level come from, and the run-time -> template dispatch on (Huber, source) that every REFERENCE launch shares:
+// f(huber, src) receives two std::integral_constant.
+static int ref_source(const Geom& g, const Records& rec) {
+    // dense mode: the column-major planes (batch.cpp allocates and fills them for every REFERENCE handle); without them, the gathering source
+    return g.mode != VORS_CANDIDATES_DENSE ? REF_SRC_SLIM : (rec.dense_t.recs ? REF_SRC_DENSE_T : REF_SRC_DENSE_ROWMAJOR);
+}
+template <class F>
+static void with_ref_source(const Geom& g, const Records& rec, F&& f) {
+    const int src = ref_source(g, rec);
+    with_bool(g.huber_delta > 0.f, [&](auto huber) {
+        if (src == REF_SRC_DENSE_T) f(huber, std::integral_constant<int, REF_SRC_DENSE_T>{});
+        else if (src == REF_SRC_DENSE_ROWMAJOR) f(huber, std::integral_constant<int, REF_SRC_DENSE_ROWMAJOR>{});
+        else f(huber, std::integral_constant<int, REF_SRC_SLIM>{});
+    });
+}
+// `n_groups` workgroups of `waves` wavefronts of the workgroup-per-pair kernel (resumed: the pairs queued by the hand-over)
+static void launch_ref_coop(const Geom& g, const TrackCall& call, int n_groups, int waves, bool ahead_step, int resumed, hipStream_t s) {
+    const size_t lds = refc_lds_bytes(waves);
+    with_ref_source(g, call.rec, [&](auto huber, auto src) {
+        with_bool(ahead_step, [&](auto ahead) {
+            auto* kernel = lm_ref_track_coop_kernel<decltype(huber)::value, decltype(src)::value, decltype(ahead)::value>;
+            // (a launch may ask for more than 64 KB of dynamic LDS only after the kernel has been told so; per device, hence not cached in a static)
+            if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                return;  // (the error stays pending: the caller's check after the step reports it against this launch)
+            launch_track(kernel, dim3(n_groups), dim3(64 * waves), lds, s, g, call, call.n_pairs, resumed);
+        });
+    });
+}
+
+void launch_lm_track_reference(const Geom& g, const TrackCall& call, const RefDevice& dev, hipStream_t s) {
+    const int n_pairs = call.n_pairs;
+    const Records& rec = call.rec;
     // (a slot of a vors_pipeline ring: the workgroup size for the pairs that are resident TOGETHER — engine.h Geom::ref_inflight_x2. Measured at
     // 512 pairs per step through a ring of 3: coarse-to-fine 0.556 -> 0.462 ms per step, DSO 0.889 -> 0.754, dense 6.18 -> 5.53 with 4
     // wavefronts per pair instead of the lone step's 5)
     const bool dense = g.mode == VORS_CANDIDATES_DENSE;
     const int resident = (int)std::min<long long>((long long)n_pairs * std::max(2, g.ref_inflight_x2) / 2, 1 << 30);
-    const int coop = refc_waves_per_pair(resident, dense, n_pairs);
-#define VORS_REF_DISPATCH(KERNEL)                                                                              \
-    do {                                                                                                       \
-        if (src == REF_SRC_DENSE_T) {                                                                          \
-            if (huber) VORS_REF_LAUNCH((KERNEL<true, REF_SRC_DENSE_T>));                                       \
-            else VORS_REF_LAUNCH((KERNEL<false, REF_SRC_DENSE_T>));                                            \
-        } else if (src == REF_SRC_DENSE_ROWMAJOR) {                                                            \
-            if (huber) VORS_REF_LAUNCH((KERNEL<true, REF_SRC_DENSE_ROWMAJOR>));                                \
-            else VORS_REF_LAUNCH((KERNEL<false, REF_SRC_DENSE_ROWMAJOR>));                                     \
-        } else {                                                                                               \
-            if (huber) VORS_REF_LAUNCH((KERNEL<true, REF_SRC_SLIM>));                                          \
-            else VORS_REF_LAUNCH((KERNEL<false, REF_SRC_SLIM>));                                               \
-        }                                                                                                      \
-    } while (0)
-#define VORS_REF_DISPATCH_COOP(AH)                                                                              \
-    do {                                                                                                       \
-        if (src == REF_SRC_DENSE_T) {                                                                          \
-            if (huber) VORS_REF_LAUNCH((lm_ref_track_coop_kernel<true, REF_SRC_DENSE_T, AH>));                 \
-            else VORS_REF_LAUNCH((lm_ref_track_coop_kernel<false, REF_SRC_DENSE_T, AH>));                      \
-        } else if (src == REF_SRC_DENSE_ROWMAJOR) {                                                            \
-            if (huber) VORS_REF_LAUNCH((lm_ref_track_coop_kernel<true, REF_SRC_DENSE_ROWMAJOR, AH>));          \
-            else VORS_REF_LAUNCH((lm_ref_track_coop_kernel<false, REF_SRC_DENSE_ROWMAJOR, AH>));               \
-        } else {                                                                                               \
-            if (huber) VORS_REF_LAUNCH((lm_ref_track_coop_kernel<true, REF_SRC_SLIM, AH>));                    \
-            else VORS_REF_LAUNCH((lm_ref_track_coop_kernel<false, REF_SRC_SLIM, AH>));                         \
-        }                                                                                                      \
-    } while (0)
+    const int coop = refc_waves_per_pair(dev, resident, dense, n_pairs);
     if (coop) {
-        const size_t lds = (size_t)2 * (coop - 1) * RW_WORDS * sizeof(float) + sizeof(RefcShared);
-        // (a launch may ask for more than 64 KB of dynamic LDS only after the kernel has been told so; per device, hence not cached in a static)
-#define VORS_REF_LAUNCH(K)                                                                                                                  \
-    do {                                                                                                                                    \
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            break; /* (the error stays pending: the caller's hipGetLastError reports it against this launch) */ \
-        hipLaunchKernelGGL(K, dim3(n_pairs), dim3(64 * coop), lds, s, g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, prev_poses7, \
-                           kf_poses7, out_poses7, out_status, out_stats, n_pairs, 0);                                                      \
-    } while (0)
-        if (coop >= 8) VORS_REF_DISPATCH_COOP(true);
-        else VORS_REF_DISPATCH_COOP(false);
-#undef VORS_REF_LAUNCH
+        launch_ref_coop(g, call, n_pairs, coop, /* ahead-step form: 8 wavefronts only */ coop >= 8, 0, s);
         return;
     }
     const int wpb = refw_waves_per_block(n_pairs);
@@ -1300,42 +1282,27 @@ void launch_lm_track_reference(const Geom& g, Pyramid cur, Pyramid kf, const uin
         ho_after = (int)((long long)n_pairs * percent / 100);
     }
     if (ho_after > 0) (void)hipMemsetAsync(rec.handoff.counters, 0, 2 * sizeof(int), s);
-#define VORS_REF_LAUNCH(K)                                                                                                                            \
-    hipLaunchKernelGGL(K, dim3((n_pairs + wpb - 1) / wpb), dim3(64 * wpb), 0, s, g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, prev_poses7, \
-                       kf_poses7, out_poses7, out_status, out_stats, n_pairs, ho_after)
     bool all_fast = true;
     for (int l = 0; l < g.L; ++l) all_fast = all_fast && g.lv[l].fu.ok && g.lv[l].fv.ok;
-    if (src == REF_SRC_DENSE_ROWMAJOR) {
-        if (huber) VORS_REF_LAUNCH((lm_ref_track_kernel<true, REF_SRC_DENSE_ROWMAJOR, false>));
-        else VORS_REF_LAUNCH((lm_ref_track_kernel<false, REF_SRC_DENSE_ROWMAJOR, false>));
-    } else if (src == REF_SRC_DENSE_T) {
-        if (huber && all_fast) VORS_REF_LAUNCH((lm_ref_track_kernel<true, REF_SRC_DENSE_T, true>));
-        else if (huber) VORS_REF_LAUNCH((lm_ref_track_kernel<true, REF_SRC_DENSE_T, false>));
-        else if (all_fast) VORS_REF_LAUNCH((lm_ref_track_kernel<false, REF_SRC_DENSE_T, true>));
-        else VORS_REF_LAUNCH((lm_ref_track_kernel<false, REF_SRC_DENSE_T, false>));
-    } else {
-        if (huber && all_fast) VORS_REF_LAUNCH((lm_ref_track_kernel<true, REF_SRC_SLIM, true>));
-        else if (huber) VORS_REF_LAUNCH((lm_ref_track_kernel<true, REF_SRC_SLIM, false>));
-        else if (all_fast) VORS_REF_LAUNCH((lm_ref_track_kernel<false, REF_SRC_SLIM, true>));
-        else VORS_REF_LAUNCH((lm_ref_track_kernel<false, REF_SRC_SLIM, false>));
-    }
-#undef VORS_REF_LAUNCH
+    with_ref_source(g, rec, [&](auto huber, auto src) {
+        constexpr bool HUBER = decltype(huber)::value;
+        constexpr int SRC = decltype(src)::value;
+        const dim3 grid((n_pairs + wpb - 1) / wpb), block(64 * wpb);
+        if constexpr (SRC == REF_SRC_DENSE_ROWMAJOR) {  // (the gathering source has no fast-division form)
+            launch_track(lm_ref_track_kernel<HUBER, SRC, false>, grid, block, 0, s, g, call, n_pairs, ho_after);
+        } else {
+            with_bool(all_fast, [&](auto fast) {
+                launch_track(lm_ref_track_kernel<HUBER, SRC, decltype(fast)::value>, grid, block, 0, s, g, call, n_pairs, ho_after);
+            });
+        }
+    });
     if (ho_after > 0) {  // the queued pairs, a workgroup each (at most n_pairs - ho_after of them; a workgroup beyond the queue returns at once)
         int hw = 4;
         if (const char* e = getenv("VORS_REF_HANDOFF_WAVES")) {
             const int v = atoi(e);
             if (v >= 2 && v <= 8) hw = v;
         }
-        const size_t lds = (size_t)2 * (hw - 1) * RW_WORDS * sizeof(float) + sizeof(RefcShared);
-#define VORS_REF_LAUNCH(K)                                                                                                                  \
-    do {                                                                                                                                    \
-        if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            break; \
-        hipLaunchKernelGGL(K, dim3(n_pairs - ho_after), dim3(64 * hw), lds, s, g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, prev_poses7, \
-                           kf_poses7, out_poses7, out_status, out_stats, n_pairs, 1);                                                      \
-    } while (0)
-        VORS_REF_DISPATCH_COOP(false);
-#undef VORS_REF_LAUNCH
+        launch_ref_coop(g, call, n_pairs - ho_after, hw, false, 1, s);
     }
 }
 
@@ -1391,15 +1358,10 @@ __global__ __launch_bounds__(64) void lm_ref_eval_level_kernel(Geom g, const uin
         refw_store29(acc, cnt, out29);
     });
 }
-void launch_lm_eval_level_reference(const Geom& g, Pyramid cur, Pyramid kf, const uint16_t* kf_depth, Records rec, int pair, int lvl,
-                                    const float* model7, float* out29, hipStream_t s) {
-    const bool huber = g.huber_delta > 0.f;
-    const int src = g.mode != VORS_CANDIDATES_DENSE ? REF_SRC_SLIM : (rec.dense_t.recs ? REF_SRC_DENSE_T : REF_SRC_DENSE_ROWMAJOR);
-#define VORS_REF_LAUNCH(K) hipLaunchKernelGGL(K, dim3(1), dim3(64), 0, s, g, cur.level0, cur.upper, kf.level0, kf.upper, kf_depth, rec, pair, lvl, model7, out29)
-    VORS_REF_DISPATCH(lm_ref_eval_level_kernel);
-#undef VORS_REF_LAUNCH
-#undef VORS_REF_DISPATCH
-#undef VORS_REF_DISPATCH_COOP
+void launch_lm_eval_level_reference(const Geom& g, const EvalCall& call, hipStream_t s) {
+    with_ref_source(g, call.rec, [&](auto huber, auto src) {
+        launch_eval(lm_ref_eval_level_kernel<decltype(huber)::value, decltype(src)::value>, dim3(64), s, g, call);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1907,7 +1869,7 @@ __global__ __launch_bounds__(RANK_BLOCK) void rank_regions_kernel(Geom g, Record
 // VORS_REF_RANK=0 keeps the two-kernel form (A/B, tests).
 bool ref_rank_from_regions(const Geom& g, const Records& rec) {
     if (g.arith != VORS_ARITH_REFERENCE || g.mode != VORS_CANDIDATES_COARSE_TO_FINE || !rec.stage || rec.n_regions > RANK_MAX_REGIONS) return false;
-    if (!g.ref_rank) return false;  // (VORS_REF_RANK=0, resolved when the handle was created: capi.cpp build_geom)
+    if (!g.ref_rank) return false;  // (VORS_REF_RANK=0, resolved when the handle was created: batch.cpp build_geom)
     for (int l = 0; l < g.L; ++l)
         if (g.lv[l].n_slots > RANK_U_MAX * RANK_BLOCK || g.lv[l].n_slots >= 65536) return false;
     return true;

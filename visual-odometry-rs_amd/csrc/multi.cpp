@@ -18,7 +18,7 @@
 #include "../../include/vors_hip.h"
 
 extern "C" const char* vors_last_error(void);
-vors_status vors_set_last_error(vors_status st, const std::string& msg);  // capi.cpp
+vors_status vors_set_last_error(vors_status st, const std::string& msg);  // operators.cpp
 
 namespace {
 

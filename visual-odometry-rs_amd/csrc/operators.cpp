@@ -1,0 +1,230 @@
+// Everything of the C ABI that is not a handle: last error, device queries and self-checks, the LM operators on explicit observations
+// (vors_lm_*), Lie helpers and the synthetic scenes.
+#include <cstring>
+
+#include "host_common.h"
+
+using namespace vors;
+
+static thread_local std::string g_last_error;
+vors_status vors_set_last_error(vors_status st, const std::string& msg) {
+    g_last_error = msg;
+    return st;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// operator level
+// ---------------------------------------------------------------------------------------------------------------
+struct ObsDev {
+    DevBuf tmpl, img, xy, iz, jac, A, B, C, XY, IZ, model, out, res;
+    Records rec{};
+    Intr k;
+};
+static vors_status upload_obs(const vors_obs* o, const float model7[7], ObsDev& d, bool want_res, hipStream_t s) {
+    if (!o || !model7) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (o->rows < 2 || o->cols < 2 || o->n < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "bad observation shape");
+    if (o->arithmetic != VORS_ARITH_EXACT && o->arithmetic != VORS_ARITH_REFERENCE)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "vors_obs.arithmetic must be VORS_ARITH_EXACT or VORS_ARITH_REFERENCE");
+    if (!o->template_ || !o->image || (o->n > 0 && (!o->coordinates || !o->_z_candidates || !o->jacobians)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "NULL observation array");
+    vors_status st = require_device();
+    if (st != VORS_OK) return st;
+    const size_t S = (size_t)o->rows * o->cols, n = (size_t)o->n;
+    for (size_t i = 0; i < n; ++i) {
+        const int x = o->coordinates[2 * i], y = o->coordinates[2 * i + 1];
+        if (x < 0 || y < 0 || x >= o->cols || y >= o->rows) return fail(VORS_ERR_INVALID_ARGUMENT, "coordinate outside the template");
+    }
+    HIP_TRY(d.tmpl.alloc(S));
+    HIP_TRY(d.img.alloc(S));
+    HIP_TRY(d.xy.alloc(n * 8));
+    HIP_TRY(d.iz.alloc(n * 4));
+    HIP_TRY(d.jac.alloc(n * 24));
+    HIP_TRY(d.A.alloc(n * 16));
+    HIP_TRY(d.B.alloc(n * 16));
+    HIP_TRY(d.C.alloc(n * 8));
+    HIP_TRY(d.XY.alloc(n * 4));
+    HIP_TRY(d.IZ.alloc(n * 4));
+    HIP_TRY(d.model.alloc(7 * 4));
+    HIP_TRY(d.out.alloc(64 * 4));
+    if (want_res) HIP_TRY(d.res.alloc(n * 4));
+    HIP_TRY(hipMemcpyAsync(d.tmpl.p, o->template_, S, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d.img.p, o->image, S, hipMemcpyHostToDevice, s));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(d.xy.p, o->coordinates, n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d.iz.p, o->_z_candidates, n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d.jac.p, o->jacobians, n * 24, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(d.model.p, model7, 28, hipMemcpyHostToDevice, s));
+    d.k = Intr{o->cu, o->cv, o->fu, o->fv, o->skew};
+    d.rec = Records{d.A.as<float4>(), d.B.as<float4>(), d.C.as<float2>(), d.XY.as<uint32_t>(), d.IZ.as<float>(), nullptr, nullptr, nullptr};
+    launch_records_from_obs(d.k, o->rows, o->cols, d.tmpl.as<uint8_t>(), o->n, d.xy.as<int32_t>(), d.iz.as<float>(),
+                            d.jac.as<float>(), d.rec, s);
+    return VORS_OK;
+}
+
+extern "C" {
+
+const char* vors_last_error(void) { return g_last_error.c_str(); }
+int vors_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return n;
+}
+int vors_abi_version(void) { return 5; }
+
+vors_status vors_selfcheck_isqrt(int* mismatches) {
+    vors_status st = require_device();
+    if (st != VORS_OK) return st;
+    if (!mismatches) return fail(VORS_ERR_INVALID_ARGUMENT, "mismatches is null");
+    const int n = vors::count_isqrt_u16_mismatches(nullptr);
+    if (n < 0) return fail(VORS_ERR_HIP, "isqrt self-check could not run");
+    *mismatches = n;
+    return VORS_OK;
+}
+
+vors_status vors_device_info(int device, int* clock_khz, int* compute_units, uint64_t* memory_bytes) {
+    vors_status st = require_device();
+    if (st != VORS_OK) return st;
+    if (device < 0 || device >= vors_device_count()) return fail(VORS_ERR_INVALID_ARGUMENT, "device index out of range");
+    int v = 0;
+    if (clock_khz) {
+        HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeClockRate, device));
+        *clock_khz = v;
+    }
+    if (compute_units) {
+        HIP_TRY(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device));
+        *compute_units = v;
+    }
+    if (memory_bytes) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        *memory_bytes = (uint64_t)prop.totalGlobalMem;
+    }
+    return VORS_OK;
+}
+
+vors_status vors_lm_eval(const vors_obs* obs, const float model7[7], float* energy, int32_t* n_inside, float g[6], float H[36],
+                         float* residuals) {
+    if (!energy || !n_inside || !g || !H) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL output");
+    ObsDev d;
+    hipStream_t s = nullptr;
+    vors_status st = upload_obs(obs, model7, d, residuals != nullptr, s);
+    if (st != VORS_OK) return st;
+    if (obs->arithmetic == VORS_ARITH_REFERENCE)
+        launch_lm_eval_obs_reference(d.k, obs->rows, obs->cols, d.img.as<uint8_t>(), obs->n, d.rec, obs->huber_delta, d.model.as<float>(),
+                                     d.out.as<float>(), residuals ? d.res.as<float>() : nullptr, s);
+    else
+        launch_lm_eval_obs(d.k, obs->rows, obs->cols, d.img.as<uint8_t>(), obs->n, d.rec, obs->huber_delta, d.model.as<float>(),
+                           d.out.as<float>(), residuals ? d.res.as<float>() : nullptr, s);
+    float out[44];
+    HIP_TRY(hipMemcpyAsync(out, d.out.p, sizeof(out), hipMemcpyDeviceToHost, s));
+    if (residuals && obs->n) HIP_TRY(hipMemcpyAsync(residuals, d.res.p, (size_t)obs->n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    *energy = out[0];
+    *n_inside = (int32_t)out[1];
+    std::memcpy(g, out + 2, 24);
+    std::memcpy(H, out + 8, 144);
+    return VORS_OK;
+}
+
+vors_status vors_lm_solve(const vors_obs* obs, const float model7[7], float out_model7[7], int32_t* nb_iter, float* energy,
+                          float* lm_coef, int* solve_status) {
+    if (!out_model7 || !nb_iter || !energy || !lm_coef || !solve_status) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL output");
+    ObsDev d;
+    hipStream_t s = nullptr;
+    vors_status st = upload_obs(obs, model7, d, false, s);
+    if (st != VORS_OK) return st;
+    if (obs->arithmetic == VORS_ARITH_REFERENCE)
+        launch_lm_solve_obs_reference(d.k, obs->rows, obs->cols, d.img.as<uint8_t>(), obs->n, d.rec, obs->huber_delta, d.model.as<float>(),
+                                      d.out.as<float>(), s);
+    else
+        launch_lm_solve_obs(d.k, obs->rows, obs->cols, d.img.as<uint8_t>(), obs->n, d.rec, obs->huber_delta, d.model.as<float>(),
+                            d.out.as<float>(), s);
+    float out[11];
+    HIP_TRY(hipMemcpyAsync(out, d.out.p, sizeof(out), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    std::memcpy(out_model7, out, 28);
+    *nb_iter = (int32_t)out[7];
+    *energy = out[8];
+    *lm_coef = out[9];
+    *solve_status = out[10] != 0.f ? VORS_TRACK_OPTIMIZER_FAILED_POSE_KEPT : VORS_TRACK_OK;
+    return VORS_OK;
+}
+
+vors_status vors_lm_step(const float H[36], const float g[6], const float model7[7], float lm_coef, float out_model7[7],
+                         int* chol_ok) {
+    if (!H || !g || !model7 || !out_model7 || !chol_ok) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    Iso out;
+    const bool ok = lm_step(H, g, iso_load(model7), lm_coef, &out);
+    *chol_ok = ok ? 1 : 0;
+    if (ok) iso_store(out, out_model7);
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Lie helpers (host arithmetic)
+// ---------------------------------------------------------------------------------------------------------------
+void vors_se3_exp(const float xi[6], float out_iso7[7]) { iso_store(se3_exp(xi), out_iso7); }
+void vors_ref_sincos(const float* x, int n, float* sin_out, float* cos_out) {
+    for (int i = 0; i < n; ++i) {
+        if (sin_out) sin_out[i] = ref_sinf(x[i]);
+        if (cos_out) cos_out[i] = ref_cosf(x[i]);
+    }
+}
+void vors_se3_log(const float iso7[7], float out_xi[6]) { se3_log(iso_load(iso7), out_xi); }
+void vors_so3_exp(const float w[3], float out_q4[4]) {
+    const Quat q = so3_exp(w);
+    out_q4[0] = q.i; out_q4[1] = q.j; out_q4[2] = q.k; out_q4[3] = q.w;
+}
+void vors_so3_log(const float q4[4], float out_w[3]) { so3_log(Quat{q4[0], q4[1], q4[2], q4[3]}, out_w); }
+void vors_iso_mul(const float a7[7], const float b7[7], float out7[7]) { iso_store(iso_mul(iso_load(a7), iso_load(b7)), out7); }
+void vors_iso_inverse(const float a7[7], float out7[7]) { iso_store(iso_inverse(iso_load(a7)), out7); }
+
+// ---------------------------------------------------------------------------------------------------------------
+// synthetic scenes
+// ---------------------------------------------------------------------------------------------------------------
+vors_status vors_synth_render_pairs(uint64_t seed0, int n_pairs, int rows, int cols, const double cam5[5], double motion_scale,
+                                    int invalid_percent, uint8_t* d_kf_gray, uint16_t* d_kf_depth, uint8_t* d_cur_gray,
+                                    uint16_t* d_cur_depth, float* d_gt_models7, void* hip_stream) {
+    if (!cam5 || !d_kf_gray || !d_kf_depth || !d_cur_gray) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_pairs < 1 || rows < 1 || cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "bad shape");
+    vors_status st = require_device();
+    if (st != VORS_OK) return st;
+    launch_synth_pairs(seed0, n_pairs, rows, cols, cam5, motion_scale, invalid_percent, d_kf_gray, d_kf_depth, d_cur_gray,
+                       d_cur_depth, d_gt_models7, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_synth_render_frames(int n_frames, const uint64_t* seeds, const uint64_t* salts, const double* xi6, int rows, int cols,
+                                     const double cam5[5], int invalid_percent, uint8_t* d_gray, uint16_t* d_depth, void* hip_stream) {
+    if (!seeds || !salts || !xi6 || !cam5 || !d_gray || !d_depth) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_frames < 1 || rows < 1 || cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "bad shape");
+    vors_status st = require_device();
+    if (st != VORS_OK) return st;
+    struct Frame {
+        uint64_t seed, salt;
+        double xi[6];
+    };
+    std::vector<Frame> h((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        h[f].seed = seeds[f];
+        h[f].salt = salts[f];
+        for (int q = 0; q < 6; ++q) h[f].xi[q] = xi6[6 * f + q];
+    }
+    DevBuf d;
+    HIP_TRY(d.alloc(h.size() * sizeof(Frame)));
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    HIP_TRY(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(Frame), hipMemcpyHostToDevice, s));
+    launch_synth_frames(d.p, n_frames, rows, cols, cam5, invalid_percent, d_gray, d_depth, s);
+    HIP_TRY(hipStreamSynchronize(s));  // (the table is freed on return)
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+}  // extern "C"

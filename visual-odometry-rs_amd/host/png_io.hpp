@@ -33,7 +33,7 @@ struct Image {
     size_t stride = 0;             // bytes per scanline
 };
 
-constexpr uint64_t MAX_PIXELS = 1ull << 28;  // the tracker's own limit (capi.cpp build_geom): refuse absurd headers before allocating
+constexpr uint64_t MAX_PIXELS = 1ull << 28;  // the tracker's own limit (batch.cpp build_geom): refuse absurd headers before allocating
 
 inline uint32_t be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 
