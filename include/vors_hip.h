@@ -19,6 +19,7 @@
 #ifndef VORS_HIP_H
 #define VORS_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -112,7 +113,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_tracker_track_checked
                               * 4: VORS_ARITH_REFERENCE, vors_obs.arithmetic, vors_ref_sincos
                               * 5: VORS_ARITH_* renumbered: 0 = REFERENCE (a zero-initialised vors_config reproduces the reference), 1 = EXACT, 2 = FUSED
-                              *    (+ vors_selfcheck_isqrt, added without a signature change) */
+                              *    (+ vors_selfcheck_isqrt, added without a signature change; + vors_batch_eval_pairs, vors_batch_pose_information,
+                              *    vors_pose_information_from_sums, likewise additions) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -327,6 +329,43 @@ void vors_multi_destroy(vors_multi* m);
  * handle's own: sums29 (HOST) = sum r^2 (Huber loss with huber_delta), n_inside, g[6], H upper triangle row-wise [21]. Synchronises.
  * This is the operator-level window on the tracker's own point sources; tests compare EXACT and FUSED through it. */
 vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const float model7[7], int arithmetic, float sums29[29]);
+
+/* The same evaluation for a whole batch, device-resident: what scoring candidate motions against a keyframe (relocalisation, loop-closure
+ * verification, a sweep of the energy around a solution) and the pose information below are made of.
+ * VORS_EVAL_FULL = eval_energy + compute_eval_data (lm_optimizer.rs:68-107), VORS_EVAL_ENERGY = eval_energy alone (lm_optimizer.rs:68-87). */
+enum { VORS_EVAL_FULL = 0, VORS_EVAL_ENERGY = 1 };
+
+/* For every pair p < n_pairs and every k < models_per_pair: one evaluation of level `level` of pair p as the handle holds it after
+ * prepare_keyframes + track_current, at model d_models[(p * models_per_pair + k)], in the given VORS_ARITH_* mode.
+ * Models: DEVICE, 7 floats each, consecutive models model_stride_bytes apart (0 = 28; sizeof(vors_pair_stats) lets the caller pass the
+ * d_out_stats array of the last track directly with models_per_pair = 1: lm_model is its first field).
+ * d_sums29: DEVICE [n_pairs * models_per_pair][29], layout of vors_batch_eval_level; VORS_EVAL_ENERGY fills [0], [1] and zeroes the rest.
+ * Enqueued on hip_stream, NOT synchronised, no allocation after the first call on a handle (that call creates the pass's workspace, which
+ * vors_batch_workspace_bytes counts from then on). The sums of a (pair, model) are the same bits whatever n_pairs, models_per_pair and
+ * its place in the batch: EXACT / FUSED cut a level into chunks by its point count alone and add the chunk sums in index order (a level
+ * whose GRID is one chunk — at most 16384 pixels, dense, or 4096 candidate slots — gives vors_batch_eval_level's bits; through the
+ * addition of chunks a sum of -0.0 comes out as +0.0); REFERENCE gives the reference's sequential sums, one wavefront per evaluation. */
+vors_status vors_batch_eval_pairs(vors_batch* b, int n_pairs, int level, int models_per_pair, const void* d_models, size_t model_stride_bytes,
+                                  int arithmetic, int what, float* d_sums29, void* hip_stream);
+
+/* POSE INFORMATION of one evaluation (29 sums) at the solution:
+ *   info36 = H, the upper triangle sums[8..28] mirrored to the full 6x6 matrix (row-major);
+ *   sigma2 = sums[0] / (n_inside - 6), the residual variance left after 6 fitted parameters;
+ *   cov36  = sigma2 * H^-1, through a 6x6 Cholesky in FLOAT64, rounded to f32 at the end (symmetric).
+ * cov36 is the covariance of the twist xi = (v, w) — the order of vors_se3_exp — in the parametrisation the reference's step uses:
+ * true model = model * exp(xi)^-1 (lm_optimizer.rs:134-135). With Huber on, sums[0] is the Huber loss and H the weighted matrix: the same
+ * formula then is an approximation. How well it is calibrated is not asserted anywhere and is NOT MEASURED yet (tools/eval_pairs_bench.py
+ * is the tool for it; DESIGN.md 7b says where that stands): a relative weight between pairs, not an absolute uncertainty.
+ * flags: bit 0 = n_inside <= 6, bit 1 = the Cholesky met a pivot that is not > 0; with either, cov36 and sigma2 are NaN; info36 is
+ * written all the same.
+ *
+ * vors_batch_pose_information = vors_batch_eval_pairs (VORS_EVAL_FULL, the handle's own arithmetic, one model per pair) followed by that
+ * algebra, all on the device. Outputs DEVICE, each nullable: info36 [n][36]; cov36 [n][36]; sigma2 [n]; flags [n]. Enqueued, not synchronised. */
+vors_status vors_batch_pose_information(vors_batch* b, int n_pairs, int level, const void* d_models, size_t model_stride_bytes,
+                                        float* d_info36, float* d_cov36, float* d_sigma2, int32_t* d_flags, void* hip_stream);
+
+/* The same algebra on the host, from one set of 29 sums (host arithmetic, needs no GPU, like vors_lm_step). Outputs nullable. */
+vors_status vors_pose_information_from_sums(const float sums29[29], float info36[36], float cov36[36], float* sigma2, int32_t* flag);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

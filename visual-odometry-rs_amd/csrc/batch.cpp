@@ -585,15 +585,22 @@ vors_status vors_batch_get_points(vors_batch* b, int pair, int level, int capaci
     return VORS_OK;
 }
 
-vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const float model7[7], int arithmetic, float sums29[29]) {
-    if (!b || !model7 || !sums29) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (pair < 0 || pair >= std::min(b->prepared_pairs, b->current_pairs) || level < 0 || level >= b->g.L)
+// What an evaluation at an explicit model needs of the handle (pairs 0 .. last_pair of it) and of the request.
+static vors_status check_eval(const vors_batch* b, int last_pair, int level, int arithmetic) {
+    if (last_pair < 0 || last_pair >= std::min(b->prepared_pairs, b->current_pairs) || level < 0 || level >= b->g.L)
         return fail(VORS_ERR_INVALID_ARGUMENT, "pair/level out of range (pair must be < the n_pairs of the last prepare_keyframes AND track_current)");
     if (!b->kf_level0 || !b->cur_level0)
         return fail(VORS_ERR_INVALID_ARGUMENT, (b->prepared_pairs > 0 && b->current_pairs > 0 && !b->kf_level0) ? "keyframe inspection is not available on a trackers-owned batch in the candidate-list modes (the handle keeps records, not frames)"
                                                                                                                  : "eval_level needs prepare_keyframes and track_current first");
     if (arithmetic != VORS_ARITH_EXACT && arithmetic != VORS_ARITH_FUSED && arithmetic != VORS_ARITH_REFERENCE)
         return fail(VORS_ERR_INVALID_ARGUMENT, "unknown arithmetic mode");
+    return VORS_OK;
+}
+
+vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const float model7[7], int arithmetic, float sums29[29]) {
+    if (!b || !model7 || !sums29) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    vors_status st = check_eval(b, pair, level, arithmetic);
+    if (st != VORS_OK) return st;
     DeviceGuard guard(b->device);
     DevBuf d_model, d_out;
     HIP_TRY(d_model.alloc(7 * sizeof(float)));
@@ -607,6 +614,87 @@ vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const floa
     else launch_lm_eval_level_exact(b->g, call, nullptr);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(sums29, d_out.p, 29 * sizeof(float), hipMemcpyDeviceToHost));
+    return VORS_OK;
+}
+
+// The workspace of the evaluation pass (engine.h EvalPairsWs): created by the first call that needs it and counted by
+// vors_batch_workspace_bytes from then on; a handle that only tracks never pays for it.
+static vors_status ensure_eval_pairs_ws(vors_batch* b) {
+    EvalPairsWs& ws = b->eval_pairs;
+    if (ws.items > 0) return VORS_OK;
+    const int items = std::min(std::max(b->max_pairs, 256), 32768);  // per slice (also the y extent of a grid)
+    int chunks = 1;
+    for (int l = 0; l < b->g.L; ++l) chunks = std::max(chunks, eval_pairs_chunks(b->g, l));
+    // (a call that failed half-way left what it had allocated in the handle: those buffers are kept and used, not allocated again)
+    if (!ws.partials) b->own.alloc(&ws.partials, (size_t)items * chunks * 32);
+    if (!ws.fctx) b->own.alloc(&ws.fctx, (size_t)items);
+    if (!ws.sums29) b->own.alloc(&ws.sums29, (size_t)b->max_pairs * 29);
+    if (b->own.err != hipSuccess) {
+        const hipError_t e = b->own.err;
+        b->own.err = hipSuccess;
+        (void)hipGetLastError();
+        return fail(VORS_ERR_HIP, std::string("hipMalloc (evaluation workspace): ") + hipGetErrorString(e));
+    }
+    ws.items = items;
+    ws.chunks = chunks;
+    return VORS_OK;
+}
+
+static vors_status batch_eval_pairs(vors_batch* b, int n_pairs, int level, int models_per_pair, const void* d_models, size_t model_stride_bytes,
+                                    int arithmetic, int what, float* d_sums29, hipStream_t s) {
+    vors_status st = ensure_eval_pairs_ws(b);
+    if (st != VORS_OK) return st;
+    EvalPairsCall call{{Pyramid{b->cur_level0, b->cur_upper}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    call.n_items = n_pairs * models_per_pair;
+    call.models_per_pair = models_per_pair;
+    call.lvl = level;
+    call.models = static_cast<const float*>(d_models);
+    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.energy_only = what == VORS_EVAL_ENERGY ? 1 : 0;
+    call.out29 = d_sums29;
+    call.ws = b->eval_pairs;
+    if (arithmetic == VORS_ARITH_REFERENCE) launch_lm_eval_pairs_reference(b->g, call, s);
+    else if (arithmetic == VORS_ARITH_FUSED) launch_lm_eval_pairs_fused(b->g, call, s);
+    else launch_lm_eval_pairs_exact(b->g, call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_batch_eval_pairs(vors_batch* b, int n_pairs, int level, int models_per_pair, const void* d_models, size_t model_stride_bytes,
+                                  int arithmetic, int what, float* d_sums29, void* hip_stream) {
+    if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: the handle b is NULL");
+    if (!d_models) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: d_models is NULL");
+    if (!d_sums29) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: d_sums29 is NULL");
+    if (n_pairs < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: n_pairs must be >= 1");
+    if (models_per_pair < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: models_per_pair must be >= 1");
+    if ((long long)n_pairs * models_per_pair > 0x7fffffffLL / 32) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: n_pairs * models_per_pair is too large");
+    if (what != VORS_EVAL_FULL && what != VORS_EVAL_ENERGY) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: unknown `what` (VORS_EVAL_FULL or VORS_EVAL_ENERGY)");
+    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    vors_status st = check_eval(b, n_pairs - 1, level, arithmetic);
+    if (st != VORS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    return batch_eval_pairs(b, n_pairs, level, models_per_pair, d_models, model_stride_bytes, arithmetic, what, d_sums29, s);
+}
+
+vors_status vors_batch_pose_information(vors_batch* b, int n_pairs, int level, const void* d_models, size_t model_stride_bytes, float* d_info36,
+                                        float* d_cov36, float* d_sigma2, int32_t* d_flags, void* hip_stream) {
+    if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: the handle b is NULL");
+    if (!d_models) return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: d_models is NULL");
+    if (n_pairs < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: n_pairs must be >= 1");
+    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    vors_status st = check_eval(b, n_pairs - 1, level, b->g.arith);
+    if (st != VORS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    if ((st = ensure_eval_pairs_ws(b)) != VORS_OK) return st;
+    if ((st = batch_eval_pairs(b, n_pairs, level, 1, d_models, model_stride_bytes, b->g.arith, VORS_EVAL_FULL, b->eval_pairs.sums29, s)) != VORS_OK) return st;
+    launch_pose_information(b->eval_pairs.sums29, n_pairs, d_info36, d_cov36, d_sigma2, d_flags, s);
+    HIP_TRY(hipGetLastError());
     return VORS_OK;
 }
 

@@ -252,6 +252,48 @@ struct EvalCall : LmScene {
     const float* model7;
     float* out29;
 };
+// One evaluation of one level per (pair, model) of a prepared batch, device-resident (vors_batch_eval_pairs): item i = pair * models_per_pair
+// + k reads its model at models + i * model_stride floats and writes out29 + i * 29. The launchers cut the items into slices of at most
+// ws.items, the capacity of the handle's workspace; a slice's item `item0 + s` uses slot s of it.
+struct EvalPairsCtx {     // FUSED arithmetic: the evaluation context of one item, as LmSplitState keeps it for a pair (same names, same meaning)
+    float fctx[21];
+    int fctx_exact;
+};
+struct EvalPairsWs {
+    float* partials;      // [items][chunks][32] chunk sums of the levels cut into several workgroups
+    EvalPairsCtx* fctx;   // [items]
+    float* sums29;        // [max_pairs][29] vors_batch_pose_information's own sums
+    int items, chunks;    // capacity: items per slice, chunks per item
+};
+struct EvalPairsCall : LmScene {
+    int n_items, models_per_pair, lvl;
+    const float* models;
+    int model_stride;     // floats
+    int energy_only;      // VORS_EVAL_ENERGY: sums 0 and 1, zeros elsewhere
+    float* out29;
+    EvalPairsWs ws;
+};
+// What the kernels of one slice get.
+struct EvalPairsArgs {
+    int item0, models_per_pair, lvl, chunk_points;
+    const float* models;
+    int model_stride;
+    float* out29;
+    float* partials;
+    EvalPairsCtx* fctx;
+    int ws_chunks;
+};
+// Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
+// the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
+inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }
+// Chunks of the grid at a level. Coarse-to-fine and dense: the level's point count. DSO: n_slots is the capacity of a list (65536), which
+// no list comes near: the selector aims at 2000 candidates and runs again with a wider net beyond 4x that, so the grid is sized for
+// 8000; a longer list is evaluated whole all the same, cut into that many (larger) chunks by the kernel.
+inline int eval_pairs_chunks(const Geom& g, int lvl) {
+    const int cp = eval_pairs_chunk_points(g);
+    const int points = g.mode == VORS_CANDIDATES_DSO ? (g.lv[lvl].n_slots < 8000 ? g.lv[lvl].n_slots : 8000) : g.lv[lvl].n_slots;
+    return points > cp ? (points + cp - 1) / cp : 1;
+}
 // THE place where the records become kernel arguments: K(g, scene..., extra...), K(g, scene..., poses and outputs..., extra...).
 template <class K, class... Extra>
 void launch_on_scene(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Geom& g, const LmScene& c, Extra... extra) {
@@ -264,6 +306,13 @@ void launch_track(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, co
 template <class K>
 void launch_eval(K kernel, dim3 block, hipStream_t s, const Geom& g, const EvalCall& c) {
     launch_on_scene(kernel, dim3(1), block, 0, s, g, c, c.pair, c.lvl, c.model7, c.out29);
+}
+inline EvalPairsArgs eval_pairs_args(const Geom& g, const EvalPairsCall& c, int item0) {
+    return EvalPairsArgs{item0, c.models_per_pair, c.lvl, eval_pairs_chunk_points(g), c.models, c.model_stride, c.out29, c.ws.partials, c.ws.fctx, c.ws.chunks};
+}
+template <class K>
+void launch_eval_pairs(K kernel, dim3 grid, dim3 block, hipStream_t s, const Geom& g, const EvalPairsCall& c, int item0) {
+    launch_on_scene(kernel, grid, block, 0, s, g, c, eval_pairs_args(g, c, item0));
 }
 // Run-time value -> template argument: f receives a std::integral_constant, `decltype(x)::value` is the compile-time constant.
 //   with_bool(huber, [&](auto h) { launch(kernel<decltype(h)::value>); });
@@ -308,6 +357,12 @@ void launch_lm_solve_obs_reference(Intr k, int rows, int cols, const uint8_t* im
 // One evaluation of one level of one pair of a prepared batch at an explicit model, per arithmetic mode -> 29 sums.
 void launch_lm_eval_level_exact(const Geom& g, const EvalCall& call, hipStream_t s);
 void launch_lm_eval_level_fused(const Geom& g, const EvalCall& call, hipStream_t s);
+// One evaluation of one level per (pair, model), per arithmetic mode -> [item][29] sums on the device, enqueued, not synchronised.
+void launch_lm_eval_pairs_exact(const Geom& g, const EvalPairsCall& call, hipStream_t s);
+void launch_lm_eval_pairs_fused(const Geom& g, const EvalPairsCall& call, hipStream_t s);
+void launch_lm_eval_pairs_reference(const Geom& g, const EvalPairsCall& call, hipStream_t s);
+// [n][29] sums -> information matrix, covariance, sigma^2, flags (lie.h pose_information), one thread per pair; outputs nullable
+void launch_pose_information(const float* sums29, int n, float* info36, float* cov36, float* sigma2, int32_t* flags, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

@@ -148,6 +148,7 @@ struct vors_batch {
     const uint16_t* kf_depth = nullptr;   // caller's depth buffer of the last prepare_keyframes (read by the dense LM kernel)
     vors::Records rec{};
     vors::LmSplitWs split{};
+    vors::EvalPairsWs eval_pairs{};  // vors_batch_eval_pairs / _pose_information: allocated by the first of those calls (items = 0 until then)
     int lm_block = 256;  // threads per frame pair in the LM kernel (256 / 512 / 1024)
     vors::RefDevice ref_device;  // REFERENCE arithmetic: what the device offers the workgroup-per-pair kernel
     // generic-mask (DSO) mode workspaces

@@ -12,8 +12,10 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define VORS_HD __host__ __device__ inline
+#define VORS_UNROLL _Pragma("unroll")
 #else
 #define VORS_HD inline
+#define VORS_UNROLL  // (a host compiler unrolls, or not, as it sees fit)
 #endif
 
 namespace vors {
@@ -188,6 +190,76 @@ VORS_HD bool cholesky6_solve(const float* h, const float* g, float lm_coef, floa
     }
     for (int i = 0; i < 6; ++i) delta[i] = b[i];
     return true;
+}
+
+// Pose information from the 29 sums of one evaluation (include/vors_hip.h, "pose information"): info36 = H, the upper triangle
+// sums[8..28] mirrored; sigma2 = sums[0] / (n_inside - 6); cov36 = sigma2 * H^-1 through a 6x6 Cholesky in f64 (H = L L^T,
+// H^-1 = L^-T L^-1), rounded to f32 at the end and symmetric by construction. Returns the flags: bit 0 = n_inside <= 6, bit 1 = a pivot
+// that is not > 0; with either, cov36 and sigma2 are NaN (info36 is written all the same). Every output is nullable. The one text the
+// host entry (vors_pose_information_from_sums) and the device kernel (lm_kernels.hip pose_information_kernel) both run.
+VORS_HD int pose_information(const float* sums29, float* info36, float* cov36, float* sigma2) {
+    double a[6][6];
+    int k = 8;
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int c = r; c < 6; ++c) {
+            const float v = sums29[k++];
+            a[r][c] = a[c][r] = (double)v;
+            if (info36) info36[r * 6 + c] = info36[c * 6 + r] = v;
+        }
+    int flags = (sums29[1] > 6.0f) ? 0 : 1;  // (a NaN count is "too few points" as well)
+    // Left-looking, lower triangle, like cholesky6_solve. No early exit: a pivot that is not > 0 is remembered and the factorisation runs
+    // on (whatever it then holds is never handed out), so that the loops unroll and the device keeps the factor in registers.
+    bool pivots_ok = true;
+VORS_UNROLL
+    for (int j = 0; j < 6; ++j) {
+VORS_UNROLL
+        for (int q = 0; q < j; ++q)
+VORS_UNROLL
+            for (int i = j; i < 6; ++i) a[i][j] -= a[j][q] * a[i][q];
+        pivots_ok = pivots_ok && a[j][j] > 0.0;
+        const double d = sqrt(a[j][j]);
+        a[j][j] = d;
+VORS_UNROLL
+        for (int i = j + 1; i < 6; ++i) a[i][j] /= d;
+    }
+    if (!pivots_ok) flags |= 2;
+    const float nan = nanf("");
+    if (flags) {
+        if (sigma2) *sigma2 = nan;
+        if (cov36)
+VORS_UNROLL
+            for (int i = 0; i < 36; ++i) cov36[i] = nan;
+        return flags;
+    }
+    const double s2 = (double)sums29[0] / ((double)sums29[1] - 6.0);
+    if (sigma2) *sigma2 = (float)s2;
+    if (!cov36) return flags;
+    double inv[6][6];  // L^-1, lower triangular, column by column (forward substitution on the unit vectors)
+VORS_UNROLL
+    for (int c = 0; c < 6; ++c)
+VORS_UNROLL
+        for (int r = 0; r < 6; ++r) {
+            if (r < c) {
+                inv[r][c] = 0.0;
+                continue;
+            }
+            double t = r == c ? 1.0 : 0.0;
+VORS_UNROLL
+            for (int q = c; q < r; ++q) t -= a[r][q] * inv[q][c];
+            inv[r][c] = t / a[r][r];
+        }
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int c = 0; c <= r; ++c) {
+            double t = 0.0;
+VORS_UNROLL
+            for (int q = r; q < 6; ++q) t += inv[q][r] * inv[q][c];  // (L^-T L^-1)[r][c], q >= max(r, c) = r
+            cov36[r * 6 + c] = cov36[c * 6 + r] = (float)(s2 * t);
+        }
+    return flags;
 }
 
 // One LM step: lm_optimizer.rs:123-136.

@@ -551,8 +551,10 @@ __device__ __forceinline__ bool model_near_identity(const Iso& m) {
     return __builtin_amdgcn_readfirstlane((r <= (VORS_ABL_WIDE_IDENTITY ? 1e-4f : 5e-6f) && t <= (VORS_ABL_WIDE_IDENTITY ? 1e-4f : 1e-6f)) ? 1 : 0) != 0;
 }
 // The context of (level intrinsics, model) written to / read from the split state (LmSplitState::fctx): formed by ONE thread per
-// pair and round; the evaluation workgroups read it with scalar loads.
-__device__ __forceinline__ void store_fused_ctx(const Geom& g, int lvl, const Iso& model, LmSplitState* st) {
+// pair and round; the evaluation workgroups read it with scalar loads. (St: LmSplitState, or the evaluation pass's EvalPairsCtx,
+// which keeps the context alone under the same names.)
+template <class St>
+__device__ __forceinline__ void store_fused_ctx(const Geom& g, int lvl, const Iso& model, St* st) {
     ImgCtx c;
     c.img = nullptr;
     c.rows = g.lv[lvl].rows;
@@ -568,7 +570,8 @@ __device__ __forceinline__ void store_fused_ctx(const Geom& g, int lvl, const Is
     for (int q = 0; q < 18; ++q) st->fctx[q] = v[q];
     st->fctx_exact = model_near_identity(model) ? 1 : 0;
 }
-__device__ __forceinline__ FusedCtx load_fused_ctx(const LmSplitState* st) {
+template <class St>
+__device__ __forceinline__ FusedCtx load_fused_ctx(const St* st) {
     FusedCtx f;
     float v[18];
     // written by an earlier launch, never by this one: read through the constant address space so that the (uniform) loads are scalar
@@ -581,7 +584,8 @@ __device__ __forceinline__ FusedCtx load_fused_ctx(const LmSplitState* st) {
     f.h00_2 = v[12]; f.h00_3 = v[13]; f.h10_2 = v[14]; f.h10_3 = v[15]; f.h20_2 = v[16]; f.h20_3 = v[17];
     return f;
 }
-__device__ __forceinline__ bool fused_ctx_exact(const LmSplitState* st) {
+template <class St>
+__device__ __forceinline__ bool fused_ctx_exact(const St* st) {
     typedef const int __attribute__((address_space(4))) cint;
     return *(cint*)(&st->fctx_exact) != 0;
 }
@@ -1078,9 +1082,9 @@ __device__ __forceinline__ void process_group(const Src& src, const typename Src
 // One evaluation sweep over the units of a level: each thread accumulates its strided share, Src::G points in flight.
 // Sources with PREFETCH keep the raw words of the NEXT unit in flight while the current one is processed, so the wavefronts
 // of a SIMD do not all stall on the same loads at the top of every iteration.
-template <int BLOCK, bool HUBER, bool WRITE_RES, class Src, bool ENERGY_ONLY = false>
+template <int BLOCK, bool HUBER, bool WRITE_RES, class Src, bool ENERGY_ONLY = false, class Pre = LmSplitState>
 __device__ __forceinline__ void eval_accumulate(const Src& src, int n_units, const ImgCtx& c, const Iso& model, float acc[NACC],
-                                                float* residuals, int first = 0, const LmSplitState* pre = nullptr) {
+                                                float* residuals, int first = 0, const Pre* pre = nullptr) {
 #pragma unroll
     for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
     if constexpr (Src::FUSED) {
@@ -2112,6 +2116,114 @@ void VORS_LAUNCH_LM_EVAL_LEVEL(const Geom& g_in, const EvalCall& call, hipStream
             launch_eval(lm_eval_level_kernel<decltype(huber)::value, decltype(dense)::value, kFused>, dim3(256), s, g, call);
         });
     });
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// vors_batch_eval_pairs: one evaluation of ONE level for every (pair, model) of a batch, device-resident. Grid = (chunks of the level) x
+// (items of a slice, engine.h EvalPairsCall); a workgroup evaluates its chunk of the item's points exactly like lm_eval_level_kernel
+// evaluates a whole level (thread-strided sums, block_reduce). A level of one chunk writes its 29 sums straight out — the very additions
+// of lm_eval_level_kernel; otherwise the chunk sums go to the workspace and lm_eval_pairs_sum_kernel adds them in index order. The
+// chunk count comes from the level (engine.h eval_pairs_chunks), so the sums of a (pair, model) are the same bits wherever it stands in
+// whatever batch. No atomics. ENERGY: eval_energy alone (sums 0 and 1 — in the EXACT arithmetic the bits of the full evaluation — zeros
+// elsewhere). FUSED: the evaluation context of an item is formed once, by lm_eval_pairs_ctx_kernel, and read with scalar loads.
+// ------------------------------------------------------------------------------------------------------------
+#define EVALP_BLOCK 256
+template <bool HUBER, bool DENSE, bool FUSED, bool ENERGY>
+__global__ __launch_bounds__(EVALP_BLOCK) void lm_eval_pairs_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                     const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                     const uint16_t* __restrict__ kf_depth, Records rec, EvalPairsArgs a) {
+    __shared__ LmShared s;
+    const int slot = blockIdx.y, item = a.item0 + slot, chunk = blockIdx.x, n_chunks = gridDim.x;
+    const int pair = item / a.models_per_pair;
+    const Iso model = iso_uniform(iso_load(a.models + (size_t)item * a.model_stride));
+    const ImgCtx c = level_ctx(g, cur0, curu, pair, a.lvl);
+    float* part = a.partials + ((size_t)slot * a.ws_chunks + chunk) * 32;
+    float acc[NACC];
+    bool mine = true;
+    with_level_source<DENSE, true, FUSED>(g, a.lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // this pair's chunks at this level (a short candidate list needs fewer than the grid has: the rest of them hold zeros)
+        const int points = DENSE ? g.lv[a.lvl].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        mine = chunk < chunks;
+        if (!mine) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        eval_accumulate<EVALP_BLOCK, HUBER, false, typename std::remove_cv<typename std::remove_reference<decltype(src)>::type>::type, ENERGY>(
+            src, last, c, model, acc, nullptr, first, FUSED ? a.fctx + slot : nullptr);
+    });
+    if (!mine) {  // (workgroup-uniform)
+        if (threadIdx.x < 32) part[threadIdx.x] = 0.f;
+        return;
+    }
+    block_reduce<EVALP_BLOCK>(acc, s, 0);
+    if (threadIdx.x < 32) {
+        const float v = threadIdx.x < (ENERGY ? 2 : NACC) ? s.sums[0][threadIdx.x] : 0.f;
+        if (n_chunks > 1) part[threadIdx.x] = v;
+        else if (threadIdx.x < NACC) a.out29[(size_t)item * 29 + threadIdx.x] = v;
+    }
+}
+#if VORS_FUSED
+// the context (H = K R K^-1, K t, near-identity verdict) of every item of a slice: one lane per item (make_fused_ctx broadcasts from
+// the first active lane, so each item has a wavefront's lane 0 to itself)
+__global__ __launch_bounds__(256) void lm_eval_pairs_ctx_kernel(Geom g, EvalPairsArgs a, int n) {
+    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if ((threadIdx.x & 63) != 0 || slot >= n) return;
+    store_fused_ctx(g, a.lvl, iso_load(a.models + (size_t)(a.item0 + slot) * a.model_stride), a.fctx + slot);
+}
+void launch_lm_eval_pairs_sum(const EvalPairsArgs& a, int n, int chunks, hipStream_t s);  // (arithmetic-independent: in the exact object)
+#define VORS_LAUNCH_LM_EVAL_PAIRS launch_lm_eval_pairs_fused
+#else
+// chunk sums -> the 29 sums of an item, chunks in index order; 32 lanes per item
+__global__ __launch_bounds__(256) void lm_eval_pairs_sum_kernel(EvalPairsArgs a, int n, int chunks) {
+    const int slot = blockIdx.x * 8 + (threadIdx.x >> 5), q = threadIdx.x & 31;
+    if (slot >= n || q >= NACC) return;
+    const float* pp = a.partials + (size_t)slot * a.ws_chunks * 32 + q;
+    float t = 0.f;
+    for (int ch = 0; ch < chunks; ++ch) t += pp[ch * 32];
+    a.out29[(size_t)(a.item0 + slot) * 29 + q] = t;
+}
+void launch_lm_eval_pairs_sum(const EvalPairsArgs& a, int n, int chunks, hipStream_t s) {
+    hipLaunchKernelGGL(lm_eval_pairs_sum_kernel, dim3((n + 7) / 8), dim3(256), 0, s, a, n, chunks);
+}
+// 29 sums -> pose information (lie.h pose_information), one thread per pair
+__global__ __launch_bounds__(64) void pose_information_kernel(const float* __restrict__ sums29, int n, float* __restrict__ info36,
+                                                              float* __restrict__ cov36, float* __restrict__ sigma2, int32_t* __restrict__ flags) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    float sums[29];
+#pragma unroll
+    for (int q = 0; q < 29; ++q) sums[q] = sums29[(size_t)p * 29 + q];
+    // (the outputs are written where they belong, by plain per-lane stores: arrays of the thread's own to copy out of end up in scratch)
+    const int fl = pose_information(sums, info36 ? info36 + (size_t)p * 36 : nullptr, cov36 ? cov36 + (size_t)p * 36 : nullptr,
+                                    sigma2 ? sigma2 + p : nullptr);
+    if (flags) flags[p] = fl;
+}
+void launch_pose_information(const float* sums29, int n, float* info36, float* cov36, float* sigma2, int32_t* flags, hipStream_t s) {
+    hipLaunchKernelGGL(pose_information_kernel, dim3((n + 63) / 64), dim3(64), 0, s, sums29, n, info36, cov36, sigma2, flags);
+}
+#define VORS_LAUNCH_LM_EVAL_PAIRS launch_lm_eval_pairs_exact
+#endif
+void VORS_LAUNCH_LM_EVAL_PAIRS(const Geom& g_in, const EvalPairsCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const int chunks = eval_pairs_chunks(g, call.lvl);
+    for (int item0 = 0; item0 < call.n_items; item0 += call.ws.items) {  // slices of the workspace's capacity, in stream order
+        const int n = std::min(call.ws.items, call.n_items - item0);
+        const EvalPairsArgs a = eval_pairs_args(g, call, item0);
+#if VORS_FUSED
+        hipLaunchKernelGGL(lm_eval_pairs_ctx_kernel, dim3((n + 3) / 4), dim3(256), 0, s, g, a, n);
+#endif
+        with_bool(g.mode == VORS_CANDIDATES_DENSE, [&](auto dense) {
+            with_bool(g.huber_delta > 0.f, [&](auto huber) {
+                with_bool(call.energy_only != 0, [&](auto energy) {
+                    launch_eval_pairs(lm_eval_pairs_kernel<decltype(huber)::value, decltype(dense)::value, kFused, decltype(energy)::value>,
+                                      dim3(chunks, n), dim3(EVALP_BLOCK), s, g, call, item0);
+                });
+            });
+        });
+        if (chunks > 1) launch_lm_eval_pairs_sum(a, n, chunks, s);
+    }
 }
 
 #if VORS_FUSED

@@ -1343,24 +1343,49 @@ __device__ __forceinline__ void refw_store29(float acc, int cnt, float* out29) {
     if (lane == 0) out29[1] = (float)cnt;
 }
 
-// One evaluation of one level of one pair of a prepared batch (vors_batch_eval_level in the REFERENCE arithmetic) -> 29 sums.
+// One evaluation of one level of one pair of a prepared batch in the REFERENCE arithmetic -> 29 sums, by one wavefront: the body of
+// vors_batch_eval_level's kernel and of vors_batch_eval_pairs's, which differ in their grids only. energy_only: sums 0 and 1 of the very
+// same evaluation, zeros elsewhere.
+template <bool HUBER, int SRC>
+__device__ __forceinline__ void ref_eval_level_body(const Geom& g, const uint8_t* cur0, const uint8_t* curu, const uint8_t* kf0, const uint8_t* kfu,
+                                                    const uint16_t* kf_depth, const Records& rec, int pair, int lvl, const float* model7,
+                                                    float* out29, float* lds, bool energy_only) {
+    const Iso model = ref_iso_uniform(iso_load(model7));
+    const RefImg c = ref_level_img<SRC>(g, cur0, curu, rec, pair, lvl);
+    ref_with_source<SRC>(g, lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n) {
+        int cnt;
+        float acc = refw_eval<HUBER>(src, n, c, model, lds, &cnt);
+        if (energy_only && (threadIdx.x & 63) != 0) acc = 0.f;
+        refw_store29(acc, cnt, out29);
+    });
+}
 template <bool HUBER, int SRC>
 __global__ __launch_bounds__(64) void lm_ref_eval_level_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
                                                                const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
                                                                const uint16_t* __restrict__ kf_depth, Records rec, int pair, int lvl,
                                                                const float* __restrict__ model7, float* __restrict__ out29) {
     __shared__ __attribute__((aligned(16))) float lds[RW_WORDS];
-    const Iso model = ref_iso_uniform(iso_load(model7));
-    const RefImg c = ref_level_img<SRC>(g, cur0, curu, rec, pair, lvl);
-    ref_with_source<SRC>(g, lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n) {
-        int cnt;
-        const float acc = refw_eval<HUBER>(src, n, c, model, lds, &cnt);
-        refw_store29(acc, cnt, out29);
-    });
+    ref_eval_level_body<HUBER, SRC>(g, cur0, curu, kf0, kfu, kf_depth, rec, pair, lvl, model7, out29, lds, false);
 }
 void launch_lm_eval_level_reference(const Geom& g, const EvalCall& call, hipStream_t s) {
     with_ref_source(g, call.rec, [&](auto huber, auto src) {
         launch_eval(lm_ref_eval_level_kernel<decltype(huber)::value, decltype(src)::value>, dim3(64), s, g, call);
+    });
+}
+// ... for every (pair, model) of a batch (engine.h EvalPairsCall): one wavefront per item, the reference's sequential sums each.
+template <bool HUBER, int SRC>
+__global__ __launch_bounds__(64) void lm_ref_eval_pairs_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                               const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                               const uint16_t* __restrict__ kf_depth, Records rec, EvalPairsArgs a, int energy_only) {
+    __shared__ __attribute__((aligned(16))) float lds[RW_WORDS];
+    const int item = a.item0 + blockIdx.x;
+    ref_eval_level_body<HUBER, SRC>(g, cur0, curu, kf0, kfu, kf_depth, rec, item / a.models_per_pair, a.lvl, a.models + (size_t)item * a.model_stride,
+                                    a.out29 + (size_t)item * 29, lds, energy_only != 0);
+}
+void launch_lm_eval_pairs_reference(const Geom& g, const EvalPairsCall& call, hipStream_t s) {
+    with_ref_source(g, call.rec, [&](auto huber, auto src) {
+        launch_on_scene(lm_ref_eval_pairs_kernel<decltype(huber)::value, decltype(src)::value>, dim3(call.n_items), dim3(64), 0, s, g, call,
+                        eval_pairs_args(g, call, 0), call.energy_only);
     });
 }
 

@@ -166,6 +166,13 @@ vors_status vors_lm_step(const float H[36], const float g[6], const float model7
     return VORS_OK;
 }
 
+vors_status vors_pose_information_from_sums(const float sums29[29], float info36[36], float cov36[36], float* sigma2, int32_t* flag) {
+    if (!sums29) return fail(VORS_ERR_INVALID_ARGUMENT, "sums29 is NULL");
+    const int fl = pose_information(sums29, info36, cov36, sigma2);
+    if (flag) *flag = fl;
+    return VORS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------

@@ -99,6 +99,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_workspace_bytes", "vors_batch_enable_kernel_timing", "vors_batch_kernel_times", "vors_batch_last_kernel_ms",
     "vors_batch_destroy",
     "vors_batch_get_keyframe_image", "vors_batch_get_current_image", "vors_batch_get_points", "vors_batch_eval_level",
+    "vors_batch_eval_pairs", "vors_batch_pose_information", "vors_pose_information_from_sums",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -182,6 +183,9 @@ def lib():
         _lib.vors_batch_get_current_image.argtypes = [vp, i, i, vp, C.POINTER(i), C.POINTER(i)]
         _lib.vors_batch_get_points.argtypes = [vp, i, i, i, vp, vp, vp, vp, C.POINTER(i)]
         _lib.vors_batch_eval_level.argtypes = [vp, i, i, vp, i, vp]
+        _lib.vors_batch_eval_pairs.argtypes = [vp, i, i, i, vp, C.c_size_t, i, i, vp, vp]
+        _lib.vors_batch_pose_information.argtypes = [vp, i, i, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        _lib.vors_pose_information_from_sums.argtypes = [vp, vp, vp, C.POINTER(f), C.POINTER(C.c_int32)]
         _lib.vors_lm_eval.argtypes = [C.POINTER(vors_obs), vp, C.POINTER(f), C.POINTER(C.c_int32), vp, vp, vp]
         _lib.vors_ref_sincos.argtypes = [vp, i, vp, vp]
         _lib.vors_ref_sincos.restype = None
@@ -513,6 +517,53 @@ class Batch:
         H = H + np.triu(H, 1).T
         return float(out[0]), int(out[1]), out[2:8].copy(), H
 
+    @staticmethod
+    def _models_arg(models):
+        """models [n, 7] / [n, K, 7] float32, or the out_stats bytes of a track (its row size tells) -> (tensor, n, K, stride in bytes)."""
+        import torch
+        if not models.is_contiguous():
+            raise VorsError("models must be a contiguous tensor")
+        if models.dtype == torch.uint8:
+            if models.numel() % PAIR_STATS_DTYPE.itemsize != 0:
+                raise VorsError("a uint8 `models` tensor must be the out_stats buffer of a track")
+            return models, models.numel() // PAIR_STATS_DTYPE.itemsize, 1, PAIR_STATS_DTYPE.itemsize
+        if models.dtype != torch.float32 or models.shape[-1] != 7 or models.dim() not in (2, 3):
+            raise VorsError(f"expected float32 models [n, 7] or [n, K, 7], got {models.dtype} {tuple(models.shape)}")
+        return models, models.shape[0], (models.shape[1] if models.dim() == 3 else 1), 0
+
+    EVAL_WHAT = {"full": 0, "energy": 1}
+
+    def eval_pairs(self, level, models, arithmetic=None, what="full", out=None):
+        """One evaluation of `level` per (pair, model) on the device (vors_batch_eval_pairs) -> sums [n, K, 29] on the current stream,
+        not synchronised. `models`: [n, 7], [n, K, 7], or the out_stats tensor of a track (evaluates at each pair's lm_model)."""
+        import torch
+        models, n, k, stride = self._models_arg(models)
+        if out is None:
+            out = torch.empty((n, k, 29), dtype=torch.float32, device=models.device)
+        elif out.dtype != torch.float32 or out.numel() != n * k * 29 or not out.is_contiguous():
+            raise VorsError(f"out must be a contiguous float32 tensor of {n} x {k} x 29 elements")
+        arith = self.config.arithmetic if arithmetic is None else arithmetic
+        if what not in self.EVAL_WHAT:
+            raise VorsError(f"eval_pairs: unknown `what` {what!r} (one of {', '.join(map(repr, self.EVAL_WHAT))})")
+        _check(lib().vors_batch_eval_pairs(self._h, n, int(level), k, self._dp(models), stride, int(arith), self.EVAL_WHAT[what],
+                                           self._dp(out), self._stream()))
+        return out.view(n, k, 29)
+
+    def pose_information(self, level, models):
+        """Information matrix, covariance of the twist, residual variance and flags of every pair at `models` ([n, 7] or a track's out_stats)
+        in the handle's arithmetic (vors_batch_pose_information) -> (info [n, 6, 6], cov [n, 6, 6], sigma2 [n], flags [n]), not synchronised."""
+        import torch
+        models, n, k, stride = self._models_arg(models)
+        if k != 1:
+            raise VorsError("pose_information takes one model per pair")
+        info = torch.empty((n, 6, 6), dtype=torch.float32, device=models.device)
+        cov = torch.empty((n, 6, 6), dtype=torch.float32, device=models.device)
+        sigma2 = torch.empty(n, dtype=torch.float32, device=models.device)
+        flags = torch.empty(n, dtype=torch.int32, device=models.device)
+        _check(lib().vors_batch_pose_information(self._h, n, int(level), self._dp(models), stride, self._dp(info), self._dp(cov),
+                                                 self._dp(sigma2), self._dp(flags), self._stream()))
+        return info, cov, sigma2, flags
+
     def keyframe_image(self, pair, level):
         out = np.empty(self.rows * self.cols, np.uint8)
         r, c = C.c_int(), C.c_int()
@@ -723,6 +774,18 @@ def lm_eval(obs, model7, want_residuals=False):
     o = obs.to_c()
     _check(lib().vors_lm_eval(C.byref(o), _ptr(model7), C.byref(e), C.byref(n), _ptr(g), _ptr(H), _ptr(res)))
     return (e.value, n.value, g, H, res) if want_residuals else (e.value, n.value, g, H)
+
+
+def pose_information_from_sums(sums29):
+    """Pose information of one evaluation's 29 sums on the host (vors_pose_information_from_sums; needs no GPU)
+    -> (info [6, 6], cov [6, 6], sigma2, flags)."""
+    sums29 = np.ascontiguousarray(sums29, np.float32)
+    if sums29.shape != (29,):
+        raise VorsError(f"expected 29 sums, got shape {sums29.shape}")
+    info, cov = np.zeros((6, 6), np.float32), np.zeros((6, 6), np.float32)
+    s2, fl = C.c_float(), C.c_int32()
+    _check(lib().vors_pose_information_from_sums(_ptr(sums29), _ptr(info), _ptr(cov), C.byref(s2), C.byref(fl)))
+    return info, cov, np.float32(s2.value), int(fl.value)
 
 
 def ref_sincos(x):
