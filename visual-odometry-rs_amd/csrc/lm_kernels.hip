@@ -1595,7 +1595,7 @@ __device__ __forceinline__ ImgCtx level_ctx(const Geom& g, const uint8_t* cur0, 
 enum LmTrackMode : int {
     LM_WHOLE_TRACK = 0,    // the whole track() of the pair: every level, pose, keyframe test, statistics
     LM_COARSE_LEVELS = 1,  // levels L-1 .. split.n_split, then hands the model over to the evaluation rounds through split.state
-    LM_EPILOGUE = 2,       // takes the rounds' results back: pose + keyframe test + statistics (and finishes whatever LM_STRAGGLERS could not take)
+    LM_EPILOGUE = 2,       // takes the rounds' results back: pose + keyframe test + statistics (LM_STRAGGLERS has finished every pair by then)
     LM_STRAGGLERS = 3,     // workgroup a finishes the a-th pair still iterating after the last round (a big workgroup each, all in parallel)
     LM_SIDE_LANE = 4,      // workgroup k finishes the levels above 0 of the k-th pair on the side lane (engine.h LmSplitWs), back to the rounds
 };
@@ -2284,9 +2284,11 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, const TrackCall& call, int block, Lm
         (void)hipStreamWaitEvent(s, split.ev_join, 0);
         launch_lm_split_merge(split, split.rounds, s);
     }
-    // the pairs still iterating (a handful, each with a long serial tail) finish in parallel, one 1024-thread workgroup each (the grid grows with
-    // the batch: a hard batch may leave more than 256 of them, and a workgroup beyond the active list returns at once)
-    launch_lm_track_mode(g, call, std::min(n_pairs, std::max(256, n_pairs / 8)), 1024, LM_STRAGGLERS, split, s);
+    // the pairs still iterating (a handful, each with a long serial tail) finish in parallel, one 1024-thread workgroup each. The grid covers
+    // the WHOLE active list (a workgroup beyond it returns at once): LM_EPILOGUE would finish a pair left over with `block` threads, and
+    // solve_level's sums depend on the workgroup size — with the list's order coming from atomics, the last bits of a hard batch would
+    // change from run to run
+    launch_lm_track_mode(g, call, n_pairs, 1024, LM_STRAGGLERS, split, s);
     launch_lm_track_mode(g, call, n_pairs, block, LM_EPILOGUE, split, s);
 }
 
