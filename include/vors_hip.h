@@ -114,7 +114,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               * 4: VORS_ARITH_REFERENCE, vors_obs.arithmetic, vors_ref_sincos
                               * 5: VORS_ARITH_* renumbered: 0 = REFERENCE (a zero-initialised vors_config reproduces the reference), 1 = EXACT, 2 = FUSED
                               *    (+ vors_selfcheck_isqrt, added without a signature change; + vors_batch_eval_pairs, vors_batch_pose_information,
-                              *    vors_pose_information_from_sums, likewise additions) */
+                              *    vors_pose_information_from_sums, likewise additions; + vors_batch_residual_maps, vors_residual_scale_from_hist,
+                              *    likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -366,6 +367,42 @@ vors_status vors_batch_pose_information(vors_batch* b, int n_pairs, int level, c
 
 /* The same algebra on the host, from one set of 29 sums (host arithmetic, needs no GPU, like vors_lm_step). Outputs nullable. */
 vors_status vors_pose_information_from_sums(const float sums29[29], float info36[36], float cov36[36], float* sigma2, int32_t* flag);
+
+/* THE PER-POINT QUANTITIES of one evaluation, for a whole batch, device-resident: what the sums above are made of. For every pair
+ * p < n_pairs, level `level` of pair p as the handle holds it after prepare_keyframes + track_current, at model d_models[p] (DEVICE, 7
+ * floats each, model_stride_bytes apart: 0 = 28; sizeof(vors_pair_stats) takes the d_out_stats array of the last track, as in
+ * vors_batch_eval_pairs). Outputs DEVICE, each nullable (at least one must be given):
+ *   d_residuals [n_pairs][rows_l * cols_l]      interpolate(u, v) - template (lm_optimizer.rs:236-247): the RAW residual, no Huber weight
+ *                                               whatever huber_delta is. Finite exactly where the point passes the strict inside test
+ *                                               (lm_optimizer.rs:227-231), NaN everywhere else.
+ *   d_warp_uv   [n_pairs][rows_l * cols_l][2]   (u, v) of warp (lm_optimizer.rs:213-219) for every usable candidate, inside or not;
+ *                                               (NaN, NaN) at every pixel that is not one.
+ *   d_hist      [n_pairs][VORS_RESIDUAL_BINS]   d_hist[p][min((int)|r|, 255)] counts the finite residuals of pair p: bins one grey level
+ *                                               wide (|r| <= 255 up to float32 rounding of the interpolation); integer counts, independent of scheduling; their sum
+ *                                               is n_inside of the evaluation.
+ *   d_scale     [n_pairs][2]                    median |r| and 1.4826 median |r| read off d_hist (vors_residual_scale_from_hist, the same
+ *                                               text on the device, bit for bit): a starting point for huber_delta. NEEDS d_hist: the
+ *                                               pass keeps no histogram of its own, d_scale without d_hist is VORS_ERR_INVALID_ARGUMENT.
+ * The planes have the KEYFRAME pixel geometry of the level, row-major rows_l x cols_l (the level's shape: floor halving), in every
+ * candidate mode: element (y, x) belongs to the usable candidate of this level at pixel (x, y) — extract_z's set
+ * (inverse_compositional.rs:260-279), the set vors_batch_get_points returns: a pixel with a candidate whose inverse depth is known.
+ * The arithmetic is always the reference's per point (what VORS_ARITH_REFERENCE and VORS_ARITH_EXACT evaluate: residuals bit-identical to
+ * the reference's), whatever the handle's: there is no arithmetic argument. A VORS_ARITH_FUSED track minimises values a few ulp away from
+ * these (its warp and its interpolation are shorter, algebraically equivalent forms), and a point within rounding of the window border may
+ * be inside for one and outside for the other.
+ * Enqueued on hip_stream, NOT synchronised, no allocation ever (the pass has no workspace: vors_batch_workspace_bytes does not change). In
+ * dense mode the keyframe's d_kf_gray / d_kf_depth must still be alive, as for vors_batch_track_current. Touches nothing track computes or reads.
+ * vors_trackers handles are out of scope, for the reason given for the pose information: a track may promote the current
+ * frame to keyframe before the caller can ask, so the pair that was solved no longer exists in the handle. */
+#define VORS_RESIDUAL_BINS 256
+vors_status vors_batch_residual_maps(vors_batch* b, int n_pairs, int level, const void* d_models, size_t model_stride_bytes,
+                                     float* d_residuals, float* d_warp_uv, uint32_t* d_hist, float* d_scale, void* hip_stream);
+
+/* The scale of a residual histogram on the host (host arithmetic, needs no GPU). In float64: n = sum of the bins (*n_inside),
+ * target = n / 2, b = the first bin whose cumulative count reaches target, *median_abs = b + (target - cumulative count before b) / hist[b],
+ * *sigma_mad = 1.4826 * that (the standard deviation of a normal distribution with this median of |r|), each rounded to f32 at the end.
+ * The median is exact to within the bin width (one grey level). n = 0: both NaN, status VORS_OK. Outputs nullable. */
+vors_status vors_residual_scale_from_hist(const uint32_t hist[VORS_RESIDUAL_BINS], float* median_abs, float* sigma_mad, uint32_t* n_inside);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

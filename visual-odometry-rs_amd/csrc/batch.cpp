@@ -698,6 +698,35 @@ vors_status vors_batch_pose_information(vors_batch* b, int n_pairs, int level, c
     return VORS_OK;
 }
 
+vors_status vors_batch_residual_maps(vors_batch* b, int n_pairs, int level, const void* d_models, size_t model_stride_bytes, float* d_residuals,
+                                     float* d_warp_uv, uint32_t* d_hist, float* d_scale, void* hip_stream) {
+    if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: the handle b is NULL");
+    if (!d_models) return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: d_models is NULL");
+    if (!d_residuals && !d_warp_uv && !d_hist && !d_scale)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: every output (d_residuals, d_warp_uv, d_hist, d_scale) is NULL");
+    if (d_scale && !d_hist) return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: d_scale needs d_hist (the pass keeps no histogram of its own)");
+    if (n_pairs < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: n_pairs must be >= 1");
+    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    vors_status st = check_eval(b, n_pairs - 1, level, VORS_ARITH_EXACT);
+    if (st != VORS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    ResidualMapsCall call{{Pyramid{b->cur_level0, b->cur_upper}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    call.n_pairs = n_pairs;
+    call.lvl = level;
+    call.models = static_cast<const float*>(d_models);
+    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.residuals = d_residuals;
+    call.warp_uv = d_warp_uv;
+    call.hist = d_hist;
+    call.scale = d_scale;
+    launch_lm_residual_maps(b->g, call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host-buffer batch entry
 // ---------------------------------------------------------------------------------------------------------------

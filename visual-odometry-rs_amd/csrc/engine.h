@@ -283,6 +283,27 @@ struct EvalPairsArgs {
     EvalPairsCtx* fctx;
     int ws_chunks;
 };
+// The per-point quantities of one level per pair of a prepared batch at one model per pair (vors_batch_residual_maps): planes in the
+// keyframe pixel geometry of the level, a 256-bin histogram of |residual| and the scale read off it. Every output is nullable.
+struct ResidualMapsCall : LmScene {
+    int n_pairs, lvl;
+    const float* models;
+    int model_stride;     // floats
+    float* residuals;     // [pair][rows_l * cols_l]
+    float* warp_uv;       // [pair][rows_l * cols_l][2]
+    uint32_t* hist;       // [pair][VORS_RESIDUAL_BINS]
+    float* scale;         // [pair][2] (needs hist)
+};
+// What the kernel of one slice of pairs gets.
+struct ResidualMapsArgs {
+    int pair0, lvl, chunk_points;
+    const float* models;
+    int model_stride;
+    float* residuals;
+    float* warp_uv;
+    uint32_t* hist;
+    int wide_stores;      // the planes are 16-byte aligned: a dense quad stores 16 bytes at a time
+};
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }
@@ -363,6 +384,9 @@ void launch_lm_eval_pairs_fused(const Geom& g, const EvalPairsCall& call, hipStr
 void launch_lm_eval_pairs_reference(const Geom& g, const EvalPairsCall& call, hipStream_t s);
 // [n][29] sums -> information matrix, covariance, sigma^2, flags (lie.h pose_information), one thread per pair; outputs nullable
 void launch_pose_information(const float* sums29, int n, float* info36, float* cov36, float* sigma2, int32_t* flags, hipStream_t s);
+// Residuals, warp field, |residual| histogram and its scale of one level per pair, in the reference's per-point arithmetic whatever the
+// handle's (lm_kernels.hip lm_residual_maps_kernel, residual_scale_kernel): enqueued, not synchronised, no workspace.
+void launch_lm_residual_maps(const Geom& g, const ResidualMapsCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

@@ -262,6 +262,29 @@ VORS_UNROLL
     return flags;
 }
 
+// Scale of the residuals from the 256-bin histogram of |r| (include/vors_hip.h, vors_batch_residual_maps: bin k counts k <= |r| < k + 1, the
+// last one 255 <= |r|), in f64: n = sum of the bins, target = n / 2, b = the first bin whose cumulative count reaches target,
+// median_abs = b + (target - count below b) / hist[b] (the bin's counts spread evenly over its width), sigma_mad = 1.4826 median_abs, each
+// rounded to f32 at the end. n = 0: both NaN. Every output is nullable. The one text the host entry (vors_residual_scale_from_hist) and
+// the device kernel (lm_kernels.hip residual_scale_kernel) both run.
+VORS_HD void residual_scale_from_hist(const uint32_t* hist, float* median_abs, float* sigma_mad, uint32_t* n_inside) {
+    unsigned long long n = 0;
+    for (int k = 0; k < 256; ++k) n += hist[k];
+    if (n_inside) *n_inside = (uint32_t)n;
+    if (n == 0) {
+        if (median_abs) *median_abs = nanf("");
+        if (sigma_mad) *sigma_mad = nanf("");
+        return;
+    }
+    const double target = 0.5 * (double)n;
+    unsigned long long below = 0;
+    int b = 0;
+    while (b < 255 && (double)(below + hist[b]) < target) below += hist[b++];  // (n > 0: some bin reaches target, and that bin is not empty)
+    const double med = (double)b + (target - (double)below) / (double)hist[b];
+    if (median_abs) *median_abs = (float)med;
+    if (sigma_mad) *sigma_mad = (float)(1.4826 * med);
+}
+
 // One LM step: lm_optimizer.rs:123-136.
 VORS_HD bool lm_step(const float* h36, const float* g6, const Iso& model, float lm_coef, Iso* out) {
     float delta[6];

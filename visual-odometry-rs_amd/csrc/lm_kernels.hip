@@ -434,15 +434,20 @@ __device__ __forceinline__ Taps load_taps(const ImgCtx& c, const Warped& w) {
     __builtin_memcpy(&b, c.img + (o + (unsigned)c.cols), 2);
     return Taps{a, b};
 }
-// bilinear (lm_optimizer.rs:236-247, term order as written) + residual + the 29 sums. Returns the residual (NaN if outside).
+// bilinear (lm_optimizer.rs:236-247, term order as written) + residual: interpolate(u, v) - template, whatever `inside` says. The ONE
+// text the sums (accumulate_point) and the per-point outputs (lm_residual_maps_kernel) are made of.
+__device__ __forceinline__ float bilinear_residual(float tmpl, const Warped& w, const Taps& t) {
+    const float vu_00 = (float)(t.top & 0xff), vu_01 = (float)(t.top >> 8), vu_10 = (float)(t.bot & 0xff), vu_11 = (float)(t.bot >> 8);
+    const float fa = w.u - w.uf, fb = w.v - w.vf;
+    const float im = (1.0f - fb) * (1.0f - fa) * vu_00 + fb * (1.0f - fa) * vu_10 + (1.0f - fb) * fa * vu_01 + fb * fa * vu_11;
+    return im - tmpl;
+}
+// bilinear_residual + the 29 sums. Returns the residual (NaN if outside).
 // ENERGY_ONLY: eval_energy alone (lm_optimizer.rs:68-87) — the sums 0 and 1; the Jacobian is not touched.
 template <bool HUBER, bool ENERGY_ONLY = false>
 __device__ __forceinline__ float accumulate_point(const ImgCtx& c, float tmpl, const float J[6], const Warped& w, const Taps& t,
                                                   float acc[NACC]) {
-    const float vu_00 = (float)(t.top & 0xff), vu_01 = (float)(t.top >> 8), vu_10 = (float)(t.bot & 0xff), vu_11 = (float)(t.bot >> 8);
-    const float fa = w.u - w.uf, fb = w.v - w.vf;
-    const float im = (1.0f - fb) * (1.0f - fa) * vu_00 + fb * (1.0f - fa) * vu_10 + (1.0f - fb) * fa * vu_01 + fb * fa * vu_11;
-    const float r_true = im - tmpl;
+    const float r_true = bilinear_residual(tmpl, w, t);
     // Outside / empty points contribute exactly nothing: selected to zero (never multiplied: 0 * inf would poison the sums).
     const float r = w.inside ? r_true : 0.f;
     if (ENERGY_ONLY) {
@@ -2296,6 +2301,155 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, const TrackCall& call, int block, Lm
 void launch_lm_track(const Geom& g, const TrackCall& call, int block, LmSplitWs split, hipStream_t s) {
     if (g.arith == VORS_ARITH_FUSED) launch_lm_track_fused(g, call, block, split, s);
     else launch_lm_track_exact(g, call, block, split, s);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// vors_batch_residual_maps: what one evaluation of a level is made of, per point instead of summed — the position every usable
+// candidate warps to, its raw residual (no Huber weight) where it passes the strict inside test, a 256-bin histogram of |residual| per
+// pair and the scale read off it. Grid = (chunks of the level) x pairs with lm_eval_pairs_kernel's cut of a level; the loop is
+// eval_accumulate's exact loop (positions -> warp_point -> load_taps -> bilinear_residual) with stores for a sink: no Jacobian, no sums,
+// no reduction, no workspace. The planes have the keyframe pixel geometry of the level (row-major) in every candidate mode: a dense pass
+// visits every pixel and writes the NaN of a pixel that is no point itself, the candidate lists scatter into planes the launcher has
+// filled with NaN. Always the reference's per-point arithmetic (this object), whatever the handle's.
+// Histogram (HIST): one sub-histogram per wavefront in LDS (4 x 1 KiB, LDS atomics), added at the end and flushed with one global integer
+// atomicAdd per non-empty bin and workgroup into a zeroed array: integer counts, so the result does not depend on the schedule. Without
+// HIST the kernel has no LDS and no atomic at all.
+// ------------------------------------------------------------------------------------------------------------
+#define RMAPS_BLOCK 256
+// Pixel index of point g of a group in the level's plane (-1: no point). The dense sources' slot() IS the pixel; a list record carries it.
+template <bool LEVEL0>
+__device__ __forceinline__ int plane_pixel(const DenseSrc<LEVEL0>& src, const typename DenseSrc<LEVEL0>::Raw& r, int g, int) {
+    return src.slot(r, g, 0);
+}
+template <bool LEVEL0, bool FAST>
+__device__ __forceinline__ int plane_pixel(const DenseQuadSrc<LEVEL0, FAST>& src, const typename DenseQuadSrc<LEVEL0, FAST>::Raw& r, int g, int) {
+    return src.slot(r, g, 0);
+}
+__device__ __forceinline__ int plane_pixel(const SlimSrc&, const SlimSrc::Raw& r, int g, int cols) {
+    return r.valid[g] ? (int)(r.r[g].xy >> 16) * cols + (int)(r.r[g].xy & 0xffffu) : -1;
+}
+template <bool HIST, class Src>
+__device__ __forceinline__ void residual_maps_sweep(const Src& src, int first, int last, const ImgCtx& c, const Iso& model, float* res, float* uv,
+                                                    bool wide, uint32_t* wave_hist) {
+    constexpr int G = Src::G;
+    const float nan = __builtin_nanf("");
+    const unsigned plane = (unsigned)(c.rows * c.cols);
+    for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
+        typename Src::Raw raw;
+        src.template fetch<RMAPS_BLOCK>(cur, last, raw);
+        Pos pos[G];
+        src.positions(raw, pos);
+        Warped w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = warp_point(c, model, pos[g]);
+        Taps t[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) t[g] = load_taps(c, w[g]);
+        float r[G], u[G], v[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float r_true = bilinear_residual(pos[g].tmpl, w[g], t[g]);
+            const bool usable = pos[g].tmpl >= 0.f;
+            r[g] = w[g].inside ? r_true : nan;
+            u[g] = usable ? w[g].u : nan;
+            v[g] = usable ? w[g].v : nan;
+        }
+        if constexpr (HIST) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (w[g].inside) atomicAdd(&wave_hist[min((int)fabsf(r[g]), VORS_RESIDUAL_BINS - 1)], 1u);  // (|r| <= 255 up to the rounding of the four products: 255.00002 happens)
+        }
+        if constexpr (G == 4) {
+            if (wide) {  // (uniform) a quad owns four adjacent pixels of one row, 16-byte aligned in both planes
+                const unsigned px = (unsigned)plane_pixel(src, raw, 0, c.cols);
+                if (res) *reinterpret_cast<float4*>(res + px) = make_float4(r[0], r[1], r[2], r[3]);
+                if (uv) {
+                    *reinterpret_cast<float4*>(uv + 2 * px) = make_float4(u[0], v[0], u[1], v[1]);
+                    *reinterpret_cast<float4*>(uv + 2 * px + 4) = make_float4(u[2], v[2], u[3], v[3]);
+                }
+                continue;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int px = plane_pixel(src, raw, g, c.cols);
+            if ((unsigned)px >= plane) continue;  // no point (a lane past the end of a list)
+            if (res) res[px] = r[g];
+            if (uv) {
+                if (wide) {
+                    *reinterpret_cast<float2*>(uv + 2 * (unsigned)px) = make_float2(u[g], v[g]);
+                } else {
+                    uv[2 * (unsigned)px] = u[g];
+                    uv[2 * (unsigned)px + 1] = v[g];
+                }
+            }
+        }
+    }
+}
+template <bool DENSE, bool HIST>
+__global__ __launch_bounds__(RMAPS_BLOCK) void lm_residual_maps_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                       const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                       const uint16_t* __restrict__ kf_depth, Records rec, ResidualMapsArgs a) {
+    __shared__ uint32_t lds_hist[HIST ? (RMAPS_BLOCK / 64) * VORS_RESIDUAL_BINS : 1];
+    const int pair = a.pair0 + blockIdx.y, chunk = blockIdx.x, n_chunks = gridDim.x;
+    const Iso model = iso_uniform(iso_load(a.models + (size_t)pair * a.model_stride));
+    const ImgCtx c = level_ctx(g, cur0, curu, pair, a.lvl);
+    const size_t plane = (size_t)c.rows * c.cols;
+    float* res = a.residuals ? a.residuals + (size_t)pair * plane : nullptr;
+    float* uv = a.warp_uv ? a.warp_uv + (size_t)pair * plane * 2 : nullptr;
+    if constexpr (HIST) {
+#pragma unroll
+        for (int k = 0; k < RMAPS_BLOCK / 64; ++k) lds_hist[k * VORS_RESIDUAL_BINS + threadIdx.x] = 0;
+        __syncthreads();
+    }
+    with_level_source<DENSE, true, false>(g, a.lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // this pair's chunks at this level, cut like lm_eval_pairs_kernel's (a short candidate list needs fewer than the grid has)
+        const int points = DENSE ? g.lv[a.lvl].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        residual_maps_sweep<HIST>(src, first, last, c, model, res, uv, a.wide_stores != 0, lds_hist + (threadIdx.x >> 6) * VORS_RESIDUAL_BINS);
+    });
+    if constexpr (HIST) {
+        __syncthreads();
+        uint32_t n = 0;
+#pragma unroll
+        for (int k = 0; k < RMAPS_BLOCK / 64; ++k) n += lds_hist[k * VORS_RESIDUAL_BINS + threadIdx.x];
+        if (n) atomicAdd(a.hist + (size_t)pair * VORS_RESIDUAL_BINS + threadIdx.x, n);
+    }
+}
+static_assert(RMAPS_BLOCK == VORS_RESIDUAL_BINS, "one thread per bin clears and flushes the histogram");
+// histogram -> (median |r|, 1.4826 median |r|) (lie.h residual_scale_from_hist), one thread per pair
+__global__ __launch_bounds__(64) void residual_scale_kernel(const uint32_t* __restrict__ hist, int n, float* __restrict__ scale) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    residual_scale_from_hist(hist + (size_t)p * VORS_RESIDUAL_BINS, scale + 2 * (size_t)p, scale + 2 * (size_t)p + 1, nullptr);
+}
+void launch_lm_residual_maps(const Geom& g_in, const ResidualMapsCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const bool dense = g.mode == VORS_CANDIDATES_DENSE;
+    const size_t plane = (size_t)g.lv[call.lvl].rows * g.lv[call.lvl].cols, n = (size_t)call.n_pairs;
+    if (!dense) {  // the lists scatter their points into planes of NaN
+        if (call.residuals) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(call.residuals), 0x7fc00000, n * plane, s);
+        if (call.warp_uv) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(call.warp_uv), 0x7fc00000, n * plane * 2, s);
+    }
+    if (call.hist) (void)hipMemsetAsync(call.hist, 0, n * VORS_RESIDUAL_BINS * sizeof(uint32_t), s);
+    ResidualMapsArgs a{0, call.lvl, eval_pairs_chunk_points(g), call.models, call.model_stride, call.residuals, call.warp_uv, call.hist,
+                       (((uintptr_t)call.residuals | (uintptr_t)call.warp_uv) % 16 == 0) ? 1 : 0};
+    const int chunks = eval_pairs_chunks(g, call.lvl);
+    for (int pair0 = 0; pair0 < call.n_pairs; pair0 += 32768) {  // (the y extent of a grid)
+        a.pair0 = pair0;
+        const int np = std::min(32768, call.n_pairs - pair0);
+        with_bool(dense, [&](auto d) {
+            with_bool(call.hist != nullptr, [&](auto h) {
+                launch_on_scene(lm_residual_maps_kernel<decltype(d)::value, decltype(h)::value>, dim3(chunks, np), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+            });
+        });
+    }
+    if (call.scale && call.hist) hipLaunchKernelGGL(residual_scale_kernel, dim3((call.n_pairs + 63) / 64), dim3(64), 0, s, call.hist, call.n_pairs, call.scale);
 }
 
 // ------------------------------------------------------------------------------------------------------------

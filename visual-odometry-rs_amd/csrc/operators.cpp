@@ -173,6 +173,12 @@ vors_status vors_pose_information_from_sums(const float sums29[29], float info36
     return VORS_OK;
 }
 
+vors_status vors_residual_scale_from_hist(const uint32_t hist[VORS_RESIDUAL_BINS], float* median_abs, float* sigma_mad, uint32_t* n_inside) {
+    if (!hist) return fail(VORS_ERR_INVALID_ARGUMENT, "hist is NULL");
+    residual_scale_from_hist(hist, median_abs, sigma_mad, n_inside);
+    return VORS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------

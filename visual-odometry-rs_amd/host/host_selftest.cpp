@@ -25,6 +25,23 @@ int main() {
     auto toy = Toy::iterative_solve(3.0, 11.0);
     if (!toy.ok() || std::fabs(toy.state->x - 3.0) > 1e-3) { std::fprintf(stderr, "trait skeleton failed\n"); return 1; }
 
+    // C-level view of the residual-map entries: the batch entry refuses a NULL handle before it touches a device, and the scale of a
+    // histogram is host arithmetic (bins 3 and 4 hold 5 points each, bin 9 ten: the 10th of 20 points ends bin 4 -> median |r| = 5)
+    {
+        if (vors_batch_residual_maps(nullptr, 1, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr) != VORS_ERR_INVALID_ARGUMENT) {
+            std::fprintf(stderr, "vors_batch_residual_maps accepted a NULL handle\n");
+            return 1;
+        }
+        uint32_t hist[VORS_RESIDUAL_BINS] = {0}, n_inside = 0;
+        hist[3] = 5; hist[4] = 5; hist[9] = 10;
+        float med = 0, sigma = 0;
+        if (vors_residual_scale_from_hist(hist, &med, &sigma, &n_inside) != VORS_OK || med != 5.0f || sigma != (float)(1.4826 * 5.0) || n_inside != 20 ||
+            vors_residual_scale_from_hist(nullptr, &med, &sigma, &n_inside) != VORS_ERR_INVALID_ARGUMENT) {
+            std::fprintf(stderr, "vors_residual_scale_from_hist failed: median %g sigma %g n %u\n", med, sigma, n_inside);
+            return 1;
+        }
+    }
+
     if (vors_device_count() < 1) { std::printf("host_selftest: link ok, no GPU (skipping device part)\n"); return 77; }
     const int rows = 120, cols = 160;
     const double s = cols / 640.0;

@@ -22,6 +22,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VORS_HIP_LIB") or os.path.join(_HERE, "libvors_hip.so")  # VORS_HIP_LIB: development builds (ablations)
 MAX_LEVELS = 8
+RESIDUAL_BINS = 256  # VORS_RESIDUAL_BINS
 
 ROW_MAJOR, COL_MAJOR = 0, 1
 CANDIDATES_COARSE_TO_FINE, CANDIDATES_DENSE, CANDIDATES_DSO = 0, 1, 2
@@ -100,6 +101,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_destroy",
     "vors_batch_get_keyframe_image", "vors_batch_get_current_image", "vors_batch_get_points", "vors_batch_eval_level",
     "vors_batch_eval_pairs", "vors_batch_pose_information", "vors_pose_information_from_sums",
+    "vors_batch_residual_maps", "vors_residual_scale_from_hist",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -186,6 +188,8 @@ def lib():
         _lib.vors_batch_eval_pairs.argtypes = [vp, i, i, i, vp, C.c_size_t, i, i, vp, vp]
         _lib.vors_batch_pose_information.argtypes = [vp, i, i, vp, C.c_size_t, vp, vp, vp, vp, vp]
         _lib.vors_pose_information_from_sums.argtypes = [vp, vp, vp, C.POINTER(f), C.POINTER(C.c_int32)]
+        _lib.vors_batch_residual_maps.argtypes = [vp, i, i, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        _lib.vors_residual_scale_from_hist.argtypes = [vp, C.POINTER(f), C.POINTER(f), C.POINTER(C.c_uint32)]
         _lib.vors_lm_eval.argtypes = [C.POINTER(vors_obs), vp, C.POINTER(f), C.POINTER(C.c_int32), vp, vp, vp]
         _lib.vors_ref_sincos.argtypes = [vp, i, vp, vp]
         _lib.vors_ref_sincos.restype = None
@@ -564,6 +568,37 @@ class Batch:
                                                  self._dp(sigma2), self._dp(flags), self._stream()))
         return info, cov, sigma2, flags
 
+    def residual_maps(self, level, models, residuals=True, warp=False, hist=False, scale=False):
+        """The per-point quantities of one evaluation of `level` per pair at `models` ([n, 7] or a track's out_stats), in the reference's
+        per-point arithmetic whatever the handle's (vors_batch_residual_maps) -> dict of the requested tensors on the current stream, not
+        synchronised: "residuals" [n, rows_l, cols_l] (raw residual, NaN where the point is not inside), "warp" [n, rows_l, cols_l, 2]
+        ((u, v) of every usable candidate, NaN elsewhere), "hist" [n, 256] (int32 view of the counts of min(int(|r|), 255)), "scale" [n, 2]
+        (median |r|, 1.4826 median |r|; computed from the histogram, which is made for it when `hist` is not asked for)."""
+        import torch
+        models, n, k, stride = self._models_arg(models)
+        if k != 1:
+            raise VorsError("residual_maps takes one model per pair")
+        if not (residuals or warp or hist or scale):
+            raise VorsError("residual_maps: nothing requested")
+        rows, cols = self.rows >> int(level), self.cols >> int(level)
+        dev = models.device
+        t_res = torch.empty((n, rows, cols), dtype=torch.float32, device=dev) if residuals else None
+        t_uv = torch.empty((n, rows, cols, 2), dtype=torch.float32, device=dev) if warp else None
+        t_hist = torch.empty((n, RESIDUAL_BINS), dtype=torch.int32, device=dev) if (hist or scale) else None
+        t_scale = torch.empty((n, 2), dtype=torch.float32, device=dev) if scale else None
+        _check(lib().vors_batch_residual_maps(self._h, n, int(level), self._dp(models), stride, self._dp(t_res), self._dp(t_uv), self._dp(t_hist),
+                                              self._dp(t_scale), self._stream()))
+        out = {}
+        if residuals:
+            out["residuals"] = t_res
+        if warp:
+            out["warp"] = t_uv
+        if hist:
+            out["hist"] = t_hist
+        if scale:
+            out["scale"] = t_scale
+        return out
+
     def keyframe_image(self, pair, level):
         out = np.empty(self.rows * self.cols, np.uint8)
         r, c = C.c_int(), C.c_int()
@@ -786,6 +821,18 @@ def pose_information_from_sums(sums29):
     s2, fl = C.c_float(), C.c_int32()
     _check(lib().vors_pose_information_from_sums(_ptr(sums29), _ptr(info), _ptr(cov), C.byref(s2), C.byref(fl)))
     return info, cov, np.float32(s2.value), int(fl.value)
+
+
+def residual_scale_from_hist(hist):
+    """Scale of the residuals from a 256-bin histogram of |r| on the host (vors_residual_scale_from_hist; needs no GPU)
+    -> (median_abs, sigma_mad = 1.4826 median_abs, n_inside); both scales NaN when the histogram is empty."""
+    hist = np.asarray(hist)
+    if hist.shape != (RESIDUAL_BINS,) or hist.dtype.kind not in "iu" or (hist < 0).any() or (hist > 0xffffffff).any():
+        raise VorsError(f"expected {RESIDUAL_BINS} counts (non-negative integers below 2^32), got {hist.dtype} {hist.shape}")
+    hist = np.ascontiguousarray(hist.astype(np.uint32))
+    med, sig, n = C.c_float(), C.c_float(), C.c_uint32()
+    _check(lib().vors_residual_scale_from_hist(_ptr(hist), C.byref(med), C.byref(sig), C.byref(n)))
+    return np.float32(med.value), np.float32(sig.value), int(n.value)
 
 
 def ref_sincos(x):
