@@ -115,7 +115,7 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               * 5: VORS_ARITH_* renumbered: 0 = REFERENCE (a zero-initialised vors_config reproduces the reference), 1 = EXACT, 2 = FUSED
                               *    (+ vors_selfcheck_isqrt, added without a signature change; + vors_batch_eval_pairs, vors_batch_pose_information,
                               *    vors_pose_information_from_sums, likewise additions; + vors_batch_residual_maps, vors_residual_scale_from_hist,
-                              *    likewise) */
+                              *    likewise; + vors_batch_reproject_depth, vors_to_depth, vors_from_depth, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -404,6 +404,41 @@ vors_status vors_batch_residual_maps(vors_batch* b, int n_pairs, int level, cons
  * The median is exact to within the bin width (one grey level). n = 0: both NaN, status VORS_OK. Outputs nullable. */
 vors_status vors_residual_scale_from_hist(const uint32_t hist[VORS_RESIDUAL_BINS], float* median_abs, float* sigma_mad, uint32_t* n_inside);
 
+/* DEPTH REPROJECTION of a prepared batch, device-resident: where the keyframe's depth lands in the current frame (a forward warp with a
+ * z-buffer), and whether it agrees with the depth the sensor measured there — the current depth map the reference's Tracker::track takes
+ * in every call (inverse_compositional.rs:170-176) but uses only when the frame becomes a keyframe. Needs vors_batch_prepare_keyframes
+ * ONLY: no current image and no current pyramid is read, so the pass is legal before any track_current; n_pairs <= the n_pairs of the last
+ * prepare. d_models / model_stride_bytes as in vors_batch_residual_maps (DEVICE, 7 floats each; 0 = 28; sizeof(vors_pair_stats) takes the
+ * d_out_stats array of the last track).
+ * For every usable point i of level `level` of pair p (extract_z's set, inverse_compositional.rs:260-279, the set vors_batch_get_points
+ * returns and the planes above mark; in dense mode it includes the zero-gradient border of level 0):
+ *   P' = M * back_project(x, y, 1 / idepth), (u, v) = project(P') / P'.z — warp, lm_optimizer.rs:213-219, in the reference's per-point
+ *   arithmetic: (u, v) have the bits vors_batch_residual_maps writes to d_warp_uv — and Z' = P'.z.
+ *   The point LANDS iff Z' > 0 and fu = floorf(u + 0.5f), fv = floorf(v + 0.5f) satisfy 0 <= fu < cols_l, 0 <= fv < rows_l (all compares in
+ *   float: NaN and huge values fail them), at the pixel q = (int)fv * cols_l + (int)fu of the CURRENT frame.
+ * Outputs DEVICE, each nullable (at least one must be given):
+ *   d_pred_z         [n_pairs][rows_l * cols_l]  current frame: the minimum Z' (metres) over the points that land at the pixel — the
+ *                                                nearest surface wins —, +inf where none lands. Bitwise reproducible (a minimum does not
+ *                                                depend on the order of arrival).
+ *   d_pred_depth     [n_pairs][rows_l * cols_l]  current frame: to_depth(depth_scale, 1.0f / z) of d_pred_z (inverse_depth.rs:37-42, see
+ *                                                vors_to_depth), 0 where it is +inf. NEEDS d_pred_z: the pass keeps no plane of its own,
+ *                                                d_pred_depth without d_pred_z is VORS_ERR_INVALID_ARGUMENT.
+ *   d_depth_residual [n_pairs][rows * cols]      KEYFRAME geometry: Z' - (float)d_cur_depth[p][q] / depth_scale at each point that lands on a
+ *                                                pixel with non-zero current depth, NaN at every other pixel. Needs d_cur_depth (and so
+ *                                                level 0).
+ *   d_counts         [n_pairs][4]                {usable points, points that land, those with a current depth, those with |residual| <=
+ *                                                tol_m}; the last two are 0 without d_cur_depth. Integers, independent of scheduling.
+ * d_cur_depth [n_pairs][rows * cols] (DEVICE, nullable): the current frames' depth maps, 0 = unknown; level 0 only (depth maps exist at full
+ * resolution only). Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: d_cur_depth with level != 0, d_depth_residual without
+ * d_cur_depth, negative or NaN tol_m, no output at all, a level out of range, a stream of another device.
+ * Contracts of vors_batch_residual_maps: enqueued on hip_stream, NOT synchronised, no allocation ever (vors_batch_workspace_bytes does not
+ * change); in dense mode the keyframe's d_kf_gray / d_kf_depth must still be alive; touches nothing track computes or reads; always the
+ * reference's per-point arithmetic whatever the handle's; vors_trackers handles are out of scope. */
+vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, const void* d_models, size_t model_stride_bytes,
+                                       const uint16_t* d_cur_depth /* nullable */, float tol_m,
+                                       float* d_pred_z, uint16_t* d_pred_depth, float* d_depth_residual, uint32_t* d_counts,
+                                       void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for
  *    `impl optimizer::State<Obs, EvalState, Iso3, String> for LMOptimizerState` (lm_optimizer.rs:111-193):
@@ -450,6 +485,10 @@ void vors_so3_exp(const float w[3], float out_q4[4]);
 void vors_so3_log(const float q4[4], float out_w[3]);
 void vors_iso_mul(const float a7[7], const float b7[7], float out7[7]);
 void vors_iso_inverse(const float a7[7], float out7[7]);
+/* inverse_depth.rs:24-29 and :37-42 for arrays (host arithmetic). from_depth: 0 -> NaN (Unknown), else scale / depth. to_depth:
+ * roundf(scale / idepth) — halves away from zero, f32::round — converted like Rust's `as u16`: NaN -> 0, <= 0 -> 0, >= 65535 -> 65535. */
+void vors_to_depth(float scale, const float* idepth, int n, uint16_t* depth_out);
+void vors_from_depth(float scale, const uint16_t* depth, int n, float* idepth_out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 5. Synthetic scene renderer on the device (bench/test tooling). Renders, for pair i in

@@ -727,6 +727,48 @@ vors_status vors_batch_residual_maps(vors_batch* b, int n_pairs, int level, cons
     return VORS_OK;
 }
 
+vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, const void* d_models, size_t model_stride_bytes,
+                                       const uint16_t* d_cur_depth, float tol_m, float* d_pred_z, uint16_t* d_pred_depth, float* d_depth_residual,
+                                       uint32_t* d_counts, void* hip_stream) {
+    if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: the handle b is NULL");
+    if (!d_models) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: d_models is NULL");
+    if (!d_pred_z && !d_pred_depth && !d_depth_residual && !d_counts)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: every output (d_pred_z, d_pred_depth, d_depth_residual, d_counts) is NULL");
+    if (d_pred_depth && !d_pred_z)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: d_pred_depth needs d_pred_z (the pass keeps no plane of its own)");
+    if (d_depth_residual && !d_cur_depth) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: d_depth_residual needs d_cur_depth");
+    if (d_cur_depth && level != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: d_cur_depth needs level 0 (depth maps exist at full resolution only)");
+    if (!(tol_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: tol_m must be >= 0 (and not NaN)");
+    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    // the keyframe side alone: no current image, no current pyramid is read, so the pass is legal before any track_current
+    if (b->prepared_pairs <= 0 || !b->kf_level0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, b->prepared_pairs > 0 ? "reproject_depth is not available on a trackers-owned batch (the handle keeps records, not frames)"
+                                                                     : "reproject_depth needs prepare_keyframes first");
+    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
+    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: level out of range");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    vors_status st = check_stream(b, s);
+    if (st != VORS_OK) return st;
+    ReprojectCall call{{Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    call.n_pairs = n_pairs;
+    call.lvl = level;
+    call.models = static_cast<const float*>(d_models);
+    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.cur_depth = d_cur_depth;
+    call.tol_m = tol_m;
+    call.pred_z = d_pred_z;
+    call.pred_depth = d_pred_depth;
+    call.residual = d_depth_residual;
+    call.counts = d_counts;
+    launch_lm_reproject_depth(b->g, call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host-buffer batch entry
 // ---------------------------------------------------------------------------------------------------------------

@@ -304,6 +304,31 @@ struct ResidualMapsArgs {
     uint32_t* hist;
     int wide_stores;      // the planes are 16-byte aligned: a dense quad stores 16 bytes at a time
 };
+// Depth reprojection of one level per pair of a prepared batch at one model per pair (vors_batch_reproject_depth): the keyframe's points
+// warped into the current frame with a z-buffer, and compared with a measured current depth map. Every output is nullable.
+struct ReprojectCall : LmScene {
+    int n_pairs, lvl;
+    const float* models;
+    int model_stride;           // floats
+    const uint16_t* cur_depth;  // [pair][S0], level 0 only; nullable
+    float tol_m;
+    float* pred_z;              // [pair][rows_l * cols_l], current frame: min Z' over the points that land, +inf elsewhere
+    uint16_t* pred_depth;       // [pair][rows_l * cols_l], current frame (needs pred_z)
+    float* residual;            // [pair][rows * cols], keyframe geometry (needs cur_depth)
+    uint32_t* counts;           // [pair][4]
+};
+// What the kernel of one slice of pairs gets.
+struct ReprojectArgs {
+    int pair0, lvl, chunk_points;
+    const float* models;
+    int model_stride;
+    const uint16_t* cur_depth;
+    float tol_m;
+    uint32_t* pred_z;           // the plane as bit patterns: Z' > 0 orders as its bits
+    float* residual;
+    uint32_t* counts;
+    int wide_stores;            // the residual plane is 16-byte aligned: a dense quad stores 16 bytes at a time
+};
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }
@@ -387,6 +412,10 @@ void launch_pose_information(const float* sums29, int n, float* info36, float* c
 // Residuals, warp field, |residual| histogram and its scale of one level per pair, in the reference's per-point arithmetic whatever the
 // handle's (lm_kernels.hip lm_residual_maps_kernel, residual_scale_kernel): enqueued, not synchronised, no workspace.
 void launch_lm_residual_maps(const Geom& g, const ResidualMapsCall& call, hipStream_t s);
+// Z-buffered forward warp of the keyframe's depth into the current frame, its u16 depth map, the geometric residual against a measured
+// current depth and the four counts, in the reference's per-point arithmetic whatever the handle's (lm_kernels.hip
+// lm_reproject_depth_kernel, pred_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
+void launch_lm_reproject_depth(const Geom& g, const ReprojectCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

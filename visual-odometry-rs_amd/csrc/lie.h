@@ -285,6 +285,17 @@ VORS_HD void residual_scale_from_hist(const uint32_t* hist, float* median_abs, f
     if (sigma_mad) *sigma_mad = (float)(1.4826 * med);
 }
 
+// Inverse depth -> depth map value: inverse_depth.rs:37-42, `(scale / x).round() as u16`. roundf rounds halves away from zero like
+// f32::round; the cast saturates like Rust's `as` (NaN -> 0, <= 0 -> 0, >= 65535 -> 65535). The comparisons are made in float BEFORE the
+// integer conversion, so no out-of-range float is ever converted. The one text the host entry (vors_to_depth) and the device kernel
+// (lm_kernels.hip pred_depth_kernel) both run.
+VORS_HD uint16_t to_depth(float scale, float idepth) {
+    const float r = roundf(scale / idepth);
+    if (!(r > 0.0f)) return 0;  // NaN, zero, negative
+    if (r >= 65535.0f) return 65535;
+    return (uint16_t)(int)r;
+}
+
 // One LM step: lm_optimizer.rs:123-136.
 VORS_HD bool lm_step(const float* h36, const float* g6, const Iso& model, float lm_coef, Iso* out) {
     float delta[6];

@@ -2453,6 +2453,184 @@ void launch_lm_residual_maps(const Geom& g_in, const ResidualMapsCall& call, hip
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// vors_batch_reproject_depth: the keyframe's points carried into the CURRENT frame — a forward warp with a z-buffer — and compared with
+// a measured current depth map. Grid, cut of a level and sources are lm_residual_maps_kernel's; the loop is positions -> warp_point_z and
+// nothing of the current image is read. A point lands at the pixel nearest to (u, v) when P'.z > 0 and that pixel is in the window (all
+// compares in float: NaN and huge values fail them, and only a landing point's coordinates are ever converted to integers).
+// Z-buffer: a positive float orders as its bit pattern, so the plane is kept as uint32 — filled with +inf (0x7f800000) by the launcher,
+// one 32-bit global atomicMin per landing point. A minimum does not depend on the order of arrival: the plane is bitwise reproducible.
+// Residual (level 0, needs the current depth): P'.z - cur_depth[q] / depth_scale in KEYFRAME geometry, stored like the residual maps
+// (dense: the pass writes the NaN of a non-point itself; lists: scattered into a plane of NaN).
+// Counts (COUNTS): per-thread integers, added across the wavefront, one LDS sum per workgroup, one global integer atomicAdd per non-zero
+// counter and workgroup into a zeroed array. Without COUNTS the kernel has no LDS.
+// ------------------------------------------------------------------------------------------------------------
+// warp (lm_optimizer.rs:213-219) as warp_point evaluates it — the same text, so (u, v) have the bits of d_warp_uv — plus the depth P'.z.
+struct WarpedZ {
+    float u, v, z;
+};
+__device__ __forceinline__ WarpedZ warp_point_z(const ImgCtx& c, const Iso& model, const Pos& p) {
+    WarpedZ w;
+    const V3 p2 = iso_transform_point(model, V3{p.X, p.Y, p.Z});
+    project_uv(c.k, p2, &w.u, &w.v);
+    w.z = p2.z;
+    return w;
+}
+template <bool COUNTS, class Src>
+__device__ __forceinline__ void reproject_sweep(const Src& src, int first, int last, const ImgCtx& c, const Iso& model, float depth_scale,
+                                                uint32_t* zbuf, const uint16_t* cur_depth, float tol_m, float* res, bool wide, uint32_t n[4]) {
+    constexpr int G = Src::G;
+    const float nan = __builtin_nanf("");
+    const unsigned plane = (unsigned)(c.rows * c.cols);
+    const float fcols = (float)c.cols, frows = (float)c.rows;
+    for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
+        typename Src::Raw raw;
+        src.template fetch<RMAPS_BLOCK>(cur, last, raw);
+        Pos pos[G];
+        src.positions(raw, pos);
+        WarpedZ w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = warp_point_z(c, model, pos[g]);
+        bool usable[G], lands[G];
+        unsigned q[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float fu = floorf(w[g].u + 0.5f), fv = floorf(w[g].v + 0.5f);
+            usable[g] = pos[g].tmpl >= 0.f;
+            lands[g] = usable[g] && (w[g].z > 0.f) && (fu >= 0.f) && (fu < fcols) && (fv >= 0.f) && (fv < frows);
+            // masked, not branched: a point that does not land addresses pixel 0 (a safe address) and is selected away
+            q[g] = (unsigned)(__float2int_rz(lands[g] ? fv : 0.f) * c.cols + __float2int_rz(lands[g] ? fu : 0.f));
+        }
+        if (zbuf) {
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+                if (lands[g]) atomicMin(zbuf + q[g], (uint32_t)__float_as_int(w[g].z));
+        }
+        float r[G];
+        if (cur_depth) {  // (uniform) one 2-byte gather per point
+            uint16_t d[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g) d[g] = cur_depth[q[g]];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const bool has = lands[g] && d[g] != 0;
+                r[g] = has ? w[g].z - (float)d[g] / depth_scale : nan;
+                if constexpr (COUNTS) {
+                    n[2] += has ? 1u : 0u;
+                    n[3] += (has && fabsf(r[g]) <= tol_m) ? 1u : 0u;
+                }
+            }
+        }
+        if constexpr (COUNTS) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                n[0] += usable[g] ? 1u : 0u;
+                n[1] += lands[g] ? 1u : 0u;
+            }
+        }
+        if (!res) continue;  // (uniform; res needs cur_depth: r is set)
+        if constexpr (G == 4) {
+            if (wide) {  // (uniform) a quad owns four adjacent pixels of one row, 16-byte aligned in the plane
+                const unsigned px = (unsigned)plane_pixel(src, raw, 0, c.cols);
+                *reinterpret_cast<float4*>(res + px) = make_float4(r[0], r[1], r[2], r[3]);
+                continue;
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const int px = plane_pixel(src, raw, g, c.cols);
+            if ((unsigned)px >= plane) continue;  // no point (a lane past the end of a list)
+            res[px] = r[g];
+        }
+    }
+}
+template <bool DENSE, bool COUNTS>
+__global__ __launch_bounds__(RMAPS_BLOCK) void lm_reproject_depth_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                         const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                         const uint16_t* __restrict__ kf_depth, Records rec, ReprojectArgs a) {
+    __shared__ uint32_t lds_counts[COUNTS ? (RMAPS_BLOCK / 64) * 4 : 1];
+    const int pair = a.pair0 + blockIdx.y, chunk = blockIdx.x, n_chunks = gridDim.x;
+    const Iso model = iso_uniform(iso_load(a.models + (size_t)pair * a.model_stride));
+    ImgCtx c{};  // the level's window and intrinsics; the current image is never read (the pass is legal before any track_current)
+    c.rows = g.lv[a.lvl].rows;
+    c.cols = g.lv[a.lvl].cols;
+    c.k = g.lv[a.lvl].k;
+    const size_t plane = (size_t)c.rows * c.cols;
+    uint32_t* zbuf = a.pred_z ? a.pred_z + (size_t)pair * plane : nullptr;
+    const uint16_t* cur_depth = a.cur_depth ? a.cur_depth + (size_t)pair * g.S0 : nullptr;  // (level 0 only: plane == S0)
+    float* res = a.residual ? a.residual + (size_t)pair * plane : nullptr;
+    uint32_t n[4] = {0u, 0u, 0u, 0u};
+    with_level_source<DENSE, true, false>(g, a.lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // this pair's chunks at this level, cut like lm_eval_pairs_kernel's (a short candidate list needs fewer than the grid has)
+        const int points = DENSE ? g.lv[a.lvl].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        reproject_sweep<COUNTS>(src, first, last, c, model, g.depth_scale, zbuf, cur_depth, a.tol_m, res, a.wide_stores != 0, n);
+    });
+    if constexpr (COUNTS) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) n[k] += (uint32_t)__shfl_xor((int)n[k], o);
+            if ((threadIdx.x & 63) == 0) lds_counts[(threadIdx.x >> 6) * 4 + k] = n[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int wv = 0; wv < RMAPS_BLOCK / 64; ++wv) t += lds_counts[wv * 4 + threadIdx.x];
+            if (t) atomicAdd(a.counts + (size_t)pair * 4 + threadIdx.x, t);
+        }
+    }
+}
+// z-buffer -> depth map: to_depth(depth_scale, 1 / z) (lie.h, inverse_depth.rs:37-42), 0 where nothing landed. Four pixels per thread
+// (16-byte loads, 8-byte stores) where the planes allow it.
+__global__ __launch_bounds__(256) void pred_depth_kernel(const float* __restrict__ z, size_t n, float depth_scale, uint16_t* __restrict__ out, int wide) {
+    const float inf = __builtin_inff();
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+    const size_t n4 = wide ? n / 4 : 0;
+    for (size_t i = t; i < n4; i += step) {
+        const float4 zz = reinterpret_cast<const float4*>(z)[i];
+        ushort4 d;
+        d.x = zz.x == inf ? (uint16_t)0 : to_depth(depth_scale, 1.0f / zz.x);
+        d.y = zz.y == inf ? (uint16_t)0 : to_depth(depth_scale, 1.0f / zz.y);
+        d.z = zz.z == inf ? (uint16_t)0 : to_depth(depth_scale, 1.0f / zz.z);
+        d.w = zz.w == inf ? (uint16_t)0 : to_depth(depth_scale, 1.0f / zz.w);
+        reinterpret_cast<ushort4*>(out)[i] = d;
+    }
+    for (size_t i = 4 * n4 + t; i < n; i += step) out[i] = z[i] == inf ? (uint16_t)0 : to_depth(depth_scale, 1.0f / z[i]);
+}
+void launch_lm_reproject_depth(const Geom& g_in, const ReprojectCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const bool dense = g.mode == VORS_CANDIDATES_DENSE;
+    const size_t plane = (size_t)g.lv[call.lvl].rows * g.lv[call.lvl].cols, n = (size_t)call.n_pairs;
+    if (call.pred_z) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(call.pred_z), 0x7f800000, n * plane, s);  // +inf: nothing has landed
+    if (call.residual && !dense) (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(call.residual), 0x7fc00000, n * plane, s);
+    if (call.counts) (void)hipMemsetAsync(call.counts, 0, n * 4 * sizeof(uint32_t), s);
+    ReprojectArgs a{0, call.lvl, eval_pairs_chunk_points(g), call.models, call.model_stride, call.cur_depth, call.tol_m,
+                    reinterpret_cast<uint32_t*>(call.pred_z), call.residual, call.counts, ((uintptr_t)call.residual % 16 == 0) ? 1 : 0};
+    const int chunks = eval_pairs_chunks(g, call.lvl);
+    for (int pair0 = 0; pair0 < call.n_pairs; pair0 += 32768) {  // (the y extent of a grid)
+        a.pair0 = pair0;
+        const int np = std::min(32768, call.n_pairs - pair0);
+        with_bool(dense, [&](auto d) {
+            with_bool(call.counts != nullptr, [&](auto k) {
+                launch_on_scene(lm_reproject_depth_kernel<decltype(d)::value, decltype(k)::value>, dim3(chunks, np), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+            });
+        });
+    }
+    if (call.pred_depth && call.pred_z) {
+        const size_t total = n * plane;
+        const int wide = (((uintptr_t)call.pred_z % 16 == 0) && ((uintptr_t)call.pred_depth % 8 == 0)) ? 1 : 0;
+        const size_t blocks = std::min<size_t>((total / 4 + 255) / 256 + 1, 8192);
+        hipLaunchKernelGGL(pred_depth_kernel, dim3((unsigned)blocks), dim3(256), 0, s, call.pred_z, total, g.depth_scale, call.pred_depth, wide);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Operator level (one pyramid level, explicit observations)
 // ------------------------------------------------------------------------------------------------------------
 #define OP_BLOCK 256

@@ -197,6 +197,12 @@ void vors_so3_exp(const float w[3], float out_q4[4]) {
 void vors_so3_log(const float q4[4], float out_w[3]) { so3_log(Quat{q4[0], q4[1], q4[2], q4[3]}, out_w); }
 void vors_iso_mul(const float a7[7], const float b7[7], float out7[7]) { iso_store(iso_mul(iso_load(a7), iso_load(b7)), out7); }
 void vors_iso_inverse(const float a7[7], float out7[7]) { iso_store(iso_inverse(iso_load(a7)), out7); }
+void vors_to_depth(float scale, const float* idepth, int n, uint16_t* depth_out) {
+    for (int i = 0; i < n; ++i) depth_out[i] = to_depth(scale, idepth[i]);
+}
+void vors_from_depth(float scale, const uint16_t* depth, int n, float* idepth_out) {
+    for (int i = 0; i < n; ++i) idepth_out[i] = depth[i] ? scale / (float)depth[i] : nanf("");  // inverse_depth.rs:24-29, Unknown = NaN
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // synthetic scenes

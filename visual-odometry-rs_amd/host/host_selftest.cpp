@@ -42,6 +42,26 @@ int main() {
         }
     }
 
+    // ... and of the depth reprojection: a NULL handle is refused before a device is touched; to_depth / from_depth are host arithmetic
+    // (halves round away from zero: 5000 / 0.8 = 6250, 2.5 / 1 -> 3; Unknown <-> 0; the cast saturates)
+    {
+        if (vors_batch_reproject_depth(nullptr, 1, 0, nullptr, 0, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr) != VORS_ERR_INVALID_ARGUMENT) {
+            std::fprintf(stderr, "vors_batch_reproject_depth accepted a NULL handle\n");
+            return 1;
+        }
+        const float idepth[4] = {0.8f, 0.0f, -1.0f, std::nanf("")};
+        uint16_t depth[4] = {1, 1, 1, 1}, half = 0;
+        const float one = 1.0f;
+        float back[4];
+        vors_to_depth(5000.0f, idepth, 4, depth);
+        vors_to_depth(2.5f, &one, 1, &half);
+        vors_from_depth(5000.0f, depth, 4, back);
+        if (depth[0] != 6250 || depth[1] != 65535 || depth[2] != 0 || depth[3] != 0 || half != 3 || back[0] != 0.8f || back[2] == back[2]) {
+            std::fprintf(stderr, "vors_to_depth / vors_from_depth failed: %u %u %u %u %u %g\n", depth[0], depth[1], depth[2], depth[3], half, back[0]);
+            return 1;
+        }
+    }
+
     if (vors_device_count() < 1) { std::printf("host_selftest: link ok, no GPU (skipping device part)\n"); return 77; }
     const int rows = 120, cols = 160;
     const double s = cols / 640.0;

@@ -102,6 +102,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_get_keyframe_image", "vors_batch_get_current_image", "vors_batch_get_points", "vors_batch_eval_level",
     "vors_batch_eval_pairs", "vors_batch_pose_information", "vors_pose_information_from_sums",
     "vors_batch_residual_maps", "vors_residual_scale_from_hist",
+    "vors_batch_reproject_depth", "vors_to_depth", "vors_from_depth",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -190,6 +191,10 @@ def lib():
         _lib.vors_pose_information_from_sums.argtypes = [vp, vp, vp, C.POINTER(f), C.POINTER(C.c_int32)]
         _lib.vors_batch_residual_maps.argtypes = [vp, i, i, vp, C.c_size_t, vp, vp, vp, vp, vp]
         _lib.vors_residual_scale_from_hist.argtypes = [vp, C.POINTER(f), C.POINTER(f), C.POINTER(C.c_uint32)]
+        _lib.vors_batch_reproject_depth.argtypes = [vp, i, i, vp, C.c_size_t, vp, f, vp, vp, vp, vp, vp]
+        for name in ("vors_to_depth", "vors_from_depth"):
+            getattr(_lib, name).argtypes = [f, vp, i, vp]
+            getattr(_lib, name).restype = None
         _lib.vors_lm_eval.argtypes = [C.POINTER(vors_obs), vp, C.POINTER(f), C.POINTER(C.c_int32), vp, vp, vp]
         _lib.vors_ref_sincos.argtypes = [vp, i, vp, vp]
         _lib.vors_ref_sincos.restype = None
@@ -599,6 +604,42 @@ class Batch:
             out["scale"] = t_scale
         return out
 
+    def reproject_depth(self, level, models, cur_depth=None, tol_m=0.0, pred_z=True, pred_depth=False, residual=False, counts=False):
+        """The keyframe's depth carried into the current frame at `models` ([n, 7] or a track's out_stats) with a z-buffer, and compared with
+        the measured current depth maps `cur_depth` ([n, rows, cols] int16 tensor holding the u16 payload, level 0 only)
+        (vors_batch_reproject_depth; needs prepare_keyframes only) -> dict of the requested tensors on the current stream, not synchronised:
+        "pred_z" [n, rows_l, cols_l] (current frame: nearest Z' in metres, +inf where no point lands), "pred_depth" [n, rows_l, cols_l]
+        (int16 tensor holding the u16 to_depth of pred_z, 0 where nothing lands; pred_z is made for it when not asked for), "residual"
+        [n, rows, cols] (keyframe geometry: Z' - cur_depth / depth_scale, NaN elsewhere), "counts" [n, 4] (int32: usable points, points
+        that land, those with a current depth, those with |residual| <= tol_m)."""
+        import torch
+        models, n, k, stride = self._models_arg(models)
+        if k != 1:
+            raise VorsError("reproject_depth takes one model per pair")
+        if not (pred_z or pred_depth or residual or counts):
+            raise VorsError("reproject_depth: nothing requested")
+        if cur_depth is not None and (cur_depth.dtype != torch.int16 or not cur_depth.is_contiguous() or
+                                      tuple(cur_depth.shape) != (n, self.rows, self.cols)):
+            raise VorsError(f"expected a contiguous int16 cur_depth [{n}, {self.rows}, {self.cols}], got {cur_depth.dtype} {tuple(cur_depth.shape)}")
+        rows, cols = self.rows >> int(level), self.cols >> int(level)
+        dev = models.device
+        t_z = torch.empty((n, rows, cols), dtype=torch.float32, device=dev) if (pred_z or pred_depth) else None
+        t_d = torch.empty((n, rows, cols), dtype=torch.int16, device=dev) if pred_depth else None
+        t_res = torch.empty((n, rows, cols), dtype=torch.float32, device=dev) if residual else None
+        t_cnt = torch.empty((n, 4), dtype=torch.int32, device=dev) if counts else None
+        _check(lib().vors_batch_reproject_depth(self._h, n, int(level), self._dp(models), stride, self._dp(cur_depth), float(tol_m), self._dp(t_z),
+                                                self._dp(t_d), self._dp(t_res), self._dp(t_cnt), self._stream()))
+        out = {}
+        if pred_z:
+            out["pred_z"] = t_z
+        if pred_depth:
+            out["pred_depth"] = t_d
+        if residual:
+            out["residual"] = t_res
+        if counts:
+            out["counts"] = t_cnt
+        return out
+
     def keyframe_image(self, pair, level):
         out = np.empty(self.rows * self.cols, np.uint8)
         r, c = C.c_int(), C.c_int()
@@ -833,6 +874,23 @@ def residual_scale_from_hist(hist):
     med, sig, n = C.c_float(), C.c_float(), C.c_uint32()
     _check(lib().vors_residual_scale_from_hist(_ptr(hist), C.byref(med), C.byref(sig), C.byref(n)))
     return np.float32(med.value), np.float32(sig.value), int(n.value)
+
+
+def to_depth(scale, idepth):
+    """inverse_depth.rs:37-42 for an array on the host (vors_to_depth; needs no GPU): round(scale / idepth), halves away from zero, converted
+    like Rust's `as u16` (NaN -> 0, <= 0 -> 0, >= 65535 -> 65535) -> uint16 array of idepth's shape."""
+    x = np.ascontiguousarray(idepth, np.float32)
+    out = np.empty(x.shape, np.uint16)
+    lib().vors_to_depth(float(scale), _ptr(x), x.size, _ptr(out))
+    return out
+
+
+def from_depth(scale, depth):
+    """inverse_depth.rs:24-29 for an array on the host (vors_from_depth): scale / depth, NaN (Unknown) where depth is 0 -> float32 array."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    out = np.empty(d.shape, np.float32)
+    lib().vors_from_depth(float(scale), _ptr(d), d.size, _ptr(out))
+    return out
 
 
 def ref_sincos(x):
