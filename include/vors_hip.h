@@ -115,7 +115,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               * 5: VORS_ARITH_* renumbered: 0 = REFERENCE (a zero-initialised vors_config reproduces the reference), 1 = EXACT, 2 = FUSED
                               *    (+ vors_selfcheck_isqrt, added without a signature change; + vors_batch_eval_pairs, vors_batch_pose_information,
                               *    vors_pose_information_from_sums, likewise additions; + vors_batch_residual_maps, vors_residual_scale_from_hist,
-                              *    likewise; + vors_batch_reproject_depth, vors_to_depth, vors_from_depth, likewise) */
+                              *    likewise; + vors_batch_reproject_depth, vors_to_depth, vors_from_depth, likewise; + vors_batch_point_cloud,
+                              *    vors_camera_back_project, vors_camera_project, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -439,6 +440,39 @@ vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, co
                                        float* d_pred_z, uint16_t* d_pred_depth, float* d_depth_residual, uint32_t* d_counts,
                                        void* hip_stream);
 
+/* POINT CLOUDS of a prepared batch, device-resident: the keyframe's usable points of level `level` as a LIST per pair, in 3-D, in a common
+ * frame — Camera::back_project (camera.rs:43-45): extrinsics::back_project(pose, intrinsics.back_project(point, depth)) — by an ordered,
+ * deterministic stream compaction. Needs vors_batch_prepare_keyframes ONLY (legal before any track_current); n_pairs <= the n_pairs of the
+ * last prepare.
+ * d_poses7 (DEVICE, nullable): 7 floats per pair, pose_stride_bytes apart (0 = 28; sizeof(vors_pair_stats) takes a d_out_stats array):
+ *   the keyframe camera -> world pose, Camera::extrinsics. NULL = identity for every pair: NO transform is applied, the camera-frame
+ *   bits come out untouched.
+ * d_keep (DEVICE, nullable) [n_pairs][rows_l * cols_l], keyframe geometry of the level: non-zero = keep; NULL keeps everything. The masks
+ *   of vors_batch_residual_maps / vors_batch_reproject_depth feed in here once the caller has thresholded them into bytes.
+ * The points of pair p are the usable points of the level (extract_z's set: what vors_batch_get_points returns and the planes above
+ * mark), with d_keep only those whose byte is non-zero, in ascending slot order of the level's source: dense mode = row-major raster
+ * order of the pixels; candidate lists = the order of vors_batch_get_points (which depends on the handle's arithmetic, see there). The
+ * order is a function of the pair's own data alone — never of scheduling or of the batch around the pair. For the point of rank
+ * i < capacity:
+ *   d_xyz   [n_pairs][capacity][3]  pose * back_project(K_level, (float)x, (float)y, 1.0f / idepth): the reference's per-point arithmetic,
+ *                                   the bits vors_camera_back_project gives for the same inputs (rows of 12 bytes)
+ *   d_pixel [n_pairs][capacity]     x | y << 16
+ *   d_gray  [n_pairs][capacity]     the template intensity of the level
+ *   d_counts[n_pairs]               the TOTAL number of points of the pair, which may exceed capacity
+ * Exactly the first min(count, capacity) entries of each list are written; the entries beyond them are left untouched. Every output is
+ * nullable, at least one must be given; capacity > 0 is required iff one of the three lists is given; d_counts alone runs only the
+ * counting pass. Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: no output at all, a level out of range, a negative capacity
+ * (or 0 with a list), n_pairs beyond the prepared count, a stream of another device.
+ * Contracts of vors_batch_residual_maps: enqueued on hip_stream, NOT synchronised; no allocation after the first call on a handle (the
+ * first call creates the per-(pair, chunk) count workspace, which vors_batch_workspace_bytes counts from then on); in dense mode the
+ * keyframe's d_kf_gray / d_kf_depth must still be alive; touches nothing track computes or reads; vors_trackers handles are out of
+ * scope. Two launches ordered by the stream; no workgroup waits for another and there is no atomic. */
+vors_status vors_batch_point_cloud(vors_batch* b, int n_pairs, int level,
+                                   const void* d_poses7 /* nullable */, size_t pose_stride_bytes,
+                                   const uint8_t* d_keep /* nullable */, int capacity,
+                                   float* d_xyz, uint32_t* d_pixel, uint8_t* d_gray, uint32_t* d_counts,
+                                   void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for
  *    `impl optimizer::State<Obs, EvalState, Iso3, String> for LMOptimizerState` (lm_optimizer.rs:111-193):
@@ -489,6 +523,12 @@ void vors_iso_inverse(const float a7[7], float out7[7]);
  * roundf(scale / idepth) — halves away from zero, f32::round — converted like Rust's `as u16`: NaN -> 0, <= 0 -> 0, >= 65535 -> 65535. */
 void vors_to_depth(float scale, const float* idepth, int n, uint16_t* depth_out);
 void vors_from_depth(float scale, const uint16_t* depth, int n, float* idepth_out);
+/* Camera::back_project and Camera::project for arrays (host arithmetic; cam5 = cu cv fu fv skew, pose7 = camera -> world, NULL =
+ * identity: no transform at all). back_project: pose * intrinsics.back_project((x, y), depth) (camera.rs:43-45, 75-77, 135-140), the text
+ * vors_batch_point_cloud runs per point. project: intrinsics.project(rotation.inverse() * (translation.inverse() * point))
+ * (camera.rs:36-39, 70-72, 126-132) -> homogeneous (u w, v w, w), no division. xy [2n], depth [n], xyz [3n], uvw [3n]; n = 0 is legal. */
+void vors_camera_back_project(const float cam5[5], const float pose7[7] /* nullable */, const float* xy, const float* depth, int n, float* xyz_out);
+void vors_camera_project(const float cam5[5], const float pose7[7] /* nullable */, const float* xyz, int n, float* uvw_out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 5. Synthetic scene renderer on the device (bench/test tooling). Renders, for pair i in

@@ -769,6 +769,63 @@ vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, co
     return VORS_OK;
 }
 
+// The count workspace of the point-cloud pass ([max_pairs][most chunks of a level] integers): created by the first call and counted by
+// vors_batch_workspace_bytes from then on, like the evaluation workspace above.
+static vors_status ensure_point_cloud_ws(vors_batch* b) {
+    if (b->cloud_counts) return VORS_OK;
+    int chunks = 1;
+    for (int l = 0; l < b->g.L; ++l) chunks = std::max(chunks, eval_pairs_chunks(b->g, l));
+    b->own.alloc(&b->cloud_counts, (size_t)b->max_pairs * chunks);
+    if (b->own.err != hipSuccess) {
+        const hipError_t e = b->own.err;
+        b->own.err = hipSuccess;
+        (void)hipGetLastError();
+        b->cloud_counts = nullptr;
+        return fail(VORS_ERR_HIP, std::string("hipMalloc (point-cloud workspace): ") + hipGetErrorString(e));
+    }
+    b->cloud_chunks = chunks;
+    return VORS_OK;
+}
+
+vors_status vors_batch_point_cloud(vors_batch* b, int n_pairs, int level, const void* d_poses7, size_t pose_stride_bytes, const uint8_t* d_keep,
+                                   int capacity, float* d_xyz, uint32_t* d_pixel, uint8_t* d_gray, uint32_t* d_counts, void* hip_stream) {
+    if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: the handle b is NULL");
+    const bool lists = d_xyz || d_pixel || d_gray;
+    if (!lists && !d_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: every output (d_xyz, d_pixel, d_gray, d_counts) is NULL");
+    if (capacity < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: negative capacity");
+    if (lists && capacity == 0) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: d_xyz / d_pixel / d_gray need capacity > 0");
+    if (pose_stride_bytes != 0 && (pose_stride_bytes % 4 != 0 || pose_stride_bytes < 28 || pose_stride_bytes > (1u << 20)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: pose_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    // the keyframe side alone, like reproject_depth: legal before any track_current
+    if (b->prepared_pairs <= 0 || !b->kf_level0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, b->prepared_pairs > 0 ? "point_cloud is not available on a trackers-owned batch (the handle keeps records, not frames)"
+                                                                     : "point_cloud needs prepare_keyframes first");
+    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
+    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: level out of range");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    vors_status st = check_stream(b, s);
+    if (st != VORS_OK) return st;
+    if ((st = ensure_point_cloud_ws(b)) != VORS_OK) return st;
+    PointCloudCall call{{Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    call.n_pairs = n_pairs;
+    call.lvl = level;
+    call.poses = static_cast<const float*>(d_poses7);
+    call.pose_stride = pose_stride_bytes ? (int)(pose_stride_bytes / 4) : 7;
+    call.keep = d_keep;
+    call.capacity = capacity;
+    call.xyz = d_xyz;
+    call.pixel = d_pixel;
+    call.gray = d_gray;
+    call.counts = d_counts;
+    call.ws = b->cloud_counts;
+    call.ws_chunks = b->cloud_chunks;
+    launch_lm_point_cloud(b->g, call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host-buffer batch entry
 // ---------------------------------------------------------------------------------------------------------------

@@ -329,6 +329,37 @@ struct ReprojectArgs {
     uint32_t* counts;
     int wide_stores;            // the residual plane is 16-byte aligned: a dense quad stores 16 bytes at a time
 };
+// Point clouds of one level per pair of a prepared batch (vors_batch_point_cloud): the usable points of the level, compacted in ascending
+// slot order into lists of `capacity` entries per pair, back-projected and carried to the world frame by one pose per pair. Every output
+// is nullable; `ws` is the handle's [pair][ws_chunks] count workspace.
+struct PointCloudCall : LmScene {
+    int n_pairs, lvl;
+    const float* poses;         // camera -> world, nullable = identity (no transform at all)
+    int pose_stride;            // floats
+    const uint8_t* keep;        // [pair][rows_l * cols_l], nullable = keep everything
+    int capacity;
+    float* xyz;                 // [pair][capacity][3]
+    uint32_t* pixel;            // [pair][capacity] x | y << 16
+    uint8_t* gray;              // [pair][capacity]
+    uint32_t* counts;           // [pair]
+    uint32_t* ws;
+    int ws_chunks;
+};
+// What the kernels of one slice of pairs get.
+struct PointCloudArgs {
+    int pair0, lvl, chunk_points;
+    const float* poses;
+    int pose_stride;
+    const uint8_t* keep;
+    int capacity;
+    float* xyz;
+    uint32_t* pixel;
+    uint8_t* gray;
+    uint32_t* counts;
+    uint32_t* ws;
+    int ws_chunks;
+    int wide_keep;              // the mask planes are 4-byte aligned: a dense quad reads its four bytes at once
+};
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }
@@ -416,6 +447,10 @@ void launch_lm_residual_maps(const Geom& g, const ResidualMapsCall& call, hipStr
 // current depth and the four counts, in the reference's per-point arithmetic whatever the handle's (lm_kernels.hip
 // lm_reproject_depth_kernel, pred_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
 void launch_lm_reproject_depth(const Geom& g, const ReprojectCall& call, hipStream_t s);
+// Ordered stream compaction of the usable (and kept) points of one level per pair into point lists in the world frame (lm_kernels.hip
+// point_cloud_kernel: a counting launch into call.ws, then a ranking and writing launch; no workgroup waits for another): enqueued, not
+// synchronised. Reads no current image.
+void launch_lm_point_cloud(const Geom& g, const PointCloudCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

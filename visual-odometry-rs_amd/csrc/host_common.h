@@ -149,6 +149,8 @@ struct vors_batch {
     vors::Records rec{};
     vors::LmSplitWs split{};
     vors::EvalPairsWs eval_pairs{};  // vors_batch_eval_pairs / _pose_information: allocated by the first of those calls (items = 0 until then)
+    uint32_t* cloud_counts = nullptr;  // vors_batch_point_cloud: [max_pairs][cloud_chunks] kept points per chunk, allocated by its first call
+    int cloud_chunks = 0;
     int lm_block = 256;  // threads per frame pair in the LM kernel (256 / 512 / 1024)
     vors::RefDevice ref_device;  // REFERENCE arithmetic: what the device offers the workgroup-per-pair kernel
     // generic-mask (DSO) mode workspaces

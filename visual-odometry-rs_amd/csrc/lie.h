@@ -347,6 +347,15 @@ VORS_HD void project_uv(const Intr& k, const V3& p, float* u, float* v) {
     *u = pu / p.z;
     *v = pv / p.z;
 }
+// Intrinsics::project, camera.rs:126-132: the homogeneous image point (no perspective division).
+VORS_HD V3 intr_project(const Intr& k, const V3& p) {
+    return V3{(k.fu * p.x + k.skew * p.y) + k.cu * p.z, k.fv * p.y + k.cv * p.z, p.z};
+}
+// extrinsics::project, camera.rs:70-72: world -> camera, rotation.inverse() * (translation.inverse() * point).
+VORS_HD V3 extr_project(const Iso& pose, const V3& p) {
+    const Quat qi{-pose.q.i, -pose.q.j, -pose.q.k, pose.q.w};
+    return quat_rotate(qi, V3{p.x + -pose.t.x, p.y + -pose.t.y, p.z + -pose.t.z});
+}
 // Jacobian of the warp: src/core/track/inverse_compositional.rs:313-341.
 VORS_HD void warp_jacobian_at(float gu, float gv, float u, float v, float _z, const Intr& k, float J[6]) {
     const float a = u - k.cu;

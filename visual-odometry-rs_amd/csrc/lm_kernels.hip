@@ -2631,6 +2631,253 @@ void launch_lm_reproject_depth(const Geom& g_in, const ReprojectCall& call, hipS
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// vors_batch_point_cloud: the usable points of a level as a LIST per pair — an ordered, deterministic stream compaction — back-projected
+// (the Pos the LM kernels warp from, camera.rs:135-140) and carried to the world frame by one pose per pair (iso_transform_point). Grid,
+// cut of a level and sources are lm_residual_maps_kernel's. Rank order is ascending SLOT order of the level's source: the dense sources
+// give a thread one unit of G adjacent pixels (slots G i .. G i + G - 1 of unit i = first + k BLOCK + t in iteration k), the candidate
+// lists give it the slots i and i + BLOCK (i = first + 2 k BLOCK + t) — two interleaved runs, ranked one after the other.
+// Two launches, ordered by the stream alone (no workgroup ever waits for another, no atomic anywhere):
+//   COUNT  every workgroup STORES the number of kept points of its chunk to ws[pair][chunk] (0 for a chunk the pair does not use);
+//   WRITE  every workgroup adds up the counts of the chunks before its own (a uniform loop over at most a few dozen integers; chunk 0
+//          also stores the total to d_counts), then repeats the sweep with the loop made UNIFORM over the workgroup — a lane past the end
+//          holds no point — and ranks: ballots of the G flags + mbcnt for the wavefront prefix, the four wavefront totals through LDS
+//          (two slots used in turn: one barrier per scan), a running base across the iterations. Points of rank < capacity are stored; a
+//          workgroup whose base has reached the capacity stops.
+// With d_counts alone, COUNT and a one-thread-per-pair sum.
+// ------------------------------------------------------------------------------------------------------------
+#define PCLOUD_WAVES (RMAPS_BLOCK / 64)
+template <bool LEVEL0>
+__device__ __forceinline__ uint32_t cloud_xy(const DenseSrc<LEVEL0>&, const typename DenseSrc<LEVEL0>::Raw& r, int) {
+    return (uint32_t)r.x | ((uint32_t)r.y << 16);
+}
+template <bool LEVEL0, bool FAST>
+__device__ __forceinline__ uint32_t cloud_xy(const DenseQuadSrc<LEVEL0, FAST>&, const typename DenseQuadSrc<LEVEL0, FAST>::Raw& r, int g) {
+    return (uint32_t)(r.x0 + g) | ((uint32_t)r.y << 16);
+}
+__device__ __forceinline__ uint32_t cloud_xy(const SlimSrc&, const SlimSrc::Raw& r, int g) { return r.r[g].xy; }
+// The points of one unit: kept = usable (extract_z's set) and not masked away. A cursor past `last` holds none (and loads nothing).
+template <int G>
+struct CloudPts {
+    V3 P[G];
+    uint32_t xy[G];
+    float tmpl[G];
+    bool kept[G];
+};
+template <class Src>
+__device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::Cursor& cur, int last, int cols, const uint8_t* keep, bool wide_keep,
+                                            CloudPts<Src::G>& o) {
+    constexpr int G = Src::G;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        o.P[g] = V3{0.f, 0.f, 0.f};
+        o.xy[g] = 0;
+        o.tmpl[g] = -1.f;
+        o.kept[g] = false;
+    }
+    if (cur.i >= last) return;
+    typename Src::Raw raw;
+    src.template fetch<RMAPS_BLOCK>(cur, last, raw);
+    Pos pos[G];
+    src.positions(raw, pos);
+    uint32_t kb[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) kb[g] = 1;
+    if (keep) {  // (uniform)
+        bool done = false;
+        if constexpr (G == 4) {
+            if (wide_keep) {  // (uniform) a quad owns four adjacent pixels of one row, 4-byte aligned in the mask plane
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + (unsigned)plane_pixel(src, raw, 0, cols));
+#pragma unroll
+                for (int g = 0; g < G; ++g) kb[g] = (w >> (8 * g)) & 0xffu;
+                done = true;
+            }
+        }
+        if (!done) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const int px = plane_pixel(src, raw, g, cols);
+                kb[g] = keep[(unsigned)max(px, 0)];  // (a lane past the end of a list reads byte 0 and is no point anyway)
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        o.P[g] = V3{pos[g].X, pos[g].Y, pos[g].Z};
+        o.xy[g] = cloud_xy(src, raw, g);
+        o.tmpl[g] = pos[g].tmpl;
+        o.kept[g] = pos[g].tmpl >= 0.f && kb[g] != 0;
+    }
+}
+template <class Src>
+__device__ __forceinline__ uint32_t cloud_count_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep) {
+    constexpr int G = Src::G;
+    uint32_t n = 0;
+    for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
+        CloudPts<G> pts;
+        cloud_fetch(src, cur, last, cols, keep, wide_keep, pts);
+#pragma unroll
+        for (int g = 0; g < G; ++g) n += pts.kept[g] ? 1u : 0u;
+    }
+    return n;
+}
+// Number of set flags before this thread's first one, over the workgroup in thread order (thread t's N flags are adjacent), and the
+// workgroup's total. Every thread of the workgroup calls it; `par` alternates between calls (the LDS slot in use).
+template <int N>
+__device__ __forceinline__ uint32_t cloud_block_rank(const bool* f, uint32_t* lds, int par, uint32_t* total) {
+    uint32_t pre = 0, wt = 0;
+#pragma unroll
+    for (int g = 0; g < N; ++g) {
+        const unsigned long long m = __ballot(f[g]);
+        pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        wt += (uint32_t)__popcll(m);
+    }
+    const int wave = threadIdx.x >> 6;
+    uint32_t* slot = lds + par * PCLOUD_WAVES;
+    if ((threadIdx.x & 63) == 0) slot[wave] = wt;
+    __syncthreads();
+    uint32_t t = 0;
+#pragma unroll
+    for (int w = 0; w < PCLOUD_WAVES; ++w) {
+        const uint32_t c = slot[w];
+        pre += w < wave ? c : 0u;
+        t += c;
+    }
+    *total = t;
+    return pre;
+}
+struct CloudOut {
+    Iso pose;
+    bool has_pose;
+    uint32_t capacity;
+    float* xyz;
+    uint32_t* pixel;
+    uint8_t* gray;
+};
+__device__ __forceinline__ void cloud_store(const CloudOut& o, uint32_t rank, const V3& P, uint32_t xy, float tmpl) {
+    if (o.xyz) {  // (uniform) rows of 12 bytes: three dword stores, consecutive ranks are consecutive addresses
+        const V3 w = o.has_pose ? iso_transform_point(o.pose, P) : P;
+        float* x = o.xyz + 3 * (size_t)rank;
+        x[0] = w.x;
+        x[1] = w.y;
+        x[2] = w.z;
+    }
+    if (o.pixel) o.pixel[rank] = xy;
+    if (o.gray) o.gray[rank] = (uint8_t)(int)tmpl;
+}
+template <class Src>
+__device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep, uint32_t base,
+                                                  const CloudOut& out, uint32_t* lds) {
+    constexpr int G = Src::G;
+    static_assert(G != 2 || std::is_same<Src, SlimSrc>::value, "G = 2 is the candidate lists' interleaved pair of slots");
+    int par = 0;
+    for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first);
+         __builtin_amdgcn_readfirstlane(cur.i - (int)threadIdx.x) < last && base < out.capacity; cur = src.template advance<RMAPS_BLOCK>(cur)) {
+        CloudPts<G> pts;
+        cloud_fetch(src, cur, last, cols, keep, wide_keep, pts);
+        if constexpr (G == 2) {  // slots i and i + BLOCK: the first points of all threads come before the second ones
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                uint32_t total;
+                const uint32_t rank = base + cloud_block_rank<1>(&pts.kept[g], lds, par, &total);
+                par ^= 1;
+                if (pts.kept[g] && rank < out.capacity) cloud_store(out, rank, pts.P[g], pts.xy[g], pts.tmpl[g]);
+                base += total;
+            }
+        } else {
+            uint32_t total;
+            uint32_t rank = base + cloud_block_rank<G>(pts.kept, lds, par, &total);
+            par ^= 1;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                if (pts.kept[g] && rank < out.capacity) cloud_store(out, rank, pts.P[g], pts.xy[g], pts.tmpl[g]);
+                rank += pts.kept[g] ? 1u : 0u;
+            }
+            base += total;
+        }
+    }
+}
+template <bool DENSE, bool WRITE>
+__global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                  const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                  const uint16_t* __restrict__ kf_depth, Records rec, PointCloudArgs a) {
+    __shared__ uint32_t lds[2 * PCLOUD_WAVES];
+    const int pair = a.pair0 + blockIdx.y, chunk = blockIdx.x, n_chunks = gridDim.x;
+    const int cols = g.lv[a.lvl].cols;
+    const size_t plane = (size_t)g.lv[a.lvl].rows * cols;
+    const uint8_t* keep = a.keep ? a.keep + (size_t)pair * plane : nullptr;
+    uint32_t* ws = a.ws + (size_t)pair * a.ws_chunks;
+    uint32_t base = 0, n = 0;
+    CloudOut out{};
+    if constexpr (WRITE) {
+        uint32_t total = 0;
+        for (int k = 0; k < n_chunks; ++k) {  // (uniform)
+            const uint32_t c = ws[k];
+            base += k < chunk ? c : 0u;
+            total += c;
+        }
+        if (chunk == 0 && threadIdx.x == 0 && a.counts) a.counts[pair] = total;
+        out.has_pose = a.poses != nullptr;
+        out.pose = out.has_pose ? iso_uniform(iso_load(a.poses + (size_t)pair * a.pose_stride)) : iso_identity();
+        out.capacity = (uint32_t)a.capacity;
+        out.xyz = a.xyz ? a.xyz + (size_t)pair * a.capacity * 3 : nullptr;
+        out.pixel = a.pixel ? a.pixel + (size_t)pair * a.capacity : nullptr;
+        out.gray = a.gray ? a.gray + (size_t)pair * a.capacity : nullptr;
+    }
+    with_level_source<DENSE, true, false>(g, a.lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // this pair's chunks at this level, cut like lm_eval_pairs_kernel's (a short candidate list needs fewer than the grid has)
+        const int points = DENSE ? g.lv[a.lvl].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        if constexpr (WRITE) cloud_write_sweep(src, first, last, cols, keep, a.wide_keep != 0, base, out, lds);
+        else n = cloud_count_sweep(src, first, last, cols, keep, a.wide_keep != 0);
+    });
+    if constexpr (!WRITE) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int wv = 0; wv < PCLOUD_WAVES; ++wv) t += lds[wv];
+            ws[chunk] = t;  // stored, not accumulated: the workspace needs no clearing
+        }
+    }
+}
+// counts alone: the chunk counts of a pair added up, one thread per pair
+__global__ __launch_bounds__(64) void point_cloud_total_kernel(const uint32_t* __restrict__ ws, int ws_chunks, int chunks, int pair0, int n,
+                                                               uint32_t* __restrict__ counts) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    uint32_t t = 0;
+    for (int k = 0; k < chunks; ++k) t += ws[(size_t)(pair0 + p) * ws_chunks + k];
+    counts[pair0 + p] = t;
+}
+void launch_lm_point_cloud(const Geom& g_in, const PointCloudCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const bool dense = g.mode == VORS_CANDIDATES_DENSE;
+    const bool write = call.xyz || call.pixel || call.gray;
+    const size_t plane = (size_t)g.lv[call.lvl].rows * g.lv[call.lvl].cols;
+    PointCloudArgs a{0, call.lvl, eval_pairs_chunk_points(g), call.poses, call.pose_stride, call.keep, call.capacity, call.xyz, call.pixel,
+                     call.gray, call.counts, call.ws, call.ws_chunks, ((uintptr_t)call.keep % 4 == 0 && plane % 4 == 0) ? 1 : 0};
+    const int chunks = std::min(eval_pairs_chunks(g, call.lvl), call.ws_chunks);
+    for (int pair0 = 0; pair0 < call.n_pairs; pair0 += 32768) {  // (the y extent of a grid)
+        a.pair0 = pair0;
+        const int np = std::min(32768, call.n_pairs - pair0);
+        with_bool(dense, [&](auto d) {
+            launch_on_scene(point_cloud_kernel<decltype(d)::value, false>, dim3(chunks, np), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+            if (write) launch_on_scene(point_cloud_kernel<decltype(d)::value, true>, dim3(chunks, np), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+        });
+        if (!write && call.counts)
+            hipLaunchKernelGGL(point_cloud_total_kernel, dim3((np + 63) / 64), dim3(64), 0, s, call.ws, call.ws_chunks, chunks, pair0, np, call.counts);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // Operator level (one pyramid level, explicit observations)
 // ------------------------------------------------------------------------------------------------------------
 #define OP_BLOCK 256

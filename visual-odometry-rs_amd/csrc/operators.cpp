@@ -203,6 +203,25 @@ void vors_to_depth(float scale, const float* idepth, int n, uint16_t* depth_out)
 void vors_from_depth(float scale, const uint16_t* depth, int n, float* idepth_out) {
     for (int i = 0; i < n; ++i) idepth_out[i] = depth[i] ? scale / (float)depth[i] : nanf("");  // inverse_depth.rs:24-29, Unknown = NaN
 }
+// Camera::back_project / Camera::project (camera.rs:43-45, 36-39) for arrays: the texts the point-cloud kernel runs (lie.h back_project,
+// iso_transform_point). A NULL pose is the identity and skips the transform, so the camera-frame bits come out untouched.
+void vors_camera_back_project(const float cam5[5], const float pose7[7], const float* xy, const float* depth, int n, float* xyz_out) {
+    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    for (int i = 0; i < n; ++i) {
+        V3 p = back_project(k, xy[2 * i], xy[2 * i + 1], depth[i]);
+        if (pose7) p = iso_transform_point(iso_load(pose7), p);
+        xyz_out[3 * i] = p.x; xyz_out[3 * i + 1] = p.y; xyz_out[3 * i + 2] = p.z;
+    }
+}
+void vors_camera_project(const float cam5[5], const float pose7[7], const float* xyz, int n, float* uvw_out) {
+    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    for (int i = 0; i < n; ++i) {
+        V3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+        if (pose7) p = extr_project(iso_load(pose7), p);
+        const V3 w = intr_project(k, p);
+        uvw_out[3 * i] = w.x; uvw_out[3 * i + 1] = w.y; uvw_out[3 * i + 2] = w.z;
+    }
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // synthetic scenes

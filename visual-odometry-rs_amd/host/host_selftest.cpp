@@ -62,6 +62,27 @@ int main() {
         }
     }
 
+    // ... and of the point clouds: a NULL handle is refused before a device is touched; Camera::back_project / project are host arithmetic
+    // (pixel (cu, cv) at depth 2 is (0, 0, 2); a NULL pose is the identity; project returns (u w, v w, w))
+    {
+        if (vors_batch_point_cloud(nullptr, 1, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr) != VORS_ERR_INVALID_ARGUMENT) {
+            std::fprintf(stderr, "vors_batch_point_cloud accepted a NULL handle\n");
+            return 1;
+        }
+        const float cam5[5] = {320.0f, 240.0f, 500.0f, 500.0f, 0.0f}, xy[4] = {320.0f, 240.0f, 820.0f, 240.0f}, depth[2] = {2.0f, 0.5f};
+        const float shift[7] = {1.0f, -2.0f, 3.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+        float cam_pts[6], world[6], uvw[6];
+        vors_camera_back_project(cam5, nullptr, xy, depth, 2, cam_pts);
+        vors_camera_back_project(cam5, shift, xy, depth, 2, world);
+        vors_camera_project(cam5, shift, world, 2, uvw);
+        if (cam_pts[0] != 0.0f || cam_pts[1] != 0.0f || cam_pts[2] != 2.0f || cam_pts[3] != 0.5f || cam_pts[5] != 0.5f || world[0] != 1.0f ||
+            world[1] != -2.0f || world[2] != 5.0f || uvw[0] != 640.0f || uvw[2] != 2.0f || uvw[3] != 410.0f || uvw[5] != 0.5f) {
+            std::fprintf(stderr, "vors_camera_back_project / vors_camera_project failed: %g %g %g | %g %g %g | %g %g %g\n", cam_pts[3], cam_pts[4], cam_pts[5],
+                         world[0], world[1], world[2], uvw[3], uvw[4], uvw[5]);
+            return 1;
+        }
+    }
+
     if (vors_device_count() < 1) { std::printf("host_selftest: link ok, no GPU (skipping device part)\n"); return 77; }
     const int rows = 120, cols = 160;
     const double s = cols / 640.0;

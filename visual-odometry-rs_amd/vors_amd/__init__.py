@@ -103,6 +103,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_eval_pairs", "vors_batch_pose_information", "vors_pose_information_from_sums",
     "vors_batch_residual_maps", "vors_residual_scale_from_hist",
     "vors_batch_reproject_depth", "vors_to_depth", "vors_from_depth",
+    "vors_batch_point_cloud", "vors_camera_back_project", "vors_camera_project",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -195,6 +196,11 @@ def lib():
         for name in ("vors_to_depth", "vors_from_depth"):
             getattr(_lib, name).argtypes = [f, vp, i, vp]
             getattr(_lib, name).restype = None
+        _lib.vors_batch_point_cloud.argtypes = [vp, i, i, vp, C.c_size_t, vp, i, vp, vp, vp, vp, vp]
+        _lib.vors_camera_back_project.argtypes = [vp, vp, vp, vp, i, vp]
+        _lib.vors_camera_back_project.restype = None
+        _lib.vors_camera_project.argtypes = [vp, vp, vp, i, vp]
+        _lib.vors_camera_project.restype = None
         _lib.vors_lm_eval.argtypes = [C.POINTER(vors_obs), vp, C.POINTER(f), C.POINTER(C.c_int32), vp, vp, vp]
         _lib.vors_ref_sincos.argtypes = [vp, i, vp, vp]
         _lib.vors_ref_sincos.restype = None
@@ -640,6 +646,63 @@ class Batch:
             out["counts"] = t_cnt
         return out
 
+    def point_cloud(self, level, poses=None, keep=None, capacity=None, xyz=True, pixel=True, gray=False, counts=True, n_pairs=None):
+        """The usable points of `level` of every pair as lists in the world frame (vors_batch_point_cloud; needs prepare_keyframes only) ->
+        dict of the requested tensors on the current stream, not synchronised: "xyz" [n, capacity, 3] (poses * back_project of each point;
+        `poses` [n, 7] float32 or a track's out_stats, camera -> world, None = identity), "pixel" [n, capacity] (int32: x | y << 16), "gray"
+        [n, capacity] (uint8), "counts" [n] (int32: the total per pair, which may exceed capacity). Only the first min(count, capacity)
+        entries of a list are written. `keep` [n, rows_l, cols_l] uint8: non-zero keeps the pixel's point. capacity None = rows_l * cols_l.
+        xyz / pixel / gray / counts may also be a tensor of that shape to write into (its other entries stay as they are). n is `n_pairs`,
+        else the rows of poses, else of keep, else the pairs of the last prepare_keyframes."""
+        import torch
+        lvl = int(level)
+        rows, cols = self.rows >> lvl, self.cols >> lvl
+        stride = 0
+        if poses is not None:
+            poses, n, k, stride = self._models_arg(poses)
+            if k != 1:
+                raise VorsError("point_cloud takes one pose per pair")
+        elif keep is not None:
+            n = keep.shape[0]
+        else:
+            refs = getattr(self, "_kf_refs", None)
+            if refs is None:
+                raise VorsError("point_cloud needs prepare_keyframes first")
+            n = refs[0].shape[0]
+        if n_pairs is not None:
+            if int(n_pairs) > n:
+                raise VorsError(f"point_cloud: n_pairs {n_pairs} exceeds the {n} poses / masks given")
+            n = int(n_pairs)
+        if keep is not None and (keep.dtype != torch.uint8 or not keep.is_contiguous() or keep.shape[0] < n or tuple(keep.shape[1:]) != (rows, cols)):
+            raise VorsError(f"expected a contiguous uint8 keep [{n}, {rows}, {cols}], got {keep.dtype} {tuple(keep.shape)}")
+        cap = rows * cols if capacity is None else int(capacity)
+        lists = any(o is not False and o is not None for o in (xyz, pixel, gray))
+        if not lists and (counts is False or counts is None):
+            raise VorsError("point_cloud: nothing requested")
+        refs = getattr(self, "_kf_refs", None)
+        dev = poses.device if poses is not None else keep.device if keep is not None else refs[0].device if refs else torch.device("cuda")
+
+        def buf(o, shape, dtype):
+            if o is False or o is None:
+                return None
+            if o is True:
+                return torch.empty(shape, dtype=dtype, device=dev)
+            if o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shape):
+                raise VorsError(f"expected a contiguous {dtype} output {tuple(shape)}, got {o.dtype} {tuple(o.shape)}")
+            return o
+
+        t_xyz = buf(xyz, (n, cap, 3), torch.float32)
+        t_pix = buf(pixel, (n, cap), torch.int32)
+        t_gray = buf(gray, (n, cap), torch.uint8)
+        t_cnt = buf(counts, (n,), torch.int32)
+        _check(lib().vors_batch_point_cloud(self._h, n, lvl, self._dp(poses), stride, self._dp(keep), cap, self._dp(t_xyz), self._dp(t_pix),
+                                            self._dp(t_gray), self._dp(t_cnt), self._stream()))
+        out = {}
+        for name, t in (("xyz", t_xyz), ("pixel", t_pix), ("gray", t_gray), ("counts", t_cnt)):
+            if t is not None:
+                out[name] = t
+        return out
+
     def keyframe_image(self, pair, level):
         out = np.empty(self.rows * self.cols, np.uint8)
         r, c = C.c_int(), C.c_int()
@@ -890,6 +953,34 @@ def from_depth(scale, depth):
     d = np.ascontiguousarray(depth, np.uint16)
     out = np.empty(d.shape, np.float32)
     lib().vors_from_depth(float(scale), _ptr(d), d.size, _ptr(out))
+    return out
+
+
+def camera_back_project(cam5, pose7, xy, depth):
+    """Camera::back_project for arrays on the host (vors_camera_back_project; needs no GPU): pose7 * intrinsics.back_project(xy, depth) with
+    cam5 = (cu, cv, fu, fv, skew), pose7 camera -> world or None (identity, no transform), xy [n, 2], depth [n] -> float32 [n, 3]. The
+    arithmetic Batch.point_cloud runs per point."""
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    d = np.ascontiguousarray(depth, np.float32).reshape(-1)
+    if k.shape != (5,) or (pose is not None and pose.shape != (7,)) or len(d) != len(xy):
+        raise VorsError("camera_back_project: cam5 [5], pose7 [7] or None, xy [n, 2], depth [n]")
+    out = np.empty((len(xy), 3), np.float32)
+    lib().vors_camera_back_project(_ptr(k), _ptr(pose), _ptr(xy), _ptr(d), len(xy), _ptr(out))
+    return out
+
+
+def camera_project(cam5, pose7, xyz):
+    """Camera::project for arrays on the host (vors_camera_project): intrinsics.project(rotation^-1 * (translation^-1 * point)) -> float32
+    [n, 3] homogeneous (u w, v w, w); pose7 None = identity (no transform)."""
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    if k.shape != (5,) or (pose is not None and pose.shape != (7,)):
+        raise VorsError("camera_project: cam5 [5], pose7 [7] or None, xyz [n, 3]")
+    out = np.empty((len(p), 3), np.float32)
+    lib().vors_camera_project(_ptr(k), _ptr(pose), _ptr(p), len(p), _ptr(out))
     return out
 
 
