@@ -116,7 +116,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    (+ vors_selfcheck_isqrt, added without a signature change; + vors_batch_eval_pairs, vors_batch_pose_information,
                               *    vors_pose_information_from_sums, likewise additions; + vors_batch_residual_maps, vors_residual_scale_from_hist,
                               *    likewise; + vors_batch_reproject_depth, vors_to_depth, vors_from_depth, likewise; + vors_batch_point_cloud,
-                              *    vors_camera_back_project, vors_camera_project, likewise) */
+                              *    vors_camera_back_project, vors_camera_project, likewise; + vors_batch_fuse_depth, vors_fuse_depth_pixels,
+                              *    likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -472,6 +473,57 @@ vors_status vors_batch_point_cloud(vors_batch* b, int n_pairs, int level,
                                    const uint8_t* d_keep /* nullable */, int capacity,
                                    float* d_xyz, uint32_t* d_pixel, uint8_t* d_gray, uint32_t* d_counts,
                                    void* hip_stream);
+
+/* DEPTH FUSION of a prepared batch, device-resident: the keyframe's depth carried into the current frame and MERGED with the depth the
+ * sensor measured there, into a depth map and a weight map in the current frame's geometry — the maps the caller hands to the next
+ * vors_batch_prepare_keyframes (the depth) and to the next fuse call (the weight): a recursive per-pixel depth filter around a tracker
+ * that otherwise drops all depth knowledge of the old keyframe the moment a new frame is promoted. Level 0 only (depth maps exist at full
+ * resolution only). Needs vors_batch_prepare_keyframes ONLY; n_pairs <= the n_pairs of the last prepare. d_models / model_stride_bytes as in
+ * vors_batch_reproject_depth (DEVICE, 7 floats each; 0 = 28; sizeof(vors_pair_stats) takes the d_out_stats array of the last track).
+ * SPLAT. The points are the usable points of level 0 (extract_z's set) whose d_kf_weight byte is non-zero; d_kf_weight (DEVICE, nullable)
+ *   [n_pairs][rows * cols] in KEYFRAME geometry, NULL = weight 1 everywhere; a zero byte removes the point, so the plane doubles as a keep
+ *   mask. Each point is warped and LANDS by the rule of vors_batch_reproject_depth, unchanged (Z' > 0, floorf(u + 0.5f), floorf(v + 0.5f)
+ *   inside the window, all compares in float), at the pixel q of the CURRENT frame.
+ *   d_zkey [n_pairs][rows * cols] (DEVICE, REQUIRED, 8-byte aligned; the pass keeps no plane of its own): the minimum over the points
+ *   landing at q of (uint64)bits(Z') << 32 | src, src = y * cols + x of the keyframe pixel; VORS_ZKEY_EMPTY where no point lands. The
+ *   nearest surface wins, among equal Z' bits the smallest source index: a minimum, bitwise reproducible whatever the order of arrival.
+ *   key >> 32 has the bits of d_pred_z; the plane is an output in its own right, a current -> keyframe correspondence map.
+ * MERGE, per current pixel q, with has_p = key != VORS_ZKEY_EMPTY, zp = the float of bits key >> 32, wk = d_kf_weight ?
+ *   d_kf_weight[key & 0xFFFFFFFF] : 1, d = d_cur_depth[q], has_m = d != 0, r = zp - (float)d / depth_scale (the depth residual's text):
+ *     case                              condition                                   fused depth                    fused weight          counter
+ *     agree                             has_p && has_m && fabsf(r) <= tol_m         to_depth(scale, MEAN)          min(wk + 1, max_weight)  0
+ *     conflict, prediction in front     has_p && has_m && r < -tol_m                d                              1                        1
+ *     conflict, prediction behind       has_p && has_m && r > tol_m                 d                              1                        2
+ *     measured only                     !has_p && has_m                             d                              1                        3
+ *     filled                            has_p && !has_m && fill_min_weight > 0      to_depth(scale, 1.0f / zp)     wk                       4
+ *                                         && wk >= fill_min_weight                  (the bits of d_pred_depth)
+ *     empty                             everything else                             0                              0                        5
+ *   MEAN = ((float)wk * (1.0f / zp) + depth_scale / (float)d) / ((float)wk + 1.0f): the weighted mean in INVERSE depth, the measurement
+ *   inverted exactly as vors_from_depth does (scale / (float)d), in this expression order on host and device. A fused depth that rounds to
+ *   0 (a surface nearer than half a depth unit) gets weight 0: a depth of 0 and a weight of 0 always coincide.
+ *   d_fused_depth [n_pairs][rows * cols] u16, d_fused_weight [n_pairs][rows * cols] u8, d_counts [n_pairs][VORS_FUSE_COUNTS] (the six
+ *   counters of a pair add up to rows * cols): DEVICE, each nullable. d_zkey alone is legal: the pass is then only the splat.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: NULL b, d_models, d_cur_depth or d_zkey; a misaligned d_zkey; tol_m negative or
+ * NaN; max_weight outside 1..255; fill_min_weight outside 0..255 (0 = never fill); a bad stride; n_pairs out of range; no
+ * prepare_keyframes; a stream of another device.
+ * Contracts of vors_batch_reproject_depth: enqueued on hip_stream, NOT synchronised, no allocation ever (vors_batch_workspace_bytes does not
+ * change); in dense mode the keyframe's d_kf_gray / d_kf_depth must still be alive; touches nothing track computes or reads; always the
+ * reference's per-point arithmetic whatever the handle's; vors_trackers handles are out of scope. */
+#define VORS_FUSE_COUNTS 6
+#define VORS_ZKEY_EMPTY 0xFFFFFFFFFFFFFFFFull
+vors_status vors_batch_fuse_depth(vors_batch* b, int n_pairs, const void* d_models, size_t model_stride_bytes,
+                                  const uint16_t* d_cur_depth, float tol_m,
+                                  const uint8_t* d_kf_weight /* nullable */, int max_weight, int fill_min_weight,
+                                  uint64_t* d_zkey, uint16_t* d_fused_depth /* nullable */, uint8_t* d_fused_weight /* nullable */,
+                                  uint32_t* d_counts /* nullable */, void* hip_stream);
+/* The merge alone for arrays on the host (the text the device kernel runs; needs no GPU): n_pixels keys and measured depths ->
+ * fused_depth, fused_weight, counts (each nullable). kf_weight (nullable) has n_kf_pixels entries. Refused with
+ * VORS_ERR_INVALID_ARGUMENT, nothing written: NULL zkey or cur_depth, depth_scale not > 0, the tol_m / max_weight / fill_min_weight
+ * refusals above, and a key other than VORS_ZKEY_EMPTY whose source index is >= n_kf_pixels (checked with or without kf_weight). */
+vors_status vors_fuse_depth_pixels(float depth_scale, float tol_m, int max_weight, int fill_min_weight, size_t n_pixels,
+                                   const uint64_t* zkey, const uint16_t* cur_depth,
+                                   const uint8_t* kf_weight /* nullable */, size_t n_kf_pixels,
+                                   uint16_t* fused_depth, uint8_t* fused_weight, uint32_t counts[VORS_FUSE_COUNTS] /* each nullable */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

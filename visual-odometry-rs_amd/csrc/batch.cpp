@@ -769,6 +769,47 @@ vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, co
     return VORS_OK;
 }
 
+vors_status vors_batch_fuse_depth(vors_batch* b, int n_pairs, const void* d_models, size_t model_stride_bytes, const uint16_t* d_cur_depth,
+                                  float tol_m, const uint8_t* d_kf_weight, int max_weight, int fill_min_weight, uint64_t* d_zkey,
+                                  uint16_t* d_fused_depth, uint8_t* d_fused_weight, uint32_t* d_counts, void* hip_stream) {
+    if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: the handle b is NULL");
+    if (!d_models) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: d_models is NULL");
+    if (!d_cur_depth) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: d_cur_depth is NULL");
+    if (!d_zkey) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: d_zkey is NULL (the pass keeps no plane of its own)");
+    if ((uintptr_t)d_zkey % 8 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: d_zkey must be 8-byte aligned");
+    if (!(tol_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: tol_m must be >= 0 (and not NaN)");
+    if (max_weight < 1 || max_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: max_weight must be in 1..255");
+    if (fill_min_weight < 0 || fill_min_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: fill_min_weight must be in 0..255");
+    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    // the keyframe side alone, like reproject_depth: legal before any track_current
+    if (b->prepared_pairs <= 0 || !b->kf_level0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, b->prepared_pairs > 0 ? "fuse_depth is not available on a trackers-owned batch (the handle keeps records, not frames)"
+                                                                     : "fuse_depth needs prepare_keyframes first");
+    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    vors_status st = check_stream(b, s);
+    if (st != VORS_OK) return st;
+    FuseDepthCall call{{Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    call.n_pairs = n_pairs;
+    call.models = static_cast<const float*>(d_models);
+    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.cur_depth = d_cur_depth;
+    call.tol_m = tol_m;
+    call.kf_weight = d_kf_weight;
+    call.max_weight = max_weight;
+    call.fill_min_weight = fill_min_weight;
+    call.zkey = d_zkey;
+    call.fused_depth = d_fused_depth;
+    call.fused_weight = d_fused_weight;
+    call.counts = d_counts;
+    launch_lm_fuse_depth(b->g, call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
 // The count workspace of the point-cloud pass ([max_pairs][most chunks of a level] integers): created by the first call and counted by
 // vors_batch_workspace_bytes from then on, like the evaluation workspace above.
 static vors_status ensure_point_cloud_ws(vors_batch* b) {

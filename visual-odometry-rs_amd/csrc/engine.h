@@ -360,6 +360,44 @@ struct PointCloudArgs {
     int ws_chunks;
     int wide_keep;              // the mask planes are 4-byte aligned: a dense quad reads its four bytes at once
 };
+// Depth fusion of level 0 of a prepared batch at one model per pair (vors_batch_fuse_depth): the keyframe's points splatted into the
+// current frame through a KEYED z-buffer (bits(Z') << 32 | source pixel, one 64-bit minimum per landing point), then merged per current
+// pixel with the measured depth (lie.h fuse_depth_pixel). zkey is required; the other outputs are nullable.
+struct FuseDepthCall : LmScene {
+    int n_pairs;
+    const float* models;
+    int model_stride;           // floats
+    const uint16_t* cur_depth;  // [pair][S0]
+    float tol_m;
+    const uint8_t* kf_weight;   // [pair][S0], keyframe geometry; nullable = 1 everywhere; 0 removes the point
+    int max_weight, fill_min_weight;
+    uint64_t* zkey;             // [pair][S0], current frame
+    uint16_t* fused_depth;      // [pair][S0], current frame
+    uint8_t* fused_weight;      // [pair][S0], current frame
+    uint32_t* counts;           // [pair][VORS_FUSE_COUNTS]
+};
+// What the splat kernel of one slice of pairs gets.
+struct FuseSplatArgs {
+    int pair0, chunk_points;
+    const float* models;
+    int model_stride;
+    const uint8_t* kf_weight;
+    unsigned long long* zkey;
+    int wide_weight;            // the weight planes are 4-byte aligned: a dense quad reads its four bytes at once
+};
+// What the merge kernel of one slice of pairs gets.
+struct FuseMergeArgs {
+    int pair0, plane;
+    float depth_scale, tol_m;
+    int max_weight, fill_min_weight;
+    const uint64_t* zkey;
+    const uint16_t* cur_depth;
+    const uint8_t* kf_weight;
+    uint16_t* fused_depth;
+    uint8_t* fused_weight;
+    uint32_t* counts;
+    int wide;                   // every plane allows four pixels per thread: 16-byte key loads, 8-byte depth and 4-byte weight accesses
+};
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }
@@ -447,6 +485,9 @@ void launch_lm_residual_maps(const Geom& g, const ResidualMapsCall& call, hipStr
 // current depth and the four counts, in the reference's per-point arithmetic whatever the handle's (lm_kernels.hip
 // lm_reproject_depth_kernel, pred_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
 void launch_lm_reproject_depth(const Geom& g, const ReprojectCall& call, hipStream_t s);
+// Keyed z-buffer splat of level 0 and the per-pixel merge with the measured depth, in the reference's per-point arithmetic whatever the
+// handle's (lm_kernels.hip lm_fuse_splat_kernel, fuse_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
+void launch_lm_fuse_depth(const Geom& g, const FuseDepthCall& call, hipStream_t s);
 // Ordered stream compaction of the usable (and kept) points of one level per pair into point lists in the world frame (lm_kernels.hip
 // point_cloud_kernel: a counting launch into call.ws, then a ranking and writing launch; no workgroup waits for another): enqueued, not
 // synchronised. Reads no current image.

@@ -296,6 +296,54 @@ VORS_HD uint16_t to_depth(float scale, float idepth) {
     return (uint16_t)(int)r;
 }
 
+// Depth fusion of one pixel of the current frame: the keyed z-buffer entry `key` = bits(Z') << 32 | src of the nearest keyframe point
+// that lands here (all ones: none), its weight (kf_weight[src], 1 without a plane) and the measured depth d (0 = unknown).
+// r = Z' - (float)d / depth_scale is the text of the depth residual (lm_kernels.hip reproject_sweep). Cases, which are also the counters:
+//   0 agree      |r| <= tol_m         depth = to_depth(scale, (wk / Z' + scale / d) / (wk + 1)), weight = min(wk + 1, max_weight)
+//   1 conflict, prediction in front   r < -tol_m: the measurement, weight 1
+//   2 conflict, prediction behind     r > tol_m:  the measurement, weight 1
+//   3 measured only                   no prediction: the measurement, weight 1
+//   4 filled     no measurement, fill_min_weight > 0 and wk >= fill_min_weight: to_depth(scale, 1 / Z') (the bits of d_pred_depth), weight wk
+//   5 empty      everything else (a NaN residual included): 0, 0
+// The mean is taken in inverse depth, the quantity the tracker works in; scale / (float)d is from_depth's expression. A fused depth that
+// rounds to 0 (a surface nearer than half a depth unit) gets weight 0, so that depth 0 and weight 0 always coincide; its case stays.
+// The expression order is fixed: the one text the host entry (vors_fuse_depth_pixels) and the device kernel (lm_kernels.hip
+// fuse_depth_kernel) both run, bit for bit. kf_weight is read at src only when the key is not empty.
+struct FusedPixel {
+    uint16_t depth;
+    uint8_t weight;
+    uint8_t kase;
+};
+VORS_HD FusedPixel fuse_depth_pixel(float depth_scale, float tol_m, int max_weight, int fill_min_weight, uint64_t key, const uint8_t* kf_weight,
+                                    uint16_t d) {
+    const bool has_p = key != 0xFFFFFFFFFFFFFFFFull, has_m = d != 0;
+    const float zp = __builtin_bit_cast(float, (uint32_t)(key >> 32));
+    const int wk = (has_p && kf_weight) ? (int)kf_weight[(uint32_t)key] : 1;
+    const float r = zp - (float)d / depth_scale;
+    FusedPixel o{0, 0, 5};
+    if (has_p && has_m) {
+        if (fabsf(r) <= tol_m) {
+            o.depth = to_depth(depth_scale, ((float)wk * (1.0f / zp) + depth_scale / (float)d) / ((float)wk + 1.0f));
+            o.weight = (uint8_t)(wk + 1 < max_weight ? wk + 1 : max_weight);
+            o.kase = 0;
+        } else if (r < -tol_m || r > tol_m) {
+            o.depth = d;
+            o.weight = 1;
+            o.kase = r < -tol_m ? 1 : 2;
+        }
+    } else if (has_m) {
+        o.depth = d;
+        o.weight = 1;
+        o.kase = 3;
+    } else if (has_p && fill_min_weight > 0 && wk >= fill_min_weight) {
+        o.depth = to_depth(depth_scale, 1.0f / zp);
+        o.weight = (uint8_t)wk;
+        o.kase = 4;
+    }
+    if (o.depth == 0) o.weight = 0;
+    return o;
+}
+
 // One LM step: lm_optimizer.rs:123-136.
 VORS_HD bool lm_step(const float* h36, const float* g6, const Iso& model, float lm_coef, Iso* out) {
     float delta[6];

@@ -2631,6 +2631,185 @@ void launch_lm_reproject_depth(const Geom& g_in, const ReprojectCall& call, hipS
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// vors_batch_fuse_depth: level 0 of the keyframe splatted into the CURRENT frame through a KEYED z-buffer, then merged per current pixel
+// with the measured depth. Two launches ordered by the stream.
+// SPLAT (lm_fuse_splat_kernel): lm_reproject_depth_kernel's grid, cut and sources; the sweep is reproject_sweep's up to the landing test —
+// a sibling, reproject_sweep itself is untouched. Then one weight byte at the SOURCE pixel (the dense quad source reads its four adjacent
+// bytes as one dword where the plane allows it; no plane: weight 1) and, per landing point of non-zero weight, one 64-bit global
+// atomicMin of bits(Z') << 32 | src into a plane the launcher has filled with ones. Z' > 0 orders as its bits, so the nearest surface
+// wins and among equal Z' the smallest source index: a minimum, bitwise reproducible whatever the order of arrival. No LDS.
+// MERGE (fuse_depth_kernel): elementwise over current pixels, 1024 per workgroup: lie.h fuse_depth_pixel on (key, weight gathered at src,
+// measured depth). Four adjacent pixels per thread where every plane allows it (two 16-byte key loads, one 8-byte depth load, an 8-byte
+// and a 4-byte store), else four pixels a workgroup width apart. Counts (COUNTS) follow the reprojection pass: per-thread integers, added
+// across the wavefront, one LDS sum per workgroup, one global integer atomicAdd per non-zero counter and workgroup into a zeroed array.
+// Without COUNTS the kernel has no LDS and no atomic.
+// ------------------------------------------------------------------------------------------------------------
+template <class Src>
+__device__ __forceinline__ void fuse_splat_sweep(const Src& src, int first, int last, const ImgCtx& c, const Iso& model, const uint8_t* kf_weight,
+                                                 bool wide_weight, unsigned long long* zkey) {
+    constexpr int G = Src::G;
+    const float fcols = (float)c.cols, frows = (float)c.rows;
+    for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
+        typename Src::Raw raw;
+        src.template fetch<RMAPS_BLOCK>(cur, last, raw);
+        Pos pos[G];
+        src.positions(raw, pos);
+        WarpedZ w[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) w[g] = warp_point_z(c, model, pos[g]);
+        bool lands[G];
+        unsigned q[G], from[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const float fu = floorf(w[g].u + 0.5f), fv = floorf(w[g].v + 0.5f);
+            lands[g] = (pos[g].tmpl >= 0.f) && (w[g].z > 0.f) && (fu >= 0.f) && (fu < fcols) && (fv >= 0.f) && (fv < frows);
+            // masked, not branched: a point that does not land addresses pixel 0 (a safe address) and is selected away
+            q[g] = (unsigned)(__float2int_rz(lands[g] ? fv : 0.f) * c.cols + __float2int_rz(lands[g] ? fu : 0.f));
+            from[g] = (unsigned)max(plane_pixel(src, raw, g, c.cols), 0);  // (a lane past the end of a list is no point: pixel 0, selected away)
+        }
+        uint32_t wb[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) wb[g] = 1;
+        if (kf_weight) {  // (uniform)
+            bool done = false;
+            if constexpr (G == 4) {
+                if (wide_weight) {  // (uniform) a quad owns four adjacent pixels of one row, 4-byte aligned in the weight plane
+                    const uint32_t ww = *reinterpret_cast<const uint32_t*>(kf_weight + from[0]);
+#pragma unroll
+                    for (int g = 0; g < G; ++g) wb[g] = (ww >> (8 * g)) & 0xffu;
+                    done = true;
+                }
+            }
+            if (!done) {
+#pragma unroll
+                for (int g = 0; g < G; ++g) wb[g] = kf_weight[from[g]];
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g)
+            if (lands[g] && wb[g] != 0)
+                atomicMin(zkey + q[g], ((unsigned long long)(uint32_t)__float_as_int(w[g].z) << 32) | (unsigned long long)from[g]);
+    }
+}
+template <bool DENSE>
+__global__ __launch_bounds__(RMAPS_BLOCK) void lm_fuse_splat_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                    const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                    const uint16_t* __restrict__ kf_depth, Records rec, FuseSplatArgs a) {
+    const int pair = a.pair0 + blockIdx.y, chunk = blockIdx.x, n_chunks = gridDim.x;
+    const Iso model = iso_uniform(iso_load(a.models + (size_t)pair * a.model_stride));
+    ImgCtx c{};  // level 0's window and intrinsics; the current image is never read (the pass is legal before any track_current)
+    c.rows = g.lv[0].rows;
+    c.cols = g.lv[0].cols;
+    c.k = g.lv[0].k;
+    const uint8_t* kf_weight = a.kf_weight ? a.kf_weight + (size_t)pair * g.S0 : nullptr;
+    unsigned long long* zkey = a.zkey + (size_t)pair * g.S0;
+    with_level_source<DENSE, true, false>(g, 0, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // this pair's chunks, cut like lm_eval_pairs_kernel's (a short candidate list needs fewer than the grid has)
+        const int points = DENSE ? g.lv[0].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        fuse_splat_sweep(src, first, last, c, model, kf_weight, a.wide_weight != 0, zkey);
+    });
+}
+#define FUSE_BLOCK 256
+#define FUSE_PIXELS 4  // per thread
+template <bool COUNTS>
+__global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_kernel(FuseMergeArgs a) {
+    __shared__ uint32_t lds_counts[COUNTS ? (FUSE_BLOCK / 64) * VORS_FUSE_COUNTS : 1];
+    const int pair = a.pair0 + blockIdx.y;
+    const size_t off = (size_t)pair * (size_t)a.plane;
+    const uint64_t* zkey = a.zkey + off;
+    const uint16_t* cur_depth = a.cur_depth + off;
+    const uint8_t* kf_weight = a.kf_weight ? a.kf_weight + off : nullptr;
+    uint16_t* fused_depth = a.fused_depth ? a.fused_depth + off : nullptr;
+    uint8_t* fused_weight = a.fused_weight ? a.fused_weight + off : nullptr;
+    const int base = blockIdx.x * (FUSE_BLOCK * FUSE_PIXELS);
+    uint32_t n[VORS_FUSE_COUNTS] = {0u, 0u, 0u, 0u, 0u, 0u};
+    FusedPixel o[FUSE_PIXELS];
+    if (a.wide) {  // (uniform; plane % 4 == 0: a thread's four pixels are all inside or all outside)
+        const int i = base + FUSE_PIXELS * (int)threadIdx.x;
+        if (i < a.plane) {
+            const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(zkey + i), k23 = *reinterpret_cast<const ulonglong2*>(zkey + i + 2);
+            const ushort4 d = *reinterpret_cast<const ushort4*>(cur_depth + i);
+            o[0] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.x, kf_weight, d.x);
+            o[1] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.y, kf_weight, d.y);
+            o[2] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.x, kf_weight, d.z);
+            o[3] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.y, kf_weight, d.w);
+            if (fused_depth) *reinterpret_cast<ushort4*>(fused_depth + i) = make_ushort4(o[0].depth, o[1].depth, o[2].depth, o[3].depth);
+            if (fused_weight)
+                *reinterpret_cast<uint32_t*>(fused_weight + i) =
+                    (uint32_t)o[0].weight | ((uint32_t)o[1].weight << 8) | ((uint32_t)o[2].weight << 16) | ((uint32_t)o[3].weight << 24);
+            if constexpr (COUNTS) {
+#pragma unroll
+                for (int j = 0; j < FUSE_PIXELS; ++j)
+#pragma unroll
+                    for (int k = 0; k < VORS_FUSE_COUNTS; ++k) n[k] += o[j].kase == k ? 1u : 0u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < FUSE_PIXELS; ++j) {
+            const int i = base + j * FUSE_BLOCK + (int)threadIdx.x;
+            if (i >= a.plane) continue;
+            o[j] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, zkey[i], kf_weight, cur_depth[i]);
+            if (fused_depth) fused_depth[i] = o[j].depth;
+            if (fused_weight) fused_weight[i] = o[j].weight;
+            if constexpr (COUNTS) {
+#pragma unroll
+                for (int k = 0; k < VORS_FUSE_COUNTS; ++k) n[k] += o[j].kase == k ? 1u : 0u;
+            }
+        }
+    }
+    if constexpr (COUNTS) {
+#pragma unroll
+        for (int k = 0; k < VORS_FUSE_COUNTS; ++k) {
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) n[k] += (uint32_t)__shfl_xor((int)n[k], sh);
+            if ((threadIdx.x & 63) == 0) lds_counts[(threadIdx.x >> 6) * VORS_FUSE_COUNTS + k] = n[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < VORS_FUSE_COUNTS) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int wv = 0; wv < FUSE_BLOCK / 64; ++wv) t += lds_counts[wv * VORS_FUSE_COUNTS + threadIdx.x];
+            if (t) atomicAdd(a.counts + (size_t)pair * VORS_FUSE_COUNTS + threadIdx.x, t);
+        }
+    }
+}
+void launch_lm_fuse_depth(const Geom& g_in, const FuseDepthCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const bool dense = g.mode == VORS_CANDIDATES_DENSE;
+    const size_t plane = (size_t)g.S0, n = (size_t)call.n_pairs;
+    // all ones = VORS_ZKEY_EMPTY: nothing has landed (a 32-bit fill over twice as many dwords)
+    (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(call.zkey), 0xFFFFFFFF, 2 * n * plane, s);
+    if (call.counts) (void)hipMemsetAsync(call.counts, 0, n * VORS_FUSE_COUNTS * sizeof(uint32_t), s);
+    FuseSplatArgs a{0, eval_pairs_chunk_points(g), call.models, call.model_stride, call.kf_weight, reinterpret_cast<unsigned long long*>(call.zkey),
+                    ((uintptr_t)call.kf_weight % 4 == 0 && plane % 4 == 0) ? 1 : 0};
+    const bool merge = call.fused_depth || call.fused_weight || call.counts;
+    const bool wide = plane % 4 == 0 && (uintptr_t)call.zkey % 16 == 0 && (uintptr_t)call.cur_depth % 8 == 0 && (uintptr_t)call.fused_depth % 8 == 0 &&
+                      (uintptr_t)call.fused_weight % 4 == 0;
+    FuseMergeArgs m{0, (int)plane, g.depth_scale, call.tol_m, call.max_weight, call.fill_min_weight, call.zkey, call.cur_depth, call.kf_weight,
+                    call.fused_depth, call.fused_weight, call.counts, wide ? 1 : 0};
+    const int chunks = eval_pairs_chunks(g, 0);
+    const unsigned blocks = (unsigned)((plane + FUSE_BLOCK * FUSE_PIXELS - 1) / (FUSE_BLOCK * FUSE_PIXELS));
+    for (int pair0 = 0; pair0 < call.n_pairs; pair0 += 32768) {  // (the y extent of a grid)
+        a.pair0 = m.pair0 = pair0;
+        const int np = std::min(32768, call.n_pairs - pair0);
+        with_bool(dense, [&](auto d) {
+            launch_on_scene(lm_fuse_splat_kernel<decltype(d)::value>, dim3(chunks, np), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+        });
+        if (merge)
+            with_bool(call.counts != nullptr, [&](auto k) {
+                hipLaunchKernelGGL(fuse_depth_kernel<decltype(k)::value>, dim3(blocks, np), dim3(FUSE_BLOCK), 0, s, m);
+            });
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // vors_batch_point_cloud: the usable points of a level as a LIST per pair — an ordered, deterministic stream compaction — back-projected
 // (the Pos the LM kernels warp from, camera.rs:135-140) and carried to the world frame by one pose per pair (iso_transform_point). Grid,
 // cut of a level and sources are lm_residual_maps_kernel's. Rank order is ascending SLOT order of the level's source: the dense sources

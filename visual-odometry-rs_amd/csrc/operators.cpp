@@ -179,6 +179,31 @@ vors_status vors_residual_scale_from_hist(const uint32_t hist[VORS_RESIDUAL_BINS
     return VORS_OK;
 }
 
+// The merge of vors_batch_fuse_depth for arrays: lie.h fuse_depth_pixel, the text the device kernel runs. Every key is checked before
+// anything is written.
+vors_status vors_fuse_depth_pixels(float depth_scale, float tol_m, int max_weight, int fill_min_weight, size_t n_pixels, const uint64_t* zkey,
+                                   const uint16_t* cur_depth, const uint8_t* kf_weight, size_t n_kf_pixels, uint16_t* fused_depth,
+                                   uint8_t* fused_weight, uint32_t counts[VORS_FUSE_COUNTS]) {
+    if (!zkey || !cur_depth) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth_pixels: zkey or cur_depth is NULL");
+    if (!(depth_scale > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth_pixels: depth_scale must be > 0");
+    if (!(tol_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth_pixels: tol_m must be >= 0 (and not NaN)");
+    if (max_weight < 1 || max_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth_pixels: max_weight must be in 1..255");
+    if (fill_min_weight < 0 || fill_min_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth_pixels: fill_min_weight must be in 0..255");
+    for (size_t i = 0; i < n_pixels; ++i)
+        if (zkey[i] != VORS_ZKEY_EMPTY && (zkey[i] & 0xFFFFFFFFull) >= n_kf_pixels)
+            return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth_pixels: a key names a source pixel beyond n_kf_pixels");
+    uint32_t n[VORS_FUSE_COUNTS] = {0, 0, 0, 0, 0, 0};
+    for (size_t i = 0; i < n_pixels; ++i) {
+        const FusedPixel o = fuse_depth_pixel(depth_scale, tol_m, max_weight, fill_min_weight, zkey[i], kf_weight, cur_depth[i]);
+        if (fused_depth) fused_depth[i] = o.depth;
+        if (fused_weight) fused_weight[i] = o.weight;
+        n[o.kase] += 1;
+    }
+    if (counts)
+        for (int k = 0; k < VORS_FUSE_COUNTS; ++k) counts[k] = n[k];
+    return VORS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------

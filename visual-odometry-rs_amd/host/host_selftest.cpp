@@ -83,6 +83,26 @@ int main() {
         }
     }
 
+    // ... and of the depth fusion: a NULL handle is refused before a device is touched; the merge is host arithmetic (1 m of weight 3
+    // and 2 m measured agree within 2 m: inverse depths 1 and 0.5, mean 0.875 -> 5714, weight 4; an empty key keeps the measurement)
+    {
+        if (vors_batch_fuse_depth(nullptr, 1, nullptr, 0, nullptr, 0.f, nullptr, 255, 0, nullptr, nullptr, nullptr, nullptr, nullptr) != VORS_ERR_INVALID_ARGUMENT) {
+            std::fprintf(stderr, "vors_batch_fuse_depth accepted a NULL handle\n");
+            return 1;
+        }
+        const uint64_t keys[2] = {0x3f80000000000000ull, VORS_ZKEY_EMPTY};
+        const uint16_t cur[2] = {10000, 7000};
+        const uint8_t w3 = 3;
+        uint16_t depth[2] = {0, 0};
+        uint8_t weight[2] = {0, 0};
+        uint32_t counts[VORS_FUSE_COUNTS];
+        if (vors_fuse_depth_pixels(5000.0f, 2.0f, 255, 0, 2, keys, cur, &w3, 1, depth, weight, counts) != VORS_OK || depth[0] != 5714 ||
+            weight[0] != 4 || depth[1] != 7000 || weight[1] != 1 || counts[0] != 1 || counts[3] != 1) {
+            std::fprintf(stderr, "vors_fuse_depth_pixels failed: %u %u %u %u\n", depth[0], weight[0], depth[1], weight[1]);
+            return 1;
+        }
+    }
+
     if (vors_device_count() < 1) { std::printf("host_selftest: link ok, no GPU (skipping device part)\n"); return 77; }
     const int rows = 120, cols = 160;
     const double s = cols / 640.0;

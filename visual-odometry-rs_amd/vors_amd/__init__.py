@@ -104,6 +104,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_residual_maps", "vors_residual_scale_from_hist",
     "vors_batch_reproject_depth", "vors_to_depth", "vors_from_depth",
     "vors_batch_point_cloud", "vors_camera_back_project", "vors_camera_project",
+    "vors_batch_fuse_depth", "vors_fuse_depth_pixels",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -201,6 +202,8 @@ def lib():
         _lib.vors_camera_back_project.restype = None
         _lib.vors_camera_project.argtypes = [vp, vp, vp, i, vp]
         _lib.vors_camera_project.restype = None
+        _lib.vors_batch_fuse_depth.argtypes = [vp, i, vp, C.c_size_t, vp, f, vp, i, i, vp, vp, vp, vp, vp]
+        _lib.vors_fuse_depth_pixels.argtypes = [f, f, i, i, C.c_size_t, vp, vp, vp, C.c_size_t, vp, vp, vp]
         _lib.vors_lm_eval.argtypes = [C.POINTER(vors_obs), vp, C.POINTER(f), C.POINTER(C.c_int32), vp, vp, vp]
         _lib.vors_ref_sincos.argtypes = [vp, i, vp, vp]
         _lib.vors_ref_sincos.restype = None
@@ -703,6 +706,40 @@ class Batch:
                 out[name] = t
         return out
 
+    def fuse_depth(self, models, cur_depth, tol_m, kf_weight=None, max_weight=255, fill_min_weight=0, depth=True, weight=True, zkey=False,
+                   counts=False):
+        """The keyframe's depth carried into the current frame at `models` ([n, 7] or a track's out_stats) through a keyed z-buffer and merged
+        with the measured current depth maps `cur_depth` ([n, rows, cols] int16 tensor holding the u16 payload) (vors_batch_fuse_depth; level
+        0, needs prepare_keyframes only) -> dict of the requested tensors on the current stream, not synchronised: "depth" [n, rows, cols]
+        (int16 tensor holding the u16 fused depth, the next prepare_keyframes' depth), "weight" [n, rows, cols] (uint8, the next call's
+        `kf_weight`), "zkey" [n, rows, cols] (int64 tensor holding the u64 payload bits(Z') << 32 | source pixel, -1 = nothing landed),
+        "counts" [n, 6] (int32: agree, prediction in front, prediction behind, measured only, filled, empty). `kf_weight` [n, rows, cols]
+        uint8 in keyframe geometry: None = 1 everywhere, 0 removes the point. The key plane is made when it is not asked for."""
+        import torch
+        models, n, k, stride = self._models_arg(models)
+        if k != 1:
+            raise VorsError("fuse_depth takes one model per pair")
+        shape = (n, self.rows, self.cols)
+        if cur_depth is None or cur_depth.dtype != torch.int16 or not cur_depth.is_contiguous() or tuple(cur_depth.shape) != shape:
+            raise VorsError(f"expected a contiguous int16 cur_depth {list(shape)}")
+        if kf_weight is not None and (kf_weight.dtype != torch.uint8 or not kf_weight.is_contiguous() or tuple(kf_weight.shape) != shape):
+            raise VorsError(f"expected a contiguous uint8 kf_weight {list(shape)}, got {kf_weight.dtype} {tuple(kf_weight.shape)}")
+        if not (depth or weight or zkey or counts):
+            raise VorsError("fuse_depth: nothing requested")
+        dev = models.device
+        t_key = torch.empty(shape, dtype=torch.int64, device=dev)
+        t_d = torch.empty(shape, dtype=torch.int16, device=dev) if depth else None
+        t_w = torch.empty(shape, dtype=torch.uint8, device=dev) if weight else None
+        t_cnt = torch.empty((n, 6), dtype=torch.int32, device=dev) if counts else None
+        _check(lib().vors_batch_fuse_depth(self._h, n, self._dp(models), stride, self._dp(cur_depth), float(tol_m), self._dp(kf_weight),
+                                           int(max_weight), int(fill_min_weight), self._dp(t_key), self._dp(t_d), self._dp(t_w),
+                                           self._dp(t_cnt), self._stream()))
+        out = {}
+        for name, want, t in (("depth", depth, t_d), ("weight", weight, t_w), ("zkey", zkey, t_key), ("counts", counts, t_cnt)):
+            if want:
+                out[name] = t
+        return out
+
     def keyframe_image(self, pair, level):
         out = np.empty(self.rows * self.cols, np.uint8)
         r, c = C.c_int(), C.c_int()
@@ -982,6 +1019,33 @@ def camera_project(cam5, pose7, xyz):
     out = np.empty((len(p), 3), np.float32)
     lib().vors_camera_project(_ptr(k), _ptr(pose), _ptr(p), len(p), _ptr(out))
     return out
+
+
+ZKEY_EMPTY = 0xFFFFFFFFFFFFFFFF
+FUSE_COUNTS = 6
+
+
+def fuse_depth_pixels(depth_scale, tol_m, zkey, cur_depth, kf_weight=None, max_weight=255, fill_min_weight=0, n_kf_pixels=None):
+    """The merge of Batch.fuse_depth for arrays on the host (vors_fuse_depth_pixels; needs no GPU): zkey (uint64, or int64 holding that
+    payload) and cur_depth (uint16) of one shape, kf_weight (uint8, any shape: indexed flat by the keys' source pixel) or None ->
+    (depth uint16, weight uint8, counts uint32 [6]). n_kf_pixels bounds the source indices (default: kf_weight's size, else zkey's)."""
+    key = np.ascontiguousarray(zkey)
+    if key.dtype == np.int64:
+        key = key.view(np.uint64)
+    d = np.ascontiguousarray(cur_depth)
+    if d.dtype == np.int16:
+        d = d.view(np.uint16)
+    w = None if kf_weight is None else np.ascontiguousarray(kf_weight)
+    if key.dtype != np.uint64 or d.dtype != np.uint16 or key.shape != d.shape or (w is not None and w.dtype != np.uint8):
+        raise VorsError("fuse_depth_pixels: zkey uint64 and cur_depth uint16 of one shape, kf_weight uint8 or None")
+    if n_kf_pixels is None:
+        n_kf_pixels = w.size if w is not None else key.size
+    if w is not None and int(n_kf_pixels) > w.size:
+        raise VorsError("fuse_depth_pixels: n_kf_pixels exceeds kf_weight")
+    depth, weight, counts = np.empty(key.shape, np.uint16), np.empty(key.shape, np.uint8), np.zeros(FUSE_COUNTS, np.uint32)
+    _check(lib().vors_fuse_depth_pixels(float(depth_scale), float(tol_m), int(max_weight), int(fill_min_weight), key.size, _ptr(key), _ptr(d),
+                                        _ptr(w), int(n_kf_pixels), _ptr(depth), _ptr(weight), _ptr(counts)))
+    return depth, weight, counts
 
 
 def ref_sincos(x):
