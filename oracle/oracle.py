@@ -404,6 +404,23 @@ def dso_mask(img, nb_target=2000, seed=0x5EEDD50):
     return mask, list(bs[:n])
 
 
+DSO_OUTCOMES = ("IN_RANGE_ALL", "SUBSAMPLE", "OUT_OF_RANGE_SAME_SIZE", "OUT_OF_RANGE_EXHAUSTED")  # dso::Outcome (vors_oracle.hpp)
+
+
+def dso_trace(img, nb_target=2000, seed=0x5EEDD50):
+    """dso_mask() with what the selection did -> dict(mask, base_sizes [rounds], level_counts [rounds][3] (picks per block level),
+    outcome (a name of DSO_OUTCOMES), keep (the sub-sampling bound, -1 when the outcome is not SUBSAMPLE))."""
+    img = np.ascontiguousarray(img, np.uint8)
+    rows, cols = img.shape
+    mask = np.zeros((rows, cols), np.uint8)
+    bs, counts, ok = np.zeros(3, np.int32), np.zeros(9, np.int32), np.zeros(2, np.int32)
+    f = lib().vo_dso_trace
+    f.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_uint8)] + [C.POINTER(C.c_int32)] * 3
+    n = f(_u8(img), rows, cols, nb_target, seed, _u8(mask), _i32(bs), _i32(counts), _i32(ok))
+    return dict(mask=mask, base_sizes=[int(b) for b in bs[:n]], level_counts=[tuple(int(c) for c in counts[3 * k:3 * k + 3]) for k in range(n)],
+                outcome=DSO_OUTCOMES[ok[0]], keep=int(ok[1]))
+
+
 def libm_sincos(x):
     """std::sin / std::cos on float32, as the oracle's se3::exp calls them (the platform libm) -> (sin, cos)."""
     x = np.ascontiguousarray(x, np.float32)

@@ -699,15 +699,32 @@ inline std::vector<size_t> pick_all_block_candidates(const BlockConfig& bc, size
     }
     return nb_picked;
 }
+// What select() did (optional, for the tests): per executed round the base block size and the picks of every block level, then which of
+// the four ends of dso.rs:115-146 it took.
+enum Outcome : int {
+    IN_RANGE_ALL = 0,            // ratio in [low, random]: every pick of the round
+    SUBSAMPLE = 1,               // ratio in (random, high]: picks kept with probability 1 / ratio (`keep` = the u8 bound)
+    OUT_OF_RANGE_SAME_SIZE = 2,  // ratio outside [low, high] and the adapted block size is the one just used: every pick
+    OUT_OF_RANGE_EXHAUSTED = 3   // ratio outside [low, high], another size wanted, no recursion left: every pick
+};
+struct SelectTrace {
+    std::vector<size_t> base_sizes;
+    std::vector<std::vector<size_t>> level_counts;  // [round][block level]
+    int outcome = -1;
+    int keep = -1;  // the sub-sampling bound, -1 when the outcome is not SUBSAMPLE
+};
 // dso.rs:98-147
 inline DMatrix<uint8_t> select(const DMatrix<uint16_t>& g, const RegionConfig& rc, BlockConfig bc, RecursiveConfig rec, size_t nb_target,
-                               uint64_t seed, std::vector<size_t>* trace_base_sizes = nullptr) {
+                               uint64_t seed, SelectTrace* trace = nullptr) {
     const DMatrix<uint16_t> med = region_median_gradients(g, rc.size);
     const DMatrix<uint16_t> thr = region_thresholds(med, rc.coef_a, rc.coef_b);
     for (;;) {
-        if (trace_base_sizes) trace_base_sizes->push_back(bc.base_size);
         DMatrix<uint8_t> picked;
         const std::vector<size_t> counts = pick_all_block_candidates(bc, rc.size, thr, g, picked);
+        if (trace) {
+            trace->base_sizes.push_back(bc.base_size);
+            trace->level_counts.push_back(counts);
+        }
         size_t nb_candidates = 0;
         for (size_t c : counts) nb_candidates += c;
         const Float ratio = (Float)nb_candidates / (Float)nb_target;
@@ -720,22 +737,28 @@ inline DMatrix<uint8_t> select(const DMatrix<uint16_t>& g, const RegionConfig& r
                 rec.nb_iterations_left -= 1;
                 continue;  // the medians / thresholds of the recursive call are identical
             }
+            if (trace) trace->outcome = target_size == bc.base_size ? OUT_OF_RANGE_SAME_SIZE : OUT_OF_RANGE_EXHAUSTED;
             for (size_t k = 0; k < mask.data.size(); ++k) mask.data[k] = picked.data[k] > 0;
         } else if (ratio > rec.random_thresh) {
             const uint8_t keep = (uint8_t)(255.0f / ratio);
+            if (trace) {
+                trace->outcome = SUBSAMPLE;
+                trace->keep = keep;
+            }
             for (int j = 0; j < mask.ncols; ++j)
                 for (int i = 0; i < mask.nrows; ++i) {
                     const uint8_t r = (uint8_t)(splitmix64(seed ^ splitmix64(((uint64_t)(uint32_t)i << 32) | (uint32_t)j)) & 0xff);
                     mask(i, j) = picked(i, j) > 0 && r <= keep;  // deviation: counter-based stand-in for rng.gen::<u8>()
                 }
         } else {
+            if (trace) trace->outcome = IN_RANGE_ALL;
             for (size_t k = 0; k < mask.data.size(); ++k) mask.data[k] = picked.data[k] > 0;
         }
         return mask;
     }
 }
 // examples/candidates_dso.rs:40-59: gradient magnitude = sqrt(squared_norm_direct) as u16; defaults with 2 recursion rounds.
-inline DMatrix<uint8_t> select_like_example(const DMatrix<uint8_t>& img, size_t nb_target, uint64_t seed, std::vector<size_t>* trace = nullptr) {
+inline DMatrix<uint8_t> select_like_example(const DMatrix<uint8_t>& img, size_t nb_target, uint64_t seed, SelectTrace* trace = nullptr) {
     DMatrix<uint16_t> g = gradient::squared_norm_direct(img);
     for (auto& v : g.data) v = (uint16_t)std::sqrt((Float)v);
     return select(g, RegionConfig{32, 1.0f, 3}, BlockConfig{4, 3, 0.5f}, RecursiveConfig{2, 0.8f, 4.0f, 1.1f}, nb_target, seed, trace);

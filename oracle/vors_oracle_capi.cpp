@@ -321,12 +321,27 @@ int vo_mean_pyramid(const uint8_t* img, int rows, int cols, int max_levels, uint
 // DSO-style level-0 mask (candidates/dso.rs with the parameters of examples/candidates_dso.rs). base_sizes (nullable, >= 3
 // entries): the block sizes of the successive rounds; returns the number of rounds.
 int vo_dso_mask(const uint8_t* img, int rows, int cols, int nb_target, uint64_t seed, uint8_t* mask_out, int32_t* base_sizes) {
-    std::vector<size_t> trace;
+    dso::SelectTrace trace;
     const auto m = dso::select_like_example(DMatrix<uint8_t>::from_row_slice(rows, cols, img), (size_t)nb_target, seed, &trace);
     m.to_row_slice(mask_out);
     if (base_sizes)
-        for (size_t k = 0; k < trace.size() && k < 3; ++k) base_sizes[k] = (int32_t)trace[k];
-    return (int)trace.size();
+        for (size_t k = 0; k < trace.base_sizes.size() && k < 3; ++k) base_sizes[k] = (int32_t)trace.base_sizes[k];
+    return (int)trace.base_sizes.size();
+}
+// The same selection with what it did: per round (at most 3) the base size and the picks of the three block levels (level_counts[3 * round
+// + level]; a block level that does not exist counts 0), outcome_keep = {dso::Outcome, sub-sampling bound or -1}. Returns the number of rounds.
+int vo_dso_trace(const uint8_t* img, int rows, int cols, int nb_target, uint64_t seed, uint8_t* mask_out, int32_t* base_sizes,
+                 int32_t* level_counts, int32_t* outcome_keep) {
+    dso::SelectTrace trace;
+    const auto m = dso::select_like_example(DMatrix<uint8_t>::from_row_slice(rows, cols, img), (size_t)nb_target, seed, &trace);
+    m.to_row_slice(mask_out);
+    for (size_t k = 0; k < trace.base_sizes.size() && k < 3; ++k) {
+        base_sizes[k] = (int32_t)trace.base_sizes[k];
+        for (size_t l = 0; l < 3; ++l) level_counts[3 * k + l] = l < trace.level_counts[k].size() ? (int32_t)trace.level_counts[k][l] : 0;
+    }
+    outcome_keep[0] = trace.outcome;
+    outcome_keep[1] = trace.keep;
+    return (int)trace.base_sizes.size();
 }
 void vo_prune_with_thresh(int thresh, int a, int b, int c, int d, uint8_t out[4]) {
     bool r[4];
