@@ -117,7 +117,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_pose_information_from_sums, likewise additions; + vors_batch_residual_maps, vors_residual_scale_from_hist,
                               *    likewise; + vors_batch_reproject_depth, vors_to_depth, vors_from_depth, likewise; + vors_batch_point_cloud,
                               *    vors_camera_back_project, vors_camera_project, likewise; + vors_batch_fuse_depth, vors_fuse_depth_pixels,
-                              *    likewise) */
+                              *    likewise; + vors_trackers_enable_depth_filter, vors_trackers_keyframe_depth, vors_trackers_workspace_bytes,
+                              *    vors_tracker_enable_depth_filter, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -140,6 +141,10 @@ vors_status vors_tracker_current_frame(const vors_tracker* t, double* timestamp,
 /* Diagnostics of the last track() and keyframe pose (not in the reference API). */
 vors_status vors_tracker_last_stats(const vors_tracker* t, vors_pair_stats* stats);
 vors_status vors_tracker_keyframe(const vors_tracker* t, double* timestamp, float pose7[7]);
+/* The recursive depth filter of vors_trackers_enable_depth_filter (below) for the single sequence, its N = 1 case: same arguments, same
+ * refusals. vors_tracker_create already took the first frame, so the call is legal until the first vors_tracker_track (refused after it and
+ * when repeated); the weights of the first keyframe are derived at this call from the depth map the tracker holds. */
+vors_status vors_tracker_enable_depth_filter(vors_tracker* t, float tol_m, int max_weight, int fill_min_weight);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -180,6 +185,25 @@ vors_status vors_trackers_last_stats(vors_trackers* t, vors_pair_stats* stats, v
 /* Stage timing as for a batch handle (stages 1 = keyframe promotion, 2 = current pyramid, 3 = LM). */
 vors_status vors_trackers_enable_kernel_timing(vors_trackers* t, int ring);
 vors_status vors_trackers_kernel_times(vors_trackers* t, int stage, float* ms_out, int capacity, int* n_out);
+/* RECURSIVE DEPTH FILTER across keyframe promotions (opt-in; without this call nothing changes: no launch, no allocation, no kernel
+ * argument). Every sequence keeps, next to its keyframe, the keyframe's depth map and a weight map (how many measurements a pixel's depth
+ * stands for). vors_trackers_init: depth = the measured depth, weight = 1 where it is non-zero, 0 where it is 0. vors_trackers_track, for
+ * exactly the sequences that promote, before the keyframe stage and on the device: the OLD keyframe's usable level-0 points are splatted
+ * at the sequence's final model of this frame (the head of its vors_pair_stats) with the keyframe's weights, and merged with this frame's
+ * d_depth — the pass and the rule table of vors_batch_fuse_depth (section 2), unchanged, as masked launches over the promotion list. The
+ * keyframe stage (all candidate modes and arithmetics) then runs on the FUSED depth instead of d_depth, and the fused weight becomes
+ * the keyframe's weight. A sequence that does not promote keeps both planes bit for bit: the filter advances at promotions only.
+ * tol_m, max_weight, fill_min_weight: those of vors_batch_fuse_depth, with its refusals (tol_m negative or NaN, max_weight outside
+ * 1..255, fill_min_weight outside 0..255). Legal after create and before vors_trackers_init only (afterwards the weights would have no
+ * history) and only once: otherwise VORS_ERR_INVALID_ARGUMENT. The call allocates every plane the filter needs (13 bytes per pixel and
+ * sequence: key plane, depth, weight, staged weight); no later call allocates. vors_trackers_workspace_bytes — the workspace of the
+ * batch handle the sequences run on, vors_batch_workspace_bytes' figure — includes them from then on. */
+vors_status vors_trackers_enable_depth_filter(vors_trackers* t, float tol_m, int max_weight, int fill_min_weight);
+/* DEVICE views [n_sequences][rows * cols] of every sequence's current keyframe depth (u16) and weight (u8), in the keyframe's geometry;
+ * valid for the life of the handle, contents valid in stream order after the last init / track. Either output may be NULL. Without an
+ * enabled filter: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_keyframe_depth(const vors_trackers* t, const uint16_t** d_depth, const uint8_t** d_weight);
+vors_status vors_trackers_workspace_bytes(const vors_trackers* t, uint64_t* bytes);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -508,7 +532,8 @@ vors_status vors_batch_point_cloud(vors_batch* b, int n_pairs, int level,
  * prepare_keyframes; a stream of another device.
  * Contracts of vors_batch_reproject_depth: enqueued on hip_stream, NOT synchronised, no allocation ever (vors_batch_workspace_bytes does not
  * change); in dense mode the keyframe's d_kf_gray / d_kf_depth must still be alive; touches nothing track computes or reads; always the
- * reference's per-point arithmetic whatever the handle's; vors_trackers handles are out of scope. */
+ * reference's per-point arithmetic whatever the handle's. Not available on the batch of a vors_trackers / vors_tracker handle: the
+ * sequence handles have their own switch, vors_trackers_enable_depth_filter / vors_tracker_enable_depth_filter (section 1). */
 #define VORS_FUSE_COUNTS 6
 #define VORS_ZKEY_EMPTY 0xFFFFFFFFFFFFFFFFull
 vors_status vors_batch_fuse_depth(vors_batch* b, int n_pairs, const void* d_models, size_t model_stride_bytes,

@@ -488,6 +488,10 @@ void launch_lm_reproject_depth(const Geom& g, const ReprojectCall& call, hipStre
 // Keyed z-buffer splat of level 0 and the per-pixel merge with the measured depth, in the reference's per-point arithmetic whatever the
 // handle's (lm_kernels.hip lm_fuse_splat_kernel, fuse_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
 void launch_lm_fuse_depth(const Geom& g, const FuseDepthCall& call, hipStream_t s);
+// The same pass as MASKED launches (the depth filter of vors_trackers): only the sequences of g.sel_list take part, their key planes
+// are filled by a masked launch too; call.n_pairs is the extent of the pair dimension (all sequences). Every plane of the call is
+// required, no counts.
+void launch_lm_fuse_depth_selected(const Geom& g, const FuseDepthCall& call, hipStream_t s);
 // Ordered stream compaction of the usable (and kept) points of one level per pair into point lists in the world frame (lm_kernels.hip
 // point_cloud_kernel: a counting launch into call.ws, then a ranking and writing launch; no workgroup waits for another): enqueued, not
 // synchronised. Reads no current image.
@@ -522,5 +526,6 @@ void launch_trackers_advance(int n_seq, int* frame_counter, const float* out_pos
 void launch_identity_poses(float* a, float* b, int n, hipStream_t s);  // two pose tables -> identity (inverse_compositional.rs:86-99)
 void launch_promote_copy(const Geom& g, const void* src, size_t src_stride, void* dst, size_t dst_stride, size_t bytes, int n_pairs,
                          hipStream_t s);
+void launch_depth_weight_init(const uint16_t* depth, uint8_t* weight, size_t n, hipStream_t s);  // weight = depth != 0
 
 }  // namespace vors

@@ -1161,5 +1161,28 @@ void launch_promote_copy(const Geom& g, const void* src, size_t src_stride, void
     hipLaunchKernelGGL(promote_copy_kernel, dim3((unsigned)((bytes + 4095) / 4096), n_pairs), dim3(256), 0, s, g, static_cast<const uint8_t*>(src),
                        src_stride, static_cast<uint8_t*>(dst), dst_stride, bytes, vec);
 }
+// Depth filter of the trackers, first frame: a measured depth has been seen once — weight 1 where the depth is non-zero, 0 where it is 0.
+// 16 pixels per thread (two 16-byte loads, one 16-byte store) where the planes allow it.
+__global__ __launch_bounds__(256) void depth_weight_init_kernel(const uint16_t* __restrict__ depth, uint8_t* __restrict__ weight, size_t n, int vec) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (i >= n) return;
+    if (vec && i + 16 <= n) {
+        const uint4 a = *reinterpret_cast<const uint4*>(depth + i), b = *reinterpret_cast<const uint4*>(depth + i + 8);
+        const uint32_t d[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t lo = d[2 * k], hi = d[2 * k + 1];
+            w[k] = ((lo & 0xffffu) ? 1u : 0u) | ((lo >> 16) ? 0x100u : 0u) | ((hi & 0xffffu) ? 0x10000u : 0u) | ((hi >> 16) ? 0x1000000u : 0u);
+        }
+        *reinterpret_cast<uint4*>(weight + i) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (size_t k = i; k < n && k < i + 16; ++k) weight[k] = depth[k] ? 1 : 0;
+    }
+}
+void launch_depth_weight_init(const uint16_t* depth, uint8_t* weight, size_t n, hipStream_t s) {
+    const int vec = (((uintptr_t)depth | (uintptr_t)weight) % 16 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(depth_weight_init_kernel, dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, s, depth, weight, n, vec);
+}
 
 }  // namespace vors

@@ -2810,6 +2810,109 @@ void launch_lm_fuse_depth(const Geom& g_in, const FuseDepthCall& call, hipStream
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// The depth filter of the lock-step trackers (vors_trackers_enable_depth_filter): the pass above as MASKED launches over the promotion
+// list (Geom::sel_list) — index k of the pair dimension is sequence select_pair(g, k), a workgroup beyond the selection returns at once.
+// Siblings: the kernels above are untouched. The host does not know how many sequences promote, so the grids are sized for all of them.
+// FILL (fuse_fill_selected_kernel): the key planes of the selected sequences to VORS_ZKEY_EMPTY, two keys (16 bytes) per thread.
+// SPLAT (lm_fuse_splat_selected_kernel): lm_fuse_splat_kernel's body on the selected sequence; the model is the head of its
+//   vors_pair_stats. One 64-bit atomicMin per landing point, no LDS.
+// MERGE (fuse_depth_selected_kernel): fuse_depth_kernel<false>'s body on the selected sequence: no counts, so no LDS and no atomic.
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fuse_fill_selected_kernel(Geom g, unsigned long long* __restrict__ zkey, int vec) {
+    const int pair = select_pair(g, blockIdx.y);
+    if (pair < 0) return;
+    unsigned long long* p = zkey + (size_t)pair * g.S0;
+    const int i = 2 * (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= g.S0) return;
+    if (vec && i + 2 <= g.S0) {  // (vec: S0 is even, every sequence's plane starts 16-byte aligned)
+        *reinterpret_cast<uint4*>(p + i) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    } else {
+        p[i] = 0xFFFFFFFFFFFFFFFFull;
+        if (i + 1 < g.S0) p[i + 1] = 0xFFFFFFFFFFFFFFFFull;
+    }
+}
+template <bool DENSE>
+__global__ __launch_bounds__(RMAPS_BLOCK) void lm_fuse_splat_selected_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                             const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                             const uint16_t* __restrict__ kf_depth, Records rec, FuseSplatArgs a) {
+    const int pair = select_pair(g, blockIdx.y), chunk = blockIdx.x, n_chunks = gridDim.x;
+    if (pair < 0) return;
+    const Iso model = iso_uniform(iso_load(a.models + (size_t)pair * a.model_stride));
+    ImgCtx c{};  // level 0's window and intrinsics; the current image is never read
+    c.rows = g.lv[0].rows;
+    c.cols = g.lv[0].cols;
+    c.k = g.lv[0].k;
+    const uint8_t* kf_weight = a.kf_weight + (size_t)pair * g.S0;
+    unsigned long long* zkey = a.zkey + (size_t)pair * g.S0;
+    with_level_source<DENSE, true, false>(g, 0, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        const int points = DENSE ? g.lv[0].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        fuse_splat_sweep(src, first, last, c, model, kf_weight, a.wide_weight != 0, zkey);
+    });
+}
+__global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_selected_kernel(Geom g, FuseMergeArgs a) {
+    const int pair = select_pair(g, blockIdx.y);
+    if (pair < 0) return;
+    const size_t off = (size_t)pair * (size_t)a.plane;
+    const uint64_t* zkey = a.zkey + off;
+    const uint16_t* cur_depth = a.cur_depth + off;
+    const uint8_t* kf_weight = a.kf_weight + off;
+    uint16_t* fused_depth = a.fused_depth + off;
+    uint8_t* fused_weight = a.fused_weight + off;
+    const int base = blockIdx.x * (FUSE_BLOCK * FUSE_PIXELS);
+    FusedPixel o[FUSE_PIXELS];
+    if (a.wide) {  // (uniform; plane % 4 == 0: a thread's four pixels are all inside or all outside)
+        const int i = base + FUSE_PIXELS * (int)threadIdx.x;
+        if (i >= a.plane) return;
+        const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(zkey + i), k23 = *reinterpret_cast<const ulonglong2*>(zkey + i + 2);
+        const ushort4 d = *reinterpret_cast<const ushort4*>(cur_depth + i);
+        o[0] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.x, kf_weight, d.x);
+        o[1] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.y, kf_weight, d.y);
+        o[2] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.x, kf_weight, d.z);
+        o[3] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.y, kf_weight, d.w);
+        *reinterpret_cast<ushort4*>(fused_depth + i) = make_ushort4(o[0].depth, o[1].depth, o[2].depth, o[3].depth);
+        *reinterpret_cast<uint32_t*>(fused_weight + i) =
+            (uint32_t)o[0].weight | ((uint32_t)o[1].weight << 8) | ((uint32_t)o[2].weight << 16) | ((uint32_t)o[3].weight << 24);
+    } else {
+#pragma unroll
+        for (int j = 0; j < FUSE_PIXELS; ++j) {
+            const int i = base + j * FUSE_BLOCK + (int)threadIdx.x;
+            if (i >= a.plane) continue;
+            o[j] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, zkey[i], kf_weight, cur_depth[i]);
+            fused_depth[i] = o[j].depth;
+            fused_weight[i] = o[j].weight;
+        }
+    }
+}
+// call.n_pairs: the sequences of the handle (the extent of the pair dimension); g_in.sel_list / sel_count: the ones that take part.
+// models, cur_depth, kf_weight, zkey, fused_depth and fused_weight are all required; counts is not written.
+void launch_lm_fuse_depth_selected(const Geom& g_in, const FuseDepthCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const bool dense = g.mode == VORS_CANDIDATES_DENSE;
+    const size_t plane = (size_t)g.S0;
+    const int n = call.n_pairs;
+    unsigned long long* zkey = reinterpret_cast<unsigned long long*>(call.zkey);
+    hipLaunchKernelGGL(fuse_fill_selected_kernel, dim3((unsigned)((plane + 511) / 512), n), dim3(256), 0, s, g, zkey,
+                       (plane % 2 == 0 && (uintptr_t)call.zkey % 16 == 0) ? 1 : 0);
+    FuseSplatArgs a{0, eval_pairs_chunk_points(g), call.models, call.model_stride, call.kf_weight, zkey,
+                    ((uintptr_t)call.kf_weight % 4 == 0 && plane % 4 == 0) ? 1 : 0};
+    const bool wide = plane % 4 == 0 && (uintptr_t)call.zkey % 16 == 0 && (uintptr_t)call.cur_depth % 8 == 0 && (uintptr_t)call.fused_depth % 8 == 0 &&
+                      (uintptr_t)call.fused_weight % 4 == 0;
+    FuseMergeArgs m{0, (int)plane, g.depth_scale, call.tol_m, call.max_weight, call.fill_min_weight, call.zkey, call.cur_depth, call.kf_weight,
+                    call.fused_depth, call.fused_weight, nullptr, wide ? 1 : 0};
+    with_bool(dense, [&](auto d) {
+        launch_on_scene(lm_fuse_splat_selected_kernel<decltype(d)::value>, dim3(eval_pairs_chunks(g, 0), n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+    });
+    const unsigned blocks = (unsigned)((plane + FUSE_BLOCK * FUSE_PIXELS - 1) / (FUSE_BLOCK * FUSE_PIXELS));
+    hipLaunchKernelGGL(fuse_depth_selected_kernel, dim3(blocks, n), dim3(FUSE_BLOCK), 0, s, g, m);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // vors_batch_point_cloud: the usable points of a level as a LIST per pair — an ordered, deterministic stream compaction — back-projected
 // (the Pos the LM kernels warp from, camera.rs:135-140) and carried to the world frame by one pose per pair (iso_transform_point). Grid,
 // cut of a level and sources are lm_residual_maps_kernel's. Rank order is ascending SLOT order of the level's source: the dense sources

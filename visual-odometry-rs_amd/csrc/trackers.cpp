@@ -20,6 +20,24 @@ struct vors_trackers {
     bool initialised = false;
     DevBuf cur_poses, kf_poses, out_poses, status, stats, kf_frame, promo_list, promo_count, frame_counter;
     DevBuf own_gray, own_depth;  // dense mode: the keyframes' level 0 and depth maps (re-read by every evaluation) live in the handle
+    // Depth filter (vors_trackers_enable_depth_filter; off: nothing below exists and no launch changes). The planes belong to the batch
+    // handle's resources (counted by its workspace figure, freed with it), [n_seq][S0] each:
+    //   zkey          the keyed z-buffer of a promotion
+    //   fused         the merge's depth output. Sparse modes: it IS the keyframe depth (nothing else reads a keyframe's depth map there).
+    //                 Dense mode: staging — the splat reads own_depth, the keyframe depth — copied into own_depth for the promoted sequences
+    //   weight        the keyframes' weights, read by the splat and gathered by the merge at the SOURCE pixel, hence:
+    //   stage_weight  the merge's weight output, copied into `weight` for the promoted sequences
+    struct DepthFilter {
+        bool on = false;
+        float tol_m = 0.f;
+        int max_weight = 255, fill_min_weight = 0;
+        uint64_t* zkey = nullptr;
+        uint16_t* fused = nullptr;
+        uint8_t *weight = nullptr, *stage_weight = nullptr;
+    } filter;
+    const uint16_t* keyframe_depth() const {
+        return batch->g.mode == VORS_CANDIDATES_DENSE ? static_cast<const uint16_t*>(own_depth.p) : filter.fused;
+    }
     ~vors_trackers() { vors_batch_destroy(batch); }
 };
 
@@ -59,6 +77,29 @@ static vors_status trackers_promote(vors_trackers* t, const uint8_t* d_gray, con
     gm.sel_count = t->promo_count.as<int>();
     if (depth_ready) HIP_TRY(hipStreamWaitEvent(s, depth_ready, 0));
     STAGE_BEGIN(b, 1, s);
+    if (t->filter.on) {
+        // The OLD keyframes of the promoted sequences (records; dense mode: own_gray / own_depth; weights) splatted at the final models of
+        // this frame's LM stage and merged with the measured depth. Everything the keyframe stage below overwrites is read here, before
+        // it in stream order; the merge writes planes nothing here reads. From here on the fused map stands for d_depth.
+        const bool dense = b->g.mode == VORS_CANDIDATES_DENSE;
+        FuseDepthCall call{{Pyramid{nullptr, nullptr}, Pyramid{dense ? t->own_gray.as<uint8_t>() : nullptr, b->kf_upper},
+                            dense ? t->own_depth.as<uint16_t>() : nullptr, b->rec}};
+        call.n_pairs = n;
+        call.models = reinterpret_cast<const float*>(t->stats.p);  // (lm_model is the head of vors_pair_stats)
+        call.model_stride = (int)(sizeof(vors_pair_stats) / 4);
+        call.cur_depth = d_depth;
+        call.tol_m = t->filter.tol_m;
+        call.kf_weight = t->filter.weight;
+        call.max_weight = t->filter.max_weight;
+        call.fill_min_weight = t->filter.fill_min_weight;
+        call.zkey = t->filter.zkey;
+        call.fused_depth = t->filter.fused;
+        call.fused_weight = t->filter.stage_weight;
+        call.counts = nullptr;
+        launch_lm_fuse_depth_selected(gm, call, s);
+        launch_promote_copy(gm, t->filter.stage_weight, (size_t)b->g.S0, t->filter.weight, (size_t)b->g.S0, (size_t)b->g.S0, n, s);
+        d_depth = t->filter.fused;
+    }
     if (b->g.mode == VORS_CANDIDATES_DENSE) {
         const size_t S = (size_t)b->g.S0;
         launch_promote_copy(gm, d_gray, S, t->own_gray.p, S, S, n, s);
@@ -152,7 +193,74 @@ static vors_status tracker_upload(vors_tracker* t, const uint8_t* gray, const ui
     return st != VORS_OK ? st : tracker_upload_depth(t, depth);
 }
 
+// The filter's state of frame 0: the keyframe depth is the measured depth, seen once where it is non-zero.
+static vors_status trackers_filter_init(vors_trackers* t, const uint16_t* d_depth, hipStream_t s) {
+    const size_t n = (size_t)t->n_seq, S = (size_t)t->batch->g.S0;
+    if (t->batch->g.mode != VORS_CANDIDATES_DENSE) HIP_TRY(hipMemcpyAsync(t->filter.fused, d_depth, n * S * 2, hipMemcpyDeviceToDevice, s));
+    launch_depth_weight_init(d_depth, t->filter.weight, n * S, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+// The switch itself: the refusals of vors_batch_fuse_depth, then every plane at once.
+static vors_status trackers_filter_enable(vors_trackers* t, float tol_m, int max_weight, int fill_min_weight) {
+    if (t->filter.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: the filter is already enabled");
+    if (!(tol_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: tol_m must be >= 0 (and not NaN)");
+    if (max_weight < 1 || max_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: max_weight must be in 1..255");
+    if (fill_min_weight < 0 || fill_min_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: fill_min_weight must be in 0..255");
+    vors_batch* b = t->batch;
+    DeviceGuard guard(b->device);
+    const size_t planes = (size_t)t->n_seq * (size_t)b->g.S0;
+    b->own.alloc(&t->filter.zkey, planes);
+    b->own.alloc(&t->filter.fused, planes);
+    b->own.alloc(&t->filter.weight, planes);
+    b->own.alloc(&t->filter.stage_weight, planes);
+    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the filter stays off)
+        const hipError_t e = b->own.err;
+        b->own.err = hipSuccess;
+        (void)hipGetLastError();
+        return fail(VORS_ERR_HIP, std::string("hipMalloc (depth filter planes): ") + hipGetErrorString(e));
+    }
+    t->filter.tol_m = tol_m;
+    t->filter.max_weight = max_weight;
+    t->filter.fill_min_weight = fill_min_weight;
+    t->filter.on = true;
+    return VORS_OK;
+}
+
 extern "C" {
+
+vors_status vors_trackers_enable_depth_filter(vors_trackers* t, float tol_m, int max_weight, int fill_min_weight) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: the handle t is NULL");
+    if (t->initialised)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: legal only before vors_trackers_init (the weights would have no history)");
+    return trackers_filter_enable(t, tol_m, max_weight, fill_min_weight);
+}
+
+vors_status vors_trackers_keyframe_depth(const vors_trackers* t, const uint16_t** d_depth, const uint8_t** d_weight) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "keyframe_depth: the handle t is NULL");
+    if (!t->filter.on) return fail(VORS_ERR_INVALID_ARGUMENT, "keyframe_depth: the depth filter is not enabled (vors_trackers_enable_depth_filter)");
+    if (d_depth) *d_depth = t->keyframe_depth();
+    if (d_weight) *d_weight = t->filter.weight;
+    return VORS_OK;
+}
+
+vors_status vors_trackers_workspace_bytes(const vors_trackers* t, uint64_t* bytes) {
+    if (!t || !bytes) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    return vors_batch_workspace_bytes(t->batch, bytes);
+}
+
+vors_status vors_tracker_enable_depth_filter(vors_tracker* t, float tol_m, int max_weight, int fill_min_weight) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: the handle t is NULL");
+    if (t->has_last) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: legal only before the first vors_tracker_track");
+    vors_status st = trackers_filter_enable(t->seq, tol_m, max_weight, fill_min_weight);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    // t->depth still holds the first frame's depth map (create ordered its upload before everything on s_main); the next upload
+    // waits for ev_frame_done, which therefore moves behind this reader
+    if ((st = trackers_filter_init(t->seq, t->depth.as<uint16_t>(), t->s_main)) != VORS_OK) return st;
+    HIP_TRY(hipEventRecord(t->ev_frame_done, t->s_main));
+    return VORS_OK;
+}
 
 vors_status vors_trackers_create(const vors_config* cfg, int n_sequences, int rows, int cols, vors_trackers** out) {
     int dev = 0;
@@ -231,6 +339,7 @@ vors_status vors_trackers_init(vors_trackers* t, const uint8_t* d_gray, const ui
     HIP_TRY(hipMemsetAsync(t->status.p, 0, n * sizeof(int32_t), s));
     HIP_TRY(hipMemsetAsync(t->frame_counter.p, 0, sizeof(int), s));
     HIP_TRY(hipGetLastError());
+    if (t->filter.on && (st = trackers_filter_init(t, d_depth, s)) != VORS_OK) return st;
     t->frame_index = 0;
     t->initialised = true;
     return VORS_OK;

@@ -132,6 +132,10 @@ class Tracker {  // inverse_compositional.rs:31-34
     const vors_pair_stats& last_stats() const { return last_; }
     int last_status() const { return last_status_; }
     void set_logging(bool on) { log_ = on; }
+    // Extension: the recursive depth filter across keyframe promotions (vors_tracker_enable_depth_filter). Before the first track().
+    void enable_depth_filter(Float tol_m, int max_weight = 255, int fill_min_weight = 0) {
+        check(vors_tracker_enable_depth_filter(h_, tol_m, max_weight, fill_min_weight));
+    }
 
    private:
     friend struct Config;

@@ -4,8 +4,10 @@
 // and prints one trajectory line `timestamp tx ty tz qx qy qz qw` per tracked frame on stdout (vors_track.rs:46-64).
 // Optional trailing flags (not in the reference): `--quiet` silences the per-frame stderr logs; `--arith exact|fused|reference` selects the
 // per-point arithmetic (include/vors_hip.h VORS_ARITH_*, default reference); `--candidates c2f|dense|dso` the level-0 mask source
-// (default c2f = the reference's coarse-to-fine selection).
+// (default c2f = the reference's coarse-to-fine selection); `--depth-filter TOL_M[,MAX_WEIGHT[,FILL_MIN_WEIGHT]]` switches the recursive
+// depth filter across keyframe promotions on (include/vors_hip.h vors_tracker_enable_depth_filter; defaults 255 and 0).
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -34,8 +36,27 @@ static std::string join(const std::string& parent, const std::string& rel) {  //
     return parent.empty() ? rel : parent + "/" + rel;
 }
 
+// "TOL_M[,MAX_WEIGHT[,FILL_MIN_WEIGHT]]": every field a whole number of its kind, nothing after the last. The VALUES are judged by the library.
+static bool parse_depth_filter(const std::string& val, float& tol_m, int& max_weight, int& fill_min_weight) {
+    if (val.empty()) return false;
+    const char* p = val.c_str();
+    char* end = nullptr;
+    tol_m = std::strtof(p, &end);
+    if (end == p) return false;
+    int* ints[2] = {&max_weight, &fill_min_weight};
+    for (int k = 0; k < 2 && *end == ','; ++k) {
+        p = end + 1;
+        const long v = std::strtol(p, &end, 10);
+        if (end == p || v < -1000000 || v > 1000000) return false;
+        *ints[k] = (int)v;
+    }
+    return *end == '\0';
+}
+
 int main(int argc, char** argv) {
-    bool quiet = false;
+    bool quiet = false, depth_filter = false;
+    float filter_tol_m = 0.0f;
+    int filter_max_weight = 255, filter_fill_min_weight = 0;
     int arithmetic = VORS_ARITH_REFERENCE, candidates = VORS_CANDIDATES_COARSE_TO_FINE;
     bool bad_flag = false;
     for (int a = 3; a < argc && !bad_flag; ++a) {  // extension flags follow the reference's two positional arguments
@@ -47,6 +68,9 @@ int main(int argc, char** argv) {
             ++a;
         } else if (flag == "--candidates" && (val == "c2f" || val == "dense" || val == "dso")) {
             candidates = val == "dense" ? VORS_CANDIDATES_DENSE : (val == "dso" ? VORS_CANDIDATES_DSO : VORS_CANDIDATES_COARSE_TO_FINE);
+            ++a;
+        } else if (flag == "--depth-filter" && parse_depth_filter(val, filter_tol_m, filter_max_weight, filter_fill_min_weight)) {
+            depth_filter = true;
             ++a;
         } else {
             bad_flag = true;
@@ -99,6 +123,7 @@ int main(int argc, char** argv) {
         track::Tracker tracker = config.init(associations[0].depth_timestamp, {depth.data(), (int)h, (int)w, VORS_ROW_MAJOR},
                                              associations[0].color_timestamp, {gray.data(), (int)h, (int)w, VORS_ROW_MAJOR});
         tracker.set_logging(!quiet);
+        if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);

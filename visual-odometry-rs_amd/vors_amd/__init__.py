@@ -94,7 +94,7 @@ class vors_obs(C.Structure):
 EXPORTED_SYMBOLS = [
     "vors_last_error", "vors_device_count", "vors_device_info", "vors_abi_version", "vors_selfcheck_isqrt",
     "vors_tracker_create", "vors_tracker_track", "vors_tracker_track_checked", "vors_tracker_current_frame", "vors_tracker_last_stats",
-    "vors_tracker_keyframe", "vors_tracker_destroy",
+    "vors_tracker_keyframe", "vors_tracker_enable_depth_filter", "vors_tracker_destroy",
     "vors_track_pairs",
     "vors_batch_create", "vors_batch_create_on", "vors_batch_device", "vors_batch_track_pairs", "vors_batch_prepare_keyframes", "vors_batch_track_current",
     "vors_batch_workspace_bytes", "vors_batch_enable_kernel_timing", "vors_batch_kernel_times", "vors_batch_last_kernel_ms",
@@ -112,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "vors_multi_destroy", "vors_multi_rccl_version",
     "vors_trackers_create", "vors_trackers_create_on", "vors_trackers_count", "vors_trackers_init", "vors_trackers_track", "vors_trackers_state",
     "vors_trackers_current_frames", "vors_trackers_last_stats", "vors_trackers_enable_kernel_timing", "vors_trackers_kernel_times", "vors_trackers_destroy",
+    "vors_trackers_enable_depth_filter", "vors_trackers_keyframe_depth", "vors_trackers_workspace_bytes",
     "vors_synth_render_frames",
     "vors_pipeline_create", "vors_pipeline_submit", "vors_pipeline_wait", "vors_pipeline_drain", "vors_pipeline_destroy",
 ]
@@ -168,6 +169,10 @@ def lib():
         _lib.vors_trackers_kernel_times.argtypes = [vp, i, vp, i, C.POINTER(i)]
         _lib.vors_trackers_destroy.argtypes = [vp]
         _lib.vors_trackers_destroy.restype = None
+        _lib.vors_trackers_enable_depth_filter.argtypes = [vp, f, i, i]
+        _lib.vors_trackers_keyframe_depth.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        _lib.vors_trackers_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+        _lib.vors_tracker_enable_depth_filter.argtypes = [vp, f, i, i]
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
         _lib.vors_batch_track_pairs.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib.vors_pipeline_create.argtypes = [i, C.POINTER(vors_config), i, i, i, i, C.POINTER(vp)]
@@ -299,10 +304,37 @@ class Config:
         return Tracker(self, keyframe_depth_timestamp, depth_map, keyframe_img_timestamp, img, layout)
 
 
+def _depth_filter_args(spec):
+    """None, a number or a tuple (tol_m[, max_weight[, fill_min_weight]]) -> None or (float, int, int) with the defaults filled in. Only
+    the SHAPE of the argument is judged here; the values are judged by the library, in one place for every caller."""
+    if spec is None:
+        return None
+    if isinstance(spec, (int, float, np.integer, np.floating)) and not isinstance(spec, bool):
+        spec = (spec,)
+    try:
+        spec = tuple(spec)
+    except TypeError:
+        raise VorsError(f"depth_filter: expected None or (tol_m[, max_weight[, fill_min_weight]]), got {spec!r}") from None
+    if not 1 <= len(spec) <= 3:
+        raise VorsError(f"depth_filter: expected 1 to 3 values (tol_m[, max_weight[, fill_min_weight]]), got {len(spec)}")
+    tol_m, max_weight, fill_min_weight = (spec + (255, 0)[len(spec) - 1:])[:3]
+    for name, v in (("max_weight", max_weight), ("fill_min_weight", fill_min_weight)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise VorsError(f"depth_filter: {name} must be an integer, got {v!r}")
+    try:
+        tol_m = float(tol_m)
+    except (TypeError, ValueError):
+        raise VorsError(f"depth_filter: tol_m must be a number, got {tol_m!r}") from None
+    return tol_m, int(max_weight), int(fill_min_weight)
+
+
 class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
-    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR):
+    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None):
+        """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
+        (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter)."""
+        depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -313,6 +345,8 @@ class Tracker:
         cfg = config.to_c()
         _check(lib().vors_tracker_create(C.byref(cfg), depth_t, _ptr(depth_map), img_t, _ptr(img), rows, cols, layout,
                                          C.byref(self._h)))
+        if depth_filter is not None:
+            _check(lib().vors_tracker_enable_depth_filter(self._h, *depth_filter))
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -818,6 +852,7 @@ class Trackers:
 
     def __init__(self, config, n_sequences, rows, cols, device=None):
         self.config, self.n, self.rows, self.cols = config, n_sequences, rows, cols
+        self._device = None if device is None else int(device)
         self._h = C.c_void_p()
         cfg = config.to_c()
         if device is None:
@@ -865,6 +900,29 @@ class Trackers:
         _check(lib().vors_trackers_last_stats(self._h, _ptr(out), Batch._stream()))
         return out
 
+    def enable_depth_filter(self, tol_m, max_weight=255, fill_min_weight=0):
+        """Recursive depth filter across keyframe promotions (vors_trackers_enable_depth_filter): before init(), once. A promoted frame's
+        keyframe is then built on the depth FUSED from the old keyframe and the measurement (Batch.fuse_depth's rule), on the device."""
+        _check(lib().vors_trackers_enable_depth_filter(self._h, *_depth_filter_args((tol_m, max_weight, fill_min_weight))))
+
+    def keyframe_depth(self, copy=True):
+        """-> (depth [n, rows, cols] int16 tensor holding the u16 payload, weight [n, rows, cols] uint8) of every sequence's current keyframe
+        (vors_trackers_keyframe_depth), valid in stream order after the last init() / track(). copy=False: views of the handle's own
+        planes, which the next track() rewrites and which die with this object."""
+        import torch
+        d, w = C.c_void_p(), C.c_void_p()
+        _check(lib().vors_trackers_keyframe_depth(self._h, C.byref(d), C.byref(w)))
+        dev = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
+        shape = (self.n, self.rows, self.cols)
+        depth = _device_view(d.value, shape, "<i2", dev)
+        weight = _device_view(w.value, shape, "|u1", dev)
+        return (depth.clone(), weight.clone()) if copy else (depth, weight)
+
+    def workspace_bytes(self):
+        b = C.c_uint64()
+        _check(lib().vors_trackers_workspace_bytes(self._h, C.byref(b)))
+        return b.value
+
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
 
@@ -873,6 +931,18 @@ class Trackers:
         n = C.c_int()
         _check(lib().vors_trackers_kernel_times(self._h, Batch.STAGES[stage], _ptr(out), 4096, C.byref(n)))
         return out[:n.value].copy()
+
+
+class _DeviceArray:
+    """A device pointer the library owns, dressed for torch.as_tensor (__cuda_array_interface__)."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+def _device_view(ptr, shape, typestr, device):
+    import torch
+    return torch.as_tensor(_DeviceArray(ptr, shape, typestr), device=device)
 
 
 def synth_render_frames(seeds, salts, xis, rows, cols, cam5, invalid_percent=2, device="cuda"):
