@@ -118,7 +118,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    likewise; + vors_batch_reproject_depth, vors_to_depth, vors_from_depth, likewise; + vors_batch_point_cloud,
                               *    vors_camera_back_project, vors_camera_project, likewise; + vors_batch_fuse_depth, vors_fuse_depth_pixels,
                               *    likewise; + vors_trackers_enable_depth_filter, vors_trackers_keyframe_depth, vors_trackers_workspace_bytes,
-                              *    vors_tracker_enable_depth_filter, likewise) */
+                              *    vors_tracker_enable_depth_filter, likewise; + vors_trackers_enable_map, vors_trackers_map,
+                              *    vors_tracker_enable_map, vors_tracker_read_map, vors_map_segment, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -145,6 +146,23 @@ vors_status vors_tracker_keyframe(const vors_tracker* t, double* timestamp, floa
  * refusals. vors_tracker_create already took the first frame, so the call is legal until the first vors_tracker_track (refused after it and
  * when repeated); the weights of the first keyframe are derived at this call from the depth map the tracker holds. */
 vors_status vors_tracker_enable_depth_filter(vors_tracker* t, float tol_m, int max_weight, int fill_min_weight);
+/* One keyframe of a sequence's KEYFRAME MAP (vors_trackers_enable_map, below): 40 bytes, one per keyframe, in order of creation. */
+typedef struct vors_map_segment {
+    int32_t  frame;      /* frame index of the keyframe (0 = the init frame): the value vors_trackers_state reports as keyframe index */
+    uint32_t first;      /* rank of its first point in the sequence's list = the sequence's total before it */
+    uint32_t count;      /* its kept points — NOT clipped by capacity */
+    float    pose7[7];   /* the keyframe camera -> world pose the points were carried through */
+} vors_map_segment;
+/* The keyframe map of vors_trackers_enable_map (below) for the single sequence, its N = 1 case: same arguments, same refusals (min_weight
+ * >= 2 needs vors_tracker_enable_depth_filter before it). vors_tracker_create already made keyframe 0, so the call is legal until the
+ * first vors_tracker_track (refused after it and when repeated) and itself emits keyframe 0's cloud, on the tracker's stream. */
+vors_status vors_tracker_enable_map(vors_tracker* t, int level, int capacity, int max_keyframes, int min_weight);
+/* The map so far to HOST buffers, each nullable; synchronises. xyz [capacity][3], pixel [capacity], gray [capacity]: the first
+ * min(total, capacity, the handle's capacity) points; segments [max_segments]: the first min(keyframes, max_segments, the handle's
+ * max_keyframes) records. *count and *n_segments are the UNCLIPPED totals. capacity / max_segments negative, or no enabled map:
+ * VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map(vors_tracker* t, int capacity, float* xyz, uint32_t* pixel, uint8_t* gray, uint32_t* count,
+                                  int max_segments, vors_map_segment* segments, uint32_t* n_segments);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -204,6 +222,37 @@ vors_status vors_trackers_enable_depth_filter(vors_trackers* t, float tol_m, int
  * enabled filter: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_keyframe_depth(const vors_trackers* t, const uint16_t** d_depth, const uint8_t** d_weight);
 vors_status vors_trackers_workspace_bytes(const vors_trackers* t, uint64_t* bytes);
+/* KEYFRAME MAP (opt-in; without this call nothing changes: no launch, no allocation, no kernel argument on any existing path). Every time
+ * a sequence gets a new keyframe — vors_trackers_init: every sequence; vors_trackers_track: exactly the promoted ones — the keyframe's
+ * cloud is appended, on the device and in stream order, to a list the handle owns for that sequence, with one vors_map_segment per
+ * keyframe. The emission comes after the keyframe stage (REFERENCE arithmetic: after the column-major sort, so the records are in their
+ * final order) as masked launches over the promotion list, and reads the handle's own data only: the records, in dense mode the handle's
+ * copy of the keyframe image and depth, and the keyframe pose, which the track call has already moved forward. Nothing of the caller's
+ * frames is read, and a sequence that does not promote is touched by no launch.
+ * Points: vors_batch_point_cloud's rule (section 2), unchanged — the usable points of `level` (extract_z's set) in ascending slot order of
+ * the level's source: row-major raster order in dense mode, the order vors_batch_get_points reports for the candidate lists. Per point:
+ * xyz = keyframe pose * back_project(K_level, x, y, 1.0f / idepth) in the reference's per-point arithmetic (the bits of
+ * vors_camera_back_project; the pose is ALWAYS applied), pixel = x | y << 16, gray = the template intensity.
+ * Keep rule: min_weight <= 1 keeps every usable point and reads no weight. min_weight >= 2 keeps a point iff the depth filter's weight at
+ * its pixel — the NEW keyframe's, after the promotion — is >= min_weight; at init every weight is 1 and nothing is kept. It needs
+ * vors_trackers_enable_depth_filter BEFORE this call and level == 0 (the weight plane exists at full resolution only).
+ * Legal after create and before vors_trackers_init, once. VORS_ERR_INVALID_ARGUMENT, with nothing allocated and nothing enqueued: NULL
+ * handle, repeated call, call after init, level outside 0..nb_levels-1, capacity < 1, max_keyframes < 1, min_weight outside 0..255,
+ * min_weight >= 2 without the filter or with level != 0. The call allocates, as part of vors_trackers_workspace_bytes' figure and freed
+ * with the handle, n * capacity * 17 bytes of lists, n * max_keyframes * 40 bytes of segments, 8 n bytes of counters and the count
+ * workspace of the pass (4 bytes per sequence and chunk of `level`, vors_batch_point_cloud's cut); no later call allocates.
+ * vors_trackers_init zeroes both counters on the stream: a handle that is initialised again starts an empty map. */
+vors_status vors_trackers_enable_map(vors_trackers* t, int level, int capacity, int max_keyframes, int min_weight);
+/* DEVICE pointers, owned by the handle and valid for its life, contents valid in stream order after the last init / track; every output
+ * is nullable:
+ *   d_xyz [n][capacity][3] f32, d_pixel [n][capacity] u32, d_gray [n][capacity] u8   the lists
+ *   d_counts [n] u32       running total of kept points of a sequence; may exceed capacity, saturates at 0xFFFFFFFF. Exactly the entries
+ *                          of rank < min(total, capacity) are written: later points are dropped but COUNTED, here and in their segment
+ *   d_segments [n][max_keyframes] vors_map_segment, d_n_segments [n] u32   every keyframe created is counted, the first max_keyframes
+ *                          records are written
+ * The order of ranks is a function of the sequence's own frames alone. Without an enabled map: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map(const vors_trackers* t, const float** d_xyz, const uint32_t** d_pixel, const uint8_t** d_gray,
+                              const uint32_t** d_counts, const vors_map_segment** d_segments, const uint32_t** d_n_segments);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -491,7 +540,8 @@ vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, co
  * Contracts of vors_batch_residual_maps: enqueued on hip_stream, NOT synchronised; no allocation after the first call on a handle (the
  * first call creates the per-(pair, chunk) count workspace, which vors_batch_workspace_bytes counts from then on); in dense mode the
  * keyframe's d_kf_gray / d_kf_depth must still be alive; touches nothing track computes or reads; vors_trackers handles are out of
- * scope. Two launches ordered by the stream; no workgroup waits for another and there is no atomic. */
+ * scope: the sequence handles have their own switch, vors_trackers_enable_map / vors_tracker_enable_map (section 1,
+ * DESIGN.md 7h). Two launches ordered by the stream; no workgroup waits for another and there is no atomic. */
 vors_status vors_batch_point_cloud(vors_batch* b, int n_pairs, int level,
                                    const void* d_poses7 /* nullable */, size_t pose_stride_bytes,
                                    const uint8_t* d_keep /* nullable */, int capacity,

@@ -360,6 +360,42 @@ struct PointCloudArgs {
     int ws_chunks;
     int wide_keep;              // the mask planes are 4-byte aligned: a dense quad reads its four bytes at once
 };
+// The keyframe map of the lock-step trackers (vors_trackers_enable_map): the point-cloud pass of one level for the SELECTED sequences
+// (Geom::sel_list, null = all), appended to per-sequence lists with one segment record per keyframe. Every buffer is the handle's own.
+struct PointCloudAppendCall : LmScene {
+    int n_seq, lvl;
+    const float* kf_poses;      // [seq][7] keyframe camera -> world, always applied
+    const int32_t* kf_frame;    // [seq] keyframe index
+    const uint8_t* weight;      // [seq][S0] the depth filter's weights; read only with min_weight >= 2 (level 0)
+    int min_weight;
+    int capacity, max_keyframes;
+    float* xyz;                 // [seq][capacity][3]
+    uint32_t* pixel;            // [seq][capacity]
+    uint8_t* gray;              // [seq][capacity]
+    uint32_t* counts;           // [seq] running total of kept points (saturating)
+    vors_map_segment* segments; // [seq][max_keyframes]
+    uint32_t* n_segments;       // [seq] keyframes created
+    uint32_t* ws;               // [seq][ws_chunks] kept points per chunk of the keyframe being appended
+    int ws_chunks;
+};
+// What its kernels get.
+struct PointCloudAppendArgs {
+    int lvl, chunk_points;
+    const float* kf_poses;
+    const int32_t* kf_frame;
+    const uint8_t* weight;      // null: keep every usable point
+    int keep_min;
+    int capacity, max_keyframes;
+    float* xyz;
+    uint32_t* pixel;
+    uint8_t* gray;
+    uint32_t* counts;
+    vors_map_segment* segments;
+    uint32_t* n_segments;
+    uint32_t* ws;
+    int ws_chunks;
+    int wide_keep;              // the weight planes are 4-byte aligned: a dense quad reads its four bytes at once
+};
 // Depth fusion of level 0 of a prepared batch at one model per pair (vors_batch_fuse_depth): the keyframe's points splatted into the
 // current frame through a KEYED z-buffer (bits(Z') << 32 | source pixel, one 64-bit minimum per landing point), then merged per current
 // pixel with the measured depth (lie.h fuse_depth_pixel). zkey is required; the other outputs are nullable.
@@ -496,6 +532,10 @@ void launch_lm_fuse_depth_selected(const Geom& g, const FuseDepthCall& call, hip
 // point_cloud_kernel: a counting launch into call.ws, then a ranking and writing launch; no workgroup waits for another): enqueued, not
 // synchronised. Reads no current image.
 void launch_lm_point_cloud(const Geom& g, const PointCloudCall& call, hipStream_t s);
+// The same pass as MASKED launches that APPEND (the keyframe map of vors_trackers; lm_kernels.hip point_cloud_append_kernel,
+// point_cloud_commit_kernel): count, write behind the sequence's running total, commit the segment record and the totals. call.n_seq is
+// the extent of the pair dimension (all sequences); only the sequences of g.sel_list (null: all) are touched.
+void launch_lm_point_cloud_append(const Geom& g, const PointCloudAppendCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

@@ -2945,9 +2945,10 @@ struct CloudPts {
     float tmpl[G];
     bool kept[G];
 };
-template <class Src>
+// THRESH (the keyframe map of the trackers, point_cloud_append_kernel): the plane holds weights and a point is kept from `keep_min` on.
+template <bool THRESH = false, class Src>
 __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::Cursor& cur, int last, int cols, const uint8_t* keep, bool wide_keep,
-                                            CloudPts<Src::G>& o) {
+                                            CloudPts<Src::G>& o, uint32_t keep_min = 1) {
     constexpr int G = Src::G;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -2987,16 +2988,18 @@ __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::
         o.P[g] = V3{pos[g].X, pos[g].Y, pos[g].Z};
         o.xy[g] = cloud_xy(src, raw, g);
         o.tmpl[g] = pos[g].tmpl;
-        o.kept[g] = pos[g].tmpl >= 0.f && kb[g] != 0;
+        if constexpr (THRESH) o.kept[g] = pos[g].tmpl >= 0.f && kb[g] >= keep_min;
+        else o.kept[g] = pos[g].tmpl >= 0.f && kb[g] != 0;
     }
 }
-template <class Src>
-__device__ __forceinline__ uint32_t cloud_count_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep) {
+template <bool THRESH = false, class Src>
+__device__ __forceinline__ uint32_t cloud_count_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep,
+                                                      uint32_t keep_min = 1) {
     constexpr int G = Src::G;
     uint32_t n = 0;
     for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
         CloudPts<G> pts;
-        cloud_fetch(src, cur, last, cols, keep, wide_keep, pts);
+        cloud_fetch<THRESH>(src, cur, last, cols, keep, wide_keep, pts, keep_min);
 #pragma unroll
         for (int g = 0; g < G; ++g) n += pts.kept[g] ? 1u : 0u;
     }
@@ -3046,16 +3049,16 @@ __device__ __forceinline__ void cloud_store(const CloudOut& o, uint32_t rank, co
     if (o.pixel) o.pixel[rank] = xy;
     if (o.gray) o.gray[rank] = (uint8_t)(int)tmpl;
 }
-template <class Src>
+template <bool THRESH = false, class Src>
 __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep, uint32_t base,
-                                                  const CloudOut& out, uint32_t* lds) {
+                                                  const CloudOut& out, uint32_t* lds, uint32_t keep_min = 1) {
     constexpr int G = Src::G;
     static_assert(G != 2 || std::is_same<Src, SlimSrc>::value, "G = 2 is the candidate lists' interleaved pair of slots");
     int par = 0;
     for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first);
          __builtin_amdgcn_readfirstlane(cur.i - (int)threadIdx.x) < last && base < out.capacity; cur = src.template advance<RMAPS_BLOCK>(cur)) {
         CloudPts<G> pts;
-        cloud_fetch(src, cur, last, cols, keep, wide_keep, pts);
+        cloud_fetch<THRESH>(src, cur, last, cols, keep, wide_keep, pts, keep_min);
         if constexpr (G == 2) {  // slots i and i + BLOCK: the first points of all threads come before the second ones
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -3157,6 +3160,104 @@ void launch_lm_point_cloud(const Geom& g_in, const PointCloudCall& call, hipStre
         if (!write && call.counts)
             hipLaunchKernelGGL(point_cloud_total_kernel, dim3((np + 63) / 64), dim3(64), 0, s, call.ws, call.ws_chunks, chunks, pair0, np, call.counts);
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The keyframe map of the lock-step trackers (vors_trackers_enable_map): the pass above as MASKED launches over the promotion list
+// (Geom::sel_list; null = every sequence, vors_trackers_init), APPENDING to one list per sequence. Siblings: the kernels above are
+// untouched. The host does not know how many sequences promote, so the grids are sized for all of them. Three launches, ordered by the
+// stream alone — no atomic, no flag, no workgroup that waits for another:
+//   COUNT   point_cloud_kernel<DENSE, false>'s body on the selected sequence -> ws[seq][chunk]
+//   WRITE   point_cloud_kernel<DENSE, true>'s body with base = counts[seq] (the sequence's running total, still the OLD one) + the
+//           counts of the chunks before its own, the lists of the sequence at seq * capacity, and the keyframe pose of the sequence
+//           (always applied). A base that has reached the capacity stores nothing.
+//   COMMIT  one thread per selected sequence: the segment record {keyframe index, old total, this keyframe's count, pose} if there is
+//           room for it, then n_segments += 1 and counts += count (saturating). After WRITE, which reads the old total.
+// Keep rule: min_weight <= 1 no plane is read; otherwise `weight` is the depth filter's weight plane (level 0) and a point is kept from
+// min_weight on.
+// ------------------------------------------------------------------------------------------------------------
+template <bool DENSE, bool WRITE>
+__global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                         const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                         const uint16_t* __restrict__ kf_depth, Records rec, PointCloudAppendArgs a) {
+    __shared__ uint32_t lds[2 * PCLOUD_WAVES];
+    const int seq = select_pair(g, blockIdx.y), chunk = blockIdx.x, n_chunks = gridDim.x;
+    if (seq < 0) return;
+    const int cols = g.lv[a.lvl].cols;
+    const uint8_t* keep = a.weight ? a.weight + (size_t)seq * g.S0 : nullptr;  // (set at level 0 only)
+    uint32_t* ws = a.ws + (size_t)seq * a.ws_chunks;
+    uint32_t base = 0, n = 0;
+    CloudOut out{};
+    if constexpr (WRITE) {
+        unsigned long long b64 = a.counts[seq];
+        for (int k = 0; k < chunk; ++k) b64 += ws[k];  // (uniform)
+        base = b64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b64;  // (>= capacity: nothing is stored)
+        out.has_pose = true;
+        out.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
+        out.capacity = (uint32_t)a.capacity;
+        out.xyz = a.xyz + (size_t)seq * a.capacity * 3;
+        out.pixel = a.pixel + (size_t)seq * a.capacity;
+        out.gray = a.gray + (size_t)seq * a.capacity;
+    }
+    with_level_source<DENSE, true, false>(g, a.lvl, seq, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // the cut of point_cloud_kernel
+        const int points = DENSE ? g.lv[a.lvl].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        if constexpr (WRITE) cloud_write_sweep<true>(src, first, last, cols, keep, a.wide_keep != 0, base, out, lds, (uint32_t)a.keep_min);
+        else n = cloud_count_sweep<true>(src, first, last, cols, keep, a.wide_keep != 0, (uint32_t)a.keep_min);
+    });
+    if constexpr (!WRITE) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int wv = 0; wv < PCLOUD_WAVES; ++wv) t += lds[wv];
+            ws[chunk] = t;  // stored, not accumulated: the workspace needs no clearing
+        }
+    }
+}
+__global__ __launch_bounds__(64) void point_cloud_commit_kernel(Geom g, PointCloudAppendArgs a, int n, int chunks) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= n) return;
+    const int seq = select_pair(g, k);
+    if (seq < 0) return;
+    uint32_t total = 0;
+    for (int c = 0; c < chunks; ++c) total += a.ws[(size_t)seq * a.ws_chunks + c];
+    const uint32_t first = a.counts[seq], idx = a.n_segments[seq];
+    if (idx < (uint32_t)a.max_keyframes) {
+        vors_map_segment* seg = a.segments + (size_t)seq * a.max_keyframes + idx;
+        seg->frame = a.kf_frame[seq];
+        seg->first = first;
+        seg->count = total;
+        for (int q = 0; q < 7; ++q) seg->pose7[q] = a.kf_poses[7 * (size_t)seq + q];
+    }
+    a.n_segments[seq] = idx == 0xFFFFFFFFu ? idx : idx + 1u;
+    a.counts[seq] = first + total < first ? 0xFFFFFFFFu : first + total;
+}
+// call.n_seq: the sequences of the handle (the extent of the pair dimension); g_in.sel_list / sel_count: the ones that get a new segment
+// (null: all of them). Every buffer of the call is required but `weight`.
+void launch_lm_point_cloud_append(const Geom& g_in, const PointCloudAppendCall& call, hipStream_t s) {
+    Geom g = g_in;
+    g.wide_loads_ok = wide_loads_ok(call);
+    const bool dense = g.mode == VORS_CANDIDATES_DENSE;
+    const bool thresh = call.min_weight >= 2 && call.weight != nullptr;
+    PointCloudAppendArgs a{call.lvl, eval_pairs_chunk_points(g), call.kf_poses, call.kf_frame, thresh ? call.weight : nullptr,
+                           thresh ? call.min_weight : 1, call.capacity, call.max_keyframes, call.xyz, call.pixel, call.gray, call.counts,
+                           call.segments, call.n_segments, call.ws, call.ws_chunks,
+                           ((uintptr_t)call.weight % 4 == 0 && (size_t)g.S0 % 4 == 0) ? 1 : 0};
+    const int chunks = std::min(eval_pairs_chunks(g, call.lvl), call.ws_chunks), n = call.n_seq;
+    with_bool(dense, [&](auto d) {
+        launch_on_scene(point_cloud_append_kernel<decltype(d)::value, false>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+        launch_on_scene(point_cloud_append_kernel<decltype(d)::value, true>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+    });
+    hipLaunchKernelGGL(point_cloud_commit_kernel, dim3((n + 63) / 64), dim3(64), 0, s, g, a, n, chunks);
 }
 
 // ------------------------------------------------------------------------------------------------------------

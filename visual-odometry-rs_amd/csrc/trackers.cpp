@@ -1,5 +1,6 @@
 // Sequences: N of them in lock-step on the device (vors_trackers_*), and the single Tracker of the reference as their N = 1 case
 // (vors_tracker_*). Both sit on a batch handle (host_common.h, batch.cpp).
+#include <algorithm>
 #include <cstring>
 #include <memory>
 
@@ -35,11 +36,54 @@ struct vors_trackers {
         uint16_t* fused = nullptr;
         uint8_t *weight = nullptr, *stage_weight = nullptr;
     } filter;
+    // Keyframe map (vors_trackers_enable_map; off: nothing below exists and no launch changes). Lists, segment records, counters and the
+    // count workspace of the point-cloud pass belong to the batch handle's resources, like the filter's planes:
+    //   xyz / pixel / gray  [n_seq][capacity] entries, the clouds of a sequence's keyframes one after the other
+    //   counts, n_segments  [n_seq] running totals (kept points, keyframes)
+    //   segments            [n_seq][max_keyframes]
+    //   ws                  [n_seq][ws_chunks] kept points per chunk of the keyframe being appended
+    struct Map {
+        bool on = false;
+        int level = 0, capacity = 0, max_keyframes = 0, min_weight = 0, ws_chunks = 0;
+        float* xyz = nullptr;
+        uint32_t *pixel = nullptr, *counts = nullptr, *n_segments = nullptr, *ws = nullptr;
+        uint8_t* gray = nullptr;
+        vors_map_segment* segments = nullptr;
+    } map;
     const uint16_t* keyframe_depth() const {
         return batch->g.mode == VORS_CANDIDATES_DENSE ? static_cast<const uint16_t*>(own_depth.p) : filter.fused;
     }
     ~vors_trackers() { vors_batch_destroy(batch); }
 };
+
+// The cloud of the NEW keyframe of every selected sequence (gm.sel_list; null: all) appended to its map. Hazards, all settled by the
+// stream: the emission reads the records, own_gray / own_depth / kf_upper (dense mode) and the filter's weight plane AFTER everything that
+// writes them in the same promotion (keyframe stage, column-major sort, the stage_weight -> weight copy) and the keyframe pose after
+// launch_trackers_advance moved it; the next frame's LM stage only reads them too; the next promotion, which rewrites them, is enqueued
+// behind. It writes the map's own buffers, which nothing else touches (the count workspace is the map's, not vors_batch_point_cloud's).
+static void trackers_map_emit(vors_trackers* t, const Geom& gm, hipStream_t s) {
+    vors_batch* b = t->batch;
+    const bool dense = b->g.mode == VORS_CANDIDATES_DENSE;
+    PointCloudAppendCall call{{Pyramid{nullptr, nullptr}, Pyramid{dense ? t->own_gray.as<uint8_t>() : nullptr, b->kf_upper},
+                               dense ? t->own_depth.as<uint16_t>() : nullptr, b->rec}};
+    call.n_seq = t->n_seq;
+    call.lvl = t->map.level;
+    call.kf_poses = t->kf_poses.as<float>();
+    call.kf_frame = t->kf_frame.as<int32_t>();
+    call.weight = t->map.min_weight >= 2 ? t->filter.weight : nullptr;
+    call.min_weight = t->map.min_weight;
+    call.capacity = t->map.capacity;
+    call.max_keyframes = t->map.max_keyframes;
+    call.xyz = t->map.xyz;
+    call.pixel = t->map.pixel;
+    call.gray = t->map.gray;
+    call.counts = t->map.counts;
+    call.segments = t->map.segments;
+    call.n_segments = t->map.n_segments;
+    call.ws = t->map.ws;
+    call.ws_chunks = t->map.ws_chunks;
+    launch_lm_point_cloud_append(gm, call, s);
+}
 
 // The two halves of vors_trackers_track: Tracker::track up to the keyframe test, and the promotion of the sequences that switch — the
 // only reader of the depth map, which may arrive on another stream (depth_ready). vors_tracker_track runs them apart, with the depth
@@ -116,6 +160,7 @@ static vors_status trackers_promote(vors_trackers* t, const uint8_t* d_gray, con
         if (b->g.mode == VORS_CANDIDATES_DENSE)
             launch_ref_dense_planes_keyframe(gm, Pyramid{t->own_gray.as<uint8_t>(), b->kf_upper}, t->own_depth.as<uint16_t>(), b->rec, n, s);
     }
+    if (t->map.on) trackers_map_emit(t, gm, s);
     STAGE_END(b, 1, s);
     HIP_TRY(hipGetLastError());
     return VORS_OK;
@@ -227,7 +272,105 @@ static vors_status trackers_filter_enable(vors_trackers* t, float tol_m, int max
     return VORS_OK;
 }
 
+// The switch itself: every refusal, then every buffer at once.
+static vors_status trackers_map_enable(vors_trackers* t, int level, int capacity, int max_keyframes, int min_weight) {
+    vors_batch* b = t->batch;
+    if (t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: the map is already enabled");
+    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: level out of range");
+    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: capacity must be >= 1");
+    if (max_keyframes < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: max_keyframes must be >= 1");
+    if (min_weight < 0 || min_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: min_weight must be in 0..255");
+    if (min_weight >= 2 && !t->filter.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: min_weight >= 2 needs the depth filter enabled first (its weights are what is tested)");
+    if (min_weight >= 2 && level != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: min_weight >= 2 needs level 0 (the weight plane exists at full resolution only)");
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)t->n_seq;
+    const int chunks = eval_pairs_chunks(b->g, level);
+    b->own.alloc(&t->map.xyz, n * (size_t)capacity * 3);
+    b->own.alloc(&t->map.pixel, n * (size_t)capacity);
+    b->own.alloc(&t->map.gray, n * (size_t)capacity);
+    b->own.alloc(&t->map.segments, n * (size_t)max_keyframes);
+    b->own.alloc(&t->map.counts, n);
+    b->own.alloc(&t->map.n_segments, n);
+    b->own.alloc(&t->map.ws, n * (size_t)chunks);
+    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the map stays off)
+        const hipError_t e = b->own.err;
+        b->own.err = hipSuccess;
+        (void)hipGetLastError();
+        return fail(VORS_ERR_HIP, std::string("hipMalloc (keyframe map): ") + hipGetErrorString(e));
+    }
+    t->map.level = level;
+    t->map.capacity = capacity;
+    t->map.max_keyframes = max_keyframes;
+    t->map.min_weight = min_weight;
+    t->map.ws_chunks = chunks;
+    t->map.on = true;
+    return VORS_OK;
+}
+// An empty map, then keyframe 0 of every sequence.
+static vors_status trackers_map_init(vors_trackers* t, hipStream_t s) {
+    const size_t n = (size_t)t->n_seq;
+    HIP_TRY(hipMemsetAsync(t->map.counts, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(t->map.n_segments, 0, n * sizeof(uint32_t), s));
+    trackers_map_emit(t, t->batch->g, s);  // (unmasked: the handle's geometry carries no selection)
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
 extern "C" {
+
+vors_status vors_trackers_enable_map(vors_trackers* t, int level, int capacity, int max_keyframes, int min_weight) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: the handle t is NULL");
+    if (t->initialised) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: legal only before vors_trackers_init (keyframe 0 would be missing)");
+    return trackers_map_enable(t, level, capacity, max_keyframes, min_weight);
+}
+
+vors_status vors_trackers_map(const vors_trackers* t, const float** d_xyz, const uint32_t** d_pixel, const uint8_t** d_gray,
+                              const uint32_t** d_counts, const vors_map_segment** d_segments, const uint32_t** d_n_segments) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map: the handle t is NULL");
+    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "map: the keyframe map is not enabled (vors_trackers_enable_map)");
+    if (d_xyz) *d_xyz = t->map.xyz;
+    if (d_pixel) *d_pixel = t->map.pixel;
+    if (d_gray) *d_gray = t->map.gray;
+    if (d_counts) *d_counts = t->map.counts;
+    if (d_segments) *d_segments = t->map.segments;
+    if (d_n_segments) *d_n_segments = t->map.n_segments;
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map(vors_tracker* t, int level, int capacity, int max_keyframes, int min_weight) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: the handle t is NULL");
+    if (t->has_last) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map: legal only before the first vors_tracker_track");
+    vors_status st = trackers_map_enable(t->seq, level, capacity, max_keyframes, min_weight);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    // keyframe 0 exists since create: its records, the handle's copies (dense mode) and the identity pose are what init left on s_main
+    return trackers_map_init(t->seq, t->s_main);
+}
+
+vors_status vors_tracker_read_map(vors_tracker* t, int capacity, float* xyz, uint32_t* pixel, uint8_t* gray, uint32_t* count, int max_segments,
+                                  vors_map_segment* segments, uint32_t* n_segments) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map: the handle t is NULL");
+    const vors_trackers::Map& m = t->seq->map;
+    if (!m.on) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map: the keyframe map is not enabled (vors_tracker_enable_map)");
+    if (capacity < 0 || max_segments < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map: negative capacity / max_segments");
+    DeviceGuard guard(t->device);
+    uint32_t totals[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&totals[0], m.counts, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipMemcpyAsync(&totals[1], m.n_segments, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    const size_t np = std::min<size_t>(std::min<uint32_t>(totals[0], (uint32_t)m.capacity), (size_t)capacity);
+    const size_t ns = std::min<size_t>(std::min<uint32_t>(totals[1], (uint32_t)m.max_keyframes), (size_t)max_segments);
+    if (xyz && np) HIP_TRY(hipMemcpyAsync(xyz, m.xyz, np * 3 * sizeof(float), hipMemcpyDeviceToHost, t->s_main));
+    if (pixel && np) HIP_TRY(hipMemcpyAsync(pixel, m.pixel, np * sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    if (gray && np) HIP_TRY(hipMemcpyAsync(gray, m.gray, np, hipMemcpyDeviceToHost, t->s_main));
+    if (segments && ns) HIP_TRY(hipMemcpyAsync(segments, m.segments, ns * sizeof(vors_map_segment), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    if (count) *count = totals[0];
+    if (n_segments) *n_segments = totals[1];
+    return VORS_OK;
+}
 
 vors_status vors_trackers_enable_depth_filter(vors_trackers* t, float tol_m, int max_weight, int fill_min_weight) {
     if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_depth_filter: the handle t is NULL");
@@ -340,6 +483,7 @@ vors_status vors_trackers_init(vors_trackers* t, const uint8_t* d_gray, const ui
     HIP_TRY(hipMemsetAsync(t->frame_counter.p, 0, sizeof(int), s));
     HIP_TRY(hipGetLastError());
     if (t->filter.on && (st = trackers_filter_init(t, d_depth, s)) != VORS_OK) return st;
+    if (t->map.on && (st = trackers_map_init(t, s)) != VORS_OK) return st;
     t->frame_index = 0;
     t->initialised = true;
     return VORS_OK;

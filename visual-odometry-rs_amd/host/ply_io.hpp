@@ -1,0 +1,66 @@
+// Binary little-endian PLY writer for the keyframe map of a sequence (vors_tracker_read_map): one vertex per point — x y z float32,
+// intensity uchar, 13 bytes — and one comment line per keyframe segment: frame, first, count and the camera -> world pose the points
+// were carried through. Header-only, no dependency beyond the standard library; the payload is assembled byte by byte, so the file is
+// little-endian on every host.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/vors_hip.h"
+
+namespace vors {
+namespace ply_io {
+
+constexpr size_t VERTEX_BYTES = 13;
+
+inline void put_f32_le(float v, unsigned char* out) {
+    std::uint32_t u;
+    std::memcpy(&u, &v, 4);
+    for (int k = 0; k < 4; ++k) out[k] = (unsigned char)((u >> (8 * k)) & 0xffu);
+}
+
+// The header: `n_points` vertices, one "comment segment ..." line per record (%.9g round-trips a float32).
+inline std::string header(size_t n_points, const vors_map_segment* segments, size_t n_segments) {
+    std::string h = "ply\nformat binary_little_endian 1.0\ncomment vors keyframe map: one segment line per keyframe (frame first count tx ty tz qx qy qz qw)\n";
+    char line[256];
+    for (size_t k = 0; k < n_segments; ++k) {
+        const vors_map_segment& s = segments[k];
+        std::snprintf(line, sizeof line, "comment segment %d %u %u %.9g %.9g %.9g %.9g %.9g %.9g %.9g\n", (int)s.frame, (unsigned)s.first,
+                      (unsigned)s.count, s.pose7[0], s.pose7[1], s.pose7[2], s.pose7[3], s.pose7[4], s.pose7[5], s.pose7[6]);
+        h += line;
+    }
+    h += "element vertex " + std::to_string(n_points) + "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar intensity\nend_header\n";
+    return h;
+}
+
+// xyz: [n_points][3], gray: [n_points]. Throws std::runtime_error when the file cannot be written.
+inline void write_map(const std::string& path, const float* xyz, const std::uint8_t* gray, size_t n_points, const vors_map_segment* segments,
+                      size_t n_segments) {
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    if (!f.good()) throw std::runtime_error("cannot open " + path + " for writing");
+    const std::string h = header(n_points, segments, n_segments);
+    f.write(h.data(), (std::streamsize)h.size());
+    std::vector<unsigned char> buf;
+    const size_t block = 65536;  // points per write
+    buf.resize(std::min(n_points, block) * VERTEX_BYTES);
+    for (size_t p0 = 0; p0 < n_points; p0 += block) {
+        const size_t n = std::min(block, n_points - p0);
+        for (size_t i = 0; i < n; ++i) {
+            unsigned char* o = buf.data() + i * VERTEX_BYTES;
+            for (int c = 0; c < 3; ++c) put_f32_le(xyz[3 * (p0 + i) + c], o + 4 * c);
+            o[12] = gray[p0 + i];
+        }
+        f.write(reinterpret_cast<const char*>(buf.data()), (std::streamsize)(n * VERTEX_BYTES));
+    }
+    f.flush();
+    if (!f.good()) throw std::runtime_error("error while writing " + path);
+}
+
+}  // namespace ply_io
+}  // namespace vors

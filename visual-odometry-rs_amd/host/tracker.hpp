@@ -9,6 +9,7 @@
 // are logged to stderr like the reference's eprintln!s); programmer errors (image too small for nb_levels) throw, where
 // the reference panics.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <charconv>
 #include <cmath>
@@ -96,7 +97,11 @@ class Tracker {  // inverse_compositional.rs:31-34
    public:
     Tracker(const Tracker&) = delete;
     Tracker& operator=(const Tracker&) = delete;
-    Tracker(Tracker&& o) noexcept : h_(o.h_), rows_(o.rows_), cols_(o.cols_), layout_(o.layout_), log_(o.log_) { o.h_ = nullptr; }
+    Tracker(Tracker&& o) noexcept
+        : h_(o.h_), rows_(o.rows_), cols_(o.cols_), layout_(o.layout_), log_(o.log_), map_capacity_(o.map_capacity_),
+          map_max_keyframes_(o.map_max_keyframes_) {
+        o.h_ = nullptr;
+    }
     ~Tracker() { vors_tracker_destroy(h_); }
 
     // Tracker::track (inverse_compositional.rs:170-240): returns () like the reference.
@@ -136,6 +141,35 @@ class Tracker {  // inverse_compositional.rs:31-34
     void enable_depth_filter(Float tol_m, int max_weight = 255, int fill_min_weight = 0) {
         check(vors_tracker_enable_depth_filter(h_, tol_m, max_weight, fill_min_weight));
     }
+    // Extension: the keyframe map (vors_tracker_enable_map): the cloud of every keyframe, appended on the device. Before the first
+    // track(), after enable_depth_filter when min_weight >= 2.
+    void enable_map(int level, int capacity, int max_keyframes, int min_weight = 0) {
+        check(vors_tracker_enable_map(h_, level, capacity, max_keyframes, min_weight));
+        map_capacity_ = capacity;
+        map_max_keyframes_ = max_keyframes;
+    }
+    struct Map {
+        std::vector<Float> xyz;               // [points][3], keyframe after keyframe
+        std::vector<std::uint32_t> pixel;     // x | y << 16
+        std::vector<std::uint8_t> gray;
+        std::vector<vors_map_segment> segments;
+        std::uint32_t count = 0, n_segments = 0;  // the UNCLIPPED totals: count > xyz.size() / 3 means the capacity was exceeded
+    };
+    // The map so far (vors_tracker_read_map; synchronises): at most `capacity` points and `max_segments` records.
+    Map read_map(int capacity = 0x7fffffff, int max_segments = 0x7fffffff) {
+        Map m;
+        check(vors_tracker_read_map(h_, 0, nullptr, nullptr, nullptr, &m.count, 0, nullptr, &m.n_segments));  // the totals first
+        // (nothing beyond the handle's own capacity was ever written)
+        const size_t np = std::min<size_t>(m.count, (size_t)std::max(std::min(capacity, map_capacity_), 0));
+        const size_t ns = std::min<size_t>(m.n_segments, (size_t)std::max(std::min(max_segments, map_max_keyframes_), 0));
+        m.xyz.resize(3 * np);
+        m.pixel.resize(np);
+        m.gray.resize(np);
+        m.segments.resize(ns);
+        std::uint32_t count = 0, n_segments = 0;
+        check(vors_tracker_read_map(h_, (int)np, m.xyz.data(), m.pixel.data(), m.gray.data(), &count, (int)ns, m.segments.data(), &n_segments));
+        return m;
+    }
 
    private:
     friend struct Config;
@@ -143,6 +177,7 @@ class Tracker {  // inverse_compositional.rs:31-34
     vors_tracker* h_ = nullptr;
     int rows_ = 0, cols_ = 0, layout_ = 0;
     bool log_ = true;
+    int map_capacity_ = 0, map_max_keyframes_ = 0;  // enable_map's
     vors_pair_stats last_{};
     int last_status_ = 0;
 };

@@ -5,13 +5,17 @@
 // Optional trailing flags (not in the reference): `--quiet` silences the per-frame stderr logs; `--arith exact|fused|reference` selects the
 // per-point arithmetic (include/vors_hip.h VORS_ARITH_*, default reference); `--candidates c2f|dense|dso` the level-0 mask source
 // (default c2f = the reference's coarse-to-fine selection); `--depth-filter TOL_M[,MAX_WEIGHT[,FILL_MIN_WEIGHT]]` switches the recursive
-// depth filter across keyframe promotions on (include/vors_hip.h vors_tracker_enable_depth_filter; defaults 255 and 0).
+// depth filter across keyframe promotions on (include/vors_hip.h vors_tracker_enable_depth_filter; defaults 255 and 0);
+// `--map FILE.ply[,LEVEL[,CAPACITY[,MAX_KEYFRAMES[,MIN_WEIGHT]]]]` collects the cloud of every keyframe on the device
+// (vors_tracker_enable_map; defaults level 0, 4 Mi points, 4096 keyframes, min_weight 0) and writes it as a binary PLY after the last frame.
+// A malformed --map list, or MIN_WEIGHT >= 2 without --depth-filter, prints the usage and exits with status 2 before any device is touched.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 
+#include "ply_io.hpp"
 #include "png_io.hpp"
 #include "tum_rgbd.hpp"
 
@@ -53,8 +57,28 @@ static bool parse_depth_filter(const std::string& val, float& tol_m, int& max_we
     return *end == '\0';
 }
 
+// "FILE.ply[,LEVEL[,CAPACITY[,MAX_KEYFRAMES[,MIN_WEIGHT]]]]": a non-empty file name, then whole numbers, nothing after the last. The VALUES
+// are judged by the library (but for the one rule that needs another flag, checked in main).
+static bool parse_map(const std::string& val, std::string& file, int ints[4]) {
+    const size_t comma = val.find(',');
+    file = val.substr(0, comma);
+    if (file.empty() || file.rfind("--", 0) == 0) return false;
+    if (comma == std::string::npos) return true;
+    const char* p = val.c_str() + comma;
+    for (int k = 0; k < 4 && *p == ','; ++k) {
+        char* end = nullptr;
+        const long v = std::strtol(p + 1, &end, 10);
+        if (end == p + 1 || v < -0x7fffffffL || v > 0x7fffffffL) return false;
+        ints[k] = (int)v;
+        p = end;
+    }
+    return *p == '\0';
+}
+
 int main(int argc, char** argv) {
-    bool quiet = false, depth_filter = false;
+    bool quiet = false, depth_filter = false, map = false, bad_map = false;
+    std::string map_file;
+    int map_ints[4] = {0, 4 << 20, 4096, 0};  // level, capacity, max_keyframes, min_weight
     float filter_tol_m = 0.0f;
     int filter_max_weight = 255, filter_fill_min_weight = 0;
     int arithmetic = VORS_ARITH_REFERENCE, candidates = VORS_CANDIDATES_COARSE_TO_FINE;
@@ -72,9 +96,19 @@ int main(int argc, char** argv) {
         } else if (flag == "--depth-filter" && parse_depth_filter(val, filter_tol_m, filter_max_weight, filter_fill_min_weight)) {
             depth_filter = true;
             ++a;
+        } else if (flag == "--map") {
+            map = parse_map(val, map_file, map_ints);
+            bad_map = !map;
+            ++a;
         } else {
             bad_flag = true;
         }
+    }
+    if (bad_map || (map && map_ints[3] >= 2 && !depth_filter)) {  // (the new flag's own errors: the usage, and a status a script can test)
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
+                     bad_map ? "Malformed --map: expected FILE.ply[,LEVEL[,CAPACITY[,MAX_KEYFRAMES[,MIN_WEIGHT]]]]"
+                             : "--map with MIN_WEIGHT >= 2 needs --depth-filter");
+        return 2;
     }
     if (argc > 3) argc = bad_flag ? 0 : 3;
     if (argc != 3) {  // vors_track.rs:75-96
@@ -124,6 +158,7 @@ int main(int argc, char** argv) {
                                              associations[0].color_timestamp, {gray.data(), (int)h, (int)w, VORS_ROW_MAJOR});
         tracker.set_logging(!quiet);
         if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
+        if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);
@@ -132,6 +167,15 @@ int main(int argc, char** argv) {
                           {gray.data(), (int)h, (int)w, VORS_ROW_MAJOR});
             const auto cf = tracker.current_frame();
             std::printf("%s\n", tum_rgbd::to_string(tum_rgbd::Frame{cf.first, cf.second}).c_str());
+        }
+        if (map) {
+            const track::Tracker::Map m = tracker.read_map();
+            if (m.count > (uint32_t)map_ints[1])
+                std::fprintf(stderr, "Warning: the map holds %u points but its capacity is %d: the last %u were dropped\n", m.count, map_ints[1],
+                             m.count - (uint32_t)map_ints[1]);
+            if (m.n_segments > (uint32_t)map_ints[2])
+                std::fprintf(stderr, "Warning: %u keyframes but room for %d segment records\n", m.n_segments, map_ints[2]);
+            ply_io::write_map(map_file, m.xyz.data(), m.gray.data(), m.gray.size(), m.segments.data(), m.segments.size());
         }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "\"%s\"\n", e.what());

@@ -94,7 +94,7 @@ class vors_obs(C.Structure):
 EXPORTED_SYMBOLS = [
     "vors_last_error", "vors_device_count", "vors_device_info", "vors_abi_version", "vors_selfcheck_isqrt",
     "vors_tracker_create", "vors_tracker_track", "vors_tracker_track_checked", "vors_tracker_current_frame", "vors_tracker_last_stats",
-    "vors_tracker_keyframe", "vors_tracker_enable_depth_filter", "vors_tracker_destroy",
+    "vors_tracker_keyframe", "vors_tracker_enable_depth_filter", "vors_tracker_enable_map", "vors_tracker_read_map", "vors_tracker_destroy",
     "vors_track_pairs",
     "vors_batch_create", "vors_batch_create_on", "vors_batch_device", "vors_batch_track_pairs", "vors_batch_prepare_keyframes", "vors_batch_track_current",
     "vors_batch_workspace_bytes", "vors_batch_enable_kernel_timing", "vors_batch_kernel_times", "vors_batch_last_kernel_ms",
@@ -113,6 +113,7 @@ EXPORTED_SYMBOLS = [
     "vors_trackers_create", "vors_trackers_create_on", "vors_trackers_count", "vors_trackers_init", "vors_trackers_track", "vors_trackers_state",
     "vors_trackers_current_frames", "vors_trackers_last_stats", "vors_trackers_enable_kernel_timing", "vors_trackers_kernel_times", "vors_trackers_destroy",
     "vors_trackers_enable_depth_filter", "vors_trackers_keyframe_depth", "vors_trackers_workspace_bytes",
+    "vors_trackers_enable_map", "vors_trackers_map",
     "vors_synth_render_frames",
     "vors_pipeline_create", "vors_pipeline_submit", "vors_pipeline_wait", "vors_pipeline_drain", "vors_pipeline_destroy",
 ]
@@ -173,6 +174,10 @@ def lib():
         _lib.vors_trackers_keyframe_depth.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_trackers_workspace_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
         _lib.vors_tracker_enable_depth_filter.argtypes = [vp, f, i, i]
+        _lib.vors_trackers_enable_map.argtypes = [vp, i, i, i, i]
+        _lib.vors_trackers_map.argtypes = [vp] + [C.POINTER(vp)] * 6
+        _lib.vors_tracker_enable_map.argtypes = [vp, i, i, i, i]
+        _lib.vors_tracker_read_map.argtypes = [vp, i, vp, vp, vp, C.POINTER(C.c_uint32), i, vp, C.POINTER(C.c_uint32)]
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
         _lib.vors_batch_track_pairs.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib.vors_pipeline_create.argtypes = [i, C.POINTER(vors_config), i, i, i, i, C.POINTER(vp)]
@@ -328,13 +333,49 @@ def _depth_filter_args(spec):
     return tol_m, int(max_weight), int(fill_min_weight)
 
 
+class vors_map_segment(C.Structure):
+    """One keyframe of a sequence's map (include/vors_hip.h vors_map_segment, 40 bytes)."""
+    _fields_ = [("frame", C.c_int32), ("first", C.c_uint32), ("count", C.c_uint32), ("pose7", C.c_float * 7)]
+
+
+MAP_SEGMENT_DTYPE = np.dtype([("frame", "<i4"), ("first", "<u4"), ("count", "<u4"), ("pose7", "<f4", (7,))])
+
+
+def decode_map_segments(segments):
+    """The "segments" entry of Trackers.map() (uint8 [n, max_keyframes, 40], any device) -> structured numpy array [n, max_keyframes]."""
+    a = segments.cpu().numpy() if hasattr(segments, "cpu") else np.asarray(segments)
+    return np.ascontiguousarray(a).view(MAP_SEGMENT_DTYPE)[..., 0]
+
+
+def _map_args(spec):
+    """None or a tuple (level, capacity, max_keyframes[, min_weight]) -> None or four ints with the default filled in. Only the SHAPE of
+    the argument is judged here; the values are judged by the library, in one place for every caller."""
+    if spec is None:
+        return None
+    try:
+        spec = tuple(spec)
+    except TypeError:
+        raise VorsError(f"map: expected None or (level, capacity, max_keyframes[, min_weight]), got {spec!r}") from None
+    if not 3 <= len(spec) <= 4:
+        raise VorsError(f"map: expected 3 or 4 values (level, capacity, max_keyframes[, min_weight]), got {len(spec)}")
+    spec = (spec + (0,))[:4]
+    for name, v in zip(("level", "capacity", "max_keyframes", "min_weight"), spec):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise VorsError(f"map: {name} must be an integer, got {v!r}")
+        if not -2 ** 31 <= int(v) < 2 ** 31:
+            raise VorsError(f"map: {name} does not fit the C int it is passed as, got {v!r}")
+    return tuple(int(v) for v in spec)
+
+
 class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
-    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None):
+    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
-        (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter)."""
+        (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
+        keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
+        self._map = map = _map_args(map)
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -347,6 +388,23 @@ class Tracker:
                                          C.byref(self._h)))
         if depth_filter is not None:
             _check(lib().vors_tracker_enable_depth_filter(self._h, *depth_filter))
+        if map is not None:
+            _check(lib().vors_tracker_enable_map(self._h, *map))
+
+    def read_map(self, capacity=None, max_segments=None):
+        """The map so far on the host (vors_tracker_read_map; synchronises) -> dict: "count" and "n_segments", the UNCLIPPED totals, "xyz"
+        [m, 3] float32, "pixel" [m] uint32 (x | y << 16), "gray" [m] uint8 with m = min(count, capacity, the handle's capacity), and
+        "segments" [k] MAP_SEGMENT_DTYPE with k = min(n_segments, max_segments, the handle's max_keyframes). None = the handle's figure."""
+        if self._map is None:
+            raise VorsError("read_map: the keyframe map is not enabled (Tracker(..., map=(level, capacity, max_keyframes)))")
+        cap = self._map[1] if capacity is None else int(capacity)
+        nseg = self._map[2] if max_segments is None else int(max_segments)
+        xyz, pixel, gray = np.zeros((max(cap, 0), 3), np.float32), np.zeros(max(cap, 0), np.uint32), np.zeros(max(cap, 0), np.uint8)
+        seg = np.zeros(max(nseg, 0), MAP_SEGMENT_DTYPE)
+        count, n_segments = C.c_uint32(), C.c_uint32()
+        _check(lib().vors_tracker_read_map(self._h, cap, _ptr(xyz), _ptr(pixel), _ptr(gray), C.byref(count), nseg, _ptr(seg), C.byref(n_segments)))
+        m, k = min(count.value, cap, self._map[1]), min(n_segments.value, nseg, self._map[2])
+        return dict(count=count.value, n_segments=n_segments.value, xyz=xyz[:m], pixel=pixel[:m], gray=gray[:m], segments=seg[:k])
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -922,6 +980,30 @@ class Trackers:
         b = C.c_uint64()
         _check(lib().vors_trackers_workspace_bytes(self._h, C.byref(b)))
         return b.value
+
+    def enable_map(self, level, capacity, max_keyframes, min_weight=0):
+        """Keyframe map (vors_trackers_enable_map): before init(), once. From then on the cloud of every new keyframe of a sequence — the
+        usable points of `level` through the keyframe pose, Batch.point_cloud's rule — is appended on the device to that sequence's list,
+        with a segment record per keyframe. min_weight >= 2 keeps the points whose depth-filter weight reaches it (level 0, filter first)."""
+        args = _map_args((level, capacity, max_keyframes, min_weight))
+        _check(lib().vors_trackers_enable_map(self._h, *args))
+        self._map = args
+
+    def map(self, copy=True):
+        """-> dict of tensors (vors_trackers_map), valid in stream order after the last init() / track(): "xyz" [n, capacity, 3] float32,
+        "pixel" [n, capacity] int32 (x | y << 16), "gray" [n, capacity] uint8, "counts" [n] int32 (the u32 running totals, which may exceed
+        capacity), "n_segments" [n] int32, "segments" [n, max_keyframes, 40] uint8 — the vors_map_segment records as bytes:
+        decode_map_segments() gives the structured view. Only the first min(counts, capacity) entries of a list and the first
+        min(n_segments, max_keyframes) records are written. copy=False: views of the handle's own buffers, which die with this object."""
+        import torch
+        p = [C.c_void_p() for _ in range(6)]
+        _check(lib().vors_trackers_map(self._h, *[C.byref(q) for q in p]))
+        _, cap, nkf, _ = self._map
+        dev = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
+        out = dict(xyz=_device_view(p[0].value, (self.n, cap, 3), "<f4", dev), pixel=_device_view(p[1].value, (self.n, cap), "<i4", dev),
+                   gray=_device_view(p[2].value, (self.n, cap), "|u1", dev), counts=_device_view(p[3].value, (self.n,), "<i4", dev),
+                   segments=_device_view(p[4].value, (self.n, nkf, 40), "|u1", dev), n_segments=_device_view(p[5].value, (self.n,), "<i4", dev))
+        return {k: v.clone() for k, v in out.items()} if copy else out
 
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
