@@ -119,7 +119,9 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_camera_back_project, vors_camera_project, likewise; + vors_batch_fuse_depth, vors_fuse_depth_pixels,
                               *    likewise; + vors_trackers_enable_depth_filter, vors_trackers_keyframe_depth, vors_trackers_workspace_bytes,
                               *    vors_tracker_enable_depth_filter, likewise; + vors_trackers_enable_map, vors_trackers_map,
-                              *    vors_tracker_enable_map, vors_tracker_read_map, vors_map_segment, likewise) */
+                              *    vors_tracker_enable_map, vors_tracker_read_map, vors_map_segment, likewise; + vors_trackers_enable_map_voxels,
+                              *    vors_trackers_map_voxels, vors_tracker_enable_map_voxels, vors_tracker_read_map_voxels, vors_voxel_keys,
+                              *    VORS_VOXEL_NONE, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -163,6 +165,14 @@ vors_status vors_tracker_enable_map(vors_tracker* t, int level, int capacity, in
  * VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_read_map(vors_tracker* t, int capacity, float* xyz, uint32_t* pixel, uint8_t* gray, uint32_t* count,
                                   int max_segments, vors_map_segment* segments, uint32_t* n_segments);
+/* The voxel filter of vors_trackers_enable_map_voxels (below) for the single sequence: same arguments, same refusals. Legal after
+ * vors_tracker_enable_map and until the first vors_tracker_track (refused after it and when repeated). vors_tracker_enable_map has already
+ * emitted keyframe 0 unfiltered, so THIS CALL RESETS THE MAP (counters, segment count, voxel table) and emits keyframe 0 again through the
+ * filter, on the tracker's stream: keyframe 0 appears once. */
+vors_status vors_tracker_enable_map_voxels(vors_tracker* t, float voxel_m, int table_slots);
+/* The filter's two counters (vors_trackers_map_voxels, below) to the host, each nullable; synchronises. Filter not enabled:
+ * VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, uint32_t* overflow);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -253,6 +263,28 @@ vors_status vors_trackers_enable_map(vors_trackers* t, int level, int capacity, 
  * The order of ranks is a function of the sequence's own frames alone. Without an enabled map: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_map(const vors_trackers* t, const float** d_xyz, const uint32_t** d_pixel, const uint8_t** d_gray,
                               const uint32_t** d_counts, const vors_map_segment** d_segments, const uint32_t** d_n_segments);
+/* VOXEL FILTER OF THE KEYFRAME MAP (opt-in on top of an enabled map; without this call nothing changes: no launch, no allocation, no
+ * kernel argument on any existing path). The map then keeps, per sequence, exactly ONE point per occupied voxel of a world-frame grid of
+ * edge voxel_m: the first in the map's own order. Precisely: let U be the list the map would hold without the filter (unclipped). The
+ * filtered list is U restricted to the entries whose voxel key (vors_voxel_keys, section 4, of the stored xyz) is not VORS_VOXEL_NONE and
+ * occurs at no lower rank of U, in U's order; xyz, pixel and gray of a kept entry are U's bits. A segment keeps frame and pose7, `count`
+ * is the keyframe's kept points and `first` the filtered total before it; d_counts, clipping by capacity / max_keyframes and saturation
+ * are vors_trackers_map's rules applied to the filtered list. The keep rule of the map (min_weight) is applied first, unchanged. The
+ * result does not depend on scheduling, on the other sequences, on the stream or on table_slots — as long as the table has not overflowed.
+ * Table: per sequence, open addressing with linear probing over table_slots entries (a power of two) of two 64-bit words, which places
+ * every voxel while a sequence's DISTINCT voxels are <= table_slots. Beyond that the sequence's sticky overflow word is set: from the
+ * overflowing keyframe on its map contents are unspecified (every store stays inside its buffers, d_counts and the segment records are
+ * still written, every call returns normally, tracking is untouched, and a point probes at most table_slots entries); the other sequences
+ * keep the exact result. vors_trackers_init empties the table and zeroes both words on the stream.
+ * Legal after vors_trackers_enable_map and before vors_trackers_init, once. VORS_ERR_INVALID_ARGUMENT, with nothing allocated and nothing
+ * enqueued: NULL handle, no enabled map, repeated call, call after init, voxel_m not finite or <= 0, table_slots not a power of two or
+ * outside 64..2^30. The call allocates, as part of vors_trackers_workspace_bytes' figure and freed with the handle,
+ * n * (16 * table_slots + 8) bytes: the table and the two words per sequence; no later call allocates. */
+vors_status vors_trackers_enable_map_voxels(vors_trackers* t, float voxel_m, int table_slots);
+/* DEVICE pointers [n] u32, owned by the handle and valid for its life, contents valid in stream order after the last init / track, each
+ * nullable: d_occupied = claimed table entries of a sequence = its distinct voxels so far (== d_counts while it has not overflowed),
+ * d_overflow = non-zero once the sequence has overflowed. Filter not enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map_voxels(const vors_trackers* t, const uint32_t** d_occupied, const uint32_t** d_overflow);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -656,6 +688,13 @@ void vors_from_depth(float scale, const uint16_t* depth, int n, float* idepth_ou
  * (camera.rs:36-39, 70-72, 126-132) -> homogeneous (u w, v w, w), no division. xy [2n], depth [n], xyz [3n], uvw [3n]; n = 0 is legal. */
 void vors_camera_back_project(const float cam5[5], const float pose7[7] /* nullable */, const float* xy, const float* depth, int n, float* xyz_out);
 void vors_camera_project(const float cam5[5], const float pose7[7] /* nullable */, const float* xyz, int n, float* uvw_out);
+/* The voxel of a point on a grid of edge voxel_m, for arrays (host arithmetic): the text the voxel filter of the keyframe map runs per
+ * point (vors_trackers_enable_map_voxels). Per axis q = floorf(w / voxel_m), an IEEE f32 division. A point has a key iff all three q are
+ * finite and -2^20 <= q < 2^20: key = (q_x + 2^20) | (q_y + 2^20) << 21 | (q_z + 2^20) << 42, below 2^63. Every other point — NaN,
+ * infinities, a quotient out of range — and every point when voxel_m is not finite or <= 0 gets VORS_VOXEL_NONE. xyz [3n], keys_out [n];
+ * n = 0 is legal. */
+#define VORS_VOXEL_NONE 0xFFFFFFFFFFFFFFFFull
+void vors_voxel_keys(float voxel_m, const float* xyz, int n, uint64_t* keys_out);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 5. Synthetic scene renderer on the device (bench/test tooling). Renders, for pair i in

@@ -360,6 +360,16 @@ struct PointCloudArgs {
     int ws_chunks;
     int wide_keep;              // the mask planes are 4-byte aligned: a dense quad reads its four bytes at once
 };
+// The voxel filter of that map (vors_trackers_enable_map_voxels): one open-addressing table per sequence, two 64-bit words per entry —
+// the voxel key (lie.h voxel_key; empty = all ones) and the tag of the point that owns the voxel (all ones until a point claims it). Only
+// the kernels of the filtered emission get this block; the unfiltered ones keep their arguments.
+struct PointCloudVoxelArgs {
+    float voxel_m = 0.f;
+    uint32_t table_slots = 0;       // a power of two
+    unsigned long long* table = nullptr;  // [seq][table_slots][2]
+    uint32_t* occupied = nullptr;   // [seq] claimed entries
+    uint32_t* overflow = nullptr;   // [seq] sticky: a point found no entry in table_slots probes
+};
 // The keyframe map of the lock-step trackers (vors_trackers_enable_map): the point-cloud pass of one level for the SELECTED sequences
 // (Geom::sel_list, null = all), appended to per-sequence lists with one segment record per keyframe. Every buffer is the handle's own.
 struct PointCloudAppendCall : LmScene {
@@ -377,6 +387,7 @@ struct PointCloudAppendCall : LmScene {
     uint32_t* n_segments;       // [seq] keyframes created
     uint32_t* ws;               // [seq][ws_chunks] kept points per chunk of the keyframe being appended
     int ws_chunks;
+    PointCloudVoxelArgs voxels; // table == null: no voxel filter, and the launches are exactly the ones above
 };
 // What its kernels get.
 struct PointCloudAppendArgs {
@@ -534,7 +545,8 @@ void launch_lm_fuse_depth_selected(const Geom& g, const FuseDepthCall& call, hip
 void launch_lm_point_cloud(const Geom& g, const PointCloudCall& call, hipStream_t s);
 // The same pass as MASKED launches that APPEND (the keyframe map of vors_trackers; lm_kernels.hip point_cloud_append_kernel,
 // point_cloud_commit_kernel): count, write behind the sequence's running total, commit the segment record and the totals. call.n_seq is
-// the extent of the pair dimension (all sequences); only the sequences of g.sel_list (null: all) are touched.
+// the extent of the pair dimension (all sequences); only the sequences of g.sel_list (null: all) are touched. With call.voxels.table set
+// the emission is CLAIM, COUNT, WRITE of point_cloud_append_voxel_kernel and the same commit.
 void launch_lm_point_cloud_append(const Geom& g, const PointCloudAppendCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.

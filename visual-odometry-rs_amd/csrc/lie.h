@@ -344,6 +344,22 @@ VORS_HD FusedPixel fuse_depth_pixel(float depth_scale, float tol_m, int max_weig
     return o;
 }
 
+// Voxel of a world point on a grid of edge voxel_m (the keyframe map's voxel filter): per axis q = floorf(w / voxel_m), an
+// IEEE division (never a multiplication by a reciprocal; the translation units that hold this text are built with -ffp-contract=off).
+// A point has a key iff all three q are finite and -2^20 <= q < 2^20: key = (qx + 2^20) | (qy + 2^20) << 21 | (qz + 2^20) << 42, below
+// 2^63. Everything else — NaN, infinities, a quotient out of range — is all ones (VORS_VOXEL_NONE), which is also what an empty table
+// entry holds: no point ever carries it. The comparisons are made in float BEFORE the integer conversion. The one text the host entry
+// (vors_voxel_keys) and the device kernels (lm_kernels.hip voxel_claim / voxel_owns) both run, bit for bit.
+VORS_HD uint64_t voxel_key(float voxel_m, float x, float y, float z) {
+    const float q[3] = {floorf(x / voxel_m), floorf(y / voxel_m), floorf(z / voxel_m)};
+    uint64_t key = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (!(q[a] >= -1048576.0f && q[a] < 1048576.0f)) return 0xFFFFFFFFFFFFFFFFull;
+        key |= (uint64_t)((int)q[a] + 1048576) << (21 * a);
+    }
+    return key;
+}
+
 // One LM step: lm_optimizer.rs:123-136.
 VORS_HD bool lm_step(const float* h36, const float* g6, const Iso& model, float lm_coef, Iso* out) {
     float delta[6];

@@ -2945,10 +2945,73 @@ struct CloudPts {
     float tmpl[G];
     bool kept[G];
 };
+// The voxel table of ONE sequence as the sweeps of its filtered emission see it (point_cloud_append_voxel_kernel, below): entry e is the
+// two words table[2 e] = voxel key (empty: all ones) and table[2 e + 1] = owner tag (unclaimed: all ones). `tag_hi` is the segment index
+// of the keyframe being emitted << 32; a point's tag is tag_hi | its slot in the level's source, so tags ascend in the map's rank order.
+struct CloudVox {
+    unsigned long long* table;
+    uint32_t* occupied;
+    uint32_t* overflow;
+    uint32_t mask;  // table_slots - 1
+    float voxel_m;
+    unsigned long long tag_hi;
+    Iso pose;       // the keyframe pose: the key is taken of the world point WRITE stores
+};
+#define VOXEL_EMPTY 0xFFFFFFFFFFFFFFFFull
+enum { VOX_OFF = 0, VOX_CLAIM = 1, VOX_OWNED = 2 };
+__device__ __forceinline__ uint32_t voxel_hash(unsigned long long key) {  // (the 64-bit finaliser of MurmurHash3)
+    key ^= key >> 33;
+    key *= 0xff51afd7ed558ccdull;
+    key ^= key >> 33;
+    key *= 0xc4ceb9fe1a85ec53ull;
+    key ^= key >> 33;
+    return (uint32_t)key;
+}
+__device__ __forceinline__ bool voxel_overflowed(const CloudVox& v) { return __hip_atomic_load(v.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; }
+// CLAIM: linear probing from the key's home entry. An empty entry is taken with one compare-and-swap on the key word (a lost race hands
+// back the winner's key, which is then compared like any other); on the entry that holds the key, ONE minimum on the owner word. Every
+// step either ends the probe or moves on: no thread waits for another. table_slots entries without success — the sequence has more
+// voxels than entries — set the sticky overflow word, which every probe reads at entry and every 64 steps and then gives up.
+__device__ __forceinline__ void voxel_claim(const CloudVox& v, unsigned long long key, unsigned long long tag) {
+    if (key == VOXEL_EMPTY) return;  // (no key: the point is dropped and not counted)
+    uint32_t e = voxel_hash(key) & v.mask;
+    for (uint32_t step = 0; step <= v.mask; ++step, e = (e + 1u) & v.mask) {
+        if ((step & 63u) == 0u && voxel_overflowed(v)) return;
+        unsigned long long* kp = v.table + 2 * (size_t)e;
+        unsigned long long k = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == VOXEL_EMPTY) {
+            k = atomicCAS(kp, VOXEL_EMPTY, key);
+            if (k == VOXEL_EMPTY) {
+                atomicAdd(v.occupied, 1u);
+                k = key;
+            }
+        }
+        if (k == key) {
+            atomicMin(kp + 1, tag);
+            return;
+        }
+    }
+    atomicOr(v.overflow, 1u);
+}
+// COUNT / WRITE: the same probe, reading only (the table does not change during these launches). True iff the voxel's owner is `tag`.
+// After an overflow nothing is owned: the keyframe contributes no point, in both sweeps alike.
+__device__ __forceinline__ bool voxel_owns(const CloudVox& v, unsigned long long key, unsigned long long tag) {
+    if (key == VOXEL_EMPTY) return false;
+    uint32_t e = voxel_hash(key) & v.mask;
+    for (uint32_t step = 0; step <= v.mask; ++step, e = (e + 1u) & v.mask) {
+        if ((step & 63u) == 0u && voxel_overflowed(v)) return false;
+        const unsigned long long k = v.table[2 * (size_t)e];
+        if (k == key) return v.table[2 * (size_t)e + 1] == tag;
+        if (k == VOXEL_EMPTY) return false;  // (never claimed: only after an overflow cut CLAIM short)
+    }
+    return false;
+}
 // THRESH (the keyframe map of the trackers, point_cloud_append_kernel): the plane holds weights and a point is kept from `keep_min` on.
-template <bool THRESH = false, class Src>
+// VOX (its voxel filter): after the keep rule, VOX_CLAIM enters every kept point into the table and leaves the flags alone, VOX_OWNED
+// keeps a point iff it owns its voxel. Slot of point g of a unit: the candidate lists' i and i + BLOCK, the dense sources' G i + g.
+template <bool THRESH = false, int VOX = VOX_OFF, class Src>
 __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::Cursor& cur, int last, int cols, const uint8_t* keep, bool wide_keep,
-                                            CloudPts<Src::G>& o, uint32_t keep_min = 1) {
+                                            CloudPts<Src::G>& o, uint32_t keep_min = 1, const CloudVox* vox = nullptr) {
     constexpr int G = Src::G;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -2991,15 +3054,26 @@ __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::
         if constexpr (THRESH) o.kept[g] = pos[g].tmpl >= 0.f && kb[g] >= keep_min;
         else o.kept[g] = pos[g].tmpl >= 0.f && kb[g] != 0;
     }
+    if constexpr (VOX != VOX_OFF) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (!o.kept[g]) continue;
+            const uint32_t slot = G == 2 ? (uint32_t)(cur.i + g * RMAPS_BLOCK) : (uint32_t)(G * cur.i + g);
+            const V3 w = iso_transform_point(vox->pose, o.P[g]);  // (cloud_store's expression: the bits the list holds)
+            const unsigned long long key = voxel_key(vox->voxel_m, w.x, w.y, w.z);
+            if constexpr (VOX == VOX_CLAIM) voxel_claim(*vox, key, vox->tag_hi | slot);
+            else o.kept[g] = voxel_owns(*vox, key, vox->tag_hi | slot);
+        }
+    }
 }
-template <bool THRESH = false, class Src>
+template <bool THRESH = false, int VOX = VOX_OFF, class Src>
 __device__ __forceinline__ uint32_t cloud_count_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep,
-                                                      uint32_t keep_min = 1) {
+                                                      uint32_t keep_min = 1, const CloudVox* vox = nullptr) {
     constexpr int G = Src::G;
     uint32_t n = 0;
     for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
         CloudPts<G> pts;
-        cloud_fetch<THRESH>(src, cur, last, cols, keep, wide_keep, pts, keep_min);
+        cloud_fetch<THRESH, VOX>(src, cur, last, cols, keep, wide_keep, pts, keep_min, vox);
 #pragma unroll
         for (int g = 0; g < G; ++g) n += pts.kept[g] ? 1u : 0u;
     }
@@ -3049,16 +3123,16 @@ __device__ __forceinline__ void cloud_store(const CloudOut& o, uint32_t rank, co
     if (o.pixel) o.pixel[rank] = xy;
     if (o.gray) o.gray[rank] = (uint8_t)(int)tmpl;
 }
-template <bool THRESH = false, class Src>
+template <bool THRESH = false, int VOX = VOX_OFF, class Src>
 __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep, uint32_t base,
-                                                  const CloudOut& out, uint32_t* lds, uint32_t keep_min = 1) {
+                                                  const CloudOut& out, uint32_t* lds, uint32_t keep_min = 1, const CloudVox* vox = nullptr) {
     constexpr int G = Src::G;
     static_assert(G != 2 || std::is_same<Src, SlimSrc>::value, "G = 2 is the candidate lists' interleaved pair of slots");
     int par = 0;
     for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first);
          __builtin_amdgcn_readfirstlane(cur.i - (int)threadIdx.x) < last && base < out.capacity; cur = src.template advance<RMAPS_BLOCK>(cur)) {
         CloudPts<G> pts;
-        cloud_fetch<THRESH>(src, cur, last, cols, keep, wide_keep, pts, keep_min);
+        cloud_fetch<THRESH, VOX>(src, cur, last, cols, keep, wide_keep, pts, keep_min, vox);
         if constexpr (G == 2) {  // slots i and i + BLOCK: the first points of all threads come before the second ones
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -3175,6 +3249,15 @@ void launch_lm_point_cloud(const Geom& g_in, const PointCloudCall& call, hipStre
 //           room for it, then n_segments += 1 and counts += count (saturating). After WRITE, which reads the old total.
 // Keep rule: min_weight <= 1 no plane is read; otherwise `weight` is the depth filter's weight plane (level 0) and a point is kept from
 // min_weight on.
+// VOXEL FILTER (vors_trackers_enable_map_voxels; point_cloud_append_voxel_kernel, below the unfiltered kernel): the list keeps ONE point
+// per occupied voxel of a world grid, the first in the map's own order. One launch more, in front:
+//   CLAIM   the COUNT sweep, whose every kept point enters the sequence's table (voxel_claim): the owner word of a voxel ends as the
+//           MINIMUM of the tags (segment index << 32 | slot) of the points that ever fell into it — a value that does not depend on the
+//           order of arrival (the keyed z-buffer's argument), that an older keyframe always wins, and that within a keyframe is the
+//           point of lowest rank. Nothing is counted or stored besides.
+//   COUNT / WRITE  as above, a point kept iff it owns its voxel (voxel_owns, a read-only probe: the table is final when CLAIM has ended).
+//   COMMIT  the same kernel.
+// The segment index is n_segments[seq], which COMMIT moves on after the three sweeps have read it.
 // ------------------------------------------------------------------------------------------------------------
 template <bool DENSE, bool WRITE>
 __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
@@ -3223,6 +3306,64 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_kernel(Geom g,
         }
     }
 }
+// (A sibling with point_cloud_append_kernel's text: sharing one body between the two moved instructions in the unfiltered kernel.)
+template <bool DENSE, bool WRITE, int VOX>
+__global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_voxel_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                               const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                               const uint16_t* __restrict__ kf_depth, Records rec,
+                                                                               PointCloudAppendArgs a, PointCloudVoxelArgs v) {
+    static_assert(VOX != VOX_OFF && !(WRITE && VOX == VOX_CLAIM), "CLAIM is a counting sweep");
+    __shared__ uint32_t lds[2 * PCLOUD_WAVES];
+    const int seq = select_pair(g, blockIdx.y), chunk = blockIdx.x, n_chunks = gridDim.x;
+    if (seq < 0) return;
+    const int cols = g.lv[a.lvl].cols;
+    const uint8_t* keep = a.weight ? a.weight + (size_t)seq * g.S0 : nullptr;  // (set at level 0 only)
+    uint32_t* ws = a.ws + (size_t)seq * a.ws_chunks;
+    uint32_t base = 0, n = 0;
+    CloudOut out{};
+    if constexpr (WRITE) {
+        unsigned long long b64 = a.counts[seq];
+        for (int k = 0; k < chunk; ++k) b64 += ws[k];  // (uniform)
+        base = b64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b64;  // (>= capacity: nothing is stored)
+        out.has_pose = true;
+        out.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
+        out.capacity = (uint32_t)a.capacity;
+        out.xyz = a.xyz + (size_t)seq * a.capacity * 3;
+        out.pixel = a.pixel + (size_t)seq * a.capacity;
+        out.gray = a.gray + (size_t)seq * a.capacity;
+    }
+    CloudVox vox;
+    vox.table = v.table + 2 * (size_t)seq * v.table_slots;
+    vox.occupied = v.occupied + seq;
+    vox.overflow = v.overflow + seq;
+    vox.mask = v.table_slots - 1u;
+    vox.voxel_m = v.voxel_m;
+    vox.tag_hi = (unsigned long long)a.n_segments[seq] << 32;
+    vox.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
+    with_level_source<DENSE, true, false>(g, a.lvl, seq, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        // the cut of point_cloud_kernel
+        const int points = DENSE ? g.lv[a.lvl].n_slots : n_units;
+        const int chunks = min(max((points + a.chunk_points - 1) / a.chunk_points, 1), n_chunks);
+        if (chunk >= chunks) return;
+        const unsigned per = (unsigned)n_units / (unsigned)chunks, rem = (unsigned)n_units - per * (unsigned)chunks;
+        const int first = (int)((unsigned)chunk * per + min((unsigned)chunk, rem));
+        const int last = (int)((unsigned)(chunk + 1) * per + min((unsigned)(chunk + 1), rem));
+        if constexpr (WRITE) cloud_write_sweep<true, VOX>(src, first, last, cols, keep, a.wide_keep != 0, base, out, lds, (uint32_t)a.keep_min, &vox);
+        else n = cloud_count_sweep<true, VOX>(src, first, last, cols, keep, a.wide_keep != 0, (uint32_t)a.keep_min, &vox);
+    });
+    if constexpr (!WRITE && VOX != VOX_CLAIM) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t t = 0;
+#pragma unroll
+            for (int wv = 0; wv < PCLOUD_WAVES; ++wv) t += lds[wv];
+            ws[chunk] = t;  // stored, not accumulated: the workspace needs no clearing
+        }
+    }
+}
 __global__ __launch_bounds__(64) void point_cloud_commit_kernel(Geom g, PointCloudAppendArgs a, int n, int chunks) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= n) return;
@@ -3254,8 +3395,16 @@ void launch_lm_point_cloud_append(const Geom& g_in, const PointCloudAppendCall& 
                            ((uintptr_t)call.weight % 4 == 0 && (size_t)g.S0 % 4 == 0) ? 1 : 0};
     const int chunks = std::min(eval_pairs_chunks(g, call.lvl), call.ws_chunks), n = call.n_seq;
     with_bool(dense, [&](auto d) {
-        launch_on_scene(point_cloud_append_kernel<decltype(d)::value, false>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
-        launch_on_scene(point_cloud_append_kernel<decltype(d)::value, true>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+        constexpr bool DENSE = decltype(d)::value;
+        if (call.voxels.table) {
+            const PointCloudVoxelArgs& v = call.voxels;
+            launch_on_scene(point_cloud_append_voxel_kernel<DENSE, false, VOX_CLAIM>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
+            launch_on_scene(point_cloud_append_voxel_kernel<DENSE, false, VOX_OWNED>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
+            launch_on_scene(point_cloud_append_voxel_kernel<DENSE, true, VOX_OWNED>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
+        } else {
+            launch_on_scene(point_cloud_append_kernel<DENSE, false>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+            launch_on_scene(point_cloud_append_kernel<DENSE, true>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
+        }
     });
     hipLaunchKernelGGL(point_cloud_commit_kernel, dim3((n + 63) / 64), dim3(64), 0, s, g, a, n, chunks);
 }

@@ -238,6 +238,12 @@ void vors_camera_back_project(const float cam5[5], const float pose7[7], const f
         xyz_out[3 * i] = p.x; xyz_out[3 * i + 1] = p.y; xyz_out[3 * i + 2] = p.z;
     }
 }
+// The voxel keys of the keyframe map's voxel filter for arrays: lie.h voxel_key, the text the device kernels run. A voxel_m that no
+// handle accepts (not finite, <= 0) gives no point a key.
+void vors_voxel_keys(float voxel_m, const float* xyz, int n, uint64_t* keys_out) {
+    const bool ok = voxel_m > 0.0f && voxel_m <= 3.4028234663852886e38f;
+    for (int i = 0; i < n; ++i) keys_out[i] = ok ? voxel_key(voxel_m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]) : VORS_VOXEL_NONE;
+}
 void vors_camera_project(const float cam5[5], const float pose7[7], const float* xyz, int n, float* uvw_out) {
     const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
     for (int i = 0; i < n; ++i) {

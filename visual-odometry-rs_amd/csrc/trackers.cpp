@@ -49,6 +49,16 @@ struct vors_trackers {
         uint32_t *pixel = nullptr, *counts = nullptr, *n_segments = nullptr, *ws = nullptr;
         uint8_t* gray = nullptr;
         vors_map_segment* segments = nullptr;
+        // Voxel filter of the map (vors_trackers_enable_map_voxels; off: nothing below exists and the emission is the unfiltered one):
+        //   table               [n_seq][table_slots][2] 64-bit words, voxel key and owner tag of an entry, all ones = empty
+        //   occupied, overflow  [n_seq] claimed entries; sticky flag of a sequence whose voxels outgrew its table
+        struct Voxels {
+            bool on = false;
+            float voxel_m = 0.f;
+            int table_slots = 0;
+            unsigned long long* table = nullptr;
+            uint32_t *occupied = nullptr, *overflow = nullptr;
+        } voxels;
     } map;
     const uint16_t* keyframe_depth() const {
         return batch->g.mode == VORS_CANDIDATES_DENSE ? static_cast<const uint16_t*>(own_depth.p) : filter.fused;
@@ -82,6 +92,10 @@ static void trackers_map_emit(vors_trackers* t, const Geom& gm, hipStream_t s) {
     call.n_segments = t->map.n_segments;
     call.ws = t->map.ws;
     call.ws_chunks = t->map.ws_chunks;
+    // The voxel filter's table is the map's own too: CLAIM, COUNT and WRITE of one emission follow each other on the stream, and the next
+    // emission, which reads what this one claimed, is enqueued behind.
+    const vors_trackers::Map::Voxels& v = t->map.voxels;
+    if (v.on) call.voxels = PointCloudVoxelArgs{v.voxel_m, (uint32_t)v.table_slots, v.table, v.occupied, v.overflow};
     launch_lm_point_cloud_append(gm, call, s);
 }
 
@@ -308,11 +322,44 @@ static vors_status trackers_map_enable(vors_trackers* t, int level, int capacity
     t->map.on = true;
     return VORS_OK;
 }
-// An empty map, then keyframe 0 of every sequence.
+// The voxel filter's switch: every refusal, then every buffer at once. `started`: the handle has passed the point up to which the call
+// is legal (vors_trackers_init / the first vors_tracker_track).
+static vors_status trackers_map_voxels_enable(vors_trackers* t, bool started, const char* before, float voxel_m, int table_slots) {
+    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: needs an enabled keyframe map first (vors_trackers_enable_map)");
+    if (t->map.voxels.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: the voxel filter is already enabled");
+    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, std::string("enable_map_voxels: legal only before ") + before);
+    if (!(voxel_m > 0.0f) || !(voxel_m <= 3.4028234663852886e38f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: voxel size voxel_m must be finite and > 0");
+    if (table_slots < 64 || table_slots > (1 << 30) || (table_slots & (table_slots - 1)) != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: table_slots must be a power of two in 64..2^30");
+    vors_batch* b = t->batch;
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)t->n_seq;
+    vors_trackers::Map::Voxels& v = t->map.voxels;
+    b->own.alloc(&v.table, n * (size_t)table_slots * 2);
+    b->own.alloc(&v.occupied, n);
+    b->own.alloc(&v.overflow, n);
+    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the filter stays off)
+        const hipError_t e = b->own.err;
+        b->own.err = hipSuccess;
+        (void)hipGetLastError();
+        return fail(VORS_ERR_HIP, std::string("hipMalloc (voxel table of the keyframe map): ") + hipGetErrorString(e));
+    }
+    v.voxel_m = voxel_m;
+    v.table_slots = table_slots;
+    v.on = true;
+    return VORS_OK;
+}
+// An empty map (and an empty voxel table), then keyframe 0 of every sequence.
 static vors_status trackers_map_init(vors_trackers* t, hipStream_t s) {
     const size_t n = (size_t)t->n_seq;
     HIP_TRY(hipMemsetAsync(t->map.counts, 0, n * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(t->map.n_segments, 0, n * sizeof(uint32_t), s));
+    if (const vors_trackers::Map::Voxels& v = t->map.voxels; v.on) {
+        HIP_TRY(hipMemsetAsync(v.table, 0xFF, n * (size_t)v.table_slots * 2 * sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(v.occupied, 0, n * sizeof(uint32_t), s));
+        HIP_TRY(hipMemsetAsync(v.overflow, 0, n * sizeof(uint32_t), s));
+    }
     trackers_map_emit(t, t->batch->g, s);  // (unmasked: the handle's geometry carries no selection)
     HIP_TRY(hipGetLastError());
     return VORS_OK;
@@ -347,6 +394,43 @@ vors_status vors_tracker_enable_map(vors_tracker* t, int level, int capacity, in
     DeviceGuard guard(t->device);
     // keyframe 0 exists since create: its records, the handle's copies (dense mode) and the identity pose are what init left on s_main
     return trackers_map_init(t->seq, t->s_main);
+}
+
+vors_status vors_trackers_enable_map_voxels(vors_trackers* t, float voxel_m, int table_slots) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: the handle t is NULL");
+    return trackers_map_voxels_enable(t, t->initialised, "vors_trackers_init (keyframe 0 would be unfiltered)", voxel_m, table_slots);
+}
+
+vors_status vors_trackers_map_voxels(const vors_trackers* t, const uint32_t** d_occupied, const uint32_t** d_overflow) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxels: the handle t is NULL");
+    if (!t->map.voxels.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxels: the voxel filter of the map is not enabled (vors_trackers_enable_map_voxels)");
+    if (d_occupied) *d_occupied = t->map.voxels.occupied;
+    if (d_overflow) *d_overflow = t->map.voxels.overflow;
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map_voxels(vors_tracker* t, float voxel_m, int table_slots) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: the handle t is NULL");
+    vors_status st = trackers_map_voxels_enable(t->seq, t->has_last, "the first vors_tracker_track", voxel_m, table_slots);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    // vors_tracker_enable_map has emitted keyframe 0 unfiltered: the map is emptied and keyframe 0 emitted again, through the filter
+    return trackers_map_init(t->seq, t->s_main);
+}
+
+vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, uint32_t* overflow) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_voxels: the handle t is NULL");
+    const vors_trackers::Map::Voxels& v = t->seq->map.voxels;
+    if (!v.on) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_voxels: the voxel filter of the map is not enabled (vors_tracker_enable_map_voxels)");
+    DeviceGuard guard(t->device);
+    uint32_t words[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&words[0], v.occupied, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipMemcpyAsync(&words[1], v.overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    if (occupied) *occupied = words[0];
+    if (overflow) *overflow = words[1];
+    return VORS_OK;
 }
 
 vors_status vors_tracker_read_map(vors_tracker* t, int capacity, float* xyz, uint32_t* pixel, uint8_t* gray, uint32_t* count, int max_segments,

@@ -171,6 +171,19 @@ class Tracker {  // inverse_compositional.rs:31-34
         return m;
     }
 
+    // Extension: the voxel filter of the keyframe map (vors_tracker_enable_map_voxels): one point per voxel of edge voxel_m, the first in
+    // the map's order. After enable_map, before the first track(); empties the map and emits keyframe 0 again, through the filter.
+    void enable_map_voxels(Float voxel_m, int table_slots) { check(vors_tracker_enable_map_voxels(h_, voxel_m, table_slots)); }
+    struct MapVoxels {
+        std::uint32_t occupied = 0, overflow = 0;  // distinct voxels so far; non-zero once they outgrew table_slots
+    };
+    // The filter's counters (vors_tracker_read_map_voxels; synchronises).
+    MapVoxels read_map_voxels() {
+        MapVoxels v;
+        check(vors_tracker_read_map_voxels(h_, &v.occupied, &v.overflow));
+        return v;
+    }
+
    private:
     friend struct Config;
     Tracker(vors_tracker* h, int rows, int cols, int layout) : h_(h), rows_(rows), cols_(cols), layout_(layout) {}

@@ -9,6 +9,10 @@
 // `--map FILE.ply[,LEVEL[,CAPACITY[,MAX_KEYFRAMES[,MIN_WEIGHT]]]]` collects the cloud of every keyframe on the device
 // (vors_tracker_enable_map; defaults level 0, 4 Mi points, 4096 keyframes, min_weight 0) and writes it as a binary PLY after the last frame.
 // A malformed --map list, or MIN_WEIGHT >= 2 without --depth-filter, prints the usage and exits with status 2 before any device is touched.
+// `--map-voxel SIZE_M[,TABLE_SLOTS]` (needs --map) keeps one point per voxel of edge SIZE_M metres in that map
+// (vors_tracker_enable_map_voxels). TABLE_SLOTS, a power of two, defaults to 8 Mi entries — twice the default capacity, so the table is at
+// most half full when the list is — and costs 16 x TABLE_SLOTS bytes of device memory (128 MiB at the default). Malformed, or without
+// --map: the usage and status 2, before any device is touched. A sequence with more voxels than entries gets a warning after the last frame.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -75,8 +79,28 @@ static bool parse_map(const std::string& val, std::string& file, int ints[4]) {
     return *p == '\0';
 }
 
+// "SIZE_M[,TABLE_SLOTS]": a number, then a whole number, nothing after the last. The VALUES are judged by the library.
+static bool parse_map_voxel(const std::string& val, float& voxel_m, int& table_slots) {
+    if (val.empty()) return false;
+    const char* p = val.c_str();
+    char* end = nullptr;
+    voxel_m = std::strtof(p, &end);
+    if (end == p) return false;
+    if (*end == ',') {
+        p = end + 1;
+        const long v = std::strtol(p, &end, 10);
+        if (end == p || v < -0x7fffffffL || v > 0x7fffffffL) return false;
+        table_slots = (int)v;
+    }
+    return *end == '\0';
+}
+
+static const int MAP_VOXEL_DEFAULT_TABLE_SLOTS = 8 << 20;  // 16 bytes each: 128 MiB
+
 int main(int argc, char** argv) {
-    bool quiet = false, depth_filter = false, map = false, bad_map = false;
+    bool quiet = false, depth_filter = false, map = false, bad_map = false, map_voxel = false, bad_map_voxel = false;
+    float voxel_m = 0.0f;
+    int voxel_table_slots = MAP_VOXEL_DEFAULT_TABLE_SLOTS;
     std::string map_file;
     int map_ints[4] = {0, 4 << 20, 4096, 0};  // level, capacity, max_keyframes, min_weight
     float filter_tol_m = 0.0f;
@@ -100,6 +124,10 @@ int main(int argc, char** argv) {
             map = parse_map(val, map_file, map_ints);
             bad_map = !map;
             ++a;
+        } else if (flag == "--map-voxel") {
+            map_voxel = parse_map_voxel(val, voxel_m, voxel_table_slots);
+            bad_map_voxel = !map_voxel;
+            ++a;
         } else {
             bad_flag = true;
         }
@@ -108,6 +136,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
                      bad_map ? "Malformed --map: expected FILE.ply[,LEVEL[,CAPACITY[,MAX_KEYFRAMES[,MIN_WEIGHT]]]]"
                              : "--map with MIN_WEIGHT >= 2 needs --depth-filter");
+        return 2;
+    }
+    if (bad_map_voxel || (map_voxel && !map)) {
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
+                     bad_map_voxel ? "Malformed --map-voxel: expected SIZE_M[,TABLE_SLOTS]" : "--map-voxel needs --map");
         return 2;
     }
     if (argc > 3) argc = bad_flag ? 0 : 3;
@@ -159,6 +192,7 @@ int main(int argc, char** argv) {
         tracker.set_logging(!quiet);
         if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
         if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
+        if (map_voxel) tracker.enable_map_voxels(voxel_m, voxel_table_slots);
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);
@@ -169,6 +203,9 @@ int main(int argc, char** argv) {
             std::printf("%s\n", tum_rgbd::to_string(tum_rgbd::Frame{cf.first, cf.second}).c_str());
         }
         if (map) {
+            if (map_voxel && tracker.read_map_voxels().overflow != 0)
+                std::fprintf(stderr, "Warning: more voxels than the %d entries of the voxel table: the map is incomplete (raise TABLE_SLOTS or SIZE_M)\n",
+                             voxel_table_slots);
             const track::Tracker::Map m = tracker.read_map();
             if (m.count > (uint32_t)map_ints[1])
                 std::fprintf(stderr, "Warning: the map holds %u points but its capacity is %d: the last %u were dropped\n", m.count, map_ints[1],

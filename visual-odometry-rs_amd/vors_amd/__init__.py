@@ -94,7 +94,8 @@ class vors_obs(C.Structure):
 EXPORTED_SYMBOLS = [
     "vors_last_error", "vors_device_count", "vors_device_info", "vors_abi_version", "vors_selfcheck_isqrt",
     "vors_tracker_create", "vors_tracker_track", "vors_tracker_track_checked", "vors_tracker_current_frame", "vors_tracker_last_stats",
-    "vors_tracker_keyframe", "vors_tracker_enable_depth_filter", "vors_tracker_enable_map", "vors_tracker_read_map", "vors_tracker_destroy",
+    "vors_tracker_keyframe", "vors_tracker_enable_depth_filter", "vors_tracker_enable_map", "vors_tracker_read_map", "vors_tracker_enable_map_voxels",
+    "vors_tracker_read_map_voxels", "vors_tracker_destroy",
     "vors_track_pairs",
     "vors_batch_create", "vors_batch_create_on", "vors_batch_device", "vors_batch_track_pairs", "vors_batch_prepare_keyframes", "vors_batch_track_current",
     "vors_batch_workspace_bytes", "vors_batch_enable_kernel_timing", "vors_batch_kernel_times", "vors_batch_last_kernel_ms",
@@ -113,7 +114,7 @@ EXPORTED_SYMBOLS = [
     "vors_trackers_create", "vors_trackers_create_on", "vors_trackers_count", "vors_trackers_init", "vors_trackers_track", "vors_trackers_state",
     "vors_trackers_current_frames", "vors_trackers_last_stats", "vors_trackers_enable_kernel_timing", "vors_trackers_kernel_times", "vors_trackers_destroy",
     "vors_trackers_enable_depth_filter", "vors_trackers_keyframe_depth", "vors_trackers_workspace_bytes",
-    "vors_trackers_enable_map", "vors_trackers_map",
+    "vors_trackers_enable_map", "vors_trackers_map", "vors_trackers_enable_map_voxels", "vors_trackers_map_voxels", "vors_voxel_keys",
     "vors_synth_render_frames",
     "vors_pipeline_create", "vors_pipeline_submit", "vors_pipeline_wait", "vors_pipeline_drain", "vors_pipeline_destroy",
 ]
@@ -178,6 +179,12 @@ def lib():
         _lib.vors_trackers_map.argtypes = [vp] + [C.POINTER(vp)] * 6
         _lib.vors_tracker_enable_map.argtypes = [vp, i, i, i, i]
         _lib.vors_tracker_read_map.argtypes = [vp, i, vp, vp, vp, C.POINTER(C.c_uint32), i, vp, C.POINTER(C.c_uint32)]
+        _lib.vors_trackers_enable_map_voxels.argtypes = [vp, f, i]
+        _lib.vors_trackers_map_voxels.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        _lib.vors_tracker_enable_map_voxels.argtypes = [vp, f, i]
+        _lib.vors_tracker_read_map_voxels.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
+        _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
         _lib.vors_batch_track_pairs.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib.vors_pipeline_create.argtypes = [i, C.POINTER(vors_config), i, i, i, i, C.POINTER(vp)]
@@ -367,15 +374,56 @@ def _map_args(spec):
     return tuple(int(v) for v in spec)
 
 
+def _map_voxels_args(spec):
+    """None or a pair (voxel_m, table_slots) -> None or (float, int). Only the SHAPE of the argument is judged here; the values (a finite
+    voxel_m > 0, table_slots a power of two in 64..2^30) are judged by the library, in one place for every caller."""
+    if spec is None:
+        return None
+    try:
+        spec = tuple(spec)
+    except TypeError:
+        raise VorsError(f"map_voxels: expected None or (voxel_m, table_slots), got {spec!r}") from None
+    if len(spec) != 2:
+        raise VorsError(f"map_voxels: expected 2 values (voxel_m, table_slots), got {len(spec)}")
+    voxel_m, table_slots = spec
+    if isinstance(voxel_m, bool) or not isinstance(voxel_m, (int, float, np.integer, np.floating)):
+        raise VorsError(f"map_voxels: voxel_m must be a number, got {voxel_m!r}")
+    if isinstance(table_slots, bool) or not isinstance(table_slots, (int, np.integer)):
+        raise VorsError(f"map_voxels: table_slots must be an integer, got {table_slots!r}")
+    if not -2 ** 31 <= int(table_slots) < 2 ** 31:
+        raise VorsError(f"map_voxels: table_slots does not fit the C int it is passed as, got {table_slots!r}")
+    return float(voxel_m), int(table_slots)
+
+
+VOXEL_NONE = 0xFFFFFFFFFFFFFFFF
+
+
+def voxel_keys(voxel_m, xyz):
+    """The voxel keys of points on a grid of edge voxel_m, on the host (vors_voxel_keys; needs no GPU): xyz [..., 3] float32 -> uint64
+    [...], the rule of the keyframe map's voxel filter (Trackers.enable_map_voxels). VOXEL_NONE where a point has no key."""
+    p = np.ascontiguousarray(xyz, np.float32)
+    if p.ndim < 1 or p.shape[-1] != 3:
+        raise VorsError("voxel_keys: xyz must be [..., 3]")
+    if p.size // 3 >= 2 ** 31:
+        raise VorsError("voxel_keys: too many points for one call")
+    out = np.empty(p.shape[:-1], np.uint64)
+    lib().vors_voxel_keys(float(voxel_m), _ptr(p), p.size // 3, _ptr(out))
+    return out
+
+
 class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
-    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None):
+    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
         (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
-        keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it."""
+        keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it. map_voxels: None,
+        or (voxel_m, table_slots) — the map's voxel filter (vors_tracker_enable_map_voxels; Trackers.enable_map_voxels); needs map."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         self._map = map = _map_args(map)
+        self._map_voxels = map_voxels = _map_voxels_args(map_voxels)
+        if map_voxels is not None and map is None:
+            raise VorsError("map_voxels: the voxel filter needs the keyframe map (Tracker(..., map=(level, capacity, max_keyframes)))")
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -390,6 +438,17 @@ class Tracker:
             _check(lib().vors_tracker_enable_depth_filter(self._h, *depth_filter))
         if map is not None:
             _check(lib().vors_tracker_enable_map(self._h, *map))
+        if map_voxels is not None:
+            _check(lib().vors_tracker_enable_map_voxels(self._h, *map_voxels))
+
+    def read_map_voxels(self):
+        """The voxel filter's counters (vors_tracker_read_map_voxels; synchronises) -> dict: "occupied", the distinct voxels so far, and
+        "overflow", non-zero once they outgrew table_slots."""
+        if self._map_voxels is None:
+            raise VorsError("read_map_voxels: the voxel filter is not enabled (Tracker(..., map_voxels=(voxel_m, table_slots)))")
+        occupied, overflow = C.c_uint32(), C.c_uint32()
+        _check(lib().vors_tracker_read_map_voxels(self._h, C.byref(occupied), C.byref(overflow)))
+        return dict(occupied=occupied.value, overflow=overflow.value)
 
     def read_map(self, capacity=None, max_segments=None):
         """The map so far on the host (vors_tracker_read_map; synchronises) -> dict: "count" and "n_segments", the UNCLIPPED totals, "xyz"
@@ -1003,6 +1062,24 @@ class Trackers:
         out = dict(xyz=_device_view(p[0].value, (self.n, cap, 3), "<f4", dev), pixel=_device_view(p[1].value, (self.n, cap), "<i4", dev),
                    gray=_device_view(p[2].value, (self.n, cap), "|u1", dev), counts=_device_view(p[3].value, (self.n,), "<i4", dev),
                    segments=_device_view(p[4].value, (self.n, nkf, 40), "|u1", dev), n_segments=_device_view(p[5].value, (self.n,), "<i4", dev))
+        return {k: v.clone() for k, v in out.items()} if copy else out
+
+    def enable_map_voxels(self, voxel_m, table_slots):
+        """Voxel filter of the keyframe map (vors_trackers_enable_map_voxels): after enable_map(), before init(), once. The map then keeps
+        one point per occupied voxel of a world grid of edge voxel_m — the first in the map's own order — through a table of table_slots
+        entries per sequence (a power of two in 64..2^30; 16 bytes each)."""
+        args = _map_voxels_args((voxel_m, table_slots))
+        _check(lib().vors_trackers_enable_map_voxels(self._h, *args))
+
+    def map_voxels(self, copy=True):
+        """-> dict of tensors (vors_trackers_map_voxels), valid in stream order after the last init() / track(): "occupied" [n] int32, the
+        distinct voxels of a sequence so far (== map()["counts"] while it has not overflowed), "overflow" [n] int32, non-zero once a
+        sequence's voxels outgrew table_slots. copy=False: views of the handle's own buffers, which die with this object."""
+        import torch
+        p = [C.c_void_p() for _ in range(2)]
+        _check(lib().vors_trackers_map_voxels(self._h, *[C.byref(q) for q in p]))
+        dev = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
+        out = dict(occupied=_device_view(p[0].value, (self.n,), "<i4", dev), overflow=_device_view(p[1].value, (self.n,), "<i4", dev))
         return {k: v.clone() for k, v in out.items()} if copy else out
 
     def enable_kernel_timing(self, ring=64):
