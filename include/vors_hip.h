@@ -121,7 +121,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_tracker_enable_depth_filter, likewise; + vors_trackers_enable_map, vors_trackers_map,
                               *    vors_tracker_enable_map, vors_tracker_read_map, vors_map_segment, likewise; + vors_trackers_enable_map_voxels,
                               *    vors_trackers_map_voxels, vors_tracker_enable_map_voxels, vors_tracker_read_map_voxels, vors_voxel_keys,
-                              *    VORS_VOXEL_NONE, likewise) */
+                              *    VORS_VOXEL_NONE, likewise; + vors_render_points, vors_render_points_host, vors_trackers_render_map,
+                              *    vors_tracker_render_map, VORS_RENDER_COUNTS, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -173,6 +174,13 @@ vors_status vors_tracker_enable_map_voxels(vors_tracker* t, float voxel_m, int t
 /* The filter's two counters (vors_trackers_map_voxels, below) to the host, each nullable; synchronises. Filter not enabled:
  * VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, uint32_t* overflow);
+/* The rendering of vors_trackers_render_map (below) for the single sequence, its N = 1 case, to HOST buffers; synchronises. pose7 (HOST,
+ * nullable): camera -> world, NULL = the current frame's pose as the device holds it. range2 (HOST, nullable): (first, count) of the ranks
+ * to render, NULL = the whole map. zkey / depth / gray [rows_l * cols_l] and counts [VORS_RENDER_COUNTS] are each nullable (zkey too: the
+ * key plane is staging here). The device staging (11 bytes per level-0 pixel and 64 bytes of arguments and counters) is the handle's own,
+ * created by the first call; no later call allocates. Same refusals; no enabled map: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_render_map(vors_tracker* t, int level, const float pose7[7] /* nullable */, const uint32_t range2[2] /* nullable */,
+                                    int footprint, uint64_t* zkey, uint16_t* depth, uint8_t* gray, uint32_t* counts);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -285,6 +293,19 @@ vors_status vors_trackers_enable_map_voxels(vors_trackers* t, float voxel_m, int
  * nullable: d_occupied = claimed table entries of a sequence = its distinct voxels so far (== d_counts while it has not overflowed),
  * d_overflow = non-zero once the sequence has overflowed. Filter not enabled: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_map_voxels(const vors_trackers* t, const uint32_t** d_occupied, const uint32_t** d_overflow);
+/* THE KEYFRAME MAP SEEN FROM A POSE: vors_render_points (section 2c) on the handle's own map — its lists, its counters, the intrinsics and
+ * the shape of pyramid level `level` (rows_l x cols_l), the handle's depth_scale. d_poses7 (DEVICE, nullable): one camera -> world pose per
+ * sequence, pose_stride_bytes apart (0 = 28); NULL = every sequence's CURRENT FRAME pose, read on the device from the handle's pose table
+ * (the pointer vors_trackers_state reports), so the call needs no synchronisation after a track. d_ranges / range_stride_bytes, footprint
+ * and the outputs d_zkey (required) / d_depth / d_gray / d_counts [n][rows_l * cols_l] resp. [n][VORS_RENDER_COUNTS]: as in
+ * vors_render_points; sizeof(vors_map_segment) with &d_segments[k].first renders keyframe k alone. Refused with
+ * VORS_ERR_INVALID_ARGUMENT, nothing enqueued: no enabled map, a call before vors_trackers_init, a level out of range, a stream of another
+ * device, and every refusal of vors_render_points. The pass reads the map and the pose table only, writes the caller's planes only, and
+ * allocates nothing; enqueued on hip_stream, NOT synchronised. */
+vors_status vors_trackers_render_map(vors_trackers* t, int level, const void* d_poses7 /* nullable */, size_t pose_stride_bytes,
+                                     const void* d_ranges /* nullable */, size_t range_stride_bytes, int footprint,
+                                     uint64_t* d_zkey, uint16_t* d_depth /* nullable */, uint8_t* d_gray /* nullable */,
+                                     uint32_t* d_counts /* nullable */, void* hip_stream);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -631,6 +652,50 @@ vors_status vors_fuse_depth_pixels(float depth_scale, float tol_m, int max_weigh
                                    const uint64_t* zkey, const uint16_t* cur_depth,
                                    const uint8_t* kf_weight /* nullable */, size_t n_kf_pixels,
                                    uint16_t* fused_depth, uint8_t* fused_weight, uint32_t counts[VORS_FUSE_COUNTS] /* each nullable */);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2c. RENDERING OF POINT LISTS INTO A CAMERA, device-resident and handle-free (like the renderer of section 5): n world-frame lists
+ *     xyz / gray — exactly the pointers of vors_trackers_map and of vors_batch_point_cloud — seen from one pose per list, as a z-buffered
+ *     u16 depth map and u8 grey image in the camera's geometry: the arguments of vors_tracker_create, vors_batch_prepare_keyframes and
+ *     vors_trackers_init. (Camera::project, camera.rs:36-39, per point; the reference has no renderer.)
+ * Lists: d_xyz [n][capacity][3] f32, d_list_gray [n][capacity] u8, d_list_counts [n] u32 (a count above capacity is clipped to it).
+ * d_ranges (DEVICE, nullable): per list a pair of u32 (first, count), range_stride_bytes apart (0 = 8; a multiple of 4 of at least 8):
+ *   only the ranks first <= rank < first + count take part, clipped to the written prefix; NULL = the whole list.
+ * Camera: cam5 (HOST) = cu cv fu fv skew, rows x cols, depth_scale; d_poses7 (DEVICE, nullable): camera -> world, Camera::extrinsics, 7
+ *   floats per list, pose_stride_bytes apart (0 = 28; a multiple of 4 of at least 28); NULL = no transform at all (the lists are already
+ *   in the camera frame), the rule of vors_batch_point_cloud.
+ * PER POINT w of rank r: c = rotation.inverse() * (translation.inverse() * w) (camera.rs:70-72), Z' = c.z, (u, v) = project(c) / c.z:
+ *   (u Z', v Z', Z') are the bits of vors_camera_project. The anchor (x0f, y0f) is (floorf(u + 0.5f), floorf(v + 0.5f)) for footprint 1
+ *   and 3 and (floorf(u), floorf(v)) for footprint 2. The point is a candidate iff Z' > 0, -4.0f <= x0f < (float)cols + 4.0f and
+ *   -4.0f <= y0f < (float)rows + 4.0f, compared in float before any integer conversion (NaN and huge values fail). Footprint 1: the
+ *   anchor pixel (the landing rule of vors_batch_reproject_depth); 2: the four pixels x0 + {0, 1}, y0 + {0, 1}; 3: the nine pixels
+ *   x0 + {-1, 0, 1}, y0 + {-1, 0, 1}. A footprint pixel is written iff it lies inside [0, cols) x [0, rows), tested in integers; the point
+ *   LANDS iff at least one is.
+ * d_zkey [n][rows * cols] (DEVICE, REQUIRED, 8-byte aligned): the minimum over the points written at the pixel of
+ *   (uint64)bits(Z') << 32 | r; VORS_ZKEY_EMPTY where none is. The nearest surface wins, among equal Z' bits the lowest rank: bitwise
+ *   reproducible whatever the order of arrival. d_zkey alone is the splat alone.
+ * d_depth [n][rows * cols] u16 = to_depth(depth_scale, 1.0f / Z') of the key (the bits of d_pred_depth), 0 where empty; d_gray
+ *   [n][rows * cols] u8 = d_list_gray at the key's rank, 0 where empty; d_counts [n][VORS_RENDER_COUNTS] u32 = {considered: the ranks in
+ *   the clipped range; in_front: those with Z' > 0; landed; covered: the pixels whose key is not empty}. DEVICE, each nullable.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: n < 1; a NULL list (d_xyz, d_list_gray, d_list_counts) or cam5; a NULL or
+ * misaligned d_zkey; footprint outside 1..3; rows, cols or capacity < 1; rows or cols > 65535 or rows * cols > 2^28 (the plane limits of
+ * vors_batch_create); depth_scale not > 0; a bad stride; a pointer off its natural alignment (d_xyz, d_list_counts, d_ranges, d_poses7,
+ * d_counts: 4 bytes; d_depth: 2 bytes). Enqueued on hip_stream on the calling thread's current device, NOT synchronised, no allocation
+ * ever. The fill of the key plane, a memset of the counters when they are asked for, the splat kernel and — with any of d_depth, d_gray,
+ * d_counts — the resolve kernel, ordered by the stream; no workgroup waits for another. */
+#define VORS_RENDER_COUNTS 4
+vors_status vors_render_points(int n, const float* d_xyz, const uint8_t* d_list_gray, const uint32_t* d_list_counts, int capacity,
+                               const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                               const float cam5[5], int rows, int cols, float depth_scale,
+                               const void* d_poses7 /* nullable */, size_t pose_stride_bytes, int footprint,
+                               uint64_t* d_zkey, uint16_t* d_depth /* nullable */, uint8_t* d_gray /* nullable */,
+                               uint32_t* d_counts /* nullable */, void* hip_stream);
+/* The same rule for ONE list on the host (host arithmetic, needs no GPU; the text the kernels run): HOST pointers, count = the list's
+ * count (clipped to capacity), range2 (nullable) = (first, count), pose7 (nullable) = camera -> world. Outputs zkey [rows * cols] (required
+ * here too: it is the z-buffer), depth, gray, counts (each nullable). The refusals above, with nothing written. */
+vors_status vors_render_points_host(const float* xyz, const uint8_t* list_gray, uint32_t count, int capacity, const uint32_t range2[2],
+                                    const float cam5[5], int rows, int cols, float depth_scale, const float pose7[7], int footprint,
+                                    uint64_t* zkey, uint16_t* depth, uint8_t* gray, uint32_t counts[VORS_RENDER_COUNTS]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

@@ -15,6 +15,7 @@ listing -DVORS_FUSED=0 lm_kernels.hip -o "$OUT/lm_kernels.s"
 listing -DVORS_FUSED=1 lm_kernels.hip -o "$OUT/lm_kernels_fused.s"
 listing lm_reference.hip -o "$OUT/lm_reference.s"
 listing dso_kernels.hip -o "$OUT/dso_kernels.s"
+if [ -f render_kernels.hip ]; then listing render_kernels.hip -o "$OUT/render_kernels.s"; fi   # (absent in parents older than the renderer)
 for p in $PIDS; do wait $p; done
 grep -h '^\s*\.amdhsa_kernel ' "$OUT"/*.s | sort > "$OUT/kernels.txt"
 echo "$(wc -l < "$OUT/kernels.txt") kernels, listings in $OUT"

@@ -445,6 +445,40 @@ struct FuseMergeArgs {
     uint32_t* counts;
     int wide;                   // every plane allows four pixels per thread: 16-byte key loads, 8-byte depth and 4-byte weight accesses
 };
+// Rendering of world-frame point lists into a camera per sequence (vors_render_points, vors_trackers_render_map; render_kernels.hip): a
+// projection-and-splat pass into a KEYED z-buffer (bits(Z') << 32 | rank of the point in its list, one 64-bit minimum per written pixel),
+// then an elementwise resolve into a u16 depth map and a u8 grey image (lie.h render_point / render_resolve). Handle-free: everything the
+// kernels read is here. zkey is required; the other outputs are nullable.
+struct RenderCall {
+    int n;                       // sequences
+    const float* xyz;            // [n][capacity][3]
+    const uint8_t* list_gray;    // [n][capacity]
+    const uint32_t* list_counts; // [n]; a count above capacity is clipped to it
+    int capacity;
+    const uint8_t* ranges;       // nullable = the whole list; (first, count) u32 pairs, range_stride BYTES apart, clipped to the written prefix
+    int range_stride;
+    Intr k;
+    int rows, cols;
+    float depth_scale;
+    const float* poses;          // camera -> world, nullable = no transform at all
+    int pose_stride;             // floats
+    int footprint;               // 1, 2 or 3
+    uint64_t* zkey;              // [n][rows * cols]
+    uint16_t* depth;             // [n][rows * cols]
+    uint8_t* gray;               // [n][rows * cols]
+    uint32_t* counts;            // [n][VORS_RENDER_COUNTS]
+};
+// Points per workgroup and trip of the splat, and the cap of its grid's x extent: a longer list goes through the stride loop.
+#define RENDER_BLOCK 256
+#define RENDER_POINTS 4  // per thread and trip
+#define RENDER_MAX_CHUNKS 1024
+inline int render_chunks(int capacity) {
+    const long long c = ((long long)capacity + RENDER_BLOCK * RENDER_POINTS - 1) / (RENDER_BLOCK * RENDER_POINTS);
+    return (int)(c < 1 ? 1 : c > RENDER_MAX_CHUNKS ? RENDER_MAX_CHUNKS : c);
+}
+// Fill of the key plane, splat, resolve: enqueued on s in this order, not synchronised, no workspace.
+void launch_render_points(const RenderCall& call, hipStream_t s);
+
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }

@@ -420,6 +420,65 @@ VORS_HD V3 extr_project(const Iso& pose, const V3& p) {
     const Quat qi{-pose.q.i, -pose.q.j, -pose.q.k, pose.q.w};
     return quat_rotate(qi, V3{p.x + -pose.t.x, p.y + -pose.t.y, p.z + -pose.t.z});
 }
+// One point of a world-frame list seen from a camera (the renderer of the keyframe map): c = extr_project(pose, w) — with no
+// pose (has_pose false: `pose` is not read) c = w, no transform at all, the rule of vors_batch_point_cloud —, Z' = c.z, (u, v) = project_uv(K, c): existing texts, unchanged, so
+// (u Z', v Z', Z') has the bits of vors_camera_project. The footprint is anchored at (x0, y0): footprint 1 the one pixel
+// (floorf(u + 0.5f), floorf(v + 0.5f)), the landing rule of the depth reprojection; 2 the four pixels floorf(u) + {0, 1}, floorf(v) + {0, 1};
+// 3 the nine pixels around footprint 1's. The point is a candidate iff Z' > 0 and the anchor lies within four pixels of the window, compared
+// in float BEFORE any integer conversion, so that NaN and huge values fail and no out-of-range float is ever converted. A footprint pixel
+// is written iff it lies inside [0, cols) x [0, rows), tested in integers (render_footprint). The one text the host entry
+// (vors_render_points_host) and the device kernel (render_kernels.hip render_splat_kernel) both run, bit for bit.
+struct RenderPoint {
+    float z;        // Z'
+    int x0, y0;     // the anchor; meaningful only for a candidate
+    bool in_front;  // Z' > 0
+    bool candidate;
+};
+VORS_HD RenderPoint render_point(const Intr& k, bool has_pose, const Iso& pose, const V3& w, int footprint, int cols, int rows) {
+    const V3 c = has_pose ? extr_project(pose, w) : w;
+    float u, v;
+    project_uv(k, c, &u, &v);
+    const float x0f = footprint == 2 ? floorf(u) : floorf(u + 0.5f), y0f = footprint == 2 ? floorf(v) : floorf(v + 0.5f);
+    RenderPoint p{c.z, 0, 0, c.z > 0.0f, false};
+    p.candidate = p.in_front && (x0f >= -4.0f) && (x0f < (float)cols + 4.0f) && (y0f >= -4.0f) && (y0f < (float)rows + 4.0f);
+    if (p.candidate) {
+        p.x0 = (int)x0f;
+        p.y0 = (int)y0f;
+    }
+    return p;
+}
+// The pixels of a candidate's footprint that lie inside the window, in row-major order of the footprint: write(y * cols + x) for each.
+// Returns whether there was one (the point "lands").
+template <class Write>
+VORS_HD bool render_footprint(const RenderPoint& p, int footprint, int cols, int rows, Write&& write) {
+    const int lo = footprint == 3 ? -1 : 0, hi = footprint == 1 ? 0 : 1;
+    bool landed = false;
+    for (int dy = lo; dy <= hi; ++dy)
+        for (int dx = lo; dx <= hi; ++dx) {
+            const int x = p.x0 + dx, y = p.y0 + dy;
+            if (x >= 0 && x < cols && y >= 0 && y < rows) {
+                write(y * cols + x);
+                landed = true;
+            }
+        }
+    return landed;
+}
+// Key of a point in the keyed z-buffer: bits(Z') << 32 | rank. Z' > 0 orders as its bits, so the unsigned minimum picks the nearest surface
+// and, among equal Z' bits, the lowest rank; all ones (VORS_ZKEY_EMPTY) is no point.
+VORS_HD uint64_t render_key(float z, uint32_t rank) { return ((uint64_t)__builtin_bit_cast(uint32_t, z) << 32) | (uint64_t)rank; }
+// One pixel of the key plane resolved: depth = to_depth(scale, 1.0f / Z') — the bits of d_pred_depth — and the grey level of the winning
+// point, both 0 where the key is empty.
+struct RenderedPixel {
+    uint16_t depth;
+    uint8_t gray;
+    bool covered;
+};
+VORS_HD RenderedPixel render_resolve(float depth_scale, uint64_t key, const uint8_t* list_gray) {
+    if (key == 0xFFFFFFFFFFFFFFFFull) return RenderedPixel{0, 0, false};
+    const float zp = __builtin_bit_cast(float, (uint32_t)(key >> 32));
+    return RenderedPixel{to_depth(depth_scale, 1.0f / zp), list_gray[(uint32_t)key], true};
+}
+
 // Jacobian of the warp: src/core/track/inverse_compositional.rs:313-341.
 VORS_HD void warp_jacobian_at(float gu, float gv, float u, float v, float _z, const Intr& k, float J[6]) {
     const float a = u - k.cu;

@@ -205,6 +205,112 @@ vors_status vors_fuse_depth_pixels(float depth_scale, float tol_m, int max_weigh
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Rendering of point lists into a camera (vors_render_points, vors_render_points_host): the refusals both share, the device entry
+// (render_kernels.hip) and the host entry, which runs the kernels' own text (lie.h render_point, render_footprint, render_resolve).
+// ---------------------------------------------------------------------------------------------------------------
+static vors_status render_refusals(const char* who, const void* xyz, const void* list_gray, const float* cam5, int capacity, int rows, int cols,
+                                   float depth_scale, int footprint, const void* zkey) {
+    const std::string w(who);
+    if (!xyz || !list_gray) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, list_gray) is NULL");
+    if (!cam5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cam5 is NULL");
+    if (!zkey) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": zkey is NULL (the pass keeps no plane of its own)");
+    if ((uintptr_t)zkey % 8 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": zkey must be 8-byte aligned");
+    if (footprint < 1 || footprint > 3) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": footprint must be 1, 2 or 3");
+    if (rows < 1 || cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must be >= 1");
+    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
+    if (rows > 65535 || cols > 65535 || (long long)rows * cols > (1ll << 28))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows / cols must not exceed 65535 and rows * cols must not exceed 2^28 pixels");
+    if (!(depth_scale > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth_scale must be > 0");
+    return VORS_OK;
+}
+
+vors_status vors_render_points(int n, const float* d_xyz, const uint8_t* d_list_gray, const uint32_t* d_list_counts, int capacity,
+                               const void* d_ranges, size_t range_stride_bytes, const float cam5[5], int rows, int cols, float depth_scale,
+                               const void* d_poses7, size_t pose_stride_bytes, int footprint, uint64_t* d_zkey, uint16_t* d_depth,
+                               uint8_t* d_gray, uint32_t* d_counts, void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: n must be >= 1");
+    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: a list (d_list_counts) is NULL");
+    vors_status st = render_refusals("render_points", d_xyz, d_list_gray, cam5, capacity, rows, cols, depth_scale, footprint, d_zkey);
+    if (st != VORS_OK) return st;
+    if (pose_stride_bytes != 0 && (pose_stride_bytes < 28 || pose_stride_bytes % 4 != 0 || pose_stride_bytes > 0x7fffffffu))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: pose_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    if (range_stride_bytes != 0 && (range_stride_bytes < 8 || range_stride_bytes % 4 != 0 || range_stride_bytes > 0x7fffffffu))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: range_stride_bytes must be 0 or a multiple of 4 of at least 8");
+    if ((uintptr_t)d_ranges % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: d_ranges must be 4-byte aligned");
+    // the kernels read floats and u32 and write u16 and u32 through these: each at its natural alignment
+    if ((uintptr_t)d_xyz % 4 != 0 || (uintptr_t)d_list_counts % 4 != 0 || (uintptr_t)d_poses7 % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: d_xyz, d_list_counts and d_poses7 must be 4-byte aligned");
+    if ((uintptr_t)d_depth % 2 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: d_depth must be 2-byte aligned");
+    if ((uintptr_t)d_counts % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: d_counts must be 4-byte aligned");
+    if ((st = require_device()) != VORS_OK) return st;
+    RenderCall call{};
+    call.n = n;
+    call.xyz = d_xyz;
+    call.list_gray = d_list_gray;
+    call.list_counts = d_list_counts;
+    call.capacity = capacity;
+    call.ranges = static_cast<const uint8_t*>(d_ranges);
+    call.range_stride = range_stride_bytes ? (int)range_stride_bytes : 8;
+    call.k = Intr{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    call.rows = rows;
+    call.cols = cols;
+    call.depth_scale = depth_scale;
+    call.poses = static_cast<const float*>(d_poses7);
+    call.pose_stride = pose_stride_bytes ? (int)(pose_stride_bytes / 4) : 7;
+    call.footprint = footprint;
+    call.zkey = d_zkey;
+    call.depth = d_depth;
+    call.gray = d_gray;
+    call.counts = d_counts;
+    launch_render_points(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_render_points_host(const float* xyz, const uint8_t* list_gray, uint32_t count, int capacity, const uint32_t range2[2],
+                                    const float cam5[5], int rows, int cols, float depth_scale, const float pose7[7], int footprint, uint64_t* zkey,
+                                    uint16_t* depth, uint8_t* gray, uint32_t counts[VORS_RENDER_COUNTS]) {
+    vors_status st = render_refusals("render_points_host", xyz, list_gray, cam5, capacity, rows, cols, depth_scale, footprint, zkey);
+    if (st != VORS_OK) return st;
+    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    Iso pose = iso_identity();
+    if (pose7) pose = iso_load(pose7);
+    const size_t plane = (size_t)rows * (size_t)cols;
+    // the range of ranks, clipped to the written prefix (the text of render_splat_kernel)
+    const uint32_t n = count < (uint32_t)capacity ? count : (uint32_t)capacity;
+    uint32_t first = 0, last = n;
+    if (range2) {
+        first = range2[0] < n ? range2[0] : n;
+        last = range2[1] > n - first ? n : first + range2[1];
+    }
+    for (size_t q = 0; q < plane; ++q) zkey[q] = VORS_ZKEY_EMPTY;
+    uint32_t c[VORS_RENDER_COUNTS] = {0, 0, 0, 0};
+    for (uint32_t rank = first; rank < last; ++rank) {
+        const float* p = xyz + 3 * (size_t)rank;
+        const RenderPoint rp = render_point(k, pose7 != nullptr, pose, V3{p[0], p[1], p[2]}, footprint, cols, rows);
+        bool landed = false;
+        if (rp.candidate) {
+            const uint64_t key = render_key(rp.z, rank);
+            landed = render_footprint(rp, footprint, cols, rows, [&](int q) {
+                if (key < zkey[q]) zkey[q] = key;
+            });
+        }
+        c[0] += 1;
+        c[1] += rp.in_front ? 1 : 0;
+        c[2] += landed ? 1 : 0;
+    }
+    for (size_t q = 0; q < plane; ++q) {
+        const RenderedPixel o = render_resolve(depth_scale, zkey[q], list_gray);
+        if (depth) depth[q] = o.depth;
+        if (gray) gray[q] = o.gray;
+        c[3] += o.covered ? 1 : 0;
+    }
+    if (counts)
+        for (int i = 0; i < VORS_RENDER_COUNTS; ++i) counts[i] = c[i];
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------
 void vors_se3_exp(const float xi[6], float out_iso7[7]) { iso_store(se3_exp(xi), out_iso7); }

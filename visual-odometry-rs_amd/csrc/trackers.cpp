@@ -193,6 +193,7 @@ struct vors_tracker {
     vors_trackers* seq = nullptr;  // n_sequences = 1
     DevBuf gray, depth, tmp8, tmp16;   // the frame on the device (row-major); tmp*: column-major uploads before the transpose
     PinnedBuf h_gray, h_depth, h_out;  // staging: frame in; pose7 + status + keyframe index + vors_pair_stats out
+    DevBuf render_zkey, render_depth, render_gray, render_args;  // vors_tracker_render_map: created by its first call (level 0's shape)
     hipStream_t s_main = nullptr, s_copy = nullptr;
     hipEvent_t ev_depth = nullptr, ev_frame_done = nullptr, ev_result = nullptr;
     // State of inverse_compositional.rs:52-60 as the host reports it
@@ -453,6 +454,67 @@ vors_status vors_tracker_read_map(vors_tracker* t, int capacity, float* xyz, uin
     HIP_TRY(hipStreamSynchronize(t->s_main));
     if (count) *count = totals[0];
     if (n_segments) *n_segments = totals[1];
+    return VORS_OK;
+}
+
+vors_status vors_trackers_render_map(vors_trackers* t, int level, const void* d_poses7, size_t pose_stride_bytes, const void* d_ranges,
+                                     size_t range_stride_bytes, int footprint, uint64_t* d_zkey, uint16_t* d_depth, uint8_t* d_gray,
+                                     uint32_t* d_counts, void* hip_stream) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: the handle t is NULL");
+    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: the keyframe map is not enabled (vors_trackers_enable_map)");
+    if (!t->initialised) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: called before vors_trackers_init (there is no map and no pose yet)");
+    vors_batch* b = t->batch;
+    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: level out of range");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    vors_status st = check_stream(b, s);
+    if (st != VORS_OK) return st;
+    const LevelGeom& lv = b->g.lv[level];
+    const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
+    // NULL poses: the current frame poses, which the track call has already moved forward in stream order
+    if (!d_poses7) pose_stride_bytes = 0;
+    return vors_render_points(t->n_seq, t->map.xyz, t->map.gray, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes, cam5, lv.rows,
+                              lv.cols, b->g.depth_scale, d_poses7 ? d_poses7 : t->cur_poses.p, pose_stride_bytes, footprint, d_zkey, d_depth,
+                              d_gray, d_counts, s);
+}
+
+vors_status vors_tracker_render_map(vors_tracker* t, int level, const float pose7[7], const uint32_t range2[2], int footprint, uint64_t* zkey,
+                                    uint16_t* depth, uint8_t* gray, uint32_t* counts) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: the handle t is NULL");
+    if (!t->seq->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: the keyframe map is not enabled (vors_tracker_enable_map)");
+    const Geom& g = t->seq->batch->g;
+    if (level < 0 || level >= g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: level out of range");
+    DeviceGuard guard(t->device);
+    const size_t S = (size_t)t->rows * t->cols, plane = (size_t)g.lv[level].rows * g.lv[level].cols;
+    struct Args {  // layout of render_args
+        float pose[7];
+        uint32_t range[2];
+        uint32_t counts[VORS_RENDER_COUNTS];
+    };
+    if (!t->render_args.p) {  // (the last of the four: a call that failed half way allocates the missing ones, DevBuf keeps what exists)
+        if (!t->render_zkey.p) HIP_TRY(t->render_zkey.alloc(S * sizeof(uint64_t)));
+        if (!t->render_depth.p) HIP_TRY(t->render_depth.alloc(S * sizeof(uint16_t)));
+        if (!t->render_gray.p) HIP_TRY(t->render_gray.alloc(S));
+        HIP_TRY(t->render_args.alloc(64));
+    }
+    static_assert(sizeof(Args) <= 64, "render_args holds one Args");
+    Args h{};
+    if (pose7) std::memcpy(h.pose, pose7, sizeof(h.pose));
+    if (range2) std::memcpy(h.range, range2, sizeof(h.range));
+    Args* d = t->render_args.as<Args>();
+    HIP_TRY(hipMemcpyAsync(d, &h, sizeof(Args), hipMemcpyHostToDevice, t->s_main));
+    vors_status st = vors_trackers_render_map(t->seq, level, pose7 ? d->pose : nullptr, 0, range2 ? d->range : nullptr, 0, footprint,
+                                              t->render_zkey.as<uint64_t>(), t->render_depth.as<uint16_t>(), t->render_gray.as<uint8_t>(),
+                                              d->counts, t->s_main);
+    if (st != VORS_OK) {
+        (void)hipStreamSynchronize(t->s_main);  // (h leaves scope)
+        return st;
+    }
+    if (zkey) HIP_TRY(hipMemcpyAsync(zkey, t->render_zkey.p, plane * sizeof(uint64_t), hipMemcpyDeviceToHost, t->s_main));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, t->render_depth.p, plane * sizeof(uint16_t), hipMemcpyDeviceToHost, t->s_main));
+    if (gray) HIP_TRY(hipMemcpyAsync(gray, t->render_gray.p, plane, hipMemcpyDeviceToHost, t->s_main));
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, d->counts, sizeof(h.counts), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
     return VORS_OK;
 }
 

@@ -183,6 +183,25 @@ class Tracker {  // inverse_compositional.rs:31-34
         check(vors_tracker_read_map_voxels(h_, &v.occupied, &v.overflow));
         return v;
     }
+    // Extension: the map seen from a pose (vors_tracker_render_map; synchronises): a z-buffered depth map and grey image in the geometry
+    // of pyramid level `level`, row-major, the arguments of Config::init. pose = nullptr: the current frame's pose; range2 = nullptr: the
+    // whole map, else (first, count) of the ranks to render (a vors_map_segment's `first`); footprint: 1, 2 or 3 pixels wide.
+    struct Rendering {
+        int rows = 0, cols = 0;
+        std::vector<std::uint16_t> depth;  // 0 = no point landed
+        std::vector<std::uint8_t> gray;
+        std::uint32_t counts[VORS_RENDER_COUNTS] = {0, 0, 0, 0};  // considered, in front, landed, covered
+    };
+    Rendering render_map(int level = 0, const Iso3* pose = nullptr, const std::uint32_t* range2 = nullptr, int footprint = 1) {
+        Rendering r;
+        if (level < 0 || level >= VORS_MAX_LEVELS) throw std::invalid_argument("Tracker::render_map: level out of range");
+        r.rows = rows_ >> level;
+        r.cols = cols_ >> level;
+        r.depth.resize((size_t)r.rows * r.cols);
+        r.gray.resize((size_t)r.rows * r.cols);
+        check(vors_tracker_render_map(h_, level, pose ? pose->data() : nullptr, range2, footprint, nullptr, r.depth.data(), r.gray.data(), r.counts));
+        return r;
+    }
 
    private:
     friend struct Config;

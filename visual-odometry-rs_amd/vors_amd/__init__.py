@@ -23,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VORS_HIP_LIB") or os.path.join(_HERE, "libvors_hip.so")  # VORS_HIP_LIB: development builds (ablations)
 MAX_LEVELS = 8
 RESIDUAL_BINS = 256  # VORS_RESIDUAL_BINS
+RENDER_COUNTS = 4  # VORS_RENDER_COUNTS: considered, in front, landed, covered
 
 ROW_MAJOR, COL_MAJOR = 0, 1
 CANDIDATES_COARSE_TO_FINE, CANDIDATES_DENSE, CANDIDATES_DSO = 0, 1, 2
@@ -95,7 +96,7 @@ EXPORTED_SYMBOLS = [
     "vors_last_error", "vors_device_count", "vors_device_info", "vors_abi_version", "vors_selfcheck_isqrt",
     "vors_tracker_create", "vors_tracker_track", "vors_tracker_track_checked", "vors_tracker_current_frame", "vors_tracker_last_stats",
     "vors_tracker_keyframe", "vors_tracker_enable_depth_filter", "vors_tracker_enable_map", "vors_tracker_read_map", "vors_tracker_enable_map_voxels",
-    "vors_tracker_read_map_voxels", "vors_tracker_destroy",
+    "vors_tracker_read_map_voxels", "vors_tracker_render_map", "vors_tracker_destroy",
     "vors_track_pairs",
     "vors_batch_create", "vors_batch_create_on", "vors_batch_device", "vors_batch_track_pairs", "vors_batch_prepare_keyframes", "vors_batch_track_current",
     "vors_batch_workspace_bytes", "vors_batch_enable_kernel_timing", "vors_batch_kernel_times", "vors_batch_last_kernel_ms",
@@ -106,6 +107,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_reproject_depth", "vors_to_depth", "vors_from_depth",
     "vors_batch_point_cloud", "vors_camera_back_project", "vors_camera_project",
     "vors_batch_fuse_depth", "vors_fuse_depth_pixels",
+    "vors_render_points", "vors_render_points_host", "vors_trackers_render_map",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -183,6 +185,10 @@ def lib():
         _lib.vors_trackers_map_voxels.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_voxels.argtypes = [vp, f, i]
         _lib.vors_tracker_read_map_voxels.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.vors_render_points.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, i, i, f, vp, C.c_size_t, i, vp, vp, vp, vp, vp]
+        _lib.vors_render_points_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, i, i, f, vp, i, vp, vp, vp, vp]
+        _lib.vors_trackers_render_map.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, i, vp, vp, vp, vp, vp]
+        _lib.vors_tracker_render_map.argtypes = [vp, i, vp, vp, i, vp, vp, vp, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -464,6 +470,24 @@ class Tracker:
         _check(lib().vors_tracker_read_map(self._h, cap, _ptr(xyz), _ptr(pixel), _ptr(gray), C.byref(count), nseg, _ptr(seg), C.byref(n_segments)))
         m, k = min(count.value, cap, self._map[1]), min(n_segments.value, nseg, self._map[2])
         return dict(count=count.value, n_segments=n_segments.value, xyz=xyz[:m], pixel=pixel[:m], gray=gray[:m], segments=seg[:k])
+
+    def render_map(self, level=0, pose7=None, range2=None, footprint=1):
+        """The map seen from a pose on the host (vors_tracker_render_map; synchronises): Trackers.render_map for the single sequence ->
+        dict: "zkey" [rows_l, cols_l] uint64, "depth" uint16, "gray" uint8, "counts" [4] uint32. pose7 None = the current frame's pose;
+        range2 None = the whole map, else (first, count) of the ranks to render."""
+        if self._map is None:
+            raise VorsError("render_map: the keyframe map is not enabled (Tracker(..., map=(level, capacity, max_keyframes)))")
+        rows, cols = self._shape[0] >> int(level), self._shape[1] >> int(level)
+        pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+        rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+        if (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,)):
+            raise VorsError("render_map: pose7 [7] or None, range2 (first, count) or None")
+        shape = (max(rows, 0), max(cols, 0))
+        out = dict(zkey=np.empty(shape, np.uint64), depth=np.empty(shape, np.uint16), gray=np.empty(shape, np.uint8),
+                   counts=np.zeros(RENDER_COUNTS, np.uint32))
+        _check(lib().vors_tracker_render_map(self._h, int(level), _ptr(pose), _ptr(rng), int(footprint), _ptr(out["zkey"]), _ptr(out["depth"]),
+                                             _ptr(out["gray"]), _ptr(out["counts"])))
+        return out
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -1082,6 +1106,21 @@ class Trackers:
         out = dict(occupied=_device_view(p[0].value, (self.n,), "<i4", dev), overflow=_device_view(p[1].value, (self.n,), "<i4", dev))
         return {k: v.clone() for k, v in out.items()} if copy else out
 
+    def render_map(self, level=0, poses=None, ranges=None, footprint=1, depth=True, gray=True, counts=False, zkey=False):
+        """The keyframe map seen from one pose per sequence (vors_trackers_render_map): render_points() on the handle's own map with the
+        intrinsics and the shape of pyramid level `level`, on the current stream, not synchronised. poses None = every sequence's current
+        frame pose, read on the device. Everything else, and the result, as in render_points()."""
+        lvl = int(level)
+        shape = (self.n, self.rows >> lvl, self.cols >> lvl)
+        dev = _torch_device(self._device)
+        poses, pose_stride = _render_poses(poses, self.n)
+        rng, range_stride = _render_ranges(ranges, self.n)
+        bufs = _render_outputs(shape, dev, zkey, depth, gray, counts)
+        _check(lib().vors_trackers_render_map(self._h, lvl, Batch._dp(poses), pose_stride, rng, range_stride, int(footprint),
+                                              *[Batch._dp(t) for t in bufs], Batch._stream()))
+        self._render_refs = (poses, ranges)
+        return _render_result(bufs, zkey, depth, gray, counts)
+
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
 
@@ -1275,6 +1314,109 @@ def fuse_depth_pixels(depth_scale, tol_m, zkey, cur_depth, kf_weight=None, max_w
     _check(lib().vors_fuse_depth_pixels(float(depth_scale), float(tol_m), int(max_weight), int(fill_min_weight), key.size, _ptr(key), _ptr(d),
                                         _ptr(w), int(n_kf_pixels), _ptr(depth), _ptr(weight), _ptr(counts)))
     return depth, weight, counts
+
+
+def _torch_device(index=None):
+    import torch
+    return torch.device("cuda", torch.cuda.current_device() if index is None else int(index))
+
+
+def _render_poses(poses, n):
+    """poses [n, 7] float32 or a track's out_stats bytes, or None -> (tensor, stride in bytes)."""
+    if poses is None:
+        return None, 0
+    poses, m, k, stride = Batch._models_arg(poses)
+    if k != 1 or m < n:
+        raise VorsError(f"render: expected one pose for each of the {n} lists")
+    return poses, stride
+
+
+def _render_ranges(ranges, n):
+    """ranges: None, an int32 tensor [n, 2] of (first, count), or (tensor, offset_bytes, stride_bytes) — e.g. (map["segments"], 40 k + 4, 40
+    MAX_KEYFRAMES) for keyframe k of every sequence -> (device pointer, stride in bytes)."""
+    import torch
+    if ranges is None:
+        return None, 0
+    if isinstance(ranges, tuple):
+        t, off, stride = ranges
+        if not t.is_contiguous() or int(off) < 0 or int(off) + 8 + (n - 1) * int(stride) > t.numel() * t.element_size():
+            raise VorsError("render: the (first, count) pairs must lie inside the contiguous ranges tensor")
+        return C.c_void_p(t.data_ptr() + int(off)), int(stride)
+    if ranges.dtype != torch.int32 or not ranges.is_contiguous() or tuple(ranges.shape) != (n, 2):
+        raise VorsError(f"render: expected a contiguous int32 ranges [{n}, 2], got {ranges.dtype} {tuple(ranges.shape)}")
+    return C.c_void_p(ranges.data_ptr()), 0
+
+
+def _render_outputs(shape, dev, zkey, depth, gray, counts):
+    """True = a new tensor, a tensor = write into it, False / None = not wanted (the key plane is made all the same)."""
+    import torch
+
+    def buf(o, shp, dtype, always=False):
+        if o is False or o is None:
+            return torch.empty(shp, dtype=dtype, device=dev) if always else None
+        if o is True:
+            return torch.empty(shp, dtype=dtype, device=dev)
+        if o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shp):
+            raise VorsError(f"expected a contiguous {dtype} output {tuple(shp)}, got {o.dtype} {tuple(o.shape)}")
+        return o
+
+    return (buf(zkey, shape, torch.int64, always=True), buf(depth, shape, torch.int16), buf(gray, shape, torch.uint8),
+            buf(counts, (shape[0], RENDER_COUNTS), torch.int32))
+
+
+def _render_result(bufs, zkey, depth, gray, counts):
+    out = {}
+    for name, want, t in zip(("zkey", "depth", "gray", "counts"), (zkey, depth, gray, counts), bufs):
+        if want is not False and want is not None:
+            out[name] = t
+    return out
+
+
+def render_points(xyz, list_gray, list_counts, cam5, rows, cols, depth_scale, poses=None, ranges=None, footprint=1, depth=True, gray=True,
+                  counts=False, zkey=False):
+    """n world-frame point lists seen from one camera pose each (vors_render_points; handle-free) -> dict of the requested tensors on the
+    current stream, not synchronised: "depth" [n, rows, cols] (int16 tensor holding the u16 payload, 0 = nothing landed), "gray" [n, rows,
+    cols] uint8, "zkey" [n, rows, cols] (int64 tensor holding bits(Z') << 32 | rank, -1 = empty), "counts" [n, 4] int32 (considered, in
+    front, landed, covered). xyz [n, capacity, 3] float32, list_gray [n, capacity] uint8, list_counts [n] int32: the tensors of
+    Trackers.map() / Batch.point_cloud(). poses [n, 7] float32 camera -> world (None = no transform); ranges: see _render_ranges;
+    footprint 1, 2 or 3 pixels wide. depth / gray / counts / zkey may also be a tensor of that shape to write into."""
+    import torch
+    n = xyz.shape[0]
+    cap = xyz.shape[1] if xyz.dim() == 3 else -1
+    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or list_gray.dtype != torch.uint8
+            or not list_gray.is_contiguous() or tuple(list_gray.shape) != (n, cap) or list_counts.dtype != torch.int32
+            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
+        raise VorsError("render_points: xyz float32 [n, capacity, 3], list_gray uint8 [n, capacity], list_counts int32 [n], contiguous")
+    k = np.ascontiguousarray(cam5, np.float32)
+    if k.shape != (5,):
+        raise VorsError("render_points: cam5 [5]")
+    poses, pose_stride = _render_poses(poses, n)
+    rng, range_stride = _render_ranges(ranges, n)
+    bufs = _render_outputs((n, int(rows), int(cols)), xyz.device, zkey, depth, gray, counts)
+    _check(lib().vors_render_points(n, Batch._dp(xyz), Batch._dp(list_gray), Batch._dp(list_counts), cap, rng, range_stride, _ptr(k), int(rows),
+                                    int(cols), float(depth_scale), Batch._dp(poses), pose_stride, int(footprint),
+                                    *[Batch._dp(t) for t in bufs], Batch._stream()))
+    return _render_result(bufs, zkey, depth, gray, counts)
+
+
+def render_points_host(xyz, list_gray, cam5, rows, cols, depth_scale, pose7=None, footprint=1, count=None, range2=None):
+    """The rule of render_points for ONE list on the host (vors_render_points_host; needs no GPU; the text the kernels run): xyz
+    [capacity, 3] float32, list_gray [capacity] uint8, count = the list's count (None = capacity; above it: clipped), range2 = (first,
+    count) or None, pose7 camera -> world or None -> dict: "zkey" [rows, cols] uint64, "depth" uint16, "gray" uint8, "counts" [4] uint32."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    g = np.ascontiguousarray(list_gray, np.uint8).reshape(-1)
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+    if len(p) != len(g) or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,)):
+        raise VorsError("render_points_host: xyz [capacity, 3], list_gray [capacity], cam5 [5], pose7 [7] or None, range2 [2] or None")
+    shape = (max(int(rows), 0), max(int(cols), 0))
+    out = dict(zkey=np.empty(shape, np.uint64), depth=np.empty(shape, np.uint16), gray=np.empty(shape, np.uint8),
+               counts=np.zeros(RENDER_COUNTS, np.uint32))
+    _check(lib().vors_render_points_host(_ptr(p), _ptr(g), len(p) if count is None else int(count), len(p), _ptr(rng), _ptr(k), int(rows),
+                                         int(cols), float(depth_scale), _ptr(pose), int(footprint), _ptr(out["zkey"]), _ptr(out["depth"]),
+                                         _ptr(out["gray"]), _ptr(out["counts"])))
+    return out
 
 
 def ref_sincos(x):
