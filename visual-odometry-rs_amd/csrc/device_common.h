@@ -1,4 +1,4 @@
-// Device helpers shared by kernels.hip, lm_kernels.hip and lm_reference.hip.
+// Device helpers shared by kernels.hip, lm_kernels.hip (and product_kernels.hip, through lm_sources.h) and lm_reference.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

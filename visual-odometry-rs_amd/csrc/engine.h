@@ -1,4 +1,4 @@
-// Internal interface between the HIP kernels and their launch functions (kernels.hip, lm_kernels.hip, lm_reference.hip, dso_kernels.hip)
+// Internal interface between the HIP kernels and their launch functions (kernels.hip, lm_kernels.hip, product_kernels.hip, lm_reference.hip, dso_kernels.hip)
 // and the host engine / C ABI (host_common.h; batch.cpp, trackers.cpp, pipeline.cpp, operators.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -517,6 +517,11 @@ void with_bool(bool v, F&& f) {
     if (v) f(std::true_type{});
     else f(std::false_type{});
 }
+// f(pair0, np) for every slice of at most 32768 pairs (the y extent of a grid), in index order
+template <class F>
+void for_pair_slices(int n_pairs, F&& f) {
+    for (int pair0 = 0; pair0 < n_pairs; pair0 += 32768) f(pair0, n_pairs - pair0 < 32768 ? n_pairs - pair0 : 32768);
+}
 // ... the first of the candidates (descending) that v reaches, the last one otherwise
 template <int First, int... Rest, class F>
 void with_largest_reached(int v, F&& f) {
@@ -560,24 +565,24 @@ void launch_lm_eval_pairs_reference(const Geom& g, const EvalPairsCall& call, hi
 // [n][29] sums -> information matrix, covariance, sigma^2, flags (lie.h pose_information), one thread per pair; outputs nullable
 void launch_pose_information(const float* sums29, int n, float* info36, float* cov36, float* sigma2, int32_t* flags, hipStream_t s);
 // Residuals, warp field, |residual| histogram and its scale of one level per pair, in the reference's per-point arithmetic whatever the
-// handle's (lm_kernels.hip lm_residual_maps_kernel, residual_scale_kernel): enqueued, not synchronised, no workspace.
+// handle's (product_kernels.hip lm_residual_maps_kernel, residual_scale_kernel): enqueued, not synchronised, no workspace.
 void launch_lm_residual_maps(const Geom& g, const ResidualMapsCall& call, hipStream_t s);
 // Z-buffered forward warp of the keyframe's depth into the current frame, its u16 depth map, the geometric residual against a measured
-// current depth and the four counts, in the reference's per-point arithmetic whatever the handle's (lm_kernels.hip
+// current depth and the four counts, in the reference's per-point arithmetic whatever the handle's (product_kernels.hip
 // lm_reproject_depth_kernel, pred_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
 void launch_lm_reproject_depth(const Geom& g, const ReprojectCall& call, hipStream_t s);
 // Keyed z-buffer splat of level 0 and the per-pixel merge with the measured depth, in the reference's per-point arithmetic whatever the
-// handle's (lm_kernels.hip lm_fuse_splat_kernel, fuse_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
+// handle's (product_kernels.hip lm_fuse_splat_kernel, fuse_depth_kernel): enqueued, not synchronised, no workspace. Reads no current image.
 void launch_lm_fuse_depth(const Geom& g, const FuseDepthCall& call, hipStream_t s);
 // The same pass as MASKED launches (the depth filter of vors_trackers): only the sequences of g.sel_list take part, their key planes
 // are filled by a masked launch too; call.n_pairs is the extent of the pair dimension (all sequences). Every plane of the call is
 // required, no counts.
 void launch_lm_fuse_depth_selected(const Geom& g, const FuseDepthCall& call, hipStream_t s);
-// Ordered stream compaction of the usable (and kept) points of one level per pair into point lists in the world frame (lm_kernels.hip
+// Ordered stream compaction of the usable (and kept) points of one level per pair into point lists in the world frame (product_kernels.hip
 // point_cloud_kernel: a counting launch into call.ws, then a ranking and writing launch; no workgroup waits for another): enqueued, not
 // synchronised. Reads no current image.
 void launch_lm_point_cloud(const Geom& g, const PointCloudCall& call, hipStream_t s);
-// The same pass as MASKED launches that APPEND (the keyframe map of vors_trackers; lm_kernels.hip point_cloud_append_kernel,
+// The same pass as MASKED launches that APPEND (the keyframe map of vors_trackers; product_kernels.hip point_cloud_append_kernel,
 // point_cloud_commit_kernel): count, write behind the sequence's running total, commit the segment record and the totals. call.n_seq is
 // the extent of the pair dimension (all sequences); only the sequences of g.sel_list (null: all) are touched. With call.voxels.table set
 // the emission is CLAIM, COUNT, WRITE of point_cloud_append_voxel_kernel and the same commit.

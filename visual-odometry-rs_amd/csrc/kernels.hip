@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void compact_regions_kernel(Geom g, Records re
 // ------------------------------------------------------------------------------------------------------------
 // keyframe precompute, dense candidates (extension): all-true level-0 mask, any image size. Candidates are the pixels
 // themselves (slot = y*cols + x at each level). NOTHING per-point is stored for level 0: the LM kernel recomputes each
-// point from the keyframe image and the depth map (lm_kernels.hip, DenseSrc). For levels >= 1 only the fused inverse depth
+// point from the keyframe image and the depth map (lm_sources.h, DenseSrc). For levels >= 1 only the fused inverse depth
 // (IZ plane, NaN = Unknown) and its weight (V plane, < 0 = Unknown) are stored: 8 B per pixel of levels >= 1.
 // Fusion follows inverse_depth.rs:49-66,81-98 with the four children in [a,b,c,d] order.
 // ------------------------------------------------------------------------------------------------------------

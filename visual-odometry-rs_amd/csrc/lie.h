@@ -266,7 +266,7 @@ VORS_UNROLL
 // last one 255 <= |r|), in f64: n = sum of the bins, target = n / 2, b = the first bin whose cumulative count reaches target,
 // median_abs = b + (target - count below b) / hist[b] (the bin's counts spread evenly over its width), sigma_mad = 1.4826 median_abs, each
 // rounded to f32 at the end. n = 0: both NaN. Every output is nullable. The one text the host entry (vors_residual_scale_from_hist) and
-// the device kernel (lm_kernels.hip residual_scale_kernel) both run.
+// the device kernel (product_kernels.hip residual_scale_kernel) both run.
 VORS_HD void residual_scale_from_hist(const uint32_t* hist, float* median_abs, float* sigma_mad, uint32_t* n_inside) {
     unsigned long long n = 0;
     for (int k = 0; k < 256; ++k) n += hist[k];
@@ -288,7 +288,7 @@ VORS_HD void residual_scale_from_hist(const uint32_t* hist, float* median_abs, f
 // Inverse depth -> depth map value: inverse_depth.rs:37-42, `(scale / x).round() as u16`. roundf rounds halves away from zero like
 // f32::round; the cast saturates like Rust's `as` (NaN -> 0, <= 0 -> 0, >= 65535 -> 65535). The comparisons are made in float BEFORE the
 // integer conversion, so no out-of-range float is ever converted. The one text the host entry (vors_to_depth) and the device kernel
-// (lm_kernels.hip pred_depth_kernel) both run.
+// (product_kernels.hip pred_depth_kernel) both run.
 VORS_HD uint16_t to_depth(float scale, float idepth) {
     const float r = roundf(scale / idepth);
     if (!(r > 0.0f)) return 0;  // NaN, zero, negative
@@ -298,7 +298,7 @@ VORS_HD uint16_t to_depth(float scale, float idepth) {
 
 // Depth fusion of one pixel of the current frame: the keyed z-buffer entry `key` = bits(Z') << 32 | src of the nearest keyframe point
 // that lands here (all ones: none), its weight (kf_weight[src], 1 without a plane) and the measured depth d (0 = unknown).
-// r = Z' - (float)d / depth_scale is the text of the depth residual (lm_kernels.hip reproject_sweep). Cases, which are also the counters:
+// r = Z' - (float)d / depth_scale is the text of the depth residual (product_kernels.hip reproject_sweep). Cases, which are also the counters:
 //   0 agree      |r| <= tol_m         depth = to_depth(scale, (wk / Z' + scale / d) / (wk + 1)), weight = min(wk + 1, max_weight)
 //   1 conflict, prediction in front   r < -tol_m: the measurement, weight 1
 //   2 conflict, prediction behind     r > tol_m:  the measurement, weight 1
@@ -307,7 +307,7 @@ VORS_HD uint16_t to_depth(float scale, float idepth) {
 //   5 empty      everything else (a NaN residual included): 0, 0
 // The mean is taken in inverse depth, the quantity the tracker works in; scale / (float)d is from_depth's expression. A fused depth that
 // rounds to 0 (a surface nearer than half a depth unit) gets weight 0, so that depth 0 and weight 0 always coincide; its case stays.
-// The expression order is fixed: the one text the host entry (vors_fuse_depth_pixels) and the device kernel (lm_kernels.hip
+// The expression order is fixed: the one text the host entry (vors_fuse_depth_pixels) and the device kernel (product_kernels.hip
 // fuse_depth_kernel) both run, bit for bit. kf_weight is read at src only when the key is not empty.
 struct FusedPixel {
     uint16_t depth;
@@ -349,7 +349,7 @@ VORS_HD FusedPixel fuse_depth_pixel(float depth_scale, float tol_m, int max_weig
 // A point has a key iff all three q are finite and -2^20 <= q < 2^20: key = (qx + 2^20) | (qy + 2^20) << 21 | (qz + 2^20) << 42, below
 // 2^63. Everything else — NaN, infinities, a quotient out of range — is all ones (VORS_VOXEL_NONE), which is also what an empty table
 // entry holds: no point ever carries it. The comparisons are made in float BEFORE the integer conversion. The one text the host entry
-// (vors_voxel_keys) and the device kernels (lm_kernels.hip voxel_claim / voxel_owns) both run, bit for bit.
+// (vors_voxel_keys) and the device kernels (product_kernels.hip voxel_claim / voxel_owns) both run, bit for bit.
 VORS_HD uint64_t voxel_key(float voxel_m, float x, float y, float z) {
     const float q[3] = {floorf(x / voxel_m), floorf(y / voxel_m), floorf(z / voxel_m)};
     uint64_t key = 0;

@@ -174,9 +174,8 @@ void launch_render_points(const RenderCall& c, hipStream_t s) {
     RenderResolveArgs m{0, (int)plane, c.capacity, c.depth_scale, c.zkey, c.list_gray, c.depth, c.gray, c.counts, wide ? 1 : 0};
     const unsigned chunks = (unsigned)render_chunks(c.capacity);
     const unsigned blocks = (unsigned)((plane + RENDER_BLOCK * RENDER_POINTS - 1) / (RENDER_BLOCK * RENDER_POINTS));
-    for (int seq0 = 0; seq0 < c.n; seq0 += 32768) {  // (the y extent of a grid)
+    for_pair_slices(c.n, [&](int seq0, int ns) {
         a.seq0 = m.seq0 = seq0;
-        const int ns = std::min(32768, c.n - seq0);
         with_bool(c.counts != nullptr, [&](auto k) {
             constexpr bool COUNTS = decltype(k)::value;
             if (c.footprint == 1) hipLaunchKernelGGL((render_splat_kernel<1, COUNTS>), dim3(chunks, ns), dim3(RENDER_BLOCK), 0, s, a);
@@ -184,7 +183,7 @@ void launch_render_points(const RenderCall& c, hipStream_t s) {
             else hipLaunchKernelGGL((render_splat_kernel<3, COUNTS>), dim3(chunks, ns), dim3(RENDER_BLOCK), 0, s, a);
             if (resolve) hipLaunchKernelGGL(render_resolve_kernel<COUNTS>, dim3(blocks, ns), dim3(RENDER_BLOCK), 0, s, m);
         });
-    }
+    });
 }
 
 }  // namespace vors
