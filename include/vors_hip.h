@@ -181,6 +181,14 @@ vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, ui
  * created by the first call; no later call allocates. Same refusals; no enabled map: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_render_map(vors_tracker* t, int level, const float pose7[7] /* nullable */, const uint32_t range2[2] /* nullable */,
                                     int footprint, uint64_t* zkey, uint16_t* depth, uint8_t* gray, uint32_t* counts);
+/* The normals of vors_trackers_enable_map_normals (below) for the single sequence: same arguments, same refusals. Legal after
+ * vors_tracker_enable_map (and vors_tracker_enable_map_voxels, if used) and until the first vors_tracker_track (refused after it and when
+ * repeated); it computes keyframe 0's normals itself, on the tracker's stream, from the depth map the tracker holds (with the depth
+ * filter: the filter's copy of it). vors_tracker_enable_map_voxels called AFTER it is refused: that call emits keyframe 0 again. */
+vors_status vors_tracker_enable_map_normals(vors_tracker* t, int step, float jump_m);
+/* The map's normals so far to a HOST buffer normals [capacity][3]: the first min(total, capacity, the handle's capacity) entries, rank for
+ * rank those of vors_tracker_read_map; synchronises. capacity negative, normals NULL or not enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map_normals(vors_tracker* t, int capacity, float* normals);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -306,6 +314,22 @@ vors_status vors_trackers_render_map(vors_trackers* t, int level, const void* d_
                                      const void* d_ranges /* nullable */, size_t range_stride_bytes, int footprint,
                                      uint64_t* d_zkey, uint16_t* d_depth /* nullable */, uint8_t* d_gray /* nullable */,
                                      uint32_t* d_counts /* nullable */, void* hip_stream);
+/* NORMALS OF THE KEYFRAME MAP (opt-in on top of an enabled map; without this call nothing changes: no launch, no allocation, no kernel
+ * argument on any existing path). Every map entry then carries the surface normal of its pixel in its keyframe's depth plane, in the world
+ * frame: vors_points_normals (section 2d) over the ranks a keyframe's emission appended, with the stored pixels, the keyframe's pose and
+ * (step, jump_m). The depth plane is the one the keyframe stage of that call ran on: the frame's depth map, with the depth filter the
+ * fused map (what vors_trackers_keyframe_depth shows after the call), at init the init depth. The caller's plane is read only by work the
+ * call itself enqueues. The pass is keyed on the stored pixels, so the voxel filter and the keep rule need nothing; a keyframe beyond
+ * max_keyframes still gets its normals; ranks at or above capacity are never stored. Per track call two more launches: a copy of the
+ * running totals before the emission and one masked launch after it. Tracking, the map's lists and its segments keep their bits.
+ * Legal after vors_trackers_enable_map and before vors_trackers_init, once. VORS_ERR_INVALID_ARGUMENT, with nothing allocated and nothing
+ * enqueued: NULL handle, no enabled map, a map whose level is not 0 (depth planes exist at full resolution only), repeated call, call
+ * after init, step outside 1..8, jump_m negative or NaN. The call allocates, as part of vors_trackers_workspace_bytes' figure and freed
+ * with the handle, n * capacity * 12 + 4 n bytes; no later call allocates. */
+vors_status vors_trackers_enable_map_normals(vors_trackers* t, int step, float jump_m);
+/* DEVICE pointer [n][capacity][3] f32, owned by the handle and valid for its life: entry r of a sequence is the normal of the map's entry
+ * r, valid in stream order after the last init / track for r < min(total, capacity). Not enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map_normals(const vors_trackers* t, const float** d_normals);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -696,6 +720,50 @@ vors_status vors_render_points(int n, const float* d_xyz, const uint8_t* d_list_
 vors_status vors_render_points_host(const float* xyz, const uint8_t* list_gray, uint32_t count, int capacity, const uint32_t range2[2],
                                     const float cam5[5], int rows, int cols, float depth_scale, const float pose7[7], int footprint,
                                     uint64_t* zkey, uint16_t* depth, uint8_t* gray, uint32_t counts[VORS_RENDER_COUNTS]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2d. SURFACE NORMALS OF DEPTH MAPS, device-resident and handle-free (the reference has no normals): per pixel of a level-0
+ *     depth plane D (u16, rows x cols, row-major) the unit normal of the surface through its back-projected neighbours.
+ * PER PIXEL (x, y): z(d) = 1.0f / (depth_scale / (float)d) (vors_from_depth's text, then the reciprocal the point cloud takes) and
+ *   P(x', y') = back_project(K, (float)x', (float)y', z(D[y'][x'])): the centre P_c has the camera-frame bits of vors_batch_point_cloud
+ *   without a pose. No normal if (x, y) is outside the plane or D[y][x] == 0. A neighbour is usable iff it lies inside the plane, its depth
+ *   is non-zero and fabsf(z_n - z_c) <= jump_m, compared in float (NaN fails). Horizontal tangent tx from (x - step, y) and (x + step, y):
+ *   both usable P(x + step) - P(x - step); only the right one P(x + step) - P_c; only the left one P_c - P(x - step); neither: no normal.
+ *   Vertical tangent ty: the same with (x, y -/+ step). m = cross(ty, tx), l2 = (m.x m.x + m.y m.y) + m.z m.z, no normal unless
+ *   l2 > 0.0f; n = m / sqrtf(l2) (three divisions), negated if (n.x P_c.x + n.y P_c.y) + n.z P_c.z > 0.0f: the normal faces the camera
+ *   whatever the signs of the focal lengths and the skew. With a pose the normal is rotated by the pose's rotation (no translation);
+ *   without one it is untouched. "No normal" is stored as three +0.0f. The one text (lie.h depth_normal) runs on the host and on the
+ *   device: the device results equal vors_depth_normals_host's bit for bit.
+ * Counts: VORS_NORMAL_COUNTS u32 per plane / list = {considered: the pixels of the plane resp. the ranks of the clipped range; with
+ *   depth: those inside the plane whose depth is non-zero; with a normal}.
+ * vors_depth_normals (PLANE form): d_depth [n][rows * cols] u16, cam5 (HOST) = cu cv fu fv skew, d_poses7 (DEVICE, nullable): camera ->
+ *   world, 7 floats per plane, pose_stride_bytes apart (0 = 28; a multiple of 4 of at least 28). Outputs (DEVICE, each nullable, at least
+ *   one required): d_normals [n][rows * cols][3] f32, every pixel written; d_counts [n][VORS_NORMAL_COUNTS].
+ * vors_points_normals (LIST form): the normals of listed pixels of the planes: d_pixel [n][capacity] u32 = x | y << 16 and d_list_counts
+ *   [n] u32 (a count above capacity is clipped to it) are the pointers of vors_batch_point_cloud and vors_trackers_map; d_ranges /
+ *   range_stride_bytes and d_poses7 / pose_stride_bytes as in vors_render_points. Outputs: d_normals [n][capacity][3] — exactly the ranks
+ *   of the clipped range are written, everything else is left untouched — and d_counts. A listed pixel outside the plane has no normal.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued and nothing written: n < 1; a NULL d_depth or cam5 (list form: d_pixel,
+ *   d_list_counts); both outputs NULL; step outside 1..8; jump_m negative or NaN; depth_scale not > 0; rows or cols < 1 (list form:
+ *   capacity < 1); rows or cols > 65535 or rows * cols > 2^28; a bad stride; a pointer off its natural alignment (d_depth: 2 bytes, the
+ *   others: 4). Enqueued on hip_stream on the calling thread's current device, NOT synchronised, no allocation ever: a memset of the
+ *   counters when they are asked for and one kernel; no workgroup waits for another. */
+#define VORS_NORMAL_COUNTS 3
+vors_status vors_depth_normals(int n, const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, int step,
+                               float jump_m, const void* d_poses7 /* nullable */, size_t pose_stride_bytes,
+                               float* d_normals /* nullable */, uint32_t* d_counts /* nullable */, void* hip_stream);
+vors_status vors_points_normals(int n, const uint16_t* d_depth, const uint32_t* d_pixel, const uint32_t* d_list_counts, int capacity,
+                                const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                                const float cam5[5], int rows, int cols, float depth_scale, int step, float jump_m,
+                                const void* d_poses7 /* nullable */, size_t pose_stride_bytes,
+                                float* d_normals /* nullable */, uint32_t* d_counts /* nullable */, void* hip_stream);
+/* The same rule for ONE plane — or, with pixel non-NULL, ONE list — on the host (host arithmetic, needs no GPU; the text the kernels run):
+ * HOST pointers. Plane form (pixel NULL; count, capacity and range2 are not read): normals [rows * cols][3]. List form: pixel [capacity],
+ * count = the list's count (clipped to capacity), range2 (nullable) = (first, count), normals [capacity][3], only the ranks of the clipped
+ * range written. pose7 (nullable) = camera -> world. The refusals above, with nothing written. */
+vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale, int step, float jump_m,
+                                    const float pose7[7], const uint32_t* pixel, uint32_t count, int capacity, const uint32_t range2[2],
+                                    float* normals, uint32_t counts[VORS_NORMAL_COUNTS]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

@@ -479,6 +479,40 @@ inline int render_chunks(int capacity) {
 // Fill of the key plane, splat, resolve: enqueued on s in this order, not synchronised, no workspace.
 void launch_render_points(const RenderCall& call, hipStream_t s);
 
+// Surface normals of level-0 depth planes (vors_depth_normals, vors_points_normals, the keyframe map's normals; normal_kernels.hip): per
+// pixel lie.h depth_normal. Handle-free: everything the kernels read is here. The plane form writes every pixel of every plane; the list
+// form writes exactly the ranks of each list's clipped range. Each output is nullable (the entries ask for at least one).
+struct NormalCall {
+    int n;                       // planes / lists
+    const uint16_t* depth;       // [n][rows * cols]
+    Intr k;
+    int rows, cols;
+    float depth_scale;
+    int step;                    // 1..8
+    float jump_m;
+    const float* poses;          // camera -> world, nullable = the normal stays in the camera frame; only the rotation is applied
+    int pose_stride;             // floats
+    float* normals;              // plane form [n][rows * cols][3], list form [n][capacity][3]
+    uint32_t* counts;            // [n][VORS_NORMAL_COUNTS]
+    // list form only
+    const uint32_t* pixel;       // [n][capacity] x | y << 16
+    const uint32_t* list_counts; // [n]; a count above capacity is clipped to it
+    int capacity;
+    const uint8_t* ranges;       // nullable = the whole list; (first, count) u32 pairs, range_stride BYTES apart, clipped to the written prefix
+    int range_stride;
+    const uint32_t* first;       // nullable; [n] first rank of the range, which then runs to the end of the written prefix (the keyframe map)
+    const int* sel_list;         // masked launch (Geom::sel_list): list k of the grid is sel_list[k] for k < *sel_count, nothing beyond
+    const int* sel_count;
+};
+#define NORMAL_BLOCK 256
+#define NORMAL_POINTS 4  // pixels per thread of the plane kernel
+// The plane form: a memset of the counters when they are asked for, then one kernel; enqueued on s, not synchronised, no workspace.
+void launch_depth_normals(const NormalCall& call, hipStream_t s);
+// The list form, the same; with sel_list a masked launch whose grid spans all n lists.
+void launch_points_normals(const NormalCall& call, hipStream_t s);
+// dst[i] = src[i] for the n running totals of the keyframe map (the ranks an emission starts from), honouring nothing: every sequence.
+void launch_normals_snapshot(const uint32_t* src, uint32_t* dst, int n, hipStream_t s);
+
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }

@@ -479,6 +479,63 @@ VORS_HD RenderedPixel render_resolve(float depth_scale, uint64_t key, const uint
     return RenderedPixel{to_depth(depth_scale, 1.0f / zp), list_gray[(uint32_t)key], true};
 }
 
+// Surface normal of one pixel of a level-0 depth plane: central differences of back-projected neighbours `step` pixels
+// away, one-sided where a neighbour is missing. z(d) = 1.0f / (depth_scale / (float)d) — vors_from_depth's text, then the reciprocal the
+// point cloud takes — and P(x', y') = back_project(K, (float)x', (float)y', z): the centre P_c has the camera-frame bits of
+// vors_batch_point_cloud. A neighbour is usable iff it lies inside the plane, its depth is non-zero and fabsf(z_n - z_c) <= jump_m (in
+// float; NaN fails). tx from (x -/+ step, y): both usable P(x + step) - P(x - step), only the right one P(x + step) - P_c, only the left
+// one P_c - P(x - step), neither: no normal; ty the same with (x, y -/+ step). m = cross(ty, tx), l2 = (m.x m.x + m.y m.y) + m.z m.z, no
+// normal unless l2 > 0; n = m / sqrtf(l2), three divisions; negated if (n.x P_c.x + n.y P_c.y) + n.z P_c.z > 0, so that it faces the
+// camera whatever the signs of the focal lengths; with a pose quat_rotate(pose.q, n), no translation, without one n untouched. "No
+// normal" is three +0.0f. The taps: depth_normal_taps gives the five flat offsets of a pixel INSIDE the plane, a tap outside the plane
+// aliasing the centre (a safe address; its value is ignored), so that a kernel issues every load before the first use. The expression
+// order is fixed: the one text the host entry (vors_depth_normals_host) and the device kernels (normal_kernels.hip) both run, bit for bit.
+struct NormalTaps {
+    int c, l, r, u, d;
+};
+VORS_HD NormalTaps depth_normal_taps(int x, int y, int cols, int rows, int step) {
+    const int c = y * cols + x;
+    return NormalTaps{c, x - step >= 0 ? c - step : c, x + step < cols ? c + step : c, y - step >= 0 ? c - step * cols : c,
+                      y + step < rows ? c + step * cols : c};
+}
+struct DepthNormal {
+    V3 n;
+    bool has_depth, has_normal;
+};
+VORS_HD float depth_normal_z(float depth_scale, uint16_t d) { return 1.0f / (depth_scale / (float)d); }
+// One tangent: `lo` / `hi` are the neighbours at -step / +step along the axis (dx, dy), in_lo / in_hi whether they lie inside the plane.
+VORS_HD bool depth_normal_tangent(const Intr& k, float depth_scale, float jump_m, int x, int y, int dx, int dy, const V3& pc, bool in_lo,
+                                  uint16_t lo, bool in_hi, uint16_t hi, V3* t) {
+    const float z_lo = depth_normal_z(depth_scale, lo), z_hi = depth_normal_z(depth_scale, hi);
+    const bool use_lo = in_lo && lo != 0 && fabsf(z_lo - pc.z) <= jump_m, use_hi = in_hi && hi != 0 && fabsf(z_hi - pc.z) <= jump_m;
+    if (!use_lo && !use_hi) return false;
+    const V3 a = use_lo ? back_project(k, (float)(x - dx), (float)(y - dy), z_lo) : pc;
+    const V3 b = use_hi ? back_project(k, (float)(x + dx), (float)(y + dy), z_hi) : pc;
+    *t = V3{b.x - a.x, b.y - a.y, b.z - a.z};
+    return true;
+}
+VORS_HD DepthNormal depth_normal(const Intr& k, float depth_scale, int step, float jump_m, int x, int y, int cols, int rows, uint16_t dc,
+                                 uint16_t dl, uint16_t dr, uint16_t du, uint16_t dd, bool has_pose, const Iso& pose) {
+    DepthNormal o{V3{0.0f, 0.0f, 0.0f}, false, false};
+    if (x < 0 || x >= cols || y < 0 || y >= rows || dc == 0) return o;
+    o.has_depth = true;
+    const V3 pc = back_project(k, (float)x, (float)y, depth_normal_z(depth_scale, dc));
+    V3 tx, ty;
+    if (!depth_normal_tangent(k, depth_scale, jump_m, x, y, step, 0, pc, x - step >= 0, dl, x + step < cols, dr, &tx)) return o;
+    if (!depth_normal_tangent(k, depth_scale, jump_m, x, y, 0, step, pc, y - step >= 0, du, y + step < rows, dd, &ty)) return o;
+    const float mx = ty.y * tx.z - ty.z * tx.y;
+    const float my = ty.z * tx.x - ty.x * tx.z;
+    const float mz = ty.x * tx.y - ty.y * tx.x;
+    const float l2 = (mx * mx + my * my) + mz * mz;
+    if (!(l2 > 0.0f)) return o;
+    const float l = sqrtf(l2);
+    V3 n{mx / l, my / l, mz / l};
+    if ((n.x * pc.x + n.y * pc.y) + n.z * pc.z > 0.0f) n = V3{-n.x, -n.y, -n.z};
+    o.n = has_pose ? quat_rotate(pose.q, n) : n;
+    o.has_normal = true;
+    return o;
+}
+
 // Jacobian of the warp: src/core/track/inverse_compositional.rs:313-341.
 VORS_HD void warp_jacobian_at(float gu, float gv, float u, float v, float _z, const Intr& k, float J[6]) {
     const float a = u - k.cu;

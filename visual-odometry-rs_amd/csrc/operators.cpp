@@ -311,6 +311,139 @@ vors_status vors_render_points_host(const float* xyz, const uint8_t* list_gray, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Surface normals of depth planes (vors_depth_normals, vors_points_normals, vors_depth_normals_host): the refusals all three share, the
+// device entries (normal_kernels.hip) and the host entry, which runs the kernels' own text (lie.h depth_normal_taps, depth_normal).
+// ---------------------------------------------------------------------------------------------------------------
+static vors_status normal_refusals(const char* who, const void* depth, const float* cam5, int rows, int cols, float depth_scale, int step,
+                                   float jump_m, bool list, const void* pixel, int capacity, const void* normals, const void* counts) {
+    const std::string w(who);
+    if (!depth) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth is NULL");
+    if (!cam5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cam5 is NULL");
+    if (list && !pixel) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (pixel) is NULL");
+    if (!normals && !counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": normals and counts are both NULL (at least one output is required)");
+    if (step < 1 || step > 8) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": step must be in 1..8");
+    if (!(jump_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": jump_m must be >= 0 (and not NaN)");
+    if (!(depth_scale > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth_scale must be > 0");
+    if (rows < 1 || cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must be >= 1");
+    if (list && capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
+    if (rows > 65535 || cols > 65535 || (long long)rows * cols > (1ll << 28))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows / cols must not exceed 65535 and rows * cols must not exceed 2^28 pixels");
+    if ((uintptr_t)depth % 2 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth must be 2-byte aligned");
+    if ((uintptr_t)pixel % 4 != 0 || (uintptr_t)normals % 4 != 0 || (uintptr_t)counts % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": pixel, normals and counts must be 4-byte aligned");
+    return VORS_OK;
+}
+static vors_status normal_stride_refusals(const char* who, const void* d_poses7, size_t pose_stride_bytes, const void* d_ranges,
+                                          size_t range_stride_bytes) {
+    const std::string w(who);
+    if (pose_stride_bytes != 0 && (pose_stride_bytes < 28 || pose_stride_bytes % 4 != 0 || pose_stride_bytes > 0x7fffffffu))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": pose_stride_bytes must be 0 or a multiple of 4 of at least 28");
+    if (range_stride_bytes != 0 && (range_stride_bytes < 8 || range_stride_bytes % 4 != 0 || range_stride_bytes > 0x7fffffffu))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": range_stride_bytes must be 0 or a multiple of 4 of at least 8");
+    if ((uintptr_t)d_ranges % 4 != 0 || (uintptr_t)d_poses7 % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_ranges and d_poses7 must be 4-byte aligned");
+    return VORS_OK;
+}
+static NormalCall normal_call(int n, const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, int step, float jump_m,
+                              const void* d_poses7, size_t pose_stride_bytes, float* d_normals, uint32_t* d_counts) {
+    NormalCall call{};
+    call.n = n;
+    call.depth = d_depth;
+    call.k = Intr{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    call.rows = rows;
+    call.cols = cols;
+    call.depth_scale = depth_scale;
+    call.step = step;
+    call.jump_m = jump_m;
+    call.poses = static_cast<const float*>(d_poses7);
+    call.pose_stride = pose_stride_bytes ? (int)(pose_stride_bytes / 4) : 7;
+    call.normals = d_normals;
+    call.counts = d_counts;
+    return call;
+}
+
+vors_status vors_depth_normals(int n, const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, int step,
+                               float jump_m, const void* d_poses7, size_t pose_stride_bytes, float* d_normals, uint32_t* d_counts,
+                               void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "depth_normals: n must be >= 1");
+    vors_status st = normal_refusals("depth_normals", d_depth, cam5, rows, cols, depth_scale, step, jump_m, false, nullptr, 0, d_normals, d_counts);
+    if (st != VORS_OK) return st;
+    if ((st = normal_stride_refusals("depth_normals", d_poses7, pose_stride_bytes, nullptr, 0)) != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    launch_depth_normals(normal_call(n, d_depth, cam5, rows, cols, depth_scale, step, jump_m, d_poses7, pose_stride_bytes, d_normals, d_counts),
+                         static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_points_normals(int n, const uint16_t* d_depth, const uint32_t* d_pixel, const uint32_t* d_list_counts, int capacity,
+                                const void* d_ranges, size_t range_stride_bytes, const float cam5[5], int rows, int cols, float depth_scale,
+                                int step, float jump_m, const void* d_poses7, size_t pose_stride_bytes, float* d_normals, uint32_t* d_counts,
+                                void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "points_normals: n must be >= 1");
+    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "points_normals: a list (d_list_counts) is NULL");
+    if ((uintptr_t)d_list_counts % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "points_normals: d_list_counts must be 4-byte aligned");
+    vors_status st =
+        normal_refusals("points_normals", d_depth, cam5, rows, cols, depth_scale, step, jump_m, true, d_pixel, capacity, d_normals, d_counts);
+    if (st != VORS_OK) return st;
+    if ((st = normal_stride_refusals("points_normals", d_poses7, pose_stride_bytes, d_ranges, range_stride_bytes)) != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    NormalCall call = normal_call(n, d_depth, cam5, rows, cols, depth_scale, step, jump_m, d_poses7, pose_stride_bytes, d_normals, d_counts);
+    call.pixel = d_pixel;
+    call.list_counts = d_list_counts;
+    call.capacity = capacity;
+    call.ranges = static_cast<const uint8_t*>(d_ranges);
+    call.range_stride = range_stride_bytes ? (int)range_stride_bytes : 8;
+    launch_points_normals(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale, int step, float jump_m,
+                                    const float pose7[7], const uint32_t* pixel, uint32_t count, int capacity, const uint32_t range2[2],
+                                    float* normals, uint32_t counts[VORS_NORMAL_COUNTS]) {
+    const bool list = pixel != nullptr;
+    vors_status st =
+        normal_refusals("depth_normals_host", depth, cam5, rows, cols, depth_scale, step, jump_m, list, pixel, capacity, normals, counts);
+    if (st != VORS_OK) return st;
+    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    Iso pose = iso_identity();
+    if (pose7) pose = iso_load(pose7);
+    uint32_t c[VORS_NORMAL_COUNTS] = {0, 0, 0};
+    // one pixel, written at `slot` (the text of the kernels: the taps of a pixel inside the plane, then depth_normal)
+    auto one = [&](int x, int y, size_t slot) {
+        const bool inside = x < cols && y < rows;
+        const NormalTaps t = inside ? depth_normal_taps(x, y, cols, rows, step) : NormalTaps{0, 0, 0, 0, 0};
+        const DepthNormal o = depth_normal(k, depth_scale, step, jump_m, x, y, cols, rows, depth[t.c], depth[t.l], depth[t.r], depth[t.u], depth[t.d],
+                                           pose7 != nullptr, pose);
+        c[0] += 1;
+        c[1] += o.has_depth ? 1 : 0;
+        c[2] += o.has_normal ? 1 : 0;
+        if (normals) {
+            normals[3 * slot] = o.n.x;
+            normals[3 * slot + 1] = o.n.y;
+            normals[3 * slot + 2] = o.n.z;
+        }
+    };
+    if (!list) {
+        for (int y = 0; y < rows; ++y)
+            for (int x = 0; x < cols; ++x) one(x, y, (size_t)y * (size_t)cols + (size_t)x);
+    } else {
+        // the range of ranks, clipped to the written prefix (the text of points_normals_kernel)
+        const uint32_t n = count < (uint32_t)capacity ? count : (uint32_t)capacity;
+        uint32_t first = 0, last = n;
+        if (range2) {
+            first = range2[0] < n ? range2[0] : n;
+            last = range2[1] > n - first ? n : first + range2[1];
+        }
+        for (uint32_t rank = first; rank < last; ++rank) one((int)(pixel[rank] & 0xffffu), (int)(pixel[rank] >> 16), rank);
+    }
+    if (counts)
+        for (int i = 0; i < VORS_NORMAL_COUNTS; ++i) counts[i] = c[i];
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------
 void vors_se3_exp(const float xi[6], float out_iso7[7]) { iso_store(se3_exp(xi), out_iso7); }

@@ -59,6 +59,16 @@ struct vors_trackers {
             unsigned long long* table = nullptr;
             uint32_t *occupied = nullptr, *overflow = nullptr;
         } voxels;
+        // Normals of the map (vors_trackers_enable_map_normals; off: nothing below exists and no launch changes):
+        //   n      [n_seq][capacity][3] the normal of every stored entry, rank for rank
+        //   first  [n_seq] the running totals as they stood before the emission in flight: the ranks its normals pass starts from
+        struct Normals {
+            bool on = false;
+            int step = 0;
+            float jump_m = 0.f;
+            float* n = nullptr;
+            uint32_t* first = nullptr;
+        } normals;
     } map;
     const uint16_t* keyframe_depth() const {
         return batch->g.mode == VORS_CANDIDATES_DENSE ? static_cast<const uint16_t*>(own_depth.p) : filter.fused;
@@ -97,6 +107,42 @@ static void trackers_map_emit(vors_trackers* t, const Geom& gm, hipStream_t s) {
     const vors_trackers::Map::Voxels& v = t->map.voxels;
     if (v.on) call.voxels = PointCloudVoxelArgs{v.voxel_m, (uint32_t)v.table_slots, v.table, v.occupied, v.overflow};
     launch_lm_point_cloud_append(gm, call, s);
+}
+
+// The normals of the entries an emission appended (vors_trackers_enable_map_normals): the list form of the normals pass over the ranks
+// [first[seq], min(counts[seq], capacity)) of the selected sequences (gm.sel_list; null: all), keyed on the stored pixels, in `depth`, the
+// [n_seq][S0] planes the keyframe stage of this call ran on. Hazards: it reads map.pixel / map.counts behind the emission that wrote them
+// and the keyframe pose behind launch_trackers_advance; `depth` is the handle's own plane or the caller's frame, which this call may read
+// in work it enqueues; it writes map.normals.n, which nothing else touches.
+static void trackers_map_normals_pass(vors_trackers* t, const Geom& gm, const uint16_t* depth, hipStream_t s) {
+    const Geom& g = t->batch->g;
+    NormalCall call{};
+    call.n = t->n_seq;
+    call.depth = depth;
+    call.k = g.lv[0].k;
+    call.rows = g.lv[0].rows;
+    call.cols = g.lv[0].cols;
+    call.depth_scale = g.depth_scale;
+    call.step = t->map.normals.step;
+    call.jump_m = t->map.normals.jump_m;
+    call.poses = t->kf_poses.as<float>();
+    call.pose_stride = 7;
+    call.normals = t->map.normals.n;
+    call.pixel = t->map.pixel;
+    call.list_counts = t->map.counts;
+    call.capacity = t->map.capacity;
+    call.first = t->map.normals.first;
+    call.sel_list = gm.sel_list;
+    call.sel_count = gm.sel_count;
+    launch_points_normals(call, s);
+}
+// The emission with what surrounds it when the map carries normals: the running totals are copied first, the normals pass follows.
+// `depth` is read only then.
+static void trackers_map_emit_all(vors_trackers* t, const Geom& gm, const uint16_t* depth, hipStream_t s) {
+    const vors_trackers::Map::Normals& nm = t->map.normals;
+    if (nm.on) launch_normals_snapshot(t->map.counts, nm.first, t->n_seq, s);
+    trackers_map_emit(t, gm, s);
+    if (nm.on) trackers_map_normals_pass(t, gm, depth, s);
 }
 
 // The two halves of vors_trackers_track: Tracker::track up to the keyframe test, and the promotion of the sequences that switch — the
@@ -174,7 +220,7 @@ static vors_status trackers_promote(vors_trackers* t, const uint8_t* d_gray, con
         if (b->g.mode == VORS_CANDIDATES_DENSE)
             launch_ref_dense_planes_keyframe(gm, Pyramid{t->own_gray.as<uint8_t>(), b->kf_upper}, t->own_depth.as<uint16_t>(), b->rec, n, s);
     }
-    if (t->map.on) trackers_map_emit(t, gm, s);
+    if (t->map.on) trackers_map_emit_all(t, gm, b->g.mode == VORS_CANDIDATES_DENSE ? t->own_depth.as<uint16_t>() : d_depth, s);
     STAGE_END(b, 1, s);
     HIP_TRY(hipGetLastError());
     return VORS_OK;
@@ -351,8 +397,35 @@ static vors_status trackers_map_voxels_enable(vors_trackers* t, bool started, co
     v.on = true;
     return VORS_OK;
 }
-// An empty map (and an empty voxel table), then keyframe 0 of every sequence.
-static vors_status trackers_map_init(vors_trackers* t, hipStream_t s) {
+// The normals' switch: every refusal, then both buffers at once. `started` / `before`: as for the voxel filter.
+static vors_status trackers_map_normals_enable(vors_trackers* t, bool started, const char* before, int step, float jump_m) {
+    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: needs an enabled keyframe map first (vors_trackers_enable_map)");
+    if (t->map.level != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: needs a map of level 0 (depth planes exist at full resolution only)");
+    if (t->map.normals.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: the normals are already enabled");
+    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, std::string("enable_map_normals: legal only before ") + before);
+    if (step < 1 || step > 8) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: step must be in 1..8");
+    if (!(jump_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: jump_m must be >= 0 (and not NaN)");
+    vors_batch* b = t->batch;
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)t->n_seq;
+    vors_trackers::Map::Normals& nm = t->map.normals;
+    b->own.alloc(&nm.n, n * (size_t)t->map.capacity * 3);
+    b->own.alloc(&nm.first, n);
+    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the normals stay off)
+        const hipError_t e = b->own.err;
+        b->own.err = hipSuccess;
+        (void)hipGetLastError();
+        return fail(VORS_ERR_HIP, std::string("hipMalloc (normals of the keyframe map): ") + hipGetErrorString(e));
+    }
+    nm.step = step;
+    nm.jump_m = jump_m;
+    nm.on = true;
+    return VORS_OK;
+}
+// An empty map (and an empty voxel table), then keyframe 0 of every sequence. `depth`: the planes keyframe 0 was made from, read only
+// when the map carries normals.
+static vors_status trackers_map_init(vors_trackers* t, const uint16_t* depth, hipStream_t s) {
     const size_t n = (size_t)t->n_seq;
     HIP_TRY(hipMemsetAsync(t->map.counts, 0, n * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(t->map.n_segments, 0, n * sizeof(uint32_t), s));
@@ -361,7 +434,7 @@ static vors_status trackers_map_init(vors_trackers* t, hipStream_t s) {
         HIP_TRY(hipMemsetAsync(v.occupied, 0, n * sizeof(uint32_t), s));
         HIP_TRY(hipMemsetAsync(v.overflow, 0, n * sizeof(uint32_t), s));
     }
-    trackers_map_emit(t, t->batch->g, s);  // (unmasked: the handle's geometry carries no selection)
+    trackers_map_emit_all(t, t->batch->g, depth, s);  // (unmasked: the handle's geometry carries no selection)
     HIP_TRY(hipGetLastError());
     return VORS_OK;
 }
@@ -394,7 +467,55 @@ vors_status vors_tracker_enable_map(vors_tracker* t, int level, int capacity, in
     if (st != VORS_OK) return st;
     DeviceGuard guard(t->device);
     // keyframe 0 exists since create: its records, the handle's copies (dense mode) and the identity pose are what init left on s_main
-    return trackers_map_init(t->seq, t->s_main);
+    return trackers_map_init(t->seq, nullptr, t->s_main);  // (no normals yet: they are enabled after the map)
+}
+
+vors_status vors_trackers_enable_map_normals(vors_trackers* t, int step, float jump_m) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: the handle t is NULL");
+    return trackers_map_normals_enable(t, t->initialised, "vors_trackers_init (keyframe 0 would have no normals)", step, jump_m);
+}
+
+vors_status vors_trackers_map_normals(const vors_trackers* t, const float** d_normals) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_normals: the handle t is NULL");
+    if (!t->map.normals.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_normals: the normals of the map are not enabled (vors_trackers_enable_map_normals)");
+    if (d_normals) *d_normals = t->map.normals.n;
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map_normals(vors_tracker* t, int step, float jump_m) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: the handle t is NULL");
+    vors_trackers* q = t->seq;
+    vors_status st = trackers_map_normals_enable(q, t->has_last, "the first vors_tracker_track", step, jump_m);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    // Keyframe 0 is in the map already: its normals are the pass over every rank so far, in the plane keyframe 0 was made from — the
+    // handle's copy (dense mode), the filter's copy, or t->depth, which still holds the first frame's depth map (the next upload waits for
+    // ev_frame_done, which therefore moves behind this reader, as in vors_tracker_enable_depth_filter)
+    const uint16_t* depth = q->batch->g.mode == VORS_CANDIDATES_DENSE ? q->own_depth.as<uint16_t>()
+                            : q->filter.on                            ? q->filter.fused
+                                                                      : t->depth.as<uint16_t>();
+    HIP_TRY(hipMemsetAsync(q->map.normals.first, 0, sizeof(uint32_t), t->s_main));
+    trackers_map_normals_pass(q, q->batch->g, depth, t->s_main);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t->ev_frame_done, t->s_main));
+    return VORS_OK;
+}
+
+vors_status vors_tracker_read_map_normals(vors_tracker* t, int capacity, float* normals) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_normals: the handle t is NULL");
+    const vors_trackers::Map& m = t->seq->map;
+    if (!m.normals.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_normals: the normals of the map are not enabled (vors_tracker_enable_map_normals)");
+    if (capacity < 0 || !normals) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_normals: negative capacity or NULL normals");
+    DeviceGuard guard(t->device);
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, m.counts, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    const size_t np = std::min<size_t>(std::min<uint32_t>(total, (uint32_t)m.capacity), (size_t)capacity);
+    if (np) HIP_TRY(hipMemcpyAsync(normals, m.normals.n, np * 3 * sizeof(float), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    return VORS_OK;
 }
 
 vors_status vors_trackers_enable_map_voxels(vors_trackers* t, float voxel_m, int table_slots) {
@@ -413,11 +534,13 @@ vors_status vors_trackers_map_voxels(const vors_trackers* t, const uint32_t** d_
 
 vors_status vors_tracker_enable_map_voxels(vors_tracker* t, float voxel_m, int table_slots) {
     if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: the handle t is NULL");
+    if (t->seq->map.normals.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxels: legal only before vors_tracker_enable_map_normals (keyframe 0 is emitted again)");
     vors_status st = trackers_map_voxels_enable(t->seq, t->has_last, "the first vors_tracker_track", voxel_m, table_slots);
     if (st != VORS_OK) return st;
     DeviceGuard guard(t->device);
     // vors_tracker_enable_map has emitted keyframe 0 unfiltered: the map is emptied and keyframe 0 emitted again, through the filter
-    return trackers_map_init(t->seq, t->s_main);
+    return trackers_map_init(t->seq, nullptr, t->s_main);  // (no normals yet: see the refusal above)
 }
 
 vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, uint32_t* overflow) {
@@ -629,7 +752,7 @@ vors_status vors_trackers_init(vors_trackers* t, const uint8_t* d_gray, const ui
     HIP_TRY(hipMemsetAsync(t->frame_counter.p, 0, sizeof(int), s));
     HIP_TRY(hipGetLastError());
     if (t->filter.on && (st = trackers_filter_init(t, d_depth, s)) != VORS_OK) return st;
-    if (t->map.on && (st = trackers_map_init(t, s)) != VORS_OK) return st;
+    if (t->map.on && (st = trackers_map_init(t, kf_depth, s)) != VORS_OK) return st;
     t->frame_index = 0;
     t->initialised = true;
     return VORS_OK;

@@ -1,7 +1,8 @@
 // Binary little-endian PLY writer for the keyframe map of a sequence (vors_tracker_read_map): one vertex per point — x y z float32,
 // intensity uchar, 13 bytes — and one comment line per keyframe segment: frame, first, count and the camera -> world pose the points
 // were carried through. Header-only, no dependency beyond the standard library; the payload is assembled byte by byte, so the file is
-// little-endian on every host.
+// little-endian on every host. With normals (the overload below; vors_tracker_read_map_normals) a vertex is x y z nx ny nz float32,
+// intensity uchar, 25 bytes.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -18,6 +19,7 @@ namespace vors {
 namespace ply_io {
 
 constexpr size_t VERTEX_BYTES = 13;
+constexpr size_t VERTEX_NORMAL_BYTES = 25;
 
 inline void put_f32_le(float v, unsigned char* out) {
     std::uint32_t u;
@@ -26,7 +28,7 @@ inline void put_f32_le(float v, unsigned char* out) {
 }
 
 // The header: `n_points` vertices, one "comment segment ..." line per record (%.9g round-trips a float32).
-inline std::string header(size_t n_points, const vors_map_segment* segments, size_t n_segments) {
+inline std::string header(size_t n_points, const vors_map_segment* segments, size_t n_segments, bool with_normals = false) {
     std::string h = "ply\nformat binary_little_endian 1.0\ncomment vors keyframe map: one segment line per keyframe (frame first count tx ty tz qx qy qz qw)\n";
     char line[256];
     for (size_t k = 0; k < n_segments; ++k) {
@@ -35,7 +37,8 @@ inline std::string header(size_t n_points, const vors_map_segment* segments, siz
                       (unsigned)s.count, s.pose7[0], s.pose7[1], s.pose7[2], s.pose7[3], s.pose7[4], s.pose7[5], s.pose7[6]);
         h += line;
     }
-    h += "element vertex " + std::to_string(n_points) + "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar intensity\nend_header\n";
+    h += "element vertex " + std::to_string(n_points) + "\nproperty float x\nproperty float y\nproperty float z\n" +
+         (with_normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "") + "property uchar intensity\nend_header\n";
     return h;
 }
 
@@ -57,6 +60,30 @@ inline void write_map(const std::string& path, const float* xyz, const std::uint
             o[12] = gray[p0 + i];
         }
         f.write(reinterpret_cast<const char*>(buf.data()), (std::streamsize)(n * VERTEX_BYTES));
+    }
+    f.flush();
+    if (!f.good()) throw std::runtime_error("error while writing " + path);
+}
+
+// The same with one normal per point: normals [n_points][3] (three zeros = the point has none), written after x y z.
+inline void write_map(const std::string& path, const float* xyz, const float* normals, const std::uint8_t* gray, size_t n_points,
+                      const vors_map_segment* segments, size_t n_segments) {
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    if (!f.good()) throw std::runtime_error("cannot open " + path + " for writing");
+    const std::string h = header(n_points, segments, n_segments, true);
+    f.write(h.data(), (std::streamsize)h.size());
+    std::vector<unsigned char> buf;
+    const size_t block = 65536;  // points per write
+    buf.resize(std::min(n_points, block) * VERTEX_NORMAL_BYTES);
+    for (size_t p0 = 0; p0 < n_points; p0 += block) {
+        const size_t n = std::min(block, n_points - p0);
+        for (size_t i = 0; i < n; ++i) {
+            unsigned char* o = buf.data() + i * VERTEX_NORMAL_BYTES;
+            for (int c = 0; c < 3; ++c) put_f32_le(xyz[3 * (p0 + i) + c], o + 4 * c);
+            for (int c = 0; c < 3; ++c) put_f32_le(normals[3 * (p0 + i) + c], o + 12 + 4 * c);
+            o[24] = gray[p0 + i];
+        }
+        f.write(reinterpret_cast<const char*>(buf.data()), (std::streamsize)(n * VERTEX_NORMAL_BYTES));
     }
     f.flush();
     if (!f.good()) throw std::runtime_error("error while writing " + path);

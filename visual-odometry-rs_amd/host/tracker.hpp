@@ -183,6 +183,21 @@ class Tracker {  // inverse_compositional.rs:31-34
         check(vors_tracker_read_map_voxels(h_, &v.occupied, &v.overflow));
         return v;
     }
+    // Extension: a surface normal per map entry (vors_tracker_enable_map_normals): central differences `step` pixels wide in the
+    // keyframe's depth plane, neighbours further than jump_m metres in depth left out. After enable_map (level 0) and enable_map_voxels,
+    // before the first track().
+    void enable_map_normals(int step, Float jump_m) { check(vors_tracker_enable_map_normals(h_, step, jump_m)); }
+    // The normals of read_map(capacity)'s points, rank for rank: [points][3], three zeros = none (vors_tracker_read_map_normals;
+    // synchronises).
+    std::vector<Float> read_map_normals(int capacity = 0x7fffffff) {
+        std::uint32_t count = 0, n_segments = 0;
+        check(vors_tracker_read_map(h_, 0, nullptr, nullptr, nullptr, &count, 0, nullptr, &n_segments));
+        const size_t np = std::min<size_t>(count, (size_t)std::max(std::min(capacity, map_capacity_), 0));
+        std::vector<Float> normals(3 * np + 3);  // (never empty: the entry refuses a NULL buffer)
+        check(vors_tracker_read_map_normals(h_, (int)np, normals.data()));
+        normals.resize(3 * np);
+        return normals;
+    }
     // Extension: the map seen from a pose (vors_tracker_render_map; synchronises): a z-buffered depth map and grey image in the geometry
     // of pyramid level `level`, row-major, the arguments of Config::init. pose = nullptr: the current frame's pose; range2 = nullptr: the
     // whole map, else (first, count) of the ranks to render (a vors_map_segment's `first`); footprint: 1, 2 or 3 pixels wide.

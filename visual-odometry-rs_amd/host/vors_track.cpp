@@ -13,6 +13,9 @@
 // (vors_tracker_enable_map_voxels). TABLE_SLOTS, a power of two, defaults to 8 Mi entries — twice the default capacity, so the table is at
 // most half full when the list is — and costs 16 x TABLE_SLOTS bytes of device memory (128 MiB at the default). Malformed, or without
 // --map: the usage and status 2, before any device is touched. A sequence with more voxels than entries gets a warning after the last frame.
+// `--map-normals STEP[,JUMP_M]` (needs --map with LEVEL 0) gives every point of that map the surface normal of its pixel in its keyframe's
+// depth map (vors_tracker_enable_map_normals; JUMP_M defaults to 0.05 m) and the PLY the properties nx ny nz. Malformed, without --map or
+// with another LEVEL: the usage and status 2, before any device is touched.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -97,8 +100,27 @@ static bool parse_map_voxel(const std::string& val, float& voxel_m, int& table_s
 
 static const int MAP_VOXEL_DEFAULT_TABLE_SLOTS = 8 << 20;  // 16 bytes each: 128 MiB
 
+// "STEP[,JUMP_M]": a whole number, then a number, nothing after the last. The VALUES are judged by the library.
+static bool parse_map_normals(const std::string& val, int& step, float& jump_m) {
+    if (val.empty()) return false;
+    const char* p = val.c_str();
+    char* end = nullptr;
+    const long v = std::strtol(p, &end, 10);
+    if (end == p || v < -0x7fffffffL || v > 0x7fffffffL) return false;
+    step = (int)v;
+    if (*end == ',') {
+        p = end + 1;
+        jump_m = std::strtof(p, &end);
+        if (end == p) return false;
+    }
+    return *end == '\0';
+}
+
 int main(int argc, char** argv) {
     bool quiet = false, depth_filter = false, map = false, bad_map = false, map_voxel = false, bad_map_voxel = false;
+    bool map_normals = false, bad_map_normals = false;
+    int normals_step = 1;
+    float normals_jump_m = 0.05f;
     float voxel_m = 0.0f;
     int voxel_table_slots = MAP_VOXEL_DEFAULT_TABLE_SLOTS;
     std::string map_file;
@@ -128,6 +150,10 @@ int main(int argc, char** argv) {
             map_voxel = parse_map_voxel(val, voxel_m, voxel_table_slots);
             bad_map_voxel = !map_voxel;
             ++a;
+        } else if (flag == "--map-normals") {
+            map_normals = parse_map_normals(val, normals_step, normals_jump_m);
+            bad_map_normals = !map_normals;
+            ++a;
         } else {
             bad_flag = true;
         }
@@ -141,6 +167,13 @@ int main(int argc, char** argv) {
     if (bad_map_voxel || (map_voxel && !map)) {
         std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
                      bad_map_voxel ? "Malformed --map-voxel: expected SIZE_M[,TABLE_SLOTS]" : "--map-voxel needs --map");
+        return 2;
+    }
+    if (bad_map_normals || (map_normals && (!map || map_ints[0] != 0))) {
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
+                     bad_map_normals ? "Malformed --map-normals: expected STEP[,JUMP_M]"
+                     : !map          ? "--map-normals needs --map"
+                                     : "--map-normals needs --map with LEVEL 0");
         return 2;
     }
     if (argc > 3) argc = bad_flag ? 0 : 3;
@@ -193,6 +226,7 @@ int main(int argc, char** argv) {
         if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
         if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
         if (map_voxel) tracker.enable_map_voxels(voxel_m, voxel_table_slots);
+        if (map_normals) tracker.enable_map_normals(normals_step, normals_jump_m);  // (last: the voxel filter emits keyframe 0 again)
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);
@@ -212,7 +246,12 @@ int main(int argc, char** argv) {
                              m.count - (uint32_t)map_ints[1]);
             if (m.n_segments > (uint32_t)map_ints[2])
                 std::fprintf(stderr, "Warning: %u keyframes but room for %d segment records\n", m.n_segments, map_ints[2]);
-            ply_io::write_map(map_file, m.xyz.data(), m.gray.data(), m.gray.size(), m.segments.data(), m.segments.size());
+            if (map_normals) {
+                const std::vector<Float> normals = tracker.read_map_normals((int)m.gray.size());
+                ply_io::write_map(map_file, m.xyz.data(), normals.data(), m.gray.data(), m.gray.size(), m.segments.data(), m.segments.size());
+            } else {
+                ply_io::write_map(map_file, m.xyz.data(), m.gray.data(), m.gray.size(), m.segments.data(), m.segments.size());
+            }
         }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "\"%s\"\n", e.what());

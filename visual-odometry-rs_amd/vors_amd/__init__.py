@@ -24,6 +24,7 @@ LIB_PATH = os.environ.get("VORS_HIP_LIB") or os.path.join(_HERE, "libvors_hip.so
 MAX_LEVELS = 8
 RESIDUAL_BINS = 256  # VORS_RESIDUAL_BINS
 RENDER_COUNTS = 4  # VORS_RENDER_COUNTS: considered, in front, landed, covered
+NORMAL_COUNTS = 3  # VORS_NORMAL_COUNTS: considered, with depth, with a normal
 
 ROW_MAJOR, COL_MAJOR = 0, 1
 CANDIDATES_COARSE_TO_FINE, CANDIDATES_DENSE, CANDIDATES_DSO = 0, 1, 2
@@ -108,6 +109,8 @@ EXPORTED_SYMBOLS = [
     "vors_batch_point_cloud", "vors_camera_back_project", "vors_camera_project",
     "vors_batch_fuse_depth", "vors_fuse_depth_pixels",
     "vors_render_points", "vors_render_points_host", "vors_trackers_render_map",
+    "vors_depth_normals", "vors_points_normals", "vors_depth_normals_host", "vors_trackers_enable_map_normals", "vors_trackers_map_normals",
+    "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -189,6 +192,13 @@ def lib():
         _lib.vors_render_points_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, i, i, f, vp, i, vp, vp, vp, vp]
         _lib.vors_trackers_render_map.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, i, vp, vp, vp, vp, vp]
         _lib.vors_tracker_render_map.argtypes = [vp, i, vp, vp, i, vp, vp, vp, vp]
+        _lib.vors_depth_normals.argtypes = [i, vp, vp, i, i, f, i, f, vp, C.c_size_t, vp, vp, vp]
+        _lib.vors_points_normals.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, i, i, f, i, f, vp, C.c_size_t, vp, vp, vp]
+        _lib.vors_depth_normals_host.argtypes = [vp, vp, i, i, f, i, f, vp, vp, C.c_uint32, i, vp, vp, vp]
+        _lib.vors_trackers_enable_map_normals.argtypes = [vp, i, f]
+        _lib.vors_trackers_map_normals.argtypes = [vp, C.POINTER(vp)]
+        _lib.vors_tracker_enable_map_normals.argtypes = [vp, i, f]
+        _lib.vors_tracker_read_map_normals.argtypes = [vp, i, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -401,6 +411,27 @@ def _map_voxels_args(spec):
     return float(voxel_m), int(table_slots)
 
 
+def _map_normals_args(spec):
+    """None or a pair (step, jump_m) -> None or (int, float). Only the SHAPE of the argument is judged here; the values (step in 1..8,
+    jump_m >= 0) are judged by the library, in one place for every caller."""
+    if spec is None:
+        return None
+    try:
+        spec = tuple(spec)
+    except TypeError:
+        raise VorsError(f"map_normals: expected None or (step, jump_m), got {spec!r}") from None
+    if len(spec) != 2:
+        raise VorsError(f"map_normals: expected 2 values (step, jump_m), got {len(spec)}")
+    step, jump_m = spec
+    if isinstance(step, bool) or not isinstance(step, (int, np.integer)):
+        raise VorsError(f"map_normals: step must be an integer, got {step!r}")
+    if not -2 ** 31 <= int(step) < 2 ** 31:
+        raise VorsError(f"map_normals: step does not fit the C int it is passed as, got {step!r}")
+    if isinstance(jump_m, bool) or not isinstance(jump_m, (int, float, np.integer, np.floating)):
+        raise VorsError(f"map_normals: jump_m must be a number, got {jump_m!r}")
+    return int(step), float(jump_m)
+
+
 VOXEL_NONE = 0xFFFFFFFFFFFFFFFF
 
 
@@ -420,16 +451,22 @@ def voxel_keys(voxel_m, xyz):
 class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
-    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None):
+    def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None,
+                 map_normals=None):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
         (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
         keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it. map_voxels: None,
-        or (voxel_m, table_slots) — the map's voxel filter (vors_tracker_enable_map_voxels; Trackers.enable_map_voxels); needs map."""
+        or (voxel_m, table_slots) — the map's voxel filter (vors_tracker_enable_map_voxels; Trackers.enable_map_voxels); needs map.
+        map_normals: None, or (step, jump_m) — a surface normal per map entry (vors_tracker_enable_map_normals;
+        Trackers.enable_map_normals), switched on last; needs map with level 0; read_map_normals() returns them."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         self._map = map = _map_args(map)
         self._map_voxels = map_voxels = _map_voxels_args(map_voxels)
         if map_voxels is not None and map is None:
             raise VorsError("map_voxels: the voxel filter needs the keyframe map (Tracker(..., map=(level, capacity, max_keyframes)))")
+        self._map_normals = map_normals = _map_normals_args(map_normals)
+        if map_normals is not None and map is None:
+            raise VorsError("map_normals: the normals need the keyframe map (Tracker(..., map=(0, capacity, max_keyframes)))")
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -446,6 +483,18 @@ class Tracker:
             _check(lib().vors_tracker_enable_map(self._h, *map))
         if map_voxels is not None:
             _check(lib().vors_tracker_enable_map_voxels(self._h, *map_voxels))
+        if map_normals is not None:
+            _check(lib().vors_tracker_enable_map_normals(self._h, *map_normals))
+
+    def read_map_normals(self, capacity=None):
+        """The map's normals so far on the host (vors_tracker_read_map_normals; synchronises) -> [m, 3] float32, rank for rank the entries
+        of read_map(capacity), m = min(count, capacity, the handle's capacity); three zeros where a point has no normal."""
+        if self._map_normals is None:
+            raise VorsError("read_map_normals: the normals are not enabled (Tracker(..., map_normals=(step, jump_m)))")
+        cap = self._map[1] if capacity is None else int(capacity)
+        normals = np.zeros((max(cap, 0), 3), np.float32)
+        _check(lib().vors_tracker_read_map_normals(self._h, cap, _ptr(normals)))
+        return normals[:min(self.read_map(capacity=0)["count"], max(cap, 0), self._map[1])]
 
     def read_map_voxels(self):
         """The voxel filter's counters (vors_tracker_read_map_voxels; synchronises) -> dict: "occupied", the distinct voxels so far, and
@@ -1095,6 +1144,22 @@ class Trackers:
         args = _map_voxels_args((voxel_m, table_slots))
         _check(lib().vors_trackers_enable_map_voxels(self._h, *args))
 
+    def enable_map_normals(self, step, jump_m):
+        """Normals of the keyframe map (vors_trackers_enable_map_normals): after enable_map() with level 0, before init(), once. Every map
+        entry then carries the surface normal of its pixel in its keyframe's depth plane, in the world frame (points_normals' rule with the
+        keyframe's pose): central differences `step` pixels wide, neighbours further than jump_m metres in depth left out."""
+        args = _map_normals_args((step, jump_m))
+        _check(lib().vors_trackers_enable_map_normals(self._h, *args))
+
+    def map_normals(self, copy=True):
+        """-> [n, capacity, 3] float32 tensor (vors_trackers_map_normals), valid in stream order after the last init() / track(): entry r
+        of a sequence is the normal of map()'s entry r, written for r < min(counts, capacity); three zeros = no normal. copy=False: a view
+        of the handle's own buffer, which dies with this object."""
+        p = C.c_void_p()
+        _check(lib().vors_trackers_map_normals(self._h, C.byref(p)))
+        out = _device_view(p.value, (self.n, self._map[1], 3), "<f4", _torch_device(self._device))
+        return out.clone() if copy else out
+
     def map_voxels(self, copy=True):
         """-> dict of tensors (vors_trackers_map_voxels), valid in stream order after the last init() / track(): "occupied" [n] int32, the
         distinct voxels of a sequence so far (== map()["counts"] while it has not overflowed), "overflow" [n] int32, non-zero once a
@@ -1416,6 +1481,98 @@ def render_points_host(xyz, list_gray, cam5, rows, cols, depth_scale, pose7=None
     _check(lib().vors_render_points_host(_ptr(p), _ptr(g), len(p) if count is None else int(count), len(p), _ptr(rng), _ptr(k), int(rows),
                                          int(cols), float(depth_scale), _ptr(pose), int(footprint), _ptr(out["zkey"]), _ptr(out["depth"]),
                                          _ptr(out["gray"]), _ptr(out["counts"])))
+    return out
+
+
+def _normals_common(cam5, who):
+    k = np.ascontiguousarray(cam5, np.float32)
+    if k.shape != (5,):
+        raise VorsError(f"{who}: cam5 [5]")
+    return k
+
+
+def _normals_outputs(shape3, dev, normals, counts):
+    """True = a new tensor, a tensor = write into it, False / None = not wanted."""
+    import torch
+    out = []
+    for o, shp, dtype in ((normals, shape3, torch.float32), (counts, (shape3[0], NORMAL_COUNTS), torch.int32)):
+        if o is False or o is None:
+            out.append(None)
+        elif o is True:
+            out.append(torch.empty(shp, dtype=dtype, device=dev))
+        elif o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shp):
+            raise VorsError(f"expected a contiguous {dtype} output {tuple(shp)}, got {o.dtype} {tuple(o.shape)}")
+        else:
+            out.append(o)
+    return out
+
+
+def depth_normals(depth, cam5, depth_scale, step, jump_m, poses=None, normals=True, counts=False):
+    """Surface normals of n level-0 depth planes (vors_depth_normals; handle-free) -> dict of the requested tensors on the current stream,
+    not synchronised: "normals" [n, rows, cols, 3] float32 (unit, facing the camera, three zeros = no normal), "counts" [n, 3] int32
+    (considered, with depth, with a normal). depth [n, rows, cols] int16 tensor holding the u16 payload; cam5 = cu cv fu fv skew; step
+    1..8 pixels to the neighbours; jump_m: a neighbour further than this in depth is left out. poses [n, 7] float32 camera -> world (None =
+    camera frame; only the rotation is applied). normals / counts may also be a tensor of that shape to write into."""
+    import torch
+    if depth.dtype != torch.int16 or depth.dim() != 3 or not depth.is_contiguous():
+        raise VorsError("depth_normals: depth int16 [n, rows, cols], contiguous")
+    n, rows, cols = depth.shape
+    k = _normals_common(cam5, "depth_normals")
+    poses, pose_stride = _render_poses(poses, n)
+    o_n, o_c = _normals_outputs((n, rows, cols, 3), depth.device, normals, counts)
+    _check(lib().vors_depth_normals(n, Batch._dp(depth), _ptr(k), rows, cols, float(depth_scale), int(step), float(jump_m), Batch._dp(poses),
+                                    pose_stride, Batch._dp(o_n), Batch._dp(o_c), Batch._stream()))
+    return {name: t for name, t in (("normals", o_n), ("counts", o_c)) if t is not None}
+
+
+def points_normals(depth, pixel, list_counts, cam5, depth_scale, step, jump_m, poses=None, ranges=None, normals=True, counts=False):
+    """Surface normals of LISTED pixels of n level-0 depth planes (vors_points_normals; handle-free) -> dict as depth_normals(), "normals"
+    [n, capacity, 3]: exactly the ranks of each list's clipped range are written, everything else of a tensor passed in is left untouched
+    (a new tensor is zeroed first). pixel [n, capacity] int32 (x | y << 16) and list_counts [n] int32: the tensors of Trackers.map() /
+    Batch.point_cloud(); ranges: see _render_ranges; a pixel outside the plane has no normal."""
+    import torch
+    if depth.dtype != torch.int16 or depth.dim() != 3 or not depth.is_contiguous():
+        raise VorsError("points_normals: depth int16 [n, rows, cols], contiguous")
+    n, rows, cols = depth.shape
+    cap = pixel.shape[1] if pixel.dim() == 2 else -1
+    if (pixel.dtype != torch.int32 or not pixel.is_contiguous() or tuple(pixel.shape) != (n, cap) or list_counts.dtype != torch.int32
+            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
+        raise VorsError("points_normals: pixel int32 [n, capacity], list_counts int32 [n], contiguous")
+    k = _normals_common(cam5, "points_normals")
+    poses, pose_stride = _render_poses(poses, n)
+    rng, range_stride = _render_ranges(ranges, n)
+    o_n, o_c = _normals_outputs((n, cap, 3), depth.device, normals, counts)
+    if normals is True:
+        o_n.zero_()
+    _check(lib().vors_points_normals(n, Batch._dp(depth), Batch._dp(pixel), Batch._dp(list_counts), cap, rng, range_stride, _ptr(k), rows, cols,
+                                     float(depth_scale), int(step), float(jump_m), Batch._dp(poses), pose_stride, Batch._dp(o_n),
+                                     Batch._dp(o_c), Batch._stream()))
+    return {name: t for name, t in (("normals", o_n), ("counts", o_c)) if t is not None}
+
+
+def depth_normals_host(depth, cam5, depth_scale, step, jump_m, pose7=None, pixel=None, count=None, range2=None, normals=None):
+    """The rule of depth_normals / points_normals for ONE plane on the host (vors_depth_normals_host; needs no GPU; the text the kernels
+    run): depth [rows, cols] uint16 -> dict: "normals" float32 and "counts" [3] uint32. pixel None: the plane form, normals [rows, cols, 3].
+    pixel [capacity] uint32 (x | y << 16): the list form, normals [capacity, 3] with only the ranks of the clipped range written — count =
+    the list's count (None = capacity; above it: clipped), range2 = (first, count) or None; `normals`: an array to write into (None = a
+    zeroed one). pose7 camera -> world or None."""
+    d = np.ascontiguousarray(depth, np.uint16)
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+    px = None if pixel is None else np.ascontiguousarray(pixel, np.uint32).reshape(-1)
+    if d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,)):
+        raise VorsError("depth_normals_host: depth [rows, cols], cam5 [5], pose7 [7] or None, range2 [2] or None")
+    rows, cols = d.shape
+    shape = (rows, cols, 3) if px is None else (len(px), 3)
+    if normals is None:
+        normals = np.zeros(shape, np.float32)
+    elif normals.dtype != np.float32 or normals.shape != shape or not normals.flags.c_contiguous:
+        raise VorsError(f"depth_normals_host: normals must be a contiguous float32 array {shape}")
+    cap = 0 if px is None else len(px)
+    out = dict(normals=normals, counts=np.zeros(NORMAL_COUNTS, np.uint32))
+    _check(lib().vors_depth_normals_host(_ptr(d), _ptr(k), rows, cols, float(depth_scale), int(step), float(jump_m), _ptr(pose), _ptr(px),
+                                         cap if count is None else int(count), cap, _ptr(rng), _ptr(normals), _ptr(out["counts"])))
     return out
 
 
