@@ -1,4 +1,5 @@
-// Device helpers shared by kernels.hip, lm_kernels.hip (and product_kernels.hip, through lm_sources.h) and lm_reference.hip.
+// Device helpers shared by kernels.hip, lm_kernels.hip (and product_kernels.hip, through lm_sources.h), lm_reference.hip and
+// render_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,37 @@ namespace vors {
 __device__ __forceinline__ int select_pair(const Geom& g, int k) {
     if (!g.sel_list) return k;
     return k < *g.sel_count ? g.sel_list[k] : -1;
+}
+
+// The count reduction of a workgroup of BLOCK threads: K per-thread integers added across the wavefront (a __shfl_xor butterfly), one
+// LDS slot per wavefront and counter (lds: (BLOCK / 64) * K words), a barrier, then thread k hands the total of counter k to the sink.
+// Every thread of the workgroup calls it. Integer sums: the result does not depend on the schedule.
+struct CountsAdd {  // one global atomicAdd per non-zero counter and workgroup, into a zeroed array
+    uint32_t* dst;
+    __device__ __forceinline__ void operator()(unsigned k, uint32_t t) const {
+        if (t) atomicAdd(dst + k, t);
+    }
+};
+struct CountsStore {  // stored, not accumulated: the destination needs no clearing
+    uint32_t* dst;
+    __device__ __forceinline__ void operator()(unsigned k, uint32_t t) const { dst[k] = t; }
+};
+template <int K, int BLOCK, class Sink>
+__device__ __forceinline__ void block_counts(uint32_t (&n)[K], uint32_t* lds, const Sink& sink) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n[k] += (uint32_t)__shfl_xor((int)n[k], o);
+        if ((threadIdx.x & 63) == 0) lds[(threadIdx.x >> 6) * K + k] = n[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        const unsigned k = K == 1 ? 0u : threadIdx.x;
+        uint32_t t = 0;
+#pragma unroll
+        for (int wv = 0; wv < BLOCK / 64; ++wv) t += lds[wv * K + k];
+        sink(k, t);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -163,8 +163,7 @@ void launch_lm_residual_maps(const Geom& g_in, const ResidualMapsCall& call, hip
 // one 32-bit global atomicMin per landing point. A minimum does not depend on the order of arrival: the plane is bitwise reproducible.
 // Residual (level 0, needs the current depth): P'.z - cur_depth[q] / depth_scale in KEYFRAME geometry, stored like the residual maps
 // (dense: the pass writes the NaN of a non-point itself; lists: scattered into a plane of NaN).
-// Counts (COUNTS): per-thread integers, added across the wavefront, one LDS sum per workgroup, one global integer atomicAdd per non-zero
-// counter and workgroup into a zeroed array. Without COUNTS the kernel has no LDS.
+// Counts (COUNTS): per-thread integers through block_counts (device_common.h) into a zeroed array. Without COUNTS the kernel has no LDS.
 // ------------------------------------------------------------------------------------------------------------
 // warp (lm_optimizer.rs:213-219) as warp_point evaluates it — the same text, so (u, v) have the bits of d_warp_uv — plus the depth P'.z.
 struct WarpedZ {
@@ -176,6 +175,36 @@ __device__ __forceinline__ WarpedZ warp_point_z(const ImgCtx& c, const Iso& mode
     project_uv(c.k, p2, &w.u, &w.v);
     w.z = p2.z;
     return w;
+}
+// The landing test of both splats (reprojection and fusion): the pixel nearest to (u, v), when the point is usable, in front of the
+// camera and that pixel is in the window. Masked, not branched: a point that does not land addresses pixel 0 (a safe address) and is
+// selected away. (fcols, frows: the window as floats, converted once by the caller — converted here, the dense kernels take more SGPRs.)
+struct Landing {
+    bool lands;
+    unsigned q;
+};
+__device__ __forceinline__ Landing landing_pixel(const WarpedZ& w, bool usable, int cols, float fcols, float frows) {
+    const float fu = floorf(w.u + 0.5f), fv = floorf(w.v + 0.5f);
+    Landing l;
+    l.lands = usable && (w.z > 0.f) && (fu >= 0.f) && (fu < fcols) && (fv >= 0.f) && (fv < frows);
+    l.q = (unsigned)(__float2int_rz(l.lands ? fv : 0.f) * cols + __float2int_rz(l.lands ? fu : 0.f));
+    return l;
+}
+// One byte per point of a unit from a byte plane in the level's pixel geometry (weights, keep masks), at the pixels px[] of its points
+// (a lane past the end of a list is no point: the caller hands pixel 0): a unit of four — the dense quad source, four adjacent pixels
+// of one row — reads them as one dword where the plane allows it (`wide`, uniform: 4-byte aligned), else G byte loads.
+template <int G>
+__device__ __forceinline__ void unit_bytes(const uint8_t* plane, bool wide, const unsigned (&px)[G], uint32_t (&out)[G]) {
+    if constexpr (G == 4) {
+        if (wide) {
+            const uint32_t w = *reinterpret_cast<const uint32_t*>(plane + px[0]);
+#pragma unroll
+            for (int g = 0; g < G; ++g) out[g] = (w >> (8 * g)) & 0xffu;
+            return;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) out[g] = plane[px[g]];
 }
 template <bool COUNTS, class Src>
 __device__ __forceinline__ void reproject_sweep(const Src& src, int first, int last, const ImgCtx& c, const Iso& model, float depth_scale,
@@ -196,11 +225,10 @@ __device__ __forceinline__ void reproject_sweep(const Src& src, int first, int l
         unsigned q[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const float fu = floorf(w[g].u + 0.5f), fv = floorf(w[g].v + 0.5f);
             usable[g] = pos[g].tmpl >= 0.f;
-            lands[g] = usable[g] && (w[g].z > 0.f) && (fu >= 0.f) && (fu < fcols) && (fv >= 0.f) && (fv < frows);
-            // masked, not branched: a point that does not land addresses pixel 0 (a safe address) and is selected away
-            q[g] = (unsigned)(__float2int_rz(lands[g] ? fv : 0.f) * c.cols + __float2int_rz(lands[g] ? fu : 0.f));
+            const Landing l = landing_pixel(w[g], usable[g], c.cols, fcols, frows);
+            lands[g] = l.lands;
+            q[g] = l.q;
         }
         if (zbuf) {
 #pragma unroll
@@ -267,21 +295,7 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void lm_reproject_depth_kernel(Geom g,
         const LevelCut cut = level_cut(n_units, chunk, chunks);
         reproject_sweep<COUNTS>(src, cut.first, cut.last, c, model, g.depth_scale, zbuf, cur_depth, a.tol_m, res, a.wide_stores != 0, n);
     });
-    if constexpr (COUNTS) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) n[k] += (uint32_t)__shfl_xor((int)n[k], o);
-            if ((threadIdx.x & 63) == 0) lds_counts[(threadIdx.x >> 6) * 4 + k] = n[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < RMAPS_BLOCK / 64; ++wv) t += lds_counts[wv * 4 + threadIdx.x];
-            if (t) atomicAdd(a.counts + (size_t)pair * 4 + threadIdx.x, t);
-        }
-    }
+    if constexpr (COUNTS) block_counts<4, RMAPS_BLOCK>(n, lds_counts, CountsAdd{a.counts + (size_t)pair * 4});
 }
 // z-buffer -> depth map: to_depth(depth_scale, 1 / z) (lie.h, inverse_depth.rs:37-42), 0 where nothing landed. Four pixels per thread
 // (16-byte loads, 8-byte stores) where the planes allow it.
@@ -328,17 +342,16 @@ void launch_lm_reproject_depth(const Geom& g_in, const ReprojectCall& call, hipS
 
 // ------------------------------------------------------------------------------------------------------------
 // vors_batch_fuse_depth: level 0 of the keyframe splatted into the CURRENT frame through a KEYED z-buffer, then merged per current pixel
-// with the measured depth. Two launches ordered by the stream.
-// SPLAT (lm_fuse_splat_kernel): lm_reproject_depth_kernel's grid, cut and sources; the sweep is reproject_sweep's up to the landing test —
-// a sibling, reproject_sweep itself is untouched. Then one weight byte at the SOURCE pixel (the dense quad source reads its four adjacent
-// bytes as one dword where the plane allows it; no plane: weight 1) and, per landing point of non-zero weight, one 64-bit global
-// atomicMin of bits(Z') << 32 | src into a plane the launcher has filled with ones. Z' > 0 orders as its bits, so the nearest surface
+// with the measured depth. Two launches ordered by the stream. Each pass has ONE body; its kernels are entry points that find the pair —
+// index blockIdx.y of a slice of the whole batch, or of the promotion list (the depth filter, below) — and say whether planes may be null.
+// SPLAT (fuse_splat_body): lm_reproject_depth_kernel's grid, cut and sources; the sweep is reproject_sweep's up to the landing test
+// (landing_pixel). Then one weight byte at the SOURCE pixel (unit_bytes; no plane: weight 1) and, per landing point of non-zero weight,
+// one 64-bit global atomicMin of bits(Z') << 32 | src into a plane filled with ones. Z' > 0 orders as its bits, so the nearest surface
 // wins and among equal Z' the smallest source index: a minimum, bitwise reproducible whatever the order of arrival. No LDS.
-// MERGE (fuse_depth_kernel): elementwise over current pixels, 1024 per workgroup: lie.h fuse_depth_pixel on (key, weight gathered at src,
+// MERGE (fuse_merge_body): elementwise over current pixels, 1024 per workgroup: lie.h fuse_depth_pixel on (key, weight gathered at src,
 // measured depth). Four adjacent pixels per thread where every plane allows it (two 16-byte key loads, one 8-byte depth load, an 8-byte
-// and a 4-byte store), else four pixels a workgroup width apart. Counts (COUNTS) follow the reprojection pass: per-thread integers, added
-// across the wavefront, one LDS sum per workgroup, one global integer atomicAdd per non-zero counter and workgroup into a zeroed array.
-// Without COUNTS the kernel has no LDS and no atomic.
+// and a 4-byte store), else four pixels a workgroup width apart. Counts (COUNTS) follow the reprojection pass (block_counts into a zeroed
+// array). Without COUNTS the kernel has no LDS and no atomic.
 // ------------------------------------------------------------------------------------------------------------
 template <class Src>
 __device__ __forceinline__ void fuse_splat_sweep(const Src& src, int first, int last, const ImgCtx& c, const Iso& model, const uint8_t* kf_weight,
@@ -353,51 +366,34 @@ __device__ __forceinline__ void fuse_splat_sweep(const Src& src, int first, int 
         WarpedZ w[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) w[g] = warp_point_z(c, model, pos[g]);
-        bool lands[G];
-        unsigned q[G], from[G];
+        Landing l[G];
+        unsigned from[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            const float fu = floorf(w[g].u + 0.5f), fv = floorf(w[g].v + 0.5f);
-            lands[g] = (pos[g].tmpl >= 0.f) && (w[g].z > 0.f) && (fu >= 0.f) && (fu < fcols) && (fv >= 0.f) && (fv < frows);
-            // masked, not branched: a point that does not land addresses pixel 0 (a safe address) and is selected away
-            q[g] = (unsigned)(__float2int_rz(lands[g] ? fv : 0.f) * c.cols + __float2int_rz(lands[g] ? fu : 0.f));
+            l[g] = landing_pixel(w[g], pos[g].tmpl >= 0.f, c.cols, fcols, frows);
             from[g] = (unsigned)max(plane_pixel(src, raw, g, c.cols), 0);  // (a lane past the end of a list is no point: pixel 0, selected away)
         }
         uint32_t wb[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) wb[g] = 1;
-        if (kf_weight) {  // (uniform)
-            bool done = false;
-            if constexpr (G == 4) {
-                if (wide_weight) {  // (uniform) a quad owns four adjacent pixels of one row, 4-byte aligned in the weight plane
-                    const uint32_t ww = *reinterpret_cast<const uint32_t*>(kf_weight + from[0]);
-#pragma unroll
-                    for (int g = 0; g < G; ++g) wb[g] = (ww >> (8 * g)) & 0xffu;
-                    done = true;
-                }
-            }
-            if (!done) {
-#pragma unroll
-                for (int g = 0; g < G; ++g) wb[g] = kf_weight[from[g]];
-            }
-        }
+        if (kf_weight) unit_bytes(kf_weight, wide_weight, from, wb);  // (uniform)
 #pragma unroll
         for (int g = 0; g < G; ++g)
-            if (lands[g] && wb[g] != 0)
-                atomicMin(zkey + q[g], ((unsigned long long)(uint32_t)__float_as_int(w[g].z) << 32) | (unsigned long long)from[g]);
+            if (l[g].lands && wb[g] != 0)
+                atomicMin(zkey + l[g].q, ((unsigned long long)(uint32_t)__float_as_int(w[g].z) << 32) | (unsigned long long)from[g]);
     }
 }
-template <bool DENSE>
-__global__ __launch_bounds__(RMAPS_BLOCK) void lm_fuse_splat_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
-                                                                    const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
-                                                                    const uint16_t* __restrict__ kf_depth, Records rec, FuseSplatArgs a) {
-    const int pair = a.pair0 + blockIdx.y, chunk = blockIdx.x, n_chunks = gridDim.x;
+// OPTIONAL_PLANES: a null kf_weight stands for weight 1 everywhere; without it the plane is required and no null test is kept.
+template <bool DENSE, bool OPTIONAL_PLANES>
+__device__ __forceinline__ void fuse_splat_body(const Geom& g, int pair, const uint8_t* kf0, const uint8_t* kfu, const uint16_t* kf_depth,
+                                                const Records& rec, const FuseSplatArgs& a) {
+    const int chunk = blockIdx.x, n_chunks = gridDim.x;
     const Iso model = iso_uniform(iso_load(a.models + (size_t)pair * a.model_stride));
     ImgCtx c{};  // level 0's window and intrinsics; the current image is never read (the pass is legal before any track_current)
     c.rows = g.lv[0].rows;
     c.cols = g.lv[0].cols;
     c.k = g.lv[0].k;
-    const uint8_t* kf_weight = a.kf_weight ? a.kf_weight + (size_t)pair * g.S0 : nullptr;
+    const uint8_t* kf_weight = (!OPTIONAL_PLANES || a.kf_weight) ? a.kf_weight + (size_t)pair * g.S0 : nullptr;
     unsigned long long* zkey = a.zkey + (size_t)pair * g.S0;
     with_exact_source<DENSE, true>(g, 0, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
         const int chunks = level_chunks(DENSE ? g.lv[0].n_slots : n_units, a.chunk_points, n_chunks);
@@ -406,18 +402,23 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void lm_fuse_splat_kernel(Geom g, cons
         fuse_splat_sweep(src, cut.first, cut.last, c, model, kf_weight, a.wide_weight != 0, zkey);
     });
 }
+template <bool DENSE>
+__global__ __launch_bounds__(RMAPS_BLOCK) void lm_fuse_splat_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                    const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                    const uint16_t* __restrict__ kf_depth, Records rec, FuseSplatArgs a) {
+    fuse_splat_body<DENSE, true>(g, a.pair0 + blockIdx.y, kf0, kfu, kf_depth, rec, a);
+}
 #define FUSE_BLOCK 256
 #define FUSE_PIXELS 4  // per thread
-template <bool COUNTS>
-__global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_kernel(FuseMergeArgs a) {
-    __shared__ uint32_t lds_counts[COUNTS ? (FUSE_BLOCK / 64) * VORS_FUSE_COUNTS : 1];
-    const int pair = a.pair0 + blockIdx.y;
+// OPTIONAL_PLANES: kf_weight and the two outputs may be null; without it all planes are required and no null test is kept.
+template <bool COUNTS, bool OPTIONAL_PLANES>
+__device__ __forceinline__ void fuse_merge_body(int pair, const FuseMergeArgs& a, uint32_t* lds_counts) {
     const size_t off = (size_t)pair * (size_t)a.plane;
     const uint64_t* zkey = a.zkey + off;
     const uint16_t* cur_depth = a.cur_depth + off;
-    const uint8_t* kf_weight = a.kf_weight ? a.kf_weight + off : nullptr;
-    uint16_t* fused_depth = a.fused_depth ? a.fused_depth + off : nullptr;
-    uint8_t* fused_weight = a.fused_weight ? a.fused_weight + off : nullptr;
+    const uint8_t* kf_weight = (!OPTIONAL_PLANES || a.kf_weight) ? a.kf_weight + off : nullptr;
+    uint16_t* fused_depth = (!OPTIONAL_PLANES || a.fused_depth) ? a.fused_depth + off : nullptr;
+    uint8_t* fused_weight = (!OPTIONAL_PLANES || a.fused_weight) ? a.fused_weight + off : nullptr;
     const int base = blockIdx.x * (FUSE_BLOCK * FUSE_PIXELS);
     uint32_t n[VORS_FUSE_COUNTS] = {0u, 0u, 0u, 0u, 0u, 0u};
     FusedPixel o[FUSE_PIXELS];
@@ -430,8 +431,8 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_kernel(FuseMergeArgs a)
             o[1] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.y, kf_weight, d.y);
             o[2] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.x, kf_weight, d.z);
             o[3] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.y, kf_weight, d.w);
-            if (fused_depth) *reinterpret_cast<ushort4*>(fused_depth + i) = make_ushort4(o[0].depth, o[1].depth, o[2].depth, o[3].depth);
-            if (fused_weight)
+            if (!OPTIONAL_PLANES || fused_depth) *reinterpret_cast<ushort4*>(fused_depth + i) = make_ushort4(o[0].depth, o[1].depth, o[2].depth, o[3].depth);
+            if (!OPTIONAL_PLANES || fused_weight)
                 *reinterpret_cast<uint32_t*>(fused_weight + i) =
                     (uint32_t)o[0].weight | ((uint32_t)o[1].weight << 8) | ((uint32_t)o[2].weight << 16) | ((uint32_t)o[3].weight << 24);
             if constexpr (COUNTS) {
@@ -447,30 +448,32 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_kernel(FuseMergeArgs a)
             const int i = base + j * FUSE_BLOCK + (int)threadIdx.x;
             if (i >= a.plane) continue;
             o[j] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, zkey[i], kf_weight, cur_depth[i]);
-            if (fused_depth) fused_depth[i] = o[j].depth;
-            if (fused_weight) fused_weight[i] = o[j].weight;
+            if (!OPTIONAL_PLANES || fused_depth) fused_depth[i] = o[j].depth;
+            if (!OPTIONAL_PLANES || fused_weight) fused_weight[i] = o[j].weight;
             if constexpr (COUNTS) {
 #pragma unroll
                 for (int k = 0; k < VORS_FUSE_COUNTS; ++k) n[k] += o[j].kase == k ? 1u : 0u;
             }
         }
     }
-    if constexpr (COUNTS) {
-#pragma unroll
-        for (int k = 0; k < VORS_FUSE_COUNTS; ++k) {
-#pragma unroll
-            for (int sh = 32; sh > 0; sh >>= 1) n[k] += (uint32_t)__shfl_xor((int)n[k], sh);
-            if ((threadIdx.x & 63) == 0) lds_counts[(threadIdx.x >> 6) * VORS_FUSE_COUNTS + k] = n[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < VORS_FUSE_COUNTS) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < FUSE_BLOCK / 64; ++wv) t += lds_counts[wv * VORS_FUSE_COUNTS + threadIdx.x];
-            if (t) atomicAdd(a.counts + (size_t)pair * VORS_FUSE_COUNTS + threadIdx.x, t);
-        }
-    }
+    if constexpr (COUNTS) block_counts<VORS_FUSE_COUNTS, FUSE_BLOCK>(n, lds_counts, CountsAdd{a.counts + (size_t)pair * VORS_FUSE_COUNTS});
 }
+template <bool COUNTS>
+__global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_kernel(FuseMergeArgs a) {
+    __shared__ uint32_t lds_counts[COUNTS ? (FUSE_BLOCK / 64) * VORS_FUSE_COUNTS : 1];
+    fuse_merge_body<COUNTS, true>(a.pair0 + blockIdx.y, a, lds_counts);
+}
+// What both launchers hand their kernels: the splat's and the merge's arguments (pair0 = 0) and the rule for the wide forms.
+static void fuse_depth_args(const Geom& g, const FuseDepthCall& call, uint32_t* counts, FuseSplatArgs* a, FuseMergeArgs* m) {
+    const size_t plane = (size_t)g.S0;
+    *a = FuseSplatArgs{0, eval_pairs_chunk_points(g), call.models, call.model_stride, call.kf_weight, reinterpret_cast<unsigned long long*>(call.zkey),
+                       ((uintptr_t)call.kf_weight % 4 == 0 && plane % 4 == 0) ? 1 : 0};
+    const bool wide = plane % 4 == 0 && (uintptr_t)call.zkey % 16 == 0 && (uintptr_t)call.cur_depth % 8 == 0 && (uintptr_t)call.fused_depth % 8 == 0 &&
+                      (uintptr_t)call.fused_weight % 4 == 0;
+    *m = FuseMergeArgs{0, (int)plane, g.depth_scale, call.tol_m, call.max_weight, call.fill_min_weight, call.zkey, call.cur_depth, call.kf_weight,
+                       call.fused_depth, call.fused_weight, counts, wide ? 1 : 0};
+}
+static unsigned fuse_merge_blocks(const Geom& g) { return (unsigned)(((size_t)g.S0 + FUSE_BLOCK * FUSE_PIXELS - 1) / (FUSE_BLOCK * FUSE_PIXELS)); }
 void launch_lm_fuse_depth(const Geom& g_in, const FuseDepthCall& call, hipStream_t s) {
     const Geom g = launch_geom(g_in, call);
     const bool dense = g.mode == VORS_CANDIDATES_DENSE;
@@ -478,15 +481,11 @@ void launch_lm_fuse_depth(const Geom& g_in, const FuseDepthCall& call, hipStream
     // all ones = VORS_ZKEY_EMPTY: nothing has landed (a 32-bit fill over twice as many dwords)
     (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(call.zkey), 0xFFFFFFFF, 2 * n * plane, s);
     if (call.counts) (void)hipMemsetAsync(call.counts, 0, n * VORS_FUSE_COUNTS * sizeof(uint32_t), s);
-    FuseSplatArgs a{0, eval_pairs_chunk_points(g), call.models, call.model_stride, call.kf_weight, reinterpret_cast<unsigned long long*>(call.zkey),
-                    ((uintptr_t)call.kf_weight % 4 == 0 && plane % 4 == 0) ? 1 : 0};
+    FuseSplatArgs a;
+    FuseMergeArgs m;
+    fuse_depth_args(g, call, call.counts, &a, &m);
     const bool merge = call.fused_depth || call.fused_weight || call.counts;
-    const bool wide = plane % 4 == 0 && (uintptr_t)call.zkey % 16 == 0 && (uintptr_t)call.cur_depth % 8 == 0 && (uintptr_t)call.fused_depth % 8 == 0 &&
-                      (uintptr_t)call.fused_weight % 4 == 0;
-    FuseMergeArgs m{0, (int)plane, g.depth_scale, call.tol_m, call.max_weight, call.fill_min_weight, call.zkey, call.cur_depth, call.kf_weight,
-                    call.fused_depth, call.fused_weight, call.counts, wide ? 1 : 0};
     const int chunks = eval_pairs_chunks(g, 0);
-    const unsigned blocks = (unsigned)((plane + FUSE_BLOCK * FUSE_PIXELS - 1) / (FUSE_BLOCK * FUSE_PIXELS));
     for_pair_slices(call.n_pairs, [&](int pair0, int np) {
         a.pair0 = m.pair0 = pair0;
         with_bool(dense, [&](auto d) {
@@ -494,7 +493,7 @@ void launch_lm_fuse_depth(const Geom& g_in, const FuseDepthCall& call, hipStream
         });
         if (merge)
             with_bool(call.counts != nullptr, [&](auto k) {
-                hipLaunchKernelGGL(fuse_depth_kernel<decltype(k)::value>, dim3(blocks, np), dim3(FUSE_BLOCK), 0, s, m);
+                hipLaunchKernelGGL(fuse_depth_kernel<decltype(k)::value>, dim3(fuse_merge_blocks(g), np), dim3(FUSE_BLOCK), 0, s, m);
             });
     });
 }
@@ -502,11 +501,10 @@ void launch_lm_fuse_depth(const Geom& g_in, const FuseDepthCall& call, hipStream
 // ------------------------------------------------------------------------------------------------------------
 // The depth filter of the lock-step trackers (vors_trackers_enable_depth_filter): the pass above as MASKED launches over the promotion
 // list (Geom::sel_list) — index k of the pair dimension is sequence select_pair(g, k), a workgroup beyond the selection returns at once.
-// Siblings: the kernels above are untouched. The host does not know how many sequences promote, so the grids are sized for all of them.
+// The host does not know how many sequences promote, so the grids are sized for all of them. What the masked form adds to the bodies
+// above is select_pair in front and a fill of its own; every plane is required and nothing is counted, so SPLAT and MERGE keep no null
+// test, no LDS and, the splat's minimum apart, no atomic. The model is the head of the sequence's vors_pair_stats.
 // FILL (fuse_fill_selected_kernel): the key planes of the selected sequences to VORS_ZKEY_EMPTY, two keys (16 bytes) per thread.
-// SPLAT (lm_fuse_splat_selected_kernel): lm_fuse_splat_kernel's body on the selected sequence; the model is the head of its
-//   vors_pair_stats. One 64-bit atomicMin per landing point, no LDS.
-// MERGE (fuse_depth_selected_kernel): fuse_depth_kernel<false>'s body on the selected sequence: no counts, so no LDS and no atomic.
 // ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fuse_fill_selected_kernel(Geom g, unsigned long long* __restrict__ zkey, int vec) {
     const int pair = select_pair(g, blockIdx.y);
@@ -525,55 +523,14 @@ template <bool DENSE>
 __global__ __launch_bounds__(RMAPS_BLOCK) void lm_fuse_splat_selected_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
                                                                              const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
                                                                              const uint16_t* __restrict__ kf_depth, Records rec, FuseSplatArgs a) {
-    const int pair = select_pair(g, blockIdx.y), chunk = blockIdx.x, n_chunks = gridDim.x;
+    const int pair = select_pair(g, blockIdx.y);
     if (pair < 0) return;
-    const Iso model = iso_uniform(iso_load(a.models + (size_t)pair * a.model_stride));
-    ImgCtx c{};  // level 0's window and intrinsics; the current image is never read
-    c.rows = g.lv[0].rows;
-    c.cols = g.lv[0].cols;
-    c.k = g.lv[0].k;
-    const uint8_t* kf_weight = a.kf_weight + (size_t)pair * g.S0;
-    unsigned long long* zkey = a.zkey + (size_t)pair * g.S0;
-    with_exact_source<DENSE, true>(g, 0, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
-        const int chunks = level_chunks(DENSE ? g.lv[0].n_slots : n_units, a.chunk_points, n_chunks);
-        if (chunk >= chunks) return;
-        const LevelCut cut = level_cut(n_units, chunk, chunks);
-        fuse_splat_sweep(src, cut.first, cut.last, c, model, kf_weight, a.wide_weight != 0, zkey);
-    });
+    fuse_splat_body<DENSE, false>(g, pair, kf0, kfu, kf_depth, rec, a);
 }
 __global__ __launch_bounds__(FUSE_BLOCK) void fuse_depth_selected_kernel(Geom g, FuseMergeArgs a) {
     const int pair = select_pair(g, blockIdx.y);
     if (pair < 0) return;
-    const size_t off = (size_t)pair * (size_t)a.plane;
-    const uint64_t* zkey = a.zkey + off;
-    const uint16_t* cur_depth = a.cur_depth + off;
-    const uint8_t* kf_weight = a.kf_weight + off;
-    uint16_t* fused_depth = a.fused_depth + off;
-    uint8_t* fused_weight = a.fused_weight + off;
-    const int base = blockIdx.x * (FUSE_BLOCK * FUSE_PIXELS);
-    FusedPixel o[FUSE_PIXELS];
-    if (a.wide) {  // (uniform; plane % 4 == 0: a thread's four pixels are all inside or all outside)
-        const int i = base + FUSE_PIXELS * (int)threadIdx.x;
-        if (i >= a.plane) return;
-        const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(zkey + i), k23 = *reinterpret_cast<const ulonglong2*>(zkey + i + 2);
-        const ushort4 d = *reinterpret_cast<const ushort4*>(cur_depth + i);
-        o[0] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.x, kf_weight, d.x);
-        o[1] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k01.y, kf_weight, d.y);
-        o[2] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.x, kf_weight, d.z);
-        o[3] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, k23.y, kf_weight, d.w);
-        *reinterpret_cast<ushort4*>(fused_depth + i) = make_ushort4(o[0].depth, o[1].depth, o[2].depth, o[3].depth);
-        *reinterpret_cast<uint32_t*>(fused_weight + i) =
-            (uint32_t)o[0].weight | ((uint32_t)o[1].weight << 8) | ((uint32_t)o[2].weight << 16) | ((uint32_t)o[3].weight << 24);
-    } else {
-#pragma unroll
-        for (int j = 0; j < FUSE_PIXELS; ++j) {
-            const int i = base + j * FUSE_BLOCK + (int)threadIdx.x;
-            if (i >= a.plane) continue;
-            o[j] = fuse_depth_pixel(a.depth_scale, a.tol_m, a.max_weight, a.fill_min_weight, zkey[i], kf_weight, cur_depth[i]);
-            fused_depth[i] = o[j].depth;
-            fused_weight[i] = o[j].weight;
-        }
-    }
+    fuse_merge_body<false, false>(pair, a, nullptr);
 }
 // call.n_pairs: the sequences of the handle (the extent of the pair dimension); g_in.sel_list / sel_count: the ones that take part.
 // models, cur_depth, kf_weight, zkey, fused_depth and fused_weight are all required; counts is not written.
@@ -582,20 +539,15 @@ void launch_lm_fuse_depth_selected(const Geom& g_in, const FuseDepthCall& call, 
     const bool dense = g.mode == VORS_CANDIDATES_DENSE;
     const size_t plane = (size_t)g.S0;
     const int n = call.n_pairs;
-    unsigned long long* zkey = reinterpret_cast<unsigned long long*>(call.zkey);
-    hipLaunchKernelGGL(fuse_fill_selected_kernel, dim3((unsigned)((plane + 511) / 512), n), dim3(256), 0, s, g, zkey,
+    FuseSplatArgs a;
+    FuseMergeArgs m;
+    fuse_depth_args(g, call, nullptr, &a, &m);
+    hipLaunchKernelGGL(fuse_fill_selected_kernel, dim3((unsigned)((plane + 511) / 512), n), dim3(256), 0, s, g, a.zkey,
                        (plane % 2 == 0 && (uintptr_t)call.zkey % 16 == 0) ? 1 : 0);
-    FuseSplatArgs a{0, eval_pairs_chunk_points(g), call.models, call.model_stride, call.kf_weight, zkey,
-                    ((uintptr_t)call.kf_weight % 4 == 0 && plane % 4 == 0) ? 1 : 0};
-    const bool wide = plane % 4 == 0 && (uintptr_t)call.zkey % 16 == 0 && (uintptr_t)call.cur_depth % 8 == 0 && (uintptr_t)call.fused_depth % 8 == 0 &&
-                      (uintptr_t)call.fused_weight % 4 == 0;
-    FuseMergeArgs m{0, (int)plane, g.depth_scale, call.tol_m, call.max_weight, call.fill_min_weight, call.zkey, call.cur_depth, call.kf_weight,
-                    call.fused_depth, call.fused_weight, nullptr, wide ? 1 : 0};
     with_bool(dense, [&](auto d) {
         launch_on_scene(lm_fuse_splat_selected_kernel<decltype(d)::value>, dim3(eval_pairs_chunks(g, 0), n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
     });
-    const unsigned blocks = (unsigned)((plane + FUSE_BLOCK * FUSE_PIXELS - 1) / (FUSE_BLOCK * FUSE_PIXELS));
-    hipLaunchKernelGGL(fuse_depth_selected_kernel, dim3(blocks, n), dim3(FUSE_BLOCK), 0, s, g, m);
+    hipLaunchKernelGGL(fuse_depth_selected_kernel, dim3(fuse_merge_blocks(g), n), dim3(FUSE_BLOCK), 0, s, g, m);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -695,9 +647,9 @@ __device__ __forceinline__ bool voxel_owns(const CloudVox& v, unsigned long long
 // THRESH (the keyframe map of the trackers, point_cloud_append_kernel): the plane holds weights and a point is kept from `keep_min` on.
 // VOX (its voxel filter): after the keep rule, VOX_CLAIM enters every kept point into the table and leaves the flags alone, VOX_OWNED
 // keeps a point iff it owns its voxel. Slot of point g of a unit: the candidate lists' i and i + BLOCK, the dense sources' G i + g.
-template <bool THRESH = false, int VOX = VOX_OFF, class Src>
+template <bool THRESH, int VOX, class Src>
 __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::Cursor& cur, int last, int cols, const uint8_t* keep, bool wide_keep,
-                                            CloudPts<Src::G>& o, uint32_t keep_min = 1, const CloudVox* vox = nullptr) {
+                                            CloudPts<Src::G>& o, uint32_t keep_min, const CloudVox* vox) {
     constexpr int G = Src::G;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -715,22 +667,10 @@ __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::
 #pragma unroll
     for (int g = 0; g < G; ++g) kb[g] = 1;
     if (keep) {  // (uniform)
-        bool done = false;
-        if constexpr (G == 4) {
-            if (wide_keep) {  // (uniform) a quad owns four adjacent pixels of one row, 4-byte aligned in the mask plane
-                const uint32_t w = *reinterpret_cast<const uint32_t*>(keep + (unsigned)plane_pixel(src, raw, 0, cols));
+        unsigned px[G];
 #pragma unroll
-                for (int g = 0; g < G; ++g) kb[g] = (w >> (8 * g)) & 0xffu;
-                done = true;
-            }
-        }
-        if (!done) {
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const int px = plane_pixel(src, raw, g, cols);
-                kb[g] = keep[(unsigned)max(px, 0)];  // (a lane past the end of a list reads byte 0 and is no point anyway)
-            }
-        }
+        for (int g = 0; g < G; ++g) px[g] = G == 4 ? (unsigned)plane_pixel(src, raw, g, cols) : (unsigned)max(plane_pixel(src, raw, g, cols), 0);  // (no clamp for a quad: it always holds four pixels, and the clamp costs its kernels VGPRs)
+        unit_bytes(keep, wide_keep, px, kb);
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
@@ -752,9 +692,9 @@ __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::
         }
     }
 }
-template <bool THRESH = false, int VOX = VOX_OFF, class Src>
+template <bool THRESH, int VOX, class Src>
 __device__ __forceinline__ uint32_t cloud_count_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep,
-                                                      uint32_t keep_min = 1, const CloudVox* vox = nullptr) {
+                                                      uint32_t keep_min, const CloudVox* vox) {
     constexpr int G = Src::G;
     uint32_t n = 0;
     for (typename Src::Cursor cur = src.template begin<RMAPS_BLOCK>(first); cur.i < last; cur = src.template advance<RMAPS_BLOCK>(cur)) {
@@ -809,9 +749,9 @@ __device__ __forceinline__ void cloud_store(const CloudOut& o, uint32_t rank, co
     if (o.pixel) o.pixel[rank] = xy;
     if (o.gray) o.gray[rank] = (uint8_t)(int)tmpl;
 }
-template <bool THRESH = false, int VOX = VOX_OFF, class Src>
+template <bool THRESH, int VOX, class Src>
 __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int last, int cols, const uint8_t* keep, bool wide_keep, uint32_t base,
-                                                  const CloudOut& out, uint32_t* lds, uint32_t keep_min = 1, const CloudVox* vox = nullptr) {
+                                                  const CloudOut& out, uint32_t* lds, uint32_t keep_min, const CloudVox* vox) {
     constexpr int G = Src::G;
     static_assert(G != 2 || std::is_same<Src, SlimSrc>::value, "G = 2 is the candidate lists' interleaved pair of slots");
     int par = 0;
@@ -841,19 +781,38 @@ __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int
         }
     }
 }
+// The pass of one workgroup, whoever launched it: the sweep over its chunk of the level — WRITE from `base` into `out`, else the count
+// STORED to ws[chunk] (VOX_CLAIM: nothing is counted) — under the keep rule THRESH and the voxel rule VOX (cloud_fetch). The kernels below
+// are its entry points: they find the pair, the planes and, for WRITE, the base and the lists. `ws` is the pair's row of the workspace.
+template <bool DENSE, bool WRITE, bool THRESH, int VOX>
+__device__ __forceinline__ void point_cloud_body(const Geom& g, int pair, const uint8_t* kf0, const uint8_t* kfu, const uint16_t* kf_depth,
+                                                 const Records& rec, int lvl, int chunk_points, const uint8_t* keep, bool wide_keep,
+                                                 uint32_t keep_min, uint32_t* ws, uint32_t base, const CloudOut& out, const CloudVox* vox,
+                                                 uint32_t* lds) {
+    const int chunk = blockIdx.x, n_chunks = gridDim.x;
+    const int cols = g.lv[lvl].cols;
+    uint32_t n[1] = {0u};
+    with_exact_source<DENSE, true>(g, lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
+        const int chunks = level_chunks(DENSE ? g.lv[lvl].n_slots : n_units, chunk_points, n_chunks);
+        if (chunk >= chunks) return;
+        const LevelCut cut = level_cut(n_units, chunk, chunks);
+        if constexpr (WRITE) cloud_write_sweep<THRESH, VOX>(src, cut.first, cut.last, cols, keep, wide_keep, base, out, lds, keep_min, vox);
+        else n[0] = cloud_count_sweep<THRESH, VOX>(src, cut.first, cut.last, cols, keep, wide_keep, keep_min, vox);
+    });
+    if constexpr (!WRITE && VOX != VOX_CLAIM) block_counts<1, RMAPS_BLOCK>(n, lds, CountsStore{ws + chunk});
+}
 template <bool DENSE, bool WRITE>
 __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
                                                                   const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
                                                                   const uint16_t* __restrict__ kf_depth, Records rec, PointCloudArgs a) {
     __shared__ uint32_t lds[2 * PCLOUD_WAVES];
     const int pair = a.pair0 + blockIdx.y, chunk = blockIdx.x, n_chunks = gridDim.x;
-    const int cols = g.lv[a.lvl].cols;
-    const size_t plane = (size_t)g.lv[a.lvl].rows * cols;
+    const size_t plane = (size_t)g.lv[a.lvl].rows * g.lv[a.lvl].cols;
     const uint8_t* keep = a.keep ? a.keep + (size_t)pair * plane : nullptr;
     uint32_t* ws = a.ws + (size_t)pair * a.ws_chunks;
-    uint32_t base = 0, n = 0;
+    uint32_t base = 0;
     CloudOut out{};
-    if constexpr (WRITE) {
+    if constexpr (WRITE) {  // the whole-batch base: the counts of the chunks before this one
         uint32_t total = 0;
         for (int k = 0; k < n_chunks; ++k) {  // (uniform)
             const uint32_t c = ws[k];
@@ -868,25 +827,8 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_kernel(Geom g, const 
         out.pixel = a.pixel ? a.pixel + (size_t)pair * a.capacity : nullptr;
         out.gray = a.gray ? a.gray + (size_t)pair * a.capacity : nullptr;
     }
-    with_exact_source<DENSE, true>(g, a.lvl, pair, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
-        const int chunks = level_chunks(DENSE ? g.lv[a.lvl].n_slots : n_units, a.chunk_points, n_chunks);
-        if (chunk >= chunks) return;
-        const LevelCut cut = level_cut(n_units, chunk, chunks);
-        if constexpr (WRITE) cloud_write_sweep(src, cut.first, cut.last, cols, keep, a.wide_keep != 0, base, out, lds);
-        else n = cloud_count_sweep(src, cut.first, cut.last, cols, keep, a.wide_keep != 0);
-    });
-    if constexpr (!WRITE) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
-        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < PCLOUD_WAVES; ++wv) t += lds[wv];
-            ws[chunk] = t;  // stored, not accumulated: the workspace needs no clearing
-        }
-    }
+    point_cloud_body<DENSE, WRITE, false, VOX_OFF>(g, pair, kf0, kfu, kf_depth, rec, a.lvl, a.chunk_points, keep, a.wide_keep != 0, 1u, ws, base, out,
+                                                   nullptr, lds);
 }
 // counts alone: the chunk counts of a pair added up, one thread per pair
 __global__ __launch_bounds__(64) void point_cloud_total_kernel(const uint32_t* __restrict__ ws, int ws_chunks, int chunks, int pair0, int n,
@@ -918,19 +860,20 @@ void launch_lm_point_cloud(const Geom& g_in, const PointCloudCall& call, hipStre
 
 // ------------------------------------------------------------------------------------------------------------
 // The keyframe map of the lock-step trackers (vors_trackers_enable_map): the pass above as MASKED launches over the promotion list
-// (Geom::sel_list; null = every sequence, vors_trackers_init), APPENDING to one list per sequence. Siblings: the kernels above are
-// untouched. The host does not know how many sequences promote, so the grids are sized for all of them. Three launches, ordered by the
-// stream alone — no atomic, no flag, no workgroup that waits for another:
-//   COUNT   point_cloud_kernel<DENSE, false>'s body on the selected sequence -> ws[seq][chunk]
-//   WRITE   point_cloud_kernel<DENSE, true>'s body with base = counts[seq] (the sequence's running total, still the OLD one) + the
-//           counts of the chunks before its own, the lists of the sequence at seq * capacity, and the keyframe pose of the sequence
-//           (always applied). A base that has reached the capacity stores nothing.
+// (Geom::sel_list; null = every sequence, vors_trackers_init), APPENDING to one list per sequence. What the masked form adds to
+// point_cloud_body is select_pair in front, the append base and the keep rule THRESH. The host does not know how many sequences promote,
+// so the grids are sized for all of them. Three launches, ordered by the stream alone — no atomic, no flag, no workgroup that waits for
+// another:
+//   COUNT   the counting sweep on the selected sequence -> ws[seq][chunk]
+//   WRITE   the writing sweep with base = counts[seq] (the sequence's running total, still the OLD one) + the counts of the chunks
+//           before its own, the lists of the sequence at seq * capacity, and the keyframe pose of the sequence (always applied). A
+//           base that has reached the capacity stores nothing.
 //   COMMIT  one thread per selected sequence: the segment record {keyframe index, old total, this keyframe's count, pose} if there is
 //           room for it, then n_segments += 1 and counts += count (saturating). After WRITE, which reads the old total.
 // Keep rule: min_weight <= 1 no plane is read; otherwise `weight` is the depth filter's weight plane (level 0) and a point is kept from
 // min_weight on.
-// VOXEL FILTER (vors_trackers_enable_map_voxels; point_cloud_append_voxel_kernel, below the unfiltered kernel): the list keeps ONE point
-// per occupied voxel of a world grid, the first in the map's own order. One launch more, in front:
+// VOXEL FILTER (vors_trackers_enable_map_voxels; point_cloud_append_voxel_kernel): the list keeps ONE point per occupied voxel of a
+// world grid, the first in the map's own order. It adds the sequence's table to the same body, and one launch more, in front:
 //   CLAIM   the COUNT sweep, whose every kept point enters the sequence's table (voxel_claim): the owner word of a voxel ends as the
 //           MINIMUM of the tags (segment index << 32 | slot) of the points that ever fell into it — a value that does not depend on the
 //           order of arrival (the keyed z-buffer's argument), that an older keyframe always wins, and that within a keyframe is the
@@ -939,50 +882,36 @@ void launch_lm_point_cloud(const Geom& g_in, const PointCloudCall& call, hipStre
 //   COMMIT  the same kernel.
 // The segment index is n_segments[seq], which COMMIT moves on after the three sweeps have read it.
 // ------------------------------------------------------------------------------------------------------------
+// The append base (saturating; >= capacity: nothing is stored) and the lists of sequence `seq`.
+__device__ __forceinline__ CloudOut cloud_out_append(const PointCloudAppendArgs& a, int seq, const uint32_t* ws, int chunk, uint32_t* base) {
+    unsigned long long b64 = a.counts[seq];
+    for (int k = 0; k < chunk; ++k) b64 += ws[k];  // (uniform)
+    *base = b64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b64;
+    CloudOut out{};
+    out.has_pose = true;
+    out.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
+    out.capacity = (uint32_t)a.capacity;
+    out.xyz = a.xyz + (size_t)seq * a.capacity * 3;
+    out.pixel = a.pixel + (size_t)seq * a.capacity;
+    out.gray = a.gray + (size_t)seq * a.capacity;
+    return out;
+}
+// (Two entry points, not one with VOX_OFF among its forms: one __global__ for both moved instructions in the unfiltered kernel.)
 template <bool DENSE, bool WRITE>
 __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
                                                                          const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
                                                                          const uint16_t* __restrict__ kf_depth, Records rec, PointCloudAppendArgs a) {
     __shared__ uint32_t lds[2 * PCLOUD_WAVES];
-    const int seq = select_pair(g, blockIdx.y), chunk = blockIdx.x, n_chunks = gridDim.x;
+    const int seq = select_pair(g, blockIdx.y);
     if (seq < 0) return;
-    const int cols = g.lv[a.lvl].cols;
     const uint8_t* keep = a.weight ? a.weight + (size_t)seq * g.S0 : nullptr;  // (set at level 0 only)
     uint32_t* ws = a.ws + (size_t)seq * a.ws_chunks;
-    uint32_t base = 0, n = 0;
+    uint32_t base = 0;
     CloudOut out{};
-    if constexpr (WRITE) {
-        unsigned long long b64 = a.counts[seq];
-        for (int k = 0; k < chunk; ++k) b64 += ws[k];  // (uniform)
-        base = b64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b64;  // (>= capacity: nothing is stored)
-        out.has_pose = true;
-        out.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
-        out.capacity = (uint32_t)a.capacity;
-        out.xyz = a.xyz + (size_t)seq * a.capacity * 3;
-        out.pixel = a.pixel + (size_t)seq * a.capacity;
-        out.gray = a.gray + (size_t)seq * a.capacity;
-    }
-    with_exact_source<DENSE, true>(g, a.lvl, seq, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
-        const int chunks = level_chunks(DENSE ? g.lv[a.lvl].n_slots : n_units, a.chunk_points, n_chunks);
-        if (chunk >= chunks) return;
-        const LevelCut cut = level_cut(n_units, chunk, chunks);
-        if constexpr (WRITE) cloud_write_sweep<true>(src, cut.first, cut.last, cols, keep, a.wide_keep != 0, base, out, lds, (uint32_t)a.keep_min);
-        else n = cloud_count_sweep<true>(src, cut.first, cut.last, cols, keep, a.wide_keep != 0, (uint32_t)a.keep_min);
-    });
-    if constexpr (!WRITE) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
-        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < PCLOUD_WAVES; ++wv) t += lds[wv];
-            ws[chunk] = t;  // stored, not accumulated: the workspace needs no clearing
-        }
-    }
+    if constexpr (WRITE) out = cloud_out_append(a, seq, ws, blockIdx.x, &base);
+    point_cloud_body<DENSE, WRITE, true, VOX_OFF>(g, seq, kf0, kfu, kf_depth, rec, a.lvl, a.chunk_points, keep, a.wide_keep != 0, (uint32_t)a.keep_min, ws,
+                                                  base, out, nullptr, lds);
 }
-// (A sibling with point_cloud_append_kernel's text: sharing one body between the two moved instructions in the unfiltered kernel.)
 template <bool DENSE, bool WRITE, int VOX>
 __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_voxel_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
                                                                                const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
@@ -990,24 +919,13 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_voxel_kernel(G
                                                                                PointCloudAppendArgs a, PointCloudVoxelArgs v) {
     static_assert(VOX != VOX_OFF && !(WRITE && VOX == VOX_CLAIM), "CLAIM is a counting sweep");
     __shared__ uint32_t lds[2 * PCLOUD_WAVES];
-    const int seq = select_pair(g, blockIdx.y), chunk = blockIdx.x, n_chunks = gridDim.x;
+    const int seq = select_pair(g, blockIdx.y);
     if (seq < 0) return;
-    const int cols = g.lv[a.lvl].cols;
     const uint8_t* keep = a.weight ? a.weight + (size_t)seq * g.S0 : nullptr;  // (set at level 0 only)
     uint32_t* ws = a.ws + (size_t)seq * a.ws_chunks;
-    uint32_t base = 0, n = 0;
+    uint32_t base = 0;
     CloudOut out{};
-    if constexpr (WRITE) {
-        unsigned long long b64 = a.counts[seq];
-        for (int k = 0; k < chunk; ++k) b64 += ws[k];  // (uniform)
-        base = b64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)b64;  // (>= capacity: nothing is stored)
-        out.has_pose = true;
-        out.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
-        out.capacity = (uint32_t)a.capacity;
-        out.xyz = a.xyz + (size_t)seq * a.capacity * 3;
-        out.pixel = a.pixel + (size_t)seq * a.capacity;
-        out.gray = a.gray + (size_t)seq * a.capacity;
-    }
+    if constexpr (WRITE) out = cloud_out_append(a, seq, ws, blockIdx.x, &base);
     CloudVox vox;
     vox.table = v.table + 2 * (size_t)seq * v.table_slots;
     vox.occupied = v.occupied + seq;
@@ -1016,25 +934,8 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_voxel_kernel(G
     vox.voxel_m = v.voxel_m;
     vox.tag_hi = (unsigned long long)a.n_segments[seq] << 32;
     vox.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
-    with_exact_source<DENSE, true>(g, a.lvl, seq, kf0, kfu, kf_depth, rec, [&](const auto& src, int n_units) {
-        const int chunks = level_chunks(DENSE ? g.lv[a.lvl].n_slots : n_units, a.chunk_points, n_chunks);
-        if (chunk >= chunks) return;
-        const LevelCut cut = level_cut(n_units, chunk, chunks);
-        if constexpr (WRITE) cloud_write_sweep<true, VOX>(src, cut.first, cut.last, cols, keep, a.wide_keep != 0, base, out, lds, (uint32_t)a.keep_min, &vox);
-        else n = cloud_count_sweep<true, VOX>(src, cut.first, cut.last, cols, keep, a.wide_keep != 0, (uint32_t)a.keep_min, &vox);
-    });
-    if constexpr (!WRITE && VOX != VOX_CLAIM) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
-        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = n;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < PCLOUD_WAVES; ++wv) t += lds[wv];
-            ws[chunk] = t;  // stored, not accumulated: the workspace needs no clearing
-        }
-    }
+    point_cloud_body<DENSE, WRITE, true, VOX>(g, seq, kf0, kfu, kf_depth, rec, a.lvl, a.chunk_points, keep, a.wide_keep != 0, (uint32_t)a.keep_min, ws,
+                                              base, out, &vox, lds);
 }
 __global__ __launch_bounds__(64) void point_cloud_commit_kernel(Geom g, PointCloudAppendArgs a, int n, int chunks) {
     const int k = blockIdx.x * 64 + threadIdx.x;

@@ -6,8 +6,8 @@
 //         goes through the stride loop. A trip takes RENDER_POINTS points per thread a workgroup width apart: consecutive lanes read
 //         consecutive 12-byte rows, all loads of a trip issued before the first use. Per written pixel one 64-bit global atomicMin without
 //         return value of bits(Z') << 32 | rank: a minimum, bitwise reproducible whatever the order of arrival; no workgroup waits for
-//         another. No LDS without COUNTS; with them per-thread integers, added across the wavefront, one LDS sum per workgroup, one global
-//         integer atomicAdd per non-zero counter and workgroup into a zeroed array (the pattern of the depth reprojection).
+//         another. No LDS without COUNTS; with them block_counts (device_common.h) into a zeroed array, like the depth reprojection.
+//         (The landing test stays lie.h render_point's: that text is also the host's, and it rounds a footprint, not one pixel.)
 // RESOLVE (render_resolve_kernel): fuse_depth_kernel's shape — elementwise over the plane, 1024 pixels per workgroup, four adjacent pixels
 //         per thread where every plane allows it (two 16-byte key loads, an 8-byte and a 4-byte store), else four pixels a workgroup width
 //         apart; the grey level is gathered from the list at the winning rank. COUNTS: the covered pixels, same pattern.
@@ -93,21 +93,7 @@ __global__ __launch_bounds__(RENDER_BLOCK) void render_splat_kernel(RenderSplatA
             }
         }
     }
-    if constexpr (COUNTS) {
-#pragma unroll
-        for (int k = 0; k < RENDER_SPLAT_COUNTS; ++k) {
-#pragma unroll
-            for (int sh = 32; sh > 0; sh >>= 1) cnt[k] += (uint32_t)__shfl_xor((int)cnt[k], sh);
-            if ((threadIdx.x & 63) == 0) lds_counts[(threadIdx.x >> 6) * RENDER_SPLAT_COUNTS + k] = cnt[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < RENDER_SPLAT_COUNTS) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < RENDER_BLOCK / 64; ++wv) t += lds_counts[wv * RENDER_SPLAT_COUNTS + threadIdx.x];
-            if (t) atomicAdd(a.counts + (size_t)seq * VORS_RENDER_COUNTS + threadIdx.x, t);
-        }
-    }
+    if constexpr (COUNTS) block_counts<RENDER_SPLAT_COUNTS, RENDER_BLOCK>(cnt, lds_counts, CountsAdd{a.counts + (size_t)seq * VORS_RENDER_COUNTS});
 }
 
 template <bool COUNTS>
@@ -120,7 +106,7 @@ __global__ __launch_bounds__(RENDER_BLOCK) void render_resolve_kernel(RenderReso
     uint16_t* depth = a.depth ? a.depth + off : nullptr;
     uint8_t* gray = a.gray ? a.gray + off : nullptr;
     const int base = blockIdx.x * (RENDER_BLOCK * RENDER_POINTS);
-    uint32_t covered = 0;
+    uint32_t covered[1] = {0u};
     RenderedPixel o[RENDER_POINTS];
     if (a.wide) {  // (uniform; plane % 4 == 0: a thread's four pixels are all inside or all outside)
         const int i = base + RENDER_POINTS * (int)threadIdx.x;
@@ -135,7 +121,7 @@ __global__ __launch_bounds__(RENDER_BLOCK) void render_resolve_kernel(RenderReso
                 *reinterpret_cast<uint32_t*>(gray + i) =
                     (uint32_t)o[0].gray | ((uint32_t)o[1].gray << 8) | ((uint32_t)o[2].gray << 16) | ((uint32_t)o[3].gray << 24);
 #pragma unroll
-            for (int j = 0; j < RENDER_POINTS; ++j) covered += o[j].covered ? 1u : 0u;
+            for (int j = 0; j < RENDER_POINTS; ++j) covered[0] += o[j].covered ? 1u : 0u;
         }
     } else {
 #pragma unroll
@@ -145,21 +131,10 @@ __global__ __launch_bounds__(RENDER_BLOCK) void render_resolve_kernel(RenderReso
             o[j] = render_resolve(a.depth_scale, zkey[i], list_gray);
             if (depth) depth[i] = o[j].depth;
             if (gray) gray[i] = o[j].gray;
-            covered += o[j].covered ? 1u : 0u;
+            covered[0] += o[j].covered ? 1u : 0u;
         }
     }
-    if constexpr (COUNTS) {
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) covered += (uint32_t)__shfl_xor((int)covered, sh);
-        if ((threadIdx.x & 63) == 0) lds_counts[threadIdx.x >> 6] = covered;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < RENDER_BLOCK / 64; ++wv) t += lds_counts[wv];
-            if (t) atomicAdd(a.counts + (size_t)seq * VORS_RENDER_COUNTS + 3, t);
-        }
-    }
+    if constexpr (COUNTS) block_counts<1, RENDER_BLOCK>(covered, lds_counts, CountsAdd{a.counts + (size_t)seq * VORS_RENDER_COUNTS + 3});
 }
 
 void launch_render_points(const RenderCall& c, hipStream_t s) {

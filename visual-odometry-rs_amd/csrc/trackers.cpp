@@ -76,16 +76,30 @@ struct vors_trackers {
     ~vors_trackers() { vors_batch_destroy(batch); }
 };
 
+// The keyframes as the batch products read them (FuseDepthCall, PointCloudAppendCall): the records, and in dense mode the handle's own
+// level 0 and depth maps with the batch's upper levels. No current frame: these passes never read one.
+static LmScene keyframe_scene(vors_trackers* t) {
+    const vors_batch* b = t->batch;
+    const bool dense = b->g.mode == VORS_CANDIDATES_DENSE;
+    return LmScene{Pyramid{nullptr, nullptr}, Pyramid{dense ? t->own_gray.as<uint8_t>() : nullptr, b->kf_upper},
+                   dense ? t->own_depth.as<uint16_t>() : nullptr, b->rec};
+}
+// A switch whose allocations from the handle's resources failed: what was created stays with them and is freed with the handle, the
+// switch stays off. `what`: the noun of the message.
+static vors_status own_alloc_failed(vors_batch* b, const char* what) {
+    const hipError_t e = b->own.err;
+    b->own.err = hipSuccess;
+    (void)hipGetLastError();
+    return fail(VORS_ERR_HIP, std::string("hipMalloc (") + what + "): " + hipGetErrorString(e));
+}
+
 // The cloud of the NEW keyframe of every selected sequence (gm.sel_list; null: all) appended to its map. Hazards, all settled by the
 // stream: the emission reads the records, own_gray / own_depth / kf_upper (dense mode) and the filter's weight plane AFTER everything that
 // writes them in the same promotion (keyframe stage, column-major sort, the stage_weight -> weight copy) and the keyframe pose after
 // launch_trackers_advance moved it; the next frame's LM stage only reads them too; the next promotion, which rewrites them, is enqueued
 // behind. It writes the map's own buffers, which nothing else touches (the count workspace is the map's, not vors_batch_point_cloud's).
 static void trackers_map_emit(vors_trackers* t, const Geom& gm, hipStream_t s) {
-    vors_batch* b = t->batch;
-    const bool dense = b->g.mode == VORS_CANDIDATES_DENSE;
-    PointCloudAppendCall call{{Pyramid{nullptr, nullptr}, Pyramid{dense ? t->own_gray.as<uint8_t>() : nullptr, b->kf_upper},
-                               dense ? t->own_depth.as<uint16_t>() : nullptr, b->rec}};
+    PointCloudAppendCall call{keyframe_scene(t)};
     call.n_seq = t->n_seq;
     call.lvl = t->map.level;
     call.kf_poses = t->kf_poses.as<float>();
@@ -185,9 +199,7 @@ static vors_status trackers_promote(vors_trackers* t, const uint8_t* d_gray, con
         // The OLD keyframes of the promoted sequences (records; dense mode: own_gray / own_depth; weights) splatted at the final models of
         // this frame's LM stage and merged with the measured depth. Everything the keyframe stage below overwrites is read here, before
         // it in stream order; the merge writes planes nothing here reads. From here on the fused map stands for d_depth.
-        const bool dense = b->g.mode == VORS_CANDIDATES_DENSE;
-        FuseDepthCall call{{Pyramid{nullptr, nullptr}, Pyramid{dense ? t->own_gray.as<uint8_t>() : nullptr, b->kf_upper},
-                            dense ? t->own_depth.as<uint16_t>() : nullptr, b->rec}};
+        FuseDepthCall call{keyframe_scene(t)};
         call.n_pairs = n;
         call.models = reinterpret_cast<const float*>(t->stats.p);  // (lm_model is the head of vors_pair_stats)
         call.model_stride = (int)(sizeof(vors_pair_stats) / 4);
@@ -320,12 +332,7 @@ static vors_status trackers_filter_enable(vors_trackers* t, float tol_m, int max
     b->own.alloc(&t->filter.fused, planes);
     b->own.alloc(&t->filter.weight, planes);
     b->own.alloc(&t->filter.stage_weight, planes);
-    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the filter stays off)
-        const hipError_t e = b->own.err;
-        b->own.err = hipSuccess;
-        (void)hipGetLastError();
-        return fail(VORS_ERR_HIP, std::string("hipMalloc (depth filter planes): ") + hipGetErrorString(e));
-    }
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "depth filter planes");
     t->filter.tol_m = tol_m;
     t->filter.max_weight = max_weight;
     t->filter.fill_min_weight = fill_min_weight;
@@ -355,12 +362,7 @@ static vors_status trackers_map_enable(vors_trackers* t, int level, int capacity
     b->own.alloc(&t->map.counts, n);
     b->own.alloc(&t->map.n_segments, n);
     b->own.alloc(&t->map.ws, n * (size_t)chunks);
-    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the map stays off)
-        const hipError_t e = b->own.err;
-        b->own.err = hipSuccess;
-        (void)hipGetLastError();
-        return fail(VORS_ERR_HIP, std::string("hipMalloc (keyframe map): ") + hipGetErrorString(e));
-    }
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "keyframe map");
     t->map.level = level;
     t->map.capacity = capacity;
     t->map.max_keyframes = max_keyframes;
@@ -386,12 +388,7 @@ static vors_status trackers_map_voxels_enable(vors_trackers* t, bool started, co
     b->own.alloc(&v.table, n * (size_t)table_slots * 2);
     b->own.alloc(&v.occupied, n);
     b->own.alloc(&v.overflow, n);
-    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the filter stays off)
-        const hipError_t e = b->own.err;
-        b->own.err = hipSuccess;
-        (void)hipGetLastError();
-        return fail(VORS_ERR_HIP, std::string("hipMalloc (voxel table of the keyframe map): ") + hipGetErrorString(e));
-    }
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "voxel table of the keyframe map");
     v.voxel_m = voxel_m;
     v.table_slots = table_slots;
     v.on = true;
@@ -412,12 +409,7 @@ static vors_status trackers_map_normals_enable(vors_trackers* t, bool started, c
     vors_trackers::Map::Normals& nm = t->map.normals;
     b->own.alloc(&nm.n, n * (size_t)t->map.capacity * 3);
     b->own.alloc(&nm.first, n);
-    if (b->own.err != hipSuccess) {  // (what was created stays with the handle's resources and is freed with it; the normals stay off)
-        const hipError_t e = b->own.err;
-        b->own.err = hipSuccess;
-        (void)hipGetLastError();
-        return fail(VORS_ERR_HIP, std::string("hipMalloc (normals of the keyframe map): ") + hipGetErrorString(e));
-    }
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "normals of the keyframe map");
     nm.step = step;
     nm.jump_m = jump_m;
     nm.on = true;
@@ -492,9 +484,7 @@ vors_status vors_tracker_enable_map_normals(vors_tracker* t, int step, float jum
     // Keyframe 0 is in the map already: its normals are the pass over every rank so far, in the plane keyframe 0 was made from — the
     // handle's copy (dense mode), the filter's copy, or t->depth, which still holds the first frame's depth map (the next upload waits for
     // ev_frame_done, which therefore moves behind this reader, as in vors_tracker_enable_depth_filter)
-    const uint16_t* depth = q->batch->g.mode == VORS_CANDIDATES_DENSE ? q->own_depth.as<uint16_t>()
-                            : q->filter.on                            ? q->filter.fused
-                                                                      : t->depth.as<uint16_t>();
+    const uint16_t* depth = (q->batch->g.mode == VORS_CANDIDATES_DENSE || q->filter.on) ? q->keyframe_depth() : t->depth.as<uint16_t>();
     HIP_TRY(hipMemsetAsync(q->map.normals.first, 0, sizeof(uint32_t), t->s_main));
     trackers_map_normals_pass(q, q->batch->g, depth, t->s_main);
     HIP_TRY(hipGetLastError());
