@@ -585,6 +585,23 @@ vors_status vors_batch_get_points(vors_batch* b, int pair, int level, int capaci
     return VORS_OK;
 }
 
+// The scene of a batch handle as the products' calls carry it: the keyframe side, and the current frame for the passes that read one.
+static LmScene batch_scene(const vors_batch* b, bool with_current) {
+    return LmScene{with_current ? Pyramid{b->cur_level0, b->cur_upper} : Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec};
+}
+
+// What a product of the keyframe side alone needs of the handle (reproject_depth, fuse_depth, point_cloud): no current image and no current
+// pyramid is read, so the pass is legal before any track_current. A product without a level argument passes 0.
+static vors_status check_keyframe_side(const char* who, const vors_batch* b, int n_pairs, int level) {
+    if (b->prepared_pairs <= 0 || !b->kf_level0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + (b->prepared_pairs > 0 ? " is not available on a trackers-owned batch (the handle keeps records, not frames)"
+                                                                                         : " needs prepare_keyframes first"));
+    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
+        return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
+    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": level out of range");
+    return VORS_OK;
+}
+
 // What an evaluation at an explicit model needs of the handle (pairs 0 .. last_pair of it) and of the request.
 static vors_status check_eval(const vors_batch* b, int last_pair, int level, int arithmetic) {
     if (last_pair < 0 || last_pair >= std::min(b->prepared_pairs, b->current_pairs) || level < 0 || level >= b->g.L)
@@ -607,7 +624,7 @@ vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const floa
     HIP_TRY(d_out.alloc(32 * sizeof(float)));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(d_model.p, model7, 7 * sizeof(float), hipMemcpyHostToDevice));
-    const EvalCall call{{Pyramid{b->cur_level0, b->cur_upper}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}, pair, level, d_model.as<float>(), d_out.as<float>()};
+    const EvalCall call{batch_scene(b, true), pair, level, d_model.as<float>(), d_out.as<float>()};
     if (arithmetic == VORS_ARITH_REFERENCE)  // sequential sums in the order of the handle's lists (column-major iff the handle itself is REFERENCE)
         launch_lm_eval_level_reference(b->g, call, nullptr);
     else if (arithmetic == VORS_ARITH_FUSED) launch_lm_eval_level_fused(b->g, call, nullptr);
@@ -629,12 +646,7 @@ static vors_status ensure_eval_pairs_ws(vors_batch* b) {
     if (!ws.partials) b->own.alloc(&ws.partials, (size_t)items * chunks * 32);
     if (!ws.fctx) b->own.alloc(&ws.fctx, (size_t)items);
     if (!ws.sums29) b->own.alloc(&ws.sums29, (size_t)b->max_pairs * 29);
-    if (b->own.err != hipSuccess) {
-        const hipError_t e = b->own.err;
-        b->own.err = hipSuccess;
-        (void)hipGetLastError();
-        return fail(VORS_ERR_HIP, std::string("hipMalloc (evaluation workspace): ") + hipGetErrorString(e));
-    }
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "evaluation workspace");
     ws.items = items;
     ws.chunks = chunks;
     return VORS_OK;
@@ -644,12 +656,12 @@ static vors_status batch_eval_pairs(vors_batch* b, int n_pairs, int level, int m
                                     int arithmetic, int what, float* d_sums29, hipStream_t s) {
     vors_status st = ensure_eval_pairs_ws(b);
     if (st != VORS_OK) return st;
-    EvalPairsCall call{{Pyramid{b->cur_level0, b->cur_upper}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    EvalPairsCall call{batch_scene(b, true)};
     call.n_items = n_pairs * models_per_pair;
     call.models_per_pair = models_per_pair;
     call.lvl = level;
     call.models = static_cast<const float*>(d_models);
-    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.model_stride = stride_words(model_stride_bytes, 7);
     call.energy_only = what == VORS_EVAL_ENERGY ? 1 : 0;
     call.out29 = d_sums29;
     call.ws = b->eval_pairs;
@@ -669,10 +681,9 @@ vors_status vors_batch_eval_pairs(vors_batch* b, int n_pairs, int level, int mod
     if (models_per_pair < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: models_per_pair must be >= 1");
     if ((long long)n_pairs * models_per_pair > 0x7fffffffLL / 32) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: n_pairs * models_per_pair is too large");
     if (what != VORS_EVAL_FULL && what != VORS_EVAL_ENERGY) return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: unknown `what` (VORS_EVAL_FULL or VORS_EVAL_ENERGY)");
-    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "eval_pairs: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    vors_status st = check_eval(b, n_pairs - 1, level, arithmetic);
+    vors_status st = stride_refusal("eval_pairs", "model_stride_bytes", model_stride_bytes, 28, BATCH_STRIDE_LIMIT);
     if (st != VORS_OK) return st;
+    if ((st = check_eval(b, n_pairs - 1, level, arithmetic)) != VORS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
     if ((st = check_stream(b, s)) != VORS_OK) return st;
@@ -684,10 +695,9 @@ vors_status vors_batch_pose_information(vors_batch* b, int n_pairs, int level, c
     if (!b) return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: the handle b is NULL");
     if (!d_models) return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: d_models is NULL");
     if (n_pairs < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: n_pairs must be >= 1");
-    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "pose_information: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    vors_status st = check_eval(b, n_pairs - 1, level, b->g.arith);
+    vors_status st = stride_refusal("pose_information", "model_stride_bytes", model_stride_bytes, 28, BATCH_STRIDE_LIMIT);
     if (st != VORS_OK) return st;
+    if ((st = check_eval(b, n_pairs - 1, level, b->g.arith)) != VORS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
     if ((st = check_stream(b, s)) != VORS_OK) return st;
@@ -706,18 +716,17 @@ vors_status vors_batch_residual_maps(vors_batch* b, int n_pairs, int level, cons
         return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: every output (d_residuals, d_warp_uv, d_hist, d_scale) is NULL");
     if (d_scale && !d_hist) return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: d_scale needs d_hist (the pass keeps no histogram of its own)");
     if (n_pairs < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: n_pairs must be >= 1");
-    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "residual_maps: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    vors_status st = check_eval(b, n_pairs - 1, level, VORS_ARITH_EXACT);
+    vors_status st = stride_refusal("residual_maps", "model_stride_bytes", model_stride_bytes, 28, BATCH_STRIDE_LIMIT);
     if (st != VORS_OK) return st;
+    if ((st = check_eval(b, n_pairs - 1, level, VORS_ARITH_EXACT)) != VORS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
     if ((st = check_stream(b, s)) != VORS_OK) return st;
-    ResidualMapsCall call{{Pyramid{b->cur_level0, b->cur_upper}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    ResidualMapsCall call{batch_scene(b, true)};
     call.n_pairs = n_pairs;
     call.lvl = level;
     call.models = static_cast<const float*>(d_models);
-    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.model_stride = stride_words(model_stride_bytes, 7);
     call.residuals = d_residuals;
     call.warp_uv = d_warp_uv;
     call.hist = d_hist;
@@ -740,24 +749,17 @@ vors_status vors_batch_reproject_depth(vors_batch* b, int n_pairs, int level, co
     if (d_cur_depth && level != 0)
         return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: d_cur_depth needs level 0 (depth maps exist at full resolution only)");
     if (!(tol_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: tol_m must be >= 0 (and not NaN)");
-    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    // the keyframe side alone: no current image, no current pyramid is read, so the pass is legal before any track_current
-    if (b->prepared_pairs <= 0 || !b->kf_level0)
-        return fail(VORS_ERR_INVALID_ARGUMENT, b->prepared_pairs > 0 ? "reproject_depth is not available on a trackers-owned batch (the handle keeps records, not frames)"
-                                                                     : "reproject_depth needs prepare_keyframes first");
-    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
-        return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
-    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "reproject_depth: level out of range");
+    vors_status st = stride_refusal("reproject_depth", "model_stride_bytes", model_stride_bytes, 28, BATCH_STRIDE_LIMIT);
+    if (st != VORS_OK) return st;
+    if ((st = check_keyframe_side("reproject_depth", b, n_pairs, level)) != VORS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
-    vors_status st = check_stream(b, s);
-    if (st != VORS_OK) return st;
-    ReprojectCall call{{Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    ReprojectCall call{batch_scene(b, false)};
     call.n_pairs = n_pairs;
     call.lvl = level;
     call.models = static_cast<const float*>(d_models);
-    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.model_stride = stride_words(model_stride_bytes, 7);
     call.cur_depth = d_cur_depth;
     call.tol_m = tol_m;
     call.pred_z = d_pred_z;
@@ -780,22 +782,16 @@ vors_status vors_batch_fuse_depth(vors_batch* b, int n_pairs, const void* d_mode
     if (!(tol_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: tol_m must be >= 0 (and not NaN)");
     if (max_weight < 1 || max_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: max_weight must be in 1..255");
     if (fill_min_weight < 0 || fill_min_weight > 255) return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: fill_min_weight must be in 0..255");
-    if (model_stride_bytes != 0 && (model_stride_bytes % 4 != 0 || model_stride_bytes < 28 || model_stride_bytes > (1u << 20)))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: model_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    // the keyframe side alone, like reproject_depth: legal before any track_current
-    if (b->prepared_pairs <= 0 || !b->kf_level0)
-        return fail(VORS_ERR_INVALID_ARGUMENT, b->prepared_pairs > 0 ? "fuse_depth is not available on a trackers-owned batch (the handle keeps records, not frames)"
-                                                                     : "fuse_depth needs prepare_keyframes first");
-    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
-        return fail(VORS_ERR_INVALID_ARGUMENT, "fuse_depth: n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
+    vors_status st = stride_refusal("fuse_depth", "model_stride_bytes", model_stride_bytes, 28, BATCH_STRIDE_LIMIT);
+    if (st != VORS_OK) return st;
+    if ((st = check_keyframe_side("fuse_depth", b, n_pairs, 0)) != VORS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
-    vors_status st = check_stream(b, s);
-    if (st != VORS_OK) return st;
-    FuseDepthCall call{{Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    FuseDepthCall call{batch_scene(b, false)};
     call.n_pairs = n_pairs;
     call.models = static_cast<const float*>(d_models);
-    call.model_stride = model_stride_bytes ? (int)(model_stride_bytes / 4) : 7;
+    call.model_stride = stride_words(model_stride_bytes, 7);
     call.cur_depth = d_cur_depth;
     call.tol_m = tol_m;
     call.kf_weight = d_kf_weight;
@@ -818,11 +814,8 @@ static vors_status ensure_point_cloud_ws(vors_batch* b) {
     for (int l = 0; l < b->g.L; ++l) chunks = std::max(chunks, eval_pairs_chunks(b->g, l));
     b->own.alloc(&b->cloud_counts, (size_t)b->max_pairs * chunks);
     if (b->own.err != hipSuccess) {
-        const hipError_t e = b->own.err;
-        b->own.err = hipSuccess;
-        (void)hipGetLastError();
         b->cloud_counts = nullptr;
-        return fail(VORS_ERR_HIP, std::string("hipMalloc (point-cloud workspace): ") + hipGetErrorString(e));
+        return own_alloc_failed(b, "point-cloud workspace");
     }
     b->cloud_chunks = chunks;
     return VORS_OK;
@@ -835,25 +828,18 @@ vors_status vors_batch_point_cloud(vors_batch* b, int n_pairs, int level, const 
     if (!lists && !d_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: every output (d_xyz, d_pixel, d_gray, d_counts) is NULL");
     if (capacity < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: negative capacity");
     if (lists && capacity == 0) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: d_xyz / d_pixel / d_gray need capacity > 0");
-    if (pose_stride_bytes != 0 && (pose_stride_bytes % 4 != 0 || pose_stride_bytes < 28 || pose_stride_bytes > (1u << 20)))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: pose_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    // the keyframe side alone, like reproject_depth: legal before any track_current
-    if (b->prepared_pairs <= 0 || !b->kf_level0)
-        return fail(VORS_ERR_INVALID_ARGUMENT, b->prepared_pairs > 0 ? "point_cloud is not available on a trackers-owned batch (the handle keeps records, not frames)"
-                                                                     : "point_cloud needs prepare_keyframes first");
-    if (n_pairs < 1 || n_pairs > b->prepared_pairs)
-        return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: n_pairs must be >= 1 and at most the n_pairs of the last prepare_keyframes");
-    if (level < 0 || level >= b->g.L) return fail(VORS_ERR_INVALID_ARGUMENT, "point_cloud: level out of range");
+    vors_status st = stride_refusal("point_cloud", "pose_stride_bytes", pose_stride_bytes, 28, BATCH_STRIDE_LIMIT);
+    if (st != VORS_OK) return st;
+    if ((st = check_keyframe_side("point_cloud", b, n_pairs, level)) != VORS_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
-    vors_status st = check_stream(b, s);
-    if (st != VORS_OK) return st;
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
     if ((st = ensure_point_cloud_ws(b)) != VORS_OK) return st;
-    PointCloudCall call{{Pyramid{nullptr, nullptr}, Pyramid{b->kf_level0, b->kf_upper}, b->kf_depth, b->rec}};
+    PointCloudCall call{batch_scene(b, false)};
     call.n_pairs = n_pairs;
     call.lvl = level;
     call.poses = static_cast<const float*>(d_poses7);
-    call.pose_stride = pose_stride_bytes ? (int)(pose_stride_bytes / 4) : 7;
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
     call.keep = d_keep;
     call.capacity = capacity;
     call.xyz = d_xyz;

@@ -31,6 +31,19 @@ inline vors_status require_device() {
     return VORS_OK;
 }
 
+// Record strides arrive in bytes; 0 asks for the packed record. The sentence is one, the upper limits are two: the batch products stop at
+// 1 MiB, the handle-free operators at what fits an int. They differ by history; making them one would change what is accepted.
+constexpr size_t BATCH_STRIDE_LIMIT = 1u << 20;
+constexpr size_t OPERATOR_STRIDE_LIMIT = 0x7fffffffu;
+inline vors_status stride_refusal(const char* who, const char* arg, size_t bytes, size_t min_bytes, size_t limit) {
+    if (bytes == 0 || (bytes % 4 == 0 && bytes >= min_bytes && bytes <= limit)) return VORS_OK;
+    return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": " + arg + " must be 0 or a multiple of 4 of at least " + std::to_string(min_bytes));
+}
+inline int stride_words(size_t bytes, int packed_words) { return bytes ? (int)(bytes / 4) : packed_words; }
+
+// cam5 of the C ABI: cu cv fu fv skew
+inline vors::Intr intr_from_cam5(const float cam5[5]) { return vors::Intr{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]}; }
+
 // Entry points run on the handle's device whatever the caller's current device is, and restore the caller's on exit.
 struct DeviceGuard {
     int prev = -1;
@@ -160,6 +173,15 @@ struct vors_batch {
     StageTimers timers;
     DeviceResources own;  // every device pointer, stream and event above that the handle created (destroy on the handle's device)
 };
+
+// Allocations from the handle's resources failed (own.err): what was created stays with them and is freed with the handle, the error is
+// cleared so that the handle stays usable, and whatever asked (a switch, a product's workspace) stays off. `what`: the noun of the message.
+inline vors_status own_alloc_failed(vors_batch* b, const char* what) {
+    const hipError_t e = b->own.err;
+    b->own.err = hipSuccess;
+    (void)hipGetLastError();
+    return fail(VORS_ERR_HIP, std::string("hipMalloc (") + what + "): " + hipGetErrorString(e));
+}
 
 // The stream work is enqueued on must belong to the handle's device (a stream of another device would silently run nothing useful).
 vors_status check_stream(const vors_batch* b, hipStream_t s);

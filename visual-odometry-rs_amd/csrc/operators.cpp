@@ -204,6 +204,13 @@ vors_status vors_fuse_depth_pixels(float depth_scale, float tol_m, int max_weigh
     return VORS_OK;
 }
 
+// The strides of the operators on point lists (vors_render_points, vors_depth_normals, vors_points_normals): one pose of 7 floats and one
+// (first, count) range of 2 u32 per list. What each entry says about the alignment of its pointers stays with it.
+static vors_status list_stride_refusals(const char* who, size_t pose_stride_bytes, size_t range_stride_bytes) {
+    vors_status st = stride_refusal(who, "pose_stride_bytes", pose_stride_bytes, 28, OPERATOR_STRIDE_LIMIT);
+    return st != VORS_OK ? st : stride_refusal(who, "range_stride_bytes", range_stride_bytes, 8, OPERATOR_STRIDE_LIMIT);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Rendering of point lists into a camera (vors_render_points, vors_render_points_host): the refusals both share, the device entry
 // (render_kernels.hip) and the host entry, which runs the kernels' own text (lie.h render_point, render_footprint, render_resolve).
@@ -232,10 +239,7 @@ vors_status vors_render_points(int n, const float* d_xyz, const uint8_t* d_list_
     if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: a list (d_list_counts) is NULL");
     vors_status st = render_refusals("render_points", d_xyz, d_list_gray, cam5, capacity, rows, cols, depth_scale, footprint, d_zkey);
     if (st != VORS_OK) return st;
-    if (pose_stride_bytes != 0 && (pose_stride_bytes < 28 || pose_stride_bytes % 4 != 0 || pose_stride_bytes > 0x7fffffffu))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: pose_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    if (range_stride_bytes != 0 && (range_stride_bytes < 8 || range_stride_bytes % 4 != 0 || range_stride_bytes > 0x7fffffffu))
-        return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: range_stride_bytes must be 0 or a multiple of 4 of at least 8");
+    if ((st = list_stride_refusals("render_points", pose_stride_bytes, range_stride_bytes)) != VORS_OK) return st;
     if ((uintptr_t)d_ranges % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "render_points: d_ranges must be 4-byte aligned");
     // the kernels read floats and u32 and write u16 and u32 through these: each at its natural alignment
     if ((uintptr_t)d_xyz % 4 != 0 || (uintptr_t)d_list_counts % 4 != 0 || (uintptr_t)d_poses7 % 4 != 0)
@@ -251,12 +255,12 @@ vors_status vors_render_points(int n, const float* d_xyz, const uint8_t* d_list_
     call.capacity = capacity;
     call.ranges = static_cast<const uint8_t*>(d_ranges);
     call.range_stride = range_stride_bytes ? (int)range_stride_bytes : 8;
-    call.k = Intr{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    call.k = intr_from_cam5(cam5);
     call.rows = rows;
     call.cols = cols;
     call.depth_scale = depth_scale;
     call.poses = static_cast<const float*>(d_poses7);
-    call.pose_stride = pose_stride_bytes ? (int)(pose_stride_bytes / 4) : 7;
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
     call.footprint = footprint;
     call.zkey = d_zkey;
     call.depth = d_depth;
@@ -272,7 +276,7 @@ vors_status vors_render_points_host(const float* xyz, const uint8_t* list_gray, 
                                     uint16_t* depth, uint8_t* gray, uint32_t counts[VORS_RENDER_COUNTS]) {
     vors_status st = render_refusals("render_points_host", xyz, list_gray, cam5, capacity, rows, cols, depth_scale, footprint, zkey);
     if (st != VORS_OK) return st;
-    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    const Intr k = intr_from_cam5(cam5);
     Iso pose = iso_identity();
     if (pose7) pose = iso_load(pose7);
     const size_t plane = (size_t)rows * (size_t)cols;
@@ -335,13 +339,10 @@ static vors_status normal_refusals(const char* who, const void* depth, const flo
 }
 static vors_status normal_stride_refusals(const char* who, const void* d_poses7, size_t pose_stride_bytes, const void* d_ranges,
                                           size_t range_stride_bytes) {
-    const std::string w(who);
-    if (pose_stride_bytes != 0 && (pose_stride_bytes < 28 || pose_stride_bytes % 4 != 0 || pose_stride_bytes > 0x7fffffffu))
-        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": pose_stride_bytes must be 0 or a multiple of 4 of at least 28");
-    if (range_stride_bytes != 0 && (range_stride_bytes < 8 || range_stride_bytes % 4 != 0 || range_stride_bytes > 0x7fffffffu))
-        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": range_stride_bytes must be 0 or a multiple of 4 of at least 8");
+    vors_status st = list_stride_refusals(who, pose_stride_bytes, range_stride_bytes);
+    if (st != VORS_OK) return st;
     if ((uintptr_t)d_ranges % 4 != 0 || (uintptr_t)d_poses7 % 4 != 0)
-        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_ranges and d_poses7 must be 4-byte aligned");
+        return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": d_ranges and d_poses7 must be 4-byte aligned");
     return VORS_OK;
 }
 static NormalCall normal_call(int n, const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, int step, float jump_m,
@@ -349,14 +350,14 @@ static NormalCall normal_call(int n, const uint16_t* d_depth, const float cam5[5
     NormalCall call{};
     call.n = n;
     call.depth = d_depth;
-    call.k = Intr{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    call.k = intr_from_cam5(cam5);
     call.rows = rows;
     call.cols = cols;
     call.depth_scale = depth_scale;
     call.step = step;
     call.jump_m = jump_m;
     call.poses = static_cast<const float*>(d_poses7);
-    call.pose_stride = pose_stride_bytes ? (int)(pose_stride_bytes / 4) : 7;
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
     call.normals = d_normals;
     call.counts = d_counts;
     return call;
@@ -406,7 +407,7 @@ vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], 
     vors_status st =
         normal_refusals("depth_normals_host", depth, cam5, rows, cols, depth_scale, step, jump_m, list, pixel, capacity, normals, counts);
     if (st != VORS_OK) return st;
-    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    const Intr k = intr_from_cam5(cam5);
     Iso pose = iso_identity();
     if (pose7) pose = iso_load(pose7);
     uint32_t c[VORS_NORMAL_COUNTS] = {0, 0, 0};
@@ -470,7 +471,7 @@ void vors_from_depth(float scale, const uint16_t* depth, int n, float* idepth_ou
 // Camera::back_project / Camera::project (camera.rs:43-45, 36-39) for arrays: the texts the point-cloud kernel runs (lie.h back_project,
 // iso_transform_point). A NULL pose is the identity and skips the transform, so the camera-frame bits come out untouched.
 void vors_camera_back_project(const float cam5[5], const float pose7[7], const float* xy, const float* depth, int n, float* xyz_out) {
-    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    const Intr k = intr_from_cam5(cam5);
     for (int i = 0; i < n; ++i) {
         V3 p = back_project(k, xy[2 * i], xy[2 * i + 1], depth[i]);
         if (pose7) p = iso_transform_point(iso_load(pose7), p);
@@ -484,7 +485,7 @@ void vors_voxel_keys(float voxel_m, const float* xyz, int n, uint64_t* keys_out)
     for (int i = 0; i < n; ++i) keys_out[i] = ok ? voxel_key(voxel_m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]) : VORS_VOXEL_NONE;
 }
 void vors_camera_project(const float cam5[5], const float pose7[7], const float* xyz, int n, float* uvw_out) {
-    const Intr k{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    const Intr k = intr_from_cam5(cam5);
     for (int i = 0; i < n; ++i) {
         V3 p{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
         if (pose7) p = extr_project(iso_load(pose7), p);

@@ -84,14 +84,6 @@ static LmScene keyframe_scene(vors_trackers* t) {
     return LmScene{Pyramid{nullptr, nullptr}, Pyramid{dense ? t->own_gray.as<uint8_t>() : nullptr, b->kf_upper},
                    dense ? t->own_depth.as<uint16_t>() : nullptr, b->rec};
 }
-// A switch whose allocations from the handle's resources failed: what was created stays with them and is freed with the handle, the
-// switch stays off. `what`: the noun of the message.
-static vors_status own_alloc_failed(vors_batch* b, const char* what) {
-    const hipError_t e = b->own.err;
-    b->own.err = hipSuccess;
-    (void)hipGetLastError();
-    return fail(VORS_ERR_HIP, std::string("hipMalloc (") + what + "): " + hipGetErrorString(e));
-}
 
 // The cloud of the NEW keyframe of every selected sequence (gm.sel_list; null: all) appended to its map. Hazards, all settled by the
 // stream: the emission reads the records, own_gray / own_depth / kf_upper (dense mode) and the filter's weight plane AFTER everything that

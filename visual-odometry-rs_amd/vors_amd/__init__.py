@@ -280,6 +280,30 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _asked(o):
+    """An output argument that may also be a tensor to write into: anything but False / None asks for the output."""
+    return o is not False and o is not None
+
+
+def _out_buf(o, shape, dtype, dev, always=False):
+    """The tensor behind an output argument: True = a new one, a tensor = that one after a check of dtype, shape and contiguity, False /
+    None = not wanted (always: made all the same, for a plane the pass needs)."""
+    import torch
+    if o is True or (always and not _asked(o)):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not _asked(o):
+        return None
+    if o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shape):
+        raise VorsError(f"expected a contiguous {dtype} output {tuple(shape)}, got {o.dtype} {tuple(o.shape)}")
+    return o
+
+
+def _result(*items):
+    """(name, kept, tensor) per output -> the dict a product returns: the kept ones. `kept` is the caller's own test of its argument: the
+    argument itself where it is a flag, _asked() of it where it may be a tensor."""
+    return {name: t for name, kept, t in items if kept}
+
+
 # ----------------------------------------------------------------------------------------------- reference mirror
 class Intrinsics:
     """src/core/camera.rs:84-91."""
@@ -332,28 +356,58 @@ class Config:
         return Tracker(self, keyframe_depth_timestamp, depth_map, keyframe_img_timestamp, img, layout)
 
 
-def _depth_filter_args(spec):
-    """None, a number or a tuple (tol_m[, max_weight[, fill_min_weight]]) -> None or (float, int, int) with the defaults filled in. Only
-    the SHAPE of the argument is judged here; the values are judged by the library, in one place for every caller."""
+_REQUIRED = object()
+
+
+def _spec_args(switch, fields, spec, scalar=False, lenient=False):
+    """The one parser of the switches' tuples. fields: (name, int or float, default or _REQUIRED) per value, in order. None -> None, else
+    the typed values with the defaults filled in. Only the SHAPE of the argument is judged here; the values are judged by the library, in
+    one place for every caller. scalar: a bare number stands for (number,). lenient (depth_filter, kept as it always was): the integers are
+    not held to the range of a C int, and the numbers are converted with float(), after the integers, rather than tested by type."""
     if spec is None:
         return None
-    if isinstance(spec, (int, float, np.integer, np.floating)) and not isinstance(spec, bool):
+    names = [f[0] for f in fields]
+    lo, hi = sum(f[2] is _REQUIRED for f in fields), len(fields)
+    sig = "(" + ", ".join(names[:lo]) + "".join(f"[, {n}" for n in names[lo:]) + "]" * (hi - lo) + ")"
+    if scalar and isinstance(spec, (int, float, np.integer, np.floating)) and not isinstance(spec, bool):
         spec = (spec,)
     try:
         spec = tuple(spec)
     except TypeError:
-        raise VorsError(f"depth_filter: expected None or (tol_m[, max_weight[, fill_min_weight]]), got {spec!r}") from None
-    if not 1 <= len(spec) <= 3:
-        raise VorsError(f"depth_filter: expected 1 to 3 values (tol_m[, max_weight[, fill_min_weight]]), got {len(spec)}")
-    tol_m, max_weight, fill_min_weight = (spec + (255, 0)[len(spec) - 1:])[:3]
-    for name, v in (("max_weight", max_weight), ("fill_min_weight", fill_min_weight)):
+        raise VorsError(f"{switch}: expected None or {sig}, got {spec!r}") from None
+    if not lo <= len(spec) <= hi:
+        count = str(lo) if lo == hi else f"{lo} or {hi}" if hi == lo + 1 else f"{lo} to {hi}"
+        raise VorsError(f"{switch}: expected {count} values {sig}, got {len(spec)}")
+    out = list(spec) + [f[2] for f in fields[len(spec):]]
+
+    def integer(name, v):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise VorsError(f"depth_filter: {name} must be an integer, got {v!r}")
-    try:
-        tol_m = float(tol_m)
-    except (TypeError, ValueError):
-        raise VorsError(f"depth_filter: tol_m must be a number, got {tol_m!r}") from None
-    return tol_m, int(max_weight), int(fill_min_weight)
+            raise VorsError(f"{switch}: {name} must be an integer, got {v!r}")
+        if not lenient and not -2 ** 31 <= int(v) < 2 ** 31:
+            raise VorsError(f"{switch}: {name} does not fit the C int it is passed as, got {v!r}")
+        return int(v)
+
+    def number(name, v):
+        if lenient:
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                pass
+        elif not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)):
+            return float(v)
+        raise VorsError(f"{switch}: {name} must be a number, got {v!r}") from None
+
+    for kinds in ((int,), (float,)) if lenient else ((int, float),):
+        for i, (name, kind, _) in enumerate(fields):
+            if kind in kinds:
+                out[i] = integer(name, out[i]) if kind is int else number(name, out[i])
+    return tuple(out)
+
+
+def _depth_filter_args(spec):
+    """None, a number or (tol_m[, max_weight[, fill_min_weight]]) -> None or (float, int, int)."""
+    return _spec_args("depth_filter", (("tol_m", float, _REQUIRED), ("max_weight", int, 255), ("fill_min_weight", int, 0)), spec, scalar=True,
+                      lenient=True)
 
 
 class vors_map_segment(C.Structure):
@@ -371,65 +425,18 @@ def decode_map_segments(segments):
 
 
 def _map_args(spec):
-    """None or a tuple (level, capacity, max_keyframes[, min_weight]) -> None or four ints with the default filled in. Only the SHAPE of
-    the argument is judged here; the values are judged by the library, in one place for every caller."""
-    if spec is None:
-        return None
-    try:
-        spec = tuple(spec)
-    except TypeError:
-        raise VorsError(f"map: expected None or (level, capacity, max_keyframes[, min_weight]), got {spec!r}") from None
-    if not 3 <= len(spec) <= 4:
-        raise VorsError(f"map: expected 3 or 4 values (level, capacity, max_keyframes[, min_weight]), got {len(spec)}")
-    spec = (spec + (0,))[:4]
-    for name, v in zip(("level", "capacity", "max_keyframes", "min_weight"), spec):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise VorsError(f"map: {name} must be an integer, got {v!r}")
-        if not -2 ** 31 <= int(v) < 2 ** 31:
-            raise VorsError(f"map: {name} does not fit the C int it is passed as, got {v!r}")
-    return tuple(int(v) for v in spec)
+    """None or (level, capacity, max_keyframes[, min_weight]) -> None or four ints."""
+    return _spec_args("map", (("level", int, _REQUIRED), ("capacity", int, _REQUIRED), ("max_keyframes", int, _REQUIRED), ("min_weight", int, 0)), spec)
 
 
 def _map_voxels_args(spec):
-    """None or a pair (voxel_m, table_slots) -> None or (float, int). Only the SHAPE of the argument is judged here; the values (a finite
-    voxel_m > 0, table_slots a power of two in 64..2^30) are judged by the library, in one place for every caller."""
-    if spec is None:
-        return None
-    try:
-        spec = tuple(spec)
-    except TypeError:
-        raise VorsError(f"map_voxels: expected None or (voxel_m, table_slots), got {spec!r}") from None
-    if len(spec) != 2:
-        raise VorsError(f"map_voxels: expected 2 values (voxel_m, table_slots), got {len(spec)}")
-    voxel_m, table_slots = spec
-    if isinstance(voxel_m, bool) or not isinstance(voxel_m, (int, float, np.integer, np.floating)):
-        raise VorsError(f"map_voxels: voxel_m must be a number, got {voxel_m!r}")
-    if isinstance(table_slots, bool) or not isinstance(table_slots, (int, np.integer)):
-        raise VorsError(f"map_voxels: table_slots must be an integer, got {table_slots!r}")
-    if not -2 ** 31 <= int(table_slots) < 2 ** 31:
-        raise VorsError(f"map_voxels: table_slots does not fit the C int it is passed as, got {table_slots!r}")
-    return float(voxel_m), int(table_slots)
+    """None or (voxel_m, table_slots) -> None or (float, int); the library wants a finite voxel_m > 0 and a power of two in 64..2^30."""
+    return _spec_args("map_voxels", (("voxel_m", float, _REQUIRED), ("table_slots", int, _REQUIRED)), spec)
 
 
 def _map_normals_args(spec):
-    """None or a pair (step, jump_m) -> None or (int, float). Only the SHAPE of the argument is judged here; the values (step in 1..8,
-    jump_m >= 0) are judged by the library, in one place for every caller."""
-    if spec is None:
-        return None
-    try:
-        spec = tuple(spec)
-    except TypeError:
-        raise VorsError(f"map_normals: expected None or (step, jump_m), got {spec!r}") from None
-    if len(spec) != 2:
-        raise VorsError(f"map_normals: expected 2 values (step, jump_m), got {len(spec)}")
-    step, jump_m = spec
-    if isinstance(step, bool) or not isinstance(step, (int, np.integer)):
-        raise VorsError(f"map_normals: step must be an integer, got {step!r}")
-    if not -2 ** 31 <= int(step) < 2 ** 31:
-        raise VorsError(f"map_normals: step does not fit the C int it is passed as, got {step!r}")
-    if isinstance(jump_m, bool) or not isinstance(jump_m, (int, float, np.integer, np.floating)):
-        raise VorsError(f"map_normals: jump_m must be a number, got {jump_m!r}")
-    return int(step), float(jump_m)
+    """None or (step, jump_m) -> None or (int, float); the library wants step in 1..8 and jump_m >= 0."""
+    return _spec_args("map_normals", (("step", int, _REQUIRED), ("jump_m", float, _REQUIRED)), spec)
 
 
 VOXEL_NONE = 0xFFFFFFFFFFFFFFFF
@@ -773,6 +780,14 @@ class Batch:
             raise VorsError(f"expected float32 models [n, 7] or [n, K, 7], got {models.dtype} {tuple(models.shape)}")
         return models, models.shape[0], (models.shape[1] if models.dim() == 3 else 1), 0
 
+    @staticmethod
+    def _one_per_pair(models, refusal):
+        """_models_arg for the products that take ONE model (pose) per pair -> (tensor, n, stride in bytes)."""
+        models, n, k, stride = Batch._models_arg(models)
+        if k != 1:
+            raise VorsError(refusal)
+        return models, n, stride
+
     EVAL_WHAT = {"full": 0, "energy": 1}
 
     def eval_pairs(self, level, models, arithmetic=None, what="full", out=None):
@@ -795,9 +810,7 @@ class Batch:
         """Information matrix, covariance of the twist, residual variance and flags of every pair at `models` ([n, 7] or a track's out_stats)
         in the handle's arithmetic (vors_batch_pose_information) -> (info [n, 6, 6], cov [n, 6, 6], sigma2 [n], flags [n]), not synchronised."""
         import torch
-        models, n, k, stride = self._models_arg(models)
-        if k != 1:
-            raise VorsError("pose_information takes one model per pair")
+        models, n, stride = self._one_per_pair(models, "pose_information takes one model per pair")
         info = torch.empty((n, 6, 6), dtype=torch.float32, device=models.device)
         cov = torch.empty((n, 6, 6), dtype=torch.float32, device=models.device)
         sigma2 = torch.empty(n, dtype=torch.float32, device=models.device)
@@ -813,9 +826,7 @@ class Batch:
         ((u, v) of every usable candidate, NaN elsewhere), "hist" [n, 256] (int32 view of the counts of min(int(|r|), 255)), "scale" [n, 2]
         (median |r|, 1.4826 median |r|; computed from the histogram, which is made for it when `hist` is not asked for)."""
         import torch
-        models, n, k, stride = self._models_arg(models)
-        if k != 1:
-            raise VorsError("residual_maps takes one model per pair")
+        models, n, stride = self._one_per_pair(models, "residual_maps takes one model per pair")
         if not (residuals or warp or hist or scale):
             raise VorsError("residual_maps: nothing requested")
         rows, cols = self.rows >> int(level), self.cols >> int(level)
@@ -826,16 +837,7 @@ class Batch:
         t_scale = torch.empty((n, 2), dtype=torch.float32, device=dev) if scale else None
         _check(lib().vors_batch_residual_maps(self._h, n, int(level), self._dp(models), stride, self._dp(t_res), self._dp(t_uv), self._dp(t_hist),
                                               self._dp(t_scale), self._stream()))
-        out = {}
-        if residuals:
-            out["residuals"] = t_res
-        if warp:
-            out["warp"] = t_uv
-        if hist:
-            out["hist"] = t_hist
-        if scale:
-            out["scale"] = t_scale
-        return out
+        return _result(("residuals", residuals, t_res), ("warp", warp, t_uv), ("hist", hist, t_hist), ("scale", scale, t_scale))
 
     def reproject_depth(self, level, models, cur_depth=None, tol_m=0.0, pred_z=True, pred_depth=False, residual=False, counts=False):
         """The keyframe's depth carried into the current frame at `models` ([n, 7] or a track's out_stats) with a z-buffer, and compared with
@@ -846,9 +848,7 @@ class Batch:
         [n, rows, cols] (keyframe geometry: Z' - cur_depth / depth_scale, NaN elsewhere), "counts" [n, 4] (int32: usable points, points
         that land, those with a current depth, those with |residual| <= tol_m)."""
         import torch
-        models, n, k, stride = self._models_arg(models)
-        if k != 1:
-            raise VorsError("reproject_depth takes one model per pair")
+        models, n, stride = self._one_per_pair(models, "reproject_depth takes one model per pair")
         if not (pred_z or pred_depth or residual or counts):
             raise VorsError("reproject_depth: nothing requested")
         if cur_depth is not None and (cur_depth.dtype != torch.int16 or not cur_depth.is_contiguous() or
@@ -862,16 +862,7 @@ class Batch:
         t_cnt = torch.empty((n, 4), dtype=torch.int32, device=dev) if counts else None
         _check(lib().vors_batch_reproject_depth(self._h, n, int(level), self._dp(models), stride, self._dp(cur_depth), float(tol_m), self._dp(t_z),
                                                 self._dp(t_d), self._dp(t_res), self._dp(t_cnt), self._stream()))
-        out = {}
-        if pred_z:
-            out["pred_z"] = t_z
-        if pred_depth:
-            out["pred_depth"] = t_d
-        if residual:
-            out["residual"] = t_res
-        if counts:
-            out["counts"] = t_cnt
-        return out
+        return _result(("pred_z", pred_z, t_z), ("pred_depth", pred_depth, t_d), ("residual", residual, t_res), ("counts", counts, t_cnt))
 
     def point_cloud(self, level, poses=None, keep=None, capacity=None, xyz=True, pixel=True, gray=False, counts=True, n_pairs=None):
         """The usable points of `level` of every pair as lists in the world frame (vors_batch_point_cloud; needs prepare_keyframes only) ->
@@ -886,9 +877,7 @@ class Batch:
         rows, cols = self.rows >> lvl, self.cols >> lvl
         stride = 0
         if poses is not None:
-            poses, n, k, stride = self._models_arg(poses)
-            if k != 1:
-                raise VorsError("point_cloud takes one pose per pair")
+            poses, n, stride = self._one_per_pair(poses, "point_cloud takes one pose per pair")
         elif keep is not None:
             n = keep.shape[0]
         else:
@@ -903,32 +892,18 @@ class Batch:
         if keep is not None and (keep.dtype != torch.uint8 or not keep.is_contiguous() or keep.shape[0] < n or tuple(keep.shape[1:]) != (rows, cols)):
             raise VorsError(f"expected a contiguous uint8 keep [{n}, {rows}, {cols}], got {keep.dtype} {tuple(keep.shape)}")
         cap = rows * cols if capacity is None else int(capacity)
-        lists = any(o is not False and o is not None for o in (xyz, pixel, gray))
-        if not lists and (counts is False or counts is None):
+        if not any(_asked(o) for o in (xyz, pixel, gray, counts)):
             raise VorsError("point_cloud: nothing requested")
         refs = getattr(self, "_kf_refs", None)
         dev = poses.device if poses is not None else keep.device if keep is not None else refs[0].device if refs else torch.device("cuda")
 
-        def buf(o, shape, dtype):
-            if o is False or o is None:
-                return None
-            if o is True:
-                return torch.empty(shape, dtype=dtype, device=dev)
-            if o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shape):
-                raise VorsError(f"expected a contiguous {dtype} output {tuple(shape)}, got {o.dtype} {tuple(o.shape)}")
-            return o
-
-        t_xyz = buf(xyz, (n, cap, 3), torch.float32)
-        t_pix = buf(pixel, (n, cap), torch.int32)
-        t_gray = buf(gray, (n, cap), torch.uint8)
-        t_cnt = buf(counts, (n,), torch.int32)
+        t_xyz = _out_buf(xyz, (n, cap, 3), torch.float32, dev)
+        t_pix = _out_buf(pixel, (n, cap), torch.int32, dev)
+        t_gray = _out_buf(gray, (n, cap), torch.uint8, dev)
+        t_cnt = _out_buf(counts, (n,), torch.int32, dev)
         _check(lib().vors_batch_point_cloud(self._h, n, lvl, self._dp(poses), stride, self._dp(keep), cap, self._dp(t_xyz), self._dp(t_pix),
                                             self._dp(t_gray), self._dp(t_cnt), self._stream()))
-        out = {}
-        for name, t in (("xyz", t_xyz), ("pixel", t_pix), ("gray", t_gray), ("counts", t_cnt)):
-            if t is not None:
-                out[name] = t
-        return out
+        return _result(("xyz", _asked(xyz), t_xyz), ("pixel", _asked(pixel), t_pix), ("gray", _asked(gray), t_gray), ("counts", _asked(counts), t_cnt))
 
     def fuse_depth(self, models, cur_depth, tol_m, kf_weight=None, max_weight=255, fill_min_weight=0, depth=True, weight=True, zkey=False,
                    counts=False):
@@ -940,9 +915,7 @@ class Batch:
         "counts" [n, 6] (int32: agree, prediction in front, prediction behind, measured only, filled, empty). `kf_weight` [n, rows, cols]
         uint8 in keyframe geometry: None = 1 everywhere, 0 removes the point. The key plane is made when it is not asked for."""
         import torch
-        models, n, k, stride = self._models_arg(models)
-        if k != 1:
-            raise VorsError("fuse_depth takes one model per pair")
+        models, n, stride = self._one_per_pair(models, "fuse_depth takes one model per pair")
         shape = (n, self.rows, self.cols)
         if cur_depth is None or cur_depth.dtype != torch.int16 or not cur_depth.is_contiguous() or tuple(cur_depth.shape) != shape:
             raise VorsError(f"expected a contiguous int16 cur_depth {list(shape)}")
@@ -958,11 +931,7 @@ class Batch:
         _check(lib().vors_batch_fuse_depth(self._h, n, self._dp(models), stride, self._dp(cur_depth), float(tol_m), self._dp(kf_weight),
                                            int(max_weight), int(fill_min_weight), self._dp(t_key), self._dp(t_d), self._dp(t_w),
                                            self._dp(t_cnt), self._stream()))
-        out = {}
-        for name, want, t in (("depth", depth, t_d), ("weight", weight, t_w), ("zkey", zkey, t_key), ("counts", counts, t_cnt)):
-            if want:
-                out[name] = t
-        return out
+        return _result(("depth", depth, t_d), ("weight", weight, t_w), ("zkey", zkey, t_key), ("counts", counts, t_cnt))
 
     def keyframe_image(self, pair, level):
         out = np.empty(self.rows * self.cols, np.uint8)
@@ -1390,9 +1359,10 @@ def _render_poses(poses, n):
     """poses [n, 7] float32 or a track's out_stats bytes, or None -> (tensor, stride in bytes)."""
     if poses is None:
         return None, 0
-    poses, m, k, stride = Batch._models_arg(poses)
-    if k != 1 or m < n:
-        raise VorsError(f"render: expected one pose for each of the {n} lists")
+    refusal = f"render: expected one pose for each of the {n} lists"
+    poses, m, stride = Batch._one_per_pair(poses, refusal)
+    if m < n:
+        raise VorsError(refusal)
     return poses, stride
 
 
@@ -1413,28 +1383,14 @@ def _render_ranges(ranges, n):
 
 
 def _render_outputs(shape, dev, zkey, depth, gray, counts):
-    """True = a new tensor, a tensor = write into it, False / None = not wanted (the key plane is made all the same)."""
+    """The output arguments of a rendering (_out_buf) -> (zkey, depth, gray, counts); the key plane is made all the same."""
     import torch
-
-    def buf(o, shp, dtype, always=False):
-        if o is False or o is None:
-            return torch.empty(shp, dtype=dtype, device=dev) if always else None
-        if o is True:
-            return torch.empty(shp, dtype=dtype, device=dev)
-        if o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shp):
-            raise VorsError(f"expected a contiguous {dtype} output {tuple(shp)}, got {o.dtype} {tuple(o.shape)}")
-        return o
-
-    return (buf(zkey, shape, torch.int64, always=True), buf(depth, shape, torch.int16), buf(gray, shape, torch.uint8),
-            buf(counts, (shape[0], RENDER_COUNTS), torch.int32))
+    return (_out_buf(zkey, shape, torch.int64, dev, always=True), _out_buf(depth, shape, torch.int16, dev), _out_buf(gray, shape, torch.uint8, dev),
+            _out_buf(counts, (shape[0], RENDER_COUNTS), torch.int32, dev))
 
 
 def _render_result(bufs, zkey, depth, gray, counts):
-    out = {}
-    for name, want, t in zip(("zkey", "depth", "gray", "counts"), (zkey, depth, gray, counts), bufs):
-        if want is not False and want is not None:
-            out[name] = t
-    return out
+    return _result(*((name, _asked(want), t) for name, want, t in zip(("zkey", "depth", "gray", "counts"), (zkey, depth, gray, counts), bufs)))
 
 
 def render_points(xyz, list_gray, list_counts, cam5, rows, cols, depth_scale, poses=None, ranges=None, footprint=1, depth=True, gray=True,
@@ -1492,19 +1448,9 @@ def _normals_common(cam5, who):
 
 
 def _normals_outputs(shape3, dev, normals, counts):
-    """True = a new tensor, a tensor = write into it, False / None = not wanted."""
+    """The output arguments of a normals pass (_out_buf) -> (normals, counts)."""
     import torch
-    out = []
-    for o, shp, dtype in ((normals, shape3, torch.float32), (counts, (shape3[0], NORMAL_COUNTS), torch.int32)):
-        if o is False or o is None:
-            out.append(None)
-        elif o is True:
-            out.append(torch.empty(shp, dtype=dtype, device=dev))
-        elif o.dtype != dtype or not o.is_contiguous() or tuple(o.shape) != tuple(shp):
-            raise VorsError(f"expected a contiguous {dtype} output {tuple(shp)}, got {o.dtype} {tuple(o.shape)}")
-        else:
-            out.append(o)
-    return out
+    return _out_buf(normals, shape3, torch.float32, dev), _out_buf(counts, (shape3[0], NORMAL_COUNTS), torch.int32, dev)
 
 
 def depth_normals(depth, cam5, depth_scale, step, jump_m, poses=None, normals=True, counts=False):
@@ -1522,7 +1468,7 @@ def depth_normals(depth, cam5, depth_scale, step, jump_m, poses=None, normals=Tr
     o_n, o_c = _normals_outputs((n, rows, cols, 3), depth.device, normals, counts)
     _check(lib().vors_depth_normals(n, Batch._dp(depth), _ptr(k), rows, cols, float(depth_scale), int(step), float(jump_m), Batch._dp(poses),
                                     pose_stride, Batch._dp(o_n), Batch._dp(o_c), Batch._stream()))
-    return {name: t for name, t in (("normals", o_n), ("counts", o_c)) if t is not None}
+    return _result(("normals", _asked(normals), o_n), ("counts", _asked(counts), o_c))
 
 
 def points_normals(depth, pixel, list_counts, cam5, depth_scale, step, jump_m, poses=None, ranges=None, normals=True, counts=False):
@@ -1547,7 +1493,7 @@ def points_normals(depth, pixel, list_counts, cam5, depth_scale, step, jump_m, p
     _check(lib().vors_points_normals(n, Batch._dp(depth), Batch._dp(pixel), Batch._dp(list_counts), cap, rng, range_stride, _ptr(k), rows, cols,
                                      float(depth_scale), int(step), float(jump_m), Batch._dp(poses), pose_stride, Batch._dp(o_n),
                                      Batch._dp(o_c), Batch._stream()))
-    return {name: t for name, t in (("normals", o_n), ("counts", o_c)) if t is not None}
+    return _result(("normals", _asked(normals), o_n), ("counts", _asked(counts), o_c))
 
 
 def depth_normals_host(depth, cam5, depth_scale, step, jump_m, pose7=None, pixel=None, count=None, range2=None, normals=None):
