@@ -70,12 +70,12 @@ def check(tol_m, key, d, kf_weight=None, max_weight=255, fill_min_weight=0, scal
     return depth.ravel(), weight.ravel(), case, counts
 
 
-def random_pixels(rng, n, n_kf):
+def random_pixels(rng, n, n_kf, scale=SCALE):
     """Depths over the whole range (0, 1 and 65535 among them), predictions near the measurement, far from it, and missing."""
     d = rng.integers(1, 65536, n).astype(np.uint16)
     d[rng.random(n) < 0.25] = 0
     d[:8] = [1, 1, 65535, 65535, 1, 65535, 0, 0]
-    near = d.astype(F32) / F32(SCALE) + rng.normal(0, 0.012, n).astype(F32)
+    near = d.astype(F32) / F32(scale) + rng.normal(0, 0.012, n).astype(F32)
     far = rng.uniform(0.05, 14.0, n).astype(F32)
     z = np.where(rng.random(n) < 0.6, near, far).astype(F32)
     z = np.where((z > 0) & (d != 0), z, far).astype(F32)

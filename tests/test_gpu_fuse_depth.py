@@ -52,11 +52,11 @@ def fuse_all(b, models, cd, tol=TOL_M, **kw):
     return host(out)
 
 
-def assert_exact_against_host_entry(m, cd_host, w_host, tol, max_weight=255, fill=0, what=""):
+def assert_exact_against_host_entry(m, cd_host, w_host, tol, max_weight=255, fill=0, what="", scale=SCALE):
     """Case 3 for a whole result: every pair's maps and counters from the device's own keys."""
     n, rows, cols = m["zkey"].shape
     for p in range(n):
-        depth, weight, counts = V.fuse_depth_pixels(SCALE, tol, m["zkey"][p], cd_host[p], None if w_host is None else w_host[p], max_weight, fill)
+        depth, weight, counts = V.fuse_depth_pixels(scale, tol, m["zkey"][p], cd_host[p], None if w_host is None else w_host[p], max_weight, fill)
         assert (m["depth"][p] == depth).all() and (m["weight"][p] == weight).all(), (what, p)
         assert m["counts"][p].tolist() == counts.tolist() and int(m["counts"][p].sum()) == rows * cols, (what, p, m["counts"][p], counts)
         assert ((m["depth"][p] == 0) == (m["weight"][p] == 0)).all(), (what, p)
@@ -69,7 +69,11 @@ def config(intr, L, mode, arith=None):
 
 @pytest.fixture(scope="module", params=PARAMS, ids=lambda p: f"{p[0][1]}x{p[0][0]}L{p[0][2]}-{('c2f', 'dense', 'dso')[p[1]]}-{p[2]}")
 def scene(request):
-    sc = Scene(*request.param)
+    return with_weights_and_holes(Scene(*request.param))
+
+
+def with_weights_and_holes(sc):
+    """A Scene + a keyframe weight plane with zeros in it and a measured depth with holes."""
     rng = np.random.default_rng(17)
     import torch
     w = rng.integers(1, 9, (N, sc.rows, sc.cols)).astype(np.uint8)
@@ -150,19 +154,22 @@ def test_tie_break_smallest_source_index():
 
 # ------------------------------------------------------------------------------------------------------------ 3
 def test_merge_exact_against_the_host_entry(scene):
-    sc = scene
+    check_merge_exact_against_the_host_entry(scene)
+
+
+def check_merge_exact_against_the_host_entry(sc):
     for k in range(2):
         plain = fused(sc, k)
-        assert_exact_against_host_entry(plain, sc.cd_host, None, TOL_M, what=f"model {k}")
+        assert_exact_against_host_entry(plain, sc.cd_host, None, TOL_M, what=f"model {k}", scale=sc.scale)
         assert (plain["counts"][:, AGREE] > 0).all()
         filled = fuse_all(sc.b, sc.d_models[k], sc.holes, fill_min_weight=1)
-        assert_exact_against_host_entry(filled, sc.holes_host, None, TOL_M, 255, 1, what=f"model {k}, holes")
+        assert_exact_against_host_entry(filled, sc.holes_host, None, TOL_M, 255, 1, what=f"model {k}, holes", scale=sc.scale)
         assert (filled["zkey"] == plain["zkey"]).all()            # the splat does not read the measurement
         at = (filled["zkey"] != EMPTY) & (sc.holes_host == 0)
         assert (filled["counts"][:, FILLED] == at.sum(axis=(1, 2))).all() and at.any()
         assert (filled["depth"][at] == sc.out(0, k)["pred_depth"].view(np.uint16)[at]).all() and (filled["weight"][at] == 1).all()
         weighted = fuse_all(sc.b, sc.d_models[k], sc.holes, kf_weight=sc.w, max_weight=6, fill_min_weight=4)
-        assert_exact_against_host_entry(weighted, sc.holes_host, sc.w_host, TOL_M, 6, 4, what=f"model {k}, holes, weights")
+        assert_exact_against_host_entry(weighted, sc.holes_host, sc.w_host, TOL_M, 6, 4, what=f"model {k}, holes, weights", scale=sc.scale)
         assert (weighted["counts"][:, [AGREE, FILLED]] > 0).all() and weighted["weight"].max() == 8   # (a filled pixel keeps its weight)
 
 

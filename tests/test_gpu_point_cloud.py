@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 import vors_amd as V
 from oracle import oracle as O
+from depth_scales import requantise_tensor
 
 N = 4
 SEED = 0x5EEDC10D
@@ -74,17 +75,21 @@ def sentinels(n, cap, pad=0, dev="cuda"):
 
 
 class Scene:
-    """4 rendered pairs on a handle that has only prepared its keyframes; the full clouds of levels 0 and L - 1 are read back once."""
+    """4 rendered pairs on a handle that has only prepared its keyframes; the full clouds of levels 0 and L - 1 are read back once.
+    scale, idepth_variance: the handle's; the rendered depth maps (quantised at V.DEPTH_SCALE) are re-quantised at another scale."""
 
-    def __init__(self, shape, mode, arith):
+    def __init__(self, shape, mode, arith, scale=V.DEPTH_SCALE, idepth_variance=1e-4):
         import torch
         self.rows, self.cols, self.L = shape
         self.mode, self.arith = mode, ARITHS[arith]
+        self.scale, self.idepth_variance = scale, idepth_variance
         self.intr = V.scaled_intrinsics(self.rows, self.cols)
         seed = SEED | (BLOCKY if mode == V.CANDIDATES_DSO else 0)
         self.kg, self.kd, self.cg, _, _ = V.synth_render_pairs(seed, N, self.rows, self.cols, self.intr, invalid_percent=INVALID_PERCENT)
+        if scale != V.DEPTH_SCALE:
+            self.kd = requantise_tensor(self.kd, scale)
         self.cfg = V.Config(nb_levels=self.L, intrinsics=V.Intrinsics(self.intr[:2], self.intr[2:4], self.intr[4]), candidates_mode=mode,
-                            arithmetic=self.arith)
+                            depth_scale=scale, idepth_variance=idepth_variance, arithmetic=self.arith)
         self.b = V.Batch(self.cfg, N, self.rows, self.cols)
         self.b.prepare_keyframes(self.kg, self.kd)
         self.poses = world_poses()
@@ -109,12 +114,13 @@ class Scene:
 
     def oracle(self):
         """Per pair and level of self.levels: the oracle's points (xy, idepth), level image and level intrinsics. Shared by the handles of a scene."""
-        key = (self.rows, self.cols, self.L, self.mode)
+        key = (self.rows, self.cols, self.L, self.mode, self.scale, self.idepth_variance)
         if key not in _oracle_cache:
             kg, kd = self.kg.cpu().numpy(), self.kd.cpu().numpy().view(np.uint16)
             per_pair = []
             for p in range(N):
-                tr = O.Tracker(O.make_config(self.L, self.intr, candidates_mode=self.mode), 0.0, kd[p], 0.0, kg[p])
+                tr = O.Tracker(O.make_config(self.L, self.intr, depth_scale=self.scale, idepth_variance=self.idepth_variance, candidates_mode=self.mode),
+                               0.0, kd[p], 0.0, kg[p])
                 per_pair.append({lvl: (tr.points(lvl)[0], tr.points(lvl)[1], tr.image(lvl), tr.level(lvl)[3]) for lvl in self.levels})
             _oracle_cache[key] = per_pair
         return _oracle_cache[key]
@@ -142,7 +148,10 @@ def unpack(pix):
 
 # ------------------------------------------------------------------------------------------------------------ 1
 def test_clouds_equal_the_oracle(scene):
-    sc = scene
+    check_clouds_equal_the_oracle(scene)
+
+
+def check_clouds_equal_the_oracle(sc):
     for p in range(N):
         for lvl in sc.levels:
             rows, cols = sc.shape(lvl)

@@ -30,6 +30,7 @@ import vors_amd as V
 from test_gpu_first_principles import level_intrinsics
 from test_oracle_first_principles import back_project, iso_to_mat, project
 from test_to_depth_host import restated as to_depth_np
+from depth_scales import requantise_tensor
 
 N = 4
 SCALE = 5000.0
@@ -93,8 +94,9 @@ def everything(b, lvl, d_models, cd):
     return m
 
 
-def assert_assignment_and_depth_map(m, p, rows, cols, what, z_positive=None):
-    """Cases 1 and 3 for one pair. z_positive: per-pixel bool plane (True where the point's Z' > 0), None = everywhere."""
+def assert_assignment_and_depth_map(m, p, rows, cols, what, z_positive=None, scale=SCALE):
+    """Cases 1 and 3 for one pair. z_positive: per-pixel bool plane (True where the point's Z' > 0), None = everywhere. scale: the handle's
+    depth scale."""
     uv, pz, cnt = m["warp"][p], m["pred_z"][p], m["counts"][p]
     assert pz.shape == (rows, cols) and pz.dtype == np.float32
     usable = ~np.isnan(uv[..., 0])
@@ -109,22 +111,25 @@ def assert_assignment_and_depth_map(m, p, rows, cols, what, z_positive=None):
     assert int(cnt[0]) == int(usable.sum()) and int(cnt[1]) == int(ok.sum()), (what, cnt, usable.sum(), ok.sum())
     # 3: the depth map from the device's own plane, IEEE division on both sides
     with np.errstate(divide="ignore"):
-        want = np.where(np.isposinf(pz), np.uint16(0), to_depth_np(SCALE, F32(1.0) / pz))
+        want = np.where(np.isposinf(pz), np.uint16(0), to_depth_np(scale, F32(1.0) / pz))
     assert (m["pred_depth"][p].view(np.uint16) == want).all(), what
     return ok, q
 
 
 class Scene:
-    """4 rendered pairs (with the rendered current depth) tracked once; models [N, 2, 7]: each pair's lm_model and one moved by se3_exp(3e-3 u)."""
+    """4 rendered pairs (with the rendered current depth) tracked once; models [N, 2, 7]: each pair's lm_model and one moved by se3_exp(3e-3 u).
+    scale, idepth_variance: the handle's; the rendered depth maps (quantised at SCALE) are re-quantised at another scale."""
 
-    def __init__(self, shape, mode, arith):
+    def __init__(self, shape, mode, arith, scale=SCALE, idepth_variance=1e-4):
         import torch
         self.rows, self.cols, self.L = shape
-        self.mode = mode
+        self.mode, self.scale = mode, scale
         self.intr = V.scaled_intrinsics(self.rows, self.cols)
         self.kg, self.kd, self.cg, self.cd, _ = V.synth_render_pairs(scene_seed(0x5EEDE7A3, mode), N, self.rows, self.cols, self.intr, want_cur_depth=True)
+        if scale != SCALE:
+            self.kd, self.cd = requantise_tensor(self.kd, scale), requantise_tensor(self.cd, scale)
         cfg = V.Config(nb_levels=self.L, intrinsics=V.Intrinsics(self.intr[:2], self.intr[2:4], self.intr[4]), candidates_mode=mode,
-                       arithmetic=ARITHS[arith])
+                       depth_scale=scale, idepth_variance=idepth_variance, arithmetic=ARITHS[arith])
         self.b, self.stats = tracked_handle(cfg, self.kg, self.kd, self.cg, self.rows, self.cols)
         lm = V.decode_stats(self.stats)["lm_model"].copy()
         rng = np.random.default_rng(11)
@@ -156,9 +161,8 @@ def scene(request):
 
 
 # ------------------------------------------------------------------------------------------------------------ 1, 2, 3
-def test_pixel_assignment_depth_values_and_depth_map(scene):
-    sc = scene
-    for lvl in (0, sc.L - 1):
+def check_pixel_assignment_depth_values_and_depth_map(sc, levels=None):
+    for lvl in (0, sc.L - 1) if levels is None else levels:
         rows, cols = sc.shape(lvl)
         for k in range(2):
             m = sc.out(lvl, k)
@@ -167,7 +171,7 @@ def test_pixel_assignment_depth_values_and_depth_map(scene):
                 what = f"level {lvl} pair {p} model {k}"
                 xy, Z = sc.z(p, lvl, k)
                 assert len(xy) > 0 and (Z > 1.0).all(), what   # the rendered scenes sit at 1.6 - 2.6 m: every point is in front of the camera
-                ok, q = assert_assignment_and_depth_map(m, p, rows, cols, what)
+                ok, q = assert_assignment_and_depth_map(m, p, rows, cols, what, scale=sc.scale)
                 assert int(m["counts"][p][0]) == len(xy), what
                 # 2: nearest float64 depth per pixel over the assignment of 1
                 okp, qp = ok[xy[:, 1], xy[:, 0]], q[xy[:, 1], xy[:, 0]]
@@ -181,9 +185,12 @@ def test_pixel_assignment_depth_values_and_depth_map(scene):
                 assert err <= 1e-5, what
 
 
+def test_pixel_assignment_depth_values_and_depth_map(scene):
+    check_pixel_assignment_depth_values_and_depth_map(scene)
+
+
 # ------------------------------------------------------------------------------------------------------------ 5
-def test_residual_plane_and_counts_against_float64(scene):
-    sc = scene
+def check_residual_plane_and_counts_against_float64(sc):
     rows, cols = sc.shape(0)
     for k in range(2):
         m = sc.out(0, k)
@@ -197,7 +204,7 @@ def test_residual_plane_and_counts_against_float64(scene):
             d = sc.cd_host[p].ravel()[qp]
             has = okp & (d != 0)
             want = np.full((rows, cols), np.nan)
-            want[xy[has, 1], xy[has, 0]] = Z[has] - d[has].astype(np.float64) / SCALE
+            want[xy[has, 1], xy[has, 0]] = Z[has] - d[has].astype(np.float64) / sc.scale
             res = m["residual"][p]
             assert (np.isfinite(res) == np.isfinite(want)).all() and np.isnan(res[~np.isfinite(want)]).all(), what
             bound = np.full((rows, cols), np.nan)
@@ -210,6 +217,10 @@ def test_residual_plane_and_counts_against_float64(scene):
             assert int(cnt[2]) == int(f.sum()), what
             assert int(cnt[3]) == int((np.abs(res[f]) <= F32(TOL_M)).sum()), what
             assert 0 < int(cnt[3]) <= int(cnt[2]) <= int(cnt[1]) <= int(cnt[0]), (what, cnt)
+
+
+def test_residual_plane_and_counts_against_float64(scene):
+    check_residual_plane_and_counts_against_float64(scene)
 
 
 # ------------------------------------------------------------------------------------------------------------ 6

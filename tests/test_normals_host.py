@@ -26,18 +26,18 @@ MEASURED_MAX_ANGLE_DEG = 0.00131  # the table above
 ANGLE_BOUND_DEG = 4 * MEASURED_MAX_ANGLE_DEG
 
 
-def normals(depth, step=1, jump_m=1.0, cam=CAM, **kw):
-    return vors_amd.depth_normals_host(depth, cam, SCALE, step, jump_m, **kw)
+def normals(depth, step=1, jump_m=1.0, cam=CAM, scale=SCALE, **kw):
+    return vors_amd.depth_normals_host(depth, cam, scale, step, jump_m, **kw)
 
 
-def tilted_depth(normal, dist, cam=CAM, rows=ROWS, cols=COLS):
+def tilted_depth(normal, dist, cam=CAM, rows=ROWS, cols=COLS, scale=SCALE):
     """The plane normal . X = dist seen through cam, quantised like a depth map."""
     cu, cv, fu, fv, skew = [float(v) for v in cam]
     x, y = np.meshgrid(np.arange(cols, dtype=np.float64), np.arange(rows, dtype=np.float64))
     ry = (y - cv) / fv
     rx = ((x - cu) - skew * ry) / fu
     z = dist / (normal[0] * rx + normal[1] * ry + normal[2])
-    d = np.rint(z * SCALE)
+    d = np.rint(z * scale)
     assert d.min() >= 1 and d.max() <= 65535
     return d.astype(np.uint16)
 
