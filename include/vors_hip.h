@@ -122,7 +122,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_tracker_enable_map, vors_tracker_read_map, vors_map_segment, likewise; + vors_trackers_enable_map_voxels,
                               *    vors_trackers_map_voxels, vors_tracker_enable_map_voxels, vors_tracker_read_map_voxels, vors_voxel_keys,
                               *    VORS_VOXEL_NONE, likewise; + vors_render_points, vors_render_points_host, vors_trackers_render_map,
-                              *    vors_tracker_render_map, VORS_RENDER_COUNTS, likewise) */
+                              *    vors_tracker_render_map, VORS_RENDER_COUNTS, likewise; + vors_icp_points, vors_icp_points_host,
+                              *    vors_icp_workspace_bytes, vors_trackers_icp_map, vors_icp_stats, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -330,6 +331,20 @@ vors_status vors_trackers_enable_map_normals(vors_trackers* t, int step, float j
 /* DEVICE pointer [n][capacity][3] f32, owned by the handle and valid for its life: entry r of a sequence is the normal of the map's entry
  * r, valid in stream order after the last init / track for r < min(total, capacity). Not enabled: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_map_normals(const vors_trackers* t, const float** d_normals);
+/* THE KEYFRAME MAP ALIGNED TO DEPTH FRAMES: vors_icp_points (section 2e) on the handle's own map and map normals, its level-0 intrinsics
+ * and shape and its depth_scale, against d_depth [n][rows * cols] u16 (DEVICE; usually the frames of the last track call). d_poses7_in
+ * (DEVICE, nullable): the start poses, pose_stride_bytes apart (0 = 28); NULL = every sequence's CURRENT FRAME pose, read on the device
+ * from the handle's pose table, so the call needs no synchronisation after a track. d_workspace: vors_icp_workspace_bytes(n, the map's
+ * capacity) bytes. Everything else as in vors_icp_points. The pass READS the handle only: the tracker's poses, its map and its later
+ * results keep their bits. Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: a NULL handle, no enabled map, no enabled map
+ * normals, a call before vors_trackers_init, a stream of another device, and every refusal of vors_icp_points. Allocates nothing;
+ * enqueued on hip_stream, NOT synchronised. */
+struct vors_icp_stats;  /* section 2e */
+vors_status vors_trackers_icp_map(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters,
+                                  int min_points, const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                                  const void* d_poses7_in /* nullable */, size_t pose_stride_bytes, void* d_workspace,
+                                  float* d_poses7_out, struct vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
+                                  float* d_residuals /* nullable */, void* hip_stream);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -764,6 +779,68 @@ vors_status vors_points_normals(int n, const uint16_t* d_depth, const uint32_t* 
 vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale, int step, float jump_m,
                                     const float pose7[7], const uint32_t* pixel, uint32_t count, int capacity, const uint32_t range2[2],
                                     float* normals, uint32_t counts[VORS_NORMAL_COUNTS]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2e. POINT-TO-PLANE ICP OF POINT LISTS WITH NORMALS AGAINST DEPTH FRAMES, device-resident and handle-free (the reference
+ *     has none): refine one camera -> world pose per list so that the measured level-0 depth plane lies on the planes of the model.
+ * Lists: d_xyz / d_normals [n][capacity][3] f32 in the world frame (a normal of three zeros = no normal) and d_list_counts [n] u32 —
+ *   the pointers of vors_trackers_map / vors_trackers_map_normals and of vors_batch_point_cloud / vors_points_normals; d_ranges /
+ *   range_stride_bytes and d_poses7_in / pose_stride_bytes as in vors_render_points, except that the poses are REQUIRED. d_depth
+ *   [n][rows * cols] u16, cam5 (HOST) = cu cv fu fv skew, depth_scale.
+ * PER POINT of rank r at the pose T: c = extr_project(T, w); the landing pixel (x, y) is vors_render_points' footprint-1 anchor
+ *   (floorf(u + 0.5f), floorf(v + 0.5f)), with its float comparisons before any integer conversion, and must lie inside the plane (tested
+ *   in integers). MATCHED iff the point is such a candidate, its normal is not three zeros, d = D[y][x] != 0 and, with
+ *   q = back_project(K, (float)x, (float)y, 1.0f / (depth_scale / (float)d)) and e = q - c, dot3(e, e) <= dist_m * dist_m in float (NaN
+ *   fails). n = conj(T.q) * nw; residual r = dot3(n, e); Jacobian row J = (n, cross(q, n)), translational three first (se3_exp's order).
+ *   A matched point contributes r r, J[i] r (6) and J[i] J[j] for i <= j row-wise (21) — sums29's slots 0, 2..7, 8..28 — and 1 to the
+ *   matched count; an unmatched one +0.0f to every sum.
+ * ORDER OF THE SUMS (part of the definition): the clipped range [first, first + count) is cut into chunks of 1024 consecutive ranks from
+ *   `first`; slot s is a rank's offset in its chunk, slots beyond the range hold zeros. Chunk sum: for (w = 512; w >= 1; w /= 2)
+ *   v[s] = v[s] + v[s + w] for s < w, in f32, per product. List sum: the chunk sums added sequentially in ascending chunk order, starting
+ *   from chunk 0's. Counts are integers. The result depends neither on capacity nor on the grid or the schedule; the device equals
+ *   vors_icp_points_host bit for bit.
+ * LOOP per list, no host round trip: `iters` times evaluate, solve, update; then ONE final evaluation at the returned pose, which is what
+ *   d_stats, d_sums29 and d_residuals describe (iters = 0: a pure evaluator at the given poses). The update is vors_lm_step's:
+ *   H mirrored from the 21 sums, g = the 6, lm_coef = damping, T' = renormalize(T * exp(delta)^-1). A list is FROZEN — its later
+ *   rounds do nothing — when matched < min_points (VORS_ICP_TOO_FEW, pose kept), when the step is refused (VORS_ICP_SINGULAR, pose kept),
+ *   or when after an update dot6(delta, delta) <= step_eps * step_eps (VORS_ICP_CONVERGED); otherwise VORS_ICP_ITERATIONS.
+ * Outputs (DEVICE): d_poses7_out [n][7] (required, may alias d_poses7_in when packed alike); d_stats [n] vors_icp_stats; d_sums29 [n][29],
+ *   the layout of vors_batch_eval_level with the matched count in slot 1, so that vors_pose_information_from_sums gives the ICP's
+ *   information matrix and covariance; d_residuals [n][capacity] f32, NaN = not matched, exactly the ranks of the clipped range written.
+ *   The last three are nullable. stats: iterations = updates applied; considered = ranks of the clipped range; matched, rms =
+ *   sqrtf(sums[0] / (float)matched) (NaN without a matched point) of the final evaluation; last_step_norm = sqrtf(dot6(delta, delta)) of
+ *   the last update (0 without one).
+ * d_workspace (DEVICE, 4-byte aligned): vors_icp_workspace_bytes(n, capacity) bytes — the chunk partials [n][chunks][28] f32, the chunk
+ *   counts and the per-list state; chunks = ceil(capacity / 1024). 0 for n < 1 or capacity < 1.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: n < 1; a NULL list, d_poses7_in, d_depth, cam5, d_workspace or d_poses7_out;
+ *   rows, cols or capacity < 1; rows or cols > 65535 or rows * cols > 2^28; depth_scale not > 0; dist_m, damping or step_eps negative or
+ *   NaN; iters outside 0..64; min_points < 6; a bad stride; a pointer off its natural alignment (d_depth: 2 bytes, the others: 4).
+ * Enqueued on hip_stream on the calling thread's current device, NOT synchronised, no allocation ever: one launch that starts the state,
+ *   per round one evaluation launch (grid = chunks x lists) and one solve launch (one wavefront per list), then the final evaluation and
+ *   the launch that writes the outputs; no workgroup waits for another and no floating-point atomic exists. */
+#define VORS_ICP_ITERATIONS 0
+#define VORS_ICP_CONVERGED 1
+#define VORS_ICP_TOO_FEW 2
+#define VORS_ICP_SINGULAR 3
+typedef struct vors_icp_stats {
+    uint32_t status, iterations, considered, matched;
+    float rms, last_step_norm;
+} vors_icp_stats;
+uint64_t vors_icp_workspace_bytes(int n, int capacity);
+vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
+                            const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                            const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth,
+                            const float cam5[5], int rows, int cols, float depth_scale,
+                            float dist_m, float damping, float step_eps, int iters, int min_points, void* d_workspace,
+                            float* d_poses7_out, vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
+                            float* d_residuals /* nullable */, void* hip_stream);
+/* The same loop for ONE list on the host (host arithmetic, needs no GPU; the texts and the order of sums the kernels run): HOST pointers,
+ * count = the list's count (clipped to capacity), range2 (nullable) = (first, count), depth [rows * cols]. No workspace. The refusals
+ * above, with nothing written. */
+vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
+                                 const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale,
+                                 float dist_m, float damping, float step_eps, int iters, int min_points,
+                                 float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Time vors_icp_points (64 lists against 64 depth planes of 640x480) and write the device part of profiles/icp_summary.md.
+
+Lists of 23 500 and 465 600 points per list (the two list lengths of profiles/normals_summary.md): pixels of the depth frame drawn
+uniformly, back-projected in the camera frame, their normals from vors_points_normals; the start pose is 5 mm and 0.2 degrees off, and
+step_eps = 0 keeps every list iterating, so that a pass at `iters` runs iters + 1 evaluation launches and iters + 1 solve launches.
+Legs, per list length: the pass at iters = 0 (the start of the state, one evaluation, one solve: the pure evaluator), the pass at iters = 8,
+and from the two one round = (t8 - t0) / 8, an evaluation launch plus a solve launch. Beside them, in the same run, the nearest existing
+pass: vors_render_points at footprint 1 over the same lists (it reads the same 12-byte rows and scatters one key per point where the
+ICP gathers one depth), splat alone (zkey only).
+Byte model of an evaluation: 12 + 12 B per point read, a 2 B gather; the partials are 112 B per 1024 points.
+HIP events around one call; a block = the median of 20 calls after 3 warm-up calls; the blocks of all legs alternate for `--blocks` rounds,
+so the figure of a leg is the median of its block medians and its run-to-run spread their range. No threshold is fixed.
+
+  python tools/icp_bench.py [--lists N] [--blocks K] [--out FILE]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from normals_bench import COLS, ROWS, SEQS, SIZES, block  # noqa: E402
+
+
+def measure(a):
+    sys.path[:0] = [os.path.join(ROOT, "visual-odometry-rs_amd"), ROOT]
+    import torch
+    import vors_amd as V
+    intr = np.asarray(V.scaled_intrinsics(ROWS, COLS), np.float32)
+    cu, cv, fu, fv, _ = [float(v) for v in intr]
+    n = a.lists
+    _, depth = V.synth_render_frames([2000 + s for s in range(n)], [0] * n, [np.zeros(6)] * n, ROWS, COLS, intr, invalid_percent=2)
+    start = np.zeros(7, np.float32)
+    V.lib().vors_se3_exp(V._ptr(np.array([0.003, -0.003, 0.003, 0.002, -0.002, 0.002], np.float32)), V._ptr(start))
+    poses = torch.from_numpy(np.tile(start, (n, 1))).cuda()
+    zkey = torch.empty((n, ROWS, COLS), dtype=torch.int64, device="cuda")
+    rng = np.random.default_rng(0)
+    legs, matched = {}, {}
+    for size in SIZES:
+        px, py = rng.integers(0, COLS, (n, size)), rng.integers(0, ROWS, (n, size))
+        pixel = torch.from_numpy((px | (py << 16)).astype(np.int32)).cuda()
+        counts = torch.full((n,), size, dtype=torch.int32, device="cuda")
+        z = torch.gather(depth.view(n, -1).to(torch.int32) & 0xffff, 1, torch.from_numpy(py * COLS + px).cuda()).to(torch.float32) / V.DEPTH_SCALE
+        xyz = torch.stack([(torch.from_numpy(px).cuda() - cu) * z / fu, (torch.from_numpy(py).cuda() - cv) * z / fv, z], -1).to(torch.float32).contiguous()
+        nrm = V.points_normals(depth, pixel, counts, intr, V.DEPTH_SCALE, 1, 0.05)["normals"]
+        gray = torch.zeros((n, size), dtype=torch.uint8, device="cuda")
+        ws = torch.empty(V.icp_workspace_bytes(n, size), dtype=torch.uint8, device="cuda")
+        stats = torch.zeros((n, 24), dtype=torch.uint8, device="cuda")
+
+        def icp(iters, xyz=xyz, nrm=nrm, counts=counts, ws=ws, stats=stats):
+            return V.icp_points(xyz, nrm, counts, depth, intr, V.DEPTH_SCALE, poses, 0.05, step_eps=0.0, iters=iters, workspace=ws, stats=stats)
+
+        icp(8)
+        torch.cuda.synchronize()
+        st = V.decode_icp_stats(stats)
+        matched[size] = (int(st["matched"].min()), int(st["matched"].max()), sorted(set(st["iterations"].tolist())), sorted(set(st["status"].tolist())))
+        model = n * size * 26 + n * ((size + 1023) // 1024) * 116
+        legs[f"{size} points: pass at iters 0"] = (lambda icp=icp: icp(0), model)
+        legs[f"{size} points: pass at iters 8"] = (lambda icp=icp: icp(8), 9 * model)
+        legs[f"{size} points: yardstick, vors_render_points footprint 1, splat alone"] = (
+            lambda xyz=xyz, gray=gray, counts=counts: V.render_points(xyz, gray, counts, intr, ROWS, COLS, V.DEPTH_SCALE, poses=poses, depth=False,
+                                                                      gray=False, zkey=zkey), n * size * 12 + n * ROWS * COLS * 8)
+    meds = {name: [] for name in legs}
+    for _ in range(a.blocks):
+        for name, (fn, _) in legs.items():
+            meds[name].append(block(torch, fn))
+    return [(name, float(np.median(meds[name])), min(meds[name]), max(meds[name]), legs[name][1]) for name in legs], matched
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lists", type=int, default=SEQS)
+    ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "icp_summary.md"))
+    a = ap.parse_args()
+    rows, matched = measure(a)
+    lines = ["# Point-to-plane ICP: vors_icp_points", "",
+             f"`python tools/icp_bench.py --lists {a.lists} --blocks {a.blocks}` on one MI355X: {a.lists} lists against {a.lists} planes of "
+             f"{COLS}x{ROWS}; medians of {a.blocks} alternating blocks of 20 calls (range of the block medians in brackets).", "",
+             "| leg | ms | range, ms | bytes of the model | GB/s of the model |", "|---|---|---|---|---|"]
+    by = {}
+    for name, med, lo, hi, nbytes in rows:
+        by[name] = (med, nbytes)
+        lines.append(f"| {name} | {med:.4f} | {lo:.4f} .. {hi:.4f} | {nbytes} | {nbytes / med / 1e6:.0f} |")
+    lines += ["", "One round (an evaluation launch and a solve launch) = (pass at iters 8 - pass at iters 0) / 8:", ""]
+    for size in SIZES:
+        t0, m = by[f"{size} points: pass at iters 0"]
+        t8, _ = by[f"{size} points: pass at iters 8"]
+        lo, hi, its, sts = matched[size]
+        lines.append(f"- {size} points: {(t8 - t0) / 8:.4f} ms, {m / ((t8 - t0) / 8) / 1e6:.0f} GB/s of the model; matched per list {lo} .. {hi}, "
+                     f"updates {its}, statuses {sts}")
+    text = "\n".join(lines) + "\n"
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
+if __name__ == "__main__":
+    main()

@@ -513,6 +513,50 @@ void launch_points_normals(const NormalCall& call, hipStream_t s);
 // dst[i] = src[i] for the n running totals of the keyframe map (the ranks an emission starts from), honouring nothing: every sequence.
 void launch_normals_snapshot(const uint32_t* src, uint32_t* dst, int n, hipStream_t s);
 
+// Point-to-plane ICP of world-frame point lists with normals against depth planes (vors_icp_points, vors_trackers_icp_map;
+// icp_kernels.hip): per point lie.h icp_landing / icp_row, the sums in lie.h's fixed order, the round's verdict lie.h icp_round.
+// Handle-free: everything the kernels read is here; the caller's workspace holds the chunk partials, the chunk counts and the state.
+struct IcpState {  // per list, in the workspace
+    float pose[7];
+    uint32_t status, iterations, frozen;
+    float last_step_norm;
+    uint32_t pad;
+};
+struct IcpCall {
+    int n;                       // lists
+    const float* xyz;            // [n][capacity][3]
+    const float* normals;        // [n][capacity][3]
+    const uint32_t* list_counts; // [n]; a count above capacity is clipped to it
+    int capacity;
+    const uint8_t* ranges;       // nullable = the whole list; (first, count) u32 pairs, range_stride BYTES apart, clipped to the written prefix
+    int range_stride;
+    const float* poses_in;       // camera -> world, required
+    int pose_stride;             // floats
+    const uint16_t* depth;       // [n][rows * cols]
+    Intr k;
+    int rows, cols;
+    float depth_scale, dist_m, damping, step_eps;
+    int iters;
+    uint32_t min_points;
+    float* partials;             // workspace: [n][icp_chunks(capacity)][VORS_ICP_SUMS]
+    uint32_t* chunk_counts;      // workspace: [n][icp_chunks(capacity)]
+    IcpState* state;             // workspace: [n]
+    float* poses_out;            // [n][7], may alias poses_in
+    vors_icp_stats* stats;       // [n], nullable
+    float* sums29;               // [n][29], nullable
+    float* residuals;            // [n][capacity], nullable
+};
+#define ICP_BLOCK 256
+#define ICP_MAX_CHUNKS 1024  // cap of the evaluation grid's x extent: a longer list goes through the stride loop
+constexpr size_t icp_chunks(int capacity) { return ((size_t)capacity + VORS_ICP_CHUNK - 1) / VORS_ICP_CHUNK; }
+// The workspace: partials, chunk counts, state, in this order (every part a multiple of 4 bytes).
+inline size_t icp_workspace_bytes(int n, int capacity) {
+    return (size_t)n * (icp_chunks(capacity) * (VORS_ICP_SUMS + 1) * 4 + sizeof(IcpState));
+}
+// The state's start, then per round one evaluation and one solve launch, then the final evaluation and the launch that writes the
+// outputs: enqueued on s in this order, not synchronised, no allocation.
+void launch_icp_points(const IcpCall& call, hipStream_t s);
+
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }

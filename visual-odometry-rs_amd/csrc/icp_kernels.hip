@@ -1,0 +1,227 @@
+// vors_icp_points / vors_trackers_icp_map: projective point-to-plane ICP of world-frame point lists with normals against level-0 depth
+// planes. Handle-free: no Geom, no records; the per-point rule is lie.h icp_landing / icp_row / icp_products, the round's
+// verdict lie.h icp_round, the order of the sums the one lie.h states — the texts vors_icp_points_host runs, bit for bit.
+// BEGIN  (icp_begin_kernel): one thread per list copies the start pose into the state in the workspace; from then on the input poses are
+//        not read again, so the output poses may alias them.
+// EVAL   (icp_eval_kernel): grid = (chunks of the list) x lists, sized from the capacity and capped at ICP_MAX_CHUNKS; a workgroup beyond
+//        the clipped range's chunks returns at once, a longer range goes through the stride loop (render_splat_kernel's scheme), and so
+//        does every workgroup of a frozen list unless the launch is the final one. A trip is one chunk of 1024 ranks: a thread takes the
+//        slots t, t + 256, t + 512, t + 768 — consecutive lanes read consecutive 12-byte rows of points and normals, all loads issued
+//        before the first use, then the four depth gathers before the rows. The halving tree: w = 512 and 256 in the thread, (p0 + p2) +
+//        (p1 + p3), into ONE set of 28 accumulators (the four rows of seven are what stays live, not four sets of products); w = 128 and
+//        64 across the four wavefronts through LDS, [product][lane] so that lanes hit consecutive banks; w = 32..1 inside wavefront 0 by
+//        __shfl_down, v[s] + v[s + w]. Lane 0 stores the chunk's 28 sums and its matched count: stored, not accumulated — the
+//        workspace needs no clearing and no floating-point atomic exists. No workgroup waits for another.
+// SOLVE  (icp_solve_kernel): one wavefront per list. Lanes 0..27 own one sum each and add the chunk partials in ascending order from
+//        chunk 0's, eight loads issued ahead of the eight dependent adds; lanes 32..63 add the integer counts. Every lane then holds all
+//        28 sums (__shfl) and runs the verdict; lane 0 stores. The final launch writes the outputs instead.
+#include "device_common.h"
+
+namespace vors {
+
+struct IcpEvalArgs {
+    int seq0;
+    IcpCall c;
+};
+
+__device__ __forceinline__ void icp_list_range(const IcpCall& c, int seq, uint32_t* first, uint32_t* last) {
+    const uint32_t* r = c.ranges ? reinterpret_cast<const uint32_t*>(c.ranges + (size_t)seq * (size_t)c.range_stride) : nullptr;
+    icp_range(c.list_counts[seq], c.capacity, r, first, last);
+}
+
+__global__ void icp_begin_kernel(IcpCall c) {
+    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
+    if (seq >= c.n) return;
+    const float* p = c.poses_in + (size_t)seq * (size_t)c.pose_stride;
+    IcpState& st = c.state[seq];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) st.pose[i] = p[i];
+    st.status = ICP_ITERATIONS;
+    st.iterations = 0u;
+    st.frozen = 0u;
+    st.last_step_norm = 0.0f;
+    st.pad = 0u;
+}
+
+template <bool FINAL, bool RESID>
+__global__ __launch_bounds__(ICP_BLOCK) void icp_eval_kernel(IcpEvalArgs a) {
+    __shared__ float lds[VORS_ICP_SUMS * 128];
+    __shared__ uint32_t lds_counts[ICP_BLOCK / 64];
+    const IcpCall& c = a.c;
+    const int seq = a.seq0 + blockIdx.y;
+    const IcpState& st = c.state[seq];
+    if (!FINAL && st.frozen) return;  // the whole workgroup
+    uint32_t first, last;
+    icp_list_range(c, seq, &first, &last);
+    // (last - first <= capacity < 2^31: nothing below wraps)
+    const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
+    if (blockIdx.x >= nchunks) return;  // the whole workgroup
+    const size_t cap_chunks = icp_chunks(c.capacity);
+    const float* xyz = c.xyz + (size_t)seq * (size_t)c.capacity * 3;
+    const float* normals = c.normals + (size_t)seq * (size_t)c.capacity * 3;
+    const uint16_t* depth = c.depth + (size_t)seq * (size_t)c.rows * (size_t)c.cols;
+    const Iso pose = iso_load(st.pose);
+    const unsigned t = threadIdx.x, wave = t >> 6;
+    for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const uint32_t base = first + chunk * VORS_ICP_CHUNK;
+        V3 w[4], nw[4];
+        bool valid[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t rank = base + j * ICP_BLOCK + t;
+            valid[j] = rank < last;
+            const size_t o = 3 * (size_t)(valid[j] ? rank : base);  // (a slot beyond the range reads the chunk's first row: a safe address)
+            w[j] = V3{xyz[o], xyz[o + 1], xyz[o + 2]};
+            nw[j] = V3{normals[o], normals[o + 1], normals[o + 2]};
+        }
+        IcpLanding l[4];
+        uint16_t d[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            l[j] = icp_landing(c.k, pose, w[j], c.cols, c.rows);
+            l[j].lands = l[j].lands && valid[j];
+            d[j] = depth[l[j].lands ? l[j].y * c.cols + l[j].x : 0];  // (no landing: pixel 0, a safe address; icp_row ignores it)
+        }
+        float row[4][7];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool m = icp_row(c.k, c.depth_scale, c.dist_m, pose, l[j], nw[j], d[j], row[j]);
+            cnt += m ? 1u : 0u;
+            if constexpr (RESID)
+                if (valid[j]) c.residuals[(size_t)seq * (size_t)c.capacity + (base + j * ICP_BLOCK + t)] = m ? row[j][0] : __builtin_nanf("");
+        }
+        // w = 512, 256: (slot t + slot t + 512) + (slot t + 256 + slot t + 768)
+        float acc[VORS_ICP_SUMS], p[VORS_ICP_SUMS], q[VORS_ICP_SUMS];
+        icp_products(row[0], p);
+        icp_products(row[2], q);
+#pragma unroll
+        for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = p[k] + q[k];
+        icp_products(row[1], p);
+        icp_products(row[3], q);
+#pragma unroll
+        for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + (p[k] + q[k]);
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, sh);
+        if ((t & 63) == 0) lds_counts[wave] = cnt;
+        // w = 128: threads 128..255 hand over
+        if (wave >= 2) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) lds[k * 128 + (t - 128)] = acc[k];
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + lds[k * 128 + t];
+        }
+        __syncthreads();
+        // w = 64: threads 64..127 hand over
+        if (wave == 1) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) lds[k * 128 + (t - 64)] = acc[k];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + lds[k * 128 + t];
+            // w = 32..1: lane s takes lane s + w's (lanes >= w compute values nobody reads)
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) {
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + __shfl_down(acc[k], sh);
+            }
+            if (t == 0) {
+                float* out = c.partials + ((size_t)seq * cap_chunks + chunk) * VORS_ICP_SUMS;
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) out[k] = acc[k];
+                c.chunk_counts[(size_t)seq * cap_chunks + chunk] = (lds_counts[0] + lds_counts[1]) + (lds_counts[2] + lds_counts[3]);
+            }
+        }
+        __syncthreads();  // (the next trip writes the LDS again)
+    }
+}
+
+template <bool FINAL>
+__global__ __launch_bounds__(64) void icp_solve_kernel(IcpCall c) {
+    const int seq = blockIdx.x;
+    const unsigned lane = threadIdx.x;
+    IcpState& st = c.state[seq];
+    if (!FINAL && st.frozen) return;  // the whole wavefront
+    uint32_t first, last;
+    icp_list_range(c, seq, &first, &last);
+    const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
+    const size_t cap_chunks = icp_chunks(c.capacity);
+    const float* part = c.partials + (size_t)seq * cap_chunks * VORS_ICP_SUMS;
+    const uint32_t* counts = c.chunk_counts + (size_t)seq * cap_chunks;
+    float sum = 0.0f;
+    uint32_t matched = 0;
+    if (lane < VORS_ICP_SUMS) {
+        if (nchunks > 0) sum = part[lane];
+        uint32_t ch = 1;
+        for (; ch + 8 <= nchunks; ch += 8) {
+            float v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = part[(size_t)(ch + i) * VORS_ICP_SUMS + lane];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) sum = sum + v[i];
+        }
+        for (; ch < nchunks; ++ch) sum = sum + part[(size_t)ch * VORS_ICP_SUMS + lane];
+    } else if (lane >= 32) {
+        for (uint32_t ch = lane - 32; ch < nchunks; ch += 32) matched += counts[ch];
+    }
+#pragma unroll
+    for (int sh = 32; sh > 0; sh >>= 1) matched += (uint32_t)__shfl_xor((int)matched, sh);
+    float sums[VORS_ICP_SUMS];
+#pragma unroll
+    for (int k = 0; k < VORS_ICP_SUMS; ++k) sums[k] = __shfl(sum, k);
+    if constexpr (!FINAL) {
+        Iso pose = iso_load(st.pose);
+        float step_norm = 0.0f;
+        const IcpStatus v = icp_round(sums, matched, c.min_points, c.damping, c.step_eps, &pose, &step_norm);
+        if (lane == 0) {
+            if (v == ICP_ITERATIONS || v == ICP_CONVERGED) {
+                iso_store(pose, st.pose);
+                st.iterations += 1u;
+                st.last_step_norm = step_norm;
+            }
+            if (v != ICP_ITERATIONS) {
+                st.status = (uint32_t)v;
+                st.frozen = 1u;
+            }
+        }
+    } else {
+        if (lane < 7) c.poses_out[(size_t)seq * 7 + lane] = st.pose[lane];
+        if (lane == 0 && c.stats) {
+            vors_icp_stats o;
+            o.status = st.status;
+            o.iterations = st.iterations;
+            o.considered = last - first;
+            o.matched = matched;
+            o.rms = sqrtf(sums[0] / (float)matched);
+            o.last_step_norm = st.last_step_norm;
+            c.stats[seq] = o;
+        }
+        if (lane == 0 && c.sums29) icp_sums29(sums, matched, c.sums29 + (size_t)seq * 29);
+    }
+}
+
+void launch_icp_points(const IcpCall& c, hipStream_t s) {
+    hipLaunchKernelGGL(icp_begin_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, s, c);
+    const size_t want = icp_chunks(c.capacity);
+    const unsigned chunks = (unsigned)(want > ICP_MAX_CHUNKS ? ICP_MAX_CHUNKS : want);
+    IcpEvalArgs a{0, c};
+    auto eval = [&](auto final_, auto resid_) {
+        for_pair_slices(c.n, [&](int seq0, int ns) {
+            a.seq0 = seq0;
+            hipLaunchKernelGGL((icp_eval_kernel<decltype(final_)::value, decltype(resid_)::value>), dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, a);
+        });
+    };
+    for (int it = 0; it < c.iters; ++it) {
+        eval(std::false_type{}, std::false_type{});
+        hipLaunchKernelGGL(icp_solve_kernel<false>, dim3((unsigned)c.n), dim3(64), 0, s, c);
+    }
+    with_bool(c.residuals != nullptr, [&](auto r) { eval(std::true_type{}, r); });
+    hipLaunchKernelGGL(icp_solve_kernel<true>, dim3((unsigned)c.n), dim3(64), 0, s, c);
+}
+
+}  // namespace vors

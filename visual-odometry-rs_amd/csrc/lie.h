@@ -536,6 +536,107 @@ VORS_HD DepthNormal depth_normal(const Intr& k, float depth_scale, int step, flo
     return o;
 }
 
+// Projective point-to-plane ICP of a world-frame point list with normals against a level-0 depth plane (the reference has
+// none). T = the camera -> world pose being refined, w / nw = a world point and its world normal (three zeros: no normal). Everything in
+// the camera frame, existing texts unchanged: c = extr_project(T, w); the landing pixel (x, y) = render_point's footprint-1 anchor, which
+// must lie inside the plane (integers); d = D[y][x]; q = back_project(K, (float)x, (float)y, depth_normal_z(depth_scale, d)); e = q - c.
+// MATCHED iff the point is a candidate that lands inside the plane, its normal is not three zeros, d != 0 and
+// dot3(e, e) <= dist_m * dist_m (in float; NaN fails). n = quat_rotate(conj(T.q), nw); the residual r = dot3(n, e); the Jacobian row
+// J = (n, cross(q, n)): the derivative of n . (exp(xi) q - c) at xi = 0, n . v + w . (q x n) for xi = (v, w) — the translational three,
+// then the rotational three, the order se3_exp reads its argument (checked against central differences of se3_exp in f64:
+// tests/test_icp_host.py test_jacobian_rule). The minimiser of sum (r + J xi)^2 is xi = -delta with H delta = g, H = sum J^T J,
+// g = sum J r: the measured cloud moves by exp(delta)^-1 in the camera frame, so the camera moves to T * exp(delta)^-1 — lm_step's update.
+// A row is a[7] = {r, J[0..5]}; an unmatched point's row is seven +0.0f, so that each of its products is +0.0f.
+// The two halves are separate so that a kernel issues the gather of d between them. The one text the host entry (vors_icp_points_host) and
+// the device kernels (icp_kernels.hip) both run, bit for bit.
+struct IcpLanding {
+    V3 c;
+    int x, y;    // meaningful only when the point lands
+    bool lands;  // a candidate whose pixel lies inside the plane
+};
+VORS_HD IcpLanding icp_landing(const Intr& k, const Iso& pose, const V3& w, int cols, int rows) {
+    const RenderPoint rp = render_point(k, true, pose, w, 1, cols, rows);
+    IcpLanding o{extr_project(pose, w), 0, 0, false};
+    if (rp.candidate && rp.x0 >= 0 && rp.x0 < cols && rp.y0 >= 0 && rp.y0 < rows) {
+        o.x = rp.x0;
+        o.y = rp.y0;
+        o.lands = true;
+    }
+    return o;
+}
+VORS_HD bool icp_row(const Intr& k, float depth_scale, float dist_m, const Iso& pose, const IcpLanding& l, const V3& nw, uint16_t d, float a[7]) {
+VORS_UNROLL
+    for (int i = 0; i < 7; ++i) a[i] = 0.0f;
+    const bool has_normal = !(nw.x == 0.0f && nw.y == 0.0f && nw.z == 0.0f);
+    if (!l.lands || !has_normal || d == 0) return false;
+    const V3 q = back_project(k, (float)l.x, (float)l.y, depth_normal_z(depth_scale, d));
+    const V3 e{q.x - l.c.x, q.y - l.c.y, q.z - l.c.z};
+    if (!(dot3(e, e) <= dist_m * dist_m)) return false;
+    const V3 n = quat_rotate(Quat{-pose.q.i, -pose.q.j, -pose.q.k, pose.q.w}, nw);
+    const V3 m = cross(q, n);
+    a[0] = dot3(n, e);
+    a[1] = n.x; a[2] = n.y; a[3] = n.z;
+    a[4] = m.x; a[5] = m.y; a[6] = m.z;
+    return true;
+}
+// The 28 products of a row, in the order of sums29's slots 0, 2..7, 8..28 (vors_batch_eval_level): r r, J[i] r, J[i] J[j] for i <= j row-wise.
+#define VORS_ICP_SUMS 28
+VORS_HD void icp_products(const float a[7], float p[VORS_ICP_SUMS]) {
+    int k = 0;
+    p[k++] = a[0] * a[0];
+VORS_UNROLL
+    for (int i = 1; i < 7; ++i) p[k++] = a[i] * a[0];
+VORS_UNROLL
+    for (int i = 1; i < 7; ++i)
+VORS_UNROLL
+        for (int j = i; j < 7; ++j) p[k++] = a[i] * a[j];
+}
+// The clipped range of ranks of a list (render_splat_kernel's text): count clipped to capacity, range2 (nullable) = (first, count).
+VORS_HD void icp_range(uint32_t count, int capacity, const uint32_t* range2, uint32_t* first, uint32_t* last) {
+    const uint32_t n = count < (uint32_t)capacity ? count : (uint32_t)capacity;
+    *first = 0;
+    *last = n;
+    if (range2) {
+        *first = range2[0] < n ? range2[0] : n;
+        *last = range2[1] > n - *first ? n : *first + range2[1];
+    }
+}
+// ORDER OF THE SUMS: the clipped range is cut into chunks of VORS_ICP_CHUNK consecutive ranks from `first`; slot s of a chunk is a rank's
+// offset in it, slots beyond the range hold zeros. Chunk sum: the halving tree for (w = 512; w >= 1; w /= 2) v[s] = v[s] + v[s + w] for
+// s < w, in f32, per product. List sum: the chunk sums added sequentially in ascending chunk order, starting from chunk 0's. The matched
+// counts are integers. Neither capacity nor the grid nor the schedule enters.
+#define VORS_ICP_CHUNK 1024
+// One round's verdict from the list sums: the statuses of vors_icp_points. H is mirrored from the 21 sums, g = sums[1..6]; the step is
+// lm_step's (the existing text), delta = cholesky6_solve's solution of the same system, kept for the convergence test.
+enum IcpStatus { ICP_ITERATIONS = 0, ICP_CONVERGED = 1, ICP_TOO_FEW = 2, ICP_SINGULAR = 3 };
+VORS_HD float dot6(const float* a, const float* b) {
+    return ((((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]) + a[4] * b[4]) + a[5] * b[5];
+}
+// -> ICP_ITERATIONS: *pose moved, go on; ICP_CONVERGED: *pose moved, stop; ICP_TOO_FEW / ICP_SINGULAR: *pose kept, stop.
+VORS_HD IcpStatus icp_round(const float sums[VORS_ICP_SUMS], uint32_t matched, uint32_t min_points, float damping, float step_eps, Iso* pose,
+                            float* step_norm) {
+    if (matched < min_points) return ICP_TOO_FEW;
+    float h[36], delta[6];
+    int k = 7;
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int c = r; c < 6; ++c) h[r * 6 + c] = h[c * 6 + r] = sums[k++];
+    Iso next;
+    if (!cholesky6_solve(h, sums + 1, damping, delta) || !lm_step(h, sums + 1, *pose, damping, &next)) return ICP_SINGULAR;
+    *pose = next;
+    const float d2 = dot6(delta, delta);
+    *step_norm = sqrtf(d2);
+    return d2 <= step_eps * step_eps ? ICP_CONVERGED : ICP_ITERATIONS;
+}
+// sums29 of vors_batch_eval_level from the 28 list sums and the matched count (slot 1).
+VORS_HD void icp_sums29(const float sums[VORS_ICP_SUMS], uint32_t matched, float* out29) {
+    out29[0] = sums[0];
+    out29[1] = (float)matched;
+VORS_UNROLL
+    for (int i = 1; i < VORS_ICP_SUMS; ++i) out29[i + 1] = sums[i];
+}
+
 // Jacobian of the warp: src/core/track/inverse_compositional.rs:313-341.
 VORS_HD void warp_jacobian_at(float gu, float gv, float u, float v, float _z, const Intr& k, float J[6]) {
     const float a = u - k.cu;

@@ -445,6 +445,153 @@ vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Point-to-plane ICP of point lists with normals against depth planes (vors_icp_points, vors_icp_points_host): the refusals both share,
+// the device entry (icp_kernels.hip) and the host entry, which runs the kernels' own texts (lie.h icp_landing, icp_row, icp_products,
+// icp_round) and the order of sums lie.h states.
+// ---------------------------------------------------------------------------------------------------------------
+static vors_status icp_refusals(const char* who, const void* xyz, const void* normals, const void* poses_in, const void* depth, const float* cam5,
+                                int capacity, int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters,
+                                int min_points, const void* poses_out, const void* stats, const void* sums29, const void* residuals) {
+    const std::string w(who);
+    if (!xyz || !normals) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, normals) is NULL");
+    if (!poses_in) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the start poses are NULL (an alignment needs a pose to refine)");
+    if (!depth) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth is NULL");
+    if (!cam5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cam5 is NULL");
+    if (!poses_out) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the output poses are NULL");
+    if (rows < 1 || cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must be >= 1");
+    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
+    if (rows > 65535 || cols > 65535 || (long long)rows * cols > (1ll << 28))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows / cols must not exceed 65535 and rows * cols must not exceed 2^28 pixels");
+    if (!(depth_scale > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth_scale must be > 0");
+    if (!(dist_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": dist_m must be >= 0 (and not NaN)");
+    if (!(damping >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": damping must be >= 0 (and not NaN)");
+    if (!(step_eps >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": step_eps must be >= 0 (and not NaN)");
+    if (iters < 0 || iters > 64) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": iters must be in 0..64");
+    if (min_points < 6) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_points must be >= 6 (a pose has six degrees of freedom)");
+    if ((uintptr_t)depth % 2 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth must be 2-byte aligned");
+    if ((uintptr_t)xyz % 4 != 0 || (uintptr_t)normals % 4 != 0 || (uintptr_t)poses_in % 4 != 0 || (uintptr_t)poses_out % 4 != 0 ||
+        (uintptr_t)stats % 4 != 0 || (uintptr_t)sums29 % 4 != 0 || (uintptr_t)residuals % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": xyz, normals, the poses, stats, sums29 and residuals must be 4-byte aligned");
+    return VORS_OK;
+}
+
+uint64_t vors_icp_workspace_bytes(int n, int capacity) { return n < 1 || capacity < 1 ? 0 : (uint64_t)icp_workspace_bytes(n, capacity); }
+
+vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity, const void* d_ranges,
+                            size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth,
+                            const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters,
+                            int min_points, void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
+                            void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: n must be >= 1");
+    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: a list (d_list_counts) is NULL");
+    vors_status st = icp_refusals("icp_points", d_xyz, d_normals, d_poses7_in, d_depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
+                                  step_eps, iters, min_points, d_poses7_out, d_stats, d_sums29, d_residuals);
+    if (st != VORS_OK) return st;
+    if (!d_workspace) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: d_workspace is NULL (the pass allocates nothing: vors_icp_workspace_bytes)");
+    if ((st = list_stride_refusals("icp_points", pose_stride_bytes, range_stride_bytes)) != VORS_OK) return st;
+    if ((uintptr_t)d_ranges % 4 != 0 || (uintptr_t)d_list_counts % 4 != 0 || (uintptr_t)d_workspace % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: d_ranges, d_list_counts and d_workspace must be 4-byte aligned");
+    if ((st = require_device()) != VORS_OK) return st;
+    IcpCall call{};
+    call.n = n;
+    call.xyz = d_xyz;
+    call.normals = d_normals;
+    call.list_counts = d_list_counts;
+    call.capacity = capacity;
+    call.ranges = static_cast<const uint8_t*>(d_ranges);
+    call.range_stride = range_stride_bytes ? (int)range_stride_bytes : 8;
+    call.poses_in = static_cast<const float*>(d_poses7_in);
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
+    call.depth = d_depth;
+    call.k = intr_from_cam5(cam5);
+    call.rows = rows;
+    call.cols = cols;
+    call.depth_scale = depth_scale;
+    call.dist_m = dist_m;
+    call.damping = damping;
+    call.step_eps = step_eps;
+    call.iters = iters;
+    call.min_points = (uint32_t)min_points;
+    // the workspace: partials, chunk counts, state (engine.h icp_workspace_bytes)
+    const size_t slots = (size_t)n * icp_chunks(capacity);
+    call.partials = static_cast<float*>(d_workspace);
+    call.chunk_counts = reinterpret_cast<uint32_t*>(call.partials + slots * VORS_ICP_SUMS);
+    call.state = reinterpret_cast<IcpState*>(call.chunk_counts + slots);
+    call.poses_out = d_poses7_out;
+    call.stats = d_stats;
+    call.sums29 = d_sums29;
+    call.residuals = d_residuals;
+    launch_icp_points(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
+                                 const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale,
+                                 float dist_m, float damping, float step_eps, int iters, int min_points, float pose7_out[7], vors_icp_stats* stats,
+                                 float sums29[29], float* residuals) {
+    vors_status st = icp_refusals("icp_points_host", xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
+                                  step_eps, iters, min_points, pose7_out, stats, sums29, residuals);
+    if (st != VORS_OK) return st;
+    const Intr k = intr_from_cam5(cam5);
+    uint32_t first, last;
+    icp_range(count, capacity, range2, &first, &last);
+    const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
+    std::vector<float> v((size_t)VORS_ICP_CHUNK * VORS_ICP_SUMS);
+    float sums[VORS_ICP_SUMS];
+    uint32_t matched = 0;
+    // one evaluation at `pose`: per chunk the slots, the halving tree, then the chunk sums in ascending order (the text of icp_eval_kernel
+    // and icp_solve_kernel)
+    auto evaluate = [&](const Iso& pose, float* res) {
+        for (int q = 0; q < VORS_ICP_SUMS; ++q) sums[q] = 0.0f;
+        matched = 0;
+        for (uint32_t chunk = 0; chunk < nchunks; ++chunk) {
+            const uint32_t base = first + chunk * VORS_ICP_CHUNK;
+            for (uint32_t s = 0; s < VORS_ICP_CHUNK; ++s) {
+                float a[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                const uint32_t rank = base + s;
+                if (rank < last) {
+                    const float* p = xyz + 3 * (size_t)rank;
+                    const float* nn = normals + 3 * (size_t)rank;
+                    const IcpLanding l = icp_landing(k, pose, V3{p[0], p[1], p[2]}, cols, rows);
+                    const uint16_t d = depth[l.lands ? (size_t)l.y * (size_t)cols + (size_t)l.x : 0];
+                    const bool m = icp_row(k, depth_scale, dist_m, pose, l, V3{nn[0], nn[1], nn[2]}, d, a);
+                    matched += m ? 1u : 0u;
+                    if (res) res[rank] = m ? a[0] : nanf("");
+                }
+                icp_products(a, v.data() + (size_t)s * VORS_ICP_SUMS);
+            }
+            for (uint32_t w = VORS_ICP_CHUNK / 2; w >= 1; w /= 2)
+                for (uint32_t s = 0; s < w; ++s)
+                    for (int q = 0; q < VORS_ICP_SUMS; ++q) v[(size_t)s * VORS_ICP_SUMS + q] = v[(size_t)s * VORS_ICP_SUMS + q] + v[(size_t)(s + w) * VORS_ICP_SUMS + q];
+            for (int q = 0; q < VORS_ICP_SUMS; ++q) sums[q] = chunk == 0 ? v[q] : sums[q] + v[q];
+        }
+    };
+    Iso pose = iso_load(pose7_in);
+    vors_icp_stats o{VORS_ICP_ITERATIONS, 0u, last - first, 0u, 0.0f, 0.0f};
+    for (int it = 0; it < iters; ++it) {
+        evaluate(pose, nullptr);
+        float step_norm = 0.0f;
+        const IcpStatus verdict = icp_round(sums, matched, (uint32_t)min_points, damping, step_eps, &pose, &step_norm);
+        if (verdict == ICP_ITERATIONS || verdict == ICP_CONVERGED) {
+            o.iterations += 1u;
+            o.last_step_norm = step_norm;
+        }
+        if (verdict != ICP_ITERATIONS) {  // frozen
+            o.status = (uint32_t)verdict;
+            break;
+        }
+    }
+    evaluate(pose, residuals);
+    o.matched = matched;
+    o.rms = sqrtf(sums[0] / (float)matched);
+    iso_store(pose, pose7_out);
+    if (stats) *stats = o;
+    if (sums29) icp_sums29(sums, matched, sums29);
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------
 void vors_se3_exp(const float xi[6], float out_iso7[7]) { iso_store(se3_exp(xi), out_iso7); }

@@ -25,6 +25,7 @@ MAX_LEVELS = 8
 RESIDUAL_BINS = 256  # VORS_RESIDUAL_BINS
 RENDER_COUNTS = 4  # VORS_RENDER_COUNTS: considered, in front, landed, covered
 NORMAL_COUNTS = 3  # VORS_NORMAL_COUNTS: considered, with depth, with a normal
+ICP_ITERATIONS, ICP_CONVERGED, ICP_TOO_FEW, ICP_SINGULAR = 0, 1, 2, 3  # VORS_ICP_*: vors_icp_stats.status
 
 ROW_MAJOR, COL_MAJOR = 0, 1
 CANDIDATES_COARSE_TO_FINE, CANDIDATES_DENSE, CANDIDATES_DSO = 0, 1, 2
@@ -110,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_fuse_depth", "vors_fuse_depth_pixels",
     "vors_render_points", "vors_render_points_host", "vors_trackers_render_map",
     "vors_depth_normals", "vors_points_normals", "vors_depth_normals_host", "vors_trackers_enable_map_normals", "vors_trackers_map_normals",
+    "vors_icp_workspace_bytes", "vors_icp_points", "vors_icp_points_host", "vors_trackers_icp_map",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
@@ -199,6 +201,11 @@ def lib():
         _lib.vors_trackers_map_normals.argtypes = [vp, C.POINTER(vp)]
         _lib.vors_tracker_enable_map_normals.argtypes = [vp, i, f]
         _lib.vors_tracker_read_map_normals.argtypes = [vp, i, vp]
+        _lib.vors_icp_workspace_bytes.argtypes = [i, i]
+        _lib.vors_icp_workspace_bytes.restype = C.c_uint64
+        _lib.vors_icp_points.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, i, i, f, f, f, f, i, i, vp, vp, vp, vp, vp, vp]
+        _lib.vors_icp_points_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, vp, vp, vp]
+        _lib.vors_trackers_icp_map.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -1155,6 +1162,27 @@ class Trackers:
         self._render_refs = (poses, ranges)
         return _render_result(bufs, zkey, depth, gray, counts)
 
+    def icp_map(self, depth, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6, poses=None, ranges=None, workspace=None, stats=True,
+                sums29=False, residuals=False):
+        """The keyframe map aligned to one depth frame per sequence (vors_trackers_icp_map): icp_points() on the handle's own map and map
+        normals with its level-0 intrinsics, on the current stream, not synchronised. depth [n, rows, cols] int16 tensor holding the u16
+        payload; poses None = every sequence's current frame pose, read on the device. The tracker itself is only read. Everything else,
+        and the result, as in icp_points()."""
+        import torch
+        self._check_frames(depth, depth)
+        if depth.dtype != torch.int16:
+            raise VorsError("icp_map: depth int16 [n, rows, cols], contiguous")
+        dev = _torch_device(self._device)
+        poses, pose_stride = _render_poses(poses, self.n)
+        rng, range_stride = _render_ranges(ranges, self.n)
+        cap = self._map[1]
+        ws, bufs = _icp_buffers(self.n, cap, dev, workspace, stats, sums29, residuals)
+        _check(lib().vors_trackers_icp_map(self._h, Batch._dp(depth), float(dist_m), float(damping), float(step_eps), int(iters), int(min_points),
+                                           rng, range_stride, Batch._dp(poses), pose_stride, Batch._dp(ws), *[Batch._dp(t) for t in bufs],
+                                           Batch._stream()))
+        self._icp_refs = (depth, poses, ranges, ws)
+        return _icp_result(bufs, stats, sums29, residuals)
+
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
 
@@ -1519,6 +1547,107 @@ def depth_normals_host(depth, cam5, depth_scale, step, jump_m, pose7=None, pixel
     out = dict(normals=normals, counts=np.zeros(NORMAL_COUNTS, np.uint32))
     _check(lib().vors_depth_normals_host(_ptr(d), _ptr(k), rows, cols, float(depth_scale), int(step), float(jump_m), _ptr(pose), _ptr(px),
                                          cap if count is None else int(count), cap, _ptr(rng), _ptr(normals), _ptr(out["counts"])))
+    return out
+
+
+class vors_icp_stats(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("considered", C.c_uint32), ("matched", C.c_uint32), ("rms", C.c_float),
+                ("last_step_norm", C.c_float)]
+
+
+ICP_STATS_DTYPE = np.dtype([("status", "<u4"), ("iterations", "<u4"), ("considered", "<u4"), ("matched", "<u4"), ("rms", "<f4"),
+                            ("last_step_norm", "<f4")])
+assert ICP_STATS_DTYPE.itemsize == C.sizeof(vors_icp_stats) == 24
+
+
+def decode_icp_stats(stats):
+    """The "stats" tensor of icp_points() ([n, 24] uint8: the vors_icp_stats records as bytes) -> a structured numpy array [n]."""
+    return np.ascontiguousarray(stats.cpu().numpy()).view(ICP_STATS_DTYPE).reshape(-1)
+
+
+def icp_workspace_bytes(n, capacity):
+    """Bytes of the workspace icp_points() needs for n lists of `capacity` (vors_icp_workspace_bytes)."""
+    return int(lib().vors_icp_workspace_bytes(int(n), int(capacity)))
+
+
+def _icp_buffers(n, cap, dev, workspace, stats, sums29, residuals):
+    """The workspace (None = a new one) and the output arguments of an ICP pass (_out_buf) -> (workspace, (poses, stats, sums29, residuals))."""
+    import torch
+    need = icp_workspace_bytes(n, cap)
+    if workspace is None:
+        workspace = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise VorsError(f"icp: expected a contiguous uint8 workspace of at least {need} bytes")
+    bufs = (torch.empty((n, 7), dtype=torch.float32, device=dev), _out_buf(stats, (n, ICP_STATS_DTYPE.itemsize), torch.uint8, dev),
+            _out_buf(sums29, (n, 29), torch.float32, dev), _out_buf(residuals, (n, cap), torch.float32, dev))
+    if residuals is True:
+        bufs[3].fill_(float("nan"))
+    return workspace, bufs
+
+
+def _icp_result(bufs, stats, sums29, residuals):
+    return _result(("poses", True, bufs[0]), ("stats", _asked(stats), bufs[1]), ("sums29", _asked(sums29), bufs[2]),
+                   ("residuals", _asked(residuals), bufs[3]))
+
+
+def icp_points(xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6,
+               ranges=None, workspace=None, stats=True, sums29=False, residuals=False):
+    """Point-to-plane ICP of n world-frame point lists with normals against one level-0 depth plane each (vors_icp_points; handle-free)
+    -> dict of tensors on the current stream, not synchronised: "poses" [n, 7] float32, the refined camera -> world poses; "stats"
+    [n, 24] uint8 (the vors_icp_stats records as bytes: decode_icp_stats()); "sums29" [n, 29] float32 of the final evaluation (the layout
+    of Batch.eval_level, for pose_information_from_sums); "residuals" [n, capacity] float32, NaN = not matched, exactly the ranks of each
+    list's clipped range written (a new tensor is filled with NaN first). xyz / normals [n, capacity, 3] float32 and list_counts [n] int32:
+    the tensors of Trackers.map() / map_normals() or Batch.point_cloud() / points_normals(). depth [n, rows, cols] int16 tensor holding
+    the u16 payload; poses [n, 7] float32 (or a track's out_stats bytes), required; ranges: see _render_ranges. iters = 0 evaluates at
+    the given poses. workspace: a uint8 tensor of icp_workspace_bytes(n, capacity) to reuse (None = a new one). stats / sums29 /
+    residuals may also be a tensor of that shape to write into."""
+    import torch
+    n = xyz.shape[0]
+    cap = xyz.shape[1] if xyz.dim() == 3 else -1
+    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or normals.dtype != torch.float32
+            or not normals.is_contiguous() or tuple(normals.shape) != (n, cap, 3) or list_counts.dtype != torch.int32
+            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
+        raise VorsError("icp_points: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
+    if depth.dtype != torch.int16 or depth.dim() != 3 or depth.shape[0] != n or not depth.is_contiguous():
+        raise VorsError("icp_points: depth int16 [n, rows, cols], contiguous")
+    if poses is None:
+        raise VorsError("icp_points: poses are required")
+    k = _normals_common(cam5, "icp_points")
+    poses, pose_stride = _render_poses(poses, n)
+    rng, range_stride = _render_ranges(ranges, n)
+    ws, bufs = _icp_buffers(n, cap, xyz.device, workspace, stats, sums29, residuals)
+    _check(lib().vors_icp_points(n, Batch._dp(xyz), Batch._dp(normals), Batch._dp(list_counts), cap, rng, range_stride, Batch._dp(poses),
+                                 pose_stride, Batch._dp(depth), _ptr(k), depth.shape[1], depth.shape[2], float(depth_scale), float(dist_m),
+                                 float(damping), float(step_eps), int(iters), int(min_points), Batch._dp(ws), *[Batch._dp(t) for t in bufs],
+                                 Batch._stream()))
+    return _icp_result(bufs, stats, sums29, residuals)
+
+
+def icp_points_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6, count=None,
+                    range2=None, residuals=None):
+    """The loop of icp_points for ONE list on the host (vors_icp_points_host; needs no GPU; the texts and the order of sums the kernels
+    run): xyz / normals [capacity, 3] float32, depth [rows, cols] uint16, pose7 camera -> world -> dict: "pose" [7] float32, "stats" (a
+    structured scalar of ICP_STATS_DTYPE), "sums29" [29] float32, "residuals" [capacity] float32 with only the ranks of the clipped range
+    written (`residuals`: an array to write into, None = one filled with NaN). count = the list's count (None = capacity; above it:
+    clipped), range2 = (first, count) or None."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(depth, np.uint16)
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+    if len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,)):
+        raise VorsError("icp_points_host: xyz and normals [capacity, 3], depth [rows, cols], cam5 [5], pose7 [7], range2 [2] or None")
+    if residuals is None:
+        residuals = np.full(len(p), np.nan, np.float32)
+    elif residuals.dtype != np.float32 or residuals.shape != (len(p),) or not residuals.flags.c_contiguous:
+        raise VorsError(f"icp_points_host: residuals must be a contiguous float32 array ({len(p)},)")
+    stats = np.zeros(1, ICP_STATS_DTYPE)
+    out = dict(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), residuals=residuals)
+    _check(lib().vors_icp_points_host(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, len(p) if count is None else int(count), len(p),
+                                      _ptr(rng), _ptr(pose), _ptr(d), _ptr(k), d.shape[0], d.shape[1], float(depth_scale), float(dist_m),
+                                      float(damping), float(step_eps), int(iters), int(min_points), _ptr(out["pose"]), _ptr(stats),
+                                      _ptr(out["sums29"]), _ptr(residuals)))
     return out
 
 
