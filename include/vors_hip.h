@@ -123,7 +123,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_trackers_map_voxels, vors_tracker_enable_map_voxels, vors_tracker_read_map_voxels, vors_voxel_keys,
                               *    VORS_VOXEL_NONE, likewise; + vors_render_points, vors_render_points_host, vors_trackers_render_map,
                               *    vors_tracker_render_map, VORS_RENDER_COUNTS, likewise; + vors_icp_points, vors_icp_points_host,
-                              *    vors_icp_workspace_bytes, vors_trackers_icp_map, vors_icp_stats, likewise) */
+                              *    vors_icp_workspace_bytes, vors_trackers_icp_map, vors_icp_stats, likewise; + vors_icp_points_robust,
+                              *    vors_icp_points_robust_host, vors_trackers_icp_map_robust, VORS_ICP_GATE_COUNTS, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -345,6 +346,15 @@ vors_status vors_trackers_icp_map(vors_trackers* t, const uint16_t* d_depth, flo
                                   const void* d_poses7_in /* nullable */, size_t pose_stride_bytes, void* d_workspace,
                                   float* d_poses7_out, struct vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
                                   float* d_residuals /* nullable */, void* hip_stream);
+/* ... and the robust pass (vors_icp_points_robust, section 2e) on the same inputs: d_frame_normals [n][rows * cols][3] f32 (DEVICE,
+ * nullable; vors_depth_normals of d_depth at level 0 without poses), min_cos, huber_m and d_gate_counts [n][4] u32 (nullable) as there.
+ * The same checks, then every refusal of vors_icp_points_robust. Reads the handle only. */
+vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters,
+                                         int min_points, const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                                         const void* d_poses7_in /* nullable */, size_t pose_stride_bytes,
+                                         const float* d_frame_normals /* nullable */, float min_cos, float huber_m, void* d_workspace,
+                                         float* d_poses7_out, struct vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
+                                         float* d_residuals /* nullable */, uint32_t* d_gate_counts /* nullable */, void* hip_stream);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -841,6 +851,43 @@ vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_
                                  const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale,
                                  float dist_m, float damping, float step_eps, int iters, int min_points,
                                  float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals);
+/* THE ROBUST PASS: vors_icp_points with two optional remedies against foreign surfaces inside the distance gate. Every
+ * argument up to min_points as in vors_icp_points, then:
+ * d_frame_normals (nullable = no normal gate): [n][rows * cols][3] f32 in the CAMERA frame — the output of vors_depth_normals on the same
+ *   d_depth with d_poses7 = NULL; three zeros = no normal. NORMAL GATE: after the tests above (lands, model normal present, d != 0, the
+ *   distance gate) and with n = conj(T.q) * nw, nf = N[y][x] at the landing pixel: MATCHED only if nf is not three zeros and
+ *   dot3(n, nf) >= min_cos in float (NaN fails). Both normals face their camera, so any min_cos > 0 culls a back-facing model point.
+ * huber_m (0 = off; > 0 = the threshold in metres): the LM kernels' Huber convention (huber_delta) on the point-to-plane residual:
+ *   ar = fabsf(r), lin = ar <= huber_m, w = lin ? 1.0f : huber_m / ar, e = lin ? r * r : huber_m * (2.0f * ar - huber_m), wr = w * r; the
+ *   28 products are e, J[i] * wr, w * (J[i] * J[j]) in the slots above. Slot 0 of d_sums29, and hence stats.rms =
+ *   sqrtf(sums[0] / matched), is then the HUBER LOSS, not the sum of squares — as huber_delta makes the trackers' energy. d_residuals
+ *   stays the raw r, unweighted, NaN for unmatched points.
+ * d_gate_counts (nullable): [n][VORS_ICP_GATE_COUNTS] u32 of the FINAL evaluation over the clipped range: [0] with_depth — lands, model
+ *   normal present, d != 0; [1] within_dist — also inside the distance gate; [2] matched — also passes the normal gate (= stats.matched);
+ *   [3] huber_linear — matched with |r| > huber_m (0 when Huber is off). Cleared by a memset when asked for; every workgroup of the final
+ *   evaluation adds once per counter with an INTEGER atomic (the order of arrival cannot matter; no floating-point atomic exists).
+ * The order of the sums, the loop, the freezing, the statuses, the stats and the workspace (vors_icp_workspace_bytes, unchanged) are
+ * vors_icp_points', word for word. d_frame_normals = NULL and huber_m = 0 reproduce vors_icp_points bit for bit in every output; the
+ * device equals vors_icp_points_robust_host bit for bit, gate counts included.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued or written: everything vors_icp_points refuses; min_cos NaN or outside
+ * [-1, 1]; huber_m negative or NaN; d_frame_normals or d_gate_counts off 4-byte alignment. */
+#define VORS_ICP_GATE_COUNTS 4
+vors_status vors_icp_points_robust(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
+                                   const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                                   const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth,
+                                   const float cam5[5], int rows, int cols, float depth_scale,
+                                   float dist_m, float damping, float step_eps, int iters, int min_points,
+                                   const float* d_frame_normals /* nullable */, float min_cos, float huber_m, void* d_workspace,
+                                   float* d_poses7_out, vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
+                                   float* d_residuals /* nullable */, uint32_t* d_gate_counts /* nullable */, void* hip_stream);
+/* ... and its host twin for ONE list: vors_icp_points_host's arguments, frame_normals [rows * cols][3] (nullable), gate_counts[4]
+ * (nullable). The same lie.h texts and the same tree as the kernels. */
+vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
+                                        const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols,
+                                        float depth_scale, float dist_m, float damping, float step_eps, int iters, int min_points,
+                                        const float* frame_normals /* nullable */, float min_cos, float huber_m,
+                                        float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
+                                        uint32_t gate_counts[VORS_ICP_GATE_COUNTS] /* nullable */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

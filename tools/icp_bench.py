@@ -12,7 +12,12 @@ Byte model of an evaluation: 12 + 12 B per point read, a 2 B gather; the partial
 HIP events around one call; a block = the median of 20 calls after 3 warm-up calls; the blocks of all legs alternate for `--blocks` rounds,
 so the figure of a leg is the median of its block medians and its run-to-run spread their range. No threshold is fixed.
 
-  python tools/icp_bench.py [--lists N] [--blocks K] [--out FILE]
+--robust times the robust pass instead (vors_icp_points_robust) and writes profiles/icp_robust_summary.md: per list length
+the pass at iters 0 and at iters 8 in four forms — the plain pass, robust neutral (no frame normals, no Huber), robust with the normal
+gate, robust with the gate and Huber — all in the same run, their blocks alternating. The frame normals are vors_depth_normals' of the
+frames. Byte model of an evaluation: 26 B per point, 38 B with the 12 B gather of the frame normal.
+
+  python tools/icp_bench.py [--robust] [--lists N] [--blocks K] [--out FILE]
 """
 import argparse
 import os
@@ -53,6 +58,25 @@ def measure(a):
         def icp(iters, xyz=xyz, nrm=nrm, counts=counts, ws=ws, stats=stats):
             return V.icp_points(xyz, nrm, counts, depth, intr, V.DEPTH_SCALE, poses, 0.05, step_eps=0.0, iters=iters, workspace=ws, stats=stats)
 
+        if a.robust:
+            frame_normals = V.depth_normals(depth, intr, V.DEPTH_SCALE, 1, 0.05)["normals"]
+            forms = {"plain": None, "robust neutral": dict(), "robust, normal gate": dict(frame_normals=frame_normals, min_cos=0.8),
+                     "robust, normal gate + Huber": dict(frame_normals=frame_normals, min_cos=0.8, huber_m=0.005)}
+            for form, kw in forms.items():
+                def run(iters, kw=kw, xyz=xyz, nrm=nrm, counts=counts, ws=ws, stats=stats):
+                    if kw is None:
+                        return icp(iters, xyz, nrm, counts, ws, stats)
+                    return V.icp_points_robust(xyz, nrm, counts, depth, intr, V.DEPTH_SCALE, poses, 0.05, step_eps=0.0, iters=iters, workspace=ws,
+                                               stats=stats, **kw)
+                run(8)
+                torch.cuda.synchronize()
+                st = V.decode_icp_stats(stats)
+                matched[size, form] = (int(st["matched"].min()), int(st["matched"].max()), sorted(set(st["iterations"].tolist())),
+                                       sorted(set(st["status"].tolist())))
+                model = n * size * (38 if kw and "frame_normals" in kw else 26) + n * ((size + 1023) // 1024) * 116
+                legs[f"{size} points, {form}: pass at iters 0"] = (lambda run=run: run(0), model)
+                legs[f"{size} points, {form}: pass at iters 8"] = (lambda run=run: run(8), 9 * model)
+            continue
         icp(8)
         torch.cuda.synchronize()
         st = V.decode_icp_stats(stats)
@@ -70,13 +94,41 @@ def measure(a):
     return [(name, float(np.median(meds[name])), min(meds[name]), max(meds[name]), legs[name][1]) for name in legs], matched
 
 
+def report_robust(a, rows, matched):
+    lines = ["# Robust point-to-plane ICP: vors_icp_points_robust beside vors_icp_points", "",
+             f"`python tools/icp_bench.py --robust --lists {a.lists} --blocks {a.blocks}` on one MI355X: {a.lists} lists against {a.lists} planes "
+             f"of {COLS}x{ROWS}; medians of {a.blocks} alternating blocks of 20 calls (range of the block medians in brackets). Byte model of "
+             "an evaluation: 26 B per point, 38 B with the gather of the frame normal.", "",
+             "| leg | ms | range, ms | bytes of the model | GB/s of the model |", "|---|---|---|---|---|"]
+    by = {}
+    for name, med, lo, hi, nbytes in rows:
+        by[name] = (med, lo, hi, nbytes)
+        lines.append(f"| {name} | {med:.4f} | {lo:.4f} .. {hi:.4f} | {nbytes} | {nbytes / med / 1e6:.0f} |")
+    lines += ["", "One round (an evaluation launch and a solve launch) = (pass at iters 8 - pass at iters 0) / 8, from the medians; the "
+              "spread is that of the pass at iters 8 over 8:", ""]
+    for (size, form), (lo, hi, its, sts) in matched.items():
+        t0, _, _, m = by[f"{size} points, {form}: pass at iters 0"]
+        t8, lo8, hi8, _ = by[f"{size} points, {form}: pass at iters 8"]
+        lines.append(f"- {size} points, {form}: {(t8 - t0) / 8:.4f} ms (spread {(hi8 - lo8) / 8:.4f}), {m / ((t8 - t0) / 8) / 1e9:.2f} TB/s of the "
+                     f"model; matched per list {lo} .. {hi}, updates {its}, statuses {sts}")
+    text = "\n".join(lines) + "\n"
+    with open(a.out, "w") as f:
+        f.write(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lists", type=int, default=SEQS)
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "icp_summary.md"))
+    ap.add_argument("--robust", action="store_true")
     a = ap.parse_args()
+    if a.robust and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "icp_robust_summary.md")
     rows, matched = measure(a)
+    if a.robust:
+        return report_robust(a, rows, matched)
     lines = ["# Point-to-plane ICP: vors_icp_points", "",
              f"`python tools/icp_bench.py --lists {a.lists} --blocks {a.blocks}` on one MI355X: {a.lists} lists against {a.lists} planes of "
              f"{COLS}x{ROWS}; medians of {a.blocks} alternating blocks of 20 calls (range of the block medians in brackets).", "",

@@ -553,9 +553,18 @@ constexpr size_t icp_chunks(int capacity) { return ((size_t)capacity + VORS_ICP_
 inline size_t icp_workspace_bytes(int n, int capacity) {
     return (size_t)n * (icp_chunks(capacity) * (VORS_ICP_SUMS + 1) * 4 + sizeof(IcpState));
 }
+// What the robust pass (vors_icp_points_robust; lie.h icp_row_robust / icp_products_robust) reads and writes beyond IcpCall. A record of
+// its own: icp_begin_kernel, icp_solve_kernel and the plain evaluation kernels take IcpCall by value, and their arguments stay as they are.
+struct IcpRobust {
+    const float* frame_normals;  // [n][rows * cols][3], camera frame, three zeros = no normal; nullable = no normal gate
+    float min_cos;
+    float huber_m;               // 0 = no Huber weight
+    uint32_t* gate_counts;       // [n][VORS_ICP_GATE_COUNTS] of the final evaluation, nullable
+};
 // The state's start, then per round one evaluation and one solve launch, then the final evaluation and the launch that writes the
-// outputs: enqueued on s in this order, not synchronised, no allocation.
-void launch_icp_points(const IcpCall& call, hipStream_t s);
+// outputs: enqueued on s in this order, not synchronised, no allocation. robust: NULL = the plain pass (vors_icp_points); otherwise the
+// robust evaluation kernels, instantiated on (frame normals given, huber_m > 0), after a memset of the gate counts when they are asked for.
+void launch_icp_points(const IcpCall& call, const IcpRobust* robust, hipStream_t s);
 
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.

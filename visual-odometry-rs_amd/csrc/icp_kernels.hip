@@ -15,6 +15,8 @@
 // SOLVE  (icp_solve_kernel): one wavefront per list. Lanes 0..27 own one sum each and add the chunk partials in ascending order from
 //        chunk 0's, eight loads issued ahead of the eight dependent adds; lanes 32..63 add the integer counts. Every lane then holds all
 //        28 sums (__shfl) and runs the verdict; lane 0 stores. The final launch writes the outputs instead.
+// vors_icp_points_robust / vors_trackers_icp_map_robust run the same launches with icp_eval_robust_kernel in EVAL's place:
+// lie.h icp_row_robust / icp_products_robust, a gather of the frame normal beside the depth's, and the gate counts of the final evaluation.
 #include "device_common.h"
 
 namespace vors {
@@ -141,6 +143,152 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_eval_kernel(IcpEvalArgs a) {
     }
 }
 
+struct IcpRobustEvalArgs {
+    int seq0;
+    IcpCall c;
+    IcpRobust r;
+};
+
+// The evaluation of the robust pass (vors_icp_points_robust): icp_eval_kernel's trip, grid, tree and stores with the rule
+// lie.h icp_row_robust<NORMALS> / icp_products_robust<HUBER>. A kernel of its own text, not a shared body: with one, the compiler
+// scheduled the plain kernels differently, and their code is to stay what it was. The frame normal of a point is gathered together with
+// its depth — 12 bytes at the landing pixel, pixel 0 without a landing — ahead of the rows that consume it, not behind the distance
+// gate. Gate counts (FINAL, when asked for): a thread counts over its trips; after the last one the workgroup reduces across its
+// wavefronts and adds once per counter with an integer atomic. A workgroup without a chunk adds nothing.
+template <bool FINAL, bool RESID, bool NORMALS, bool HUBER>
+__global__ __launch_bounds__(ICP_BLOCK) void icp_eval_robust_kernel(IcpRobustEvalArgs a) {
+    __shared__ float lds[VORS_ICP_SUMS * 128];
+    __shared__ uint32_t lds_counts[ICP_BLOCK / 64];
+    __shared__ uint32_t lds_gates[VORS_ICP_GATE_COUNTS * (ICP_BLOCK / 64)];
+    const IcpCall& c = a.c;
+    const IcpRobust& rb = a.r;
+    const int seq = a.seq0 + blockIdx.y;
+    const IcpState& st = c.state[seq];
+    if (!FINAL && st.frozen) return;  // the whole workgroup
+    uint32_t first, last;
+    icp_list_range(c, seq, &first, &last);
+    // (last - first <= capacity < 2^31: nothing below wraps)
+    const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
+    if (blockIdx.x >= nchunks) return;  // the whole workgroup
+    const size_t cap_chunks = icp_chunks(c.capacity);
+    const float* xyz = c.xyz + (size_t)seq * (size_t)c.capacity * 3;
+    const float* normals = c.normals + (size_t)seq * (size_t)c.capacity * 3;
+    const uint16_t* depth = c.depth + (size_t)seq * (size_t)c.rows * (size_t)c.cols;
+    const Iso pose = iso_load(st.pose);
+    const unsigned t = threadIdx.x, wave = t >> 6;
+    const float* frame_normals = nullptr;
+    if constexpr (NORMALS) frame_normals = rb.frame_normals + (size_t)seq * (size_t)c.rows * (size_t)c.cols * 3;
+    uint32_t gates[VORS_ICP_GATE_COUNTS] = {0u, 0u, 0u, 0u};
+    for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const uint32_t base = first + chunk * VORS_ICP_CHUNK;
+        V3 w[4], nw[4];
+        bool valid[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t rank = base + j * ICP_BLOCK + t;
+            valid[j] = rank < last;
+            const size_t o = 3 * (size_t)(valid[j] ? rank : base);  // (a slot beyond the range reads the chunk's first row: a safe address)
+            w[j] = V3{xyz[o], xyz[o + 1], xyz[o + 2]};
+            nw[j] = V3{normals[o], normals[o + 1], normals[o + 2]};
+        }
+        IcpLanding l[4];
+        uint16_t d[4];
+        V3 nf[4] = {};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            l[j] = icp_landing(c.k, pose, w[j], c.cols, c.rows);
+            l[j].lands = l[j].lands && valid[j];
+            const int pixel = l[j].lands ? l[j].y * c.cols + l[j].x : 0;  // (no landing: pixel 0, a safe address; the row ignores it)
+            d[j] = depth[pixel];
+            if constexpr (NORMALS) {
+                const float* f = frame_normals + 3 * (size_t)pixel;
+                nf[j] = V3{f[0], f[1], f[2]};
+            }
+        }
+        float row[4][7];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const IcpGate g = icp_row_robust<NORMALS>(c.k, c.depth_scale, c.dist_m, rb.min_cos, pose, l[j], nw[j], d[j], nf[j], row[j]);
+            const bool m = g == ICP_GATE_MATCHED;
+            if constexpr (FINAL) {
+                gates[0] += g >= ICP_GATE_DEPTH ? 1u : 0u;
+                gates[1] += g >= ICP_GATE_DIST ? 1u : 0u;
+                gates[2] += m ? 1u : 0u;
+            }
+            cnt += m ? 1u : 0u;
+            if constexpr (RESID)
+                if (valid[j]) c.residuals[(size_t)seq * (size_t)c.capacity + (base + j * ICP_BLOCK + t)] = m ? row[j][0] : __builtin_nanf("");
+        }
+        // w = 512, 256: (slot t + slot t + 512) + (slot t + 256 + slot t + 768)
+        float acc[VORS_ICP_SUMS], p[VORS_ICP_SUMS], q[VORS_ICP_SUMS];
+        // (a row's products; the final evaluation counts the points that lie on Huber's linear branch)
+        auto products = [&](const float* r7, float* o) {
+            const bool linear = icp_products_robust<HUBER>(r7, rb.huber_m, o);
+            if constexpr (FINAL && HUBER) gates[3] += linear ? 1u : 0u;
+        };
+        products(row[0], p);
+        products(row[2], q);
+#pragma unroll
+        for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = p[k] + q[k];
+        products(row[1], p);
+        products(row[3], q);
+#pragma unroll
+        for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + (p[k] + q[k]);
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, sh);
+        if ((t & 63) == 0) lds_counts[wave] = cnt;
+        // w = 128: threads 128..255 hand over
+        if (wave >= 2) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) lds[k * 128 + (t - 128)] = acc[k];
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + lds[k * 128 + t];
+        }
+        __syncthreads();
+        // w = 64: threads 64..127 hand over
+        if (wave == 1) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) lds[k * 128 + (t - 64)] = acc[k];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + lds[k * 128 + t];
+            // w = 32..1: lane s takes lane s + w's (lanes >= w compute values nobody reads)
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) {
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + __shfl_down(acc[k], sh);
+            }
+            if (t == 0) {
+                float* out = c.partials + ((size_t)seq * cap_chunks + chunk) * VORS_ICP_SUMS;
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) out[k] = acc[k];
+                c.chunk_counts[(size_t)seq * cap_chunks + chunk] = (lds_counts[0] + lds_counts[1]) + (lds_counts[2] + lds_counts[3]);
+            }
+        }
+        __syncthreads();  // (the next trip writes the LDS again)
+    }
+    if constexpr (FINAL) {
+        if (!rb.gate_counts) return;  // the whole workgroup
+#pragma unroll
+        for (int g = 0; g < VORS_ICP_GATE_COUNTS; ++g) {
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) gates[g] += (uint32_t)__shfl_xor((int)gates[g], sh);
+            if ((t & 63) == 0) lds_gates[g * (ICP_BLOCK / 64) + wave] = gates[g];
+        }
+        __syncthreads();
+        if (t < VORS_ICP_GATE_COUNTS) {
+            const uint32_t* v = lds_gates + t * (ICP_BLOCK / 64);
+            atomicAdd(rb.gate_counts + (size_t)seq * VORS_ICP_GATE_COUNTS + t, (v[0] + v[1]) + (v[2] + v[3]));
+        }
+    }
+}
+
 template <bool FINAL>
 __global__ __launch_bounds__(64) void icp_solve_kernel(IcpCall c) {
     const int seq = blockIdx.x;
@@ -205,15 +353,26 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(IcpCall c) {
     }
 }
 
-void launch_icp_points(const IcpCall& c, hipStream_t s) {
+void launch_icp_points(const IcpCall& c, const IcpRobust* robust, hipStream_t s) {
+    if (robust && robust->gate_counts) (void)hipMemsetAsync(robust->gate_counts, 0, (size_t)c.n * VORS_ICP_GATE_COUNTS * sizeof(uint32_t), s);
     hipLaunchKernelGGL(icp_begin_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, s, c);
     const size_t want = icp_chunks(c.capacity);
     const unsigned chunks = (unsigned)(want > ICP_MAX_CHUNKS ? ICP_MAX_CHUNKS : want);
     IcpEvalArgs a{0, c};
+    IcpRobustEvalArgs ra{0, c, robust ? *robust : IcpRobust{}};
     auto eval = [&](auto final_, auto resid_) {
         for_pair_slices(c.n, [&](int seq0, int ns) {
-            a.seq0 = seq0;
-            hipLaunchKernelGGL((icp_eval_kernel<decltype(final_)::value, decltype(resid_)::value>), dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, a);
+            a.seq0 = ra.seq0 = seq0;
+            if (!robust) {
+                hipLaunchKernelGGL((icp_eval_kernel<decltype(final_)::value, decltype(resid_)::value>), dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, a);
+                return;
+            }
+            with_bool(ra.r.frame_normals != nullptr, [&](auto nrm) {
+                with_bool(ra.r.huber_m > 0.0f, [&](auto hub) {
+                    hipLaunchKernelGGL((icp_eval_robust_kernel<decltype(final_)::value, decltype(resid_)::value, decltype(nrm)::value, decltype(hub)::value>),
+                                       dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, ra);
+                });
+            });
         });
     };
     for (int it = 0; it < c.iters; ++it) {

@@ -591,6 +591,58 @@ VORS_UNROLL
 VORS_UNROLL
         for (int j = i; j < 7; ++j) p[k++] = a[i] * a[j];
 }
+// The robust rule (vors_icp_points_robust): icp_row's tests in icp_row's order and arithmetic, then — NORMALS — the gate
+// against the frame's own normal at the landing pixel, nf (camera frame, vors_depth_normals' output without a pose; three zeros = none):
+// MATCHED only if nf is not three zeros and dot3(n, nf) >= min_cos in float (NaN fails). Both normals face their camera, so any
+// min_cos > 0 culls a back-facing model point. -> the last gate passed, which is what vors_icp_points_robust's gate counts count;
+// ICP_GATE_MATCHED is icp_row's `true`, and only then is the row other than seven +0.0f. NORMALS = false is icp_row's arithmetic.
+enum IcpGate { ICP_GATE_NONE = 0, ICP_GATE_DEPTH = 1, ICP_GATE_DIST = 2, ICP_GATE_MATCHED = 3 };
+template <bool NORMALS>
+VORS_HD IcpGate icp_row_robust(const Intr& k, float depth_scale, float dist_m, float min_cos, const Iso& pose, const IcpLanding& l, const V3& nw,
+                               uint16_t d, const V3& nf, float a[7]) {
+VORS_UNROLL
+    for (int i = 0; i < 7; ++i) a[i] = 0.0f;
+    const bool has_normal = !(nw.x == 0.0f && nw.y == 0.0f && nw.z == 0.0f);
+    if (!l.lands || !has_normal || d == 0) return ICP_GATE_NONE;
+    const V3 q = back_project(k, (float)l.x, (float)l.y, depth_normal_z(depth_scale, d));
+    const V3 e{q.x - l.c.x, q.y - l.c.y, q.z - l.c.z};
+    if (!(dot3(e, e) <= dist_m * dist_m)) return ICP_GATE_DEPTH;
+    const V3 n = quat_rotate(Quat{-pose.q.i, -pose.q.j, -pose.q.k, pose.q.w}, nw);
+    if (NORMALS) {
+        const bool has_frame_normal = !(nf.x == 0.0f && nf.y == 0.0f && nf.z == 0.0f);
+        if (!has_frame_normal || !(dot3(n, nf) >= min_cos)) return ICP_GATE_DIST;
+    }
+    const V3 m = cross(q, n);
+    a[0] = dot3(n, e);
+    a[1] = n.x; a[2] = n.y; a[3] = n.z;
+    a[4] = m.x; a[5] = m.y; a[6] = m.z;
+    return ICP_GATE_MATCHED;
+}
+// The 28 products under the Huber weight of the LM kernels (lm_reference.hip refw_residual2 / refw_products_of), huber_m > 0:
+// ar = |r|, lin = ar <= huber_m, w = lin ? 1 : huber_m / ar, e = lin ? r r : huber_m (2 ar - huber_m), wr = w r; the products are e,
+// J[i] wr, w (J[i] J[j]) in icp_products' slots — slot 0 is then the Huber loss, not the sum of squares. -> the point lies on the
+// linear branch (|r| > huber_m); a row of zeros gives +0.0f everywhere and false. HUBER = false is icp_products' own text.
+template <bool HUBER>
+VORS_HD bool icp_products_robust(const float a[7], float huber_m, float p[VORS_ICP_SUMS]) {
+    if (!HUBER) {
+        icp_products(a, p);
+        return false;
+    }
+    const float r = a[0], ar = fabsf(r);
+    const bool lin = ar <= huber_m;
+    const float w = lin ? 1.0f : huber_m / ar;
+    const float e = lin ? r * r : huber_m * (2.0f * ar - huber_m);
+    const float wr = w * r;
+    int k = 0;
+    p[k++] = e;
+VORS_UNROLL
+    for (int i = 1; i < 7; ++i) p[k++] = a[i] * wr;
+VORS_UNROLL
+    for (int i = 1; i < 7; ++i)
+VORS_UNROLL
+        for (int j = i; j < 7; ++j) p[k++] = w * (a[i] * a[j]);
+    return !lin;
+}
 // The clipped range of ranks of a list (render_splat_kernel's text): count clipped to capacity, range2 (nullable) = (first, count).
 VORS_HD void icp_range(uint32_t count, int capacity, const uint32_t* range2, uint32_t* first, uint32_t* last) {
     const uint32_t n = count < (uint32_t)capacity ? count : (uint32_t)capacity;

@@ -475,22 +475,35 @@ static vors_status icp_refusals(const char* who, const void* xyz, const void* no
     return VORS_OK;
 }
 
+// ... and what the robust entries refuse beyond that
+static vors_status icp_robust_refusals(const char* who, const void* frame_normals, float min_cos, float huber_m, const void* gate_counts) {
+    const std::string w(who);
+    if (!(min_cos >= -1.0f && min_cos <= 1.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_cos must lie in [-1, 1] (and not be NaN)");
+    if (!(huber_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": huber_m must be >= 0 (and not NaN; 0 = no Huber weight)");
+    if ((uintptr_t)frame_normals % 4 != 0 || (uintptr_t)gate_counts % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the frame normals and the gate counts must be 4-byte aligned");
+    return VORS_OK;
+}
+
 uint64_t vors_icp_workspace_bytes(int n, int capacity) { return n < 1 || capacity < 1 ? 0 : (uint64_t)icp_workspace_bytes(n, capacity); }
 
-vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity, const void* d_ranges,
-                            size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth,
-                            const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters,
-                            int min_points, void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
-                            void* hip_stream) {
-    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: n must be >= 1");
-    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: a list (d_list_counts) is NULL");
-    vors_status st = icp_refusals("icp_points", d_xyz, d_normals, d_poses7_in, d_depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
-                                  step_eps, iters, min_points, d_poses7_out, d_stats, d_sums29, d_residuals);
+// The device pass: robust = NULL is vors_icp_points (who = its name in a refusal)
+static vors_status icp_points_device(const char* who, int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
+                                     const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
+                                     const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping,
+                                     float step_eps, int iters, int min_points, const IcpRobust* robust, void* d_workspace, float* d_poses7_out,
+                                     vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, void* hip_stream) {
+    const std::string w(who);
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be >= 1");
+    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (d_list_counts) is NULL");
+    vors_status st = icp_refusals(who, d_xyz, d_normals, d_poses7_in, d_depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping, step_eps,
+                                  iters, min_points, d_poses7_out, d_stats, d_sums29, d_residuals);
     if (st != VORS_OK) return st;
-    if (!d_workspace) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: d_workspace is NULL (the pass allocates nothing: vors_icp_workspace_bytes)");
-    if ((st = list_stride_refusals("icp_points", pose_stride_bytes, range_stride_bytes)) != VORS_OK) return st;
+    if (robust && (st = icp_robust_refusals(who, robust->frame_normals, robust->min_cos, robust->huber_m, robust->gate_counts)) != VORS_OK) return st;
+    if (!d_workspace) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_workspace is NULL (the pass allocates nothing: vors_icp_workspace_bytes)");
+    if ((st = list_stride_refusals(who, pose_stride_bytes, range_stride_bytes)) != VORS_OK) return st;
     if ((uintptr_t)d_ranges % 4 != 0 || (uintptr_t)d_list_counts % 4 != 0 || (uintptr_t)d_workspace % 4 != 0)
-        return fail(VORS_ERR_INVALID_ARGUMENT, "icp_points: d_ranges, d_list_counts and d_workspace must be 4-byte aligned");
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_ranges, d_list_counts and d_workspace must be 4-byte aligned");
     if ((st = require_device()) != VORS_OK) return st;
     IcpCall call{};
     call.n = n;
@@ -521,45 +534,77 @@ vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, c
     call.stats = d_stats;
     call.sums29 = d_sums29;
     call.residuals = d_residuals;
-    launch_icp_points(call, static_cast<hipStream_t>(hip_stream));
+    launch_icp_points(call, robust, static_cast<hipStream_t>(hip_stream));
     HIP_TRY(hipGetLastError());
     return VORS_OK;
 }
 
-vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
-                                 const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale,
-                                 float dist_m, float damping, float step_eps, int iters, int min_points, float pose7_out[7], vors_icp_stats* stats,
-                                 float sums29[29], float* residuals) {
-    vors_status st = icp_refusals("icp_points_host", xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
-                                  step_eps, iters, min_points, pose7_out, stats, sums29, residuals);
-    if (st != VORS_OK) return st;
-    const Intr k = intr_from_cam5(cam5);
+vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity, const void* d_ranges,
+                            size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth,
+                            const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters,
+                            int min_points, void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
+                            void* hip_stream) {
+    return icp_points_device("icp_points", n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in, pose_stride_bytes,
+                             d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, nullptr, d_workspace, d_poses7_out,
+                             d_stats, d_sums29, d_residuals, hip_stream);
+}
+
+vors_status vors_icp_points_robust(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
+                                   const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
+                                   const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping,
+                                   float step_eps, int iters, int min_points, const float* d_frame_normals, float min_cos, float huber_m,
+                                   void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
+                                   uint32_t* d_gate_counts, void* hip_stream) {
+    const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
+    return icp_points_device("icp_points_robust", n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in,
+                             pose_stride_bytes, d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, &robust,
+                             d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, hip_stream);
+}
+
+// The loop of the host entries, after their refusals. point(pose, landing, nw, pixel, a, products) is the per-point rule: it fills the
+// row a[7] and its 28 products, and returns the last gate passed and whether the point lies on Huber's linear branch.
+struct IcpHostPoint {
+    IcpGate gate;
+    bool linear;
+};
+extern "C++" template <class Point>
+static void icp_host_loop(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2], const float pose7_in[7],
+                          const Intr& k, int rows, int cols, float damping, float step_eps, int iters, int min_points, Point point,
+                          float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals, uint32_t* gate_counts) {
     uint32_t first, last;
     icp_range(count, capacity, range2, &first, &last);
     const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
     std::vector<float> v((size_t)VORS_ICP_CHUNK * VORS_ICP_SUMS);
     float sums[VORS_ICP_SUMS];
-    uint32_t matched = 0;
+    uint32_t matched = 0, gates[VORS_ICP_GATE_COUNTS];
     // one evaluation at `pose`: per chunk the slots, the halving tree, then the chunk sums in ascending order (the text of icp_eval_kernel
     // and icp_solve_kernel)
     auto evaluate = [&](const Iso& pose, float* res) {
         for (int q = 0; q < VORS_ICP_SUMS; ++q) sums[q] = 0.0f;
+        for (int q = 0; q < VORS_ICP_GATE_COUNTS; ++q) gates[q] = 0u;
         matched = 0;
         for (uint32_t chunk = 0; chunk < nchunks; ++chunk) {
             const uint32_t base = first + chunk * VORS_ICP_CHUNK;
             for (uint32_t s = 0; s < VORS_ICP_CHUNK; ++s) {
                 float a[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+                float* products = v.data() + (size_t)s * VORS_ICP_SUMS;
                 const uint32_t rank = base + s;
                 if (rank < last) {
                     const float* p = xyz + 3 * (size_t)rank;
                     const float* nn = normals + 3 * (size_t)rank;
                     const IcpLanding l = icp_landing(k, pose, V3{p[0], p[1], p[2]}, cols, rows);
-                    const uint16_t d = depth[l.lands ? (size_t)l.y * (size_t)cols + (size_t)l.x : 0];
-                    const bool m = icp_row(k, depth_scale, dist_m, pose, l, V3{nn[0], nn[1], nn[2]}, d, a);
+                    const size_t pixel = l.lands ? (size_t)l.y * (size_t)cols + (size_t)l.x : 0;
+                    const IcpHostPoint o = point(pose, l, V3{nn[0], nn[1], nn[2]}, pixel, a, products);
+                    const bool m = o.gate == ICP_GATE_MATCHED;
                     matched += m ? 1u : 0u;
+                    gates[0] += o.gate >= ICP_GATE_DEPTH ? 1u : 0u;
+                    gates[1] += o.gate >= ICP_GATE_DIST ? 1u : 0u;
+                    gates[2] += m ? 1u : 0u;
+                    gates[3] += o.linear ? 1u : 0u;
                     if (res) res[rank] = m ? a[0] : nanf("");
+                } else {
+                    icp_products(a, products);  // (a slot beyond the range: zeros)
                 }
-                icp_products(a, v.data() + (size_t)s * VORS_ICP_SUMS);
             }
             for (uint32_t w = VORS_ICP_CHUNK / 2; w >= 1; w /= 2)
                 for (uint32_t s = 0; s < w; ++s)
@@ -588,6 +633,51 @@ vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_
     iso_store(pose, pose7_out);
     if (stats) *stats = o;
     if (sums29) icp_sums29(sums, matched, sums29);
+    if (gate_counts)
+        for (int q = 0; q < VORS_ICP_GATE_COUNTS; ++q) gate_counts[q] = gates[q];
+}
+
+vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
+                                 const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale,
+                                 float dist_m, float damping, float step_eps, int iters, int min_points, float pose7_out[7], vors_icp_stats* stats,
+                                 float sums29[29], float* residuals) {
+    vors_status st = icp_refusals("icp_points_host", xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
+                                  step_eps, iters, min_points, pose7_out, stats, sums29, residuals);
+    if (st != VORS_OK) return st;
+    const Intr k = intr_from_cam5(cam5);
+    icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
+                  [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, float* a, float* products) {
+                      const bool m = icp_row(k, depth_scale, dist_m, pose, l, nw, depth[pixel], a);
+                      icp_products(a, products);
+                      return IcpHostPoint{m ? ICP_GATE_MATCHED : ICP_GATE_NONE, false};
+                  },
+                  pose7_out, stats, sums29, residuals, nullptr);
+    return VORS_OK;
+}
+
+vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
+                                        const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols,
+                                        float depth_scale, float dist_m, float damping, float step_eps, int iters, int min_points,
+                                        const float* frame_normals, float min_cos, float huber_m, float pose7_out[7], vors_icp_stats* stats,
+                                        float sums29[29], float* residuals, uint32_t gate_counts[VORS_ICP_GATE_COUNTS]) {
+    vors_status st = icp_refusals("icp_points_robust_host", xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
+                                  step_eps, iters, min_points, pose7_out, stats, sums29, residuals);
+    if (st != VORS_OK) return st;
+    if ((st = icp_robust_refusals("icp_points_robust_host", frame_normals, min_cos, huber_m, gate_counts)) != VORS_OK) return st;
+    const Intr k = intr_from_cam5(cam5);
+    with_bool(frame_normals != nullptr, [&](auto nrm) {
+        with_bool(huber_m > 0.0f, [&](auto hub) {
+            icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
+                          [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, float* a, float* products) {
+                              V3 nf{0.0f, 0.0f, 0.0f};
+                              if constexpr (decltype(nrm)::value) nf = V3{frame_normals[3 * pixel], frame_normals[3 * pixel + 1], frame_normals[3 * pixel + 2]};
+                              const IcpGate g =
+                                  icp_row_robust<decltype(nrm)::value>(k, depth_scale, dist_m, min_cos, pose, l, nw, depth[pixel], nf, a);
+                              return IcpHostPoint{g, icp_products_robust<decltype(hub)::value>(a, huber_m, products)};
+                          },
+                          pose7_out, stats, sums29, residuals, gate_counts);
+        });
+    });
     return VORS_OK;
 }
 

@@ -583,20 +583,26 @@ vors_status vors_trackers_render_map(vors_trackers* t, int level, const void* d_
                               d_gray, d_counts, s);
 }
 
-vors_status vors_trackers_icp_map(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters, int min_points,
-                                  const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
-                                  void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
-                                  void* hip_stream) {
+// What the two icp_map entries check of the handle before they forward (the stream is checked under the caller's DeviceGuard)
+static vors_status icp_map_refusals(const vors_trackers* t) {
     if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_map: the handle t is NULL");
     if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_map: the keyframe map is not enabled (vors_trackers_enable_map)");
     if (!t->map.normals.on)
         return fail(VORS_ERR_INVALID_ARGUMENT, "icp_map: the normals of the map are not enabled (vors_trackers_enable_map_normals)");
     if (!t->initialised) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_map: called before vors_trackers_init (there is no map and no pose yet)");
+    return VORS_OK;
+}
+
+vors_status vors_trackers_icp_map(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters, int min_points,
+                                  const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
+                                  void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
+                                  void* hip_stream) {
+    vors_status st = icp_map_refusals(t);
+    if (st != VORS_OK) return st;
     vors_batch* b = t->batch;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     DeviceGuard guard(b->device);
-    vors_status st = check_stream(b, s);
-    if (st != VORS_OK) return st;
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
     const LevelGeom& lv = b->g.lv[0];  // (map normals exist for a level-0 map only)
     const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
     // NULL poses: the current frame poses, which the track call has already moved forward in stream order; the pass only reads them
@@ -604,6 +610,26 @@ vors_status vors_trackers_icp_map(vors_trackers* t, const uint16_t* d_depth, flo
     return vors_icp_points(t->n_seq, t->map.xyz, t->map.normals.n, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes,
                            d_poses7_in ? d_poses7_in : t->cur_poses.p, pose_stride_bytes, d_depth, cam5, lv.rows, lv.cols, b->g.depth_scale, dist_m,
                            damping, step_eps, iters, min_points, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, s);
+}
+
+vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters,
+                                         int min_points, const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in,
+                                         size_t pose_stride_bytes, const float* d_frame_normals, float min_cos, float huber_m, void* d_workspace,
+                                         float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
+                                         uint32_t* d_gate_counts, void* hip_stream) {
+    vors_status st = icp_map_refusals(t);
+    if (st != VORS_OK) return st;
+    vors_batch* b = t->batch;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    const LevelGeom& lv = b->g.lv[0];
+    const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
+    if (!d_poses7_in) pose_stride_bytes = 0;  // (the current frame poses, as in vors_trackers_icp_map)
+    return vors_icp_points_robust(t->n_seq, t->map.xyz, t->map.normals.n, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes,
+                                  d_poses7_in ? d_poses7_in : t->cur_poses.p, pose_stride_bytes, d_depth, cam5, lv.rows, lv.cols,
+                                  b->g.depth_scale, dist_m, damping, step_eps, iters, min_points, d_frame_normals, min_cos, huber_m, d_workspace,
+                                  d_poses7_out, d_stats, d_sums29, d_residuals, d_gate_counts, s);
 }
 
 vors_status vors_tracker_render_map(vors_tracker* t, int level, const float pose7[7], const uint32_t range2[2], int footprint, uint64_t* zkey,

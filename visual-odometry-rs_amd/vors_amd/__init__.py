@@ -112,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "vors_render_points", "vors_render_points_host", "vors_trackers_render_map",
     "vors_depth_normals", "vors_points_normals", "vors_depth_normals_host", "vors_trackers_enable_map_normals", "vors_trackers_map_normals",
     "vors_icp_workspace_bytes", "vors_icp_points", "vors_icp_points_host", "vors_trackers_icp_map",
+    "vors_icp_points_robust", "vors_icp_points_robust_host", "vors_trackers_icp_map_robust",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
@@ -206,6 +207,10 @@ def lib():
         _lib.vors_icp_points.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, i, i, f, f, f, f, i, i, vp, vp, vp, vp, vp, vp]
         _lib.vors_icp_points_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, vp, vp, vp]
         _lib.vors_trackers_icp_map.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        _lib.vors_icp_points_robust.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, vp, vp, vp,
+                                                vp, vp, vp, vp]
+        _lib.vors_icp_points_robust_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, vp, vp, vp, vp, vp]
+        _lib.vors_trackers_icp_map_robust.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, f, f, vp, vp, vp, vp, vp, vp, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -1183,6 +1188,28 @@ class Trackers:
         self._icp_refs = (depth, poses, ranges, ws)
         return _icp_result(bufs, stats, sums29, residuals)
 
+    def icp_map_robust(self, depth, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6, frame_normals=None, min_cos=0.0, huber_m=0.0,
+                       poses=None, ranges=None, workspace=None, stats=True, sums29=False, residuals=False, gate_counts=False):
+        """icp_map() through the robust pass (vors_trackers_icp_map_robust): icp_points_robust() on the handle's own map and map normals.
+        frame_normals [n, rows, cols, 3] float32 (depth_normals() of `depth` at level 0 without poses; None = no gate), min_cos, huber_m
+        and gate_counts as in icp_points_robust(); everything else as in icp_map()."""
+        import torch
+        self._check_frames(depth, depth)
+        if depth.dtype != torch.int16:
+            raise VorsError("icp_map_robust: depth int16 [n, rows, cols], contiguous")
+        dev = _torch_device(self._device)
+        poses, pose_stride = _render_poses(poses, self.n)
+        rng, range_stride = _render_ranges(ranges, self.n)
+        cap = self._map[1] if getattr(self, "_map", None) else 1  # (no map: the entry refuses)
+        ws, bufs = _icp_buffers(self.n, cap, dev, workspace, stats, sums29, residuals)
+        gates =_icp_robust_buffers("icp_map_robust", frame_normals, depth.shape, gate_counts, dev)
+        _check(lib().vors_trackers_icp_map_robust(self._h, Batch._dp(depth), float(dist_m), float(damping), float(step_eps), int(iters),
+                                                  int(min_points), rng, range_stride, Batch._dp(poses), pose_stride, Batch._dp(frame_normals),
+                                                  float(min_cos), float(huber_m), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
+                                                  Batch._stream()))
+        self._icp_refs = (depth, poses, ranges, ws, frame_normals)
+        return dict(_icp_result(bufs, stats, sums29, residuals), **_result(("gate_counts", _asked(gate_counts), gates)))
+
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
 
@@ -1621,6 +1648,81 @@ def icp_points(xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_
                                  float(damping), float(step_eps), int(iters), int(min_points), Batch._dp(ws), *[Batch._dp(t) for t in bufs],
                                  Batch._stream()))
     return _icp_result(bufs, stats, sums29, residuals)
+
+
+ICP_GATE_COUNTS = 4  # VORS_ICP_GATE_COUNTS: with_depth, within_dist, matched, huber_linear
+
+
+def _icp_robust_buffers(who, frame_normals, shape, gate_counts, dev):
+    """The frame normals (None = no normal gate; float32 [n, rows, cols, 3], contiguous) checked, and the tensor behind gate_counts."""
+    import torch
+    if frame_normals is not None and (frame_normals.dtype != torch.float32 or not frame_normals.is_contiguous()
+                                      or tuple(frame_normals.shape) != tuple(shape) + (3,)):
+        raise VorsError(f"{who}: frame_normals float32 {tuple(shape) + (3,)}, contiguous (depth_normals() of the same depth without poses)")
+    return _out_buf(gate_counts, (shape[0], ICP_GATE_COUNTS), torch.int32, dev)
+
+
+def icp_points_robust(xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6,
+                      frame_normals=None, min_cos=0.0, huber_m=0.0, ranges=None, workspace=None, stats=True, sums29=False, residuals=False,
+                      gate_counts=False):
+    """icp_points() with a normal-compatibility gate against the frame's own normals and Huber weights (vors_icp_points_robust):
+    frame_normals [n, rows, cols, 3] float32 in the camera frame (depth_normals() of the same depth without poses; None = no gate), a
+    point is matched only if dot(model normal in the camera, frame normal) >= min_cos; huber_m > 0 = the Huber threshold on the
+    point-to-plane residual in metres ("sums29"[0] and stats rms are then the Huber loss). gate_counts: "gate_counts" [n, 4] int32 of the
+    final evaluation (with_depth, within_dist, matched, huber_linear). frame_normals None and huber_m 0: icp_points() bit for bit.
+    Everything else, and the result, as in icp_points()."""
+    import torch
+    n = xyz.shape[0]
+    cap = xyz.shape[1] if xyz.dim() == 3 else -1
+    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or normals.dtype != torch.float32
+            or not normals.is_contiguous() or tuple(normals.shape) != (n, cap, 3) or list_counts.dtype != torch.int32
+            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
+        raise VorsError("icp_points_robust: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
+    if depth.dtype != torch.int16 or depth.dim() != 3 or depth.shape[0] != n or not depth.is_contiguous():
+        raise VorsError("icp_points_robust: depth int16 [n, rows, cols], contiguous")
+    if poses is None:
+        raise VorsError("icp_points_robust: poses are required")
+    k = _normals_common(cam5, "icp_points_robust")
+    poses, pose_stride = _render_poses(poses, n)
+    rng, range_stride = _render_ranges(ranges, n)
+    ws, bufs = _icp_buffers(n, cap, xyz.device, workspace, stats, sums29, residuals)
+    gates = _icp_robust_buffers("icp_points_robust", frame_normals, depth.shape, gate_counts, xyz.device)
+    _check(lib().vors_icp_points_robust(n, Batch._dp(xyz), Batch._dp(normals), Batch._dp(list_counts), cap, rng, range_stride, Batch._dp(poses),
+                                        pose_stride, Batch._dp(depth), _ptr(k), depth.shape[1], depth.shape[2], float(depth_scale),
+                                        float(dist_m), float(damping), float(step_eps), int(iters), int(min_points), Batch._dp(frame_normals),
+                                        float(min_cos), float(huber_m), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
+                                        Batch._stream()))
+    return dict(_icp_result(bufs, stats, sums29, residuals), **_result(("gate_counts", _asked(gate_counts), gates)))
+
+
+def icp_points_robust_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6,
+                           frame_normals=None, min_cos=0.0, huber_m=0.0, count=None, range2=None, residuals=None):
+    """The loop of icp_points_robust for ONE list on the host (vors_icp_points_robust_host; needs no GPU): icp_points_host()'s arguments,
+    frame_normals [rows, cols, 3] float32 (None = no gate), min_cos, huber_m -> icp_points_host()'s dict and "gate_counts" [4] uint32."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(depth, np.uint16)
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+    fn = None if frame_normals is None else np.ascontiguousarray(frame_normals, np.float32)
+    if (len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,))
+            or (fn is not None and fn.shape != d.shape + (3,))):
+        raise VorsError("icp_points_robust_host: xyz and normals [capacity, 3], depth [rows, cols], cam5 [5], pose7 [7], range2 [2] or None, "
+                        "frame_normals [rows, cols, 3] or None")
+    if residuals is None:
+        residuals = np.full(len(p), np.nan, np.float32)
+    elif residuals.dtype != np.float32 or residuals.shape != (len(p),) or not residuals.flags.c_contiguous:
+        raise VorsError(f"icp_points_robust_host: residuals must be a contiguous float32 array ({len(p)},)")
+    stats = np.zeros(1, ICP_STATS_DTYPE)
+    out = dict(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), residuals=residuals,
+               gate_counts=np.zeros(ICP_GATE_COUNTS, np.uint32))
+    _check(lib().vors_icp_points_robust_host(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, len(p) if count is None else int(count),
+                                             len(p), _ptr(rng), _ptr(pose), _ptr(d), _ptr(k), d.shape[0], d.shape[1], float(depth_scale),
+                                             float(dist_m), float(damping), float(step_eps), int(iters), int(min_points), _ptr(fn), float(min_cos),
+                                             float(huber_m), _ptr(out["pose"]), _ptr(stats), _ptr(out["sums29"]), _ptr(residuals),
+                                             _ptr(out["gate_counts"])))
+    return out
 
 
 def icp_points_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6, count=None,
