@@ -124,7 +124,9 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    VORS_VOXEL_NONE, likewise; + vors_render_points, vors_render_points_host, vors_trackers_render_map,
                               *    vors_tracker_render_map, VORS_RENDER_COUNTS, likewise; + vors_icp_points, vors_icp_points_host,
                               *    vors_icp_workspace_bytes, vors_trackers_icp_map, vors_icp_stats, likewise; + vors_icp_points_robust,
-                              *    vors_icp_points_robust_host, vors_trackers_icp_map_robust, VORS_ICP_GATE_COUNTS, likewise) */
+                              *    vors_icp_points_robust_host, vors_trackers_icp_map_robust, VORS_ICP_GATE_COUNTS, likewise; + vors_trackers_enable_map_icp,
+                              *    vors_trackers_map_icp, vors_tracker_enable_map_icp, vors_tracker_read_map_icp, vors_map_icp_window_host,
+                              *    vors_map_icp_verdict_host, vors_map_icp_params, vors_map_icp_record, VORS_MAP_ICP_*, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -191,6 +193,29 @@ vors_status vors_tracker_enable_map_normals(vors_tracker* t, int step, float jum
 /* The map's normals so far to a HOST buffer normals [capacity][3]: the first min(total, capacity, the handle's capacity) entries, rank for
  * rank those of vors_tracker_read_map; synchronises. capacity negative, normals NULL or not enabled: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_read_map_normals(vors_tracker* t, int capacity, float* normals);
+/* Parameters of the MAP ICP CORRECTION at keyframe promotion (vors_trackers_enable_map_icp, below). */
+typedef struct vors_map_icp_params {
+    float dist_m, damping, step_eps; int32_t iters, min_points;   /* vors_icp_points' */
+    int32_t normal_gate; float min_cos, huber_m;                  /* vors_icp_points_robust'; normal_gate = 0: no frame normals are computed or kept */
+    int32_t last_keyframes;                                       /* window: 0 = the whole map */
+    float min_match_ratio, max_rms, max_trans_m, max_rot_rad;     /* the verdict */
+} vors_map_icp_params;
+#define VORS_MAP_ICP_NOT_ATTEMPTED 0   /* not promoted in the last call */
+#define VORS_MAP_ICP_ACCEPTED      1
+#define VORS_MAP_ICP_ICP_STATUS    2   /* TOO_FEW or SINGULAR (an empty window ends here) */
+#define VORS_MAP_ICP_FEW_MATCHES   3
+#define VORS_MAP_ICP_RMS           4
+#define VORS_MAP_ICP_STEP          5   /* correction larger than max_trans_m / max_rot_rad */
+#define VORS_MAP_ICP_NONFINITE     6
+struct vors_map_icp_record;  /* section 2e, behind vors_icp_stats */
+/* The correction of vors_trackers_enable_map_icp (below) for the single sequence, its N = 1 case: same parameters, same refusals. Legal
+ * after vors_tracker_enable_map_normals and until the first vors_tracker_track (refused after it and when repeated). With it,
+ * vors_tracker_track reads its results back BEHIND the promotion instead of under it, so that the pose it returns, vors_tracker_current_frame
+ * and vors_tracker_keyframe report the corrected pose; a frame then waits for its promotion. */
+vors_status vors_tracker_enable_map_icp(vors_tracker* t, const vors_map_icp_params* params);
+/* The record of the LAST vors_tracker_track and the running totals (attempted, accepted) to the host, each nullable; synchronises. Not
+ * enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map_icp(vors_tracker* t, struct vors_map_icp_record* record, uint32_t totals[2]);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -355,6 +380,41 @@ vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_dep
                                          const float* d_frame_normals /* nullable */, float min_cos, float huber_m, void* d_workspace,
                                          float* d_poses7_out, struct vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
                                          float* d_residuals /* nullable */, uint32_t* d_gate_counts /* nullable */, void* hip_stream);
+/* MAP ICP CORRECTION AT KEYFRAME PROMOTION (opt-in on top of an enabled map with normals; without this call nothing changes: no launch, no
+ * allocation, no kernel argument on any existing path). vors_trackers_track then closes the loop between the map and the trajectory: for
+ * every sequence it promotes — behind the keyframe stage and BEFORE the new keyframe's cloud is emitted — the EXISTING map (a window of it)
+ * is aligned to the new keyframe's depth by vors_icp_points_robust's pass, starting from the keyframe pose the call has just written; a
+ * result that passes the verdict replaces the sequence's keyframe pose, current frame pose and output pose, so that the emission and the
+ * normals pass behind it append the new cloud at the corrected pose, vors_trackers_current_frames / _state report it and the next
+ * frame's LM starts from it. A rejected result changes nothing. The depth plane is the one the emission's normals pass reads: the caller's
+ * frame, with the depth filter the fused plane, in dense mode the handle's copy. Not run at vors_trackers_init (the map is still empty).
+ * Window (one text, lie.h map_icp_window; host twin vors_map_icp_window_host): n_rec = min(n_segments, max_keyframes), total = min(count,
+ *   capacity); first = 0 when last_keyframes == 0 or n_rec <= last_keyframes, else the `first` of recorded segment n_rec - last_keyframes,
+ *   clipped to total; the window is (first, total - first) — always to the end of the list — of the map as it stood BEFORE this
+ *   promotion's emission: a keyframe's own cloud is never part of its model.
+ * Verdict (one text, lie.h map_icp_verdict; host twin vors_map_icp_verdict_host), the first failure names it, every comparison in float,
+ *   NaN fails: NONFINITE — a non-finite number in the ICP's pose; ICP_STATUS — status neither ITERATIONS nor CONVERGED; FEW_MATCHES —
+ *   (float)matched >= min_match_ratio * (float)considered fails; RMS — rms <= max_rms fails; STEP — with D = inverse(pose before) * pose
+ *   after, dot3(D.t, D.t) <= max_trans_m^2 or fabsf(D.q.w) >= cosf(0.5f * max_rot_rad) fails (the cosine is taken once, at this call).
+ * Launches: the host cannot know whether a sequence promotes, so EVERY track call enqueues the stage — ARM (one thread per sequence: promoted
+ *   flag, window, start pose, record reset), with normal_gate one masked launch for the frame normals of the promoted sequences (the rule
+ *   of vors_depth_normals without poses, at the map normals' step / jump_m), the ICP's memset and 2 * iters + 3 launches, APPLY (one thread
+ *   per promoted sequence): 2 * iters + 5 kernel launches and one memset, + 1 with normal_gate. A sequence that is not promoted has the
+ *   window (0, 0): its evaluation workgroups return at once and the first solve freezes it. Nothing waits on the host. Measured (64 sequences of
+ *   640x480, 6 rounds): 0.157 ms per track call when nothing promotes.
+ * Legal where vors_trackers_enable_map_normals is legal and after it: before vors_trackers_init, once. VORS_ERR_INVALID_ARGUMENT, nothing
+ * allocated: NULL handle or params, no enabled map, no enabled map normals, repeated call, call after init, everything
+ * vors_icp_points_robust refuses of the shared parameters, last_keyframes < 0, min_match_ratio outside [0, 1] or NaN, max_rms /
+ * max_trans_m / max_rot_rad negative or NaN. The call allocates, as part of vors_trackers_workspace_bytes' figure and freed with the
+ * handle: vors_icp_workspace_bytes(n, capacity), and per sequence 8 bytes of window, 4 of flag, 56 of poses, 24 + 16 of staged
+ * statistics and gate counts, a vors_map_icp_record (112 bytes) and 8 bytes of totals; with normal_gate n * rows * cols * 12 bytes of
+ * frame normals. No later call allocates. vors_trackers_init zeroes records and totals on the stream. */
+vors_status vors_trackers_enable_map_icp(vors_trackers* t, const vors_map_icp_params* params);
+/* DEVICE pointers, owned by the handle and valid for its life, contents valid in stream order after the last track, each nullable:
+ * d_records [n] — of the LAST track call, verdict NOT_ATTEMPTED for a sequence it did not promote — and d_totals [n][2] u32: promotions
+ * attempted and accepted since init. Not enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map_icp(const vors_trackers* t, const struct vors_map_icp_record** d_records,
+                                  const uint32_t** d_totals /* [n][2]: attempted, accepted */);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -888,6 +948,24 @@ vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, 
                                         const float* frame_normals /* nullable */, float min_cos, float huber_m,
                                         float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
                                         uint32_t gate_counts[VORS_ICP_GATE_COUNTS] /* nullable */);
+/* What vors_trackers_enable_map_icp (section 1b) keeps per sequence of the LAST track call: 112 bytes. A sequence the call did not
+ * promote has verdict NOT_ATTEMPTED, frame = its keyframe's index, the window (0, 0), pose_before = pose_after = its keyframe pose and
+ * zeros elsewhere. For a promoted one: frame = the new keyframe's index, the window, the pass's statistics and gate counts, pose_before =
+ * the keyframe pose the LM stage produced and pose_after = the ICP's output, ACCEPTED OR NOT. */
+typedef struct vors_map_icp_record {
+    int32_t frame; uint32_t verdict, range_first, range_count;
+    vors_icp_stats stats; uint32_t gate_counts[VORS_ICP_GATE_COUNTS];
+    float pose_before[7], pose_after[7];
+} vors_map_icp_record;
+/* The two rules of the correction on the HOST, host arithmetic, no GPU: the texts the kernels run (lie.h map_icp_window, map_icp_verdict).
+ * window: segments [min(n_segments, max_keyframes)] (nullable when that is 0 or last_keyframes is 0), count / n_segments the unclipped
+ * totals of vors_trackers_map -> range2 = (first, count). Refused: range2 NULL, capacity or max_keyframes < 1, last_keyframes < 0, segments
+ * NULL where a record is read. verdict: params' four verdict fields (the others are not read) -> *verdict, a VORS_MAP_ICP_* other than
+ * NOT_ATTEMPTED. Refused: a NULL argument, and the verdict fields vors_trackers_enable_map_icp refuses. */
+vors_status vors_map_icp_window_host(const vors_map_segment* segments, uint32_t n_segments, int max_keyframes, uint32_t count, int capacity,
+                                     int last_keyframes, uint32_t range2[2]);
+vors_status vors_map_icp_verdict_host(const vors_map_icp_params* params, const vors_icp_stats* stats, const float pose_before[7],
+                                      const float pose_after[7], uint32_t* verdict);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

@@ -566,6 +566,35 @@ struct IcpRobust {
 // robust evaluation kernels, instantiated on (frame normals given, huber_m > 0), after a memset of the gate counts when they are asked for.
 void launch_icp_points(const IcpCall& call, const IcpRobust* robust, hipStream_t s);
 
+// The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp; map_icp_kernels.hip): what surrounds
+// launch_icp_points there. Handle-free: everything the kernels read is here.
+struct MapIcpCall {
+    int n;                           // sequences
+    const int* promo_list;           // the promotion list of this track call and its length, on the device
+    const int* promo_count;
+    const int32_t* kf_frame;         // [n] frame index of every sequence's keyframe (the new one for a promoted sequence)
+    const uint32_t* counts;          // the map as it stands BEFORE this promotion's emission: running totals, segment records and counts
+    const vors_map_segment* segments;
+    const uint32_t* n_segments;
+    int capacity, max_keyframes, last_keyframes;
+    MapIcpGates gates;
+    float *kf_poses, *cur_poses, *out_poses;  // [n][7] the tracker's pose tables: read by ARM, written by APPLY for an accepted sequence
+    uint32_t* promoted;              // [n] staging: 1 = on the promotion list of this call
+    uint32_t* ranges;                // [n][2] the window, (0, 0) for a sequence that is not promoted
+    float *start_poses, *result_poses;        // [n][7] the ICP's input and output
+    vors_icp_stats* stats;           // [n] staging of the ICP's outputs
+    uint32_t* gate_counts;           // [n][VORS_ICP_GATE_COUNTS]
+    vors_map_icp_record* records;    // [n]
+    uint32_t* totals;                // [n][2] attempted, accepted
+};
+// ARM: one thread per sequence — promoted flag, window, start pose, the record reset to NOT_ATTEMPTED. Enqueued on s.
+void launch_map_icp_arm(const MapIcpCall& call, hipStream_t s);
+// APPLY: one thread per entry of the promotion list — the verdict, the write-back of an accepted pose, the record, the totals.
+void launch_map_icp_apply(const MapIcpCall& call, hipStream_t s);
+// The plane form of the normals pass for the sequences of call.sel_list only (required here), without a pose and without counts: per
+// pixel lie.h depth_normal, the text and the bits of launch_depth_normals, whose kernel knows no selection and stays as it is.
+void launch_map_icp_frame_normals(const NormalCall& call, hipStream_t s);
+
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.
 inline int eval_pairs_chunk_points(const Geom& g) { return g.mode == VORS_CANDIDATES_DENSE ? 16384 : 4096; }

@@ -183,6 +183,12 @@ inline vors_status own_alloc_failed(vors_batch* b, const char* what) {
     return fail(VORS_ERR_HIP, std::string("hipMalloc (") + what + "): " + hipGetErrorString(e));
 }
 
+// The map ICP correction's parameters (operators.cpp, beside the ICP's own refusals): every refusal of vors_map_icp_params, in the name
+// of `who`, and the verdict's thresholds as lie.h map_icp_verdict reads them (the cosine of half max_rot_rad is taken here, once).
+extern "C" {
+vors_status map_icp_params_refusals(const char* who, const vors_map_icp_params* params);
+vors::MapIcpGates map_icp_gates(const vors_map_icp_params& params);
+}
 // The stream work is enqueued on must belong to the handle's device (a stream of another device would silently run nothing useful).
 vors_status check_stream(const vors_batch* b, hipStream_t s);
 // Tracker::track up to the keyframe test for the prepared keyframes of `b`, with the keyframe poses on the device (batch.cpp;

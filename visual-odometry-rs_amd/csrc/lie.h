@@ -689,6 +689,58 @@ VORS_UNROLL
     for (int i = 1; i < VORS_ICP_SUMS; ++i) out29[i + 1] = sums[i];
 }
 
+// The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp): its two rules, each ONE text, run by the
+// host twins (vors_map_icp_window_host, vors_map_icp_verdict_host) and by map_icp_arm_kernel / map_icp_apply_kernel.
+// WINDOW: the ranks of a sequence's map the new keyframe is aligned against. DEFINITION: n_rec = min(n_segments, max_keyframes),
+// total = min(count, capacity); first = 0 when last_keyframes == 0 or n_rec <= last_keyframes, otherwise the `first` of recorded segment
+// n_rec - last_keyframes, clipped to total; the window is (first, total - first): it always runs to the end of the list, so the points of
+// keyframes beyond max_keyframes stay inside it. segment_words: the sequence's vors_map_segment records as 32-bit words, ten per record,
+// `first` at word 1 (read only in the second case).
+#define MAP_SEGMENT_WORDS 10
+VORS_HD void map_icp_window(const uint32_t* segment_words, uint32_t n_segments, int max_keyframes, uint32_t count, int capacity, int last_keyframes,
+                            uint32_t range2[2]) {
+    const uint32_t n_rec = n_segments < (uint32_t)max_keyframes ? n_segments : (uint32_t)max_keyframes;
+    const uint32_t total = count < (uint32_t)capacity ? count : (uint32_t)capacity;
+    uint32_t first = 0;
+    if (last_keyframes != 0 && n_rec > (uint32_t)last_keyframes) {
+        first = segment_words[(size_t)(n_rec - (uint32_t)last_keyframes) * MAP_SEGMENT_WORDS + 1];
+        if (first > total) first = total;
+    }
+    range2[0] = first;
+    range2[1] = total - first;
+}
+// VERDICT on one alignment. DEFINITION: the tests run in this order and the first failure names the verdict; every comparison is in
+// float and NaN fails. 1 NONFINITE: any of pose_after's seven numbers is not finite. 2 ICP_STATUS: the status is neither ITERATIONS nor
+// CONVERGED (rms is read only behind this test: it is NaN when nothing matched). 3 FEW_MATCHES: (float)matched >= min_match_ratio *
+// (float)considered does not hold. 4 RMS: rms <= max_rms does not hold. 5 STEP: with D = inverse(pose_before) * pose_after (iso_inverse,
+// iso_mul), dot3(D.t, D.t) <= max_trans_m * max_trans_m or fabsf(D.q.w) >= cos_half_rot does not hold; cos_half_rot =
+// cosf(0.5f * max_rot_rad) is evaluated once, on the host, when the stage is enabled, and handed to the kernel and the twin alike.
+enum MapIcpVerdict {
+    MAP_ICP_NOT_ATTEMPTED = 0, MAP_ICP_ACCEPTED = 1, MAP_ICP_ICP_STATUS = 2, MAP_ICP_FEW_MATCHES = 3, MAP_ICP_RMS = 4, MAP_ICP_STEP = 5,
+    MAP_ICP_NONFINITE = 6
+};
+struct MapIcpGates {
+    float min_match_ratio, max_rms, max_trans_m, cos_half_rot;
+};
+VORS_HD bool f32_finite(float v) {
+    union { float f; uint32_t u; } b;
+    b.f = v;
+    return (b.u & 0x7f800000u) != 0x7f800000u;
+}
+VORS_HD MapIcpVerdict map_icp_verdict(const MapIcpGates& g, uint32_t status, uint32_t matched, uint32_t considered, float rms,
+                                      const float pose_before[7], const float pose_after[7]) {
+VORS_UNROLL
+    for (int i = 0; i < 7; ++i)
+        if (!f32_finite(pose_after[i])) return MAP_ICP_NONFINITE;
+    if (status != (uint32_t)ICP_ITERATIONS && status != (uint32_t)ICP_CONVERGED) return MAP_ICP_ICP_STATUS;
+    if (!((float)matched >= g.min_match_ratio * (float)considered)) return MAP_ICP_FEW_MATCHES;
+    if (!(rms <= g.max_rms)) return MAP_ICP_RMS;
+    const Iso d = iso_mul(iso_inverse(iso_load(pose_before)), iso_load(pose_after));
+    if (!(dot3(d.t, d.t) <= g.max_trans_m * g.max_trans_m)) return MAP_ICP_STEP;
+    if (!(fabsf(d.q.w) >= g.cos_half_rot)) return MAP_ICP_STEP;
+    return MAP_ICP_ACCEPTED;
+}
+
 // Jacobian of the warp: src/core/track/inverse_compositional.rs:313-341.
 VORS_HD void warp_jacobian_at(float gu, float gv, float u, float v, float _z, const Intr& k, float J[6]) {
     const float a = u - k.cu;

@@ -682,6 +682,60 @@ vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp, trackers.cpp): what it refuses of its parameters — one
+// sentence each, shared by the enable entries and the host twins — the verdict's thresholds as the rule reads them, and the two host
+// twins, which run lie.h map_icp_window / map_icp_verdict, the kernels' own texts.
+// ---------------------------------------------------------------------------------------------------------------
+static vors_status map_icp_verdict_refusals(const std::string& w, const vors_map_icp_params& p) {
+    if (!(p.min_match_ratio >= 0.0f && p.min_match_ratio <= 1.0f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_match_ratio must lie in [0, 1] (and not be NaN)");
+    if (!(p.max_rms >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": max_rms must be >= 0 (and not NaN)");
+    if (!(p.max_trans_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": max_trans_m must be >= 0 (and not NaN)");
+    if (!(p.max_rot_rad >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": max_rot_rad must be >= 0 (and not NaN)");
+    return VORS_OK;
+}
+vors_status map_icp_params_refusals(const char* who, const vors_map_icp_params* p) {
+    const std::string w(who);
+    if (!p) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": params is NULL");
+    // (what vors_icp_points_robust refuses of the shared parameters, in its own sentences: the lists, planes and shapes are the handle's)
+    alignas(16) static const float some[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    vors_status st = icp_refusals(who, some, some, some, some, some, 1, 1, 1, 1.0f, p->dist_m, p->damping, p->step_eps, p->iters, p->min_points, some,
+                                  nullptr, nullptr, nullptr);
+    if (st != VORS_OK) return st;
+    if ((st = icp_robust_refusals(who, nullptr, p->min_cos, p->huber_m, nullptr)) != VORS_OK) return st;
+    if (p->last_keyframes < 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": last_keyframes must be >= 0 (0 = the whole map)");
+    return map_icp_verdict_refusals(w, *p);
+}
+MapIcpGates map_icp_gates(const vors_map_icp_params& p) {
+    return MapIcpGates{p.min_match_ratio, p.max_rms, p.max_trans_m, cosf(0.5f * p.max_rot_rad)};
+}
+
+vors_status vors_map_icp_window_host(const vors_map_segment* segments, uint32_t n_segments, int max_keyframes, uint32_t count, int capacity,
+                                     int last_keyframes, uint32_t range2[2]) {
+    if (!range2) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_window_host: range2 is NULL");
+    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_window_host: capacity must be >= 1");
+    if (max_keyframes < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_window_host: max_keyframes must be >= 1");
+    if (last_keyframes < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_window_host: last_keyframes must be >= 0 (0 = the whole map)");
+    const uint32_t n_rec = n_segments < (uint32_t)max_keyframes ? n_segments : (uint32_t)max_keyframes;
+    if (!segments && last_keyframes != 0 && n_rec > (uint32_t)last_keyframes)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_window_host: segments is NULL where a record is read");
+    if ((uintptr_t)segments % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_window_host: segments must be 4-byte aligned");
+    static_assert(sizeof(vors_map_segment) == MAP_SEGMENT_WORDS * 4 && offsetof(vors_map_segment, first) == 4, "lie.h map_icp_window's record");
+    map_icp_window(reinterpret_cast<const uint32_t*>(segments), n_segments, max_keyframes, count, capacity, last_keyframes, range2);
+    return VORS_OK;
+}
+
+vors_status vors_map_icp_verdict_host(const vors_map_icp_params* params, const vors_icp_stats* stats, const float pose_before[7],
+                                      const float pose_after[7], uint32_t* verdict) {
+    if (!params || !stats || !pose_before || !pose_after || !verdict)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_verdict_host: a NULL argument (params, stats, pose_before, pose_after, verdict)");
+    vors_status st = map_icp_verdict_refusals("map_icp_verdict_host", *params);
+    if (st != VORS_OK) return st;
+    *verdict = (uint32_t)map_icp_verdict(map_icp_gates(*params), stats->status, stats->matched, stats->considered, stats->rms, pose_before, pose_after);
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------
 void vors_se3_exp(const float xi[6], float out_iso7[7]) { iso_store(se3_exp(xi), out_iso7); }

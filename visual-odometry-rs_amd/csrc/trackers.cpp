@@ -69,6 +69,23 @@ struct vors_trackers {
             float* n = nullptr;
             uint32_t* first = nullptr;
         } normals;
+        // ICP correction at promotion (vors_trackers_enable_map_icp; off: nothing below exists and no launch changes):
+        //   workspace          the ICP pass's (engine.h icp_workspace_bytes)
+        //   promoted, ranges   [n_seq], [n_seq][2]: this call's promotion flags and windows
+        //   start, result      [n_seq][7] the ICP's input and output poses
+        //   stats, gates       [n_seq] staging of the ICP's statistics and gate counts, copied into the records by APPLY
+        //   records, totals    [n_seq], [n_seq][2]: what vors_trackers_map_icp shows
+        //   frame_normals      [n_seq][S0][3], with normal_gate only
+        struct Icp {
+            bool on = false;
+            vors_map_icp_params p{};
+            MapIcpGates gates{};
+            void* workspace = nullptr;
+            uint32_t *promoted = nullptr, *ranges = nullptr, *gate_counts = nullptr, *totals = nullptr;
+            float *start = nullptr, *result = nullptr, *frame_normals = nullptr;
+            vors_icp_stats* stats = nullptr;
+            vors_map_icp_record* records = nullptr;
+        } icp;
     } map;
     const uint16_t* keyframe_depth() const {
         return batch->g.mode == VORS_CANDIDATES_DENSE ? static_cast<const uint16_t*>(own_depth.p) : filter.fused;
@@ -151,6 +168,89 @@ static void trackers_map_emit_all(vors_trackers* t, const Geom& gm, const uint16
     if (nm.on) trackers_map_normals_pass(t, gm, depth, s);
 }
 
+// The ICP correction of the promoted sequences (vors_trackers_enable_map_icp), between the keyframe stage and the emission: ARM, the frame
+// normals of the promoted sequences (normal_gate), the robust ICP pass as vors_trackers_icp_map_robust forwards it — device ranges, the
+// handle's workspace, statistics and gate counts into staging — and APPLY. `depth`: the planes the emission's normals pass reads.
+// Hazards, all settled by the stream: ARM reads the keyframe poses and kf_frame behind launch_trackers_advance, and the map's counts and
+// segments BEFORE this promotion's emission (enqueued behind the stage) and behind the previous one; the ICP reads map.xyz / map.normals.n,
+// which only an emission and its normals pass write; APPLY writes the three pose tables behind everything of this call that reads them
+// (the LM stage, launch_trackers_advance, a single tracker's read-back when it is ordered here) and before the emission, the normals pass
+// and the next call's LM stage, which read them. Everything else is the stage's own.
+static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint16_t* depth, hipStream_t s) {
+    const Geom& g = t->batch->g;
+    const vors_trackers::Map& m = t->map;
+    const vors_trackers::Map::Icp& ic = m.icp;
+    const LevelGeom& lv = g.lv[0];  // (map normals exist for a level-0 map only)
+    MapIcpCall mc{};
+    mc.n = t->n_seq;
+    mc.promo_list = gm.sel_list;
+    mc.promo_count = gm.sel_count;
+    mc.kf_frame = t->kf_frame.as<int32_t>();
+    mc.counts = m.counts;
+    mc.segments = m.segments;
+    mc.n_segments = m.n_segments;
+    mc.capacity = m.capacity;
+    mc.max_keyframes = m.max_keyframes;
+    mc.last_keyframes = ic.p.last_keyframes;
+    mc.gates = ic.gates;
+    mc.kf_poses = t->kf_poses.as<float>();
+    mc.cur_poses = t->cur_poses.as<float>();
+    mc.out_poses = t->out_poses.as<float>();
+    mc.promoted = ic.promoted;
+    mc.ranges = ic.ranges;
+    mc.start_poses = ic.start;
+    mc.result_poses = ic.result;
+    mc.stats = ic.stats;
+    mc.gate_counts = ic.gate_counts;
+    mc.records = ic.records;
+    mc.totals = ic.totals;
+    launch_map_icp_arm(mc, s);
+    if (ic.frame_normals) {
+        NormalCall nc{};
+        nc.n = t->n_seq;
+        nc.depth = depth;
+        nc.k = lv.k;
+        nc.rows = lv.rows;
+        nc.cols = lv.cols;
+        nc.depth_scale = g.depth_scale;
+        nc.step = m.normals.step;
+        nc.jump_m = m.normals.jump_m;
+        nc.normals = ic.frame_normals;
+        nc.sel_list = gm.sel_list;
+        nc.sel_count = gm.sel_count;
+        launch_map_icp_frame_normals(nc, s);
+    }
+    IcpCall call{};
+    call.n = t->n_seq;
+    call.xyz = m.xyz;
+    call.normals = m.normals.n;
+    call.list_counts = m.counts;
+    call.capacity = m.capacity;
+    call.ranges = reinterpret_cast<const uint8_t*>(ic.ranges);
+    call.range_stride = 8;
+    call.poses_in = ic.start;
+    call.pose_stride = 7;
+    call.depth = depth;
+    call.k = lv.k;
+    call.rows = lv.rows;
+    call.cols = lv.cols;
+    call.depth_scale = g.depth_scale;
+    call.dist_m = ic.p.dist_m;
+    call.damping = ic.p.damping;
+    call.step_eps = ic.p.step_eps;
+    call.iters = ic.p.iters;
+    call.min_points = (uint32_t)ic.p.min_points;
+    const size_t slots = (size_t)t->n_seq * icp_chunks(m.capacity);  // the workspace: partials, chunk counts, state (engine.h icp_workspace_bytes)
+    call.partials = static_cast<float*>(ic.workspace);
+    call.chunk_counts = reinterpret_cast<uint32_t*>(call.partials + slots * VORS_ICP_SUMS);
+    call.state = reinterpret_cast<IcpState*>(call.chunk_counts + slots);
+    call.poses_out = ic.result;
+    call.stats = ic.stats;
+    const IcpRobust robust{ic.frame_normals, ic.p.min_cos, ic.p.huber_m, ic.gate_counts};
+    launch_icp_points(call, &robust, s);
+    launch_map_icp_apply(mc, s);
+}
+
 // The two halves of vors_trackers_track: Tracker::track up to the keyframe test, and the promotion of the sequences that switch — the
 // only reader of the depth map, which may arrive on another stream (depth_ready). vors_tracker_track runs them apart, with the depth
 // upload in between.
@@ -224,7 +324,11 @@ static vors_status trackers_promote(vors_trackers* t, const uint8_t* d_gray, con
         if (b->g.mode == VORS_CANDIDATES_DENSE)
             launch_ref_dense_planes_keyframe(gm, Pyramid{t->own_gray.as<uint8_t>(), b->kf_upper}, t->own_depth.as<uint16_t>(), b->rec, n, s);
     }
-    if (t->map.on) trackers_map_emit_all(t, gm, b->g.mode == VORS_CANDIDATES_DENSE ? t->own_depth.as<uint16_t>() : d_depth, s);
+    if (t->map.on) {
+        const uint16_t* map_depth = b->g.mode == VORS_CANDIDATES_DENSE ? t->own_depth.as<uint16_t>() : d_depth;
+        if (t->map.icp.on) trackers_map_icp_stage(t, gm, map_depth, s);
+        trackers_map_emit_all(t, gm, map_depth, s);
+    }
     STAGE_END(b, 1, s);
     HIP_TRY(hipGetLastError());
     return VORS_OK;
@@ -407,6 +511,47 @@ static vors_status trackers_map_normals_enable(vors_trackers* t, bool started, c
     nm.on = true;
     return VORS_OK;
 }
+// The ICP correction's switch: every refusal, then every buffer at once. `started` / `before`: as for the voxel filter.
+static vors_status trackers_map_icp_enable(vors_trackers* t, bool started, const char* before, const vors_map_icp_params* p) {
+    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: needs an enabled keyframe map first (vors_trackers_enable_map)");
+    if (!t->map.normals.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: needs the normals of the map first (vors_trackers_enable_map_normals)");
+    if (t->map.icp.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: the correction is already enabled");
+    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, std::string("enable_map_icp: legal only before ") + before);
+    vors_status st = map_icp_params_refusals("enable_map_icp", p);
+    if (st != VORS_OK) return st;
+    vors_batch* b = t->batch;
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)t->n_seq;
+    vors_trackers::Map::Icp& ic = t->map.icp;
+    uint8_t* ws = nullptr;
+    b->own.alloc(&ws, icp_workspace_bytes(t->n_seq, t->map.capacity));
+    b->own.alloc(&ic.promoted, n);
+    b->own.alloc(&ic.ranges, n * 2);
+    b->own.alloc(&ic.start, n * 7);
+    b->own.alloc(&ic.result, n * 7);
+    b->own.alloc(&ic.stats, n);
+    b->own.alloc(&ic.gate_counts, n * VORS_ICP_GATE_COUNTS);
+    b->own.alloc(&ic.records, n);
+    b->own.alloc(&ic.totals, n * 2);
+    if (p->normal_gate) b->own.alloc(&ic.frame_normals, n * (size_t)b->g.S0 * 3);
+    if (b->own.err != hipSuccess) {
+        ic = vors_trackers::Map::Icp{};
+        return own_alloc_failed(b, "ICP correction of the keyframe map");
+    }
+    ic.workspace = ws;
+    ic.p = *p;
+    ic.gates = map_icp_gates(*p);
+    ic.on = true;
+    return VORS_OK;
+}
+// Records and totals of the correction as a handle starts (and starts again) with: zeros, i.e. NOT_ATTEMPTED and nothing counted.
+static vors_status trackers_map_icp_init(vors_trackers* t, hipStream_t s) {
+    const size_t n = (size_t)t->n_seq;
+    HIP_TRY(hipMemsetAsync(t->map.icp.records, 0, n * sizeof(vors_map_icp_record), s));
+    HIP_TRY(hipMemsetAsync(t->map.icp.totals, 0, n * 2 * sizeof(uint32_t), s));
+    return VORS_OK;
+}
 // An empty map (and an empty voxel table), then keyframe 0 of every sequence. `depth`: the planes keyframe 0 was made from, read only
 // when the map carries normals.
 static vors_status trackers_map_init(vors_trackers* t, const uint16_t* depth, hipStream_t s) {
@@ -496,6 +641,38 @@ vors_status vors_tracker_read_map_normals(vors_tracker* t, int capacity, float* 
     HIP_TRY(hipStreamSynchronize(t->s_main));
     const size_t np = std::min<size_t>(std::min<uint32_t>(total, (uint32_t)m.capacity), (size_t)capacity);
     if (np) HIP_TRY(hipMemcpyAsync(normals, m.normals.n, np * 3 * sizeof(float), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    return VORS_OK;
+}
+
+vors_status vors_trackers_enable_map_icp(vors_trackers* t, const vors_map_icp_params* params) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: the handle t is NULL");
+    return trackers_map_icp_enable(t, t->initialised, "vors_trackers_init", params);
+}
+
+vors_status vors_trackers_map_icp(const vors_trackers* t, const vors_map_icp_record** d_records, const uint32_t** d_totals) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp: the handle t is NULL");
+    if (!t->map.icp.on) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp: the ICP correction is not enabled (vors_trackers_enable_map_icp)");
+    if (d_records) *d_records = t->map.icp.records;
+    if (d_totals) *d_totals = t->map.icp.totals;
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map_icp(vors_tracker* t, const vors_map_icp_params* params) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: the handle t is NULL");
+    vors_status st = trackers_map_icp_enable(t->seq, t->has_last, "the first vors_tracker_track", params);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    return trackers_map_icp_init(t->seq, t->s_main);
+}
+
+vors_status vors_tracker_read_map_icp(vors_tracker* t, vors_map_icp_record* record, uint32_t totals[2]) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp: the handle t is NULL");
+    const vors_trackers::Map::Icp& ic = t->seq->map.icp;
+    if (!ic.on) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp: the ICP correction is not enabled (vors_tracker_enable_map_icp)");
+    DeviceGuard guard(t->device);
+    if (record) HIP_TRY(hipMemcpyAsync(record, ic.records, sizeof(vors_map_icp_record), hipMemcpyDeviceToHost, t->s_main));
+    if (totals) HIP_TRY(hipMemcpyAsync(totals, ic.totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
     HIP_TRY(hipStreamSynchronize(t->s_main));
     return VORS_OK;
 }
@@ -784,6 +961,7 @@ vors_status vors_trackers_init(vors_trackers* t, const uint8_t* d_gray, const ui
     HIP_TRY(hipGetLastError());
     if (t->filter.on && (st = trackers_filter_init(t, d_depth, s)) != VORS_OK) return st;
     if (t->map.on && (st = trackers_map_init(t, kf_depth, s)) != VORS_OK) return st;
+    if (t->map.icp.on && (st = trackers_map_icp_init(t, s)) != VORS_OK) return st;  // (the stage itself is not run: the map was empty)
     t->frame_index = 0;
     t->initialised = true;
     return VORS_OK;
@@ -905,11 +1083,21 @@ vors_status vors_tracker_track(vors_tracker* t, double depth_time, const uint16_
     // the LM kernel's chain of ~35 dependent evaluations. Not kept.)
     if ((st = tracker_upload_gray(t, gray)) != VORS_OK) return st;
     if ((st = trackers_track_lm(t->seq, t->gray.as<uint8_t>(), t->s_main)) != VORS_OK) return st;
-    launch_tracker_pack_out(d_pose, d_status, d_kf, d_stats, o, t->s_main);
-    HIP_TRY(hipGetLastError());  // (a failed launch is reported against THIS frame, not against whatever touches the stream next)
-    HIP_TRY(hipEventRecord(t->ev_result, t->s_main));
+    // With the map ICP correction the promotion may still move the pose: the results are then packed BEHIND it, and the frame waits for
+    // its promotion. Without it nothing changes: packed here, read back under the promotion.
+    const bool corrected = t->seq->map.icp.on;
+    if (!corrected) {
+        launch_tracker_pack_out(d_pose, d_status, d_kf, d_stats, o, t->s_main);
+        HIP_TRY(hipGetLastError());  // (a failed launch is reported against THIS frame, not against whatever touches the stream next)
+        HIP_TRY(hipEventRecord(t->ev_result, t->s_main));
+    }
     if ((st = tracker_upload_depth(t, depth)) != VORS_OK) return st;
     if ((st = trackers_promote(t->seq, t->gray.as<uint8_t>(), t->depth.as<uint16_t>(), t->ev_depth, t->s_main)) != VORS_OK) return st;
+    if (corrected) {
+        launch_tracker_pack_out(d_pose, d_status, d_kf, d_stats, o, t->s_main);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(t->ev_result, t->s_main));
+    }
     HIP_TRY(hipEventRecord(t->ev_frame_done, t->s_main));
     HIP_TRY(hipEventSynchronize(t->ev_result));
     t->last = o->stats;

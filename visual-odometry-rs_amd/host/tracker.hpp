@@ -198,6 +198,15 @@ class Tracker {  // inverse_compositional.rs:31-34
         normals.resize(3 * np);
         return normals;
     }
+    // Extension: the ICP correction at keyframe promotion (vors_tracker_enable_map_icp): a promoted frame's pose is refined against the
+    // map before its cloud is emitted. After enable_map_normals, before the first track().
+    void enable_map_icp(const vors_map_icp_params& params) { check(vors_tracker_enable_map_icp(h_, &params)); }
+    // The running totals of the correction: promotions attempted and accepted (vors_tracker_read_map_icp; synchronises).
+    std::pair<std::uint32_t, std::uint32_t> read_map_icp_totals() {
+        std::uint32_t totals[2] = {0, 0};
+        check(vors_tracker_read_map_icp(h_, nullptr, totals));
+        return {totals[0], totals[1]};
+    }
     // Extension: the map seen from a pose (vors_tracker_render_map; synchronises): a z-buffered depth map and grey image in the geometry
     // of pyramid level `level`, row-major, the arguments of Config::init. pose = nullptr: the current frame's pose; range2 = nullptr: the
     // whole map, else (first, count) of the ranks to render (a vors_map_segment's `first`); footprint: 1, 2 or 3 pixels wide.

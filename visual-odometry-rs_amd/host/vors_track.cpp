@@ -16,6 +16,12 @@
 // `--map-normals STEP[,JUMP_M]` (needs --map with LEVEL 0) gives every point of that map the surface normal of its pixel in its keyframe's
 // depth map (vors_tracker_enable_map_normals; JUMP_M defaults to 0.05 m) and the PLY the properties nx ny nz. Malformed, without --map or
 // with another LEVEL: the usage and status 2, before any device is touched.
+// `--map-icp DIST_M[,ITERS[,LAST_KEYFRAMES[,MIN_COS[,HUBER_M]]]]` (needs --map and --map-normals) refines the pose of every frame that
+// becomes a keyframe against the map before its cloud is appended (vors_tracker_enable_map_icp). Defaults: ITERS 8, LAST_KEYFRAMES 0 (the
+// whole map), MIN_COS 0.9 against the frame's own normals, HUBER_M 0 (none); the verdict accepts a correction with at least 0.3 of the
+// window matched, an rms of at most 0.01 m, and a step of at most 0.05 m and 0.05 rad. Malformed, or without --map / --map-normals: the
+// usage (which repeats these defaults) and status 2, before any device is touched. After the last frame one line on stderr:
+// `map-icp: attempted A accepted B`.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -116,7 +122,45 @@ static bool parse_map_normals(const std::string& val, int& step, float& jump_m) 
     return *end == '\0';
 }
 
+// "DIST_M[,ITERS[,LAST_KEYFRAMES[,MIN_COS[,HUBER_M]]]]": a number, two whole numbers, two numbers, nothing after the last. The VALUES are
+// judged by the library.
+static const char* MAP_ICP_HELP =
+    "Malformed --map-icp: expected DIST_M[,ITERS[,LAST_KEYFRAMES[,MIN_COS[,HUBER_M]]]] (defaults: ITERS 8, LAST_KEYFRAMES 0 = the whole map, "
+    "MIN_COS 0.9, HUBER_M 0; accepted: >= 0.3 of the window matched, rms <= 0.01 m, step <= 0.05 m and <= 0.05 rad)";
+static bool parse_map_icp(const std::string& val, vors_map_icp_params& p) {
+    if (val.empty()) return false;
+    const char* s = val.c_str();
+    char* end = nullptr;
+    p.dist_m = std::strtof(s, &end);
+    if (end == s) return false;
+    int32_t* ints[2] = {&p.iters, &p.last_keyframes};
+    for (int k = 0; k < 2 && *end == ','; ++k) {
+        s = end + 1;
+        const long v = std::strtol(s, &end, 10);
+        if (end == s || v < -0x7fffffffL || v > 0x7fffffffL) return false;
+        *ints[k] = (int32_t)v;
+    }
+    float* floats[2] = {&p.min_cos, &p.huber_m};
+    for (int k = 0; k < 2 && *end == ','; ++k) {
+        s = end + 1;
+        *floats[k] = std::strtof(s, &end);
+        if (end == s) return false;
+    }
+    return *end == '\0';
+}
+
 int main(int argc, char** argv) {
+    bool map_icp = false, bad_map_icp = false;
+    vors_map_icp_params icp_params{};
+    icp_params.step_eps = 1e-5f;
+    icp_params.iters = 8;
+    icp_params.min_points = 6;
+    icp_params.normal_gate = 1;
+    icp_params.min_cos = 0.9f;
+    icp_params.min_match_ratio = 0.3f;
+    icp_params.max_rms = 0.01f;
+    icp_params.max_trans_m = 0.05f;
+    icp_params.max_rot_rad = 0.05f;
     bool quiet = false, depth_filter = false, map = false, bad_map = false, map_voxel = false, bad_map_voxel = false;
     bool map_normals = false, bad_map_normals = false;
     int normals_step = 1;
@@ -154,6 +198,10 @@ int main(int argc, char** argv) {
             map_normals = parse_map_normals(val, normals_step, normals_jump_m);
             bad_map_normals = !map_normals;
             ++a;
+        } else if (flag == "--map-icp") {
+            map_icp = parse_map_icp(val, icp_params);
+            bad_map_icp = !map_icp;
+            ++a;
         } else {
             bad_flag = true;
         }
@@ -174,6 +222,10 @@ int main(int argc, char** argv) {
                      bad_map_normals ? "Malformed --map-normals: expected STEP[,JUMP_M]"
                      : !map          ? "--map-normals needs --map"
                                      : "--map-normals needs --map with LEVEL 0");
+        return 2;
+    }
+    if (bad_map_icp || (map_icp && (!map || !map_normals))) {
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE, bad_map_icp ? MAP_ICP_HELP : !map ? "--map-icp needs --map" : "--map-icp needs --map-normals");
         return 2;
     }
     if (argc > 3) argc = bad_flag ? 0 : 3;
@@ -226,7 +278,8 @@ int main(int argc, char** argv) {
         if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
         if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
         if (map_voxel) tracker.enable_map_voxels(voxel_m, voxel_table_slots);
-        if (map_normals) tracker.enable_map_normals(normals_step, normals_jump_m);  // (last: the voxel filter emits keyframe 0 again)
+        if (map_normals) tracker.enable_map_normals(normals_step, normals_jump_m);  // (behind the voxel filter, which emits keyframe 0 again)
+        if (map_icp) tracker.enable_map_icp(icp_params);
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);
@@ -235,6 +288,10 @@ int main(int argc, char** argv) {
                           {gray.data(), (int)h, (int)w, VORS_ROW_MAJOR});
             const auto cf = tracker.current_frame();
             std::printf("%s\n", tum_rgbd::to_string(tum_rgbd::Frame{cf.first, cf.second}).c_str());
+        }
+        if (map_icp) {
+            const auto totals = tracker.read_map_icp_totals();
+            std::fprintf(stderr, "map-icp: attempted %u accepted %u\n", totals.first, totals.second);
         }
         if (map) {
             if (map_voxel && tracker.read_map_voxels().overflow != 0)

@@ -114,6 +114,8 @@ EXPORTED_SYMBOLS = [
     "vors_icp_workspace_bytes", "vors_icp_points", "vors_icp_points_host", "vors_trackers_icp_map",
     "vors_icp_points_robust", "vors_icp_points_robust_host", "vors_trackers_icp_map_robust",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
+    "vors_trackers_enable_map_icp", "vors_trackers_map_icp", "vors_tracker_enable_map_icp", "vors_tracker_read_map_icp",
+    "vors_map_icp_window_host", "vors_map_icp_verdict_host",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -211,6 +213,12 @@ def lib():
                                                 vp, vp, vp, vp]
         _lib.vors_icp_points_robust_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, vp, vp, vp, vp, vp]
         _lib.vors_trackers_icp_map_robust.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, f, f, vp, vp, vp, vp, vp, vp, vp]
+        _lib.vors_trackers_enable_map_icp.argtypes = [vp, vp]
+        _lib.vors_trackers_map_icp.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        _lib.vors_tracker_enable_map_icp.argtypes = [vp, vp]
+        _lib.vors_tracker_read_map_icp.argtypes = [vp, vp, vp]
+        _lib.vors_map_icp_window_host.argtypes = [vp, C.c_uint32, i, C.c_uint32, i, i, vp]
+        _lib.vors_map_icp_verdict_host.argtypes = [vp, vp, vp, vp, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -471,13 +479,15 @@ class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
     def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None,
-                 map_normals=None):
+                 map_normals=None, map_icp=None):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
         (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
         keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it. map_voxels: None,
         or (voxel_m, table_slots) — the map's voxel filter (vors_tracker_enable_map_voxels; Trackers.enable_map_voxels); needs map.
         map_normals: None, or (step, jump_m) — a surface normal per map entry (vors_tracker_enable_map_normals;
-        Trackers.enable_map_normals), switched on last; needs map with level 0; read_map_normals() returns them."""
+        Trackers.enable_map_normals), switched on after the voxel filter; needs map with level 0; read_map_normals() returns them.
+        map_icp: None, a number (dist_m) or a dict of map_icp_params()' keywords — the ICP correction at keyframe promotion
+        (vors_tracker_enable_map_icp; Trackers.enable_map_icp), switched on last; needs map_normals; read_map_icp() returns its record."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         self._map = map = _map_args(map)
         self._map_voxels = map_voxels = _map_voxels_args(map_voxels)
@@ -486,6 +496,9 @@ class Tracker:
         self._map_normals = map_normals = _map_normals_args(map_normals)
         if map_normals is not None and map is None:
             raise VorsError("map_normals: the normals need the keyframe map (Tracker(..., map=(0, capacity, max_keyframes)))")
+        self._map_icp = map_icp = _map_icp_arg(map_icp)
+        if map_icp is not None and map_normals is None:
+            raise VorsError("map_icp: the correction needs the map's normals (Tracker(..., map_normals=(step, jump_m)))")
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -504,6 +517,17 @@ class Tracker:
             _check(lib().vors_tracker_enable_map_voxels(self._h, *map_voxels))
         if map_normals is not None:
             _check(lib().vors_tracker_enable_map_normals(self._h, *map_normals))
+        if map_icp is not None:
+            _check(lib().vors_tracker_enable_map_icp(self._h, C.byref(map_icp)))
+
+    def read_map_icp(self):
+        """The correction's record of the last track() and its running totals on the host (vors_tracker_read_map_icp; synchronises) ->
+        dict: "record", a structured scalar of MAP_ICP_RECORD_DTYPE, and "totals" [2] uint32 (attempted, accepted)."""
+        if self._map_icp is None:
+            raise VorsError("read_map_icp: the correction is not enabled (Tracker(..., map_icp=dist_m or a dict of parameters))")
+        rec, totals = np.zeros(1, MAP_ICP_RECORD_DTYPE), np.zeros(2, np.uint32)
+        _check(lib().vors_tracker_read_map_icp(self._h, _ptr(rec), _ptr(totals)))
+        return dict(record=rec[0], totals=totals)
 
     def read_map_normals(self, capacity=None):
         """The map's normals so far on the host (vors_tracker_read_map_normals; synchronises) -> [m, 3] float32, rank for rank the entries
@@ -1141,6 +1165,25 @@ class Trackers:
         out = _device_view(p.value, (self.n, self._map[1], 3), "<f4", _torch_device(self._device))
         return out.clone() if copy else out
 
+    def enable_map_icp(self, **params):
+        """ICP correction at keyframe promotion (vors_trackers_enable_map_icp): after enable_map_normals(), before init(), once. Every
+        promoted sequence's existing map is then aligned to the new keyframe's depth (icp_points_robust's pass from the keyframe pose the
+        LM stage produced) before the keyframe's cloud is emitted; a result that passes the verdict replaces the sequence's poses.
+        params: map_icp_params()' keywords — dist_m required, the rest MAP_ICP_DEFAULTS."""
+        p = map_icp_params(**params)
+        _check(lib().vors_trackers_enable_map_icp(self._h, C.byref(p)))
+
+    def map_icp(self, copy=True):
+        """-> dict of tensors (vors_trackers_map_icp), valid in stream order after the last track(): "records" [n, 112] uint8 — the
+        vors_map_icp_record of every sequence for the LAST track call as bytes: decode_map_icp_records() — and "totals" [n, 2] int32,
+        promotions attempted and accepted since init(). copy=False: views of the handle's own buffers, which die with this object."""
+        p = [C.c_void_p() for _ in range(2)]
+        _check(lib().vors_trackers_map_icp(self._h, *[C.byref(q) for q in p]))
+        dev = _torch_device(self._device)
+        out = dict(records=_device_view(p[0].value, (self.n, MAP_ICP_RECORD_DTYPE.itemsize), "|u1", dev),
+                   totals=_device_view(p[1].value, (self.n, 2), "<i4", dev))
+        return {k: v.clone() for k, v in out.items()} if copy else out
+
     def map_voxels(self, copy=True):
         """-> dict of tensors (vors_trackers_map_voxels), valid in stream order after the last init() / track(): "occupied" [n] int32, the
         distinct voxels of a sequence so far (== map()["counts"] while it has not overflowed), "overflow" [n] int32, non-zero once a
@@ -1651,6 +1694,98 @@ def icp_points(xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_
 
 
 ICP_GATE_COUNTS = 4  # VORS_ICP_GATE_COUNTS: with_depth, within_dist, matched, huber_linear
+
+
+class vors_map_icp_params(C.Structure):
+    """Parameters of the map ICP correction at keyframe promotion (include/vors_hip.h vors_map_icp_params, 52 bytes)."""
+    _fields_ = [("dist_m", C.c_float), ("damping", C.c_float), ("step_eps", C.c_float), ("iters", C.c_int32), ("min_points", C.c_int32),
+                ("normal_gate", C.c_int32), ("min_cos", C.c_float), ("huber_m", C.c_float), ("last_keyframes", C.c_int32),
+                ("min_match_ratio", C.c_float), ("max_rms", C.c_float), ("max_trans_m", C.c_float), ("max_rot_rad", C.c_float)]
+
+
+class vors_map_icp_record(C.Structure):
+    """What the correction keeps per sequence of the last track call (include/vors_hip.h vors_map_icp_record, 112 bytes)."""
+    _fields_ = [("frame", C.c_int32), ("verdict", C.c_uint32), ("range_first", C.c_uint32), ("range_count", C.c_uint32),
+                ("stats", vors_icp_stats), ("gate_counts", C.c_uint32 * ICP_GATE_COUNTS), ("pose_before", C.c_float * 7),
+                ("pose_after", C.c_float * 7)]
+
+
+MAP_ICP_RECORD_DTYPE = np.dtype([("frame", "<i4"), ("verdict", "<u4"), ("range_first", "<u4"), ("range_count", "<u4"), ("stats", ICP_STATS_DTYPE),
+                                 ("gate_counts", "<u4", (ICP_GATE_COUNTS,)), ("pose_before", "<f4", (7,)), ("pose_after", "<f4", (7,))])
+assert MAP_ICP_RECORD_DTYPE.itemsize == C.sizeof(vors_map_icp_record) == 112 and C.sizeof(vors_map_icp_params) == 52
+MAP_ICP_NOT_ATTEMPTED, MAP_ICP_ACCEPTED, MAP_ICP_ICP_STATUS, MAP_ICP_FEW_MATCHES, MAP_ICP_RMS, MAP_ICP_STEP, MAP_ICP_NONFINITE = range(7)
+# The defaults of every parameter but dist_m (the vors_track CLI documents the same): the ICP's as in icp_points_robust(), the frame-normal
+# gate on at min_cos 0.9, the whole map as the window, and a verdict that asks for three matches in ten, 1 cm rms, and a correction of at
+# most 5 cm and 0.05 rad.
+MAP_ICP_DEFAULTS = dict(damping=0.0, step_eps=1e-5, iters=8, min_points=6, normal_gate=1, min_cos=0.9, huber_m=0.0, last_keyframes=0,
+                        min_match_ratio=0.3, max_rms=0.01, max_trans_m=0.05, max_rot_rad=0.05)
+
+
+def map_icp_params(dist_m=_REQUIRED, **params):
+    """The vors_map_icp_params record of keyword arguments: dist_m is required, the rest defaults to MAP_ICP_DEFAULTS. Only names and types
+    are judged here; the values are judged by the library, in one place for every caller."""
+    if dist_m is _REQUIRED:
+        raise VorsError("map_icp: dist_m is required")
+    unknown = sorted(set(params) - set(MAP_ICP_DEFAULTS))
+    if unknown:
+        raise VorsError(f"map_icp: unknown parameter {unknown[0]!r} (dist_m, {', '.join(MAP_ICP_DEFAULTS)})")
+    values = dict(MAP_ICP_DEFAULTS, dist_m=dist_m, **params)
+    p = vors_map_icp_params()
+    for name, kind in vors_map_icp_params._fields_:
+        v = values[name]
+        if isinstance(v, (bool, np.bool_)) and name == "normal_gate":
+            v = int(v)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise VorsError(f"map_icp: {name} must be a number, got {v!r}")
+        if kind is C.c_int32:
+            if not isinstance(v, (int, np.integer)) or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise VorsError(f"map_icp: {name} must be an integer that fits a C int, got {v!r}")
+            v = int(v)
+        setattr(p, name, v)
+    return p
+
+
+def _map_icp_arg(spec):
+    """Tracker(map_icp=...): None, a number (dist_m) or a dict of map_icp_params()' keywords -> None or the record."""
+    if spec is None:
+        return None
+    if isinstance(spec, dict):
+        return map_icp_params(**spec)
+    return map_icp_params(dist_m=spec)
+
+
+def decode_map_icp_records(records):
+    """The "records" tensor of Trackers.map_icp() ([n, 112] uint8: the vors_map_icp_record records as bytes) -> a structured numpy array
+    [n] of MAP_ICP_RECORD_DTYPE (its "stats" field is ICP_STATS_DTYPE)."""
+    a = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
+    return np.ascontiguousarray(a).view(MAP_ICP_RECORD_DTYPE).reshape(-1)
+
+
+def map_icp_window_host(segments, n_segments, max_keyframes, count, capacity, last_keyframes):
+    """The window rule of the map ICP correction on the host (vors_map_icp_window_host; needs no GPU): segments = the sequence's records
+    (MAP_SEGMENT_DTYPE, at least min(n_segments, max_keyframes) of them, or None), n_segments / count its unclipped totals ->
+    (first, count) of the ranks the new keyframe is aligned against."""
+    seg = None if segments is None else np.ascontiguousarray(segments, MAP_SEGMENT_DTYPE).reshape(-1)
+    if seg is not None and len(seg) < min(int(n_segments), int(max_keyframes)):
+        raise VorsError("map_icp_window_host: fewer segment records than min(n_segments, max_keyframes)")
+    out = np.zeros(2, np.uint32)
+    _check(lib().vors_map_icp_window_host(_ptr(seg) if seg is not None and len(seg) else None, int(n_segments), int(max_keyframes), int(count),
+                                          int(capacity), int(last_keyframes), _ptr(out)))
+    return int(out[0]), int(out[1])
+
+
+def map_icp_verdict_host(params, stats, pose_before, pose_after):
+    """The verdict rule of the map ICP correction on the host (vors_map_icp_verdict_host; needs no GPU): params = map_icp_params(...) or
+    a dict of its keywords (only the four verdict fields are read), stats = a structured scalar of ICP_STATS_DTYPE -> a MAP_ICP_* verdict."""
+    p = map_icp_params(**params) if isinstance(params, dict) else params
+    s = np.zeros(1, ICP_STATS_DTYPE)
+    s[0] = stats
+    a, b = np.ascontiguousarray(pose_before, np.float32), np.ascontiguousarray(pose_after, np.float32)
+    if a.shape != (7,) or b.shape != (7,):
+        raise VorsError("map_icp_verdict_host: pose_before and pose_after [7]")
+    v = C.c_uint32(99)
+    _check(lib().vors_map_icp_verdict_host(C.byref(p), _ptr(s), _ptr(a), _ptr(b), C.byref(v)))
+    return v.value
 
 
 def _icp_robust_buffers(who, frame_normals, shape, gate_counts, dev):
