@@ -126,7 +126,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_icp_workspace_bytes, vors_trackers_icp_map, vors_icp_stats, likewise; + vors_icp_points_robust,
                               *    vors_icp_points_robust_host, vors_trackers_icp_map_robust, VORS_ICP_GATE_COUNTS, likewise; + vors_trackers_enable_map_icp,
                               *    vors_trackers_map_icp, vors_tracker_enable_map_icp, vors_tracker_read_map_icp, vors_map_icp_window_host,
-                              *    vors_map_icp_verdict_host, vors_map_icp_params, vors_map_icp_record, VORS_MAP_ICP_*, likewise) */
+                              *    vors_map_icp_verdict_host, vors_map_icp_params, vors_map_icp_record, VORS_MAP_ICP_*, likewise; + vors_icp_points_joint,
+                              *    vors_icp_points_joint_host, vors_trackers_icp_map_joint, VORS_ICP_PHOTO_COUNTS, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -380,6 +381,18 @@ vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_dep
                                          const float* d_frame_normals /* nullable */, float min_cos, float huber_m, void* d_workspace,
                                          float* d_poses7_out, struct vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
                                          float* d_residuals /* nullable */, uint32_t* d_gate_counts /* nullable */, void* hip_stream);
+/* ... and the joint pass (vors_icp_points_joint, section 2e) on the same inputs, with the map's own grey levels (vors_trackers_map's
+ * d_gray) as the list's: d_frame_gray [n][rows * cols] u8 (DEVICE, the level-0 grey frames the depth belongs to; nullable when
+ * photo_scale_m is 0), photo_scale_m, photo_huber_grey, d_photo_residuals [n][capacity] f32 and d_photo_counts [n][2] u32 (both
+ * nullable) as there. The same checks, then every refusal of vors_icp_points_joint. Reads the handle only. */
+vors_status vors_trackers_icp_map_joint(vors_trackers* t, const uint16_t* d_depth, const uint8_t* d_frame_gray /* nullable */, float dist_m,
+                                        float damping, float step_eps, int iters, int min_points, const void* d_ranges /* nullable */,
+                                        size_t range_stride_bytes, const void* d_poses7_in /* nullable */, size_t pose_stride_bytes,
+                                        const float* d_frame_normals /* nullable */, float min_cos, float huber_m, float photo_scale_m,
+                                        float photo_huber_grey, void* d_workspace, float* d_poses7_out,
+                                        struct vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
+                                        float* d_residuals /* nullable */, uint32_t* d_gate_counts /* nullable */,
+                                        float* d_photo_residuals /* nullable */, uint32_t* d_photo_counts /* nullable */, void* hip_stream);
 /* MAP ICP CORRECTION AT KEYFRAME PROMOTION (opt-in on top of an enabled map with normals; without this call nothing changes: no launch, no
  * allocation, no kernel argument on any existing path). vors_trackers_track then closes the loop between the map and the trajectory: for
  * every sequence it promotes — behind the keyframe stage and BEFORE the new keyframe's cloud is emitted — the EXISTING map (a window of it)
@@ -948,6 +961,60 @@ vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, 
                                         const float* frame_normals /* nullable */, float min_cos, float huber_m,
                                         float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
                                         uint32_t gate_counts[VORS_ICP_GATE_COUNTS] /* nullable */);
+/* THE JOINT PASS: vors_icp_points_robust with a PHOTOMETRIC row per matched point against the frame's level-0 grey plane.
+ * Point-to-plane rows do not constrain motion inside a plane; a grey-level row holds exactly the in-plane translation and the rotation
+ * about the normal. vors_icp_points_robust's arguments, and:
+ * d_list_gray [n][capacity] u8: the grey level of every list point (vors_trackers_map's d_gray, vors_batch_point_cloud's grey);
+ *   d_frame_gray [n][rows * cols] u8: the level-0 grey frame d_depth belongs to. Both nullable when photo_scale_m is 0, else required.
+ * photo_scale_m (0 = no photometric row; > 0 = metres per grey level, which puts both residuals into one unit) and photo_huber_grey (0 =
+ *   off; > 0 = the Huber threshold in grey levels; photo_huber_m = photo_scale_m * photo_huber_grey is taken once on the host).
+ * PER POINT: everything up to and including MATCHED, the geometric row and its 28 products are vors_icp_points_robust's, word for word.
+ *   PHOTO iff photo_scale_m > 0, the point is MATCHED and, with c = extr_project(T, w), (u, v) = project_uv(K, c), x0f = floorf(u),
+ *   y0f = floorf(v): x0f >= 0 && x0f + 1 <= cols - 1 && y0f >= 0 && y0f + 1 <= rows - 1, in float before any integer conversion (NaN
+ *   fails). fx = u - x0f, fy = v - y0f; taps I00 = G[y0][x0], I10 = G[y0][x0 + 1], I01 = G[y0 + 1][x0], I11 = G[y0 + 1][x0 + 1] as
+ *   float; top = I00 + fx * (I10 - I00), bot = I01 + fx * (I11 - I01), I = top + fy * (bot - top); gx = (1 - fy) * (I10 - I00) +
+ *   fy * (I11 - I01), gy = (1 - fx) * (I01 - I00) + fx * (I11 - I10) — the derivatives of the interpolant itself, no gradient image.
+ *   Residual r_p = s * (I - (float)grey) with s = photo_scale_m. Jacobian (the camera moves to T * exp(xi), c(xi) = exp(xi)^-1 c):
+ *   iz = 1.0f / c.z, du/dc = (fu * iz, skew * iz, -(((fu * c.x + skew * c.y) * iz) * iz)), dv/dc = (0, fv * iz, -(((fv * c.y) * iz) * iz)),
+ *   a = s * (gx * du/dc + gy * dv/dc), J_p = (-a, cross(a, c)), translational three first. Its 28 products p_p are those of the Huber
+ *   rule above applied to {r_p, J_p} with the threshold photo_huber_m. A PHOTO point contributes p_g[k] + p_p[k] in f32, geometric
+ *   first; any other point p_g[k] alone, with NOTHING added — so that photo_scale_m = 0 is vors_icp_points_robust bit for bit in every
+ *   shared output (-0.0f + +0.0f would be +0.0f).
+ * Slot 0 of d_sums29 is the JOINT energy (the geometric loss plus the photometric loss, both in square metres), and stats.rms =
+ *   sqrtf(sums[0] / matched) is the joint energy's; matched, and slot 1, stay the GEOMETRIC count. d_residuals stays the raw geometric r.
+ * d_photo_residuals (nullable): [n][capacity] f32, I - grey in GREY LEVELS, unscaled and unweighted, NaN = not PHOTO; exactly the ranks
+ *   of the clipped range written. d_photo_counts (nullable): [n][VORS_ICP_PHOTO_COUNTS] u32 of the FINAL evaluation: [0] photo_used — the
+ *   PHOTO points; [1] photo_huber_linear — those with |r_p| > photo_huber_m (0 when that Huber is off). A memset when asked for and one
+ *   integer atomic per workgroup and counter, as the gate counts.
+ * The order of the sums, the loop, the freezing, the statuses and the workspace (vors_icp_workspace_bytes, unchanged) are
+ * vors_icp_points', word for word; the device equals vors_icp_points_joint_host bit for bit, every count included.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued or written: everything vors_icp_points_robust refuses; photo_scale_m or
+ * photo_huber_grey negative or NaN; photo_scale_m > 0 with d_list_gray or d_frame_gray NULL; d_photo_residuals or d_photo_counts off
+ * 4-byte alignment.
+ * Launches: vors_icp_points', with the joint evaluation kernel in the evaluation's place, after a memset per asked-for count array. */
+#define VORS_ICP_PHOTO_COUNTS 2
+vors_status vors_icp_points_joint(int n, const float* d_xyz, const float* d_normals, const uint8_t* d_list_gray /* nullable */,
+                                  const uint32_t* d_list_counts, int capacity,
+                                  const void* d_ranges /* nullable */, size_t range_stride_bytes,
+                                  const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth,
+                                  const uint8_t* d_frame_gray /* nullable */, const float cam5[5], int rows, int cols, float depth_scale,
+                                  float dist_m, float damping, float step_eps, int iters, int min_points,
+                                  const float* d_frame_normals /* nullable */, float min_cos, float huber_m,
+                                  float photo_scale_m, float photo_huber_grey, void* d_workspace,
+                                  float* d_poses7_out, vors_icp_stats* d_stats /* nullable */, float* d_sums29 /* nullable */,
+                                  float* d_residuals /* nullable */, uint32_t* d_gate_counts /* nullable */,
+                                  float* d_photo_residuals /* nullable */, uint32_t* d_photo_counts /* nullable */, void* hip_stream);
+/* ... and its host twin for ONE list: vors_icp_points_robust_host's arguments, list_gray [capacity], frame_gray [rows * cols],
+ * photo_residuals [capacity] (nullable), photo_counts[2] (nullable). The same lie.h texts and the same tree as the kernels. */
+vors_status vors_icp_points_joint_host(const float* xyz, const float* normals, const uint8_t* list_gray /* nullable */, uint32_t count,
+                                       int capacity, const uint32_t range2[2], const float pose7_in[7], const uint16_t* depth,
+                                       const uint8_t* frame_gray /* nullable */, const float cam5[5], int rows, int cols, float depth_scale,
+                                       float dist_m, float damping, float step_eps, int iters, int min_points,
+                                       const float* frame_normals /* nullable */, float min_cos, float huber_m,
+                                       float photo_scale_m, float photo_huber_grey,
+                                       float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
+                                       uint32_t gate_counts[VORS_ICP_GATE_COUNTS] /* nullable */, float* photo_residuals /* nullable */,
+                                       uint32_t photo_counts[VORS_ICP_PHOTO_COUNTS] /* nullable */);
 /* What vors_trackers_enable_map_icp (section 1b) keeps per sequence of the LAST track call: 112 bytes. A sequence the call did not
  * promote has verdict NOT_ATTEMPTED, frame = its keyframe's index, the window (0, 0), pose_before = pose_after = its keyframe pose and
  * zeros elsewhere. For a promoted one: frame = the new keyframe's index, the window, the pass's statistics and gate counts, pose_before =

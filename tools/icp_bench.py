@@ -17,7 +17,12 @@ the pass at iters 0 and at iters 8 in four forms — the plain pass, robust neut
 gate, robust with the gate and Huber — all in the same run, their blocks alternating. The frame normals are vors_depth_normals' of the
 frames. Byte model of an evaluation: 26 B per point, 38 B with the 12 B gather of the frame normal.
 
-  python tools/icp_bench.py [--robust] [--lists N] [--blocks K] [--out FILE]
+--joint times the joint pass (vors_icp_points_joint) beside the robust one and writes profiles/icp_joint_summary.md: per list
+length the pass at iters 0 and at iters 8 as robust with the gate and Huber, as joint with the same and the photometric rows, and as joint
+with the photo Huber weight too. The list's grey is the frame's at the point's pixel. Byte model of an evaluation: the robust pass's 38 B
+per point, and 1 B of list grey and 4 gathered tap bytes: 43 B.
+
+  python tools/icp_bench.py [--robust | --joint] [--lists N] [--blocks K] [--out FILE]
 """
 import argparse
 import os
@@ -37,7 +42,7 @@ def measure(a):
     intr = np.asarray(V.scaled_intrinsics(ROWS, COLS), np.float32)
     cu, cv, fu, fv, _ = [float(v) for v in intr]
     n = a.lists
-    _, depth = V.synth_render_frames([2000 + s for s in range(n)], [0] * n, [np.zeros(6)] * n, ROWS, COLS, intr, invalid_percent=2)
+    frame_gray, depth = V.synth_render_frames([2000 + s for s in range(n)], [0] * n, [np.zeros(6)] * n, ROWS, COLS, intr, invalid_percent=2)
     start = np.zeros(7, np.float32)
     V.lib().vors_se3_exp(V._ptr(np.array([0.003, -0.003, 0.003, 0.002, -0.002, 0.002], np.float32)), V._ptr(start))
     poses = torch.from_numpy(np.tile(start, (n, 1))).cuda()
@@ -58,14 +63,22 @@ def measure(a):
         def icp(iters, xyz=xyz, nrm=nrm, counts=counts, ws=ws, stats=stats):
             return V.icp_points(xyz, nrm, counts, depth, intr, V.DEPTH_SCALE, poses, 0.05, step_eps=0.0, iters=iters, workspace=ws, stats=stats)
 
-        if a.robust:
+        if a.robust or a.joint:
             frame_normals = V.depth_normals(depth, intr, V.DEPTH_SCALE, 1, 0.05)["normals"]
             forms = {"plain": None, "robust neutral": dict(), "robust, normal gate": dict(frame_normals=frame_normals, min_cos=0.8),
                      "robust, normal gate + Huber": dict(frame_normals=frame_normals, min_cos=0.8, huber_m=0.005)}
+            if a.joint:
+                list_gray = torch.gather(frame_gray.view(n, -1), 1, torch.from_numpy(py * COLS + px).cuda()).contiguous()
+                both = forms["robust, normal gate + Huber"]
+                forms = {"robust, normal gate + Huber": both, "joint, normal gate + Huber + photometric rows": dict(both, photo_scale_m=0.0005),
+                         "joint, the same + photo Huber": dict(both, photo_scale_m=0.0005, photo_huber_grey=10.0)}
             for form, kw in forms.items():
-                def run(iters, kw=kw, xyz=xyz, nrm=nrm, counts=counts, ws=ws, stats=stats):
+                def run(iters, kw=kw, xyz=xyz, nrm=nrm, counts=counts, ws=ws, stats=stats, list_gray=list_gray if a.joint else None):
                     if kw is None:
                         return icp(iters, xyz, nrm, counts, ws, stats)
+                    if "photo_scale_m" in kw:
+                        return V.icp_points_joint(xyz, nrm, list_gray, counts, depth, frame_gray, intr, V.DEPTH_SCALE, poses, 0.05, step_eps=0.0,
+                                                  iters=iters, workspace=ws, stats=stats, **kw)
                     return V.icp_points_robust(xyz, nrm, counts, depth, intr, V.DEPTH_SCALE, poses, 0.05, step_eps=0.0, iters=iters, workspace=ws,
                                                stats=stats, **kw)
                 run(8)
@@ -73,7 +86,8 @@ def measure(a):
                 st = V.decode_icp_stats(stats)
                 matched[size, form] = (int(st["matched"].min()), int(st["matched"].max()), sorted(set(st["iterations"].tolist())),
                                        sorted(set(st["status"].tolist())))
-                model = n * size * (38 if kw and "frame_normals" in kw else 26) + n * ((size + 1023) // 1024) * 116
+                model = n * size * ((38 if kw and "frame_normals" in kw else 26) + (5 if kw and "photo_scale_m" in kw else 0)) \
+                    + n * ((size + 1023) // 1024) * 116
                 legs[f"{size} points, {form}: pass at iters 0"] = (lambda run=run: run(0), model)
                 legs[f"{size} points, {form}: pass at iters 8"] = (lambda run=run: run(8), 9 * model)
             continue
@@ -95,10 +109,12 @@ def measure(a):
 
 
 def report_robust(a, rows, matched):
-    lines = ["# Robust point-to-plane ICP: vors_icp_points_robust beside vors_icp_points", "",
-             f"`python tools/icp_bench.py --robust --lists {a.lists} --blocks {a.blocks}` on one MI355X: {a.lists} lists against {a.lists} planes "
+    title = ("# Joint point-to-plane and photometric ICP: vors_icp_points_joint beside vors_icp_points_robust" if a.joint else
+             "# Robust point-to-plane ICP: vors_icp_points_robust beside vors_icp_points")
+    lines = [title, "",
+             f"`python tools/icp_bench.py {'--joint' if a.joint else '--robust'} --lists {a.lists} --blocks {a.blocks}` on one MI355X: {a.lists} lists against {a.lists} planes "
              f"of {COLS}x{ROWS}; medians of {a.blocks} alternating blocks of 20 calls (range of the block medians in brackets). Byte model of "
-             "an evaluation: 26 B per point, 38 B with the gather of the frame normal.", "",
+             "an evaluation: 26 B per point, 38 B with the gather of the frame normal" + (", 43 B with the list's grey byte and the four taps." if a.joint else "."), "",
              "| leg | ms | range, ms | bytes of the model | GB/s of the model |", "|---|---|---|---|---|"]
     by = {}
     for name, med, lo, hi, nbytes in rows:
@@ -123,11 +139,12 @@ def main():
     ap.add_argument("--blocks", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "icp_summary.md"))
     ap.add_argument("--robust", action="store_true")
+    ap.add_argument("--joint", action="store_true")
     a = ap.parse_args()
-    if a.robust and a.out == ap.get_default("out"):
-        a.out = os.path.join(ROOT, "profiles", "icp_robust_summary.md")
+    if (a.robust or a.joint) and a.out == ap.get_default("out"):
+        a.out = os.path.join(ROOT, "profiles", "icp_joint_summary.md" if a.joint else "icp_robust_summary.md")
     rows, matched = measure(a)
-    if a.robust:
+    if a.robust or a.joint:
         return report_robust(a, rows, matched)
     lines = ["# Point-to-plane ICP: vors_icp_points", "",
              f"`python tools/icp_bench.py --lists {a.lists} --blocks {a.blocks}` on one MI355X: {a.lists} lists against {a.lists} planes of "

@@ -561,10 +561,22 @@ struct IcpRobust {
     float huber_m;               // 0 = no Huber weight
     uint32_t* gate_counts;       // [n][VORS_ICP_GATE_COUNTS] of the final evaluation, nullable
 };
+// What the joint pass (vors_icp_points_joint; lie.h icp_photo_footprint / icp_row_photo) reads and writes beyond IcpCall and IcpRobust.
+#define ICP_PHOTO_COUNTS VORS_ICP_PHOTO_COUNTS
+struct IcpJoint {
+    const uint8_t* list_gray;    // [n][capacity]; not read when photo_scale_m == 0
+    const uint8_t* frame_gray;   // [n][rows * cols] level 0; not read when photo_scale_m == 0
+    float photo_scale_m;         // metres per grey level; 0 = no photometric row: the robust pass
+    float photo_huber_m;         // photo_scale_m * photo_huber_grey, taken ONCE on the host; 0 = no Huber weight
+    float* photo_residuals;      // [n][capacity] I - grey in grey levels, NaN = not PHOTO, nullable
+    uint32_t* photo_counts;      // [n][ICP_PHOTO_COUNTS] of the final evaluation, nullable
+};
 // The state's start, then per round one evaluation and one solve launch, then the final evaluation and the launch that writes the
 // outputs: enqueued on s in this order, not synchronised, no allocation. robust: NULL = the plain pass (vors_icp_points); otherwise the
 // robust evaluation kernels, instantiated on (frame normals given, huber_m > 0), after a memset of the gate counts when they are asked for.
-void launch_icp_points(const IcpCall& call, const IcpRobust* robust, hipStream_t s);
+// joint (needs robust): the joint evaluation kernels in their place, instantiated on photo_huber_m > 0 as well, after a memset of the
+// photo counts when they are asked for.
+void launch_icp_points(const IcpCall& call, const IcpRobust* robust, hipStream_t s, const IcpJoint* joint = nullptr);
 
 // The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp; map_icp_kernels.hip): what surrounds
 // launch_icp_points there. Handle-free: everything the kernels read is here.

@@ -17,6 +17,9 @@
 //        28 sums (__shfl) and runs the verdict; lane 0 stores. The final launch writes the outputs instead.
 // vors_icp_points_robust / vors_trackers_icp_map_robust run the same launches with icp_eval_robust_kernel in EVAL's place:
 // lie.h icp_row_robust / icp_products_robust, a gather of the frame normal beside the depth's, and the gate counts of the final evaluation.
+// vors_icp_points_joint / vors_trackers_icp_map_joint run them with icp_eval_joint_kernel there: a photometric row per
+// matched point beside the geometric one (lie.h icp_photo_footprint / icp_row_photo), the list's grey byte and four gathered taps of the
+// frame's grey plane, and the photo counts of the final evaluation.
 #include "device_common.h"
 
 namespace vors {
@@ -289,6 +292,192 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_eval_robust_kernel(IcpRobustEva
     }
 }
 
+struct IcpJointEvalArgs {
+    int seq0;
+    IcpCall c;
+    IcpRobust r;
+    IcpJoint j;
+};
+
+// The evaluation of the joint pass (vors_icp_points_joint): icp_eval_robust_kernel's trip, grid, tree and stores, and for
+// every matched point whose bilinear footprint lies inside the frame's grey plane a photometric row beside the geometric one (lie.h
+// icp_photo_footprint / icp_row_photo), its products under icp_products_robust<PHUBER> added to the point's own before the tree. A text
+// of its own for the reason given above the robust kernel. The grey byte of a point is loaded with its row of the list; the four taps —
+// two 2-byte loads, rows y0 and y0 + 1, offset 0 without a footprint inside — are gathered with the depth and the frame normal, ahead
+// of the rows. photo_scale_m == 0 (or a plane of fewer than two rows or columns, where no footprint fits): workgroup-uniform, no grey
+// pointer is read and no point is PHOTO — the robust pass. Photo counts (FINAL, when asked for): as the gate counts.
+template <bool FINAL, bool RESID, bool NORMALS, bool HUBER, bool PHUBER>
+__global__ __launch_bounds__(ICP_BLOCK) void icp_eval_joint_kernel(IcpJointEvalArgs a) {
+    constexpr int COUNTERS = VORS_ICP_GATE_COUNTS + ICP_PHOTO_COUNTS;
+    __shared__ float lds[VORS_ICP_SUMS * 128];
+    __shared__ uint32_t lds_counts[ICP_BLOCK / 64];
+    __shared__ uint32_t lds_gates[COUNTERS * (ICP_BLOCK / 64)];
+    const IcpCall& c = a.c;
+    const IcpRobust& rb = a.r;
+    const IcpJoint& jt = a.j;
+    const int seq = a.seq0 + blockIdx.y;
+    const IcpState& st = c.state[seq];
+    if (!FINAL && st.frozen) return;  // the whole workgroup
+    uint32_t first, last;
+    icp_list_range(c, seq, &first, &last);
+    // (last - first <= capacity < 2^31: nothing below wraps)
+    const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
+    if (blockIdx.x >= nchunks) return;  // the whole workgroup
+    const size_t cap_chunks = icp_chunks(c.capacity);
+    const float* xyz = c.xyz + (size_t)seq * (size_t)c.capacity * 3;
+    const float* normals = c.normals + (size_t)seq * (size_t)c.capacity * 3;
+    const uint16_t* depth = c.depth + (size_t)seq * (size_t)c.rows * (size_t)c.cols;
+    const Iso pose = iso_load(st.pose);
+    const unsigned t = threadIdx.x, wave = t >> 6;
+    const float* frame_normals = nullptr;
+    if constexpr (NORMALS) frame_normals = rb.frame_normals + (size_t)seq * (size_t)c.rows * (size_t)c.cols * 3;
+    const bool photo_on = jt.photo_scale_m > 0.0f && c.rows >= 2 && c.cols >= 2;  // (uniform)
+    const uint8_t* list_gray = photo_on ? jt.list_gray + (size_t)seq * (size_t)c.capacity : nullptr;
+    const uint8_t* frame_gray = photo_on ? jt.frame_gray + (size_t)seq * (size_t)c.rows * (size_t)c.cols : nullptr;
+    uint32_t gates[COUNTERS] = {0u, 0u, 0u, 0u, 0u, 0u};  // the four gate counts, then photo_used, photo_huber_linear
+    for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const uint32_t base = first + chunk * VORS_ICP_CHUNK;
+        V3 w[4], nw[4];
+        uint8_t gw[4] = {0, 0, 0, 0};
+        bool valid[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t rank = base + j * ICP_BLOCK + t;
+            valid[j] = rank < last;
+            const size_t r = (size_t)(valid[j] ? rank : base);  // (a slot beyond the range reads the chunk's first row: a safe address)
+            const size_t o = 3 * r;
+            w[j] = V3{xyz[o], xyz[o + 1], xyz[o + 2]};
+            nw[j] = V3{normals[o], normals[o + 1], normals[o + 2]};
+            if (photo_on) gw[j] = list_gray[r];
+        }
+        IcpLanding l[4];
+        IcpFootprint fp[4];
+        uint16_t d[4], top[4] = {0, 0, 0, 0}, bot[4] = {0, 0, 0, 0};
+        V3 nf[4] = {};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            l[j] = icp_landing(c.k, pose, w[j], c.cols, c.rows);
+            l[j].lands = l[j].lands && valid[j];
+            const int pixel = l[j].lands ? l[j].y * c.cols + l[j].x : 0;  // (no landing: pixel 0, a safe address; the row ignores it)
+            d[j] = depth[pixel];
+            if constexpr (NORMALS) {
+                const float* f = frame_normals + 3 * (size_t)pixel;
+                nf[j] = V3{f[0], f[1], f[2]};
+            }
+            fp[j] = icp_photo_footprint(c.k, l[j].c, c.cols, c.rows);
+            if (photo_on) {
+                // (no footprint inside: offset 0 — bytes 0, 1, cols, cols + 1 exist in a plane of two rows and two columns)
+                const uint8_t* g = frame_gray + (unsigned)fp[j].off;
+                __builtin_memcpy(&top[j], g, 2);  // two adjacent bytes per row: one (possibly unaligned) 16-bit load each
+                __builtin_memcpy(&bot[j], g + (unsigned)c.cols, 2);
+            }
+        }
+        float row[4][7], prow[4][7];
+        bool photo[4];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const IcpGate g = icp_row_robust<NORMALS>(c.k, c.depth_scale, c.dist_m, rb.min_cos, pose, l[j], nw[j], d[j], nf[j], row[j]);
+            const bool m = g == ICP_GATE_MATCHED;
+            photo[j] = m && photo_on && fp[j].inside;
+            const float dg = icp_row_photo(c.k, jt.photo_scale_m, l[j].c, fp[j], photo[j], (uint8_t)(top[j] & 0xff), (uint8_t)(top[j] >> 8),
+                                           (uint8_t)(bot[j] & 0xff), (uint8_t)(bot[j] >> 8), gw[j], prow[j]);
+            if constexpr (FINAL) {
+                gates[0] += g >= ICP_GATE_DEPTH ? 1u : 0u;
+                gates[1] += g >= ICP_GATE_DIST ? 1u : 0u;
+                gates[2] += m ? 1u : 0u;
+                gates[4] += photo[j] ? 1u : 0u;
+            }
+            cnt += m ? 1u : 0u;
+            if constexpr (RESID)
+                if (valid[j]) {
+                    const size_t o = (size_t)seq * (size_t)c.capacity + (base + j * ICP_BLOCK + t);
+                    if (c.residuals) c.residuals[o] = m ? row[j][0] : __builtin_nanf("");
+                    if (jt.photo_residuals) jt.photo_residuals[o] = photo[j] ? dg : __builtin_nanf("");
+                }
+        }
+        // w = 512, 256: (slot t + slot t + 512) + (slot t + 256 + slot t + 768)
+        float acc[VORS_ICP_SUMS], p[VORS_ICP_SUMS], q[VORS_ICP_SUMS];
+        // (a point's products: the geometric row's, and for a PHOTO point the photometric row's added to them; the final evaluation
+        // counts the points that lie on either Huber's linear branch)
+        auto products = [&](int j, float* o) {
+            const bool linear = icp_products_robust<HUBER>(row[j], rb.huber_m, o);
+            if constexpr (FINAL && HUBER) gates[3] += linear ? 1u : 0u;
+            if (photo[j]) {
+                float pp[VORS_ICP_SUMS];
+                const bool plinear = icp_products_robust<PHUBER>(prow[j], jt.photo_huber_m, pp);
+                if constexpr (FINAL && PHUBER) gates[5] += plinear ? 1u : 0u;
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) o[k] = o[k] + pp[k];
+            }
+        };
+        products(0, p);
+        products(2, q);
+#pragma unroll
+        for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = p[k] + q[k];
+        products(1, p);
+        products(3, q);
+#pragma unroll
+        for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + (p[k] + q[k]);
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, sh);
+        if ((t & 63) == 0) lds_counts[wave] = cnt;
+        // w = 128: threads 128..255 hand over
+        if (wave >= 2) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) lds[k * 128 + (t - 128)] = acc[k];
+        }
+        __syncthreads();
+        if (wave < 2) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + lds[k * 128 + t];
+        }
+        __syncthreads();
+        // w = 64: threads 64..127 hand over
+        if (wave == 1) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) lds[k * 128 + (t - 64)] = acc[k];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + lds[k * 128 + t];
+            // w = 32..1: lane s takes lane s + w's (lanes >= w compute values nobody reads)
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) {
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) acc[k] = acc[k] + __shfl_down(acc[k], sh);
+            }
+            if (t == 0) {
+                float* out = c.partials + ((size_t)seq * cap_chunks + chunk) * VORS_ICP_SUMS;
+#pragma unroll
+                for (int k = 0; k < VORS_ICP_SUMS; ++k) out[k] = acc[k];
+                c.chunk_counts[(size_t)seq * cap_chunks + chunk] = (lds_counts[0] + lds_counts[1]) + (lds_counts[2] + lds_counts[3]);
+            }
+        }
+        __syncthreads();  // (the next trip writes the LDS again)
+    }
+    if constexpr (FINAL) {
+        if (!rb.gate_counts && !jt.photo_counts) return;  // the whole workgroup
+#pragma unroll
+        for (int g = 0; g < COUNTERS; ++g) {
+#pragma unroll
+            for (int sh = 32; sh > 0; sh >>= 1) gates[g] += (uint32_t)__shfl_xor((int)gates[g], sh);
+            if ((t & 63) == 0) lds_gates[g * (ICP_BLOCK / 64) + wave] = gates[g];
+        }
+        __syncthreads();
+        if (t < COUNTERS) {
+            const uint32_t* v = lds_gates + t * (ICP_BLOCK / 64);
+            const uint32_t sum = (v[0] + v[1]) + (v[2] + v[3]);
+            if (t < VORS_ICP_GATE_COUNTS) {
+                if (rb.gate_counts) atomicAdd(rb.gate_counts + (size_t)seq * VORS_ICP_GATE_COUNTS + t, sum);
+            } else if (jt.photo_counts) {
+                atomicAdd(jt.photo_counts + (size_t)seq * ICP_PHOTO_COUNTS + (t - VORS_ICP_GATE_COUNTS), sum);
+            }
+        }
+    }
+}
+
 template <bool FINAL>
 __global__ __launch_bounds__(64) void icp_solve_kernel(IcpCall c) {
     const int seq = blockIdx.x;
@@ -353,22 +542,32 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(IcpCall c) {
     }
 }
 
-void launch_icp_points(const IcpCall& c, const IcpRobust* robust, hipStream_t s) {
+void launch_icp_points(const IcpCall& c, const IcpRobust* robust, hipStream_t s, const IcpJoint* joint) {
     if (robust && robust->gate_counts) (void)hipMemsetAsync(robust->gate_counts, 0, (size_t)c.n * VORS_ICP_GATE_COUNTS * sizeof(uint32_t), s);
+    if (joint && joint->photo_counts) (void)hipMemsetAsync(joint->photo_counts, 0, (size_t)c.n * ICP_PHOTO_COUNTS * sizeof(uint32_t), s);
     hipLaunchKernelGGL(icp_begin_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, s, c);
     const size_t want = icp_chunks(c.capacity);
     const unsigned chunks = (unsigned)(want > ICP_MAX_CHUNKS ? ICP_MAX_CHUNKS : want);
     IcpEvalArgs a{0, c};
     IcpRobustEvalArgs ra{0, c, robust ? *robust : IcpRobust{}};
+    IcpJointEvalArgs ja{0, c, ra.r, joint ? *joint : IcpJoint{}};
     auto eval = [&](auto final_, auto resid_) {
         for_pair_slices(c.n, [&](int seq0, int ns) {
-            a.seq0 = ra.seq0 = seq0;
+            a.seq0 = ra.seq0 = ja.seq0 = seq0;
             if (!robust) {
                 hipLaunchKernelGGL((icp_eval_kernel<decltype(final_)::value, decltype(resid_)::value>), dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, a);
                 return;
             }
             with_bool(ra.r.frame_normals != nullptr, [&](auto nrm) {
                 with_bool(ra.r.huber_m > 0.0f, [&](auto hub) {
+                    if (joint) {
+                        with_bool(ja.j.photo_huber_m > 0.0f, [&](auto phub) {
+                            hipLaunchKernelGGL((icp_eval_joint_kernel<decltype(final_)::value, decltype(resid_)::value, decltype(nrm)::value,
+                                                                      decltype(hub)::value, decltype(phub)::value>),
+                                               dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, ja);
+                        });
+                        return;
+                    }
                     hipLaunchKernelGGL((icp_eval_robust_kernel<decltype(final_)::value, decltype(resid_)::value, decltype(nrm)::value, decltype(hub)::value>),
                                        dim3(chunks, ns), dim3(ICP_BLOCK), 0, s, ra);
                 });
@@ -379,7 +578,7 @@ void launch_icp_points(const IcpCall& c, const IcpRobust* robust, hipStream_t s)
         eval(std::false_type{}, std::false_type{});
         hipLaunchKernelGGL(icp_solve_kernel<false>, dim3((unsigned)c.n), dim3(64), 0, s, c);
     }
-    with_bool(c.residuals != nullptr, [&](auto r) { eval(std::true_type{}, r); });
+    with_bool(c.residuals != nullptr || (joint && joint->photo_residuals), [&](auto r) { eval(std::true_type{}, r); });
     hipLaunchKernelGGL(icp_solve_kernel<true>, dim3((unsigned)c.n), dim3(64), 0, s, c);
 }
 

@@ -643,6 +643,64 @@ VORS_UNROLL
         for (int j = i; j < 7; ++j) p[k++] = w * (a[i] * a[j]);
     return !lin;
 }
+// The joint rule (vors_icp_points_joint): icp_row_robust's row, and for a MATCHED point a PHOTOMETRIC row against the
+// frame's level-0 grey plane G, which holds what point-to-plane leaves free — the translation inside the plane, the rotation about its
+// normal. With c = l.c and (u, v) = project_uv(K, c): x0f = floorf(u), y0f = floorf(v); the bilinear footprint lies inside G iff
+// x0f >= 0 && x0f + 1 <= cols - 1 && y0f >= 0 && y0f + 1 <= rows - 1, compared in float BEFORE any integer conversion (render_point's
+// convention: NaN fails, no out-of-range float is converted). PHOTO iff photo_scale_m > 0, the point is MATCHED and its footprint is
+// inside. fx = u - x0f, fy = v - y0f; the taps I00 = G[y0][x0], I10 = G[y0][x0 + 1], I01 = G[y0 + 1][x0], I11 = G[y0 + 1][x0 + 1] as
+// float; top = I00 + fx (I10 - I00), bot = I01 + fx (I11 - I01), I = top + fy (bot - top); gx = (1 - fy)(I10 - I00) + fy (I11 - I01),
+// gy = (1 - fx)(I01 - I00) + fx (I11 - I10): the exact derivatives of the interpolant, no gradient image. (The LM kernels' bilinear text,
+// lm_sources.h bilinear_residual, is a device function over their own records and gives no derivative: this is a text of its own.)
+// d = I - (float)grey_w in grey levels, r_p = s d with s = photo_scale_m (metres per grey level: both residuals in one unit).
+// Jacobian, icp_row's convention — the camera moves to T exp(xi), so c(xi) = exp(xi)^-1 c = c - v - w x c + ...: iz = 1 / z,
+// du/dc = (fu iz, skew iz, -((fu x + skew y) iz) iz), dv/dc = (0, fv iz, -((fv y) iz) iz), a = s (gx du/dc + gy dv/dc),
+// J_p = (-a, cross(a, c)) (checked against central differences of se3_exp in f64: tests/test_icp_joint_host.py test_jacobian_rule).
+// The row is a[7] = {r_p, J_p}; a point that is not PHOTO has seven +0.0f and contributes its geometric products ALONE (nothing is
+// added to them, so that photo_scale_m = 0 is vors_icp_points_robust bit for bit; -0.0f + +0.0f would be +0.0f). A PHOTO point's 28
+// products are p_g[k] + p_p[k] in f32, geometric first, p_p = icp_products_robust<PHUBER>(a_p, photo_huber_m).
+// The two halves are separate so that a kernel issues the four gathers between them; a footprint that is not inside has offset 0.
+struct IcpFootprint {
+    float fx, fy;
+    int off;      // y0 * cols + x0; 0 unless inside (a safe address when the plane has two rows and two columns)
+    bool inside;
+};
+VORS_HD IcpFootprint icp_photo_footprint(const Intr& k, const V3& c, int cols, int rows) {
+    float u, v;
+    project_uv(k, c, &u, &v);
+    const float x0f = floorf(u), y0f = floorf(v);
+    IcpFootprint f{0.0f, 0.0f, 0, false};
+    f.inside = (x0f >= 0.0f) && (x0f + 1.0f <= (float)(cols - 1)) && (y0f >= 0.0f) && (y0f + 1.0f <= (float)(rows - 1));
+    if (f.inside) {
+        f.fx = u - x0f;
+        f.fy = v - y0f;
+        f.off = (int)y0f * cols + (int)x0f;
+    }
+    return f;
+}
+// -> d = I - grey in grey levels (meaningful only when `photo`, which the caller decides: MATCHED && f.inside && photo_scale_m > 0).
+VORS_HD float icp_row_photo(const Intr& k, float photo_scale_m, const V3& c, const IcpFootprint& f, bool photo, uint8_t t00, uint8_t t10,
+                            uint8_t t01, uint8_t t11, uint8_t grey_w, float a[7]) {
+VORS_UNROLL
+    for (int i = 0; i < 7; ++i) a[i] = 0.0f;
+    if (!photo) return 0.0f;
+    const float i00 = (float)t00, i10 = (float)t10, i01 = (float)t01, i11 = (float)t11;
+    const float dx0 = i10 - i00, dx1 = i11 - i01;
+    const float top = i00 + f.fx * dx0, bot = i01 + f.fx * dx1;
+    const float im = top + f.fy * (bot - top);
+    const float gx = (1.0f - f.fy) * dx0 + f.fy * dx1;
+    const float gy = (1.0f - f.fx) * (i01 - i00) + f.fx * (i11 - i10);
+    const float d = im - (float)grey_w;
+    const float iz = 1.0f / c.z;
+    const float dux = k.fu * iz, duy = k.skew * iz, duz = -(((k.fu * c.x + k.skew * c.y) * iz) * iz);
+    const float dvy = k.fv * iz, dvz = -(((k.fv * c.y) * iz) * iz);
+    const V3 g{photo_scale_m * (gx * dux), photo_scale_m * (gx * duy + gy * dvy), photo_scale_m * (gx * duz + gy * dvz)};
+    const V3 m = cross(g, c);
+    a[0] = photo_scale_m * d;
+    a[1] = -g.x; a[2] = -g.y; a[3] = -g.z;
+    a[4] = m.x; a[5] = m.y; a[6] = m.z;
+    return d;
+}
 // The clipped range of ranks of a list (render_splat_kernel's text): count clipped to capacity, range2 (nullable) = (first, count).
 VORS_HD void icp_range(uint32_t count, int capacity, const uint32_t* range2, uint32_t* first, uint32_t* last) {
     const uint32_t n = count < (uint32_t)capacity ? count : (uint32_t)capacity;

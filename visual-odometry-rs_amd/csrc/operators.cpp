@@ -485,14 +485,33 @@ static vors_status icp_robust_refusals(const char* who, const void* frame_normal
     return VORS_OK;
 }
 
+// photo_huber_m = photo_scale_m * photo_huber_grey, the ONE product that kernel and host twin both read
+static float icp_photo_huber_m(float photo_scale_m, float photo_huber_grey) { return photo_scale_m * photo_huber_grey; }
+
+// ... and what the joint entries refuse beyond those
+static vors_status icp_joint_refusals(const char* who, const void* list_gray, const void* frame_gray, float photo_scale_m, float photo_huber_grey,
+                                      const void* photo_residuals, const void* photo_counts) {
+    const std::string w(who);
+    if (!(photo_scale_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_scale_m must be >= 0 (and not NaN; 0 = no photometric term)");
+    if (!(photo_huber_grey >= 0.0f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_huber_grey must be >= 0 (and not NaN; 0 = no Huber weight)");
+    if (photo_scale_m > 0.0f && (!list_gray || !frame_gray))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_scale_m > 0 needs the grey levels of the list and of the frame");
+    if ((uintptr_t)photo_residuals % 4 != 0 || (uintptr_t)photo_counts % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the photo residuals and the photo counts must be 4-byte aligned");
+    return VORS_OK;
+}
+
 uint64_t vors_icp_workspace_bytes(int n, int capacity) { return n < 1 || capacity < 1 ? 0 : (uint64_t)icp_workspace_bytes(n, capacity); }
 
-// The device pass: robust = NULL is vors_icp_points (who = its name in a refusal)
+// The device pass: robust = NULL is vors_icp_points (who = its name in a refusal); joint (with robust) is vors_icp_points_joint, its
+// photo_huber_m still holding photo_huber_grey, which is scaled here, once, after the refusals
 static vors_status icp_points_device(const char* who, int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
                                      const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
                                      const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping,
                                      float step_eps, int iters, int min_points, const IcpRobust* robust, void* d_workspace, float* d_poses7_out,
-                                     vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, void* hip_stream) {
+                                     vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, void* hip_stream,
+                                     const IcpJoint* joint = nullptr) {
     const std::string w(who);
     if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be >= 1");
     if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (d_list_counts) is NULL");
@@ -500,6 +519,9 @@ static vors_status icp_points_device(const char* who, int n, const float* d_xyz,
                                   iters, min_points, d_poses7_out, d_stats, d_sums29, d_residuals);
     if (st != VORS_OK) return st;
     if (robust && (st = icp_robust_refusals(who, robust->frame_normals, robust->min_cos, robust->huber_m, robust->gate_counts)) != VORS_OK) return st;
+    if (joint && (st = icp_joint_refusals(who, joint->list_gray, joint->frame_gray, joint->photo_scale_m, joint->photo_huber_m,
+                                          joint->photo_residuals, joint->photo_counts)) != VORS_OK)
+        return st;
     if (!d_workspace) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_workspace is NULL (the pass allocates nothing: vors_icp_workspace_bytes)");
     if ((st = list_stride_refusals(who, pose_stride_bytes, range_stride_bytes)) != VORS_OK) return st;
     if ((uintptr_t)d_ranges % 4 != 0 || (uintptr_t)d_list_counts % 4 != 0 || (uintptr_t)d_workspace % 4 != 0)
@@ -534,7 +556,12 @@ static vors_status icp_points_device(const char* who, int n, const float* d_xyz,
     call.stats = d_stats;
     call.sums29 = d_sums29;
     call.residuals = d_residuals;
-    launch_icp_points(call, robust, static_cast<hipStream_t>(hip_stream));
+    IcpJoint jt{};
+    if (joint) {
+        jt = *joint;
+        jt.photo_huber_m = icp_photo_huber_m(joint->photo_scale_m, joint->photo_huber_m);
+    }
+    launch_icp_points(call, robust, static_cast<hipStream_t>(hip_stream), joint ? &jt : nullptr);
     HIP_TRY(hipGetLastError());
     return VORS_OK;
 }
@@ -561,27 +588,32 @@ vors_status vors_icp_points_robust(int n, const float* d_xyz, const float* d_nor
                              d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, hip_stream);
 }
 
-// The loop of the host entries, after their refusals. point(pose, landing, nw, pixel, a, products) is the per-point rule: it fills the
-// row a[7] and its 28 products, and returns the last gate passed and whether the point lies on Huber's linear branch.
+// The loop of the host entries, after their refusals. point(pose, landing, nw, pixel, rank, a, products) is the per-point rule: it fills
+// the row a[7] and the point's 28 products, and returns the last gate passed and whether the point lies on Huber's linear branch (the
+// joint pass: and what its photometric row gave).
 struct IcpHostPoint {
     IcpGate gate;
     bool linear;
+    bool photo = false, photo_linear = false;  // the joint pass: a photometric row exists; it lies on its Huber's linear branch
+    float photo_d = 0.0f;                      // I - grey in grey levels
 };
 extern "C++" template <class Point>
 static void icp_host_loop(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2], const float pose7_in[7],
                           const Intr& k, int rows, int cols, float damping, float step_eps, int iters, int min_points, Point point,
-                          float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals, uint32_t* gate_counts) {
+                          float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals, uint32_t* gate_counts,
+                          float* photo_residuals = nullptr, uint32_t* photo_counts = nullptr) {
     uint32_t first, last;
     icp_range(count, capacity, range2, &first, &last);
     const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
     std::vector<float> v((size_t)VORS_ICP_CHUNK * VORS_ICP_SUMS);
     float sums[VORS_ICP_SUMS];
-    uint32_t matched = 0, gates[VORS_ICP_GATE_COUNTS];
+    uint32_t matched = 0, gates[VORS_ICP_GATE_COUNTS], photos[ICP_PHOTO_COUNTS];
     // one evaluation at `pose`: per chunk the slots, the halving tree, then the chunk sums in ascending order (the text of icp_eval_kernel
     // and icp_solve_kernel)
-    auto evaluate = [&](const Iso& pose, float* res) {
+    auto evaluate = [&](const Iso& pose, float* res, float* photo_res) {
         for (int q = 0; q < VORS_ICP_SUMS; ++q) sums[q] = 0.0f;
         for (int q = 0; q < VORS_ICP_GATE_COUNTS; ++q) gates[q] = 0u;
+        for (int q = 0; q < ICP_PHOTO_COUNTS; ++q) photos[q] = 0u;
         matched = 0;
         for (uint32_t chunk = 0; chunk < nchunks; ++chunk) {
             const uint32_t base = first + chunk * VORS_ICP_CHUNK;
@@ -594,14 +626,17 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
                     const float* nn = normals + 3 * (size_t)rank;
                     const IcpLanding l = icp_landing(k, pose, V3{p[0], p[1], p[2]}, cols, rows);
                     const size_t pixel = l.lands ? (size_t)l.y * (size_t)cols + (size_t)l.x : 0;
-                    const IcpHostPoint o = point(pose, l, V3{nn[0], nn[1], nn[2]}, pixel, a, products);
+                    const IcpHostPoint o = point(pose, l, V3{nn[0], nn[1], nn[2]}, pixel, rank, a, products);
                     const bool m = o.gate == ICP_GATE_MATCHED;
                     matched += m ? 1u : 0u;
                     gates[0] += o.gate >= ICP_GATE_DEPTH ? 1u : 0u;
                     gates[1] += o.gate >= ICP_GATE_DIST ? 1u : 0u;
                     gates[2] += m ? 1u : 0u;
                     gates[3] += o.linear ? 1u : 0u;
+                    photos[0] += o.photo ? 1u : 0u;
+                    photos[1] += o.photo_linear ? 1u : 0u;
                     if (res) res[rank] = m ? a[0] : nanf("");
+                    if (photo_res) photo_res[rank] = o.photo ? o.photo_d : nanf("");
                 } else {
                     icp_products(a, products);  // (a slot beyond the range: zeros)
                 }
@@ -615,7 +650,7 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
     Iso pose = iso_load(pose7_in);
     vors_icp_stats o{VORS_ICP_ITERATIONS, 0u, last - first, 0u, 0.0f, 0.0f};
     for (int it = 0; it < iters; ++it) {
-        evaluate(pose, nullptr);
+        evaluate(pose, nullptr, nullptr);
         float step_norm = 0.0f;
         const IcpStatus verdict = icp_round(sums, matched, (uint32_t)min_points, damping, step_eps, &pose, &step_norm);
         if (verdict == ICP_ITERATIONS || verdict == ICP_CONVERGED) {
@@ -627,7 +662,7 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
             break;
         }
     }
-    evaluate(pose, residuals);
+    evaluate(pose, residuals, photo_residuals);
     o.matched = matched;
     o.rms = sqrtf(sums[0] / (float)matched);
     iso_store(pose, pose7_out);
@@ -635,6 +670,8 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
     if (sums29) icp_sums29(sums, matched, sums29);
     if (gate_counts)
         for (int q = 0; q < VORS_ICP_GATE_COUNTS; ++q) gate_counts[q] = gates[q];
+    if (photo_counts)
+        for (int q = 0; q < ICP_PHOTO_COUNTS; ++q) photo_counts[q] = photos[q];
 }
 
 vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
@@ -646,7 +683,7 @@ vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_
     if (st != VORS_OK) return st;
     const Intr k = intr_from_cam5(cam5);
     icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
-                  [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, float* a, float* products) {
+                  [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t, float* a, float* products) {
                       const bool m = icp_row(k, depth_scale, dist_m, pose, l, nw, depth[pixel], a);
                       icp_products(a, products);
                       return IcpHostPoint{m ? ICP_GATE_MATCHED : ICP_GATE_NONE, false};
@@ -668,7 +705,7 @@ vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, 
     with_bool(frame_normals != nullptr, [&](auto nrm) {
         with_bool(huber_m > 0.0f, [&](auto hub) {
             icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
-                          [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, float* a, float* products) {
+                          [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t, float* a, float* products) {
                               V3 nf{0.0f, 0.0f, 0.0f};
                               if constexpr (decltype(nrm)::value) nf = V3{frame_normals[3 * pixel], frame_normals[3 * pixel + 1], frame_normals[3 * pixel + 2]};
                               const IcpGate g =
@@ -676,6 +713,65 @@ vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, 
                               return IcpHostPoint{g, icp_products_robust<decltype(hub)::value>(a, huber_m, products)};
                           },
                           pose7_out, stats, sums29, residuals, gate_counts);
+        });
+    });
+    return VORS_OK;
+}
+
+vors_status vors_icp_points_joint(int n, const float* d_xyz, const float* d_normals, const uint8_t* d_list_gray, const uint32_t* d_list_counts,
+                                  int capacity, const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
+                                  const uint16_t* d_depth, const uint8_t* d_frame_gray, const float cam5[5], int rows, int cols, float depth_scale,
+                                  float dist_m, float damping, float step_eps, int iters, int min_points, const float* d_frame_normals,
+                                  float min_cos, float huber_m, float photo_scale_m, float photo_huber_grey, void* d_workspace,
+                                  float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, uint32_t* d_gate_counts,
+                                  float* d_photo_residuals, uint32_t* d_photo_counts, void* hip_stream) {
+    const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
+    const IcpJoint joint{d_list_gray, d_frame_gray, photo_scale_m, photo_huber_grey, d_photo_residuals, d_photo_counts};
+    return icp_points_device("icp_points_joint", n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in,
+                             pose_stride_bytes, d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, &robust,
+                             d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, hip_stream, &joint);
+}
+
+vors_status vors_icp_points_joint_host(const float* xyz, const float* normals, const uint8_t* list_gray, uint32_t count, int capacity,
+                                       const uint32_t range2[2], const float pose7_in[7], const uint16_t* depth, const uint8_t* frame_gray,
+                                       const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps,
+                                       int iters, int min_points, const float* frame_normals, float min_cos, float huber_m, float photo_scale_m,
+                                       float photo_huber_grey, float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
+                                       uint32_t gate_counts[VORS_ICP_GATE_COUNTS], float* photo_residuals,
+                                       uint32_t photo_counts[VORS_ICP_PHOTO_COUNTS]) {
+    const char* who = "icp_points_joint_host";
+    vors_status st = icp_refusals(who, xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping, step_eps, iters,
+                                  min_points, pose7_out, stats, sums29, residuals);
+    if (st != VORS_OK) return st;
+    if ((st = icp_robust_refusals(who, frame_normals, min_cos, huber_m, gate_counts)) != VORS_OK) return st;
+    if ((st = icp_joint_refusals(who, list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals, photo_counts)) != VORS_OK) return st;
+    const Intr k = intr_from_cam5(cam5);
+    const float photo_huber_m = icp_photo_huber_m(photo_scale_m, photo_huber_grey);
+    const bool photo_on = photo_scale_m > 0.0f && rows >= 2 && cols >= 2;  // (no footprint fits a plane of one row or column)
+    with_bool(frame_normals != nullptr, [&](auto nrm) {
+        with_bool(huber_m > 0.0f, [&](auto hub) {
+            with_bool(photo_huber_m > 0.0f, [&](auto phub) {
+                icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
+                              [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t rank, float* a, float* products) {
+                                  V3 nf{0.0f, 0.0f, 0.0f};
+                                  if constexpr (decltype(nrm)::value)
+                                      nf = V3{frame_normals[3 * pixel], frame_normals[3 * pixel + 1], frame_normals[3 * pixel + 2]};
+                                  const IcpGate g =
+                                      icp_row_robust<decltype(nrm)::value>(k, depth_scale, dist_m, min_cos, pose, l, nw, depth[pixel], nf, a);
+                                  IcpHostPoint o{g, icp_products_robust<decltype(hub)::value>(a, huber_m, products)};
+                                  const IcpFootprint f = icp_photo_footprint(k, l.c, cols, rows);
+                                  o.photo = g == ICP_GATE_MATCHED && photo_on && f.inside;
+                                  if (o.photo) {
+                                      const uint8_t* t = frame_gray + f.off;
+                                      float ap[7], pp[VORS_ICP_SUMS];
+                                      o.photo_d = icp_row_photo(k, photo_scale_m, l.c, f, true, t[0], t[1], t[cols], t[cols + 1], list_gray[rank], ap);
+                                      o.photo_linear = icp_products_robust<decltype(phub)::value>(ap, photo_huber_m, pp);
+                                      for (int q = 0; q < VORS_ICP_SUMS; ++q) products[q] = products[q] + pp[q];
+                                  }
+                                  return o;
+                              },
+                              pose7_out, stats, sums29, residuals, gate_counts, photo_residuals, photo_counts);
+            });
         });
     });
     return VORS_OK;

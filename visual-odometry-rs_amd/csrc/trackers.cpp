@@ -809,6 +809,28 @@ vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_dep
                                   d_poses7_out, d_stats, d_sums29, d_residuals, d_gate_counts, s);
 }
 
+vors_status vors_trackers_icp_map_joint(vors_trackers* t, const uint16_t* d_depth, const uint8_t* d_frame_gray, float dist_m, float damping,
+                                        float step_eps, int iters, int min_points, const void* d_ranges, size_t range_stride_bytes,
+                                        const void* d_poses7_in, size_t pose_stride_bytes, const float* d_frame_normals, float min_cos,
+                                        float huber_m, float photo_scale_m, float photo_huber_grey, void* d_workspace, float* d_poses7_out,
+                                        vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, uint32_t* d_gate_counts,
+                                        float* d_photo_residuals, uint32_t* d_photo_counts, void* hip_stream) {
+    vors_status st = icp_map_refusals(t);
+    if (st != VORS_OK) return st;
+    vors_batch* b = t->batch;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    if ((st = check_stream(b, s)) != VORS_OK) return st;
+    const LevelGeom& lv = b->g.lv[0];
+    const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
+    if (!d_poses7_in) pose_stride_bytes = 0;  // (the current frame poses, as in vors_trackers_icp_map)
+    return vors_icp_points_joint(t->n_seq, t->map.xyz, t->map.normals.n, t->map.gray, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes,
+                                 d_poses7_in ? d_poses7_in : t->cur_poses.p, pose_stride_bytes, d_depth, d_frame_gray, cam5, lv.rows, lv.cols,
+                                 b->g.depth_scale, dist_m, damping, step_eps, iters, min_points, d_frame_normals, min_cos, huber_m, photo_scale_m,
+                                 photo_huber_grey, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, d_gate_counts, d_photo_residuals,
+                                 d_photo_counts, s);
+}
+
 vors_status vors_tracker_render_map(vors_tracker* t, int level, const float pose7[7], const uint32_t range2[2], int footprint, uint64_t* zkey,
                                     uint16_t* depth, uint8_t* gray, uint32_t* counts) {
     if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "render_map: the handle t is NULL");

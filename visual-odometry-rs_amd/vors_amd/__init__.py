@@ -113,6 +113,7 @@ EXPORTED_SYMBOLS = [
     "vors_depth_normals", "vors_points_normals", "vors_depth_normals_host", "vors_trackers_enable_map_normals", "vors_trackers_map_normals",
     "vors_icp_workspace_bytes", "vors_icp_points", "vors_icp_points_host", "vors_trackers_icp_map",
     "vors_icp_points_robust", "vors_icp_points_robust_host", "vors_trackers_icp_map_robust",
+    "vors_icp_points_joint", "vors_icp_points_joint_host", "vors_trackers_icp_map_joint",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_trackers_enable_map_icp", "vors_trackers_map_icp", "vors_tracker_enable_map_icp", "vors_tracker_read_map_icp",
     "vors_map_icp_window_host", "vors_map_icp_verdict_host",
@@ -213,6 +214,12 @@ def lib():
                                                 vp, vp, vp, vp]
         _lib.vors_icp_points_robust_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, vp, vp, vp, vp, vp]
         _lib.vors_trackers_icp_map_robust.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, f, f, vp, vp, vp, vp, vp, vp, vp]
+        _lib.vors_icp_points_joint.argtypes = [i, vp, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, f, f,
+                                               vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.vors_icp_points_joint_host.argtypes = [vp, vp, vp, C.c_uint32, i, vp, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, f, f, vp, vp, vp,
+                                                    vp, vp, vp, vp]
+        _lib.vors_trackers_icp_map_joint.argtypes = [vp, vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, f, f, f, f, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp, vp]
         _lib.vors_trackers_enable_map_icp.argtypes = [vp, vp]
         _lib.vors_trackers_map_icp.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_icp.argtypes = [vp, vp]
@@ -1253,6 +1260,33 @@ class Trackers:
         self._icp_refs = (depth, poses, ranges, ws, frame_normals)
         return dict(_icp_result(bufs, stats, sums29, residuals), **_result(("gate_counts", _asked(gate_counts), gates)))
 
+    def icp_map_joint(self, depth, dist_m, frame_gray=None, damping=0.0, step_eps=1e-5, iters=8, min_points=6, frame_normals=None, min_cos=0.0,
+                      huber_m=0.0, photo_scale_m=0.0, photo_huber_grey=0.0, poses=None, ranges=None, workspace=None, stats=True, sums29=False,
+                      residuals=False, gate_counts=False, photo_residuals=False, photo_counts=False):
+        """icp_map_robust() through the joint pass (vors_trackers_icp_map_joint): icp_points_joint() on the handle's own map, map normals
+        and map grey levels. frame_gray [n, rows, cols] uint8 (the level-0 grey frames `depth` belongs to; None only with photo_scale_m 0),
+        photo_scale_m, photo_huber_grey, photo_residuals and photo_counts as in icp_points_joint(); everything else as in icp_map_robust()."""
+        import torch
+        self._check_frames(depth, depth)
+        if depth.dtype != torch.int16:
+            raise VorsError("icp_map_joint: depth int16 [n, rows, cols], contiguous")
+        dev = _torch_device(self._device)
+        poses, pose_stride = _render_poses(poses, self.n)
+        rng, range_stride = _render_ranges(ranges, self.n)
+        cap = self._map[1] if getattr(self, "_map", None) else 1  # (no map: the entry refuses)
+        ws, bufs = _icp_buffers(self.n, cap, dev, workspace, stats, sums29, residuals)
+        gates = _icp_robust_buffers("icp_map_joint", frame_normals, depth.shape, gate_counts, dev)
+        photo = _icp_joint_buffers("icp_map_joint", None, frame_gray, depth.shape, cap, photo_residuals, photo_counts, dev)
+        _check(lib().vors_trackers_icp_map_joint(self._h, Batch._dp(depth), Batch._dp(frame_gray), float(dist_m), float(damping), float(step_eps),
+                                                 int(iters), int(min_points), rng, range_stride, Batch._dp(poses), pose_stride,
+                                                 Batch._dp(frame_normals), float(min_cos), float(huber_m), float(photo_scale_m),
+                                                 float(photo_huber_grey), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
+                                                 *[Batch._dp(t) for t in photo], Batch._stream()))
+        self._icp_refs = (depth, poses, ranges, ws, frame_normals, frame_gray)
+        return dict(_icp_result(bufs, stats, sums29, residuals),
+                    **_result(("gate_counts", _asked(gate_counts), gates), ("photo_residuals", _asked(photo_residuals), photo[0]),
+                              ("photo_counts", _asked(photo_counts), photo[1])))
+
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
 
@@ -1857,6 +1891,102 @@ def icp_points_robust_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m
                                              float(dist_m), float(damping), float(step_eps), int(iters), int(min_points), _ptr(fn), float(min_cos),
                                              float(huber_m), _ptr(out["pose"]), _ptr(stats), _ptr(out["sums29"]), _ptr(residuals),
                                              _ptr(out["gate_counts"])))
+    return out
+
+
+ICP_PHOTO_COUNTS = 2  # VORS_ICP_PHOTO_COUNTS: photo_used, photo_huber_linear
+
+
+def _icp_joint_buffers(who, list_gray, frame_gray, shape, cap, photo_residuals, photo_counts, dev):
+    """The grey levels of the lists (None = not given or the handle's own; uint8 [n, capacity]) and of the frames (None or uint8
+    [n, rows, cols]) checked, and the tensors behind photo_residuals and photo_counts -> (photo_residuals, photo_counts)."""
+    import torch
+    n = shape[0]
+    if list_gray is not None and (list_gray.dtype != torch.uint8 or not list_gray.is_contiguous() or tuple(list_gray.shape) != (n, cap)):
+        raise VorsError(f"{who}: list_gray uint8 {(n, cap)}, contiguous")
+    if frame_gray is not None and (frame_gray.dtype != torch.uint8 or not frame_gray.is_contiguous() or tuple(frame_gray.shape) != tuple(shape)):
+        raise VorsError(f"{who}: frame_gray uint8 {tuple(shape)}, contiguous")
+    res = _out_buf(photo_residuals, (n, cap), torch.float32, dev)
+    if photo_residuals is True:
+        res.fill_(float("nan"))
+    return res, _out_buf(photo_counts, (n, ICP_PHOTO_COUNTS), torch.int32, dev)
+
+
+def icp_points_joint(xyz, normals, list_gray, list_counts, depth, frame_gray, cam5, depth_scale, poses, dist_m, damping=0.0, step_eps=1e-5,
+                     iters=8, min_points=6, frame_normals=None, min_cos=0.0, huber_m=0.0, photo_scale_m=0.0, photo_huber_grey=0.0, ranges=None,
+                     workspace=None, stats=True, sums29=False, residuals=False, gate_counts=False, photo_residuals=False, photo_counts=False):
+    """icp_points_robust() with a photometric row per matched point against the frames' level-0 grey (vors_icp_points_joint), which holds
+    what point-to-plane leaves free: the motion inside a plane. list_gray [n, capacity] uint8 (the "gray" of Trackers.map() /
+    Batch.point_cloud()) and frame_gray [n, rows, cols] uint8; both may be None only with photo_scale_m 0. photo_scale_m: metres per grey
+    level (0 = no photometric row: icp_points_robust() bit for bit); photo_huber_grey: its Huber threshold in grey levels (0 = off).
+    "sums29"[0] and stats rms are then the joint energy's; matched stays the geometric count. photo_residuals: "photo_residuals"
+    [n, capacity] float32, I - grey in grey levels, NaN = no photometric row (a new tensor is filled with NaN first); photo_counts:
+    "photo_counts" [n, 2] int32 of the final evaluation (photo_used, photo_huber_linear). Everything else, and the rest of the result,
+    as in icp_points_robust()."""
+    import torch
+    n = xyz.shape[0]
+    cap = xyz.shape[1] if xyz.dim() == 3 else -1
+    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or normals.dtype != torch.float32
+            or not normals.is_contiguous() or tuple(normals.shape) != (n, cap, 3) or list_counts.dtype != torch.int32
+            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
+        raise VorsError("icp_points_joint: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
+    if depth.dtype != torch.int16 or depth.dim() != 3 or depth.shape[0] != n or not depth.is_contiguous():
+        raise VorsError("icp_points_joint: depth int16 [n, rows, cols], contiguous")
+    if poses is None:
+        raise VorsError("icp_points_joint: poses are required")
+    k = _normals_common(cam5, "icp_points_joint")
+    poses, pose_stride = _render_poses(poses, n)
+    rng, range_stride = _render_ranges(ranges, n)
+    ws, bufs = _icp_buffers(n, cap, xyz.device, workspace, stats, sums29, residuals)
+    gates = _icp_robust_buffers("icp_points_joint", frame_normals, depth.shape, gate_counts, xyz.device)
+    photo = _icp_joint_buffers("icp_points_joint", list_gray, frame_gray, depth.shape, cap, photo_residuals, photo_counts, xyz.device)
+    _check(lib().vors_icp_points_joint(n, Batch._dp(xyz), Batch._dp(normals), Batch._dp(list_gray), Batch._dp(list_counts), cap, rng, range_stride,
+                                       Batch._dp(poses), pose_stride, Batch._dp(depth), Batch._dp(frame_gray), _ptr(k), depth.shape[1],
+                                       depth.shape[2], float(depth_scale), float(dist_m), float(damping), float(step_eps), int(iters),
+                                       int(min_points), Batch._dp(frame_normals), float(min_cos), float(huber_m), float(photo_scale_m),
+                                       float(photo_huber_grey), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
+                                       *[Batch._dp(t) for t in photo], Batch._stream()))
+    return dict(_icp_result(bufs, stats, sums29, residuals),
+                **_result(("gate_counts", _asked(gate_counts), gates), ("photo_residuals", _asked(photo_residuals), photo[0]),
+                          ("photo_counts", _asked(photo_counts), photo[1])))
+
+
+def icp_points_joint_host(xyz, normals, list_gray, depth, frame_gray, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8,
+                          min_points=6, frame_normals=None, min_cos=0.0, huber_m=0.0, photo_scale_m=0.0, photo_huber_grey=0.0, count=None,
+                          range2=None, residuals=None, photo_residuals=None):
+    """The loop of icp_points_joint for ONE list on the host (vors_icp_points_joint_host; needs no GPU): icp_points_robust_host()'s
+    arguments, list_gray [capacity] uint8 and frame_gray [rows, cols] uint8 (None only with photo_scale_m 0), photo_scale_m,
+    photo_huber_grey -> icp_points_robust_host()'s dict, "photo_residuals" [capacity] float32 (`photo_residuals`: an array to write
+    into, None = one filled with NaN) and "photo_counts" [2] uint32."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(depth, np.uint16)
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+    fn = None if frame_normals is None else np.ascontiguousarray(frame_normals, np.float32)
+    lg = None if list_gray is None else np.ascontiguousarray(list_gray, np.uint8).reshape(-1)
+    fg = None if frame_gray is None else np.ascontiguousarray(frame_gray, np.uint8)
+    if (len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,))
+            or (fn is not None and fn.shape != d.shape + (3,)) or (lg is not None and len(lg) != len(p)) or (fg is not None and fg.shape != d.shape)):
+        raise VorsError("icp_points_joint_host: xyz and normals [capacity, 3], list_gray [capacity] or None, depth [rows, cols], frame_gray "
+                        "[rows, cols] or None, cam5 [5], pose7 [7], range2 [2] or None, frame_normals [rows, cols, 3] or None")
+    out = {}
+    for name, given in (("residuals", residuals), ("photo_residuals", photo_residuals)):
+        if given is None:
+            given = np.full(len(p), np.nan, np.float32)
+        elif given.dtype != np.float32 or given.shape != (len(p),) or not given.flags.c_contiguous:
+            raise VorsError(f"icp_points_joint_host: {name} must be a contiguous float32 array ({len(p)},)")
+        out[name] = given
+    stats = np.zeros(1, ICP_STATS_DTYPE)
+    out.update(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), gate_counts=np.zeros(ICP_GATE_COUNTS, np.uint32),
+               photo_counts=np.zeros(ICP_PHOTO_COUNTS, np.uint32))
+    _check(lib().vors_icp_points_joint_host(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, _ptr(lg) if lg is not None and len(lg) else None,
+                                            len(p) if count is None else int(count), len(p), _ptr(rng), _ptr(pose), _ptr(d), _ptr(fg), _ptr(k),
+                                            d.shape[0], d.shape[1], float(depth_scale), float(dist_m), float(damping), float(step_eps), int(iters),
+                                            int(min_points), _ptr(fn), float(min_cos), float(huber_m), float(photo_scale_m),
+                                            float(photo_huber_grey), _ptr(out["pose"]), _ptr(stats), _ptr(out["sums29"]), _ptr(out["residuals"]),
+                                            _ptr(out["gate_counts"]), _ptr(out["photo_residuals"]), _ptr(out["photo_counts"])))
     return out
 
 
