@@ -549,9 +549,15 @@ struct IcpCall {
 #define ICP_BLOCK 256
 #define ICP_MAX_CHUNKS 1024  // cap of the evaluation grid's x extent: a longer list goes through the stride loop
 constexpr size_t icp_chunks(int capacity) { return ((size_t)capacity + VORS_ICP_CHUNK - 1) / VORS_ICP_CHUNK; }
-// The workspace: partials, chunk counts, state, in this order (every part a multiple of 4 bytes).
+// The workspace: partials, chunk counts, state, in this order (every part a multiple of 4 bytes): its size, and the three pointers of a call.
 inline size_t icp_workspace_bytes(int n, int capacity) {
     return (size_t)n * (icp_chunks(capacity) * (VORS_ICP_SUMS + 1) * 4 + sizeof(IcpState));
+}
+inline void icp_workspace_carve(IcpCall* call, void* workspace, int n, int capacity) {
+    const size_t slots = (size_t)n * icp_chunks(capacity);
+    call->partials = static_cast<float*>(workspace);
+    call->chunk_counts = reinterpret_cast<uint32_t*>(call->partials + slots * VORS_ICP_SUMS);
+    call->state = reinterpret_cast<IcpState*>(call->chunk_counts + slots);
 }
 // What the robust pass (vors_icp_points_robust; lie.h icp_row_robust / icp_products_robust) reads and writes beyond IcpCall. A record of
 // its own: icp_begin_kernel, icp_solve_kernel and the plain evaluation kernels take IcpCall by value, and their arguments stay as they are.

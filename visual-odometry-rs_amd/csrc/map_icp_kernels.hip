@@ -1,19 +1,19 @@
 // The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp): what surrounds the robust ICP pass
-// (icp_kernels.hip, unchanged) in a track call. A translation unit of its own, so that every other one's code stays what it was. The two
+// (icp_kernels.hip) in a track call. A translation unit of its own. The two
 // rules are lie.h map_icp_window / map_icp_verdict, the texts vors_map_icp_window_host / vors_map_icp_verdict_host run.
 // ARM    (map_icp_arm_kernel): one thread per sequence. The promotion list holds every promoted sequence once, so a thread finds its own
 //        flag by scanning it (at most n entries of 4 bytes, read by every thread from the cache) — no scatter, no second launch, no
 //        ordering between threads. It writes the window — (0, 0) for a sequence that is not promoted: its evaluation workgroups then
 //        return at once and the first solve freezes it TOO_FEW — copies the keyframe pose into the start pose and resets the record.
 // FRAME NORMALS (map_icp_frame_normals_kernel): the plane form of the normals pass for the promoted sequences only. depth_normals_kernel
-//        knows no selection and is not touched; this is its narrow trip (four pixels a workgroup width apart, five u16 taps, three dword
-//        stores each) under select_pair's rule, without pose and counts: per pixel lie.h depth_normal, hence vors_depth_normals' bits.
+//        knows no selection; this kernel runs its narrow trip (normals_device.h normals_narrow_trip: four pixels a workgroup width apart,
+//        five u16 taps, three dword stores each) under select_pair's rule, without pose and counts: hence vors_depth_normals' bits.
 // APPLY  (map_icp_apply_kernel): one thread per entry of the promotion list. The verdict; ACCEPTED: the ICP's pose into the three pose
 //        tables; the record; the totals (plain read-modify-write: a sequence is on the list once).
 // Every index is a sequence below n or a pixel below rows * cols; a list entry outside 0..n-1 (there is none) is skipped, not trusted.
 #include <cstddef>
 
-#include "device_common.h"
+#include "normals_device.h"
 
 namespace vors {
 
@@ -92,35 +92,8 @@ __global__ __launch_bounds__(NORMAL_BLOCK) void map_icp_frame_normals_kernel(Map
     const int plane = c.rows * c.cols;
     const uint16_t* depth = c.depth + (size_t)seq * (size_t)plane;
     float* normals = c.normals + (size_t)seq * (size_t)plane * 3;
-    const int base = blockIdx.x * (NORMAL_BLOCK * NORMAL_POINTS);
-    int xs[NORMAL_POINTS], ys[NORMAL_POINTS];
-    uint16_t d[NORMAL_POINTS][5];
-    bool valid[NORMAL_POINTS];
-#pragma unroll
-    for (int j = 0; j < NORMAL_POINTS; ++j) {
-        const int i = base + j * NORMAL_BLOCK + (int)threadIdx.x;
-        valid[j] = i < plane;
-        const int q = valid[j] ? i : 0;  // (a lane past the end reads pixel 0: a safe address)
-        ys[j] = q / c.cols;
-        xs[j] = q - ys[j] * c.cols;
-        const NormalTaps t = depth_normal_taps(xs[j], ys[j], c.cols, c.rows, c.step);
-        d[j][0] = depth[t.c];
-        d[j][1] = depth[t.l];
-        d[j][2] = depth[t.r];
-        d[j][3] = depth[t.u];
-        d[j][4] = depth[t.d];
-    }
-#pragma unroll
-    for (int j = 0; j < NORMAL_POINTS; ++j) {
-        if (!valid[j]) continue;
-        const int i = base + j * NORMAL_BLOCK + (int)threadIdx.x;
-        const DepthNormal o = depth_normal(c.k, c.depth_scale, c.step, c.jump_m, xs[j], ys[j], c.cols, c.rows, d[j][0], d[j][1], d[j][2], d[j][3],
-                                           d[j][4], false, iso_identity());
-        float* out = normals + 3 * (size_t)i;
-        out[0] = o.n.x;
-        out[1] = o.n.y;
-        out[2] = o.n.z;
-    }
+    uint32_t cnt[VORS_NORMAL_COUNTS] = {0u, 0u, 0u};  // (not kept)
+    normals_narrow_trip(c, depth, normals, plane, blockIdx.x * (NORMAL_BLOCK * NORMAL_POINTS), false, iso_identity(), cnt);
 }
 
 void launch_map_icp_arm(const MapIcpCall& c, hipStream_t s) {

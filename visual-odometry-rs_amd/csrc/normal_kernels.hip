@@ -3,7 +3,8 @@
 // PLANE (depth_normals_kernel): fuse_depth_kernel's shape — elementwise over the plane, 1024 pixels per workgroup. Where every plane allows
 //         it (cols % 4 == 0, depth 8-byte and normals 16-byte aligned) a thread takes four adjacent pixels of one row: the centres and the
 //         rows above and below as 8-byte loads, the eight horizontal taps as u16 loads, the four 12-byte rows out as three 16-byte stores;
-//         else four pixels a workgroup width apart, five u16 loads and three dword stores at consecutive addresses each. All loads of a
+//         else four pixels a workgroup width apart, five u16 loads and three dword stores at consecutive addresses each (normals_device.h
+//         normals_narrow_trip, the text the map ICP stage's frame normals run too). All loads of a
 //         trip are issued before the first use; a tap outside the plane reads the centre's address. Neighbour rows come through L2: a
 //         workgroup's 1024 pixels are a few consecutive rows, read once from HBM and again from the cache by the rows `step` away.
 // LIST  (points_normals_kernel): a gather, one point per lane — 4 bytes of pixel, five u16 taps, a 12-byte row out. grid = (chunks of the
@@ -11,11 +12,11 @@
 //         beyond the clipped range returns at once, a longer range goes through the stride loop (render_splat_kernel's scheme). Masked
 //         (sel_list): the keyframe map's launch over the promotion list.
 // COUNTS: per-thread integers, added across the wavefront, one LDS sum per workgroup, one global integer atomicAdd per non-zero counter
-//         and workgroup into a zeroed array (the pattern of the depth reprojection); compiled out without them. No workgroup waits for
+//         and workgroup into a zeroed array (device_common.h block_counts); compiled out without them. No workgroup waits for
 //         another.
 #include <algorithm>
 
-#include "device_common.h"
+#include "normals_device.h"
 
 namespace vors {
 
@@ -24,25 +25,6 @@ struct NormalArgs {
     NormalCall c;
     int wide;  // plane form: every plane allows four adjacent pixels per thread
 };
-
-template <bool COUNTS>
-__device__ __forceinline__ void normal_counts_commit(uint32_t (&cnt)[VORS_NORMAL_COUNTS], uint32_t* lds_counts, uint32_t* counts, int seq) {
-    if constexpr (COUNTS) {
-#pragma unroll
-        for (int k = 0; k < VORS_NORMAL_COUNTS; ++k) {
-#pragma unroll
-            for (int sh = 32; sh > 0; sh >>= 1) cnt[k] += (uint32_t)__shfl_xor((int)cnt[k], sh);
-            if ((threadIdx.x & 63) == 0) lds_counts[(threadIdx.x >> 6) * VORS_NORMAL_COUNTS + k] = cnt[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < VORS_NORMAL_COUNTS) {
-            uint32_t t = 0;
-#pragma unroll
-            for (int wv = 0; wv < NORMAL_BLOCK / 64; ++wv) t += lds_counts[wv * VORS_NORMAL_COUNTS + threadIdx.x];
-            if (t) atomicAdd(counts + (size_t)seq * VORS_NORMAL_COUNTS + threadIdx.x, t);
-        }
-    }
-}
 
 template <bool COUNTS>
 __global__ __launch_bounds__(NORMAL_BLOCK) void depth_normals_kernel(NormalArgs a) {
@@ -57,7 +39,6 @@ __global__ __launch_bounds__(NORMAL_BLOCK) void depth_normals_kernel(NormalArgs 
     const bool has_pose = c.poses != nullptr;
     const int base = blockIdx.x * (NORMAL_BLOCK * NORMAL_POINTS);
     uint32_t cnt[VORS_NORMAL_COUNTS] = {0u, 0u, 0u};
-    DepthNormal o[NORMAL_POINTS];
     if (a.wide) {  // (uniform; cols % 4 == 0: a thread's four pixels share a row and are all inside or all outside)
         const int i = base + NORMAL_POINTS * (int)threadIdx.x;
         if (i < plane) {
@@ -72,6 +53,7 @@ __global__ __launch_bounds__(NORMAL_BLOCK) void depth_normals_kernel(NormalArgs 
                 dl[j] = depth[x + j - c.step >= 0 ? i + j - c.step : i + j];
                 dr[j] = depth[x + j + c.step < c.cols ? i + j + c.step : i + j];
             }
+            DepthNormal o[NORMAL_POINTS];
             const uint16_t dc[NORMAL_POINTS] = {dc4.x, dc4.y, dc4.z, dc4.w}, du[NORMAL_POINTS] = {du4.x, du4.y, du4.z, du4.w},
                            dd[NORMAL_POINTS] = {dd4.x, dd4.y, dd4.z, dd4.w};
 #pragma unroll
@@ -89,41 +71,9 @@ __global__ __launch_bounds__(NORMAL_BLOCK) void depth_normals_kernel(NormalArgs 
             }
         }
     } else {
-        int xs[NORMAL_POINTS], ys[NORMAL_POINTS];
-        uint16_t d[NORMAL_POINTS][5];
-        bool valid[NORMAL_POINTS];
-#pragma unroll
-        for (int j = 0; j < NORMAL_POINTS; ++j) {
-            const int i = base + j * NORMAL_BLOCK + (int)threadIdx.x;
-            valid[j] = i < plane;
-            const int q = valid[j] ? i : 0;  // (a lane past the end reads pixel 0: a safe address)
-            ys[j] = q / c.cols;
-            xs[j] = q - ys[j] * c.cols;
-            const NormalTaps t = depth_normal_taps(xs[j], ys[j], c.cols, c.rows, c.step);
-            d[j][0] = depth[t.c];
-            d[j][1] = depth[t.l];
-            d[j][2] = depth[t.r];
-            d[j][3] = depth[t.u];
-            d[j][4] = depth[t.d];
-        }
-#pragma unroll
-        for (int j = 0; j < NORMAL_POINTS; ++j) {
-            if (!valid[j]) continue;
-            const int i = base + j * NORMAL_BLOCK + (int)threadIdx.x;
-            o[j] = depth_normal(c.k, c.depth_scale, c.step, c.jump_m, xs[j], ys[j], c.cols, c.rows, d[j][0], d[j][1], d[j][2], d[j][3], d[j][4],
-                                has_pose, pose);
-            cnt[0] += 1u;
-            cnt[1] += o[j].has_depth ? 1u : 0u;
-            cnt[2] += o[j].has_normal ? 1u : 0u;
-            if (normals) {
-                float* out = normals + 3 * (size_t)i;
-                out[0] = o[j].n.x;
-                out[1] = o[j].n.y;
-                out[2] = o[j].n.z;
-            }
-        }
+        normals_narrow_trip(c, depth, normals, plane, base, has_pose, pose, cnt);
     }
-    normal_counts_commit<COUNTS>(cnt, lds_counts, c.counts, seq);
+    if constexpr (COUNTS) block_counts<VORS_NORMAL_COUNTS, NORMAL_BLOCK>(cnt, lds_counts, CountsAdd{c.counts + (size_t)seq * VORS_NORMAL_COUNTS});
 }
 
 #define NORMAL_MAX_CHUNKS 1024
@@ -177,7 +127,7 @@ __global__ __launch_bounds__(NORMAL_BLOCK) void points_normals_kernel(NormalArgs
             out[2] = o.n.z;
         }
     }
-    normal_counts_commit<COUNTS>(cnt, lds_counts, c.counts, seq);
+    if constexpr (COUNTS) block_counts<VORS_NORMAL_COUNTS, NORMAL_BLOCK>(cnt, lds_counts, CountsAdd{c.counts + (size_t)seq * VORS_NORMAL_COUNTS});
 }
 
 __global__ void normals_snapshot_kernel(const uint32_t* src, uint32_t* dst, int n) {

@@ -547,11 +547,7 @@ static vors_status icp_points_device(const char* who, int n, const float* d_xyz,
     call.step_eps = step_eps;
     call.iters = iters;
     call.min_points = (uint32_t)min_points;
-    // the workspace: partials, chunk counts, state (engine.h icp_workspace_bytes)
-    const size_t slots = (size_t)n * icp_chunks(capacity);
-    call.partials = static_cast<float*>(d_workspace);
-    call.chunk_counts = reinterpret_cast<uint32_t*>(call.partials + slots * VORS_ICP_SUMS);
-    call.state = reinterpret_cast<IcpState*>(call.chunk_counts + slots);
+    icp_workspace_carve(&call, d_workspace, n, capacity);
     call.poses_out = d_poses7_out;
     call.stats = d_stats;
     call.sums29 = d_sums29;

@@ -240,10 +240,7 @@ static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint1
     call.step_eps = ic.p.step_eps;
     call.iters = ic.p.iters;
     call.min_points = (uint32_t)ic.p.min_points;
-    const size_t slots = (size_t)t->n_seq * icp_chunks(m.capacity);  // the workspace: partials, chunk counts, state (engine.h icp_workspace_bytes)
-    call.partials = static_cast<float*>(ic.workspace);
-    call.chunk_counts = reinterpret_cast<uint32_t*>(call.partials + slots * VORS_ICP_SUMS);
-    call.state = reinterpret_cast<IcpState*>(call.chunk_counts + slots);
+    icp_workspace_carve(&call, ic.workspace, t->n_seq, m.capacity);
     call.poses_out = ic.result;
     call.stats = ic.stats;
     const IcpRobust robust{ic.frame_normals, ic.p.min_cos, ic.p.huber_m, ic.gate_counts};
