@@ -127,7 +127,10 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_icp_points_robust_host, vors_trackers_icp_map_robust, VORS_ICP_GATE_COUNTS, likewise; + vors_trackers_enable_map_icp,
                               *    vors_trackers_map_icp, vors_tracker_enable_map_icp, vors_tracker_read_map_icp, vors_map_icp_window_host,
                               *    vors_map_icp_verdict_host, vors_map_icp_params, vors_map_icp_record, VORS_MAP_ICP_*, likewise; + vors_icp_points_joint,
-                              *    vors_icp_points_joint_host, vors_trackers_icp_map_joint, VORS_ICP_PHOTO_COUNTS, likewise) */
+                              *    vors_icp_points_joint_host, vors_trackers_icp_map_joint, VORS_ICP_PHOTO_COUNTS, likewise; + vors_icp_condition,
+                              *    vors_icp_condition_from_sums, vors_trackers_enable_map_icp_joint, vors_trackers_map_icp_joint,
+                              *    vors_tracker_enable_map_icp_joint, vors_tracker_read_map_icp_joint, vors_map_icp_verdict_joint_host,
+                              *    vors_map_icp_joint_params, vors_map_icp_joint_record, VORS_MAP_ICP_CONDITION, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -217,6 +220,20 @@ vors_status vors_tracker_enable_map_icp(vors_tracker* t, const vors_map_icp_para
 /* The record of the LAST vors_tracker_track and the running totals (attempted, accepted) to the host, each nullable; synchronises. Not
  * enabled: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_read_map_icp(vors_tracker* t, struct vors_map_icp_record* record, uint32_t totals[2]);
+/* Parameters of the map ICP correction THROUGH THE JOINT PASS AND WITH THE CONDITION TEST (vors_trackers_enable_map_icp_joint, below). */
+typedef struct vors_map_icp_joint_params {
+    vors_map_icp_params icp;                 /* every field as in vors_trackers_enable_map_icp */
+    float photo_scale_m, photo_huber_grey;   /* vors_icp_points_joint's; photo_scale_m = 0: the robust pass */
+    float max_dilution_t, max_dilution_r;    /* the CONDITION test; 0 = that bound is off */
+} vors_map_icp_joint_params;
+#define VORS_MAP_ICP_CONDITION     7   /* joint stage only: a dilution above its bound, or no dilution at all (H has no Cholesky factor) */
+struct vors_map_icp_joint_record;  /* section 2e, behind vors_map_icp_record */
+/* The correction of vors_trackers_enable_map_icp_joint (below) for the single sequence, its N = 1 case: same parameters, same refusals.
+ * Legal exactly where vors_tracker_enable_map_icp is, INSTEAD of it: either one after the other is refused. vors_tracker_track reads its
+ * results back behind the promotion, as with vors_tracker_enable_map_icp, and vors_tracker_read_map_icp works unchanged. */
+vors_status vors_tracker_enable_map_icp_joint(vors_tracker* t, const vors_map_icp_joint_params* params);
+/* The joint record of the LAST vors_tracker_track to the host (nullable); synchronises. No joint stage: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map_icp_joint(vors_tracker* t, struct vors_map_icp_joint_record* record);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -428,6 +445,33 @@ vors_status vors_trackers_enable_map_icp(vors_trackers* t, const vors_map_icp_pa
  * attempted and accepted since init. Not enabled: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_map_icp(const vors_trackers* t, const struct vors_map_icp_record** d_records,
                                   const uint32_t** d_totals /* [n][2]: attempted, accepted */);
+/* THE SAME CORRECTION THROUGH THE JOINT PASS, WITH A TEST ON THE CONDITIONING OF H IN THE VERDICT (opt-in, INSTEAD of
+ * vors_trackers_enable_map_icp: legal exactly where that call is, and either one after the other is refused). Point-to-plane rows do not
+ * constrain motion inside a plane, and nothing vors_trackers_enable_map_icp's verdict reads notices a slide; this stage differs from it in
+ * three things and in nothing else (window, launches' order, hazards, what an accepted or rejected result does are that call's):
+ * 1. The pass is vors_icp_points_joint's: list grey = the map's grey levels (vors_trackers_map's d_gray), frame grey = the level-0 grey
+ *    plane of the promoted frame (the caller's d_gray; in dense mode the handle's copy of it), photo_scale_m and photo_huber_grey as there.
+ *    photo_scale_m = 0 is the robust pass bit for bit. The pass's sums29 and photo counts are staged per sequence.
+ * 2. The verdict (one text, lie.h map_icp_verdict_joint; host twin vors_map_icp_verdict_joint_host) is vors_trackers_enable_map_icp's,
+ *    called as it stands, and ONLY BEHIND ACCEPTED: CONDITION when max_dilution_t > 0 and dilution_t <= max_dilution_t does not hold,
+ *    then the same for dilution_r; in float, NaN fails — a system whose H has no Cholesky factor fails every bound that is on. The
+ *    dilutions are vors_icp_condition's (section 2e) of the staged sums29, i.e. of the pass's FINAL evaluation at the pose it proposes.
+ *    With both bounds 0 the verdict is vors_trackers_enable_map_icp's for every input; the dilutions are computed and recorded all the same.
+ * 3. Beside every vors_map_icp_record there is a vors_map_icp_joint_record (section 2e), same indexing and lifetime: zeros for a sequence
+ *    the call did not promote.
+ * vors_trackers_map_icp works on such a handle unchanged; d_totals counts a CONDITION verdict as attempted and not accepted.
+ * Launches per track call: vors_trackers_enable_map_icp's, with the joint evaluation kernel in the evaluation's place and APPLY replaced
+ * by one that also takes the condition, plus the memset of the photo counts and one launch of one thread per sequence that resets the
+ * joint records (ARM itself stays as it is). Measured (64 sequences of 640x480, 6 rounds): 0.180 ms per track call when
+ * nothing promotes, against 0.159 ms for vors_trackers_enable_map_icp in the same session.
+ * VORS_ERR_INVALID_ARGUMENT, nothing allocated: everything vors_trackers_enable_map_icp refuses (of params->icp), either enable called
+ * before, photo_scale_m or photo_huber_grey negative or NaN, max_dilution_t or max_dilution_r negative or NaN. On top of
+ * vors_trackers_enable_map_icp's memory the call allocates per sequence 116 bytes of sums, 8 of photo counts and a
+ * vors_map_icp_joint_record (20 bytes), part of vors_trackers_workspace_bytes' figure and freed with the handle. No later call allocates. */
+vors_status vors_trackers_enable_map_icp_joint(vors_trackers* t, const vors_map_icp_joint_params* params);
+/* DEVICE pointer, owned by the handle and valid for its life, contents valid in stream order after the last track: d_joint_records [n],
+ * entry for entry beside vors_trackers_map_icp's d_records (nullable). No joint stage on this handle: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map_icp_joint(const vors_trackers* t, const struct vors_map_icp_joint_record** d_joint_records);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1015,6 +1059,23 @@ vors_status vors_icp_points_joint_host(const float* xyz, const float* normals, c
                                        float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
                                        uint32_t gate_counts[VORS_ICP_GATE_COUNTS] /* nullable */, float* photo_residuals /* nullable */,
                                        uint32_t photo_counts[VORS_ICP_PHOTO_COUNTS] /* nullable */);
+/* CONDITIONING OF AN ICP SYSTEM: the "dilution of precision" of the 29 sums of one evaluation (d_sums29 of vors_icp_points*: slot 1 = the
+ * matched count n, slots 8..28 = the upper triangle of H). One text (lie.h icp_condition) for the host entry and the device kernel. H is
+ * mirrored from the sums and is UNDAMPED; it is factored by the left-looking lower Cholesky in float64, the order of
+ * vors_pose_information_from_sums; C = H^-1 = L^-T L^-1 in float64; tt = (C00 + C11) + C22, rr = (C33 + C44) + C55;
+ * dilution_t = (float)sqrt((double)n * tt), dilution_r = (float)sqrt((double)n * rr). Geometric and photometric rows are both in metres:
+ * dilution_t has no unit, dilution_r is in 1/m. A direction the rows do not hold makes them large — or leaves H without a factor.
+ * Neither the list length nor the residuals enter (the residual-scaled covariance of vors_pose_information_from_sums depends on both: a
+ * perfect synthetic scene has rms -> 0 and would pass any bound on it while it slides). With Huber weights H is the weighted matrix.
+ * flags: bit 0 = !(sums29[1] > 6.0f), bit 1 = a pivot that is not > 0 (no early exit, as there); with either, both dilutions are NaN.
+ * vors_icp_condition_from_sums: host arithmetic, no GPU, outputs nullable; sums29 NULL is refused.
+ * vors_icp_condition: n systems, d_sums29 [n][29] -> d_dilution2 [n][2] = (dilution_t, dilution_r), d_flags [n] (nullable); one thread
+ * per system, enqueued on hip_stream, not synchronised, no allocation; bit for bit the host entry's. Refused with
+ * VORS_ERR_INVALID_ARGUMENT, nothing enqueued: n < 1, d_sums29 or d_dilution2 NULL, a pointer off 4-byte alignment. */
+vors_status vors_icp_condition_from_sums(const float sums29[29], float* dilution_t /* nullable */, float* dilution_r /* nullable */,
+                                         int32_t* flags /* nullable */);
+vors_status vors_icp_condition(int n, const float* d_sums29 /* [n][29] */, float* d_dilution2 /* [n][2] */, int32_t* d_flags /* nullable */,
+                               void* hip_stream);
 /* What vors_trackers_enable_map_icp (section 1b) keeps per sequence of the LAST track call: 112 bytes. A sequence the call did not
  * promote has verdict NOT_ATTEMPTED, frame = its keyframe's index, the window (0, 0), pose_before = pose_after = its keyframe pose and
  * zeros elsewhere. For a promoted one: frame = the new keyframe's index, the window, the pass's statistics and gate counts, pose_before =
@@ -1033,6 +1094,17 @@ vors_status vors_map_icp_window_host(const vors_map_segment* segments, uint32_t 
                                      int last_keyframes, uint32_t range2[2]);
 vors_status vors_map_icp_verdict_host(const vors_map_icp_params* params, const vors_icp_stats* stats, const float pose_before[7],
                                       const float pose_after[7], uint32_t* verdict);
+/* What vors_trackers_enable_map_icp_joint (section 1b) keeps BESIDE the vors_map_icp_record of a sequence, same indexing and lifetime:
+ * 20 bytes. dilution_t / dilution_r / condition_flags: vors_icp_condition of the pass's final sums29 (NaN, NaN and flags != 0 where H has
+ * no factor or too few points matched); photo_counts: vors_icp_points_joint's. Zeros for a sequence the call did not promote. */
+typedef struct vors_map_icp_joint_record {
+    float dilution_t, dilution_r; int32_t condition_flags; uint32_t photo_counts[VORS_ICP_PHOTO_COUNTS];
+} vors_map_icp_joint_record;
+/* The joint stage's verdict on the HOST (lie.h map_icp_verdict_joint, the text map_icp_apply_joint_kernel runs): vors_map_icp_verdict_host
+ * on params->icp, and only behind ACCEPTED the two bounds on the dilutions given -> *verdict, a VORS_MAP_ICP_* other than NOT_ATTEMPTED.
+ * Refused: a NULL argument, the verdict fields vors_trackers_enable_map_icp refuses, a dilution bound negative or NaN. */
+vors_status vors_map_icp_verdict_joint_host(const vors_map_icp_joint_params* params, const vors_icp_stats* stats, const float pose_before[7],
+                                            const float pose_after[7], float dilution_t, float dilution_r, uint32_t* verdict);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

@@ -612,6 +612,23 @@ void launch_map_icp_apply(const MapIcpCall& call, hipStream_t s);
 // The plane form of the normals pass for the sequences of call.sel_list only (required here), without a pose and without counts: per
 // pixel lie.h depth_normal, the text and the bits of launch_depth_normals, whose kernel knows no selection and stays as it is.
 void launch_map_icp_frame_normals(const NormalCall& call, hipStream_t s);
+// The correction through the joint pass with the condition test (vors_trackers_enable_map_icp_joint): what its two
+// kernels read and write beyond MapIcpCall. A record of its own: map_icp_arm_kernel and map_icp_apply_kernel take MapIcpCall by value,
+// and their arguments stay as they are.
+struct MapIcpJointCall {
+    MapIcpCall c;
+    MapIcpConditionGates condition;
+    const float* sums29;                       // [n][29] staging of the pass's final sums
+    const uint32_t* photo_counts;              // [n][VORS_ICP_PHOTO_COUNTS] staging
+    vors_map_icp_joint_record* joint_records;  // [n]
+};
+// ARM's second half: one thread per sequence, the joint record reset to zeros (map_icp_arm_kernel itself is launched by launch_map_icp_arm).
+void launch_map_icp_arm_joint(const MapIcpJointCall& call, hipStream_t s);
+// APPLY of the joint stage, in launch_map_icp_apply's place: lie.h icp_condition on the staged sums, lie.h map_icp_verdict_joint, the plain
+// record exactly as APPLY writes it, the joint record, the totals, the write-back of an accepted pose.
+void launch_map_icp_apply_joint(const MapIcpJointCall& call, hipStream_t s);
+// [n][29] sums -> [n][2] dilutions and [n] flags (nullable) (lie.h icp_condition), one thread per system; enqueued on s.
+void launch_icp_condition(const float* sums29, int n, float* dilution2, int32_t* flags, hipStream_t s);
 
 // Points per workgroup of an evaluation pass: a level of more points is cut into ceil(points / this) chunks of equal size, a function of
 // the level's point count alone — never of the batch — so that the order of the additions belongs to the level.

@@ -188,6 +188,10 @@ inline vors_status own_alloc_failed(vors_batch* b, const char* what) {
 extern "C" {
 vors_status map_icp_params_refusals(const char* who, const vors_map_icp_params* params);
 vors::MapIcpGates map_icp_gates(const vors_map_icp_params& params);
+// ... and of vors_map_icp_joint_params: the above of its `icp`, what vors_icp_points_joint refuses of the two photo fields, the two
+// dilution bounds; photo_huber_m = photo_scale_m * photo_huber_grey as vors_icp_points_joint takes it (once, on the host).
+vors_status map_icp_joint_params_refusals(const char* who, const vors_map_icp_joint_params* params);
+float map_icp_photo_huber_m(const vors_map_icp_joint_params& params);
 }
 // The stream work is enqueued on must belong to the handle's device (a stream of another device would silently run nothing useful).
 vors_status check_stream(const vors_batch* b, hipStream_t s);

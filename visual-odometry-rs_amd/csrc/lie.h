@@ -799,6 +799,94 @@ VORS_UNROLL
     return MAP_ICP_ACCEPTED;
 }
 
+// The correction with the joint pass and a test on the conditioning of H (vors_trackers_enable_map_icp_joint): two rules,
+// each ONE text, run by the host entries (vors_icp_condition_from_sums, vors_map_icp_verdict_joint_host) and by icp_condition_kernel /
+// map_icp_apply_joint_kernel.
+// CONDITION: the "dilution of precision" of an ICP system from the 29 sums of one evaluation (slot 1 = matched count n, slots 8..28 =
+// the upper triangle of H). H is mirrored from the sums, UNDAMPED, and factored by the left-looking lower Cholesky in f64, in
+// pose_information's order; C = H^-1 = L^-T L^-1 in f64; tt = (C00 + C11) + C22, rr = (C33 + C44) + C55;
+// dilution_t = (float)sqrt((double)n * tt), dilution_r = (float)sqrt((double)n * rr). Geometric and photometric rows are both in metres,
+// so dilution_t has no unit and dilution_r is in 1/m. Neither the list length nor the residuals enter: sigma2 of pose_information does,
+// and a perfect synthetic scene, whose rms tends to 0, would pass any bound on its covariance while it slides. With Huber weights H is
+// the WEIGHTED matrix; that is accepted. -> flags: bit 0 = !(n > 6.0f) (a NaN count too), bit 1 = a pivot that is not > 0 (no early
+// exit: as in pose_information, the factorisation runs on and what it then holds is never handed out); with either, both dilutions are
+// NaN. Both outputs are nullable. A second text of the factorisation and the inverse beside pose_information's, on purpose: that function
+// and its kernel stay word for word as they are, and only the diagonal of C is formed here.
+VORS_HD int icp_condition(const float* sums29, float* dilution_t, float* dilution_r) {
+    double a[6][6];
+    int k = 8;
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int c = r; c < 6; ++c) {
+            const double v = (double)sums29[k++];
+            a[r][c] = a[c][r] = v;
+        }
+    int flags = (sums29[1] > 6.0f) ? 0 : 1;
+    bool pivots_ok = true;
+VORS_UNROLL
+    for (int j = 0; j < 6; ++j) {
+VORS_UNROLL
+        for (int q = 0; q < j; ++q)
+VORS_UNROLL
+            for (int i = j; i < 6; ++i) a[i][j] -= a[j][q] * a[i][q];
+        pivots_ok = pivots_ok && a[j][j] > 0.0;
+        const double d = sqrt(a[j][j]);
+        a[j][j] = d;
+VORS_UNROLL
+        for (int i = j + 1; i < 6; ++i) a[i][j] /= d;
+    }
+    if (!pivots_ok) flags |= 2;
+    if (flags) {
+        const float nan = nanf("");
+        if (dilution_t) *dilution_t = nan;
+        if (dilution_r) *dilution_r = nan;
+        return flags;
+    }
+    double inv[6][6];  // L^-1, lower triangular, column by column (forward substitution on the unit vectors)
+VORS_UNROLL
+    for (int c = 0; c < 6; ++c)
+VORS_UNROLL
+        for (int r = 0; r < 6; ++r) {
+            if (r < c) {
+                inv[r][c] = 0.0;
+                continue;
+            }
+            double t = r == c ? 1.0 : 0.0;
+VORS_UNROLL
+            for (int q = c; q < r; ++q) t -= a[r][q] * inv[q][c];
+            inv[r][c] = t / a[r][r];
+        }
+    double diag[6];  // (L^-T L^-1)[r][r]
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r) {
+        double t = 0.0;
+VORS_UNROLL
+        for (int q = r; q < 6; ++q) t += inv[q][r] * inv[q][r];
+        diag[r] = t;
+    }
+    const double n = (double)sums29[1];
+    const double tt = (diag[0] + diag[1]) + diag[2], rr = (diag[3] + diag[4]) + diag[5];
+    if (dilution_t) *dilution_t = (float)sqrt(n * tt);
+    if (dilution_r) *dilution_r = (float)sqrt(n * rr);
+    return flags;
+}
+// VERDICT of the joint stage. DEFINITION: map_icp_verdict as it stands; only behind ACCEPTED it returns CONDITION (7, the value of
+// VORS_MAP_ICP_CONDITION) when a bound is > 0 and dilution <= bound does not hold — dilution_t first — compared in float, NaN fails: a
+// failed Cholesky therefore fails every bound that is on. With both bounds 0 it is map_icp_verdict for every input.
+#define MAP_ICP_CONDITION 7u
+struct MapIcpConditionGates {
+    float max_dilution_t, max_dilution_r;
+};
+VORS_HD uint32_t map_icp_verdict_joint(const MapIcpGates& g, const MapIcpConditionGates& cg, uint32_t status, uint32_t matched, uint32_t considered,
+                                       float rms, const float pose_before[7], const float pose_after[7], float dilution_t, float dilution_r) {
+    const MapIcpVerdict v = map_icp_verdict(g, status, matched, considered, rms, pose_before, pose_after);
+    if (v != MAP_ICP_ACCEPTED) return (uint32_t)v;
+    if (cg.max_dilution_t > 0.0f && !(dilution_t <= cg.max_dilution_t)) return MAP_ICP_CONDITION;
+    if (cg.max_dilution_r > 0.0f && !(dilution_r <= cg.max_dilution_r)) return MAP_ICP_CONDITION;
+    return (uint32_t)MAP_ICP_ACCEPTED;
+}
+
 // Jacobian of the warp: src/core/track/inverse_compositional.rs:313-341.
 VORS_HD void warp_jacobian_at(float gu, float gv, float u, float v, float _z, const Intr& k, float J[6]) {
     const float a = u - k.cu;

@@ -10,6 +10,8 @@
 //        five u16 taps, three dword stores each) under select_pair's rule, without pose and counts: hence vors_depth_normals' bits.
 // APPLY  (map_icp_apply_kernel): one thread per entry of the promotion list. The verdict; ACCEPTED: the ICP's pose into the three pose
 //        tables; the record; the totals (plain read-modify-write: a sequence is on the list once).
+// JOINT  (vors_trackers_enable_map_icp_joint): map_icp_arm_joint_kernel, map_icp_apply_joint_kernel and icp_condition_kernel,
+//        described where they stand, behind APPLY.
 // Every index is a sequence below n or a pixel below rows * cols; a list entry outside 0..n-1 (there is none) is skipped, not trusted.
 #include <cstddef>
 
@@ -78,6 +80,73 @@ __global__ void map_icp_apply_kernel(MapIcpCall c) {
     }
 }
 
+// The joint stage (vors_trackers_enable_map_icp_joint). ARM is map_icp_arm_kernel as it stands, followed by
+// map_icp_arm_joint_kernel: one thread per sequence, the joint record reset to zeros. APPLY is replaced by map_icp_apply_joint_kernel:
+// map_icp_apply_kernel's index discipline and its writes, word for word, around lie.h icp_condition on the sequence's staged sums and
+// lie.h map_icp_verdict_joint; then the joint record. Also here: icp_condition_kernel (vors_icp_condition), one thread per system.
+static_assert(sizeof(vors_map_icp_joint_record) == 20, "vors_map_icp_joint_record is 20 bytes");
+static_assert(VORS_MAP_ICP_CONDITION == MAP_ICP_CONDITION, "lie.h map_icp_verdict_joint returns the header's value");
+
+__global__ void map_icp_arm_joint_kernel(MapIcpJointCall j) {
+    const int seq = blockIdx.x * blockDim.x + threadIdx.x;
+    if (seq >= j.c.n) return;
+    j.joint_records[seq] = vors_map_icp_joint_record{};
+}
+
+__global__ void map_icp_apply_joint_kernel(MapIcpJointCall j) {
+    const MapIcpCall& c = j.c;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= min(max(*c.promo_count, 0), c.n)) return;
+    const int seq = c.promo_list[k];
+    if (seq < 0 || seq >= c.n) return;
+    vors_map_icp_record& r = c.records[seq];
+    const vors_icp_stats st = c.stats[seq];
+    float after[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) after[i] = c.result_poses[(size_t)seq * 7 + i];
+    float sums[29];
+#pragma unroll
+    for (int q = 0; q < 29; ++q) sums[q] = j.sums29[(size_t)seq * 29 + q];
+    vors_map_icp_joint_record jr{};
+    jr.condition_flags = icp_condition(sums, &jr.dilution_t, &jr.dilution_r);
+    const uint32_t v = map_icp_verdict_joint(c.gates, j.condition, st.status, st.matched, st.considered, st.rms, r.pose_before, after, jr.dilution_t,
+                                             jr.dilution_r);
+    r.verdict = v;
+    r.stats = st;
+#pragma unroll
+    for (int g = 0; g < VORS_ICP_GATE_COUNTS; ++g) r.gate_counts[g] = c.gate_counts[(size_t)seq * VORS_ICP_GATE_COUNTS + g];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) r.pose_after[i] = after[i];
+#pragma unroll
+    for (int q = 0; q < VORS_ICP_PHOTO_COUNTS; ++q) jr.photo_counts[q] = j.photo_counts[(size_t)seq * VORS_ICP_PHOTO_COUNTS + q];
+    j.joint_records[seq] = jr;
+    c.totals[2 * seq] += 1u;
+    if (v == (uint32_t)MAP_ICP_ACCEPTED) {
+        c.totals[2 * seq + 1] += 1u;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            c.kf_poses[(size_t)seq * 7 + i] = after[i];
+            c.cur_poses[(size_t)seq * 7 + i] = after[i];
+            c.out_poses[(size_t)seq * 7 + i] = after[i];
+        }
+    }
+}
+
+// 29 sums -> dilutions and flags (lie.h icp_condition), one thread per system
+__global__ __launch_bounds__(64) void icp_condition_kernel(const float* __restrict__ sums29, int n, float* __restrict__ dilution2,
+                                                           int32_t* __restrict__ flags) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    float sums[29];
+#pragma unroll
+    for (int q = 0; q < 29; ++q) sums[q] = sums29[(size_t)p * 29 + q];
+    float dt, dr;
+    const int fl = icp_condition(sums, &dt, &dr);
+    dilution2[(size_t)p * 2] = dt;
+    dilution2[(size_t)p * 2 + 1] = dr;
+    if (flags) flags[p] = fl;
+}
+
 struct MapIcpNormalArgs {
     int seq0;
     NormalCall c;
@@ -102,6 +171,18 @@ void launch_map_icp_arm(const MapIcpCall& c, hipStream_t s) {
 
 void launch_map_icp_apply(const MapIcpCall& c, hipStream_t s) {
     hipLaunchKernelGGL(map_icp_apply_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, s, c);
+}
+
+void launch_map_icp_arm_joint(const MapIcpJointCall& j, hipStream_t s) {
+    hipLaunchKernelGGL(map_icp_arm_joint_kernel, dim3((unsigned)((j.c.n + 255) / 256)), dim3(256), 0, s, j);
+}
+
+void launch_map_icp_apply_joint(const MapIcpJointCall& j, hipStream_t s) {
+    hipLaunchKernelGGL(map_icp_apply_joint_kernel, dim3((unsigned)((j.c.n + 255) / 256)), dim3(256), 0, s, j);
+}
+
+void launch_icp_condition(const float* sums29, int n, float* dilution2, int32_t* flags, hipStream_t s) {
+    hipLaunchKernelGGL(icp_condition_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, sums29, n, dilution2, flags);
 }
 
 void launch_map_icp_frame_normals(const NormalCall& c, hipStream_t s) {

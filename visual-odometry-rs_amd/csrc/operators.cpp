@@ -828,6 +828,59 @@ vors_status vors_map_icp_verdict_host(const vors_map_icp_params* params, const v
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The correction through the joint pass with the condition test (vors_trackers_enable_map_icp_joint, trackers.cpp): the
+// refusals of its parameters, the conditioning measure on the host and on the device (lie.h icp_condition) and the verdict's host twin
+// (lie.h map_icp_verdict_joint).
+// ---------------------------------------------------------------------------------------------------------------
+static vors_status map_icp_condition_refusals(const std::string& w, const vors_map_icp_joint_params& p) {
+    if (!(p.max_dilution_t >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": max_dilution_t must be >= 0 (and not NaN; 0 = that bound is off)");
+    if (!(p.max_dilution_r >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": max_dilution_r must be >= 0 (and not NaN; 0 = that bound is off)");
+    return VORS_OK;
+}
+vors_status map_icp_joint_params_refusals(const char* who, const vors_map_icp_joint_params* p) {
+    if (!p) return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": params is NULL");
+    vors_status st = map_icp_params_refusals(who, &p->icp);
+    if (st != VORS_OK) return st;
+    // (what vors_icp_points_joint refuses of the two photo fields, in its own sentences: the grey levels are the handle's)
+    alignas(16) static const float some[4] = {0.f, 0.f, 0.f, 0.f};
+    if ((st = icp_joint_refusals(who, some, some, p->photo_scale_m, p->photo_huber_grey, nullptr, nullptr)) != VORS_OK) return st;
+    return map_icp_condition_refusals(who, *p);
+}
+float map_icp_photo_huber_m(const vors_map_icp_joint_params& p) { return icp_photo_huber_m(p.photo_scale_m, p.photo_huber_grey); }
+
+vors_status vors_icp_condition_from_sums(const float sums29[29], float* dilution_t, float* dilution_r, int32_t* flags) {
+    if (!sums29) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_condition_from_sums: sums29 is NULL");
+    const int fl = icp_condition(sums29, dilution_t, dilution_r);
+    if (flags) *flags = fl;
+    return VORS_OK;
+}
+
+vors_status vors_icp_condition(int n, const float* d_sums29, float* d_dilution2, int32_t* d_flags, void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_condition: n must be >= 1");
+    if (!d_sums29) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_condition: d_sums29 is NULL");
+    if (!d_dilution2) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_condition: d_dilution2 is NULL");
+    if ((uintptr_t)d_sums29 % 4 != 0 || (uintptr_t)d_dilution2 % 4 != 0 || (uintptr_t)d_flags % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "icp_condition: d_sums29, d_dilution2 and d_flags must be 4-byte aligned");
+    vors_status st = require_device();
+    if (st != VORS_OK) return st;
+    launch_icp_condition(d_sums29, n, d_dilution2, d_flags, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_map_icp_verdict_joint_host(const vors_map_icp_joint_params* params, const vors_icp_stats* stats, const float pose_before[7],
+                                            const float pose_after[7], float dilution_t, float dilution_r, uint32_t* verdict) {
+    if (!params || !stats || !pose_before || !pose_after || !verdict)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_verdict_joint_host: a NULL argument (params, stats, pose_before, pose_after, verdict)");
+    vors_status st = map_icp_verdict_refusals("map_icp_verdict_joint_host", params->icp);
+    if (st != VORS_OK) return st;
+    if ((st = map_icp_condition_refusals("map_icp_verdict_joint_host", *params)) != VORS_OK) return st;
+    *verdict = map_icp_verdict_joint(map_icp_gates(params->icp), MapIcpConditionGates{params->max_dilution_t, params->max_dilution_r}, stats->status,
+                                     stats->matched, stats->considered, stats->rms, pose_before, pose_after, dilution_t, dilution_r);
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Lie helpers (host arithmetic)
 // ---------------------------------------------------------------------------------------------------------------
 void vors_se3_exp(const float xi[6], float out_iso7[7]) { iso_store(se3_exp(xi), out_iso7); }

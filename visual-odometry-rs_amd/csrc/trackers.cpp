@@ -76,9 +76,17 @@ struct vors_trackers {
         //   stats, gates       [n_seq] staging of the ICP's statistics and gate counts, copied into the records by APPLY
         //   records, totals    [n_seq], [n_seq][2]: what vors_trackers_map_icp shows
         //   frame_normals      [n_seq][S0][3], with normal_gate only
+        // Through the joint pass with the condition test (vors_trackers_enable_map_icp_joint; `joint`, otherwise nothing below exists):
+        //   jp                 the parameters; p above is jp.icp
+        //   sums29, photo_counts   [n_seq][29], [n_seq][VORS_ICP_PHOTO_COUNTS] staging of the pass's final sums and photo counts
+        //   joint_records      [n_seq], beside records: what vors_trackers_map_icp_joint shows
         struct Icp {
-            bool on = false;
+            bool on = false, joint = false;
             vors_map_icp_params p{};
+            vors_map_icp_joint_params jp{};
+            float* sums29 = nullptr;
+            uint32_t* photo_counts = nullptr;
+            vors_map_icp_joint_record* joint_records = nullptr;
             MapIcpGates gates{};
             void* workspace = nullptr;
             uint32_t *promoted = nullptr, *ranges = nullptr, *gate_counts = nullptr, *totals = nullptr;
@@ -176,7 +184,11 @@ static void trackers_map_emit_all(vors_trackers* t, const Geom& gm, const uint16
 // which only an emission and its normals pass write; APPLY writes the three pose tables behind everything of this call that reads them
 // (the LM stage, launch_trackers_advance, a single tracker's read-back when it is ordered here) and before the emission, the normals pass
 // and the next call's LM stage, which read them. Everything else is the stage's own.
-static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint16_t* depth, hipStream_t s) {
+// The joint stage (vors_trackers_enable_map_icp_joint) is this sequence with three differences: the pass is the joint one — list grey =
+// the map's, frame grey = `gray`, the level-0 plane the keyframe stage of this call read (the caller's frame, or own_gray behind its
+// promote copy), which nothing writes before the next call — with its sums and photo counts into staging; ARM is followed by the reset
+// of the joint records; APPLY is the joint one. `gray` is read only then.
+static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint16_t* depth, const uint8_t* gray, hipStream_t s) {
     const Geom& g = t->batch->g;
     const vors_trackers::Map& m = t->map;
     const vors_trackers::Map::Icp& ic = m.icp;
@@ -205,6 +217,11 @@ static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint1
     mc.records = ic.records;
     mc.totals = ic.totals;
     launch_map_icp_arm(mc, s);
+    // (the joint stage's record: built only where the joint stage runs, so that the plain path reads as it always did)
+    auto joint_call = [&] {
+        return MapIcpJointCall{mc, MapIcpConditionGates{ic.jp.max_dilution_t, ic.jp.max_dilution_r}, ic.sums29, ic.photo_counts, ic.joint_records};
+    };
+    if (ic.joint) launch_map_icp_arm_joint(joint_call(), s);
     if (ic.frame_normals) {
         NormalCall nc{};
         nc.n = t->n_seq;
@@ -244,8 +261,15 @@ static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint1
     call.poses_out = ic.result;
     call.stats = ic.stats;
     const IcpRobust robust{ic.frame_normals, ic.p.min_cos, ic.p.huber_m, ic.gate_counts};
-    launch_icp_points(call, &robust, s);
-    launch_map_icp_apply(mc, s);
+    if (!ic.joint) {
+        launch_icp_points(call, &robust, s);
+        launch_map_icp_apply(mc, s);
+        return;
+    }
+    call.sums29 = ic.sums29;
+    const IcpJoint joint{m.gray, gray, ic.jp.photo_scale_m, map_icp_photo_huber_m(ic.jp), nullptr, ic.photo_counts};
+    launch_icp_points(call, &robust, s, &joint);
+    launch_map_icp_apply_joint(joint_call(), s);
 }
 
 // The two halves of vors_trackers_track: Tracker::track up to the keyframe test, and the promotion of the sequences that switch — the
@@ -323,7 +347,8 @@ static vors_status trackers_promote(vors_trackers* t, const uint8_t* d_gray, con
     }
     if (t->map.on) {
         const uint16_t* map_depth = b->g.mode == VORS_CANDIDATES_DENSE ? t->own_depth.as<uint16_t>() : d_depth;
-        if (t->map.icp.on) trackers_map_icp_stage(t, gm, map_depth, s);
+        if (t->map.icp.on)
+            trackers_map_icp_stage(t, gm, map_depth, b->g.mode == VORS_CANDIDATES_DENSE ? t->own_gray.as<uint8_t>() : d_gray, s);
         trackers_map_emit_all(t, gm, map_depth, s);
     }
     STAGE_END(b, 1, s);
@@ -509,14 +534,19 @@ static vors_status trackers_map_normals_enable(vors_trackers* t, bool started, c
     return VORS_OK;
 }
 // The ICP correction's switch: every refusal, then every buffer at once. `started` / `before`: as for the voxel filter.
-static vors_status trackers_map_icp_enable(vors_trackers* t, bool started, const char* before, const vors_map_icp_params* p) {
-    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: needs an enabled keyframe map first (vors_trackers_enable_map)");
+// jp: NULL = vors_trackers_enable_map_icp with p; otherwise vors_trackers_enable_map_icp_joint (p is not read). One flag for both: either
+// enable after the other finds the correction already enabled.
+static vors_status trackers_map_icp_enable(vors_trackers* t, bool started, const char* before, const vors_map_icp_params* p,
+                                           const vors_map_icp_joint_params* jp = nullptr, bool joint = false) {
+    const std::string w(joint ? "enable_map_icp_joint" : "enable_map_icp");
+    if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": needs an enabled keyframe map first (vors_trackers_enable_map)");
     if (!t->map.normals.on)
-        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: needs the normals of the map first (vors_trackers_enable_map_normals)");
-    if (t->map.icp.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp: the correction is already enabled");
-    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, std::string("enable_map_icp: legal only before ") + before);
-    vors_status st = map_icp_params_refusals("enable_map_icp", p);
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": needs the normals of the map first (vors_trackers_enable_map_normals)");
+    if (t->map.icp.on) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the correction is already enabled");
+    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": legal only before " + before);
+    vors_status st = joint ? map_icp_joint_params_refusals(w.c_str(), jp) : map_icp_params_refusals(w.c_str(), p);
     if (st != VORS_OK) return st;
+    if (joint) p = &jp->icp;
     vors_batch* b = t->batch;
     DeviceGuard guard(b->device);
     const size_t n = (size_t)t->n_seq;
@@ -532,6 +562,11 @@ static vors_status trackers_map_icp_enable(vors_trackers* t, bool started, const
     b->own.alloc(&ic.records, n);
     b->own.alloc(&ic.totals, n * 2);
     if (p->normal_gate) b->own.alloc(&ic.frame_normals, n * (size_t)b->g.S0 * 3);
+    if (joint) {
+        b->own.alloc(&ic.sums29, n * 29);
+        b->own.alloc(&ic.photo_counts, n * VORS_ICP_PHOTO_COUNTS);
+        b->own.alloc(&ic.joint_records, n);
+    }
     if (b->own.err != hipSuccess) {
         ic = vors_trackers::Map::Icp{};
         return own_alloc_failed(b, "ICP correction of the keyframe map");
@@ -539,6 +574,8 @@ static vors_status trackers_map_icp_enable(vors_trackers* t, bool started, const
     ic.workspace = ws;
     ic.p = *p;
     ic.gates = map_icp_gates(*p);
+    if (joint) ic.jp = *jp;
+    ic.joint = joint;
     ic.on = true;
     return VORS_OK;
 }
@@ -547,6 +584,7 @@ static vors_status trackers_map_icp_init(vors_trackers* t, hipStream_t s) {
     const size_t n = (size_t)t->n_seq;
     HIP_TRY(hipMemsetAsync(t->map.icp.records, 0, n * sizeof(vors_map_icp_record), s));
     HIP_TRY(hipMemsetAsync(t->map.icp.totals, 0, n * 2 * sizeof(uint32_t), s));
+    if (t->map.icp.joint) HIP_TRY(hipMemsetAsync(t->map.icp.joint_records, 0, n * sizeof(vors_map_icp_joint_record), s));
     return VORS_OK;
 }
 // An empty map (and an empty voxel table), then keyframe 0 of every sequence. `depth`: the planes keyframe 0 was made from, read only
@@ -670,6 +708,38 @@ vors_status vors_tracker_read_map_icp(vors_tracker* t, vors_map_icp_record* reco
     DeviceGuard guard(t->device);
     if (record) HIP_TRY(hipMemcpyAsync(record, ic.records, sizeof(vors_map_icp_record), hipMemcpyDeviceToHost, t->s_main));
     if (totals) HIP_TRY(hipMemcpyAsync(totals, ic.totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    return VORS_OK;
+}
+
+vors_status vors_trackers_enable_map_icp_joint(vors_trackers* t, const vors_map_icp_joint_params* params) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp_joint: the handle t is NULL");
+    return trackers_map_icp_enable(t, t->initialised, "vors_trackers_init", nullptr, params, true);
+}
+
+vors_status vors_trackers_map_icp_joint(const vors_trackers* t, const vors_map_icp_joint_record** d_joint_records) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_joint: the handle t is NULL");
+    if (!t->map.icp.joint)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_joint: the joint ICP correction is not enabled (vors_trackers_enable_map_icp_joint)");
+    if (d_joint_records) *d_joint_records = t->map.icp.joint_records;
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map_icp_joint(vors_tracker* t, const vors_map_icp_joint_params* params) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp_joint: the handle t is NULL");
+    vors_status st = trackers_map_icp_enable(t->seq, t->has_last, "the first vors_tracker_track", nullptr, params, true);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    return trackers_map_icp_init(t->seq, t->s_main);
+}
+
+vors_status vors_tracker_read_map_icp_joint(vors_tracker* t, vors_map_icp_joint_record* record) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp_joint: the handle t is NULL");
+    const vors_trackers::Map::Icp& ic = t->seq->map.icp;
+    if (!ic.joint)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp_joint: the joint ICP correction is not enabled (vors_tracker_enable_map_icp_joint)");
+    DeviceGuard guard(t->device);
+    if (record) HIP_TRY(hipMemcpyAsync(record, ic.joint_records, sizeof(vors_map_icp_joint_record), hipMemcpyDeviceToHost, t->s_main));
     HIP_TRY(hipStreamSynchronize(t->s_main));
     return VORS_OK;
 }

@@ -207,6 +207,16 @@ class Tracker {  // inverse_compositional.rs:31-34
         check(vors_tracker_read_map_icp(h_, nullptr, totals));
         return {totals[0], totals[1]};
     }
+    // Extension: the same correction through the joint pass with the condition test (vors_tracker_enable_map_icp_joint), INSTEAD of
+    // enable_map_icp. read_map_icp_totals() works unchanged.
+    void enable_map_icp_joint(const vors_map_icp_joint_params& params) { check(vors_tracker_enable_map_icp_joint(h_, &params)); }
+    // The verdict (a VORS_MAP_ICP_*) of the last track() (vors_tracker_read_map_icp; synchronises). What vors_track counts CONDITION
+    // verdicts from; works with either correction.
+    std::uint32_t read_map_icp_verdict() {
+        vors_map_icp_record record{};
+        check(vors_tracker_read_map_icp(h_, &record, nullptr));
+        return record.verdict;
+    }
     // Extension: the map seen from a pose (vors_tracker_render_map; synchronises): a z-buffered depth map and grey image in the geometry
     // of pyramid level `level`, row-major, the arguments of Config::init. pose = nullptr: the current frame's pose; range2 = nullptr: the
     // whole map, else (first, count) of the ranks to render (a vors_map_segment's `first`); footprint: 1, 2 or 3 pixels wide.

@@ -22,6 +22,11 @@
 // window matched, an rms of at most 0.01 m, and a step of at most 0.05 m and 0.05 rad. Malformed, or without --map / --map-normals: the
 // usage (which repeats these defaults) and status 2, before any device is touched. After the last frame one line on stderr:
 // `map-icp: attempted A accepted B`.
+// `--map-icp-joint PHOTO_SCALE_M[,PHOTO_HUBER_GREY[,MAX_DILUTION_T[,MAX_DILUTION_R]]]` (needs --map-icp, whose fields become the correction's)
+// runs that correction through the joint point-to-plane and photometric pass with a test on the conditioning of the system in the verdict
+// (vors_tracker_enable_map_icp_joint). PHOTO_SCALE_M: metres per grey level, 0 = no photometric row; defaults: PHOTO_HUBER_GREY 0 (none),
+// both bounds 0 (off). Malformed or without --map-icp: the usage and status 2, before any device is touched. The line after the last
+// frame is then `map-icp: attempted A accepted B condition C`, C the corrections the condition test alone rejected.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -149,8 +154,29 @@ static bool parse_map_icp(const std::string& val, vors_map_icp_params& p) {
     return *end == '\0';
 }
 
+// "PHOTO_SCALE_M[,PHOTO_HUBER_GREY[,MAX_DILUTION_T[,MAX_DILUTION_R]]]": up to four numbers, nothing after the last. The VALUES are judged
+// by the library.
+static const char* MAP_ICP_JOINT_HELP =
+    "Malformed --map-icp-joint: expected PHOTO_SCALE_M[,PHOTO_HUBER_GREY[,MAX_DILUTION_T[,MAX_DILUTION_R]]] (metres per grey level, 0 = no "
+    "photometric row; defaults: PHOTO_HUBER_GREY 0 = none, MAX_DILUTION_T 0 and MAX_DILUTION_R 0 = that bound is off)";
+static bool parse_map_icp_joint(const std::string& val, vors_map_icp_joint_params& p) {
+    if (val.empty()) return false;
+    const char* s = val.c_str();
+    char* end = nullptr;
+    p.photo_scale_m = std::strtof(s, &end);
+    if (end == s) return false;
+    float* floats[3] = {&p.photo_huber_grey, &p.max_dilution_t, &p.max_dilution_r};
+    for (int k = 0; k < 3 && *end == ','; ++k) {
+        s = end + 1;
+        *floats[k] = std::strtof(s, &end);
+        if (end == s) return false;
+    }
+    return *end == '\0';
+}
+
 int main(int argc, char** argv) {
-    bool map_icp = false, bad_map_icp = false;
+    bool map_icp = false, bad_map_icp = false, map_icp_joint = false, bad_map_icp_joint = false;
+    vors_map_icp_joint_params joint_params{};
     vors_map_icp_params icp_params{};
     icp_params.step_eps = 1e-5f;
     icp_params.iters = 8;
@@ -202,6 +228,10 @@ int main(int argc, char** argv) {
             map_icp = parse_map_icp(val, icp_params);
             bad_map_icp = !map_icp;
             ++a;
+        } else if (flag == "--map-icp-joint") {
+            map_icp_joint = parse_map_icp_joint(val, joint_params);
+            bad_map_icp_joint = !map_icp_joint;
+            ++a;
         } else {
             bad_flag = true;
         }
@@ -226,6 +256,10 @@ int main(int argc, char** argv) {
     }
     if (bad_map_icp || (map_icp && (!map || !map_normals))) {
         std::fprintf(stderr, "%s\n\"%s\"\n", USAGE, bad_map_icp ? MAP_ICP_HELP : !map ? "--map-icp needs --map" : "--map-icp needs --map-normals");
+        return 2;
+    }
+    if (bad_map_icp_joint || (map_icp_joint && !map_icp)) {
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE, bad_map_icp_joint ? MAP_ICP_JOINT_HELP : "--map-icp-joint needs --map-icp");
         return 2;
     }
     if (argc > 3) argc = bad_flag ? 0 : 3;
@@ -279,7 +313,13 @@ int main(int argc, char** argv) {
         if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
         if (map_voxel) tracker.enable_map_voxels(voxel_m, voxel_table_slots);
         if (map_normals) tracker.enable_map_normals(normals_step, normals_jump_m);  // (behind the voxel filter, which emits keyframe 0 again)
-        if (map_icp) tracker.enable_map_icp(icp_params);
+        std::uint32_t condition = 0;
+        if (map_icp_joint) {
+            joint_params.icp = icp_params;
+            tracker.enable_map_icp_joint(joint_params);
+        } else if (map_icp) {
+            tracker.enable_map_icp(icp_params);
+        }
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);
@@ -288,10 +328,17 @@ int main(int argc, char** argv) {
                           {gray.data(), (int)h, (int)w, VORS_ROW_MAJOR});
             const auto cf = tracker.current_frame();
             std::printf("%s\n", tum_rgbd::to_string(tum_rgbd::Frame{cf.first, cf.second}).c_str());
+            // The handle's totals are (attempted, accepted) and their layout is ABI, so CONDITION is counted here, from the record of each
+            // frame: one small read-back and one synchronisation per frame, which exist for this counter alone and only with this flag
+            // (the frame has already waited for its promotion: with the correction on, track() reads its results back behind it).
+            if (map_icp_joint && tracker.read_map_icp_verdict() == VORS_MAP_ICP_CONDITION) ++condition;
         }
         if (map_icp) {
             const auto totals = tracker.read_map_icp_totals();
-            std::fprintf(stderr, "map-icp: attempted %u accepted %u\n", totals.first, totals.second);
+            if (map_icp_joint)
+                std::fprintf(stderr, "map-icp: attempted %u accepted %u condition %u\n", totals.first, totals.second, condition);
+            else
+                std::fprintf(stderr, "map-icp: attempted %u accepted %u\n", totals.first, totals.second);
         }
         if (map) {
             if (map_voxel && tracker.read_map_voxels().overflow != 0)

@@ -117,6 +117,8 @@ EXPORTED_SYMBOLS = [
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_trackers_enable_map_icp", "vors_trackers_map_icp", "vors_tracker_enable_map_icp", "vors_tracker_read_map_icp",
     "vors_map_icp_window_host", "vors_map_icp_verdict_host",
+    "vors_icp_condition_from_sums", "vors_icp_condition", "vors_trackers_enable_map_icp_joint", "vors_trackers_map_icp_joint",
+    "vors_tracker_enable_map_icp_joint", "vors_tracker_read_map_icp_joint", "vors_map_icp_verdict_joint_host",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -226,6 +228,13 @@ def lib():
         _lib.vors_tracker_read_map_icp.argtypes = [vp, vp, vp]
         _lib.vors_map_icp_window_host.argtypes = [vp, C.c_uint32, i, C.c_uint32, i, i, vp]
         _lib.vors_map_icp_verdict_host.argtypes = [vp, vp, vp, vp, vp]
+        _lib.vors_icp_condition_from_sums.argtypes = [vp, vp, vp, vp]
+        _lib.vors_icp_condition.argtypes = [i, vp, vp, vp, vp]
+        _lib.vors_trackers_enable_map_icp_joint.argtypes = [vp, vp]
+        _lib.vors_trackers_map_icp_joint.argtypes = [vp, C.POINTER(vp)]
+        _lib.vors_tracker_enable_map_icp_joint.argtypes = [vp, vp]
+        _lib.vors_tracker_read_map_icp_joint.argtypes = [vp, vp]
+        _lib.vors_map_icp_verdict_joint_host.argtypes = [vp, vp, vp, vp, f, f, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -486,7 +495,7 @@ class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
     def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None,
-                 map_normals=None, map_icp=None):
+                 map_normals=None, map_icp=None, map_icp_joint=None):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
         (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
         keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it. map_voxels: None,
@@ -494,7 +503,10 @@ class Tracker:
         map_normals: None, or (step, jump_m) — a surface normal per map entry (vors_tracker_enable_map_normals;
         Trackers.enable_map_normals), switched on after the voxel filter; needs map with level 0; read_map_normals() returns them.
         map_icp: None, a number (dist_m) or a dict of map_icp_params()' keywords — the ICP correction at keyframe promotion
-        (vors_tracker_enable_map_icp; Trackers.enable_map_icp), switched on last; needs map_normals; read_map_icp() returns its record."""
+        (vors_tracker_enable_map_icp; Trackers.enable_map_icp), switched on last; needs map_normals; read_map_icp() returns its record.
+        map_icp_joint: None, or a dict of map_icp_joint_params()' keywords — the same correction through the joint pass with the condition
+        test (vors_tracker_enable_map_icp_joint; Trackers.enable_map_icp_joint), INSTEAD of map_icp; read_map_icp() works unchanged and
+        read_map_icp_joint() returns the joint record."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         self._map = map = _map_args(map)
         self._map_voxels = map_voxels = _map_voxels_args(map_voxels)
@@ -506,6 +518,11 @@ class Tracker:
         self._map_icp = map_icp = _map_icp_arg(map_icp)
         if map_icp is not None and map_normals is None:
             raise VorsError("map_icp: the correction needs the map's normals (Tracker(..., map_normals=(step, jump_m)))")
+        self._map_icp_joint = map_icp_joint = None if map_icp_joint is None else map_icp_joint_params(**map_icp_joint)
+        if map_icp_joint is not None and map_icp is not None:
+            raise VorsError("map_icp_joint: the joint stage stands INSTEAD of map_icp: give one of the two")
+        if map_icp_joint is not None and map_normals is None:
+            raise VorsError("map_icp_joint: the correction needs the map's normals (Tracker(..., map_normals=(step, jump_m)))")
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -526,11 +543,22 @@ class Tracker:
             _check(lib().vors_tracker_enable_map_normals(self._h, *map_normals))
         if map_icp is not None:
             _check(lib().vors_tracker_enable_map_icp(self._h, C.byref(map_icp)))
+        if map_icp_joint is not None:
+            _check(lib().vors_tracker_enable_map_icp_joint(self._h, C.byref(map_icp_joint)))
+
+    def read_map_icp_joint(self):
+        """The joint stage's record of the last track() on the host (vors_tracker_read_map_icp_joint; synchronises) -> a structured scalar
+        of MAP_ICP_JOINT_RECORD_DTYPE, beside read_map_icp()'s record."""
+        if self._map_icp_joint is None:
+            raise VorsError("read_map_icp_joint: the joint correction is not enabled (Tracker(..., map_icp_joint=a dict of parameters))")
+        rec = np.zeros(1, MAP_ICP_JOINT_RECORD_DTYPE)
+        _check(lib().vors_tracker_read_map_icp_joint(self._h, _ptr(rec)))
+        return rec[0]
 
     def read_map_icp(self):
         """The correction's record of the last track() and its running totals on the host (vors_tracker_read_map_icp; synchronises) ->
         dict: "record", a structured scalar of MAP_ICP_RECORD_DTYPE, and "totals" [2] uint32 (attempted, accepted)."""
-        if self._map_icp is None:
+        if self._map_icp is None and self._map_icp_joint is None:
             raise VorsError("read_map_icp: the correction is not enabled (Tracker(..., map_icp=dist_m or a dict of parameters))")
         rec, totals = np.zeros(1, MAP_ICP_RECORD_DTYPE), np.zeros(2, np.uint32)
         _check(lib().vors_tracker_read_map_icp(self._h, _ptr(rec), _ptr(totals)))
@@ -1180,6 +1208,23 @@ class Trackers:
         p = map_icp_params(**params)
         _check(lib().vors_trackers_enable_map_icp(self._h, C.byref(p)))
 
+    def enable_map_icp_joint(self, **params):
+        """The correction of enable_map_icp() through the joint pass and with the condition test (vors_trackers_enable_map_icp_joint):
+        INSTEAD of enable_map_icp(), legal where it is. The pass is icp_points_joint()'s (list grey = the map's, frame grey = the promoted
+        frame's level 0); behind ACCEPTED the verdict returns MAP_ICP_CONDITION when a dilution (icp_condition() of the pass's final sums)
+        exceeds its bound. params: map_icp_joint_params()' keywords — dist_m required, the rest MAP_ICP_DEFAULTS and MAP_ICP_JOINT_DEFAULTS."""
+        p = map_icp_joint_params(**params)
+        _check(lib().vors_trackers_enable_map_icp_joint(self._h, C.byref(p)))
+
+    def map_icp_joint(self, copy=True):
+        """-> [n, 20] uint8 tensor (vors_trackers_map_icp_joint), valid in stream order after the last track(): the
+        vors_map_icp_joint_record of every sequence beside map_icp()'s records, as bytes: decode_map_icp_joint_records(). copy=False: a view
+        of the handle's own buffer, which dies with this object."""
+        p = C.c_void_p()
+        _check(lib().vors_trackers_map_icp_joint(self._h, C.byref(p)))
+        out = _device_view(p.value, (self.n, MAP_ICP_JOINT_RECORD_DTYPE.itemsize), "|u1", _torch_device(self._device))
+        return out.clone() if copy else out
+
     def map_icp(self, copy=True):
         """-> dict of tensors (vors_trackers_map_icp), valid in stream order after the last track(): "records" [n, 112] uint8 — the
         vors_map_icp_record of every sequence for the LAST track call as bytes: decode_map_icp_records() — and "totals" [n, 2] int32,
@@ -1822,6 +1867,96 @@ def map_icp_verdict_host(params, stats, pose_before, pose_after):
     return v.value
 
 
+ICP_PHOTO_COUNTS = 2  # VORS_ICP_PHOTO_COUNTS: photo_used, photo_huber_linear
+
+
+class vors_map_icp_joint_params(C.Structure):
+    """Parameters of the correction through the joint pass with the condition test (include/vors_hip.h vors_map_icp_joint_params, 68 bytes)."""
+    _fields_ = [("icp", vors_map_icp_params), ("photo_scale_m", C.c_float), ("photo_huber_grey", C.c_float), ("max_dilution_t", C.c_float),
+                ("max_dilution_r", C.c_float)]
+
+
+class vors_map_icp_joint_record(C.Structure):
+    """What the joint stage keeps beside a vors_map_icp_record (include/vors_hip.h vors_map_icp_joint_record, 20 bytes)."""
+    _fields_ = [("dilution_t", C.c_float), ("dilution_r", C.c_float), ("condition_flags", C.c_int32), ("photo_counts", C.c_uint32 * ICP_PHOTO_COUNTS)]
+
+
+MAP_ICP_JOINT_RECORD_DTYPE = np.dtype([("dilution_t", "<f4"), ("dilution_r", "<f4"), ("condition_flags", "<i4"),
+                                       ("photo_counts", "<u4", (ICP_PHOTO_COUNTS,))])
+assert MAP_ICP_JOINT_RECORD_DTYPE.itemsize == C.sizeof(vors_map_icp_joint_record) == 20 and C.sizeof(vors_map_icp_joint_params) == 68
+MAP_ICP_CONDITION = 7
+# The defaults of the joint stage's own parameters: no photometric row (the robust pass) and both bounds off — vors_trackers_enable_map_icp's
+# behaviour, with the dilutions recorded.
+MAP_ICP_JOINT_DEFAULTS = dict(photo_scale_m=0.0, photo_huber_grey=0.0, max_dilution_t=0.0, max_dilution_r=0.0)
+
+
+def map_icp_joint_params(dist_m=_REQUIRED, **params):
+    """The vors_map_icp_joint_params record of keyword arguments: map_icp_params()' keywords and MAP_ICP_JOINT_DEFAULTS'. Only names and
+    types are judged here; the values are judged by the library."""
+    own = {k: params.pop(k) for k in list(params) if k in MAP_ICP_JOINT_DEFAULTS}
+    p = vors_map_icp_joint_params()
+    p.icp = map_icp_params(dist_m, **params)
+    for name, default in MAP_ICP_JOINT_DEFAULTS.items():
+        v = own.get(name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise VorsError(f"map_icp_joint: {name} must be a number, got {v!r}")
+        setattr(p, name, v)
+    return p
+
+
+def decode_map_icp_joint_records(records):
+    """The tensor of Trackers.map_icp_joint() ([n, 20] uint8) -> a structured numpy array [n] of MAP_ICP_JOINT_RECORD_DTYPE."""
+    a = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
+    return np.ascontiguousarray(a).view(MAP_ICP_JOINT_RECORD_DTYPE).reshape(-1)
+
+
+def icp_condition_from_sums(sums29):
+    """The conditioning of one ICP system on the host (vors_icp_condition_from_sums; needs no GPU): sums29 [29] float32 of one evaluation
+    (icp_points*()'s "sums29") -> (dilution_t, dilution_r, flags): numpy float32 scalars, NaN when flags != 0 (bit 0: at most 6 matched
+    points, bit 1: H has no Cholesky factor)."""
+    s = np.ascontiguousarray(sums29, np.float32)
+    if s.shape != (29,):
+        raise VorsError("icp_condition_from_sums: sums29 [29]")
+    out = np.zeros(2, np.float32)
+    fl = C.c_int32(0)
+    _check(lib().vors_icp_condition_from_sums(_ptr(s), out[0:].ctypes.data_as(C.c_void_p), out[1:].ctypes.data_as(C.c_void_p), C.byref(fl)))
+    return out[0], out[1], fl.value
+
+
+def icp_condition(sums29, dilutions=None, flags=None):
+    """The conditioning of n ICP systems on the device (vors_icp_condition; current stream, not synchronised): sums29 [n, 29] float32
+    tensor -> (dilutions [n, 2] float32: dilution_t, dilution_r; flags [n] int32), the bits of icp_condition_from_sums(). dilutions /
+    flags: tensors of that shape to write into (None = new ones)."""
+    import torch
+    if sums29.dtype != torch.float32 or sums29.dim() != 2 or sums29.shape[1] != 29 or not sums29.is_contiguous():
+        raise VorsError("icp_condition: sums29 float32 [n, 29], contiguous")
+    n = sums29.shape[0]
+    if dilutions is None:
+        dilutions = torch.empty((n, 2), dtype=torch.float32, device=sums29.device)
+    if flags is None:
+        flags = torch.empty(n, dtype=torch.int32, device=sums29.device)
+    if (dilutions.dtype != torch.float32 or tuple(dilutions.shape) != (n, 2) or not dilutions.is_contiguous() or flags.dtype != torch.int32
+            or tuple(flags.shape) != (n,) or not flags.is_contiguous()):
+        raise VorsError("icp_condition: dilutions float32 [n, 2] and flags int32 [n], contiguous")
+    _check(lib().vors_icp_condition(n, Batch._dp(sums29), Batch._dp(dilutions), Batch._dp(flags), Batch._stream()))
+    return dilutions, flags
+
+
+def map_icp_verdict_joint_host(params, stats, pose_before, pose_after, dilution_t, dilution_r):
+    """The joint stage's verdict on the host (vors_map_icp_verdict_joint_host; needs no GPU): params = map_icp_joint_params(...) or a dict
+    of its keywords (the four verdict fields and the two bounds are read), stats = a structured scalar of ICP_STATS_DTYPE -> a MAP_ICP_*
+    verdict, MAP_ICP_CONDITION among them."""
+    p = map_icp_joint_params(**params) if isinstance(params, dict) else params
+    s = np.zeros(1, ICP_STATS_DTYPE)
+    s[0] = stats
+    a, b = np.ascontiguousarray(pose_before, np.float32), np.ascontiguousarray(pose_after, np.float32)
+    if a.shape != (7,) or b.shape != (7,):
+        raise VorsError("map_icp_verdict_joint_host: pose_before and pose_after [7]")
+    v = C.c_uint32(99)
+    _check(lib().vors_map_icp_verdict_joint_host(C.byref(p), _ptr(s), _ptr(a), _ptr(b), float(dilution_t), float(dilution_r), C.byref(v)))
+    return v.value
+
+
 def _icp_robust_buffers(who, frame_normals, shape, gate_counts, dev):
     """The frame normals (None = no normal gate; float32 [n, rows, cols, 3], contiguous) checked, and the tensor behind gate_counts."""
     import torch
@@ -1892,9 +2027,6 @@ def icp_points_robust_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m
                                              float(huber_m), _ptr(out["pose"]), _ptr(stats), _ptr(out["sums29"]), _ptr(residuals),
                                              _ptr(out["gate_counts"])))
     return out
-
-
-ICP_PHOTO_COUNTS = 2  # VORS_ICP_PHOTO_COUNTS: photo_used, photo_huber_linear
 
 
 def _icp_joint_buffers(who, list_gray, frame_gray, shape, cap, photo_residuals, photo_counts, dev):
