@@ -71,3 +71,12 @@ def test_refused_without_map_normals():
     with pytest.raises(V.VorsError) as e:
         tr.icp_map(frames_of(MODE)[0][1], **ICP)
     assert str(e.value) == "vors_hip error -1: icp_map: the normals of the map are not enabled (vors_trackers_enable_map_normals)"
+
+
+def test_refused_without_map():
+    """A handle without a map, no frame tracked: the library's own sentence, as from icp_map_robust() and icp_map_joint()."""
+    rows, cols, _ = SHAPES[MODE]
+    tr = V.Trackers(config(MODE, ARITH), N_SEQ, rows, cols)
+    with pytest.raises(V.VorsError) as e:
+        tr.icp_map(frames_of(MODE)[0][1], **ICP)
+    assert str(e.value) == "vors_hip error -1: icp_map: the keyframe map is not enabled (vors_trackers_enable_map)"

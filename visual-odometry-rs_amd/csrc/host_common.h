@@ -192,6 +192,22 @@ vors::MapIcpGates map_icp_gates(const vors_map_icp_params& params);
 // dilution bounds; photo_huber_m = photo_scale_m * photo_huber_grey as vors_icp_points_joint takes it (once, on the host).
 vors_status map_icp_joint_params_refusals(const char* who, const vors_map_icp_joint_params* params);
 float map_icp_photo_huber_m(const vors_map_icp_joint_params& params);
+// One ICP pass as a C entry states it, before anything is judged (operators.cpp): `call` holds the lists, planes, scalars and outputs as
+// given, and what IcpCall keeps in other units or derives stands beside it — the pass fills call.k, range_stride, pose_stride,
+// min_points and the workspace's three pointers from these after the refusals. robust NULL: the plain pass; joint (needs robust): its
+// photo_huber_m still holds photo_huber_grey, scaled once by the pass.
+struct IcpArgs {
+    vors::IcpCall call;
+    const float* cam5;
+    int min_points;
+    size_t range_stride_bytes, pose_stride_bytes;
+    void* workspace;
+    const vors::IcpRobust* robust;
+    const vors::IcpJoint* joint;
+};
+// The device pass of vors_icp_points, _robust and _joint, and of their forwards on the sequence handle: every refusal in the name of
+// `who`, then launch_icp_points on s. Internal: hidden, so that the library's dynamic symbols stay the ones it had.
+__attribute__((visibility("hidden"))) vors_status icp_points_device(const char* who, const IcpArgs& args, hipStream_t s);
 }
 // The stream work is enqueued on must belong to the handle's device (a stream of another device would silently run nothing useful).
 vors_status check_stream(const vors_batch* b, hipStream_t s);

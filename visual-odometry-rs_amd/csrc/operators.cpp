@@ -449,38 +449,37 @@ vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], 
 // the device entry (icp_kernels.hip) and the host entry, which runs the kernels' own texts (lie.h icp_landing, icp_row, icp_products,
 // icp_round) and the order of sums lie.h states.
 // ---------------------------------------------------------------------------------------------------------------
-static vors_status icp_refusals(const char* who, const void* xyz, const void* normals, const void* poses_in, const void* depth, const float* cam5,
-                                int capacity, int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters,
-                                int min_points, const void* poses_out, const void* stats, const void* sums29, const void* residuals) {
+static vors_status icp_refusals(const char* who, const IcpArgs& a) {
     const std::string w(who);
-    if (!xyz || !normals) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, normals) is NULL");
-    if (!poses_in) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the start poses are NULL (an alignment needs a pose to refine)");
-    if (!depth) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth is NULL");
-    if (!cam5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cam5 is NULL");
-    if (!poses_out) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the output poses are NULL");
-    if (rows < 1 || cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must be >= 1");
-    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
-    if (rows > 65535 || cols > 65535 || (long long)rows * cols > (1ll << 28))
+    const IcpCall& c = a.call;
+    if (!c.xyz || !c.normals) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, normals) is NULL");
+    if (!c.poses_in) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the start poses are NULL (an alignment needs a pose to refine)");
+    if (!c.depth) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth is NULL");
+    if (!a.cam5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cam5 is NULL");
+    if (!c.poses_out) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the output poses are NULL");
+    if (c.rows < 1 || c.cols < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must be >= 1");
+    if (c.capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
+    if (c.rows > 65535 || c.cols > 65535 || (long long)c.rows * c.cols > (1ll << 28))
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows / cols must not exceed 65535 and rows * cols must not exceed 2^28 pixels");
-    if (!(depth_scale > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth_scale must be > 0");
-    if (!(dist_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": dist_m must be >= 0 (and not NaN)");
-    if (!(damping >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": damping must be >= 0 (and not NaN)");
-    if (!(step_eps >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": step_eps must be >= 0 (and not NaN)");
-    if (iters < 0 || iters > 64) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": iters must be in 0..64");
-    if (min_points < 6) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_points must be >= 6 (a pose has six degrees of freedom)");
-    if ((uintptr_t)depth % 2 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth must be 2-byte aligned");
-    if ((uintptr_t)xyz % 4 != 0 || (uintptr_t)normals % 4 != 0 || (uintptr_t)poses_in % 4 != 0 || (uintptr_t)poses_out % 4 != 0 ||
-        (uintptr_t)stats % 4 != 0 || (uintptr_t)sums29 % 4 != 0 || (uintptr_t)residuals % 4 != 0)
+    if (!(c.depth_scale > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth_scale must be > 0");
+    if (!(c.dist_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": dist_m must be >= 0 (and not NaN)");
+    if (!(c.damping >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": damping must be >= 0 (and not NaN)");
+    if (!(c.step_eps >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": step_eps must be >= 0 (and not NaN)");
+    if (c.iters < 0 || c.iters > 64) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": iters must be in 0..64");
+    if (a.min_points < 6) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_points must be >= 6 (a pose has six degrees of freedom)");
+    if ((uintptr_t)c.depth % 2 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth must be 2-byte aligned");
+    if ((uintptr_t)c.xyz % 4 != 0 || (uintptr_t)c.normals % 4 != 0 || (uintptr_t)c.poses_in % 4 != 0 || (uintptr_t)c.poses_out % 4 != 0 ||
+        (uintptr_t)c.stats % 4 != 0 || (uintptr_t)c.sums29 % 4 != 0 || (uintptr_t)c.residuals % 4 != 0)
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": xyz, normals, the poses, stats, sums29 and residuals must be 4-byte aligned");
     return VORS_OK;
 }
 
 // ... and what the robust entries refuse beyond that
-static vors_status icp_robust_refusals(const char* who, const void* frame_normals, float min_cos, float huber_m, const void* gate_counts) {
+static vors_status icp_robust_refusals(const char* who, const IcpRobust& r) {
     const std::string w(who);
-    if (!(min_cos >= -1.0f && min_cos <= 1.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_cos must lie in [-1, 1] (and not be NaN)");
-    if (!(huber_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": huber_m must be >= 0 (and not NaN; 0 = no Huber weight)");
-    if ((uintptr_t)frame_normals % 4 != 0 || (uintptr_t)gate_counts % 4 != 0)
+    if (!(r.min_cos >= -1.0f && r.min_cos <= 1.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_cos must lie in [-1, 1] (and not be NaN)");
+    if (!(r.huber_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": huber_m must be >= 0 (and not NaN; 0 = no Huber weight)");
+    if ((uintptr_t)r.frame_normals % 4 != 0 || (uintptr_t)r.gate_counts % 4 != 0)
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the frame normals and the gate counts must be 4-byte aligned");
     return VORS_OK;
 }
@@ -488,78 +487,74 @@ static vors_status icp_robust_refusals(const char* who, const void* frame_normal
 // photo_huber_m = photo_scale_m * photo_huber_grey, the ONE product that kernel and host twin both read
 static float icp_photo_huber_m(float photo_scale_m, float photo_huber_grey) { return photo_scale_m * photo_huber_grey; }
 
-// ... and what the joint entries refuse beyond those
-static vors_status icp_joint_refusals(const char* who, const void* list_gray, const void* frame_gray, float photo_scale_m, float photo_huber_grey,
-                                      const void* photo_residuals, const void* photo_counts) {
+// ... and what the joint entries refuse beyond those (j.photo_huber_m still holds photo_huber_grey, as the entries take it)
+static vors_status icp_joint_refusals(const char* who, const IcpJoint& j) {
     const std::string w(who);
-    if (!(photo_scale_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_scale_m must be >= 0 (and not NaN; 0 = no photometric term)");
-    if (!(photo_huber_grey >= 0.0f))
+    if (!(j.photo_scale_m >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_scale_m must be >= 0 (and not NaN; 0 = no photometric term)");
+    if (!(j.photo_huber_m >= 0.0f))
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_huber_grey must be >= 0 (and not NaN; 0 = no Huber weight)");
-    if (photo_scale_m > 0.0f && (!list_gray || !frame_gray))
+    if (j.photo_scale_m > 0.0f && (!j.list_gray || !j.frame_gray))
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": photo_scale_m > 0 needs the grey levels of the list and of the frame");
-    if ((uintptr_t)photo_residuals % 4 != 0 || (uintptr_t)photo_counts % 4 != 0)
+    if ((uintptr_t)j.photo_residuals % 4 != 0 || (uintptr_t)j.photo_counts % 4 != 0)
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the photo residuals and the photo counts must be 4-byte aligned");
     return VORS_OK;
 }
 
+// The three in the order every entry states them: the common part, then the parts of the form
+static vors_status icp_form_refusals(const char* who, const IcpArgs& a) {
+    vors_status st = icp_refusals(who, a);
+    if (st == VORS_OK && a.robust) st = icp_robust_refusals(who, *a.robust);
+    if (st == VORS_OK && a.joint) st = icp_joint_refusals(who, *a.joint);
+    return st;
+}
+
 uint64_t vors_icp_workspace_bytes(int n, int capacity) { return n < 1 || capacity < 1 ? 0 : (uint64_t)icp_workspace_bytes(n, capacity); }
 
-// The device pass: robust = NULL is vors_icp_points (who = its name in a refusal); joint (with robust) is vors_icp_points_joint, its
-// photo_huber_m still holding photo_huber_grey, which is scaled here, once, after the refusals
-static vors_status icp_points_device(const char* who, int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
-                                     const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
-                                     const uint16_t* d_depth, const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping,
-                                     float step_eps, int iters, int min_points, const IcpRobust* robust, void* d_workspace, float* d_poses7_out,
-                                     vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, void* hip_stream,
-                                     const IcpJoint* joint = nullptr) {
+// The device pass of every form (host_common.h IcpArgs): the refusals in the name of `who`, then what the record leaves to derive
+vors_status icp_points_device(const char* who, const IcpArgs& a, hipStream_t s) {
     const std::string w(who);
-    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be >= 1");
-    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (d_list_counts) is NULL");
-    vors_status st = icp_refusals(who, d_xyz, d_normals, d_poses7_in, d_depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping, step_eps,
-                                  iters, min_points, d_poses7_out, d_stats, d_sums29, d_residuals);
+    IcpCall call = a.call;
+    if (call.n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be >= 1");
+    if (!call.list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (d_list_counts) is NULL");
+    vors_status st = icp_form_refusals(who, a);
     if (st != VORS_OK) return st;
-    if (robust && (st = icp_robust_refusals(who, robust->frame_normals, robust->min_cos, robust->huber_m, robust->gate_counts)) != VORS_OK) return st;
-    if (joint && (st = icp_joint_refusals(who, joint->list_gray, joint->frame_gray, joint->photo_scale_m, joint->photo_huber_m,
-                                          joint->photo_residuals, joint->photo_counts)) != VORS_OK)
-        return st;
-    if (!d_workspace) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_workspace is NULL (the pass allocates nothing: vors_icp_workspace_bytes)");
-    if ((st = list_stride_refusals(who, pose_stride_bytes, range_stride_bytes)) != VORS_OK) return st;
-    if ((uintptr_t)d_ranges % 4 != 0 || (uintptr_t)d_list_counts % 4 != 0 || (uintptr_t)d_workspace % 4 != 0)
+    if (!a.workspace) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_workspace is NULL (the pass allocates nothing: vors_icp_workspace_bytes)");
+    if ((st = list_stride_refusals(who, a.pose_stride_bytes, a.range_stride_bytes)) != VORS_OK) return st;
+    if ((uintptr_t)call.ranges % 4 != 0 || (uintptr_t)call.list_counts % 4 != 0 || (uintptr_t)a.workspace % 4 != 0)
         return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_ranges, d_list_counts and d_workspace must be 4-byte aligned");
     if ((st = require_device()) != VORS_OK) return st;
-    IcpCall call{};
-    call.n = n;
-    call.xyz = d_xyz;
-    call.normals = d_normals;
-    call.list_counts = d_list_counts;
-    call.capacity = capacity;
-    call.ranges = static_cast<const uint8_t*>(d_ranges);
-    call.range_stride = range_stride_bytes ? (int)range_stride_bytes : 8;
-    call.poses_in = static_cast<const float*>(d_poses7_in);
-    call.pose_stride = stride_words(pose_stride_bytes, 7);
-    call.depth = d_depth;
-    call.k = intr_from_cam5(cam5);
-    call.rows = rows;
-    call.cols = cols;
-    call.depth_scale = depth_scale;
-    call.dist_m = dist_m;
-    call.damping = damping;
-    call.step_eps = step_eps;
-    call.iters = iters;
-    call.min_points = (uint32_t)min_points;
-    icp_workspace_carve(&call, d_workspace, n, capacity);
-    call.poses_out = d_poses7_out;
-    call.stats = d_stats;
-    call.sums29 = d_sums29;
-    call.residuals = d_residuals;
+    call.range_stride = a.range_stride_bytes ? (int)a.range_stride_bytes : 8;
+    call.pose_stride = stride_words(a.pose_stride_bytes, 7);
+    call.k = intr_from_cam5(a.cam5);
+    call.min_points = (uint32_t)a.min_points;
+    icp_workspace_carve(&call, a.workspace, call.n, call.capacity);
     IcpJoint jt{};
-    if (joint) {
-        jt = *joint;
-        jt.photo_huber_m = icp_photo_huber_m(joint->photo_scale_m, joint->photo_huber_m);
+    if (a.joint) {
+        jt = *a.joint;
+        jt.photo_huber_m = icp_photo_huber_m(jt.photo_scale_m, jt.photo_huber_m);
     }
-    launch_icp_points(call, robust, static_cast<hipStream_t>(hip_stream), joint ? &jt : nullptr);
+    launch_icp_points(call, a.robust, s, a.joint ? &jt : nullptr);
     HIP_TRY(hipGetLastError());
     return VORS_OK;
+}
+
+// The arguments every entry shares, device and host, as the record holds them. A host entry states its ONE list as n = 1 with the
+// count behind d_list_counts (the caller's to keep alive through the pass), range2 behind d_ranges, no strides and no workspace.
+static IcpArgs icp_args(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity, const void* d_ranges,
+                        size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes, const uint16_t* d_depth, const float cam5[5],
+                        int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters, int min_points,
+                        void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
+                        const IcpRobust* robust = nullptr, const IcpJoint* joint = nullptr) {
+    IcpArgs a{};
+    IcpCall& c = a.call;
+    c.n = n; c.xyz = d_xyz; c.normals = d_normals; c.list_counts = d_list_counts; c.capacity = capacity;
+    c.ranges = static_cast<const uint8_t*>(d_ranges); a.range_stride_bytes = range_stride_bytes;
+    c.poses_in = static_cast<const float*>(d_poses7_in); a.pose_stride_bytes = pose_stride_bytes;
+    c.depth = d_depth; a.cam5 = cam5; c.rows = rows; c.cols = cols; c.depth_scale = depth_scale;
+    c.dist_m = dist_m; c.damping = damping; c.step_eps = step_eps; c.iters = iters; a.min_points = min_points;
+    a.workspace = d_workspace; c.poses_out = d_poses7_out; c.stats = d_stats; c.sums29 = d_sums29; c.residuals = d_residuals;
+    a.robust = robust; a.joint = joint;
+    return a;
 }
 
 vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity, const void* d_ranges,
@@ -567,9 +562,11 @@ vors_status vors_icp_points(int n, const float* d_xyz, const float* d_normals, c
                             const float cam5[5], int rows, int cols, float depth_scale, float dist_m, float damping, float step_eps, int iters,
                             int min_points, void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
                             void* hip_stream) {
-    return icp_points_device("icp_points", n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in, pose_stride_bytes,
-                             d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, nullptr, d_workspace, d_poses7_out,
-                             d_stats, d_sums29, d_residuals, hip_stream);
+    return icp_points_device("icp_points",
+                             icp_args(n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in, pose_stride_bytes,
+                                      d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, d_workspace,
+                                      d_poses7_out, d_stats, d_sums29, d_residuals),
+                             static_cast<hipStream_t>(hip_stream));
 }
 
 vors_status vors_icp_points_robust(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
@@ -579,14 +576,32 @@ vors_status vors_icp_points_robust(int n, const float* d_xyz, const float* d_nor
                                    void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
                                    uint32_t* d_gate_counts, void* hip_stream) {
     const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
-    return icp_points_device("icp_points_robust", n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in,
-                             pose_stride_bytes, d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, &robust,
-                             d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, hip_stream);
+    return icp_points_device("icp_points_robust",
+                             icp_args(n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in, pose_stride_bytes,
+                                      d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, d_workspace,
+                                      d_poses7_out, d_stats, d_sums29, d_residuals, &robust),
+                             static_cast<hipStream_t>(hip_stream));
 }
 
-// The loop of the host entries, after their refusals. point(pose, landing, nw, pixel, rank, a, products) is the per-point rule: it fills
-// the row a[7] and the point's 28 products, and returns the last gate passed and whether the point lies on Huber's linear branch (the
-// joint pass: and what its photometric row gave).
+vors_status vors_icp_points_joint(int n, const float* d_xyz, const float* d_normals, const uint8_t* d_list_gray, const uint32_t* d_list_counts,
+                                  int capacity, const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
+                                  const uint16_t* d_depth, const uint8_t* d_frame_gray, const float cam5[5], int rows, int cols, float depth_scale,
+                                  float dist_m, float damping, float step_eps, int iters, int min_points, const float* d_frame_normals,
+                                  float min_cos, float huber_m, float photo_scale_m, float photo_huber_grey, void* d_workspace,
+                                  float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, uint32_t* d_gate_counts,
+                                  float* d_photo_residuals, uint32_t* d_photo_counts, void* hip_stream) {
+    const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
+    const IcpJoint joint{d_list_gray, d_frame_gray, photo_scale_m, photo_huber_grey, d_photo_residuals, d_photo_counts};
+    return icp_points_device("icp_points_joint",
+                             icp_args(n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in, pose_stride_bytes,
+                                      d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, d_workspace,
+                                      d_poses7_out, d_stats, d_sums29, d_residuals, &robust, &joint),
+                             static_cast<hipStream_t>(hip_stream));
+}
+
+// The loop of the host entries, after their refusals, over the ONE list of c (c.list_counts[0], c.ranges = its range2 or NULL, c.k set).
+// point(pose, landing, nw, pixel, rank, a, products) is the per-point rule: it fills the row a[7] and the point's 28 products, and
+// returns the last gate passed and whether the point lies on Huber's linear branch (the joint pass: and what its photometric row gave).
 struct IcpHostPoint {
     IcpGate gate;
     bool linear;
@@ -594,12 +609,11 @@ struct IcpHostPoint {
     float photo_d = 0.0f;                      // I - grey in grey levels
 };
 extern "C++" template <class Point>
-static void icp_host_loop(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2], const float pose7_in[7],
-                          const Intr& k, int rows, int cols, float damping, float step_eps, int iters, int min_points, Point point,
-                          float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals, uint32_t* gate_counts,
-                          float* photo_residuals = nullptr, uint32_t* photo_counts = nullptr) {
+static void icp_host_loop(const IcpCall& c, Point point, uint32_t* gate_counts, float* photo_residuals, uint32_t* photo_counts) {
+    const Intr& k = c.k;
+    const int rows = c.rows, cols = c.cols;
     uint32_t first, last;
-    icp_range(count, capacity, range2, &first, &last);
+    icp_range(c.list_counts[0], c.capacity, reinterpret_cast<const uint32_t*>(c.ranges), &first, &last);
     const uint32_t nchunks = (last - first + (VORS_ICP_CHUNK - 1)) / VORS_ICP_CHUNK;
     std::vector<float> v((size_t)VORS_ICP_CHUNK * VORS_ICP_SUMS);
     float sums[VORS_ICP_SUMS];
@@ -618,8 +632,8 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
                 float* products = v.data() + (size_t)s * VORS_ICP_SUMS;
                 const uint32_t rank = base + s;
                 if (rank < last) {
-                    const float* p = xyz + 3 * (size_t)rank;
-                    const float* nn = normals + 3 * (size_t)rank;
+                    const float* p = c.xyz + 3 * (size_t)rank;
+                    const float* nn = c.normals + 3 * (size_t)rank;
                     const IcpLanding l = icp_landing(k, pose, V3{p[0], p[1], p[2]}, cols, rows);
                     const size_t pixel = l.lands ? (size_t)l.y * (size_t)cols + (size_t)l.x : 0;
                     const IcpHostPoint o = point(pose, l, V3{nn[0], nn[1], nn[2]}, pixel, rank, a, products);
@@ -643,12 +657,12 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
             for (int q = 0; q < VORS_ICP_SUMS; ++q) sums[q] = chunk == 0 ? v[q] : sums[q] + v[q];
         }
     };
-    Iso pose = iso_load(pose7_in);
+    Iso pose = iso_load(c.poses_in);
     vors_icp_stats o{VORS_ICP_ITERATIONS, 0u, last - first, 0u, 0.0f, 0.0f};
-    for (int it = 0; it < iters; ++it) {
+    for (int it = 0; it < c.iters; ++it) {
         evaluate(pose, nullptr, nullptr);
         float step_norm = 0.0f;
-        const IcpStatus verdict = icp_round(sums, matched, (uint32_t)min_points, damping, step_eps, &pose, &step_norm);
+        const IcpStatus verdict = icp_round(sums, matched, c.min_points, c.damping, c.step_eps, &pose, &step_norm);
         if (verdict == ICP_ITERATIONS || verdict == ICP_CONVERGED) {
             o.iterations += 1u;
             o.last_step_norm = step_norm;
@@ -658,34 +672,85 @@ static void icp_host_loop(const float* xyz, const float* normals, uint32_t count
             break;
         }
     }
-    evaluate(pose, residuals, photo_residuals);
+    evaluate(pose, c.residuals, photo_residuals);
     o.matched = matched;
     o.rms = sqrtf(sums[0] / (float)matched);
-    iso_store(pose, pose7_out);
-    if (stats) *stats = o;
-    if (sums29) icp_sums29(sums, matched, sums29);
+    iso_store(pose, c.poses_out);
+    if (c.stats) *c.stats = o;
+    if (c.sums29) icp_sums29(sums, matched, c.sums29);
     if (gate_counts)
         for (int q = 0; q < VORS_ICP_GATE_COUNTS; ++q) gate_counts[q] = gates[q];
     if (photo_counts)
         for (int q = 0; q < ICP_PHOTO_COUNTS; ++q) photo_counts[q] = photos[q];
 }
 
+// The host pass of every form, mirroring icp_points_device: the refusals in the name of `who`, then the loop with the form's per-point
+// rule. The rules are three texts: the plain one (icp_row / icp_products), the robust one (icp_row_robust / icp_products_robust), and the
+// joint one, which is the robust one followed by the photometric row.
+static vors_status icp_points_host(const char* who, const IcpArgs& a) {
+    vors_status st = icp_form_refusals(who, a);
+    if (st != VORS_OK) return st;
+    IcpCall c = a.call;
+    const Intr k = c.k = intr_from_cam5(a.cam5);
+    c.min_points = (uint32_t)a.min_points;
+    const uint16_t* depth = c.depth;
+    const int rows = c.rows, cols = c.cols;
+    if (!a.robust) {
+        icp_host_loop(c,
+                      [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t, float* row, float* products) {
+                          const bool m = icp_row(k, c.depth_scale, c.dist_m, pose, l, nw, depth[pixel], row);
+                          icp_products(row, products);
+                          return IcpHostPoint{m ? ICP_GATE_MATCHED : ICP_GATE_NONE, false};
+                      },
+                      nullptr, nullptr, nullptr);
+        return VORS_OK;
+    }
+    const IcpRobust r = *a.robust;
+    IcpJoint j{};
+    if (a.joint) j = *a.joint;
+    const float photo_huber_m = icp_photo_huber_m(j.photo_scale_m, j.photo_huber_m);
+    const bool photo_on = j.photo_scale_m > 0.0f && rows >= 2 && cols >= 2;  // (no footprint fits a plane of one row or column)
+    with_bool(r.frame_normals != nullptr, [&](auto nrm) {
+        with_bool(r.huber_m > 0.0f, [&](auto hub) {
+            auto robust_point = [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t, float* row, float* products) {
+                V3 nf{0.0f, 0.0f, 0.0f};
+                if constexpr (decltype(nrm)::value) nf = V3{r.frame_normals[3 * pixel], r.frame_normals[3 * pixel + 1], r.frame_normals[3 * pixel + 2]};
+                const IcpGate g = icp_row_robust<decltype(nrm)::value>(k, c.depth_scale, c.dist_m, r.min_cos, pose, l, nw, depth[pixel], nf, row);
+                return IcpHostPoint{g, icp_products_robust<decltype(hub)::value>(row, r.huber_m, products)};
+            };
+            if (!a.joint) {
+                icp_host_loop(c, robust_point, r.gate_counts, nullptr, nullptr);
+                return;
+            }
+            with_bool(photo_huber_m > 0.0f, [&](auto phub) {
+                icp_host_loop(c,
+                              [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t rank, float* row, float* products) {
+                                  IcpHostPoint o = robust_point(pose, l, nw, pixel, rank, row, products);
+                                  const IcpFootprint f = icp_photo_footprint(k, l.c, cols, rows);
+                                  o.photo = o.gate == ICP_GATE_MATCHED && photo_on && f.inside;
+                                  if (o.photo) {
+                                      const uint8_t* t = j.frame_gray + f.off;
+                                      float ap[7], pp[VORS_ICP_SUMS];
+                                      o.photo_d = icp_row_photo(k, j.photo_scale_m, l.c, f, true, t[0], t[1], t[cols], t[cols + 1], j.list_gray[rank], ap);
+                                      o.photo_linear = icp_products_robust<decltype(phub)::value>(ap, photo_huber_m, pp);
+                                      for (int q = 0; q < VORS_ICP_SUMS; ++q) products[q] = products[q] + pp[q];
+                                  }
+                                  return o;
+                              },
+                              r.gate_counts, j.photo_residuals, j.photo_counts);
+            });
+        });
+    });
+    return VORS_OK;
+}
+
 vors_status vors_icp_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
                                  const float pose7_in[7], const uint16_t* depth, const float cam5[5], int rows, int cols, float depth_scale,
                                  float dist_m, float damping, float step_eps, int iters, int min_points, float pose7_out[7], vors_icp_stats* stats,
                                  float sums29[29], float* residuals) {
-    vors_status st = icp_refusals("icp_points_host", xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
-                                  step_eps, iters, min_points, pose7_out, stats, sums29, residuals);
-    if (st != VORS_OK) return st;
-    const Intr k = intr_from_cam5(cam5);
-    icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
-                  [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t, float* a, float* products) {
-                      const bool m = icp_row(k, depth_scale, dist_m, pose, l, nw, depth[pixel], a);
-                      icp_products(a, products);
-                      return IcpHostPoint{m ? ICP_GATE_MATCHED : ICP_GATE_NONE, false};
-                  },
-                  pose7_out, stats, sums29, residuals, nullptr);
-    return VORS_OK;
+    return icp_points_host("icp_points_host",
+                           icp_args(1, xyz, normals, &count, capacity, range2, 0, pose7_in, 0, depth, cam5, rows, cols, depth_scale, dist_m, damping,
+                                    step_eps, iters, min_points, nullptr, pose7_out, stats, sums29, residuals));
 }
 
 vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, uint32_t count, int capacity, const uint32_t range2[2],
@@ -693,39 +758,10 @@ vors_status vors_icp_points_robust_host(const float* xyz, const float* normals, 
                                         float depth_scale, float dist_m, float damping, float step_eps, int iters, int min_points,
                                         const float* frame_normals, float min_cos, float huber_m, float pose7_out[7], vors_icp_stats* stats,
                                         float sums29[29], float* residuals, uint32_t gate_counts[VORS_ICP_GATE_COUNTS]) {
-    vors_status st = icp_refusals("icp_points_robust_host", xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping,
-                                  step_eps, iters, min_points, pose7_out, stats, sums29, residuals);
-    if (st != VORS_OK) return st;
-    if ((st = icp_robust_refusals("icp_points_robust_host", frame_normals, min_cos, huber_m, gate_counts)) != VORS_OK) return st;
-    const Intr k = intr_from_cam5(cam5);
-    with_bool(frame_normals != nullptr, [&](auto nrm) {
-        with_bool(huber_m > 0.0f, [&](auto hub) {
-            icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
-                          [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t, float* a, float* products) {
-                              V3 nf{0.0f, 0.0f, 0.0f};
-                              if constexpr (decltype(nrm)::value) nf = V3{frame_normals[3 * pixel], frame_normals[3 * pixel + 1], frame_normals[3 * pixel + 2]};
-                              const IcpGate g =
-                                  icp_row_robust<decltype(nrm)::value>(k, depth_scale, dist_m, min_cos, pose, l, nw, depth[pixel], nf, a);
-                              return IcpHostPoint{g, icp_products_robust<decltype(hub)::value>(a, huber_m, products)};
-                          },
-                          pose7_out, stats, sums29, residuals, gate_counts);
-        });
-    });
-    return VORS_OK;
-}
-
-vors_status vors_icp_points_joint(int n, const float* d_xyz, const float* d_normals, const uint8_t* d_list_gray, const uint32_t* d_list_counts,
-                                  int capacity, const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
-                                  const uint16_t* d_depth, const uint8_t* d_frame_gray, const float cam5[5], int rows, int cols, float depth_scale,
-                                  float dist_m, float damping, float step_eps, int iters, int min_points, const float* d_frame_normals,
-                                  float min_cos, float huber_m, float photo_scale_m, float photo_huber_grey, void* d_workspace,
-                                  float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, uint32_t* d_gate_counts,
-                                  float* d_photo_residuals, uint32_t* d_photo_counts, void* hip_stream) {
-    const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
-    const IcpJoint joint{d_list_gray, d_frame_gray, photo_scale_m, photo_huber_grey, d_photo_residuals, d_photo_counts};
-    return icp_points_device("icp_points_joint", n, d_xyz, d_normals, d_list_counts, capacity, d_ranges, range_stride_bytes, d_poses7_in,
-                             pose_stride_bytes, d_depth, cam5, rows, cols, depth_scale, dist_m, damping, step_eps, iters, min_points, &robust,
-                             d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, hip_stream, &joint);
+    const IcpRobust robust{frame_normals, min_cos, huber_m, gate_counts};
+    return icp_points_host("icp_points_robust_host",
+                           icp_args(1, xyz, normals, &count, capacity, range2, 0, pose7_in, 0, depth, cam5, rows, cols, depth_scale, dist_m, damping,
+                                    step_eps, iters, min_points, nullptr, pose7_out, stats, sums29, residuals, &robust));
 }
 
 vors_status vors_icp_points_joint_host(const float* xyz, const float* normals, const uint8_t* list_gray, uint32_t count, int capacity,
@@ -735,42 +771,11 @@ vors_status vors_icp_points_joint_host(const float* xyz, const float* normals, c
                                        float photo_huber_grey, float pose7_out[7], vors_icp_stats* stats, float sums29[29], float* residuals,
                                        uint32_t gate_counts[VORS_ICP_GATE_COUNTS], float* photo_residuals,
                                        uint32_t photo_counts[VORS_ICP_PHOTO_COUNTS]) {
-    const char* who = "icp_points_joint_host";
-    vors_status st = icp_refusals(who, xyz, normals, pose7_in, depth, cam5, capacity, rows, cols, depth_scale, dist_m, damping, step_eps, iters,
-                                  min_points, pose7_out, stats, sums29, residuals);
-    if (st != VORS_OK) return st;
-    if ((st = icp_robust_refusals(who, frame_normals, min_cos, huber_m, gate_counts)) != VORS_OK) return st;
-    if ((st = icp_joint_refusals(who, list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals, photo_counts)) != VORS_OK) return st;
-    const Intr k = intr_from_cam5(cam5);
-    const float photo_huber_m = icp_photo_huber_m(photo_scale_m, photo_huber_grey);
-    const bool photo_on = photo_scale_m > 0.0f && rows >= 2 && cols >= 2;  // (no footprint fits a plane of one row or column)
-    with_bool(frame_normals != nullptr, [&](auto nrm) {
-        with_bool(huber_m > 0.0f, [&](auto hub) {
-            with_bool(photo_huber_m > 0.0f, [&](auto phub) {
-                icp_host_loop(xyz, normals, count, capacity, range2, pose7_in, k, rows, cols, damping, step_eps, iters, min_points,
-                              [&](const Iso& pose, const IcpLanding& l, const V3& nw, size_t pixel, uint32_t rank, float* a, float* products) {
-                                  V3 nf{0.0f, 0.0f, 0.0f};
-                                  if constexpr (decltype(nrm)::value)
-                                      nf = V3{frame_normals[3 * pixel], frame_normals[3 * pixel + 1], frame_normals[3 * pixel + 2]};
-                                  const IcpGate g =
-                                      icp_row_robust<decltype(nrm)::value>(k, depth_scale, dist_m, min_cos, pose, l, nw, depth[pixel], nf, a);
-                                  IcpHostPoint o{g, icp_products_robust<decltype(hub)::value>(a, huber_m, products)};
-                                  const IcpFootprint f = icp_photo_footprint(k, l.c, cols, rows);
-                                  o.photo = g == ICP_GATE_MATCHED && photo_on && f.inside;
-                                  if (o.photo) {
-                                      const uint8_t* t = frame_gray + f.off;
-                                      float ap[7], pp[VORS_ICP_SUMS];
-                                      o.photo_d = icp_row_photo(k, photo_scale_m, l.c, f, true, t[0], t[1], t[cols], t[cols + 1], list_gray[rank], ap);
-                                      o.photo_linear = icp_products_robust<decltype(phub)::value>(ap, photo_huber_m, pp);
-                                      for (int q = 0; q < VORS_ICP_SUMS; ++q) products[q] = products[q] + pp[q];
-                                  }
-                                  return o;
-                              },
-                              pose7_out, stats, sums29, residuals, gate_counts, photo_residuals, photo_counts);
-            });
-        });
-    });
-    return VORS_OK;
+    const IcpRobust robust{frame_normals, min_cos, huber_m, gate_counts};
+    const IcpJoint joint{list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals, photo_counts};
+    return icp_points_host("icp_points_joint_host",
+                           icp_args(1, xyz, normals, &count, capacity, range2, 0, pose7_in, 0, depth, cam5, rows, cols, depth_scale, dist_m, damping,
+                                    step_eps, iters, min_points, nullptr, pose7_out, stats, sums29, residuals, &robust, &joint));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -790,11 +795,11 @@ vors_status map_icp_params_refusals(const char* who, const vors_map_icp_params* 
     const std::string w(who);
     if (!p) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": params is NULL");
     // (what vors_icp_points_robust refuses of the shared parameters, in its own sentences: the lists, planes and shapes are the handle's)
-    alignas(16) static const float some[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    vors_status st = icp_refusals(who, some, some, some, some, some, 1, 1, 1, 1.0f, p->dist_m, p->damping, p->step_eps, p->iters, p->min_points, some,
-                                  nullptr, nullptr, nullptr);
+    alignas(16) static float some[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    vors_status st = icp_refusals(who, icp_args(1, some, some, nullptr, 1, nullptr, 0, some, 0, reinterpret_cast<const uint16_t*>(some), some, 1, 1, 1.0f,
+                                                p->dist_m, p->damping, p->step_eps, p->iters, p->min_points, nullptr, some, nullptr, nullptr, nullptr));
     if (st != VORS_OK) return st;
-    if ((st = icp_robust_refusals(who, nullptr, p->min_cos, p->huber_m, nullptr)) != VORS_OK) return st;
+    if ((st = icp_robust_refusals(who, IcpRobust{nullptr, p->min_cos, p->huber_m, nullptr})) != VORS_OK) return st;
     if (p->last_keyframes < 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": last_keyframes must be >= 0 (0 = the whole map)");
     return map_icp_verdict_refusals(w, *p);
 }
@@ -842,8 +847,8 @@ vors_status map_icp_joint_params_refusals(const char* who, const vors_map_icp_jo
     vors_status st = map_icp_params_refusals(who, &p->icp);
     if (st != VORS_OK) return st;
     // (what vors_icp_points_joint refuses of the two photo fields, in its own sentences: the grey levels are the handle's)
-    alignas(16) static const float some[4] = {0.f, 0.f, 0.f, 0.f};
-    if ((st = icp_joint_refusals(who, some, some, p->photo_scale_m, p->photo_huber_grey, nullptr, nullptr)) != VORS_OK) return st;
+    static const uint8_t some[4] = {0, 0, 0, 0};
+    if ((st = icp_joint_refusals(who, IcpJoint{some, some, p->photo_scale_m, p->photo_huber_grey, nullptr, nullptr})) != VORS_OK) return st;
     return map_icp_condition_refusals(who, *p);
 }
 float map_icp_photo_huber_m(const vors_map_icp_joint_params& p) { return icp_photo_huber_m(p.photo_scale_m, p.photo_huber_grey); }

@@ -176,6 +176,16 @@ static void trackers_map_emit_all(vors_trackers* t, const Geom& gm, const uint16
     if (nm.on) trackers_map_normals_pass(t, gm, depth, s);
 }
 
+// What every ICP pass over the handle's own map states of it, the correction's stage and the vors_trackers_icp_map* forwards alike: the
+// lists, the level-0 camera and shape (map normals exist for a level-0 map only), the depth scale. The rest is the caller's.
+static IcpCall map_icp_call(const vors_trackers* t, const uint16_t* depth) {
+    const Geom& g = t->batch->g;
+    IcpCall call{};
+    call.n = t->n_seq; call.xyz = t->map.xyz; call.normals = t->map.normals.n; call.list_counts = t->map.counts; call.capacity = t->map.capacity;
+    call.depth = depth; call.k = g.lv[0].k; call.rows = g.lv[0].rows; call.cols = g.lv[0].cols; call.depth_scale = g.depth_scale;
+    return call;
+}
+
 // The ICP correction of the promoted sequences (vors_trackers_enable_map_icp), between the keyframe stage and the emission: ARM, the frame
 // normals of the promoted sequences (normal_gate), the robust ICP pass as vors_trackers_icp_map_robust forwards it — device ranges, the
 // handle's workspace, statistics and gate counts into staging — and APPLY. `depth`: the planes the emission's normals pass reads.
@@ -237,21 +247,11 @@ static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint1
         nc.sel_count = gm.sel_count;
         launch_map_icp_frame_normals(nc, s);
     }
-    IcpCall call{};
-    call.n = t->n_seq;
-    call.xyz = m.xyz;
-    call.normals = m.normals.n;
-    call.list_counts = m.counts;
-    call.capacity = m.capacity;
+    IcpCall call = map_icp_call(t, depth);
     call.ranges = reinterpret_cast<const uint8_t*>(ic.ranges);
     call.range_stride = 8;
     call.poses_in = ic.start;
     call.pose_stride = 7;
-    call.depth = depth;
-    call.k = lv.k;
-    call.rows = lv.rows;
-    call.cols = lv.cols;
-    call.depth_scale = g.depth_scale;
     call.dist_m = ic.p.dist_m;
     call.damping = ic.p.damping;
     call.step_eps = ic.p.step_eps;
@@ -827,7 +827,7 @@ vors_status vors_trackers_render_map(vors_trackers* t, int level, const void* d_
                               d_gray, d_counts, s);
 }
 
-// What the two icp_map entries check of the handle before they forward (the stream is checked under the caller's DeviceGuard)
+// What the icp_map entries check of the handle before they forward (the stream is checked under the forward's DeviceGuard)
 static vors_status icp_map_refusals(const vors_trackers* t) {
     if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_map: the handle t is NULL");
     if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "icp_map: the keyframe map is not enabled (vors_trackers_enable_map)");
@@ -837,23 +837,39 @@ static vors_status icp_map_refusals(const vors_trackers* t) {
     return VORS_OK;
 }
 
+// The forward of the three entries below: the handle's own refusals, then icp_points_device (operators.cpp) on the handle's lists with
+// its level-0 intrinsics, refusing in the name of `who`, the handle-free entry of the form. robust / joint: as IcpArgs takes them; the
+// joint part's list grey is the map's, filled here.
+static vors_status trackers_icp_map(const char* who, vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps,
+                                    int iters, int min_points, const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in,
+                                    size_t pose_stride_bytes, void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29,
+                                    float* d_residuals, const IcpRobust* robust, IcpJoint* joint, void* hip_stream) {
+    vors_status st = icp_map_refusals(t);
+    if (st != VORS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(t->batch->device);
+    if ((st = check_stream(t->batch, s)) != VORS_OK) return st;
+    IcpArgs a{};
+    IcpCall& c = a.call = map_icp_call(t, d_depth);
+    const float cam5[5] = {c.k.cu, c.k.cv, c.k.fu, c.k.fv, c.k.skew};
+    a.cam5 = cam5;
+    c.ranges = static_cast<const uint8_t*>(d_ranges); a.range_stride_bytes = range_stride_bytes;
+    // NULL poses: the current frame poses, which the track call has already moved forward in stream order; the pass only reads them
+    c.poses_in = d_poses7_in ? static_cast<const float*>(d_poses7_in) : t->cur_poses.as<float>();
+    a.pose_stride_bytes = d_poses7_in ? pose_stride_bytes : 0;
+    c.dist_m = dist_m; c.damping = damping; c.step_eps = step_eps; c.iters = iters; a.min_points = min_points;
+    a.workspace = d_workspace; c.poses_out = d_poses7_out; c.stats = d_stats; c.sums29 = d_sums29; c.residuals = d_residuals;
+    if (joint) joint->list_gray = t->map.gray;
+    a.robust = robust; a.joint = joint;
+    return icp_points_device(who, a, s);
+}
+
 vors_status vors_trackers_icp_map(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters, int min_points,
                                   const void* d_ranges, size_t range_stride_bytes, const void* d_poses7_in, size_t pose_stride_bytes,
                                   void* d_workspace, float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
                                   void* hip_stream) {
-    vors_status st = icp_map_refusals(t);
-    if (st != VORS_OK) return st;
-    vors_batch* b = t->batch;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    DeviceGuard guard(b->device);
-    if ((st = check_stream(b, s)) != VORS_OK) return st;
-    const LevelGeom& lv = b->g.lv[0];  // (map normals exist for a level-0 map only)
-    const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
-    // NULL poses: the current frame poses, which the track call has already moved forward in stream order; the pass only reads them
-    if (!d_poses7_in) pose_stride_bytes = 0;
-    return vors_icp_points(t->n_seq, t->map.xyz, t->map.normals.n, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes,
-                           d_poses7_in ? d_poses7_in : t->cur_poses.p, pose_stride_bytes, d_depth, cam5, lv.rows, lv.cols, b->g.depth_scale, dist_m,
-                           damping, step_eps, iters, min_points, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, s);
+    return trackers_icp_map("icp_points", t, d_depth, dist_m, damping, step_eps, iters, min_points, d_ranges, range_stride_bytes, d_poses7_in,
+                            pose_stride_bytes, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, nullptr, nullptr, hip_stream);
 }
 
 vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_depth, float dist_m, float damping, float step_eps, int iters,
@@ -861,19 +877,9 @@ vors_status vors_trackers_icp_map_robust(vors_trackers* t, const uint16_t* d_dep
                                          size_t pose_stride_bytes, const float* d_frame_normals, float min_cos, float huber_m, void* d_workspace,
                                          float* d_poses7_out, vors_icp_stats* d_stats, float* d_sums29, float* d_residuals,
                                          uint32_t* d_gate_counts, void* hip_stream) {
-    vors_status st = icp_map_refusals(t);
-    if (st != VORS_OK) return st;
-    vors_batch* b = t->batch;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    DeviceGuard guard(b->device);
-    if ((st = check_stream(b, s)) != VORS_OK) return st;
-    const LevelGeom& lv = b->g.lv[0];
-    const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
-    if (!d_poses7_in) pose_stride_bytes = 0;  // (the current frame poses, as in vors_trackers_icp_map)
-    return vors_icp_points_robust(t->n_seq, t->map.xyz, t->map.normals.n, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes,
-                                  d_poses7_in ? d_poses7_in : t->cur_poses.p, pose_stride_bytes, d_depth, cam5, lv.rows, lv.cols,
-                                  b->g.depth_scale, dist_m, damping, step_eps, iters, min_points, d_frame_normals, min_cos, huber_m, d_workspace,
-                                  d_poses7_out, d_stats, d_sums29, d_residuals, d_gate_counts, s);
+    const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
+    return trackers_icp_map("icp_points_robust", t, d_depth, dist_m, damping, step_eps, iters, min_points, d_ranges, range_stride_bytes, d_poses7_in,
+                            pose_stride_bytes, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, &robust, nullptr, hip_stream);
 }
 
 vors_status vors_trackers_icp_map_joint(vors_trackers* t, const uint16_t* d_depth, const uint8_t* d_frame_gray, float dist_m, float damping,
@@ -882,20 +888,10 @@ vors_status vors_trackers_icp_map_joint(vors_trackers* t, const uint16_t* d_dept
                                         float huber_m, float photo_scale_m, float photo_huber_grey, void* d_workspace, float* d_poses7_out,
                                         vors_icp_stats* d_stats, float* d_sums29, float* d_residuals, uint32_t* d_gate_counts,
                                         float* d_photo_residuals, uint32_t* d_photo_counts, void* hip_stream) {
-    vors_status st = icp_map_refusals(t);
-    if (st != VORS_OK) return st;
-    vors_batch* b = t->batch;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    DeviceGuard guard(b->device);
-    if ((st = check_stream(b, s)) != VORS_OK) return st;
-    const LevelGeom& lv = b->g.lv[0];
-    const float cam5[5] = {lv.k.cu, lv.k.cv, lv.k.fu, lv.k.fv, lv.k.skew};
-    if (!d_poses7_in) pose_stride_bytes = 0;  // (the current frame poses, as in vors_trackers_icp_map)
-    return vors_icp_points_joint(t->n_seq, t->map.xyz, t->map.normals.n, t->map.gray, t->map.counts, t->map.capacity, d_ranges, range_stride_bytes,
-                                 d_poses7_in ? d_poses7_in : t->cur_poses.p, pose_stride_bytes, d_depth, d_frame_gray, cam5, lv.rows, lv.cols,
-                                 b->g.depth_scale, dist_m, damping, step_eps, iters, min_points, d_frame_normals, min_cos, huber_m, photo_scale_m,
-                                 photo_huber_grey, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, d_gate_counts, d_photo_residuals,
-                                 d_photo_counts, s);
+    const IcpRobust robust{d_frame_normals, min_cos, huber_m, d_gate_counts};
+    IcpJoint joint{nullptr, d_frame_gray, photo_scale_m, photo_huber_grey, d_photo_residuals, d_photo_counts};
+    return trackers_icp_map("icp_points_joint", t, d_depth, dist_m, damping, step_eps, iters, min_points, d_ranges, range_stride_bytes, d_poses7_in,
+                            pose_stride_bytes, d_workspace, d_poses7_out, d_stats, d_sums29, d_residuals, &robust, &joint, hip_stream);
 }
 
 vors_status vors_tracker_render_map(vors_tracker* t, int level, const float pose7[7], const uint32_t range2[2], int footprint, uint64_t* zkey,

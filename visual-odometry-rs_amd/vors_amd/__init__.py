@@ -209,19 +209,20 @@ def lib():
         _lib.vors_tracker_read_map_normals.argtypes = [vp, i, vp]
         _lib.vors_icp_workspace_bytes.argtypes = [i, i]
         _lib.vors_icp_workspace_bytes.restype = C.c_uint64
-        _lib.vors_icp_points.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, i, i, f, f, f, f, i, i, vp, vp, vp, vp, vp, vp]
-        _lib.vors_icp_points_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, vp, vp, vp]
-        _lib.vors_trackers_icp_map.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
-        _lib.vors_icp_points_robust.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, vp, vp, vp,
-                                                vp, vp, vp, vp]
-        _lib.vors_icp_points_robust_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, vp, vp, vp, vp, vp]
-        _lib.vors_trackers_icp_map_robust.argtypes = [vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, f, f, vp, vp, vp, vp, vp, vp, vp]
-        _lib.vors_icp_points_joint.argtypes = [i, vp, vp, vp, vp, i, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, f, f,
-                                               vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        _lib.vors_icp_points_joint_host.argtypes = [vp, vp, vp, C.c_uint32, i, vp, vp, vp, vp, vp, i, i, f, f, f, f, i, i, vp, f, f, f, f, vp, vp, vp,
-                                                    vp, vp, vp, vp]
-        _lib.vors_trackers_icp_map_joint.argtypes = [vp, vp, vp, f, f, f, i, i, vp, C.c_size_t, vp, C.c_size_t, vp, f, f, f, f, vp, vp, vp, vp, vp, vp,
-                                                     vp, vp, vp]
+        # The nine ICP entries (include/vors_hip.h 2e and the handle's forwards) from the pieces their lists share, each counted once:
+        u32, sz = C.c_uint32, C.c_size_t
+        strided = [vp, sz, vp, sz]  # ranges and poses, each with its stride in bytes
+        plane = [i, i, f]  # rows, cols, depth_scale
+        scalars = [f, f, f, i, i]  # dist_m, damping, step_eps, iters, min_points
+        out = [vp, vp, vp, vp]  # poses, stats, sums29, residuals
+        robust, joint = [vp, f, f], [f, f]  # frame normals, min_cos, huber_m; photo_scale_m, photo_huber_grey
+        # per form: the grey levels (of the lists, of the frames: one pointer each), its inputs behind min_points, its outputs behind residuals
+        for form, gray, more_in, more_out in (("", [], [], []), ("_robust", [], robust, [vp]), ("_joint", [vp], robust + joint, [vp, vp, vp])):
+            getattr(_lib, f"vors_icp_points{form}").argtypes = ([i, vp, vp] + gray + [vp, i] + strided + [vp] + gray + [vp] + plane + scalars + more_in
+                                                                + [vp] + out + more_out + [vp])
+            getattr(_lib, f"vors_icp_points{form}_host").argtypes = ([vp, vp] + gray + [u32, i, vp, vp, vp] + gray + [vp] + plane + scalars + more_in
+                                                                     + out + more_out)
+            getattr(_lib, f"vors_trackers_icp_map{form}").argtypes = [vp, vp] + gray + scalars + strided + more_in + [vp] + out + more_out + [vp]
         _lib.vors_trackers_enable_map_icp.argtypes = [vp, vp]
         _lib.vors_trackers_map_icp.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_icp.argtypes = [vp, vp]
@@ -1080,6 +1081,8 @@ class Trackers:
     """N sequences in lock-step, device resident (vors_trackers_*): Config::init / Tracker::track / current_frame for every
     sequence with the whole tracker state machine (poses, keyframe test, per-sequence keyframe promotion) on the device."""
 
+    _map = None  # enable_map()'s arguments, once it was accepted
+
     def __init__(self, config, n_sequences, rows, cols, device=None):
         self.config, self.n, self.rows, self.cols = config, n_sequences, rows, cols
         self._device = None if device is None else int(device)
@@ -1139,14 +1142,17 @@ class Trackers:
         """-> (depth [n, rows, cols] int16 tensor holding the u16 payload, weight [n, rows, cols] uint8) of every sequence's current keyframe
         (vors_trackers_keyframe_depth), valid in stream order after the last init() / track(). copy=False: views of the handle's own
         planes, which the next track() rewrites and which die with this object."""
-        import torch
-        d, w = C.c_void_p(), C.c_void_p()
-        _check(lib().vors_trackers_keyframe_depth(self._h, C.byref(d), C.byref(w)))
-        dev = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
-        shape = (self.n, self.rows, self.cols)
-        depth = _device_view(d.value, shape, "<i2", dev)
-        weight = _device_view(w.value, shape, "|u1", dev)
-        return (depth.clone(), weight.clone()) if copy else (depth, weight)
+        plane = (self.rows, self.cols)
+        return tuple(self._views(lib().vors_trackers_keyframe_depth, copy, depth=(plane, "<i2"), weight=(plane, "|u1")).values())
+
+    def _views(self, entry, copy, **specs):
+        """What the getters share. entry(handle, a pointer out per item of specs) -> dict of tensors over the handle's own buffers, cloned
+        when copy. specs: key=(the shape behind [n], typestr), in the order of the entry's pointers."""
+        p = [C.c_void_p() for _ in specs]
+        _check(entry(self._h, *[C.byref(q) for q in p]))
+        dev = _torch_device(self._device)
+        out = {key: _device_view(q.value, (self.n,) + tuple(shape), typestr, dev) for q, (key, (shape, typestr)) in zip(p, specs.items())}
+        return {key: t.clone() for key, t in out.items()} if copy else out
 
     def workspace_bytes(self):
         b = C.c_uint64()
@@ -1167,15 +1173,9 @@ class Trackers:
         capacity), "n_segments" [n] int32, "segments" [n, max_keyframes, 40] uint8 — the vors_map_segment records as bytes:
         decode_map_segments() gives the structured view. Only the first min(counts, capacity) entries of a list and the first
         min(n_segments, max_keyframes) records are written. copy=False: views of the handle's own buffers, which die with this object."""
-        import torch
-        p = [C.c_void_p() for _ in range(6)]
-        _check(lib().vors_trackers_map(self._h, *[C.byref(q) for q in p]))
-        _, cap, nkf, _ = self._map
-        dev = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
-        out = dict(xyz=_device_view(p[0].value, (self.n, cap, 3), "<f4", dev), pixel=_device_view(p[1].value, (self.n, cap), "<i4", dev),
-                   gray=_device_view(p[2].value, (self.n, cap), "|u1", dev), counts=_device_view(p[3].value, (self.n,), "<i4", dev),
-                   segments=_device_view(p[4].value, (self.n, nkf, 40), "|u1", dev), n_segments=_device_view(p[5].value, (self.n,), "<i4", dev))
-        return {k: v.clone() for k, v in out.items()} if copy else out
+        _, cap, nkf, _ = self._map or (0, 0, 0, 0)  # (no map: the entry refuses)
+        return self._views(lib().vors_trackers_map, copy, xyz=((cap, 3), "<f4"), pixel=((cap,), "<i4"), gray=((cap,), "|u1"), counts=((), "<i4"),
+                           segments=((nkf, 40), "|u1"), n_segments=((), "<i4"))
 
     def enable_map_voxels(self, voxel_m, table_slots):
         """Voxel filter of the keyframe map (vors_trackers_enable_map_voxels): after enable_map(), before init(), once. The map then keeps
@@ -1195,10 +1195,8 @@ class Trackers:
         """-> [n, capacity, 3] float32 tensor (vors_trackers_map_normals), valid in stream order after the last init() / track(): entry r
         of a sequence is the normal of map()'s entry r, written for r < min(counts, capacity); three zeros = no normal. copy=False: a view
         of the handle's own buffer, which dies with this object."""
-        p = C.c_void_p()
-        _check(lib().vors_trackers_map_normals(self._h, C.byref(p)))
-        out = _device_view(p.value, (self.n, self._map[1], 3), "<f4", _torch_device(self._device))
-        return out.clone() if copy else out
+        cap = self._map[1] if self._map else 0  # (no map: the entry refuses)
+        return self._views(lib().vors_trackers_map_normals, copy, normals=((cap, 3), "<f4"))["normals"]
 
     def enable_map_icp(self, **params):
         """ICP correction at keyframe promotion (vors_trackers_enable_map_icp): after enable_map_normals(), before init(), once. Every
@@ -1220,32 +1218,19 @@ class Trackers:
         """-> [n, 20] uint8 tensor (vors_trackers_map_icp_joint), valid in stream order after the last track(): the
         vors_map_icp_joint_record of every sequence beside map_icp()'s records, as bytes: decode_map_icp_joint_records(). copy=False: a view
         of the handle's own buffer, which dies with this object."""
-        p = C.c_void_p()
-        _check(lib().vors_trackers_map_icp_joint(self._h, C.byref(p)))
-        out = _device_view(p.value, (self.n, MAP_ICP_JOINT_RECORD_DTYPE.itemsize), "|u1", _torch_device(self._device))
-        return out.clone() if copy else out
+        return self._views(lib().vors_trackers_map_icp_joint, copy, records=((MAP_ICP_JOINT_RECORD_DTYPE.itemsize,), "|u1"))["records"]
 
     def map_icp(self, copy=True):
         """-> dict of tensors (vors_trackers_map_icp), valid in stream order after the last track(): "records" [n, 112] uint8 — the
         vors_map_icp_record of every sequence for the LAST track call as bytes: decode_map_icp_records() — and "totals" [n, 2] int32,
         promotions attempted and accepted since init(). copy=False: views of the handle's own buffers, which die with this object."""
-        p = [C.c_void_p() for _ in range(2)]
-        _check(lib().vors_trackers_map_icp(self._h, *[C.byref(q) for q in p]))
-        dev = _torch_device(self._device)
-        out = dict(records=_device_view(p[0].value, (self.n, MAP_ICP_RECORD_DTYPE.itemsize), "|u1", dev),
-                   totals=_device_view(p[1].value, (self.n, 2), "<i4", dev))
-        return {k: v.clone() for k, v in out.items()} if copy else out
+        return self._views(lib().vors_trackers_map_icp, copy, records=((MAP_ICP_RECORD_DTYPE.itemsize,), "|u1"), totals=((2,), "<i4"))
 
     def map_voxels(self, copy=True):
         """-> dict of tensors (vors_trackers_map_voxels), valid in stream order after the last init() / track(): "occupied" [n] int32, the
         distinct voxels of a sequence so far (== map()["counts"] while it has not overflowed), "overflow" [n] int32, non-zero once a
         sequence's voxels outgrew table_slots. copy=False: views of the handle's own buffers, which die with this object."""
-        import torch
-        p = [C.c_void_p() for _ in range(2)]
-        _check(lib().vors_trackers_map_voxels(self._h, *[C.byref(q) for q in p]))
-        dev = torch.device("cuda", torch.cuda.current_device() if self._device is None else self._device)
-        out = dict(occupied=_device_view(p[0].value, (self.n,), "<i4", dev), overflow=_device_view(p[1].value, (self.n,), "<i4", dev))
-        return {k: v.clone() for k, v in out.items()} if copy else out
+        return self._views(lib().vors_trackers_map_voxels, copy, occupied=((), "<i4"), overflow=((), "<i4"))
 
     def render_map(self, level=0, poses=None, ranges=None, footprint=1, depth=True, gray=True, counts=False, zkey=False):
         """The keyframe map seen from one pose per sequence (vors_trackers_render_map): render_points() on the handle's own map with the
@@ -1268,42 +1253,34 @@ class Trackers:
         normals with its level-0 intrinsics, on the current stream, not synchronised. depth [n, rows, cols] int16 tensor holding the u16
         payload; poses None = every sequence's current frame pose, read on the device. The tracker itself is only read. Everything else,
         and the result, as in icp_points()."""
+        return self._icp_map("icp_map", depth, dist_m, damping, step_eps, iters, min_points, poses, ranges, workspace, stats, sums29, residuals)
+
+    def _icp_map(self, who, depth, dist_m, damping, step_eps, iters, min_points, poses, ranges, workspace, stats, sums29, residuals, robust=None,
+                 joint=None):
+        """The body of icp_map(), icp_map_robust() and icp_map_joint(): vors_trackers_<who>. robust, joint: see _icp_pass (the lists' grey
+        levels are the handle's own: None)."""
         import torch
         self._check_frames(depth, depth)
         if depth.dtype != torch.int16:
-            raise VorsError("icp_map: depth int16 [n, rows, cols], contiguous")
-        dev = _torch_device(self._device)
+            raise VorsError(f"{who}: depth int16 [n, rows, cols], contiguous")
         poses, pose_stride = _render_poses(poses, self.n)
         rng, range_stride = _render_ranges(ranges, self.n)
-        cap = self._map[1]
-        ws, bufs = _icp_buffers(self.n, cap, dev, workspace, stats, sums29, residuals)
-        _check(lib().vors_trackers_icp_map(self._h, Batch._dp(depth), float(dist_m), float(damping), float(step_eps), int(iters), int(min_points),
-                                           rng, range_stride, Batch._dp(poses), pose_stride, Batch._dp(ws), *[Batch._dp(t) for t in bufs],
-                                           Batch._stream()))
-        self._icp_refs = (depth, poses, ranges, ws)
-        return _icp_result(bufs, stats, sums29, residuals)
+        cap = self._map[1] if self._map else 1  # (no map: the entry refuses)
+        ws, more_in, outs, result = _icp_pass(who, self.n, cap, depth, _torch_device(self._device), workspace, stats, sums29, residuals, robust, joint)
+        frame_gray = [] if joint is None else [Batch._dp(joint[1])]
+        _check(getattr(lib(), "vors_trackers_" + who)(self._h, Batch._dp(depth), *frame_gray, float(dist_m), float(damping), float(step_eps),
+                                                      int(iters), int(min_points), rng, range_stride, Batch._dp(poses), pose_stride, *more_in, *outs,
+                                                      Batch._stream()))
+        self._icp_refs = (depth, poses, ranges, ws) + (() if robust is None else (robust[0],)) + (() if joint is None else (joint[1],))
+        return result
 
     def icp_map_robust(self, depth, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6, frame_normals=None, min_cos=0.0, huber_m=0.0,
                        poses=None, ranges=None, workspace=None, stats=True, sums29=False, residuals=False, gate_counts=False):
         """icp_map() through the robust pass (vors_trackers_icp_map_robust): icp_points_robust() on the handle's own map and map normals.
         frame_normals [n, rows, cols, 3] float32 (depth_normals() of `depth` at level 0 without poses; None = no gate), min_cos, huber_m
         and gate_counts as in icp_points_robust(); everything else as in icp_map()."""
-        import torch
-        self._check_frames(depth, depth)
-        if depth.dtype != torch.int16:
-            raise VorsError("icp_map_robust: depth int16 [n, rows, cols], contiguous")
-        dev = _torch_device(self._device)
-        poses, pose_stride = _render_poses(poses, self.n)
-        rng, range_stride = _render_ranges(ranges, self.n)
-        cap = self._map[1] if getattr(self, "_map", None) else 1  # (no map: the entry refuses)
-        ws, bufs = _icp_buffers(self.n, cap, dev, workspace, stats, sums29, residuals)
-        gates =_icp_robust_buffers("icp_map_robust", frame_normals, depth.shape, gate_counts, dev)
-        _check(lib().vors_trackers_icp_map_robust(self._h, Batch._dp(depth), float(dist_m), float(damping), float(step_eps), int(iters),
-                                                  int(min_points), rng, range_stride, Batch._dp(poses), pose_stride, Batch._dp(frame_normals),
-                                                  float(min_cos), float(huber_m), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
-                                                  Batch._stream()))
-        self._icp_refs = (depth, poses, ranges, ws, frame_normals)
-        return dict(_icp_result(bufs, stats, sums29, residuals), **_result(("gate_counts", _asked(gate_counts), gates)))
+        return self._icp_map("icp_map_robust", depth, dist_m, damping, step_eps, iters, min_points, poses, ranges, workspace, stats, sums29, residuals,
+                             (frame_normals, min_cos, huber_m, gate_counts))
 
     def icp_map_joint(self, depth, dist_m, frame_gray=None, damping=0.0, step_eps=1e-5, iters=8, min_points=6, frame_normals=None, min_cos=0.0,
                       huber_m=0.0, photo_scale_m=0.0, photo_huber_grey=0.0, poses=None, ranges=None, workspace=None, stats=True, sums29=False,
@@ -1311,26 +1288,9 @@ class Trackers:
         """icp_map_robust() through the joint pass (vors_trackers_icp_map_joint): icp_points_joint() on the handle's own map, map normals
         and map grey levels. frame_gray [n, rows, cols] uint8 (the level-0 grey frames `depth` belongs to; None only with photo_scale_m 0),
         photo_scale_m, photo_huber_grey, photo_residuals and photo_counts as in icp_points_joint(); everything else as in icp_map_robust()."""
-        import torch
-        self._check_frames(depth, depth)
-        if depth.dtype != torch.int16:
-            raise VorsError("icp_map_joint: depth int16 [n, rows, cols], contiguous")
-        dev = _torch_device(self._device)
-        poses, pose_stride = _render_poses(poses, self.n)
-        rng, range_stride = _render_ranges(ranges, self.n)
-        cap = self._map[1] if getattr(self, "_map", None) else 1  # (no map: the entry refuses)
-        ws, bufs = _icp_buffers(self.n, cap, dev, workspace, stats, sums29, residuals)
-        gates = _icp_robust_buffers("icp_map_joint", frame_normals, depth.shape, gate_counts, dev)
-        photo = _icp_joint_buffers("icp_map_joint", None, frame_gray, depth.shape, cap, photo_residuals, photo_counts, dev)
-        _check(lib().vors_trackers_icp_map_joint(self._h, Batch._dp(depth), Batch._dp(frame_gray), float(dist_m), float(damping), float(step_eps),
-                                                 int(iters), int(min_points), rng, range_stride, Batch._dp(poses), pose_stride,
-                                                 Batch._dp(frame_normals), float(min_cos), float(huber_m), float(photo_scale_m),
-                                                 float(photo_huber_grey), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
-                                                 *[Batch._dp(t) for t in photo], Batch._stream()))
-        self._icp_refs = (depth, poses, ranges, ws, frame_normals, frame_gray)
-        return dict(_icp_result(bufs, stats, sums29, residuals),
-                    **_result(("gate_counts", _asked(gate_counts), gates), ("photo_residuals", _asked(photo_residuals), photo[0]),
-                              ("photo_counts", _asked(photo_counts), photo[1])))
+        return self._icp_map("icp_map_joint", depth, dist_m, damping, step_eps, iters, min_points, poses, ranges, workspace, stats, sums29, residuals,
+                             (frame_normals, min_cos, huber_m, gate_counts),
+                             (None, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals, photo_counts))
 
     def enable_kernel_timing(self, ring=64):
         _check(lib().vors_trackers_enable_kernel_timing(self._h, int(ring)))
@@ -1750,26 +1710,104 @@ def icp_points(xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_
     the u16 payload; poses [n, 7] float32 (or a track's out_stats bytes), required; ranges: see _render_ranges. iters = 0 evaluates at
     the given poses. workspace: a uint8 tensor of icp_workspace_bytes(n, capacity) to reuse (None = a new one). stats / sums29 /
     residuals may also be a tensor of that shape to write into."""
+    return _icp_device("icp_points", xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_m, damping, step_eps, iters, min_points,
+                       ranges, workspace, stats, sums29, residuals)
+
+
+def _icp_pass(who, n, cap, depth, dev, workspace, stats, sums29, residuals, robust, joint):
+    """What the handle-free and the Trackers forms of a device pass share behind their own checks: the workspace, the output tensors and
+    what a form adds. robust: None or (frame_normals, min_cos, huber_m, gate_counts); joint (with robust): None or (list_gray, frame_gray,
+    photo_scale_m, photo_huber_grey, photo_residuals, photo_counts) -> (workspace, the form's C arguments behind min_points, the C
+    arguments from the workspace to the last output, the result dict)."""
+    ws, bufs = _icp_buffers(n, cap, dev, workspace, stats, sums29, residuals)
+    more_in, outs, result = [], list(bufs), _icp_result(bufs, stats, sums29, residuals)
+    if robust is not None:
+        frame_normals, min_cos, huber_m, gate_counts = robust
+        gates = _icp_robust_buffers(who, frame_normals, depth.shape, gate_counts, dev)
+        more_in += [Batch._dp(frame_normals), float(min_cos), float(huber_m)]
+        outs.append(gates)
+        result.update(_result(("gate_counts", _asked(gate_counts), gates)))
+    if joint is not None:
+        list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals, photo_counts = joint
+        photo = _icp_joint_buffers(who, list_gray, frame_gray, depth.shape, cap, photo_residuals, photo_counts, dev)
+        more_in += [float(photo_scale_m), float(photo_huber_grey)]
+        outs += photo
+        result.update(_result(("photo_residuals", _asked(photo_residuals), photo[0]), ("photo_counts", _asked(photo_counts), photo[1])))
+    return ws, more_in, [Batch._dp(t) for t in [ws] + outs], result
+
+
+def _icp_device(who, xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_m, damping, step_eps, iters, min_points, ranges, workspace,
+                stats, sums29, residuals, robust=None, joint=None):
+    """The body of icp_points(), icp_points_robust() and icp_points_joint(): vors_<who>. robust, joint: see _icp_pass."""
     import torch
     n = xyz.shape[0]
     cap = xyz.shape[1] if xyz.dim() == 3 else -1
     if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or normals.dtype != torch.float32
             or not normals.is_contiguous() or tuple(normals.shape) != (n, cap, 3) or list_counts.dtype != torch.int32
             or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
-        raise VorsError("icp_points: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
+        raise VorsError(f"{who}: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
     if depth.dtype != torch.int16 or depth.dim() != 3 or depth.shape[0] != n or not depth.is_contiguous():
-        raise VorsError("icp_points: depth int16 [n, rows, cols], contiguous")
+        raise VorsError(f"{who}: depth int16 [n, rows, cols], contiguous")
     if poses is None:
-        raise VorsError("icp_points: poses are required")
-    k = _normals_common(cam5, "icp_points")
+        raise VorsError(f"{who}: poses are required")
+    k = _normals_common(cam5, who)
     poses, pose_stride = _render_poses(poses, n)
     rng, range_stride = _render_ranges(ranges, n)
-    ws, bufs = _icp_buffers(n, cap, xyz.device, workspace, stats, sums29, residuals)
-    _check(lib().vors_icp_points(n, Batch._dp(xyz), Batch._dp(normals), Batch._dp(list_counts), cap, rng, range_stride, Batch._dp(poses),
-                                 pose_stride, Batch._dp(depth), _ptr(k), depth.shape[1], depth.shape[2], float(depth_scale), float(dist_m),
-                                 float(damping), float(step_eps), int(iters), int(min_points), Batch._dp(ws), *[Batch._dp(t) for t in bufs],
-                                 Batch._stream()))
-    return _icp_result(bufs, stats, sums29, residuals)
+    _, more_in, outs, result = _icp_pass(who, n, cap, depth, xyz.device, workspace, stats, sums29, residuals, robust, joint)
+    list_gray, frame_gray = ([], []) if joint is None else ([Batch._dp(joint[0])], [Batch._dp(joint[1])])
+    _check(getattr(lib(), "vors_" + who)(n, Batch._dp(xyz), Batch._dp(normals), *list_gray, Batch._dp(list_counts), cap, rng, range_stride,
+                                         Batch._dp(poses), pose_stride, Batch._dp(depth), *frame_gray, _ptr(k), depth.shape[1], depth.shape[2],
+                                         float(depth_scale), float(dist_m), float(damping), float(step_eps), int(iters), int(min_points), *more_in,
+                                         *outs, Batch._stream()))
+    return result
+
+
+def _icp_host(who, xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping, step_eps, iters, min_points, count, range2, residuals,
+              robust=None, joint=None):
+    """The body of icp_points_host(), icp_points_robust_host() and icp_points_joint_host(): vors_<who>. robust: None or (frame_normals,
+    min_cos, huber_m); joint (with robust): None or (list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals)."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(depth, np.uint16)
+    k = np.ascontiguousarray(cam5, np.float32)
+    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
+    bad = len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,))
+    wanted = {"residuals": residuals}
+    more_in, gray_shapes = [], ("", "")
+    if robust is not None:
+        fn = None if robust[0] is None else np.ascontiguousarray(robust[0], np.float32)
+        bad = bad or (fn is not None and fn.shape != d.shape + (3,))
+        more_in += [_ptr(fn), float(robust[1]), float(robust[2])]
+    if joint is not None:
+        lg = None if joint[0] is None else np.ascontiguousarray(joint[0], np.uint8).reshape(-1)
+        fg = None if joint[1] is None else np.ascontiguousarray(joint[1], np.uint8)
+        bad = bad or (lg is not None and len(lg) != len(p)) or (fg is not None and fg.shape != d.shape)
+        more_in += [float(joint[2]), float(joint[3])]
+        wanted["photo_residuals"] = joint[4]
+        gray_shapes = ("list_gray [capacity] or None, ", "frame_gray [rows, cols] or None, ")
+    if bad:
+        raise VorsError(f"{who}: xyz and normals [capacity, 3], {gray_shapes[0]}depth [rows, cols], {gray_shapes[1]}cam5 [5], pose7 [7], "
+                        f"range2 [2] or None{'' if robust is None else ', frame_normals [rows, cols, 3] or None'}")
+    for name, given in wanted.items():
+        if given is None:
+            given = np.full(len(p), np.nan, np.float32)
+        elif given.dtype != np.float32 or given.shape != (len(p),) or not given.flags.c_contiguous:
+            raise VorsError(f"{who}: {name} must be a contiguous float32 array ({len(p)},)")
+        wanted[name] = given
+    stats = np.zeros(1, ICP_STATS_DTYPE)
+    out = dict(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), residuals=wanted["residuals"])
+    if robust is not None:
+        out["gate_counts"] = np.zeros(ICP_GATE_COUNTS, np.uint32)
+    if joint is not None:
+        out.update(photo_residuals=wanted["photo_residuals"], photo_counts=np.zeros(ICP_PHOTO_COUNTS, np.uint32))
+    list_gray, frame_gray = ([], []) if joint is None else ([_ptr(lg) if lg is not None and len(lg) else None], [_ptr(fg)])
+    _check(getattr(lib(), "vors_" + who)(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, *list_gray,
+                                         len(p) if count is None else int(count), len(p), _ptr(rng), _ptr(pose), _ptr(d), *frame_gray, _ptr(k),
+                                         d.shape[0], d.shape[1], float(depth_scale), float(dist_m), float(damping), float(step_eps), int(iters),
+                                         int(min_points), *more_in, _ptr(out["pose"]), _ptr(stats),
+                                         *[_ptr(a) for name, a in out.items() if name not in ("pose", "stats")]))
+    return out
 
 
 ICP_GATE_COUNTS = 4  # VORS_ICP_GATE_COUNTS: with_depth, within_dist, matched, huber_linear
@@ -1808,20 +1846,24 @@ def map_icp_params(dist_m=_REQUIRED, **params):
     unknown = sorted(set(params) - set(MAP_ICP_DEFAULTS))
     if unknown:
         raise VorsError(f"map_icp: unknown parameter {unknown[0]!r} (dist_m, {', '.join(MAP_ICP_DEFAULTS)})")
-    values = dict(MAP_ICP_DEFAULTS, dist_m=dist_m, **params)
-    p = vors_map_icp_params()
-    for name, kind in vors_map_icp_params._fields_:
+    return _map_icp_fields(vors_map_icp_params(), "map_icp", vors_map_icp_params._fields_, dict(MAP_ICP_DEFAULTS, dist_m=dist_m, **params))
+
+
+def _map_icp_fields(record, who, fields, values):
+    """The field coercion of map_icp_params() and map_icp_joint_params(): every (name, C type) of `fields` set in `record` from values[name]
+    — a number, an integer where the field is one, a bool only for normal_gate — refused in the name of `who` -> record."""
+    for name, kind in fields:
         v = values[name]
         if isinstance(v, (bool, np.bool_)) and name == "normal_gate":
             v = int(v)
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise VorsError(f"map_icp: {name} must be a number, got {v!r}")
+            raise VorsError(f"{who}: {name} must be a number, got {v!r}")
         if kind is C.c_int32:
             if not isinstance(v, (int, np.integer)) or not -2 ** 31 <= int(v) < 2 ** 31:
-                raise VorsError(f"map_icp: {name} must be an integer that fits a C int, got {v!r}")
+                raise VorsError(f"{who}: {name} must be an integer that fits a C int, got {v!r}")
             v = int(v)
-        setattr(p, name, v)
-    return p
+        setattr(record, name, v)
+    return record
 
 
 def _map_icp_arg(spec):
@@ -1836,8 +1878,12 @@ def _map_icp_arg(spec):
 def decode_map_icp_records(records):
     """The "records" tensor of Trackers.map_icp() ([n, 112] uint8: the vors_map_icp_record records as bytes) -> a structured numpy array
     [n] of MAP_ICP_RECORD_DTYPE (its "stats" field is ICP_STATS_DTYPE)."""
+    return _decode_records(records, MAP_ICP_RECORD_DTYPE)
+
+
+def _decode_records(records, dtype):
     a = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
-    return np.ascontiguousarray(a).view(MAP_ICP_RECORD_DTYPE).reshape(-1)
+    return np.ascontiguousarray(a).view(dtype).reshape(-1)
 
 
 def map_icp_window_host(segments, n_segments, max_keyframes, count, capacity, last_keyframes):
@@ -1856,14 +1902,19 @@ def map_icp_window_host(segments, n_segments, max_keyframes, count, capacity, la
 def map_icp_verdict_host(params, stats, pose_before, pose_after):
     """The verdict rule of the map ICP correction on the host (vors_map_icp_verdict_host; needs no GPU): params = map_icp_params(...) or
     a dict of its keywords (only the four verdict fields are read), stats = a structured scalar of ICP_STATS_DTYPE -> a MAP_ICP_* verdict."""
-    p = map_icp_params(**params) if isinstance(params, dict) else params
+    return _map_icp_verdict("map_icp_verdict_host", map_icp_params, params, stats, pose_before, pose_after)
+
+
+def _map_icp_verdict(who, build, params, stats, pose_before, pose_after, *dilutions):
+    """The body of map_icp_verdict_host() and map_icp_verdict_joint_host(): vors_<who>; build: the parameter builder a dict goes through."""
+    p = build(**params) if isinstance(params, dict) else params
     s = np.zeros(1, ICP_STATS_DTYPE)
     s[0] = stats
     a, b = np.ascontiguousarray(pose_before, np.float32), np.ascontiguousarray(pose_after, np.float32)
     if a.shape != (7,) or b.shape != (7,):
-        raise VorsError("map_icp_verdict_host: pose_before and pose_after [7]")
+        raise VorsError(f"{who}: pose_before and pose_after [7]")
     v = C.c_uint32(99)
-    _check(lib().vors_map_icp_verdict_host(C.byref(p), _ptr(s), _ptr(a), _ptr(b), C.byref(v)))
+    _check(getattr(lib(), "vors_" + who)(C.byref(p), _ptr(s), _ptr(a), _ptr(b), *[float(x) for x in dilutions], C.byref(v)))
     return v.value
 
 
@@ -1896,18 +1947,12 @@ def map_icp_joint_params(dist_m=_REQUIRED, **params):
     own = {k: params.pop(k) for k in list(params) if k in MAP_ICP_JOINT_DEFAULTS}
     p = vors_map_icp_joint_params()
     p.icp = map_icp_params(dist_m, **params)
-    for name, default in MAP_ICP_JOINT_DEFAULTS.items():
-        v = own.get(name, default)
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise VorsError(f"map_icp_joint: {name} must be a number, got {v!r}")
-        setattr(p, name, v)
-    return p
+    return _map_icp_fields(p, "map_icp_joint", vors_map_icp_joint_params._fields_[1:], dict(MAP_ICP_JOINT_DEFAULTS, **own))
 
 
 def decode_map_icp_joint_records(records):
     """The tensor of Trackers.map_icp_joint() ([n, 20] uint8) -> a structured numpy array [n] of MAP_ICP_JOINT_RECORD_DTYPE."""
-    a = records.cpu().numpy() if hasattr(records, "cpu") else np.asarray(records)
-    return np.ascontiguousarray(a).view(MAP_ICP_JOINT_RECORD_DTYPE).reshape(-1)
+    return _decode_records(records, MAP_ICP_JOINT_RECORD_DTYPE)
 
 
 def icp_condition_from_sums(sums29):
@@ -1946,15 +1991,7 @@ def map_icp_verdict_joint_host(params, stats, pose_before, pose_after, dilution_
     """The joint stage's verdict on the host (vors_map_icp_verdict_joint_host; needs no GPU): params = map_icp_joint_params(...) or a dict
     of its keywords (the four verdict fields and the two bounds are read), stats = a structured scalar of ICP_STATS_DTYPE -> a MAP_ICP_*
     verdict, MAP_ICP_CONDITION among them."""
-    p = map_icp_joint_params(**params) if isinstance(params, dict) else params
-    s = np.zeros(1, ICP_STATS_DTYPE)
-    s[0] = stats
-    a, b = np.ascontiguousarray(pose_before, np.float32), np.ascontiguousarray(pose_after, np.float32)
-    if a.shape != (7,) or b.shape != (7,):
-        raise VorsError("map_icp_verdict_joint_host: pose_before and pose_after [7]")
-    v = C.c_uint32(99)
-    _check(lib().vors_map_icp_verdict_joint_host(C.byref(p), _ptr(s), _ptr(a), _ptr(b), float(dilution_t), float(dilution_r), C.byref(v)))
-    return v.value
+    return _map_icp_verdict("map_icp_verdict_joint_host", map_icp_joint_params, params, stats, pose_before, pose_after, dilution_t, dilution_r)
 
 
 def _icp_robust_buffers(who, frame_normals, shape, gate_counts, dev):
@@ -1975,58 +2012,16 @@ def icp_points_robust(xyz, normals, list_counts, depth, cam5, depth_scale, poses
     point-to-plane residual in metres ("sums29"[0] and stats rms are then the Huber loss). gate_counts: "gate_counts" [n, 4] int32 of the
     final evaluation (with_depth, within_dist, matched, huber_linear). frame_normals None and huber_m 0: icp_points() bit for bit.
     Everything else, and the result, as in icp_points()."""
-    import torch
-    n = xyz.shape[0]
-    cap = xyz.shape[1] if xyz.dim() == 3 else -1
-    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or normals.dtype != torch.float32
-            or not normals.is_contiguous() or tuple(normals.shape) != (n, cap, 3) or list_counts.dtype != torch.int32
-            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
-        raise VorsError("icp_points_robust: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
-    if depth.dtype != torch.int16 or depth.dim() != 3 or depth.shape[0] != n or not depth.is_contiguous():
-        raise VorsError("icp_points_robust: depth int16 [n, rows, cols], contiguous")
-    if poses is None:
-        raise VorsError("icp_points_robust: poses are required")
-    k = _normals_common(cam5, "icp_points_robust")
-    poses, pose_stride = _render_poses(poses, n)
-    rng, range_stride = _render_ranges(ranges, n)
-    ws, bufs = _icp_buffers(n, cap, xyz.device, workspace, stats, sums29, residuals)
-    gates = _icp_robust_buffers("icp_points_robust", frame_normals, depth.shape, gate_counts, xyz.device)
-    _check(lib().vors_icp_points_robust(n, Batch._dp(xyz), Batch._dp(normals), Batch._dp(list_counts), cap, rng, range_stride, Batch._dp(poses),
-                                        pose_stride, Batch._dp(depth), _ptr(k), depth.shape[1], depth.shape[2], float(depth_scale),
-                                        float(dist_m), float(damping), float(step_eps), int(iters), int(min_points), Batch._dp(frame_normals),
-                                        float(min_cos), float(huber_m), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
-                                        Batch._stream()))
-    return dict(_icp_result(bufs, stats, sums29, residuals), **_result(("gate_counts", _asked(gate_counts), gates)))
+    return _icp_device("icp_points_robust", xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_m, damping, step_eps, iters, min_points,
+                       ranges, workspace, stats, sums29, residuals, (frame_normals, min_cos, huber_m, gate_counts))
 
 
 def icp_points_robust_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6,
                            frame_normals=None, min_cos=0.0, huber_m=0.0, count=None, range2=None, residuals=None):
     """The loop of icp_points_robust for ONE list on the host (vors_icp_points_robust_host; needs no GPU): icp_points_host()'s arguments,
     frame_normals [rows, cols, 3] float32 (None = no gate), min_cos, huber_m -> icp_points_host()'s dict and "gate_counts" [4] uint32."""
-    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-    d = np.ascontiguousarray(depth, np.uint16)
-    k = np.ascontiguousarray(cam5, np.float32)
-    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
-    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
-    fn = None if frame_normals is None else np.ascontiguousarray(frame_normals, np.float32)
-    if (len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,))
-            or (fn is not None and fn.shape != d.shape + (3,))):
-        raise VorsError("icp_points_robust_host: xyz and normals [capacity, 3], depth [rows, cols], cam5 [5], pose7 [7], range2 [2] or None, "
-                        "frame_normals [rows, cols, 3] or None")
-    if residuals is None:
-        residuals = np.full(len(p), np.nan, np.float32)
-    elif residuals.dtype != np.float32 or residuals.shape != (len(p),) or not residuals.flags.c_contiguous:
-        raise VorsError(f"icp_points_robust_host: residuals must be a contiguous float32 array ({len(p)},)")
-    stats = np.zeros(1, ICP_STATS_DTYPE)
-    out = dict(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), residuals=residuals,
-               gate_counts=np.zeros(ICP_GATE_COUNTS, np.uint32))
-    _check(lib().vors_icp_points_robust_host(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, len(p) if count is None else int(count),
-                                             len(p), _ptr(rng), _ptr(pose), _ptr(d), _ptr(k), d.shape[0], d.shape[1], float(depth_scale),
-                                             float(dist_m), float(damping), float(step_eps), int(iters), int(min_points), _ptr(fn), float(min_cos),
-                                             float(huber_m), _ptr(out["pose"]), _ptr(stats), _ptr(out["sums29"]), _ptr(residuals),
-                                             _ptr(out["gate_counts"])))
-    return out
+    return _icp_host("icp_points_robust_host", xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping, step_eps, iters, min_points, count,
+                     range2, residuals, (frame_normals, min_cos, huber_m))
 
 
 def _icp_joint_buffers(who, list_gray, frame_gray, shape, cap, photo_residuals, photo_counts, dev):
@@ -2055,32 +2050,9 @@ def icp_points_joint(xyz, normals, list_gray, list_counts, depth, frame_gray, ca
     [n, capacity] float32, I - grey in grey levels, NaN = no photometric row (a new tensor is filled with NaN first); photo_counts:
     "photo_counts" [n, 2] int32 of the final evaluation (photo_used, photo_huber_linear). Everything else, and the rest of the result,
     as in icp_points_robust()."""
-    import torch
-    n = xyz.shape[0]
-    cap = xyz.shape[1] if xyz.dim() == 3 else -1
-    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or normals.dtype != torch.float32
-            or not normals.is_contiguous() or tuple(normals.shape) != (n, cap, 3) or list_counts.dtype != torch.int32
-            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,)):
-        raise VorsError("icp_points_joint: xyz and normals float32 [n, capacity, 3], list_counts int32 [n], contiguous")
-    if depth.dtype != torch.int16 or depth.dim() != 3 or depth.shape[0] != n or not depth.is_contiguous():
-        raise VorsError("icp_points_joint: depth int16 [n, rows, cols], contiguous")
-    if poses is None:
-        raise VorsError("icp_points_joint: poses are required")
-    k = _normals_common(cam5, "icp_points_joint")
-    poses, pose_stride = _render_poses(poses, n)
-    rng, range_stride = _render_ranges(ranges, n)
-    ws, bufs = _icp_buffers(n, cap, xyz.device, workspace, stats, sums29, residuals)
-    gates = _icp_robust_buffers("icp_points_joint", frame_normals, depth.shape, gate_counts, xyz.device)
-    photo = _icp_joint_buffers("icp_points_joint", list_gray, frame_gray, depth.shape, cap, photo_residuals, photo_counts, xyz.device)
-    _check(lib().vors_icp_points_joint(n, Batch._dp(xyz), Batch._dp(normals), Batch._dp(list_gray), Batch._dp(list_counts), cap, rng, range_stride,
-                                       Batch._dp(poses), pose_stride, Batch._dp(depth), Batch._dp(frame_gray), _ptr(k), depth.shape[1],
-                                       depth.shape[2], float(depth_scale), float(dist_m), float(damping), float(step_eps), int(iters),
-                                       int(min_points), Batch._dp(frame_normals), float(min_cos), float(huber_m), float(photo_scale_m),
-                                       float(photo_huber_grey), Batch._dp(ws), *[Batch._dp(t) for t in bufs], Batch._dp(gates),
-                                       *[Batch._dp(t) for t in photo], Batch._stream()))
-    return dict(_icp_result(bufs, stats, sums29, residuals),
-                **_result(("gate_counts", _asked(gate_counts), gates), ("photo_residuals", _asked(photo_residuals), photo[0]),
-                          ("photo_counts", _asked(photo_counts), photo[1])))
+    return _icp_device("icp_points_joint", xyz, normals, list_counts, depth, cam5, depth_scale, poses, dist_m, damping, step_eps, iters, min_points,
+                       ranges, workspace, stats, sums29, residuals, (frame_normals, min_cos, huber_m, gate_counts),
+                       (list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals, photo_counts))
 
 
 def icp_points_joint_host(xyz, normals, list_gray, depth, frame_gray, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8,
@@ -2090,36 +2062,8 @@ def icp_points_joint_host(xyz, normals, list_gray, depth, frame_gray, cam5, dept
     arguments, list_gray [capacity] uint8 and frame_gray [rows, cols] uint8 (None only with photo_scale_m 0), photo_scale_m,
     photo_huber_grey -> icp_points_robust_host()'s dict, "photo_residuals" [capacity] float32 (`photo_residuals`: an array to write
     into, None = one filled with NaN) and "photo_counts" [2] uint32."""
-    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-    d = np.ascontiguousarray(depth, np.uint16)
-    k = np.ascontiguousarray(cam5, np.float32)
-    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
-    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
-    fn = None if frame_normals is None else np.ascontiguousarray(frame_normals, np.float32)
-    lg = None if list_gray is None else np.ascontiguousarray(list_gray, np.uint8).reshape(-1)
-    fg = None if frame_gray is None else np.ascontiguousarray(frame_gray, np.uint8)
-    if (len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,))
-            or (fn is not None and fn.shape != d.shape + (3,)) or (lg is not None and len(lg) != len(p)) or (fg is not None and fg.shape != d.shape)):
-        raise VorsError("icp_points_joint_host: xyz and normals [capacity, 3], list_gray [capacity] or None, depth [rows, cols], frame_gray "
-                        "[rows, cols] or None, cam5 [5], pose7 [7], range2 [2] or None, frame_normals [rows, cols, 3] or None")
-    out = {}
-    for name, given in (("residuals", residuals), ("photo_residuals", photo_residuals)):
-        if given is None:
-            given = np.full(len(p), np.nan, np.float32)
-        elif given.dtype != np.float32 or given.shape != (len(p),) or not given.flags.c_contiguous:
-            raise VorsError(f"icp_points_joint_host: {name} must be a contiguous float32 array ({len(p)},)")
-        out[name] = given
-    stats = np.zeros(1, ICP_STATS_DTYPE)
-    out.update(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), gate_counts=np.zeros(ICP_GATE_COUNTS, np.uint32),
-               photo_counts=np.zeros(ICP_PHOTO_COUNTS, np.uint32))
-    _check(lib().vors_icp_points_joint_host(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, _ptr(lg) if lg is not None and len(lg) else None,
-                                            len(p) if count is None else int(count), len(p), _ptr(rng), _ptr(pose), _ptr(d), _ptr(fg), _ptr(k),
-                                            d.shape[0], d.shape[1], float(depth_scale), float(dist_m), float(damping), float(step_eps), int(iters),
-                                            int(min_points), _ptr(fn), float(min_cos), float(huber_m), float(photo_scale_m),
-                                            float(photo_huber_grey), _ptr(out["pose"]), _ptr(stats), _ptr(out["sums29"]), _ptr(out["residuals"]),
-                                            _ptr(out["gate_counts"]), _ptr(out["photo_residuals"]), _ptr(out["photo_counts"])))
-    return out
+    return _icp_host("icp_points_joint_host", xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping, step_eps, iters, min_points, count,
+                     range2, residuals, (frame_normals, min_cos, huber_m), (list_gray, frame_gray, photo_scale_m, photo_huber_grey, photo_residuals))
 
 
 def icp_points_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping=0.0, step_eps=1e-5, iters=8, min_points=6, count=None,
@@ -2129,25 +2073,8 @@ def icp_points_host(xyz, normals, depth, cam5, depth_scale, pose7, dist_m, dampi
     structured scalar of ICP_STATS_DTYPE), "sums29" [29] float32, "residuals" [capacity] float32 with only the ranks of the clipped range
     written (`residuals`: an array to write into, None = one filled with NaN). count = the list's count (None = capacity; above it:
     clipped), range2 = (first, count) or None."""
-    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
-    nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
-    d = np.ascontiguousarray(depth, np.uint16)
-    k = np.ascontiguousarray(cam5, np.float32)
-    pose = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
-    rng = None if range2 is None else np.ascontiguousarray(range2, np.uint32)
-    if len(p) != len(nn) or d.ndim != 2 or k.shape != (5,) or (pose is not None and pose.shape != (7,)) or (rng is not None and rng.shape != (2,)):
-        raise VorsError("icp_points_host: xyz and normals [capacity, 3], depth [rows, cols], cam5 [5], pose7 [7], range2 [2] or None")
-    if residuals is None:
-        residuals = np.full(len(p), np.nan, np.float32)
-    elif residuals.dtype != np.float32 or residuals.shape != (len(p),) or not residuals.flags.c_contiguous:
-        raise VorsError(f"icp_points_host: residuals must be a contiguous float32 array ({len(p)},)")
-    stats = np.zeros(1, ICP_STATS_DTYPE)
-    out = dict(pose=np.zeros(7, np.float32), stats=stats[0], sums29=np.zeros(29, np.float32), residuals=residuals)
-    _check(lib().vors_icp_points_host(_ptr(p) if len(p) else None, _ptr(nn) if len(nn) else None, len(p) if count is None else int(count), len(p),
-                                      _ptr(rng), _ptr(pose), _ptr(d), _ptr(k), d.shape[0], d.shape[1], float(depth_scale), float(dist_m),
-                                      float(damping), float(step_eps), int(iters), int(min_points), _ptr(out["pose"]), _ptr(stats),
-                                      _ptr(out["sums29"]), _ptr(residuals)))
-    return out
+    return _icp_host("icp_points_host", xyz, normals, depth, cam5, depth_scale, pose7, dist_m, damping, step_eps, iters, min_points, count, range2,
+                     residuals)
 
 
 def ref_sincos(x):
