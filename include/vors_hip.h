@@ -130,7 +130,10 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_icp_points_joint_host, vors_trackers_icp_map_joint, VORS_ICP_PHOTO_COUNTS, likewise; + vors_icp_condition,
                               *    vors_icp_condition_from_sums, vors_trackers_enable_map_icp_joint, vors_trackers_map_icp_joint,
                               *    vors_tracker_enable_map_icp_joint, vors_tracker_read_map_icp_joint, vors_map_icp_verdict_joint_host,
-                              *    vors_map_icp_joint_params, vors_map_icp_joint_record, VORS_MAP_ICP_CONDITION, likewise) */
+                              *    vors_map_icp_joint_params, vors_map_icp_joint_record, VORS_MAP_ICP_CONDITION, likewise;
+                              *    + vors_trackers_enable_map_voxel_stats, vors_trackers_map_voxel_stats, vors_trackers_map_voxel_means,
+                              *    vors_tracker_enable_map_voxel_stats, vors_tracker_read_map_voxel_stats, vors_tracker_map_voxel_means,
+                              *    vors_voxel_means, vors_voxel_means_host, vors_voxel_stats_host, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -182,6 +185,20 @@ vors_status vors_tracker_enable_map_voxels(vors_tracker* t, float voxel_m, int t
 /* The filter's two counters (vors_trackers_map_voxels, below) to the host, each nullable; synchronises. Filter not enabled:
  * VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, uint32_t* overflow);
+/* The voxels' statistics of vors_trackers_enable_map_voxel_stats (below) for the single sequence: same refusals. Legal after
+ * vors_tracker_enable_map_voxels, before vors_tracker_enable_map_normals and until the first vors_tracker_track (refused after it and
+ * when repeated). Like vors_tracker_enable_map_voxels THIS CALL RESETS THE MAP and emits keyframe 0 again, now counted. */
+vors_status vors_tracker_enable_map_voxel_stats(vors_tracker* t);
+/* The statistics so far to HOST buffers, each nullable; synchronises. sums [capacity][4] int64, obs [capacity][2]: the first
+ * min(total, capacity, the handle's capacity) ranks, rank for rank those of vors_tracker_read_map. Negative capacity or statistics not
+ * enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map_voxel_stats(vors_tracker* t, int capacity, int64_t* sums, uint32_t* obs);
+/* The averaged list of vors_trackers_map_voxel_means (below) for the single sequence, to HOST buffers, each nullable but at least one
+ * required; synchronises. xyz_mean [capacity][3], gray_mean [capacity]: the first min(total, capacity, the handle's capacity) ranks;
+ * *kept counts the passing ranks of the whole clipped list. The handle keeps no device staging for it: the statistics are read back and
+ * resolved by vors_voxel_means_host, the text of the device pass, so the bits are those of the N = 1 handle. */
+vors_status vors_tracker_map_voxel_means(vors_tracker* t, uint32_t min_count, uint32_t min_span, int capacity, float* xyz_mean,
+                                         uint8_t* gray_mean, uint32_t* kept);
 /* The rendering of vors_trackers_render_map (below) for the single sequence, its N = 1 case, to HOST buffers; synchronises. pose7 (HOST,
  * nullable): camera -> world, NULL = the current frame's pose as the device holds it. range2 (HOST, nullable): (first, count) of the ranks
  * to render, NULL = the whole map. zkey / depth / gray [rows_l * cols_l] and counts [VORS_RENDER_COUNTS] are each nullable (zkey too: the
@@ -346,6 +363,35 @@ vors_status vors_trackers_enable_map_voxels(vors_trackers* t, float voxel_m, int
  * nullable: d_occupied = claimed table entries of a sequence = its distinct voxels so far (== d_counts while it has not overflowed),
  * d_overflow = non-zero once the sequence has overflowed. Filter not enabled: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_map_voxels(const vors_trackers* t, const uint32_t** d_occupied, const uint32_t** d_overflow);
+/* STATISTICS OF THE MAP'S VOXELS (opt-in on top of the voxel filter; without this call nothing changes: no launch, no allocation, no
+ * kernel argument on any existing path). The map's own lists, counts, segments and normals keep exactly their bits; the statistics live
+ * in arrays of their own, rank-aligned with the lists. Per sequence and rank r < min(total, capacity): let f be the stored xyz of rank r
+ * (the voxel's first point) and P(r) every point of every keyframe emitted so far that passes the map's keep rule (min_weight) and whose
+ * voxel key (vors_voxel_keys, of the world point the map would store) equals f's; the first point itself is in P(r). Then
+ *   sums[r][a] = sum over P(r) of (int64) rintf(((w_a - f_a) / voxel_m) * 1048576.0f), a = x, y, z: an f32 subtraction, an IEEE f32
+ *                division, an exact multiplication, round-half-even. |q_a| stays near 2^20, so 2^32 observations fit below 2^53;
+ *   sums[r][3] = sum over P(r) of the u8 grey the map would store;
+ *   obs[r]     = {|P(r)| (wraps at 2^32), the highest segment index — the keyframe's index among the sequence's keyframes — of a
+ *                contributor}; the rank's own segment is the lowest, so the difference is the span over which the voxel was re-observed.
+ * The sums are integers accumulated with integer atomics, so they do not depend on scheduling, on the other sequences, on the stream or
+ * on table_slots. A voxel whose rank is at or beyond capacity accumulates nothing. From the keyframe at which a sequence overflows its
+ * table its statistics are unspecified like the rest of its map; every store stays inside its buffers. vors_trackers_init zeroes
+ * everything on the stream. Per emission the filter's WRITE launch is replaced by one that also records ranks, and one launch is added.
+ * Legal after vors_trackers_enable_map_voxels and before vors_trackers_init, once; VORS_ERR_INVALID_ARGUMENT otherwise and for a NULL
+ * handle, with nothing allocated and nothing enqueued. The call allocates, as part of vors_trackers_workspace_bytes' figure and freed
+ * with the handle, n * (4 * table_slots + 40 * capacity) bytes; no later call allocates. */
+vors_status vors_trackers_enable_map_voxel_stats(vors_trackers* t);
+/* DEVICE pointers, owned by the handle and valid for its life, contents valid in stream order after the last init / track, each
+ * nullable: d_sums [n][capacity][4] int64, d_obs [n][capacity][2] u32. Statistics not enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map_voxel_stats(const vors_trackers* t, const int64_t** d_sums, const uint32_t** d_obs);
+/* THE AVERAGED MAP: vors_voxel_means (section 2d) on the handle's own lists and statistics, with the handle's voxel_m. The first segment
+ * of a rank is found inside the pass by a binary search over the `first` of the sequence's segment records (no plane of its own, no
+ * launch more); a rank of a keyframe beyond max_keyframes has no record and takes the last recorded segment. Outputs (DEVICE, each
+ * nullable, at least one required) as in vors_voxel_means. Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: NULL handle,
+ * statistics not enabled, a call before vors_trackers_init, no output at all, misaligned outputs, a stream of another device. The pass
+ * reads the map only, writes the caller's arrays only and allocates nothing; enqueued on hip_stream, NOT synchronised. */
+vors_status vors_trackers_map_voxel_means(vors_trackers* t, uint32_t min_count, uint32_t min_span, float* d_xyz_mean /* nullable */,
+                                          uint8_t* d_gray_mean /* nullable */, uint32_t* d_kept /* nullable */, void* hip_stream);
 /* THE KEYFRAME MAP SEEN FROM A POSE: vors_render_points (section 2c) on the handle's own map — its lists, its counters, the intrinsics and
  * the shape of pyramid level `level` (rows_l x cols_l), the handle's depth_scale. d_poses7 (DEVICE, nullable): one camera -> world pose per
  * sequence, pose_stride_bytes apart (0 = 28); NULL = every sequence's CURRENT FRAME pose, read on the device from the handle's pose table
@@ -862,6 +908,38 @@ vors_status vors_render_points(int n, const float* d_xyz, const uint8_t* d_list_
 vors_status vors_render_points_host(const float* xyz, const uint8_t* list_gray, uint32_t count, int capacity, const uint32_t range2[2],
                                     const float cam5[5], int rows, int cols, float depth_scale, const float pose7[7], int footprint,
                                     uint64_t* zkey, uint16_t* depth, uint8_t* gray, uint32_t counts[VORS_RENDER_COUNTS]);
+/* THE AVERAGED LIST OF VOXEL STATISTICS (vors_trackers_enable_map_voxel_stats, section 2), device-resident and handle-free,
+ * in the shape this section's and the next sections' passes take: n lists d_xyz [n][capacity][3] / d_list_counts [n] with statistics
+ * d_sums [n][capacity][4] int64 / d_obs [n][capacity][2] u32 — the pointers of vors_trackers_map and vors_trackers_map_voxel_stats —
+ * resolved per rank r below min(count, capacity), with f = d_xyz[r]:
+ *   mean_a = f_a + voxel_m * (float)((double)sums_a / ((double)count * 1048576.0)), the division and conversions in IEEE f64;
+ *   grey   = (uint8)((2 * sum_grey + count) / (2 * count)) in integers.
+ * A rank with count < max(min_count, 1), or with last_segment - first_segment < min_span, gets a NaN triple (bits 0x7FC00000) and grey 0.
+ * The candidate test of vors_render_points and every ICP gate are written so that NaN fails: such a rank is skipped by every consumer
+ * without compaction, and the list stays rank-aligned with vors_trackers_map_normals. d_first_segment_of_rank [n][capacity] u32
+ * (nullable): the segment index of every rank's own keyframe; NULL = no span test, and min_span must then be 0. Nothing of the map's
+ * grey list is read (the mean grey comes from the sums). Outputs, each nullable, at least one required: d_xyz_mean [n][capacity][3] f32,
+ * d_gray_mean [n][capacity] u8 — ranks at or beyond the clipped count are not written — and d_kept [n] u32, the passing ranks.
+ * VORS_ERR_INVALID_ARGUMENT, nothing enqueued: n outside 1..65535, a NULL list, no output at all, d_sums not 8-byte aligned, a 4-byte
+ * array not 4-byte aligned, voxel_m not finite or <= 0, capacity < 1, min_span != 0 without d_first_segment_of_rank. The call allocates
+ * nothing; the clear of d_kept and one launch are enqueued on hip_stream, NOT synchronised. */
+vors_status vors_voxel_means(int n, const float* d_xyz, const uint32_t* d_list_counts, int capacity, const int64_t* d_sums,
+                             const uint32_t* d_obs, float voxel_m, uint32_t min_count, uint32_t min_span,
+                             const uint32_t* d_first_segment_of_rank /* nullable */, float* d_xyz_mean /* nullable */,
+                             uint8_t* d_gray_mean /* nullable */, uint32_t* d_kept /* nullable */, void* hip_stream);
+/* The same resolve for ONE list in HOST memory (no GPU): the text the kernel runs, bit for bit. Same refusals. */
+vors_status vors_voxel_means_host(const float* xyz, uint32_t count, int capacity, const int64_t* sums, const uint32_t* obs, float voxel_m,
+                                  uint32_t min_count, uint32_t min_span, const uint32_t* first_segment_of_rank /* nullable */,
+                                  float* xyz_mean /* nullable */, uint8_t* gray_mean /* nullable */, uint32_t* kept /* nullable */);
+/* The statistics themselves for ONE unfiltered list U in HOST memory (no GPU): what the device map of a sequence holds after the
+ * keyframes that make up U. xyz [n][3], gray [n], segment_of [n] (nullable = all 0): U's entries and the segment index of each. The
+ * filtered list is U at the first occurrence of every voxel key, in U's order: *total (nullable) its unclipped length, first_index
+ * [min(total, capacity)] (nullable) the index in U of every rank's first point. sums [capacity][4] and obs [capacity][2] are required
+ * and written whole (zeros beyond the filtered list). Refused: a NULL list with n > 0, NULL sums or obs, voxel_m not finite or <= 0,
+ * capacity < 1. */
+vors_status vors_voxel_stats_host(const float* xyz, const uint8_t* gray, const uint32_t* segment_of /* nullable */, uint32_t n, float voxel_m,
+                                  int capacity, uint32_t* total /* nullable */, uint32_t* first_index /* nullable */, int64_t* sums,
+                                  uint32_t* obs);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 2d. SURFACE NORMALS OF DEPTH MAPS, device-resident and handle-free (the reference has no normals): per pixel of a level-0

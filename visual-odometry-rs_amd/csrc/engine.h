@@ -370,6 +370,13 @@ struct PointCloudVoxelArgs {
     uint32_t* occupied = nullptr;   // [seq] claimed entries
     uint32_t* overflow = nullptr;   // [seq] sticky: a point found no entry in table_slots probes
 };
+// The statistics of that filter's voxels (vors_trackers_enable_map_voxel_stats), rank-aligned with the lists. Only the two
+// kernels the statistics add get this block (the WRITE that also records ranks, and ACCUMULATE); every other kernel keeps its arguments.
+struct PointCloudVoxelStatsArgs {
+    uint32_t* rank_of = nullptr;    // [seq][table_slots] rank of the voxel of a table entry; all ones: none (yet, or beyond the sweep)
+    long long* sums = nullptr;      // [seq][capacity][4] fixed-point offsets x, y, z (lie.h voxel_offset_q) and grey
+    uint32_t* obs = nullptr;        // [seq][capacity][2] observations (wraps at 2^32), highest contributing segment index
+};
 // The keyframe map of the lock-step trackers (vors_trackers_enable_map): the point-cloud pass of one level for the SELECTED sequences
 // (Geom::sel_list, null = all), appended to per-sequence lists with one segment record per keyframe. Every buffer is the handle's own.
 struct PointCloudAppendCall : LmScene {
@@ -388,6 +395,7 @@ struct PointCloudAppendCall : LmScene {
     uint32_t* ws;               // [seq][ws_chunks] kept points per chunk of the keyframe being appended
     int ws_chunks;
     PointCloudVoxelArgs voxels; // table == null: no voxel filter, and the launches are exactly the ones above
+    PointCloudVoxelStatsArgs voxel_stats;  // rank_of == null: no statistics, and the launches are exactly the filter's
 };
 // What its kernels get.
 struct PointCloudAppendArgs {
@@ -736,8 +744,32 @@ void launch_lm_point_cloud(const Geom& g, const PointCloudCall& call, hipStream_
 // The same pass as MASKED launches that APPEND (the keyframe map of vors_trackers; product_kernels.hip point_cloud_append_kernel,
 // point_cloud_commit_kernel): count, write behind the sequence's running total, commit the segment record and the totals. call.n_seq is
 // the extent of the pair dimension (all sequences); only the sequences of g.sel_list (null: all) are touched. With call.voxels.table set
-// the emission is CLAIM, COUNT, WRITE of point_cloud_append_voxel_kernel and the same commit.
+// the emission is CLAIM, COUNT, WRITE of point_cloud_append_voxel_kernel and the same commit. With call.voxel_stats.rank_of set as well,
+// WRITE is point_cloud_append_voxel_stats_kernel's, which records ranks, and its ACCUMULATE follows in front of the commit.
 void launch_lm_point_cloud_append(const Geom& g, const PointCloudAppendCall& call, hipStream_t s);
+// The resolve of voxel statistics into an averaged list (vors_voxel_means, vors_trackers_map_voxel_means; product_kernels.hip
+// voxel_means_kernel): per rank below the clipped count lie.h voxel_mean. Handle-free: everything the kernel reads is here. The first
+// segment of a rank comes from `first_segment` (one word per rank), or from `segments` by a binary search over their `first` (the
+// handle's own map), or from nowhere (both null: no span test). Each output is nullable.
+struct VoxelMeansCall {
+    int n;                              // lists
+    const float* xyz;                   // [n][capacity][3]
+    const uint32_t* list_counts;        // [n]; a count above capacity is clipped to it
+    int capacity;
+    const long long* sums;              // [n][capacity][4]
+    const uint32_t* obs;                // [n][capacity][2]
+    float voxel_m;
+    uint32_t min_count, min_span;
+    const uint32_t* first_segment;      // [n][capacity], nullable
+    const vors_map_segment* segments;   // [n][max_keyframes], nullable
+    const uint32_t* n_segments;         // [n], with segments
+    int max_keyframes;
+    float* xyz_mean;                    // [n][capacity][3]
+    uint8_t* gray_mean;                 // [n][capacity]
+    uint32_t* kept;                     // [n]
+};
+// The clear of `kept` and one launch: enqueued on s, not synchronised, no workspace.
+void launch_voxel_means(const VoxelMeansCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

@@ -360,6 +360,45 @@ VORS_HD uint64_t voxel_key(float voxel_m, float x, float y, float z) {
     return key;
 }
 
+// Statistics of a voxel of that map (vors_trackers_enable_map_voxel_stats). The sums are FIXED POINT in 64-bit integers:
+// integer addition is associative and commutative, so a sum of these has the same bits whatever the order of arrival.
+// voxel_offset_q: one axis of an observation w relative to the voxel's first point f (the stored xyz of the rank), in units of
+// voxel_m / 2^20: an f32 subtraction, an IEEE f32 division (never a reciprocal multiply), an exact multiplication by 2^20, rintf (halves
+// to even). Bound: two points with one voxel key lie within one edge of each other on every axis, up to the rounding of the two
+// quotients, so |q| stays near 2^20 < 2^21, and 2^32 observations (the count wraps there) sum below 2^53 < 2^63: no overflow, and the
+// f64 conversion of voxel_mean is exact.
+VORS_HD int64_t voxel_offset_q(float voxel_m, float w, float f) { return (int64_t)rintf(((w - f) / voxel_m) * 1048576.0f); }
+// The resolve of one rank (vors_voxel_means, vors_voxel_means_host): centroid = f + voxel_m * (float)(sum / (count 2^20)) per axis, the
+// division and conversions in IEEE f64; grey = (2 sum + count) / (2 count) in integers (the mean rounded half up). A rank seen fewer than
+// max(min_count, 1) times, or over a span of segments last_segment - first_segment below min_span, is rejected: a NaN triple (one bit
+// pattern) and grey 0, which every consumer of a list skips. The one text host and device run.
+#define VORS_VOXEL_MEAN_NAN_BITS 0x7FC00000u
+struct VoxelMean {
+    float xyz[3];
+    uint8_t gray;
+    bool kept;
+};
+VORS_HD VoxelMean voxel_mean(float voxel_m, const float* f, const int64_t* sums4, uint32_t count, uint32_t last_segment, uint32_t first_segment,
+                             uint32_t min_count, uint32_t min_span) {
+    VoxelMean o;
+    const uint32_t span = last_segment > first_segment ? last_segment - first_segment : 0u;
+    o.kept = count >= (min_count > 1u ? min_count : 1u) && span >= min_span;
+    if (!o.kept) {
+        union {
+            uint32_t u;
+            float f;
+        } nan;
+        nan.u = VORS_VOXEL_MEAN_NAN_BITS;
+        o.xyz[0] = o.xyz[1] = o.xyz[2] = nan.f;
+        o.gray = 0;
+        return o;
+    }
+    const double den = (double)count * 1048576.0;
+    for (int a = 0; a < 3; ++a) o.xyz[a] = f[a] + voxel_m * (float)((double)sums4[a] / den);
+    o.gray = (uint8_t)((2 * (uint64_t)sums4[3] + count) / (2 * (uint64_t)count));
+    return o;
+}
+
 // One LM step: lm_optimizer.rs:123-136.
 VORS_HD bool lm_step(const float* h36, const float* g6, const Iso& model, float lm_coef, Iso* out) {
     float delta[6];

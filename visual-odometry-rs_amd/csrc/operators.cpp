@@ -1,6 +1,8 @@
 // Everything of the C ABI that is not a handle: last error, device queries and self-checks, the LM operators on explicit observations
 // (vors_lm_*), Lie helpers and the synthetic scenes.
 #include <cstring>
+#include <unordered_map>
+#include <vector>
 
 #include "host_common.h"
 
@@ -925,6 +927,116 @@ void vors_voxel_keys(float voxel_m, const float* xyz, int n, uint64_t* keys_out)
     const bool ok = voxel_m > 0.0f && voxel_m <= 3.4028234663852886e38f;
     for (int i = 0; i < n; ++i) keys_out[i] = ok ? voxel_key(voxel_m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]) : VORS_VOXEL_NONE;
 }
+// The statistics of the map's voxels for ONE unfiltered list U (vors_trackers_enable_map_voxel_stats): what the device map of a sequence
+// holds after the keyframes that make up U, by lie.h voxel_key / voxel_offset_q, the texts the device kernels run. Ranks are handed out
+// in U's order of first occurrence of a key, which is the order of the filtered list.
+vors_status vors_voxel_stats_host(const float* xyz, const uint8_t* gray, const uint32_t* segment_of, uint32_t n, float voxel_m, int capacity,
+                                  uint32_t* total, uint32_t* first_index, int64_t* sums, uint32_t* obs) {
+    if (n && (!xyz || !gray)) return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_stats_host: a list (xyz, gray) is NULL");
+    if (!sums || !obs) return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_stats_host: sums or obs is NULL");
+    if (!(voxel_m > 0.0f) || !(voxel_m <= 3.4028234663852886e38f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_stats_host: voxel size voxel_m must be finite and > 0");
+    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_stats_host: capacity must be >= 1");
+    std::memset(sums, 0, (size_t)capacity * 4 * sizeof(int64_t));
+    std::memset(obs, 0, (size_t)capacity * 2 * sizeof(uint32_t));
+    std::unordered_map<uint64_t, uint32_t> rank_of;    // key -> rank
+    std::vector<uint32_t> first;                       // rank < capacity -> index in U of the voxel's first point
+    uint32_t next = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* w = xyz + 3 * (size_t)i;
+        const uint64_t key = voxel_key(voxel_m, w[0], w[1], w[2]);
+        if (key == VORS_VOXEL_NONE) continue;
+        auto it = rank_of.find(key);
+        if (it == rank_of.end()) {
+            it = rank_of.emplace(key, next).first;
+            if (next < (uint32_t)capacity) first.push_back(i);
+            next += 1;
+        }
+        const uint32_t r = it->second;
+        if (r >= (uint32_t)capacity) continue;
+        const float* f = xyz + 3 * (size_t)first[r];
+        for (int a = 0; a < 3; ++a) sums[4 * (size_t)r + a] += voxel_offset_q(voxel_m, w[a], f[a]);
+        sums[4 * (size_t)r + 3] += gray[i];
+        obs[2 * (size_t)r] += 1u;
+        const uint32_t seg = segment_of ? segment_of[i] : 0u;
+        if (seg > obs[2 * (size_t)r + 1]) obs[2 * (size_t)r + 1] = seg;
+    }
+    if (total) *total = next;
+    if (first_index)
+        for (size_t r = 0; r < first.size(); ++r) first_index[r] = first[r];
+    return VORS_OK;
+}
+
+// The resolve of the statistics (vors_voxel_means, vors_voxel_means_host): the refusals both share, the device entry
+// (product_kernels.hip voxel_means_kernel) and the host entry, which runs the kernel's own text (lie.h voxel_mean).
+static vors_status voxel_means_refusals(const char* who, const void* xyz, const void* sums, const void* obs, float voxel_m, int capacity,
+                                        uint32_t min_span, const void* first_segment, const void* xyz_mean, const void* gray_mean,
+                                        const void* kept) {
+    const std::string w(who);
+    if (!xyz || !sums || !obs) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, sums, obs) is NULL");
+    if (!xyz_mean && !gray_mean && !kept) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": no output at all (xyz_mean, gray_mean and kept are NULL)");
+    if (!(voxel_m > 0.0f) || !(voxel_m <= 3.4028234663852886e38f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": voxel size voxel_m must be finite and > 0");
+    if (capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
+    if (!first_segment && min_span != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_span must be 0 without the first segment of every rank (there is no span to test)");
+    if ((uintptr_t)sums % 8 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": sums must be 8-byte aligned");
+    if ((uintptr_t)xyz % 4 != 0 || (uintptr_t)obs % 4 != 0 || (uintptr_t)first_segment % 4 != 0 || (uintptr_t)xyz_mean % 4 != 0 ||
+        (uintptr_t)kept % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": xyz, obs, first_segment_of_rank, xyz_mean and kept must be 4-byte aligned");
+    return VORS_OK;
+}
+
+vors_status vors_voxel_means(int n, const float* d_xyz, const uint32_t* d_list_counts, int capacity, const int64_t* d_sums, const uint32_t* d_obs,
+                             float voxel_m, uint32_t min_count, uint32_t min_span, const uint32_t* d_first_segment_of_rank, float* d_xyz_mean,
+                             uint8_t* d_gray_mean, uint32_t* d_kept, void* hip_stream) {
+    if (n < 1 || n > 65535) return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_means: n must be in 1..65535");
+    if (!d_list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_means: a list (d_list_counts) is NULL");
+    if ((uintptr_t)d_list_counts % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, "voxel_means: d_list_counts must be 4-byte aligned");
+    vors_status st = voxel_means_refusals("voxel_means", d_xyz, d_sums, d_obs, voxel_m, capacity, min_span, d_first_segment_of_rank, d_xyz_mean,
+                                          d_gray_mean, d_kept);
+    if (st != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    VoxelMeansCall call{};
+    call.n = n;
+    call.xyz = d_xyz;
+    call.list_counts = d_list_counts;
+    call.capacity = capacity;
+    call.sums = reinterpret_cast<const long long*>(d_sums);
+    call.obs = d_obs;
+    call.voxel_m = voxel_m;
+    call.min_count = min_count;
+    call.min_span = min_span;
+    call.first_segment = d_first_segment_of_rank;
+    call.xyz_mean = d_xyz_mean;
+    call.gray_mean = d_gray_mean;
+    call.kept = d_kept;
+    launch_voxel_means(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_voxel_means_host(const float* xyz, uint32_t count, int capacity, const int64_t* sums, const uint32_t* obs, float voxel_m,
+                                  uint32_t min_count, uint32_t min_span, const uint32_t* first_segment_of_rank, float* xyz_mean,
+                                  uint8_t* gray_mean, uint32_t* kept) {
+    vors_status st = voxel_means_refusals("voxel_means_host", xyz, sums, obs, voxel_m, capacity, min_span, first_segment_of_rank, xyz_mean,
+                                          gray_mean, kept);
+    if (st != VORS_OK) return st;
+    const uint32_t n = count < (uint32_t)capacity ? count : (uint32_t)capacity;
+    uint32_t k = 0;
+    for (uint32_t r = 0; r < n; ++r) {
+        const uint32_t* ob = obs + 2 * (size_t)r;
+        const VoxelMean m = voxel_mean(voxel_m, xyz + 3 * (size_t)r, sums + 4 * (size_t)r, ob[0], ob[1],
+                                       first_segment_of_rank ? first_segment_of_rank[r] : ob[1], min_count, min_span);
+        if (xyz_mean)
+            for (int a = 0; a < 3; ++a) xyz_mean[3 * (size_t)r + a] = m.xyz[a];
+        if (gray_mean) gray_mean[r] = m.gray;
+        k += m.kept ? 1u : 0u;
+    }
+    if (kept) *kept = k;
+    return VORS_OK;
+}
+
 void vors_camera_project(const float cam5[5], const float pose7[7], const float* xyz, int n, float* uvw_out) {
     const Intr k = intr_from_cam5(cam5);
     for (int i = 0; i < n; ++i) {

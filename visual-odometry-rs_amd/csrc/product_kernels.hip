@@ -582,6 +582,7 @@ struct CloudPts {
     uint32_t xy[G];
     float tmpl[G];
     bool kept[G];
+    uint32_t entry[G];  // VOX_OWNED_RANK only: the table entry of a kept point's voxel
 };
 // The voxel table of ONE sequence as the sweeps of its filtered emission see it (point_cloud_append_voxel_kernel, below): entry e is the
 // two words table[2 e] = voxel key (empty: all ones) and table[2 e + 1] = owner tag (unclaimed: all ones). `tag_hi` is the segment index
@@ -596,7 +597,18 @@ struct CloudVox {
     Iso pose;       // the keyframe pose: the key is taken of the world point WRITE stores
 };
 #define VOXEL_EMPTY 0xFFFFFFFFFFFFFFFFull
-enum { VOX_OFF = 0, VOX_CLAIM = 1, VOX_OWNED = 2 };
+enum { VOX_OFF = 0, VOX_CLAIM = 1, VOX_OWNED = 2, VOX_OWNED_RANK = 3, VOX_ACCUM = 4 };
+// What the two sweeps of the voxel statistics (vors_trackers_enable_map_voxel_stats; point_cloud_append_voxel_stats_kernel) see besides:
+// the sequence's rank words, sums and observation records, its list of first points, and the segment index of the keyframe being emitted.
+struct CloudVoxStats : CloudVox {
+    uint32_t* rank_of;         // [table_slots]
+    unsigned long long* sums;  // [capacity][4], two's complement
+    uint32_t* obs;             // [capacity][2]
+    const float* xyz;          // [capacity][3] the sequence's list
+    uint32_t capacity;
+    uint32_t segment;
+};
+#define VOXEL_NO_ENTRY 0xFFFFFFFFu
 __device__ __forceinline__ uint32_t voxel_hash(unsigned long long key) {  // (the 64-bit finaliser of MurmurHash3)
     key ^= key >> 33;
     key *= 0xff51afd7ed558ccdull;
@@ -644,9 +656,41 @@ __device__ __forceinline__ bool voxel_owns(const CloudVox& v, unsigned long long
     }
     return false;
 }
+// voxel_owns' probe, which says WHERE: the entry that holds `key`; VOXEL_NO_ENTRY when none does, the point has no key or the sequence
+// has overflowed. Reading only, and it gives up on the overflow word exactly as voxel_owns does.
+__device__ __forceinline__ uint32_t voxel_find(const CloudVox& v, unsigned long long key) {
+    if (key == VOXEL_EMPTY) return VOXEL_NO_ENTRY;
+    uint32_t e = voxel_hash(key) & v.mask;
+    for (uint32_t step = 0; step <= v.mask; ++step, e = (e + 1u) & v.mask) {
+        if ((step & 63u) == 0u && voxel_overflowed(v)) return VOXEL_NO_ENTRY;
+        const unsigned long long k = v.table[2 * (size_t)e];
+        if (k == key) return e;
+        if (k == VOXEL_EMPTY) return VOXEL_NO_ENTRY;
+    }
+    return VOXEL_NO_ENTRY;
+}
+// ACCUMULATE: one observation w (the world point WRITE would store) of grey `gray` into the statistics of its voxel, if the voxel has a
+// rank below the capacity. `f`, the list entry at that rank, is final: the WRITE of this or an earlier emission stored it. Integer
+// atomics only — three 64-bit additions of lie.h voxel_offset_q, one of the grey, a 32-bit addition and a 32-bit maximum —, so the
+// result has the same bits whatever the order of arrival. No thread waits for another.
+__device__ __forceinline__ void voxel_accumulate(const CloudVoxStats& v, unsigned long long key, const V3& w, uint32_t gray) {
+    const uint32_t e = voxel_find(v, key);
+    if (e == VOXEL_NO_ENTRY) return;
+    const uint32_t r = v.rank_of[e];
+    if (r >= v.capacity) return;  // (all ones included: a voxel without a stored first point accumulates nothing)
+    const float* f = v.xyz + 3 * (size_t)r;
+    unsigned long long* s = v.sums + 4 * (size_t)r;
+    atomicAdd(s + 0, (unsigned long long)voxel_offset_q(v.voxel_m, w.x, f[0]));
+    atomicAdd(s + 1, (unsigned long long)voxel_offset_q(v.voxel_m, w.y, f[1]));
+    atomicAdd(s + 2, (unsigned long long)voxel_offset_q(v.voxel_m, w.z, f[2]));
+    atomicAdd(s + 3, (unsigned long long)gray);
+    atomicAdd(v.obs + 2 * (size_t)r, 1u);
+    atomicMax(v.obs + 2 * (size_t)r + 1, v.segment);
+}
 // THRESH (the keyframe map of the trackers, point_cloud_append_kernel): the plane holds weights and a point is kept from `keep_min` on.
 // VOX (its voxel filter): after the keep rule, VOX_CLAIM enters every kept point into the table and leaves the flags alone, VOX_OWNED
-// keeps a point iff it owns its voxel. Slot of point g of a unit: the candidate lists' i and i + BLOCK, the dense sources' G i + g.
+// keeps a point iff it owns its voxel (VOX_OWNED_RANK: and notes the entry), VOX_ACCUM adds every kept point to the statistics of its
+// voxel and leaves the flags alone. Slot of point g of a unit: the candidate lists' i and i + BLOCK, the dense sources' G i + g.
 template <bool THRESH, int VOX, class Src>
 __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::Cursor& cur, int last, int cols, const uint8_t* keep, bool wide_keep,
                                             CloudPts<Src::G>& o, uint32_t keep_min, const CloudVox* vox) {
@@ -688,7 +732,11 @@ __device__ __forceinline__ void cloud_fetch(const Src& src, const typename Src::
             const V3 w = iso_transform_point(vox->pose, o.P[g]);  // (cloud_store's expression: the bits the list holds)
             const unsigned long long key = voxel_key(vox->voxel_m, w.x, w.y, w.z);
             if constexpr (VOX == VOX_CLAIM) voxel_claim(*vox, key, vox->tag_hi | slot);
-            else o.kept[g] = voxel_owns(*vox, key, vox->tag_hi | slot);
+            else if constexpr (VOX == VOX_ACCUM) voxel_accumulate(*static_cast<const CloudVoxStats*>(vox), key, w, (uint32_t)(uint8_t)(int)o.tmpl[g]);
+            else if constexpr (VOX == VOX_OWNED_RANK) {
+                o.entry[g] = voxel_find(*vox, key);
+                o.kept[g] = o.entry[g] != VOXEL_NO_ENTRY && vox->table[2 * (size_t)o.entry[g] + 1] == (vox->tag_hi | slot);
+            } else o.kept[g] = voxel_owns(*vox, key, vox->tag_hi | slot);
         }
     }
 }
@@ -766,6 +814,8 @@ __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int
                 const uint32_t rank = base + cloud_block_rank<1>(&pts.kept[g], lds, par, &total);
                 par ^= 1;
                 if (pts.kept[g] && rank < out.capacity) cloud_store(out, rank, pts.P[g], pts.xy[g], pts.tmpl[g]);
+                if constexpr (VOX == VOX_OWNED_RANK)
+                    if (pts.kept[g]) static_cast<const CloudVoxStats*>(vox)->rank_of[pts.entry[g]] = rank;
                 base += total;
             }
         } else {
@@ -775,6 +825,8 @@ __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 if (pts.kept[g] && rank < out.capacity) cloud_store(out, rank, pts.P[g], pts.xy[g], pts.tmpl[g]);
+                if constexpr (VOX == VOX_OWNED_RANK)
+                    if (pts.kept[g]) static_cast<const CloudVoxStats*>(vox)->rank_of[pts.entry[g]] = rank;
                 rank += pts.kept[g] ? 1u : 0u;
             }
             base += total;
@@ -782,7 +834,7 @@ __device__ __forceinline__ void cloud_write_sweep(const Src& src, int first, int
     }
 }
 // The pass of one workgroup, whoever launched it: the sweep over its chunk of the level — WRITE from `base` into `out`, else the count
-// STORED to ws[chunk] (VOX_CLAIM: nothing is counted) — under the keep rule THRESH and the voxel rule VOX (cloud_fetch). The kernels below
+// STORED to ws[chunk] (VOX_CLAIM, VOX_ACCUM: nothing is counted) — under the keep rule THRESH and the voxel rule VOX (cloud_fetch). The kernels below
 // are its entry points: they find the pair, the planes and, for WRITE, the base and the lists. `ws` is the pair's row of the workspace.
 template <bool DENSE, bool WRITE, bool THRESH, int VOX>
 __device__ __forceinline__ void point_cloud_body(const Geom& g, int pair, const uint8_t* kf0, const uint8_t* kfu, const uint16_t* kf_depth,
@@ -799,7 +851,7 @@ __device__ __forceinline__ void point_cloud_body(const Geom& g, int pair, const 
         if constexpr (WRITE) cloud_write_sweep<THRESH, VOX>(src, cut.first, cut.last, cols, keep, wide_keep, base, out, lds, keep_min, vox);
         else n[0] = cloud_count_sweep<THRESH, VOX>(src, cut.first, cut.last, cols, keep, wide_keep, keep_min, vox);
     });
-    if constexpr (!WRITE && VOX != VOX_CLAIM) block_counts<1, RMAPS_BLOCK>(n, lds, CountsStore{ws + chunk});
+    if constexpr (!WRITE && VOX != VOX_CLAIM && VOX != VOX_ACCUM) block_counts<1, RMAPS_BLOCK>(n, lds, CountsStore{ws + chunk});
 }
 template <bool DENSE, bool WRITE>
 __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
@@ -937,6 +989,48 @@ __global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_voxel_kernel(G
     point_cloud_body<DENSE, WRITE, true, VOX>(g, seq, kf0, kfu, kf_depth, rec, a.lvl, a.chunk_points, keep, a.wide_keep != 0, (uint32_t)a.keep_min, ws,
                                               base, out, &vox, lds);
 }
+// VOXEL STATISTICS (vors_trackers_enable_map_voxel_stats; a sibling entry point, so that the three kernels above keep their
+// arguments and their instructions): per rank of the filtered list, fixed-point sums of every observation of its voxel relative to the
+// stored first point, the sum of their greys, their number and the highest segment index among them. The emission becomes
+//   CLAIM, COUNT   as above
+//   WRITE          <VOX_OWNED_RANK>, in the place of <VOX_OWNED>: the same sweep, which also stores rank_of[entry] = rank for every owned
+//                  point it ranks, whether the rank is below the capacity or not. A workgroup whose base has reached the capacity stops
+//                  as before, so an entry it never ranks keeps all ones — which reads as a rank beyond every capacity.
+//   ACCUMULATE     <VOX_ACCUM>: CLAIM's sweep over the same points; each probes read-only (the table is final), reads its voxel's rank
+//                  and adds itself to the rank's statistics (voxel_accumulate). The first point of a voxel counts itself.
+//   COMMIT         as above, behind ACCUMULATE: the segment index all sweeps read is still n_segments[seq].
+template <bool DENSE, bool WRITE, int VOX>
+__global__ __launch_bounds__(RMAPS_BLOCK) void point_cloud_append_voxel_stats_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __restrict__ curu,
+                                                                                     const uint8_t* __restrict__ kf0, const uint8_t* __restrict__ kfu,
+                                                                                     const uint16_t* __restrict__ kf_depth, Records rec,
+                                                                                     PointCloudAppendArgs a, PointCloudVoxelArgs v,
+                                                                                     PointCloudVoxelStatsArgs st) {
+    static_assert((WRITE && VOX == VOX_OWNED_RANK) || (!WRITE && VOX == VOX_ACCUM), "WRITE records ranks, ACCUMULATE is a counting sweep");
+    __shared__ uint32_t lds[2 * PCLOUD_WAVES];
+    const int seq = select_pair(g, blockIdx.y);
+    if (seq < 0) return;
+    const uint8_t* keep = a.weight ? a.weight + (size_t)seq * g.S0 : nullptr;  // (set at level 0 only)
+    uint32_t* ws = a.ws + (size_t)seq * a.ws_chunks;
+    uint32_t base = 0;
+    CloudOut out{};
+    if constexpr (WRITE) out = cloud_out_append(a, seq, ws, blockIdx.x, &base);
+    CloudVoxStats vox;
+    vox.table = v.table + 2 * (size_t)seq * v.table_slots;
+    vox.occupied = v.occupied + seq;
+    vox.overflow = v.overflow + seq;
+    vox.mask = v.table_slots - 1u;
+    vox.voxel_m = v.voxel_m;
+    vox.segment = a.n_segments[seq];
+    vox.tag_hi = (unsigned long long)vox.segment << 32;
+    vox.pose = iso_uniform(iso_load(a.kf_poses + 7 * (size_t)seq));
+    vox.rank_of = st.rank_of + (size_t)seq * v.table_slots;
+    vox.sums = reinterpret_cast<unsigned long long*>(st.sums) + 4 * (size_t)seq * a.capacity;
+    vox.obs = st.obs + 2 * (size_t)seq * a.capacity;
+    vox.xyz = a.xyz + 3 * (size_t)seq * a.capacity;
+    vox.capacity = (uint32_t)a.capacity;
+    point_cloud_body<DENSE, WRITE, true, VOX>(g, seq, kf0, kfu, kf_depth, rec, a.lvl, a.chunk_points, keep, a.wide_keep != 0, (uint32_t)a.keep_min, ws,
+                                              base, out, &vox, lds);
+}
 __global__ __launch_bounds__(64) void point_cloud_commit_kernel(Geom g, PointCloudAppendArgs a, int n, int chunks) {
     const int k = blockIdx.x * 64 + threadIdx.x;
     if (k >= n) return;
@@ -972,13 +1066,75 @@ void launch_lm_point_cloud_append(const Geom& g_in, const PointCloudAppendCall& 
             const PointCloudVoxelArgs& v = call.voxels;
             launch_on_scene(point_cloud_append_voxel_kernel<DENSE, false, VOX_CLAIM>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
             launch_on_scene(point_cloud_append_voxel_kernel<DENSE, false, VOX_OWNED>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
-            launch_on_scene(point_cloud_append_voxel_kernel<DENSE, true, VOX_OWNED>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
+            if (call.voxel_stats.rank_of) {
+                const PointCloudVoxelStatsArgs& st = call.voxel_stats;
+                launch_on_scene(point_cloud_append_voxel_stats_kernel<DENSE, true, VOX_OWNED_RANK>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v, st);
+                launch_on_scene(point_cloud_append_voxel_stats_kernel<DENSE, false, VOX_ACCUM>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v, st);
+            } else {
+                launch_on_scene(point_cloud_append_voxel_kernel<DENSE, true, VOX_OWNED>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a, v);
+            }
         } else {
             launch_on_scene(point_cloud_append_kernel<DENSE, false>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
             launch_on_scene(point_cloud_append_kernel<DENSE, true>, dim3(chunks, n), dim3(RMAPS_BLOCK), 0, s, g, call, a);
         }
     });
     hipLaunchKernelGGL(point_cloud_commit_kernel, dim3((n + 63) / 64), dim3(64), 0, s, g, a, n, chunks);
+}
+
+
+// ------------------------------------------------------------------------------------------------------------
+// vors_voxel_means / vors_trackers_map_voxel_means: the statistics above resolved into an averaged list, rank for rank (lie.h voxel_mean,
+// the text vors_voxel_means_host runs). One thread per rank below the clipped count, grid y = list; a rejected rank gets a NaN triple
+// and grey 0, nothing is compacted. The first segment of a rank: one word per rank, or a binary search for the last segment whose
+// `first` is <= the rank (an empty segment shares its `first` with its successor, which the search prefers; a rank of a keyframe beyond
+// max_keyframes has no record and takes the last recorded one), or none. `kept`: a shuffle reduction and one 32-bit atomicAdd per wavefront into
+// a cleared word — an integer sum. No LDS.
+// ------------------------------------------------------------------------------------------------------------
+#define VMEANS_BLOCK 256
+__global__ __launch_bounds__(VMEANS_BLOCK) void voxel_means_kernel(VoxelMeansCall c) {
+    const int i = blockIdx.y;
+    const uint32_t count = c.list_counts[i], n = count < (uint32_t)c.capacity ? count : (uint32_t)c.capacity;
+    const size_t row = (size_t)i * (size_t)c.capacity;
+    const uint32_t n_seg = c.segments ? min(c.n_segments[i], (uint32_t)c.max_keyframes) : 0u;
+    const vors_map_segment* seg = c.segments ? c.segments + (size_t)i * c.max_keyframes : nullptr;
+    uint32_t kept = 0;
+    for (uint32_t r = blockIdx.x * VMEANS_BLOCK + threadIdx.x; r < n; r += gridDim.x * VMEANS_BLOCK) {
+        const uint32_t* ob = c.obs + 2 * (row + r);
+        uint32_t first_segment = ob[1];  // (no source: span 0)
+        if (c.first_segment) first_segment = c.first_segment[row + r];
+        else if (n_seg) {
+            uint32_t lo = 0, hi = n_seg;  // the last index in [0, n_seg) with first <= r; segment 0 has first 0
+            while (hi - lo > 1u) {
+                const uint32_t mid = lo + (hi - lo) / 2u;
+                if (seg[mid].first <= r) lo = mid;
+                else hi = mid;
+            }
+            first_segment = lo;
+        }
+        const float* f = c.xyz + 3 * (row + r);
+        const long long* sp = c.sums + 4 * (row + r);
+        const float f3[3] = {f[0], f[1], f[2]};
+        const int64_t s4[4] = {sp[0], sp[1], sp[2], sp[3]};
+        const VoxelMean m = voxel_mean(c.voxel_m, f3, s4, ob[0], ob[1], first_segment, c.min_count, c.min_span);
+        if (c.xyz_mean) {
+            float* o = c.xyz_mean + 3 * (row + r);
+            o[0] = m.xyz[0];
+            o[1] = m.xyz[1];
+            o[2] = m.xyz[2];
+        }
+        if (c.gray_mean) c.gray_mean[row + r] = m.gray;
+        kept += m.kept ? 1u : 0u;
+    }
+    if (c.kept) {  // (uniform)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) kept += __shfl_down(kept, off, 64);
+        if ((threadIdx.x & 63) == 0 && kept) atomicAdd(c.kept + i, kept);
+    }
+}
+void launch_voxel_means(const VoxelMeansCall& c, hipStream_t s) {
+    if (c.kept) (void)hipMemsetAsync(c.kept, 0, (size_t)c.n * sizeof(uint32_t), s);
+    const long long blocks = ((long long)c.capacity + VMEANS_BLOCK - 1) / VMEANS_BLOCK;
+    hipLaunchKernelGGL(voxel_means_kernel, dim3((unsigned)std::min<long long>(blocks, 4096), c.n), dim3(VMEANS_BLOCK), 0, s, c);
 }
 
 }  // namespace vors

@@ -58,6 +58,12 @@ struct vors_trackers {
             int table_slots = 0;
             unsigned long long* table = nullptr;
             uint32_t *occupied = nullptr, *overflow = nullptr;
+            // Statistics of the voxels (vors_trackers_enable_map_voxel_stats; off: nothing below exists and the emission is the filter's):
+            //   rank_of  [n_seq][table_slots] the rank of an entry's voxel in the list, all ones = none; cleared with the table
+            //   sums     [n_seq][capacity][4] int64, obs [n_seq][capacity][2] u32: rank-aligned with the lists
+            bool stats = false;
+            uint32_t *rank_of = nullptr, *obs = nullptr;
+            long long* sums = nullptr;
         } voxels;
         // Normals of the map (vors_trackers_enable_map_normals; off: nothing below exists and no launch changes):
         //   n      [n_seq][capacity][3] the normal of every stored entry, rank for rank
@@ -137,6 +143,10 @@ static void trackers_map_emit(vors_trackers* t, const Geom& gm, hipStream_t s) {
     // emission, which reads what this one claimed, is enqueued behind.
     const vors_trackers::Map::Voxels& v = t->map.voxels;
     if (v.on) call.voxels = PointCloudVoxelArgs{v.voxel_m, (uint32_t)v.table_slots, v.table, v.occupied, v.overflow};
+    // ... and so are the statistics: WRITE stores rank_of, ACCUMULATE behind it reads rank_of and the list entries WRITE (of this or an
+    // earlier emission) stored, and touches sums / obs with integer atomics only; later emissions read and extend rank_of. Besides
+    // ACCUMULATE only init's clear writes sums / obs.
+    if (v.stats) call.voxel_stats = PointCloudVoxelStatsArgs{v.rank_of, v.sums, v.obs};
     launch_lm_point_cloud_append(gm, call, s);
 }
 
@@ -512,6 +522,28 @@ static vors_status trackers_map_voxels_enable(vors_trackers* t, bool started, co
     v.on = true;
     return VORS_OK;
 }
+// The switch of the voxels' statistics: every refusal, then every buffer at once. `started` / `before`: as for the voxel filter.
+static vors_status trackers_map_voxel_stats_enable(vors_trackers* t, bool started, const char* before) {
+    vors_trackers::Map::Voxels& v = t->map.voxels;
+    if (!v.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxel_stats: needs the voxel filter of the map first (vors_trackers_enable_map_voxels)");
+    if (v.stats) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxel_stats: the statistics are already enabled");
+    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, std::string("enable_map_voxel_stats: legal only before ") + before);
+    vors_batch* b = t->batch;
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)t->n_seq;
+    uint32_t *rank_of = nullptr, *obs = nullptr;
+    long long* sums = nullptr;
+    b->own.alloc(&rank_of, n * (size_t)v.table_slots);
+    b->own.alloc(&sums, n * (size_t)t->map.capacity * 4);
+    b->own.alloc(&obs, n * (size_t)t->map.capacity * 2);
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "voxel statistics of the keyframe map");
+    v.rank_of = rank_of;
+    v.sums = sums;
+    v.obs = obs;
+    v.stats = true;
+    return VORS_OK;
+}
 // The normals' switch: every refusal, then both buffers at once. `started` / `before`: as for the voxel filter.
 static vors_status trackers_map_normals_enable(vors_trackers* t, bool started, const char* before, int step, float jump_m) {
     if (!t->map.on) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_normals: needs an enabled keyframe map first (vors_trackers_enable_map)");
@@ -597,6 +629,11 @@ static vors_status trackers_map_init(vors_trackers* t, const uint16_t* depth, hi
         HIP_TRY(hipMemsetAsync(v.table, 0xFF, n * (size_t)v.table_slots * 2 * sizeof(unsigned long long), s));
         HIP_TRY(hipMemsetAsync(v.occupied, 0, n * sizeof(uint32_t), s));
         HIP_TRY(hipMemsetAsync(v.overflow, 0, n * sizeof(uint32_t), s));
+        if (v.stats) {
+            HIP_TRY(hipMemsetAsync(v.rank_of, 0xFF, n * (size_t)v.table_slots * sizeof(uint32_t), s));
+            HIP_TRY(hipMemsetAsync(v.sums, 0, n * (size_t)t->map.capacity * 4 * sizeof(long long), s));
+            HIP_TRY(hipMemsetAsync(v.obs, 0, n * (size_t)t->map.capacity * 2 * sizeof(uint32_t), s));
+        }
     }
     trackers_map_emit_all(t, t->batch->g, depth, s);  // (unmasked: the handle's geometry carries no selection)
     HIP_TRY(hipGetLastError());
@@ -780,6 +817,132 @@ vors_status vors_tracker_read_map_voxels(vors_tracker* t, uint32_t* occupied, ui
     HIP_TRY(hipStreamSynchronize(t->s_main));
     if (occupied) *occupied = words[0];
     if (overflow) *overflow = words[1];
+    return VORS_OK;
+}
+
+vors_status vors_trackers_enable_map_voxel_stats(vors_trackers* t) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxel_stats: the handle t is NULL");
+    return trackers_map_voxel_stats_enable(t, t->initialised, "vors_trackers_init (keyframe 0 would not be counted)");
+}
+
+vors_status vors_trackers_map_voxel_stats(const vors_trackers* t, const int64_t** d_sums, const uint32_t** d_obs) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_stats: the handle t is NULL");
+    if (!t->map.voxels.stats)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_stats: the voxel statistics are not enabled (vors_trackers_enable_map_voxel_stats)");
+    if (d_sums) *d_sums = reinterpret_cast<const int64_t*>(t->map.voxels.sums);
+    if (d_obs) *d_obs = t->map.voxels.obs;
+    return VORS_OK;
+}
+
+vors_status vors_trackers_map_voxel_means(vors_trackers* t, uint32_t min_count, uint32_t min_span, float* d_xyz_mean, uint8_t* d_gray_mean,
+                                          uint32_t* d_kept, void* hip_stream) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: the handle t is NULL");
+    const vors_trackers::Map& m = t->map;
+    if (!m.voxels.stats)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: the voxel statistics are not enabled (vors_trackers_enable_map_voxel_stats)");
+    if (!t->initialised) return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: called before vors_trackers_init (there is no map yet)");
+    if (!d_xyz_mean && !d_gray_mean && !d_kept)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: no output at all (d_xyz_mean, d_gray_mean and d_kept are NULL)");
+    if ((uintptr_t)d_xyz_mean % 4 != 0 || (uintptr_t)d_kept % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: d_xyz_mean and d_kept must be 4-byte aligned");
+    vors_batch* b = t->batch;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    vors_status st = check_stream(b, s);
+    if (st != VORS_OK) return st;
+    // the first segment of a rank: a binary search over the handle's segment records, inside the pass (no plane of its own)
+    VoxelMeansCall call{};
+    call.n = t->n_seq; call.xyz = m.xyz; call.list_counts = m.counts; call.capacity = m.capacity; call.sums = m.voxels.sums; call.obs = m.voxels.obs;
+    call.voxel_m = m.voxels.voxel_m; call.min_count = min_count; call.min_span = min_span;
+    call.segments = m.segments; call.n_segments = m.n_segments; call.max_keyframes = m.max_keyframes;
+    call.xyz_mean = d_xyz_mean; call.gray_mean = d_gray_mean; call.kept = d_kept;
+    launch_voxel_means(call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map_voxel_stats(vors_tracker* t) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxel_stats: the handle t is NULL");
+    if (t->seq->map.normals.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_voxel_stats: legal only before vors_tracker_enable_map_normals (keyframe 0 is emitted again)");
+    vors_status st = trackers_map_voxel_stats_enable(t->seq, t->has_last, "the first vors_tracker_track");
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    // vors_tracker_enable_map_voxels has emitted keyframe 0 without statistics: the map is emptied and keyframe 0 emitted again, counted
+    return trackers_map_init(t->seq, nullptr, t->s_main);  // (no normals yet: see the refusal above)
+}
+
+// The clipped count of the single sequence's list (synchronises).
+static vors_status tracker_map_clipped_count(vors_tracker* t, uint32_t* np) {
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, t->seq->map.counts, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    *np = std::min<uint32_t>(total, (uint32_t)t->seq->map.capacity);
+    return VORS_OK;
+}
+
+vors_status vors_tracker_read_map_voxel_stats(vors_tracker* t, int capacity, int64_t* sums, uint32_t* obs) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_voxel_stats: the handle t is NULL");
+    const vors_trackers::Map::Voxels& v = t->seq->map.voxels;
+    if (!v.stats)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_voxel_stats: the voxel statistics are not enabled (vors_tracker_enable_map_voxel_stats)");
+    if (capacity < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_voxel_stats: negative capacity");
+    DeviceGuard guard(t->device);
+    uint32_t clipped = 0;
+    vors_status st = tracker_map_clipped_count(t, &clipped);
+    if (st != VORS_OK) return st;
+    const size_t np = std::min<size_t>(clipped, (size_t)capacity);
+    if (sums && np) HIP_TRY(hipMemcpyAsync(sums, v.sums, np * 4 * sizeof(int64_t), hipMemcpyDeviceToHost, t->s_main));
+    if (obs && np) HIP_TRY(hipMemcpyAsync(obs, v.obs, np * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    return VORS_OK;
+}
+
+// Host buffers, like its siblings, and no device buffer of its own: the statistics, the list and the segment records are read back and
+// resolved by vors_voxel_means_host — lie.h voxel_mean, the text the device pass runs, so the bits are those of
+// vors_trackers_map_voxel_means; the first segment of a rank is the same search over the records.
+vors_status vors_tracker_map_voxel_means(vors_tracker* t, uint32_t min_count, uint32_t min_span, int capacity, float* xyz_mean, uint8_t* gray_mean,
+                                         uint32_t* kept) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: the handle t is NULL");
+    const vors_trackers::Map& m = t->seq->map;
+    if (!m.voxels.stats)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: the voxel statistics are not enabled (vors_tracker_enable_map_voxel_stats)");
+    if (capacity < 0) return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: negative capacity");
+    if (!xyz_mean && !gray_mean && !kept)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_voxel_means: no output at all (xyz_mean, gray_mean and kept are NULL)");
+    DeviceGuard guard(t->device);
+    uint32_t np = 0, n_seg = 0;
+    vors_status st = tracker_map_clipped_count(t, &np);
+    if (st != VORS_OK) return st;
+    HIP_TRY(hipMemcpyAsync(&n_seg, m.n_segments, sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    n_seg = std::min<uint32_t>(n_seg, (uint32_t)m.max_keyframes);
+    std::vector<float> xyz((size_t)np * 3), mean((size_t)np * 3);
+    std::vector<int64_t> sums((size_t)np * 4);
+    std::vector<uint32_t> obs((size_t)np * 2), first_segment(np);
+    std::vector<uint8_t> gray(np);
+    std::vector<vors_map_segment> seg(n_seg);
+    if (np) {
+        HIP_TRY(hipMemcpyAsync(xyz.data(), m.xyz, xyz.size() * sizeof(float), hipMemcpyDeviceToHost, t->s_main));
+        HIP_TRY(hipMemcpyAsync(sums.data(), m.voxels.sums, sums.size() * sizeof(int64_t), hipMemcpyDeviceToHost, t->s_main));
+        HIP_TRY(hipMemcpyAsync(obs.data(), m.voxels.obs, obs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, t->s_main));
+    }
+    if (n_seg) HIP_TRY(hipMemcpyAsync(seg.data(), m.segments, seg.size() * sizeof(vors_map_segment), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    for (uint32_t r = 0, j = 0; r < np; ++r) {  // (the last record whose first is <= r; ranks ascend, so j only moves on)
+        while (j + 1 < n_seg && seg[j + 1].first <= r) ++j;
+        first_segment[r] = j;
+    }
+    uint32_t k = 0;
+    if (np) {
+        st = vors_voxel_means_host(xyz.data(), np, (int)np, sums.data(), obs.data(), m.voxels.voxel_m, min_count, min_span, first_segment.data(),
+                                   mean.data(), gray.data(), &k);
+        if (st != VORS_OK) return st;
+    }
+    const size_t no = std::min<size_t>(np, (size_t)capacity);
+    if (xyz_mean && no) std::memcpy(xyz_mean, mean.data(), no * 3 * sizeof(float));
+    if (gray_mean && no) std::memcpy(gray_mean, gray.data(), no);
+    if (kept) *kept = k;
     return VORS_OK;
 }
 

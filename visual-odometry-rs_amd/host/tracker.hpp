@@ -183,6 +183,30 @@ class Tracker {  // inverse_compositional.rs:31-34
         check(vors_tracker_read_map_voxels(h_, &v.occupied, &v.overflow));
         return v;
     }
+    // Extension: statistics of the map's voxels (vors_tracker_enable_map_voxel_stats): per rank fixed-point sums of every observation of
+    // its voxel, the sum of their greys, their number and the last segment that saw it. After enable_map_voxels, before
+    // enable_map_normals and the first track(); empties the map and emits keyframe 0 again, counted.
+    void enable_map_voxel_stats() { check(vors_tracker_enable_map_voxel_stats(h_)); }
+    struct MapVoxelMeans {
+        std::vector<Float> xyz_mean;          // [ranks][3]; NaN = the rank was rejected
+        std::vector<std::uint8_t> gray_mean;  // [ranks]
+        std::vector<std::uint32_t> obs;       // [ranks][2] observations, last segment (vors_tracker_read_map_voxel_stats)
+        std::uint32_t kept = 0;
+    };
+    // The averaged map, rank for rank read_map(capacity)'s points (vors_tracker_map_voxel_means; synchronises): centroids and mean grey
+    // of the ranks seen at least min_count times over at least min_span segments.
+    MapVoxelMeans map_voxel_means(std::uint32_t min_count = 1, std::uint32_t min_span = 0, int capacity = 0x7fffffff) {
+        std::uint32_t count = 0, n_segments = 0;
+        check(vors_tracker_read_map(h_, 0, nullptr, nullptr, nullptr, &count, 0, nullptr, &n_segments));
+        const size_t np = std::min<size_t>(count, (size_t)std::max(std::min(capacity, map_capacity_), 0));
+        MapVoxelMeans m;
+        m.xyz_mean.resize(3 * np);
+        m.gray_mean.resize(np);
+        m.obs.resize(2 * np);
+        check(vors_tracker_map_voxel_means(h_, min_count, min_span, (int)np, m.xyz_mean.data(), m.gray_mean.data(), &m.kept));
+        check(vors_tracker_read_map_voxel_stats(h_, (int)np, nullptr, m.obs.data()));
+        return m;
+    }
     // Extension: a surface normal per map entry (vors_tracker_enable_map_normals): central differences `step` pixels wide in the
     // keyframe's depth plane, neighbours further than jump_m metres in depth left out. After enable_map (level 0) and enable_map_voxels,
     // before the first track().

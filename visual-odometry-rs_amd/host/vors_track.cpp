@@ -13,6 +13,9 @@
 // (vors_tracker_enable_map_voxels). TABLE_SLOTS, a power of two, defaults to 8 Mi entries — twice the default capacity, so the table is at
 // most half full when the list is — and costs 16 x TABLE_SLOTS bytes of device memory (128 MiB at the default). Malformed, or without
 // --map: the usage and status 2, before any device is touched. A sequence with more voxels than entries gets a warning after the last frame.
+// `--map-voxel-means MIN_COUNT[,MIN_SPAN]` (needs --map-voxel) keeps statistics of every voxel (vors_tracker_enable_map_voxel_stats) and
+// writes the AVERAGED map: centroid and mean grey of every voxel seen at least MIN_COUNT times over at least MIN_SPAN keyframes (default 0),
+// with an extra `uint obs` property; the other voxels are left out of the file. Malformed or without --map-voxel: the usage and status 2.
 // `--map-normals STEP[,JUMP_M]` (needs --map with LEVEL 0) gives every point of that map the surface normal of its pixel in its keyframe's
 // depth map (vors_tracker_enable_map_normals; JUMP_M defaults to 0.05 m) and the PLY the properties nx ny nz. Malformed, without --map or
 // with another LEVEL: the usage and status 2, before any device is touched.
@@ -109,6 +112,23 @@ static bool parse_map_voxel(const std::string& val, float& voxel_m, int& table_s
     return *end == '\0';
 }
 
+// "MIN_COUNT[,MIN_SPAN]": whole numbers >= 0, nothing after the last.
+static bool parse_map_voxel_means(const std::string& val, uint32_t& min_count, uint32_t& min_span) {
+    if (val.empty()) return false;
+    const char* p = val.c_str();
+    char* end = nullptr;
+    uint32_t* out[2] = {&min_count, &min_span};
+    for (int k = 0; k < 2; ++k) {
+        const long long v = std::strtoll(p, &end, 10);
+        if (end == p || v < 0 || v > 0xFFFFFFFFll) return false;
+        *out[k] = (uint32_t)v;
+        if (*end != ',') break;
+        p = end + 1;
+        if (k == 1) return false;
+    }
+    return *end == '\0';
+}
+
 static const int MAP_VOXEL_DEFAULT_TABLE_SLOTS = 8 << 20;  // 16 bytes each: 128 MiB
 
 // "STEP[,JUMP_M]": a whole number, then a number, nothing after the last. The VALUES are judged by the library.
@@ -188,7 +208,8 @@ int main(int argc, char** argv) {
     icp_params.max_trans_m = 0.05f;
     icp_params.max_rot_rad = 0.05f;
     bool quiet = false, depth_filter = false, map = false, bad_map = false, map_voxel = false, bad_map_voxel = false;
-    bool map_normals = false, bad_map_normals = false;
+    bool map_normals = false, bad_map_normals = false, map_voxel_means = false, bad_map_voxel_means = false;
+    uint32_t means_min_count = 1, means_min_span = 0;
     int normals_step = 1;
     float normals_jump_m = 0.05f;
     float voxel_m = 0.0f;
@@ -220,6 +241,10 @@ int main(int argc, char** argv) {
             map_voxel = parse_map_voxel(val, voxel_m, voxel_table_slots);
             bad_map_voxel = !map_voxel;
             ++a;
+        } else if (flag == "--map-voxel-means") {
+            map_voxel_means = parse_map_voxel_means(val, means_min_count, means_min_span);
+            bad_map_voxel_means = !map_voxel_means;
+            ++a;
         } else if (flag == "--map-normals") {
             map_normals = parse_map_normals(val, normals_step, normals_jump_m);
             bad_map_normals = !map_normals;
@@ -245,6 +270,11 @@ int main(int argc, char** argv) {
     if (bad_map_voxel || (map_voxel && !map)) {
         std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
                      bad_map_voxel ? "Malformed --map-voxel: expected SIZE_M[,TABLE_SLOTS]" : "--map-voxel needs --map");
+        return 2;
+    }
+    if (bad_map_voxel_means || (map_voxel_means && !map_voxel)) {
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
+                     bad_map_voxel_means ? "Malformed --map-voxel-means: expected MIN_COUNT[,MIN_SPAN]" : "--map-voxel-means needs --map-voxel");
         return 2;
     }
     if (bad_map_normals || (map_normals && (!map || map_ints[0] != 0))) {
@@ -312,6 +342,7 @@ int main(int argc, char** argv) {
         if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
         if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
         if (map_voxel) tracker.enable_map_voxels(voxel_m, voxel_table_slots);
+        if (map_voxel_means) tracker.enable_map_voxel_stats();  // (in front of the normals: it emits keyframe 0 again, too)
         if (map_normals) tracker.enable_map_normals(normals_step, normals_jump_m);  // (behind the voxel filter, which emits keyframe 0 again)
         std::uint32_t condition = 0;
         if (map_icp_joint) {
@@ -350,7 +381,15 @@ int main(int argc, char** argv) {
                              m.count - (uint32_t)map_ints[1]);
             if (m.n_segments > (uint32_t)map_ints[2])
                 std::fprintf(stderr, "Warning: %u keyframes but room for %d segment records\n", m.n_segments, map_ints[2]);
-            if (map_normals) {
+            if (map_voxel_means) {  // ranks are aligned: the normals of the map's points go with their voxels' centroids
+                const track::Tracker::MapVoxelMeans mm = tracker.map_voxel_means(means_min_count, means_min_span, (int)m.gray.size());
+                std::vector<Float> normals;
+                if (map_normals) normals = tracker.read_map_normals((int)m.gray.size());
+                std::vector<std::uint32_t> obs(m.gray.size());
+                for (size_t r = 0; r < obs.size(); ++r) obs[r] = mm.obs[2 * r];
+                ply_io::write_map_means(map_file, mm.xyz_mean.data(), map_normals ? normals.data() : nullptr, mm.gray_mean.data(), obs.data(),
+                                        obs.size(), m.segments.data(), m.segments.size());
+            } else if (map_normals) {
                 const std::vector<Float> normals = tracker.read_map_normals((int)m.gray.size());
                 ply_io::write_map(map_file, m.xyz.data(), normals.data(), m.gray.data(), m.gray.size(), m.segments.data(), m.segments.size());
             } else {

@@ -128,6 +128,8 @@ EXPORTED_SYMBOLS = [
     "vors_trackers_current_frames", "vors_trackers_last_stats", "vors_trackers_enable_kernel_timing", "vors_trackers_kernel_times", "vors_trackers_destroy",
     "vors_trackers_enable_depth_filter", "vors_trackers_keyframe_depth", "vors_trackers_workspace_bytes",
     "vors_trackers_enable_map", "vors_trackers_map", "vors_trackers_enable_map_voxels", "vors_trackers_map_voxels", "vors_voxel_keys",
+    "vors_trackers_enable_map_voxel_stats", "vors_trackers_map_voxel_stats", "vors_trackers_map_voxel_means", "vors_tracker_enable_map_voxel_stats",
+    "vors_tracker_read_map_voxel_stats", "vors_tracker_map_voxel_means", "vors_voxel_means", "vors_voxel_means_host", "vors_voxel_stats_host",
     "vors_synth_render_frames",
     "vors_pipeline_create", "vors_pipeline_submit", "vors_pipeline_wait", "vors_pipeline_drain", "vors_pipeline_destroy",
 ]
@@ -196,6 +198,15 @@ def lib():
         _lib.vors_trackers_map_voxels.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_voxels.argtypes = [vp, f, i]
         _lib.vors_tracker_read_map_voxels.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.vors_trackers_enable_map_voxel_stats.argtypes = [vp]
+        _lib.vors_trackers_map_voxel_stats.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        _lib.vors_trackers_map_voxel_means.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        _lib.vors_tracker_enable_map_voxel_stats.argtypes = [vp]
+        _lib.vors_tracker_read_map_voxel_stats.argtypes = [vp, i, vp, vp]
+        _lib.vors_tracker_map_voxel_means.argtypes = [vp, C.c_uint32, C.c_uint32, i, vp, vp, C.POINTER(C.c_uint32)]
+        _lib.vors_voxel_means.argtypes = [i, vp, vp, i, vp, vp, f, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+        _lib.vors_voxel_means_host.argtypes = [vp, C.c_uint32, i, vp, vp, f, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint32)]
+        _lib.vors_voxel_stats_host.argtypes = [vp, vp, vp, C.c_uint32, f, i, C.POINTER(C.c_uint32), vp, vp, vp]
         _lib.vors_render_points.argtypes = [i, vp, vp, vp, i, vp, C.c_size_t, vp, i, i, f, vp, C.c_size_t, i, vp, vp, vp, vp, vp]
         _lib.vors_render_points_host.argtypes = [vp, vp, C.c_uint32, i, vp, vp, i, i, f, vp, i, vp, vp, vp, vp]
         _lib.vors_trackers_render_map.argtypes = [vp, i, vp, C.c_size_t, vp, C.c_size_t, i, vp, vp, vp, vp, vp]
@@ -492,11 +503,58 @@ def voxel_keys(voxel_m, xyz):
     return out
 
 
+def _u32(name, v):
+    """An argument the library takes as uint32."""
+    v = int(v)
+    if v < 0 or v > 0xFFFFFFFF:
+        raise VorsError(f"{name} must be in 0..2^32 - 1")
+    return v
+
+
+def voxel_stats_host(xyz, gray, voxel_m, capacity, segment_of=None):
+    """The statistics of the map's voxels for ONE unfiltered list on the host (vors_voxel_stats_host; needs no GPU; the texts the kernels
+    run): xyz [m, 3] float32, gray [m] uint8, segment_of [m] uint32 (the segment index of every entry; None = all 0) -> dict: "total", the
+    unclipped length of the filtered list, "first_index" [k] uint32, the index of every rank's first point, k = min(total, capacity),
+    "sums" [k, 4] int64 and "obs" [k, 2] uint32 (count, last segment) — what Trackers.map_voxel_stats() holds for the sequence."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    g = np.ascontiguousarray(gray, np.uint8).reshape(-1)
+    seg = None if segment_of is None else np.ascontiguousarray(segment_of, np.uint32).reshape(-1)
+    if len(p) != len(g) or (seg is not None and len(seg) != len(p)):
+        raise VorsError("voxel_stats_host: xyz [m, 3], gray [m], segment_of [m] or None")
+    cap = int(capacity)
+    total = C.c_uint32()
+    first = np.zeros(max(cap, 0), np.uint32)
+    sums, obs = np.zeros((max(cap, 0), 4), np.int64), np.zeros((max(cap, 0), 2), np.uint32)
+    _check(lib().vors_voxel_stats_host(_ptr(p), _ptr(g), _ptr(seg), len(p), float(voxel_m), cap, C.byref(total), _ptr(first), _ptr(sums), _ptr(obs)))
+    k = min(total.value, cap)
+    return dict(total=total.value, first_index=first[:k], sums=sums[:k], obs=obs[:k])
+
+
+def voxel_means_host(xyz, sums, obs, voxel_m, min_count=1, min_span=0, first_segment_of_rank=None, count=None):
+    """The rule of voxel_means for ONE list on the host (vors_voxel_means_host; needs no GPU; the text the kernel runs): xyz [capacity, 3]
+    float32, sums [capacity, 4] int64, obs [capacity, 2] uint32, count = the list's count (None = capacity; above it: clipped),
+    first_segment_of_rank [capacity] uint32 or None (then min_span must be 0) -> dict: "xyz_mean" [capacity, 3] float32 and "gray_mean"
+    [capacity] uint8 (zeros beyond the clipped count), "kept"."""
+    p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    s = np.ascontiguousarray(sums, np.int64).reshape(-1, 4)
+    o = np.ascontiguousarray(obs, np.uint32).reshape(-1, 2)
+    fs = None if first_segment_of_rank is None else np.ascontiguousarray(first_segment_of_rank, np.uint32).reshape(-1)
+    if len(s) != len(p) or len(o) != len(p) or (fs is not None and len(fs) != len(p)):
+        raise VorsError("voxel_means_host: xyz [capacity, 3], sums [capacity, 4], obs [capacity, 2], first_segment_of_rank [capacity] or None")
+    out = dict(xyz_mean=np.zeros((len(p), 3), np.float32), gray_mean=np.zeros(len(p), np.uint8))
+    kept = C.c_uint32()
+    _check(lib().vors_voxel_means_host(_ptr(p), len(p) if count is None else _u32("count", count), len(p), _ptr(s), _ptr(o), float(voxel_m),
+                                       _u32("min_count", min_count), _u32("min_span", min_span), _ptr(fs), _ptr(out["xyz_mean"]),
+                                       _ptr(out["gray_mean"]), C.byref(kept)))
+    out["kept"] = kept.value
+    return out
+
+
 class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
     def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None,
-                 map_normals=None, map_icp=None, map_icp_joint=None):
+                 map_normals=None, map_icp=None, map_icp_joint=None, map_voxel_stats=False):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
         (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
         keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it. map_voxels: None,
@@ -507,12 +565,17 @@ class Tracker:
         (vors_tracker_enable_map_icp; Trackers.enable_map_icp), switched on last; needs map_normals; read_map_icp() returns its record.
         map_icp_joint: None, or a dict of map_icp_joint_params()' keywords — the same correction through the joint pass with the condition
         test (vors_tracker_enable_map_icp_joint; Trackers.enable_map_icp_joint), INSTEAD of map_icp; read_map_icp() works unchanged and
-        read_map_icp_joint() returns the joint record."""
+        read_map_icp_joint() returns the joint record. map_voxel_stats: True — the statistics of the map's voxels
+        (vors_tracker_enable_map_voxel_stats; Trackers.enable_map_voxel_stats), switched on right after the voxel filter; needs map_voxels;
+        read_map_voxel_stats() and map_voxel_means() return them."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         self._map = map = _map_args(map)
         self._map_voxels = map_voxels = _map_voxels_args(map_voxels)
         if map_voxels is not None and map is None:
             raise VorsError("map_voxels: the voxel filter needs the keyframe map (Tracker(..., map=(level, capacity, max_keyframes)))")
+        self._map_voxel_stats = bool(map_voxel_stats)
+        if self._map_voxel_stats and map_voxels is None:
+            raise VorsError("map_voxel_stats: the statistics need the voxel filter (Tracker(..., map_voxels=(voxel_m, table_slots)))")
         self._map_normals = map_normals = _map_normals_args(map_normals)
         if map_normals is not None and map is None:
             raise VorsError("map_normals: the normals need the keyframe map (Tracker(..., map=(0, capacity, max_keyframes)))")
@@ -540,6 +603,8 @@ class Tracker:
             _check(lib().vors_tracker_enable_map(self._h, *map))
         if map_voxels is not None:
             _check(lib().vors_tracker_enable_map_voxels(self._h, *map_voxels))
+        if self._map_voxel_stats:
+            _check(lib().vors_tracker_enable_map_voxel_stats(self._h))
         if map_normals is not None:
             _check(lib().vors_tracker_enable_map_normals(self._h, *map_normals))
         if map_icp is not None:
@@ -574,6 +639,30 @@ class Tracker:
         normals = np.zeros((max(cap, 0), 3), np.float32)
         _check(lib().vors_tracker_read_map_normals(self._h, cap, _ptr(normals)))
         return normals[:min(self.read_map(capacity=0)["count"], max(cap, 0), self._map[1])]
+
+    def _voxel_stats_rows(self, who, capacity):
+        if not self._map_voxel_stats:
+            raise VorsError(f"{who}: the voxel statistics are not enabled (Tracker(..., map_voxel_stats=True))")
+        cap = self._map[1] if capacity is None else int(capacity)
+        return cap, min(self.read_map(capacity=0)["count"], max(cap, 0), self._map[1])
+
+    def read_map_voxel_stats(self, capacity=None):
+        """The voxels' statistics so far on the host (vors_tracker_read_map_voxel_stats; synchronises) -> dict: "sums" [m, 4] int64 and
+        "obs" [m, 2] uint32 (count, last segment), rank for rank the entries of read_map(capacity)."""
+        cap, m = self._voxel_stats_rows("read_map_voxel_stats", capacity)
+        sums, obs = np.zeros((max(cap, 0), 4), np.int64), np.zeros((max(cap, 0), 2), np.uint32)
+        _check(lib().vors_tracker_read_map_voxel_stats(self._h, cap, _ptr(sums), _ptr(obs)))
+        return dict(sums=sums[:m], obs=obs[:m])
+
+    def map_voxel_means(self, min_count=1, min_span=0, capacity=None):
+        """The averaged map on the host (vors_tracker_map_voxel_means; synchronises) -> dict: "xyz_mean" [m, 3] float32 and "gray_mean" [m]
+        uint8, rank for rank the entries of read_map(capacity) — NaN and grey 0 where a rank was seen fewer than min_count times or over
+        fewer than min_span segments —, and "kept", the passing ranks of the whole list."""
+        cap, m = self._voxel_stats_rows("map_voxel_means", capacity)
+        xyz, gray, kept = np.zeros((max(cap, 0), 3), np.float32), np.zeros(max(cap, 0), np.uint8), C.c_uint32()
+        _check(lib().vors_tracker_map_voxel_means(self._h, _u32("min_count", min_count), _u32("min_span", min_span), cap, _ptr(xyz), _ptr(gray),
+                                                  C.byref(kept)))
+        return dict(xyz_mean=xyz[:m], gray_mean=gray[:m], kept=kept.value)
 
     def read_map_voxels(self):
         """The voxel filter's counters (vors_tracker_read_map_voxels; synchronises) -> dict: "occupied", the distinct voxels so far, and
@@ -1184,6 +1273,32 @@ class Trackers:
         args = _map_voxels_args((voxel_m, table_slots))
         _check(lib().vors_trackers_enable_map_voxels(self._h, *args))
 
+    def enable_map_voxel_stats(self):
+        """Statistics of the map's voxels (vors_trackers_enable_map_voxel_stats): after enable_map_voxels(), before init(), once. Every
+        rank of the filtered list then carries fixed-point sums of all observations of its voxel, the sum of their greys, their number and
+        the last segment that saw it, beside the lists, which keep their bits: map_voxel_stats(), map_voxel_means()."""
+        _check(lib().vors_trackers_enable_map_voxel_stats(self._h))
+
+    def map_voxel_stats(self, copy=True):
+        """-> dict of tensors (vors_trackers_map_voxel_stats), valid in stream order after the last init() / track(): "sums" [n, capacity,
+        4] int64 (offsets x, y, z from the rank's stored point in units of voxel_m / 2^20, and grey) and "obs" [n, capacity, 2] int32
+        (the u32 count and last segment), rank for rank with map(). copy=False: views of the handle's own buffers, which die with this
+        object."""
+        cap = self._map[1] if self._map else 0  # (no map: the entry refuses)
+        return self._views(lib().vors_trackers_map_voxel_stats, copy, sums=((cap, 4), "<i8"), obs=((cap, 2), "<i4"))
+
+    def map_voxel_means(self, min_count=1, min_span=0, xyz_mean=True, gray_mean=True, kept=True):
+        """The averaged map (vors_trackers_map_voxel_means): voxel_means() on the handle's own lists and statistics, the span taken from
+        its segments, on the current stream, not synchronised. The result as in voxel_means()."""
+        import torch
+        cap = self._map[1] if self._map else 1  # (no map: the entry refuses)
+        dev = _torch_device(self._device)
+        bufs = (_out_buf(xyz_mean, (self.n, cap, 3), torch.float32, dev), _out_buf(gray_mean, (self.n, cap), torch.uint8, dev),
+                _out_buf(kept, (self.n,), torch.int32, dev))
+        _check(lib().vors_trackers_map_voxel_means(self._h, _u32("min_count", min_count), _u32("min_span", min_span),
+                                                   *[Batch._dp(t) for t in bufs], Batch._stream()))
+        return _voxel_means_result(bufs, xyz_mean, gray_mean, kept)
+
     def enable_map_normals(self, step, jump_m):
         """Normals of the keyframe map (vors_trackers_enable_map_normals): after enable_map() with level 0, before init(), once. Every map
         entry then carries the surface normal of its pixel in its keyframe's depth plane, in the world frame (points_normals' rule with the
@@ -1555,6 +1670,37 @@ def render_points(xyz, list_gray, list_counts, cam5, rows, cols, depth_scale, po
                                     int(cols), float(depth_scale), Batch._dp(poses), pose_stride, int(footprint),
                                     *[Batch._dp(t) for t in bufs], Batch._stream()))
     return _render_result(bufs, zkey, depth, gray, counts)
+
+
+def _voxel_means_result(bufs, xyz_mean, gray_mean, kept):
+    return _result(*((name, _asked(want), t) for name, want, t in zip(("xyz_mean", "gray_mean", "kept"), (xyz_mean, gray_mean, kept), bufs)))
+
+
+def voxel_means(xyz, list_counts, sums, obs, voxel_m, min_count=1, min_span=0, first_segment_of_rank=None, xyz_mean=True, gray_mean=True,
+                kept=True):
+    """Voxel statistics resolved into an averaged list (vors_voxel_means; handle-free) -> dict of the requested tensors on the current
+    stream, not synchronised: "xyz_mean" [n, capacity, 3] float32 and "gray_mean" [n, capacity] uint8, written for the ranks below
+    min(count, capacity) — the centroid and mean grey of the rank's voxel, or NaN and grey 0 where it was seen fewer than max(min_count, 1)
+    times or over fewer than min_span segments, which render_points() and every ICP pass skip — and "kept" [n] int32, the passing ranks.
+    xyz [n, capacity, 3] float32, list_counts [n] int32: the tensors of Trackers.map(); sums [n, capacity, 4] int64, obs [n, capacity, 2]
+    int32: those of Trackers.map_voxel_stats(); first_segment_of_rank [n, capacity] int32 or None (then min_span must be 0). xyz_mean /
+    gray_mean / kept may also be a tensor of that shape to write into."""
+    import torch
+    n = xyz.shape[0]
+    cap = xyz.shape[1] if xyz.dim() == 3 else -1
+    fs = first_segment_of_rank
+    if (xyz.dtype != torch.float32 or not xyz.is_contiguous() or xyz.dim() != 3 or xyz.shape[2] != 3 or list_counts.dtype != torch.int32
+            or not list_counts.is_contiguous() or tuple(list_counts.shape) != (n,) or sums.dtype != torch.int64 or not sums.is_contiguous()
+            or tuple(sums.shape) != (n, cap, 4) or obs.dtype != torch.int32 or not obs.is_contiguous() or tuple(obs.shape) != (n, cap, 2)
+            or (fs is not None and (fs.dtype != torch.int32 or not fs.is_contiguous() or tuple(fs.shape) != (n, cap)))):
+        raise VorsError("voxel_means: xyz float32 [n, capacity, 3], list_counts int32 [n], sums int64 [n, capacity, 4], obs int32 [n, capacity, 2], "
+                        "first_segment_of_rank int32 [n, capacity] or None, contiguous")
+    bufs = (_out_buf(xyz_mean, (n, cap, 3), torch.float32, xyz.device), _out_buf(gray_mean, (n, cap), torch.uint8, xyz.device),
+            _out_buf(kept, (n,), torch.int32, xyz.device))
+    _check(lib().vors_voxel_means(n, Batch._dp(xyz), Batch._dp(list_counts), cap, Batch._dp(sums), Batch._dp(obs), float(voxel_m),
+                                  _u32("min_count", min_count), _u32("min_span", min_span), Batch._dp(fs), *[Batch._dp(t) for t in bufs],
+                                  Batch._stream()))
+    return _voxel_means_result(bufs, xyz_mean, gray_mean, kept)
 
 
 def render_points_host(xyz, list_gray, cam5, rows, cols, depth_scale, pose7=None, footprint=1, count=None, range2=None):
