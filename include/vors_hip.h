@@ -133,7 +133,9 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_map_icp_joint_params, vors_map_icp_joint_record, VORS_MAP_ICP_CONDITION, likewise;
                               *    + vors_trackers_enable_map_voxel_stats, vors_trackers_map_voxel_stats, vors_trackers_map_voxel_means,
                               *    vors_tracker_enable_map_voxel_stats, vors_tracker_read_map_voxel_stats, vors_tracker_map_voxel_means,
-                              *    vors_voxel_means, vors_voxel_means_host, vors_voxel_stats_host, likewise) */
+                              *    vors_voxel_means, vors_voxel_means_host, vors_voxel_stats_host, likewise; + vors_trackers_enable_map_icp_means,
+                              *    vors_trackers_map_icp_means, vors_tracker_enable_map_icp_means, vors_tracker_read_map_icp_means,
+                              *    vors_map_icp_means_record, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -251,6 +253,13 @@ struct vors_map_icp_joint_record;  /* section 2e, behind vors_map_icp_record */
 vors_status vors_tracker_enable_map_icp_joint(vors_tracker* t, const vors_map_icp_joint_params* params);
 /* The joint record of the LAST vors_tracker_track to the host (nullable); synchronises. No joint stage: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_tracker_read_map_icp_joint(vors_tracker* t, struct vors_map_icp_joint_record* record);
+struct vors_map_icp_means_record;  /* section 2e, behind vors_map_icp_joint_record */
+/* The averaged model of vors_trackers_enable_map_icp_means (below) for the single sequence, its N = 1 case: same arguments, same refusals.
+ * Legal after vors_tracker_enable_map_voxel_stats and after one of vors_tracker_enable_map_icp / _joint, until the first
+ * vors_tracker_track (refused after it and when repeated). */
+vors_status vors_tracker_enable_map_icp_means(vors_tracker* t, uint32_t min_count, uint32_t min_span);
+/* The means record of the LAST vors_tracker_track to the host (nullable); synchronises. Means not enabled: VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_tracker_read_map_icp_means(vors_tracker* t, struct vors_map_icp_means_record* record);
 void vors_tracker_destroy(vors_tracker* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -518,6 +527,32 @@ vors_status vors_trackers_enable_map_icp_joint(vors_trackers* t, const vors_map_
 /* DEVICE pointer, owned by the handle and valid for its life, contents valid in stream order after the last track: d_joint_records [n],
  * entry for entry beside vors_trackers_map_icp's d_records (nullable). No joint stage on this handle: VORS_ERR_INVALID_ARGUMENT. */
 vors_status vors_trackers_map_icp_joint(const vors_trackers* t, const struct vors_map_icp_joint_record** d_joint_records);
+/* THE AVERAGED MAP AS THE CORRECTION'S MODEL (opt-in on top of either correction and of the voxels' statistics; without
+ * this call nothing changes: no launch, no allocation, no kernel argument on any existing path). With the voxel filter the map's lists
+ * hold the FIRST point that fell into each voxel; the correction then aligns that one sample per voxel. With this call the pass reads,
+ * in the lists' place, the centroid and mean grey of every observation of the voxel: in every track call, behind ARM and before the
+ * ICP's first launch, one pass resolves the ranks of every promoted sequence's window — vors_trackers_map_voxel_means' rule (lie.h
+ * voxel_mean with min_count, min_span; the first segment of a rank by the same search over the segment records) on the statistics as
+ * they stood BEFORE this promotion's emission — into staging the handle owns, rank for rank: xyz_mean [n][capacity][3] f32 and gray_mean
+ * [n][capacity] u8. A rank that fails gets voxel_mean's NaN triple and grey 0, which every gate of the ICP skips; nothing is compacted,
+ * so the map's normals (the normal of the voxel's first point; there are no mean normals) stay aligned. The pass's xyz is the staging,
+ * and with the joint stage its list grey is gray_mean. ARM, APPLY, the window, both verdicts and the ICP itself are what they were:
+ * `considered` stays the ranks of the WINDOW, rejected ranks included, so min_match_ratio is a ratio of the whole window — a caller who
+ * filters hard reads `kept` of the record below and sets the ratio accordingly.
+ * Per sequence a vors_map_icp_means_record (section 2e) of the LAST track call: resolved = the window's length, kept = its passing ranks;
+ * zeros for a sequence the call did not promote. Launches per track call: one memset of the records and one launch over n sequences (the
+ * host cannot know which promote: a sequence with the window (0, 0) is left by its workgroups at once).
+ * Legal after vors_trackers_enable_map_voxel_stats and after one of vors_trackers_enable_map_icp / _joint, before vors_trackers_init,
+ * once. VORS_ERR_INVALID_ARGUMENT, nothing allocated and nothing enqueued: NULL handle, no statistics enabled, no correction enabled,
+ * repeated call, call after init. The call allocates, as part of vors_trackers_workspace_bytes' figure and freed with the handle,
+ * n * capacity * 13 + 8 n bytes; no later call allocates. vors_trackers_init zeroes staging and records on the stream. */
+vors_status vors_trackers_enable_map_icp_means(vors_trackers* t, uint32_t min_count, uint32_t min_span);
+/* DEVICE pointers, owned by the handle and valid for its life, contents valid in stream order after the last track, each nullable:
+ * d_xyz_mean [n][capacity][3] f32, d_gray_mean [n][capacity] u8, d_records [n]. The staging holds, per sequence, whatever its windows
+ * have written since init — a later window overwrites only its own ranks — and zero bytes elsewhere. Means not enabled:
+ * VORS_ERR_INVALID_ARGUMENT. */
+vors_status vors_trackers_map_icp_means(const vors_trackers* t, const float** d_xyz_mean, const uint8_t** d_gray_mean,
+                                        const struct vors_map_icp_means_record** d_records);
 void vors_trackers_destroy(vors_trackers* t);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1178,6 +1213,12 @@ vors_status vors_map_icp_verdict_host(const vors_map_icp_params* params, const v
 typedef struct vors_map_icp_joint_record {
     float dilution_t, dilution_r; int32_t condition_flags; uint32_t photo_counts[VORS_ICP_PHOTO_COUNTS];
 } vors_map_icp_joint_record;
+/* What vors_trackers_enable_map_icp_means (section 1b) keeps per sequence of the LAST track call: 8 bytes. resolved = the length of the
+ * window whose ranks were resolved into the staging, kept = those of them that passed (min_count, min_span). Zeros for a sequence the
+ * call did not promote. */
+typedef struct vors_map_icp_means_record {
+    uint32_t resolved, kept;
+} vors_map_icp_means_record;
 /* The joint stage's verdict on the HOST (lie.h map_icp_verdict_joint, the text map_icp_apply_joint_kernel runs): vors_map_icp_verdict_host
  * on params->icp, and only behind ACCEPTED the two bounds on the dilutions given -> *verdict, a VORS_MAP_ICP_* other than NOT_ATTEMPTED.
  * Refused: a NULL argument, the verdict fields vors_trackers_enable_map_icp refuses, a dilution bound negative or NaN. */

@@ -751,6 +751,9 @@ void launch_lm_point_cloud_append(const Geom& g, const PointCloudAppendCall& cal
 // voxel_means_kernel): per rank below the clipped count lie.h voxel_mean. Handle-free: everything the kernel reads is here. The first
 // segment of a rank comes from `first_segment` (one word per rank), or from `segments` by a binary search over their `first` (the
 // handle's own map), or from nowhere (both null: no span test). Each output is nullable.
+// The WINDOWED form (launch_voxel_means_window; the means of the map ICP correction, vors_trackers_enable_map_icp_means): the same body
+// over the ranks [first, first + len) of `ranges`, clipped to the clipped count, instead of [0, clipped count); `kept` is then not read,
+// the count goes into `records`, and a list whose window is empty is left by its workgroups at once.
 struct VoxelMeansCall {
     int n;                              // lists
     const float* xyz;                   // [n][capacity][3]
@@ -767,9 +770,13 @@ struct VoxelMeansCall {
     float* xyz_mean;                    // [n][capacity][3]
     uint8_t* gray_mean;                 // [n][capacity]
     uint32_t* kept;                     // [n]
+    const uint32_t* ranges;             // [n][2] (first, len) per list: the windowed form only
+    vors_map_icp_means_record* records; // [n] {resolved = len, kept}: the windowed form only
 };
 // The clear of `kept` and one launch: enqueued on s, not synchronised, no workspace.
 void launch_voxel_means(const VoxelMeansCall& call, hipStream_t s);
+// The windowed form: the clear of `records` and one launch over call.n lists; ranges, records, segments, xyz_mean and gray_mean required.
+void launch_voxel_means_window(const VoxelMeansCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

@@ -86,6 +86,10 @@ struct vors_trackers {
         //   jp                 the parameters; p above is jp.icp
         //   sums29, photo_counts   [n_seq][29], [n_seq][VORS_ICP_PHOTO_COUNTS] staging of the pass's final sums and photo counts
         //   joint_records      [n_seq], beside records: what vors_trackers_map_icp_joint shows
+        // With the averaged model (vors_trackers_enable_map_icp_means; `means`, otherwise nothing below exists):
+        //   mean_xyz, mean_gray    [n_seq][capacity][3], [n_seq][capacity] staging of the resolve, rank-aligned with the lists: the pass's
+        //                          xyz and (joint) list grey in the lists' place
+        //   means_records          [n_seq]: what vors_trackers_map_icp_means shows
         struct Icp {
             bool on = false, joint = false;
             vors_map_icp_params p{};
@@ -99,6 +103,11 @@ struct vors_trackers {
             float *start = nullptr, *result = nullptr, *frame_normals = nullptr;
             vors_icp_stats* stats = nullptr;
             vors_map_icp_record* records = nullptr;
+            bool means = false;
+            uint32_t means_min_count = 1, means_min_span = 0;
+            float* mean_xyz = nullptr;
+            uint8_t* mean_gray = nullptr;
+            vors_map_icp_means_record* means_records = nullptr;
         } icp;
     } map;
     const uint16_t* keyframe_depth() const {
@@ -208,6 +217,11 @@ static IcpCall map_icp_call(const vors_trackers* t, const uint16_t* depth) {
 // the map's, frame grey = `gray`, the level-0 plane the keyframe stage of this call read (the caller's frame, or own_gray behind its
 // promote copy), which nothing writes before the next call — with its sums and photo counts into staging; ARM is followed by the reset
 // of the joint records; APPLY is the joint one. `gray` is read only then.
+// With the averaged model (vors_trackers_enable_map_icp_means) one pass stands between ARM (and the joint records' reset) and the ICP's
+// first launch: the windowed resolve of the voxels' statistics into the stage's own staging, which the pass then reads as its xyz and
+// (joint) list grey. Hazards: the resolve reads ic.ranges behind ARM; it reads sums, obs, the rank-aligned map.xyz, the segment records
+// and n_segments as they stood BEFORE this promotion's emission (enqueued behind the stage), which only an emission writes; the ICP reads
+// the staging behind the resolve; nothing else writes the staging or the means records, and the resolve writes nothing else.
 static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint16_t* depth, const uint8_t* gray, hipStream_t s) {
     const Geom& g = t->batch->g;
     const vors_trackers::Map& m = t->map;
@@ -258,6 +272,15 @@ static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint1
         launch_map_icp_frame_normals(nc, s);
     }
     IcpCall call = map_icp_call(t, depth);
+    if (ic.means) {
+        VoxelMeansCall vm{};
+        vm.n = t->n_seq; vm.xyz = m.xyz; vm.list_counts = m.counts; vm.capacity = m.capacity; vm.sums = m.voxels.sums; vm.obs = m.voxels.obs;
+        vm.voxel_m = m.voxels.voxel_m; vm.min_count = ic.means_min_count; vm.min_span = ic.means_min_span;
+        vm.segments = m.segments; vm.n_segments = m.n_segments; vm.max_keyframes = m.max_keyframes;
+        vm.xyz_mean = ic.mean_xyz; vm.gray_mean = ic.mean_gray; vm.ranges = ic.ranges; vm.records = ic.means_records;
+        launch_voxel_means_window(vm, s);
+        call.xyz = ic.mean_xyz;
+    }
     call.ranges = reinterpret_cast<const uint8_t*>(ic.ranges);
     call.range_stride = 8;
     call.poses_in = ic.start;
@@ -277,7 +300,7 @@ static void trackers_map_icp_stage(vors_trackers* t, const Geom& gm, const uint1
         return;
     }
     call.sums29 = ic.sums29;
-    const IcpJoint joint{m.gray, gray, ic.jp.photo_scale_m, map_icp_photo_huber_m(ic.jp), nullptr, ic.photo_counts};
+    const IcpJoint joint{ic.means ? ic.mean_gray : m.gray, gray, ic.jp.photo_scale_m, map_icp_photo_huber_m(ic.jp), nullptr, ic.photo_counts};
     launch_icp_points(call, &robust, s, &joint);
     launch_map_icp_apply_joint(joint_call(), s);
 }
@@ -619,6 +642,43 @@ static vors_status trackers_map_icp_init(vors_trackers* t, hipStream_t s) {
     if (t->map.icp.joint) HIP_TRY(hipMemsetAsync(t->map.icp.joint_records, 0, n * sizeof(vors_map_icp_joint_record), s));
     return VORS_OK;
 }
+// The switch of the correction's averaged model: every refusal, then every buffer at once. `started` / `before`: as for the voxel filter.
+static vors_status trackers_map_icp_means_enable(vors_trackers* t, bool started, const char* before, uint32_t min_count, uint32_t min_span) {
+    vors_trackers::Map::Icp& ic = t->map.icp;
+    if (!t->map.voxels.stats)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp_means: needs the voxel statistics first (vors_trackers_enable_map_voxel_stats)");
+    if (!ic.on)
+        return fail(VORS_ERR_INVALID_ARGUMENT,
+                    "enable_map_icp_means: needs the correction first (vors_trackers_enable_map_icp or vors_trackers_enable_map_icp_joint)");
+    if (ic.means) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp_means: the averaged model is already enabled");
+    if (started) return fail(VORS_ERR_INVALID_ARGUMENT, std::string("enable_map_icp_means: legal only before ") + before);
+    vors_batch* b = t->batch;
+    DeviceGuard guard(b->device);
+    const size_t n = (size_t)t->n_seq;
+    float* xyz = nullptr;
+    uint8_t* gray = nullptr;
+    vors_map_icp_means_record* records = nullptr;
+    b->own.alloc(&xyz, n * (size_t)t->map.capacity * 3);
+    b->own.alloc(&gray, n * (size_t)t->map.capacity);
+    b->own.alloc(&records, n);
+    if (b->own.err != hipSuccess) return own_alloc_failed(b, "averaged model of the ICP correction");
+    ic.mean_xyz = xyz;
+    ic.mean_gray = gray;
+    ic.means_records = records;
+    ic.means_min_count = min_count;
+    ic.means_min_span = min_span;
+    ic.means = true;
+    return VORS_OK;
+}
+// Staging and records of the averaged model as a handle starts (and starts again) with: zero bytes.
+static vors_status trackers_map_icp_means_init(vors_trackers* t, hipStream_t s) {
+    const vors_trackers::Map::Icp& ic = t->map.icp;
+    const size_t n = (size_t)t->n_seq, cap = (size_t)t->map.capacity;
+    HIP_TRY(hipMemsetAsync(ic.mean_xyz, 0, n * cap * 3 * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(ic.mean_gray, 0, n * cap, s));
+    HIP_TRY(hipMemsetAsync(ic.means_records, 0, n * sizeof(vors_map_icp_means_record), s));
+    return VORS_OK;
+}
 // An empty map (and an empty voxel table), then keyframe 0 of every sequence. `depth`: the planes keyframe 0 was made from, read only
 // when the map carries normals.
 static vors_status trackers_map_init(vors_trackers* t, const uint16_t* depth, hipStream_t s) {
@@ -777,6 +837,41 @@ vors_status vors_tracker_read_map_icp_joint(vors_tracker* t, vors_map_icp_joint_
         return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp_joint: the joint ICP correction is not enabled (vors_tracker_enable_map_icp_joint)");
     DeviceGuard guard(t->device);
     if (record) HIP_TRY(hipMemcpyAsync(record, ic.joint_records, sizeof(vors_map_icp_joint_record), hipMemcpyDeviceToHost, t->s_main));
+    HIP_TRY(hipStreamSynchronize(t->s_main));
+    return VORS_OK;
+}
+
+vors_status vors_trackers_enable_map_icp_means(vors_trackers* t, uint32_t min_count, uint32_t min_span) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp_means: the handle t is NULL");
+    return trackers_map_icp_means_enable(t, t->initialised, "vors_trackers_init", min_count, min_span);
+}
+
+vors_status vors_trackers_map_icp_means(const vors_trackers* t, const float** d_xyz_mean, const uint8_t** d_gray_mean,
+                                        const vors_map_icp_means_record** d_records) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_means: the handle t is NULL");
+    if (!t->map.icp.means)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "map_icp_means: the averaged model is not enabled (vors_trackers_enable_map_icp_means)");
+    if (d_xyz_mean) *d_xyz_mean = t->map.icp.mean_xyz;
+    if (d_gray_mean) *d_gray_mean = t->map.icp.mean_gray;
+    if (d_records) *d_records = t->map.icp.means_records;
+    return VORS_OK;
+}
+
+vors_status vors_tracker_enable_map_icp_means(vors_tracker* t, uint32_t min_count, uint32_t min_span) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "enable_map_icp_means: the handle t is NULL");
+    vors_status st = trackers_map_icp_means_enable(t->seq, t->has_last, "the first vors_tracker_track", min_count, min_span);
+    if (st != VORS_OK) return st;
+    DeviceGuard guard(t->device);
+    return trackers_map_icp_means_init(t->seq, t->s_main);
+}
+
+vors_status vors_tracker_read_map_icp_means(vors_tracker* t, vors_map_icp_means_record* record) {
+    if (!t) return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp_means: the handle t is NULL");
+    const vors_trackers::Map::Icp& ic = t->seq->map.icp;
+    if (!ic.means)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "read_map_icp_means: the averaged model is not enabled (vors_tracker_enable_map_icp_means)");
+    DeviceGuard guard(t->device);
+    if (record) HIP_TRY(hipMemcpyAsync(record, ic.means_records, sizeof(vors_map_icp_means_record), hipMemcpyDeviceToHost, t->s_main));
     HIP_TRY(hipStreamSynchronize(t->s_main));
     return VORS_OK;
 }
@@ -1210,6 +1305,7 @@ vors_status vors_trackers_init(vors_trackers* t, const uint8_t* d_gray, const ui
     if (t->filter.on && (st = trackers_filter_init(t, d_depth, s)) != VORS_OK) return st;
     if (t->map.on && (st = trackers_map_init(t, kf_depth, s)) != VORS_OK) return st;
     if (t->map.icp.on && (st = trackers_map_icp_init(t, s)) != VORS_OK) return st;  // (the stage itself is not run: the map was empty)
+    if (t->map.icp.means && (st = trackers_map_icp_means_init(t, s)) != VORS_OK) return st;
     t->frame_index = 0;
     t->initialised = true;
     return VORS_OK;

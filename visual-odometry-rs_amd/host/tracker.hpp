@@ -241,6 +241,18 @@ class Tracker {  // inverse_compositional.rs:31-34
         check(vors_tracker_read_map_icp(h_, &record, nullptr));
         return record.verdict;
     }
+    // Extension: the averaged map as the correction's model (vors_tracker_enable_map_icp_means): the pass reads the centroid and mean grey
+    // of every voxel seen at least min_count times over at least min_span segments in the lists' place. After enable_map_voxel_stats and
+    // one of enable_map_icp / enable_map_icp_joint, before the first track().
+    void enable_map_icp_means(std::uint32_t min_count = 1, std::uint32_t min_span = 0) {
+        check(vors_tracker_enable_map_icp_means(h_, min_count, min_span));
+    }
+    // The means record of the last track(): the window's length and its passing ranks (vors_tracker_read_map_icp_means; synchronises).
+    vors_map_icp_means_record read_map_icp_means() {
+        vors_map_icp_means_record record{};
+        check(vors_tracker_read_map_icp_means(h_, &record));
+        return record;
+    }
     // Extension: the map seen from a pose (vors_tracker_render_map; synchronises): a z-buffered depth map and grey image in the geometry
     // of pyramid level `level`, row-major, the arguments of Config::init. pose = nullptr: the current frame's pose; range2 = nullptr: the
     // whole map, else (first, count) of the ranks to render (a vors_map_segment's `first`); footprint: 1, 2 or 3 pixels wide.

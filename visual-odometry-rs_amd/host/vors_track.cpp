@@ -30,6 +30,12 @@
 // (vors_tracker_enable_map_icp_joint). PHOTO_SCALE_M: metres per grey level, 0 = no photometric row; defaults: PHOTO_HUBER_GREY 0 (none),
 // both bounds 0 (off). Malformed or without --map-icp: the usage and status 2, before any device is touched. The line after the last
 // frame is then `map-icp: attempted A accepted B condition C`, C the corrections the condition test alone rejected.
+// `--map-icp-means MIN_COUNT[,MIN_SPAN]` (needs --map-voxel and --map-icp, with or without --map-icp-joint) gives that correction the
+// averaged map as its model (vors_tracker_enable_map_icp_means): the centroid and mean grey of every voxel seen at least MIN_COUNT times
+// over at least MIN_SPAN keyframes, in the place of the voxel's first point. It switches the voxels' statistics on itself when
+// --map-voxel-means has not. Malformed or without --map-voxel / --map-icp: the usage and status 2, before any device is touched. After
+// the last frame a second line on stderr: `map-icp-means: attempted A accepted B kept / resolved Q`, Q the mean share of a window's
+// ranks that passed, over the corrections with a window that is not empty.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -210,6 +216,8 @@ int main(int argc, char** argv) {
     bool quiet = false, depth_filter = false, map = false, bad_map = false, map_voxel = false, bad_map_voxel = false;
     bool map_normals = false, bad_map_normals = false, map_voxel_means = false, bad_map_voxel_means = false;
     uint32_t means_min_count = 1, means_min_span = 0;
+    bool map_icp_means = false, bad_map_icp_means = false;
+    uint32_t icp_means_min_count = 1, icp_means_min_span = 0;
     int normals_step = 1;
     float normals_jump_m = 0.05f;
     float voxel_m = 0.0f;
@@ -244,6 +252,10 @@ int main(int argc, char** argv) {
         } else if (flag == "--map-voxel-means") {
             map_voxel_means = parse_map_voxel_means(val, means_min_count, means_min_span);
             bad_map_voxel_means = !map_voxel_means;
+            ++a;
+        } else if (flag == "--map-icp-means") {
+            map_icp_means = parse_map_voxel_means(val, icp_means_min_count, icp_means_min_span);
+            bad_map_icp_means = !map_icp_means;
             ++a;
         } else if (flag == "--map-normals") {
             map_normals = parse_map_normals(val, normals_step, normals_jump_m);
@@ -290,6 +302,13 @@ int main(int argc, char** argv) {
     }
     if (bad_map_icp_joint || (map_icp_joint && !map_icp)) {
         std::fprintf(stderr, "%s\n\"%s\"\n", USAGE, bad_map_icp_joint ? MAP_ICP_JOINT_HELP : "--map-icp-joint needs --map-icp");
+        return 2;
+    }
+    if (bad_map_icp_means || (map_icp_means && (!map_voxel || !map_icp))) {
+        std::fprintf(stderr, "%s\n\"%s\"\n", USAGE,
+                     bad_map_icp_means ? "Malformed --map-icp-means: expected MIN_COUNT[,MIN_SPAN]"
+                     : !map_voxel      ? "--map-icp-means needs --map-voxel"
+                                       : "--map-icp-means needs --map-icp");
         return 2;
     }
     if (argc > 3) argc = bad_flag ? 0 : 3;
@@ -342,7 +361,7 @@ int main(int argc, char** argv) {
         if (depth_filter) tracker.enable_depth_filter(filter_tol_m, filter_max_weight, filter_fill_min_weight);
         if (map) tracker.enable_map(map_ints[0], map_ints[1], map_ints[2], map_ints[3]);  // (after the filter: min_weight reads its weights)
         if (map_voxel) tracker.enable_map_voxels(voxel_m, voxel_table_slots);
-        if (map_voxel_means) tracker.enable_map_voxel_stats();  // (in front of the normals: it emits keyframe 0 again, too)
+        if (map_voxel_means || map_icp_means) tracker.enable_map_voxel_stats();  // (in front of the normals: it emits keyframe 0 again, too)
         if (map_normals) tracker.enable_map_normals(normals_step, normals_jump_m);  // (behind the voxel filter, which emits keyframe 0 again)
         std::uint32_t condition = 0;
         if (map_icp_joint) {
@@ -351,6 +370,9 @@ int main(int argc, char** argv) {
         } else if (map_icp) {
             tracker.enable_map_icp(icp_params);
         }
+        if (map_icp_means) tracker.enable_map_icp_means(icp_means_min_count, icp_means_min_span);
+        double kept_share = 0.0;
+        std::uint32_t windows = 0;
         for (size_t k = 1; k < associations.size(); ++k) {  // vors_track.rs:49-64
             uint32_t w2, h2;
             read_images(associations[k], depth, gray, w2, h2);
@@ -363,6 +385,13 @@ int main(int argc, char** argv) {
             // frame: one small read-back and one synchronisation per frame, which exist for this counter alone and only with this flag
             // (the frame has already waited for its promotion: with the correction on, track() reads its results back behind it).
             if (map_icp_joint && tracker.read_map_icp_verdict() == VORS_MAP_ICP_CONDITION) ++condition;
+            if (map_icp_means) {  // (the same kind of read-back, for the second line alone and only with this flag)
+                const vors_map_icp_means_record r = tracker.read_map_icp_means();
+                if (r.resolved) {
+                    kept_share += (double)r.kept / (double)r.resolved;
+                    ++windows;
+                }
+            }
         }
         if (map_icp) {
             const auto totals = tracker.read_map_icp_totals();
@@ -370,6 +399,9 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "map-icp: attempted %u accepted %u condition %u\n", totals.first, totals.second, condition);
             else
                 std::fprintf(stderr, "map-icp: attempted %u accepted %u\n", totals.first, totals.second);
+            if (map_icp_means)
+                std::fprintf(stderr, "map-icp-means: attempted %u accepted %u kept / resolved %.4f\n", totals.first, totals.second,
+                             windows ? kept_share / windows : 0.0);
         }
         if (map) {
             if (map_voxel && tracker.read_map_voxels().overflow != 0)

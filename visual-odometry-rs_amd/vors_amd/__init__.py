@@ -119,6 +119,7 @@ EXPORTED_SYMBOLS = [
     "vors_map_icp_window_host", "vors_map_icp_verdict_host",
     "vors_icp_condition_from_sums", "vors_icp_condition", "vors_trackers_enable_map_icp_joint", "vors_trackers_map_icp_joint",
     "vors_tracker_enable_map_icp_joint", "vors_tracker_read_map_icp_joint", "vors_map_icp_verdict_joint_host",
+    "vors_trackers_enable_map_icp_means", "vors_trackers_map_icp_means", "vors_tracker_enable_map_icp_means", "vors_tracker_read_map_icp_means",
     "vors_lm_eval", "vors_lm_step", "vors_lm_solve",
     "vors_ref_sincos", "vors_se3_exp", "vors_se3_log", "vors_so3_exp", "vors_so3_log", "vors_iso_mul", "vors_iso_inverse",
     "vors_synth_render_pairs",
@@ -247,6 +248,10 @@ def lib():
         _lib.vors_tracker_enable_map_icp_joint.argtypes = [vp, vp]
         _lib.vors_tracker_read_map_icp_joint.argtypes = [vp, vp]
         _lib.vors_map_icp_verdict_joint_host.argtypes = [vp, vp, vp, vp, f, f, vp]
+        _lib.vors_trackers_enable_map_icp_means.argtypes = [vp, C.c_uint32, C.c_uint32]
+        _lib.vors_trackers_map_icp_means.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        _lib.vors_tracker_enable_map_icp_means.argtypes = [vp, C.c_uint32, C.c_uint32]
+        _lib.vors_tracker_read_map_icp_means.argtypes = [vp, vp]
         _lib.vors_voxel_keys.argtypes = [f, vp, i, vp]
         _lib.vors_voxel_keys.restype = None
         _lib.vors_synth_render_frames.argtypes = [i, vp, vp, vp, i, i, vp, i, vp, vp, vp]
@@ -554,7 +559,7 @@ class Tracker:
     """core::track::inverse_compositional::Tracker. Construct through Config.init."""
 
     def __init__(self, config, depth_t, depth_map, img_t, img, layout=ROW_MAJOR, depth_filter=None, map=None, map_voxels=None,
-                 map_normals=None, map_icp=None, map_icp_joint=None, map_voxel_stats=False):
+                 map_normals=None, map_icp=None, map_icp_joint=None, map_voxel_stats=False, map_icp_means=None):
         """depth_filter: None, or (tol_m[, max_weight[, fill_min_weight]]) — the recursive depth filter across keyframe promotions
         (vors_tracker_enable_depth_filter; Trackers.enable_depth_filter). map: None, or (level, capacity, max_keyframes[, min_weight]) — the
         keyframe map (vors_tracker_enable_map; Trackers.enable_map), switched on after the filter; read_map() returns it. map_voxels: None,
@@ -567,7 +572,9 @@ class Tracker:
         test (vors_tracker_enable_map_icp_joint; Trackers.enable_map_icp_joint), INSTEAD of map_icp; read_map_icp() works unchanged and
         read_map_icp_joint() returns the joint record. map_voxel_stats: True — the statistics of the map's voxels
         (vors_tracker_enable_map_voxel_stats; Trackers.enable_map_voxel_stats), switched on right after the voxel filter; needs map_voxels;
-        read_map_voxel_stats() and map_voxel_means() return them."""
+        read_map_voxel_stats() and map_voxel_means() return them. map_icp_means: None, or (min_count[, min_span]) — the averaged map as the
+        correction's model (vors_tracker_enable_map_icp_means; Trackers.enable_map_icp_means), switched on last; needs map_voxel_stats
+        and one of map_icp / map_icp_joint; read_map_icp_means() returns its record."""
         depth_filter = _depth_filter_args(depth_filter)  # (before anything is created: a bad tuple costs no handle)
         self._map = map = _map_args(map)
         self._map_voxels = map_voxels = _map_voxels_args(map_voxels)
@@ -587,6 +594,11 @@ class Tracker:
             raise VorsError("map_icp_joint: the joint stage stands INSTEAD of map_icp: give one of the two")
         if map_icp_joint is not None and map_normals is None:
             raise VorsError("map_icp_joint: the correction needs the map's normals (Tracker(..., map_normals=(step, jump_m)))")
+        self._map_icp_means = map_icp_means = _map_icp_means_args(map_icp_means)
+        if map_icp_means is not None and not self._map_voxel_stats:
+            raise VorsError("map_icp_means: the averaged model needs the voxel statistics (Tracker(..., map_voxel_stats=True))")
+        if map_icp_means is not None and map_icp is None and map_icp_joint is None:
+            raise VorsError("map_icp_means: the averaged model needs the correction (Tracker(..., map_icp=... or map_icp_joint=...))")
         img = np.ascontiguousarray(img, np.uint8)
         depth_map = np.ascontiguousarray(depth_map, np.uint16)
         rows, cols = img.shape if layout == ROW_MAJOR else img.shape[::-1]
@@ -611,6 +623,17 @@ class Tracker:
             _check(lib().vors_tracker_enable_map_icp(self._h, C.byref(map_icp)))
         if map_icp_joint is not None:
             _check(lib().vors_tracker_enable_map_icp_joint(self._h, C.byref(map_icp_joint)))
+        if map_icp_means is not None:
+            _check(lib().vors_tracker_enable_map_icp_means(self._h, *map_icp_means))
+
+    def read_map_icp_means(self):
+        """The averaged model's record of the last track() on the host (vors_tracker_read_map_icp_means; synchronises) -> a structured
+        scalar of MAP_ICP_MEANS_RECORD_DTYPE: resolved, the window's length, and kept, its ranks that passed."""
+        if self._map_icp_means is None:
+            raise VorsError("read_map_icp_means: the averaged model is not enabled (Tracker(..., map_icp_means=(min_count, min_span)))")
+        rec = np.zeros(1, MAP_ICP_MEANS_RECORD_DTYPE)
+        _check(lib().vors_tracker_read_map_icp_means(self._h, _ptr(rec)))
+        return rec[0]
 
     def read_map_icp_joint(self):
         """The joint stage's record of the last track() on the host (vors_tracker_read_map_icp_joint; synchronises) -> a structured scalar
@@ -1334,6 +1357,25 @@ class Trackers:
         vors_map_icp_joint_record of every sequence beside map_icp()'s records, as bytes: decode_map_icp_joint_records(). copy=False: a view
         of the handle's own buffer, which dies with this object."""
         return self._views(lib().vors_trackers_map_icp_joint, copy, records=((MAP_ICP_JOINT_RECORD_DTYPE.itemsize,), "|u1"))["records"]
+
+    def enable_map_icp_means(self, min_count=1, min_span=0):
+        """The averaged map as the correction's model (vors_trackers_enable_map_icp_means): after enable_map_voxel_stats() and one of
+        enable_map_icp() / enable_map_icp_joint(), before init(), once. Every track() then resolves the window of each promoted sequence
+        (map_voxel_means()' rule with min_count, min_span, on the statistics as they stood before the promotion's emission) into staging
+        of the handle, and the correction's pass reads centroids and mean grey in the lists' place; rejected ranks are NaN rows the pass
+        skips and still count as `considered`."""
+        _check(lib().vors_trackers_enable_map_icp_means(self._h, _u32("min_count", min_count), _u32("min_span", min_span)))
+
+    def map_icp_means(self, copy=True):
+        """-> dict (vors_trackers_map_icp_means), valid in stream order after the last track(): "xyz_mean" [n, capacity, 3] float32 and
+        "gray_mean" [n, capacity] uint8 tensors — the staging: per sequence what its windows have written since init(), zero bytes
+        elsewhere — and "records", a structured numpy array [n] of MAP_ICP_MEANS_RECORD_DTYPE for the LAST track call (decoded:
+        synchronises). copy=False: the tensors are views of the handle's own buffers, which die with this object."""
+        cap = self._map[1] if self._map else 0  # (no map: the entry refuses)
+        out = self._views(lib().vors_trackers_map_icp_means, copy, xyz_mean=((cap, 3), "<f4"), gray_mean=((cap,), "|u1"),
+                          records=((MAP_ICP_MEANS_RECORD_DTYPE.itemsize,), "|u1"))
+        out["records"] = decode_map_icp_means_records(out["records"])
+        return out
 
     def map_icp(self, copy=True):
         """-> dict of tensors (vors_trackers_map_icp), valid in stream order after the last track(): "records" [n, 112] uint8 — the
@@ -2099,6 +2141,31 @@ def map_icp_joint_params(dist_m=_REQUIRED, **params):
 def decode_map_icp_joint_records(records):
     """The tensor of Trackers.map_icp_joint() ([n, 20] uint8) -> a structured numpy array [n] of MAP_ICP_JOINT_RECORD_DTYPE."""
     return _decode_records(records, MAP_ICP_JOINT_RECORD_DTYPE)
+
+
+class vors_map_icp_means_record(C.Structure):
+    """What the averaged model keeps per sequence of the last track call (include/vors_hip.h vors_map_icp_means_record, 8 bytes)."""
+    _fields_ = [("resolved", C.c_uint32), ("kept", C.c_uint32)]
+
+
+MAP_ICP_MEANS_RECORD_DTYPE = np.dtype([("resolved", "<u4"), ("kept", "<u4")])
+assert MAP_ICP_MEANS_RECORD_DTYPE.itemsize == C.sizeof(vors_map_icp_means_record) == 8
+
+
+def decode_map_icp_means_records(records):
+    """The bytes of vors_trackers_map_icp_means' records ([n, 8] uint8 tensor or array) -> a structured numpy array [n] of
+    MAP_ICP_MEANS_RECORD_DTYPE."""
+    return _decode_records(records, MAP_ICP_MEANS_RECORD_DTYPE)
+
+
+def _map_icp_means_args(arg):
+    """Tracker(map_icp_means=...): None, or (min_count[, min_span]) -> None or the two u32."""
+    if arg is None:
+        return None
+    arg = tuple(arg) if isinstance(arg, (tuple, list)) else (arg,)
+    if not 1 <= len(arg) <= 2:
+        raise VorsError("map_icp_means: (min_count[, min_span])")
+    return _u32("min_count", arg[0]), _u32("min_span", arg[1] if len(arg) > 1 else 0)
 
 
 def icp_condition_from_sums(sums29):
