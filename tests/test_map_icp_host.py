@@ -39,6 +39,13 @@ def window(seg, n_segments, max_keyframes, count, capacity, last_keyframes):
     ([0, 0, 40], 16, 1000),                 # empty keyframes
     ([], 16, 1000),                         # an empty map
     ([7], 1, 1),
+    ([100, 0, 0, 40, 0], 5, 1000),          # empty recorded segments share their `first` with their successor; a trailing one sits at the total
+    ([100, 0, 0, 40, 0], 3, 1000),          # ... and the last recorded segment is an empty one whose successor has no record
+    ([100, 0, 0, 40, 0], 5, 50),            # a capacity inside segment 0: every later `first` lies above the total
+    ([100, 0, 0, 40, 0], 3, 50),
+    ([100, 0, 0, 40, 0], 5, 120),           # a capacity inside segment 3: the trailing empty segment's `first` lies above the total
+    ([100, 0, 0, 40, 0], 3, 120),
+    ([100, 50, 70, 30, 20, 10], 2, 90),     # n_segments > max_keyframes and a capacity below the last recorded `first`
 ])
 def test_window_rule(counts, max_keyframes, capacity):
     seg, n_segments, count = segments(counts), len(counts), int(sum(counts))
@@ -50,6 +57,35 @@ def test_window_rule(counts, max_keyframes, capacity):
     if n_rec >= 2:
         assert V.map_icp_window_host(seg[:n_rec], n_segments, max_keyframes, count, capacity, 1)[0] == min(int(seg[n_rec - 1]["first"]), min(count, capacity))
     assert V.map_icp_window_host(None, n_segments, max_keyframes, count, capacity, 0) == (0, min(count, capacity))
+
+
+@pytest.mark.parametrize("counts, max_keyframes, capacity, last_keyframes, want", [
+    # the edges the cases above are meant to reach, written out by hand from the definition (no helper of this file enters)
+    ([100, 0, 0, 40, 0], 5, 1000, 1, (140, 0)),    # the trailing empty segment: an empty window at the total
+    ([100, 0, 0, 40, 0], 5, 1000, 2, (100, 40)),
+    ([100, 0, 0, 40, 0], 5, 1000, 3, (100, 40)),   # an empty segment's `first` is its successor's
+    ([100, 0, 0, 40, 0], 5, 1000, 4, (100, 40)),
+    ([100, 0, 0, 40, 0], 5, 1000, 5, (0, 140)),
+    ([100, 0, 0, 40, 0], 3, 1000, 1, (100, 40)),   # frozen at recorded segment 2, an empty one: the unrecorded keyframe 3 stays inside
+    ([100, 0, 0, 40, 0], 3, 1000, 2, (100, 40)),
+    ([100, 0, 0, 40, 0], 3, 1000, 3, (0, 140)),
+    ([100, 0, 0, 40, 0], 5, 50, 1, (50, 0)),       # `first` 140 above a total of 50
+    ([100, 0, 0, 40, 0], 5, 50, 4, (50, 0)),       # `first` 100 above a total of 50
+    ([100, 0, 0, 40, 0], 3, 50, 1, (50, 0)),
+    ([100, 0, 0, 40, 0], 3, 50, 0, (0, 50)),
+    ([100, 0, 0, 40, 0], 5, 120, 1, (120, 0)),     # `first` 140 above a total of 120
+    ([100, 0, 0, 40, 0], 5, 120, 2, (100, 20)),
+    ([100, 0, 0, 40, 0], 3, 120, 1, (100, 20)),
+    ([100, 50, 70, 30, 20, 10], 2, 90, 1, (90, 0)),     # the last recorded `first` is 100
+    ([100, 50, 70, 30, 20, 10], 2, 90, 2, (0, 90)),
+    ([100, 50, 70, 30, 20, 10], 3, 120, 1, (120, 0)),   # recorded segment 2 starts at 150
+    ([100, 50, 70, 30, 20, 10], 3, 120, 2, (100, 20)),
+])
+def test_window_edges_written_out(counts, max_keyframes, capacity, last_keyframes, want):
+    seg, n_segments, count = segments(counts), len(counts), int(sum(counts))
+    n_rec = min(n_segments, max_keyframes)
+    assert V.map_icp_window_host(seg[:n_rec], n_segments, max_keyframes, count, capacity, last_keyframes) == want
+    assert window(seg, n_segments, max_keyframes, count, capacity, last_keyframes) == want
 
 
 def test_window_saturated_count():
