@@ -10,6 +10,9 @@
  *  - Every function returns a vors_status (0 = ok, <0 = error); vors_last_error() gives the message of the last
  *    error on the calling thread.
  *  - Handles are NOT thread-safe (one thread per handle, mirroring `&mut self`); distinct handles are independent.
+ *    Tested: distinct handles of every kind, creation and destruction included, used from distinct host threads
+ *    at the same time give the bits of one thread's calls. The settings read once per process are read race-free
+ *    (function-local statics); the library never writes the environment.
  *  - Images: gray u8 and depth u16 (TUM scale, 0 = unknown), rows x cols, `layout` = VORS_ROW_MAJOR (decoder order)
  *    or VORS_COL_MAJOR (nalgebra DMatrix::as_slice(), element (row,col) at col*rows+row).
  *  - Poses / models: 7 floats  tx ty tz qx qy qz qw  (nalgebra Isometry3<f32>: translation + unit quaternion
@@ -571,9 +574,9 @@ vors_status vors_track_pairs(const vors_config* cfg, int n_pairs, const uint8_t*
  * (a hipStream_t passed as void*; NULL = default stream) and NOT synchronised: outputs are valid once the stream
  * reaches this point. Workspaces are allocated once at create() for up to max_pairs pairs. */
 typedef struct vors_batch vors_batch;
-/* Scheduling knobs (environment, read at create() — except VORS_DSO_SCAN, VORS_DSO_PLANES and VORS_PYRAMID_FUSED, which are read ONCE PER
- * PROCESS, at the first keyframe stage / pyramid; results stay within the stated tolerance whatever their value — they only
- * change how the same arithmetic is spread over the chip; tests/test_gpu_parity.py covers the variants):
+/* Scheduling knobs (environment, read at create() — except VORS_DSO_SCAN and VORS_DSO_PLANES, which are read at every keyframe stage, and
+ * VORS_PYRAMID_FUSED, which is read ONCE PER PROCESS, at the first pyramid, race-free; results stay within the stated tolerance whatever
+ * their value — they only change how the same arithmetic is spread over the chip; tests/test_gpu_parity.py covers the variants):
  *   VORS_LM_BLOCK=64..1024       threads per frame pair in the per-pair LM kernel (default by batch size and mode)
  *   VORS_LM_SPLIT=0              dense mode: one per-pair kernel for all levels instead of evaluation rounds
  *   VORS_LM_SPLIT_LEVELS=n       dense mode: the n finest levels are solved by evaluation rounds (default: levels of >= 64 Ki pixels)

@@ -176,15 +176,19 @@ __global__ __launch_bounds__(1024) void pyramid_fused_kernel(const uint8_t* __re
     }
 }
 
-static int g_pyramid_fused = -1;  // VORS_PYRAMID_FUSED=0 keeps one level per launch (development aid)
+// VORS_PYRAMID_FUSED=0 keeps one level per launch (development aid). Read once per process, at the first pyramid; a function-local
+// static, so two host threads that each build their first pyramid do not race on it.
+static bool pyramid_fused_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("VORS_PYRAMID_FUSED");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
 
 void launch_pyramid(const Geom& g, Pyramid pyr, int n_pairs, hipStream_t s) {
-    if (g_pyramid_fused < 0) {
-        const char* e = getenv("VORS_PYRAMID_FUSED");
-        g_pyramid_fused = (e && e[0] == '0') ? 0 : 1;
-    }
     int first = 1;
-    if (g_pyramid_fused && g.L >= 2 && g.lv[0].cols % 16 == 0 && ((uintptr_t)pyr.level0) % 16 == 0 && g.S0 % 16 == 0 &&
+    if (pyramid_fused_enabled() && g.L >= 2 && g.lv[0].cols % 16 == 0 && ((uintptr_t)pyr.level0) % 16 == 0 && g.S0 % 16 == 0 &&
         ((uintptr_t)pyr.upper) % 16 == 0 && g.upper_stride % 16 == 0) {
         PyrLevels lv{};
         lv.n = std::min(g.L - 1, 5);
@@ -906,7 +910,7 @@ void launch_zero_ints(const Geom& g, int* base, int stride, int n_pairs, hipStre
 // Region geometry of the coarse-to-fine keyframe kernel (read by batch.cpp when it sizes the handle): roots per wavefront, and
 // wavefront regions per pair.
 static int keyframe_roots_per_wave(const Geom& g) {
-    static int kf_r = getenv("VORS_KF_R") ? atoi(getenv("VORS_KF_R")) : 4;  // roots per wavefront (tuning knob)
+    static const int kf_r = getenv("VORS_KF_R") ? atoi(getenv("VORS_KF_R")) : 4;  // roots per wavefront (tuning knob)
     int r = kf_r >= 8 ? 8 : (kf_r >= 4 ? 4 : (kf_r >= 2 ? 2 : 1));
     while (r > 1 && (size_t)KF_WAVES * r * kf_nodes(g.L) * 16 > 64 * 1024) r >>= 1;  // stay inside the 64 KiB a workgroup may ask for
     return r;
