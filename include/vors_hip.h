@@ -709,6 +709,16 @@ void vors_multi_destroy(vors_multi* m);
  * This is the operator-level window on the tracker's own point sources; tests compare EXACT and FUSED through it. */
 vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const float model7[7], int arithmetic, float sums29[29]);
 
+/* What the go-on prediction of the dense FUSED evaluation rounds did with each of the first n_pairs pairs in the handle's last
+ * track: log (HOST, n_pairs ints) = OR of the bits below over the pair's level-0 candidates; all zero on a handle without the prediction.
+ * The prediction chooses a schedule, never a number, so no other output shows it: this is the window tests look through. Synchronises. */
+#define VORS_PREDICT_FULL 1        /* a candidate was predicted to go on and evaluated in full at once ... */
+#define VORS_PREDICT_FULL_GO_ON 2  /* ... and was accepted with the level going on: its g and H were kept */
+#define VORS_PREDICT_FULL_STOP 4   /* ... and was accepted with the level ending there */
+#define VORS_PREDICT_FULL_REJECTED 8 /* ... and was rejected */
+#define VORS_PREDICT_MISSED 16     /* a candidate that could have been predicted was not, and was accepted with the level going on */
+vors_status vors_batch_lm_predict_log(vors_batch* b, int n_pairs, int32_t* log);
+
 /* The same evaluation for a whole batch, device-resident: what scoring candidate motions against a keyframe (relocalisation, loop-closure
  * verification, a sweep of the energy around a solution) and the pose information below are made of.
  * VORS_EVAL_FULL = eval_energy + compute_eval_data (lm_optimizer.rs:68-107), VORS_EVAL_ENERGY = eval_energy alone (lm_optimizer.rs:68-87). */

@@ -166,6 +166,8 @@ struct SplitPlan {
     int chunks;      // = slots, or 0: no level is solved by rounds (launch_lm_track then runs the per-pair kernel for every level)
     int n_split, rounds;
     bool side_lane;
+    bool predict;    // a level-0 candidate whose step promises a go-on is evaluated in full at once (lm_kernels.hip lm_split_step_kernel)
+    float predict_tau;
 };
 static SplitPlan plan_split(const Geom& g, int max_pairs) {
     SplitPlan p{};
@@ -204,6 +206,12 @@ static SplitPlan plan_split(const Geom& g, int max_pairs) {
     const int side_from = (getenv("VORS_LM_SIDE") && atoi(getenv("VORS_LM_SIDE")) == 1) ? 512 : 2048;
     p.side_lane = p.chunks > 0 && p.n_split == 2 && max_pairs >= side_from && !(getenv("VORS_LM_SIDE") && atoi(getenv("VORS_LM_SIDE")) == 0);
     if (p.side_lane && !getenv("VORS_LM_SPLIT_ROUNDS")) p.rounds = 10;  // (the long tail of rounds was theirs; measured 8 / 10 / 12 / 16 / 26 at 4096 pairs)
+    // predicted go-ons (profiles/lm_predict_experiments/README.md): FUSED only — the promise is formed from the fast step's delta; the other
+    // arithmetics keep the plain schedule. VORS_LM_PREDICT=0 turns it off (development knob; the results are the same bits either way)
+    p.predict = p.chunks > 0 && g.arith == VORS_ARITH_FUSED && !(getenv("VORS_LM_PREDICT") && atoi(getenv("VORS_LM_PREDICT")) == 0);
+    // VORS_LM_PREDICT_TAU (development knob): the threshold on the promised decrease; tests set it far below and far above the default
+    // to make the prediction wrong in either direction
+    p.predict_tau = getenv("VORS_LM_PREDICT_TAU") ? (float)atof(getenv("VORS_LM_PREDICT_TAU")) : VORS_LM_PREDICT_TAU;
     return p;
 }
 
@@ -270,6 +278,9 @@ static void allocate_workspaces(vors_batch* b) {
         ws.chunks = sp.chunks;
         ws.n_split = sp.n_split;
         ws.rounds = sp.rounds;
+        ws.predict = sp.predict ? 1 : 0;
+        ws.predict_tau = sp.predict_tau;
+        if (sp.predict) own.alloc(&ws.pred_log, np);
         ws.cap = b->max_pairs;
         own.alloc(&ws.state, np);
         own.alloc(&ws.partials, np * sp.slots * 32);
@@ -631,6 +642,19 @@ vors_status vors_batch_eval_level(vors_batch* b, int pair, int level, const floa
     else launch_lm_eval_level_exact(b->g, call, nullptr);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(sums29, d_out.p, 29 * sizeof(float), hipMemcpyDeviceToHost));
+    return VORS_OK;
+}
+
+vors_status vors_batch_lm_predict_log(vors_batch* b, int n_pairs, int32_t* log) {
+    if (!b || !log) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_pairs < 0 || n_pairs > b->max_pairs) return fail(VORS_ERR_INVALID_ARGUMENT, "n_pairs out of range");
+    DeviceGuard guard(b->device);
+    HIP_TRY(hipDeviceSynchronize());
+    if (!b->split.pred_log) {  // no prediction on this handle (not dense FUSED, no level solved by rounds, VORS_LM_PREDICT=0)
+        for (int i = 0; i < n_pairs; ++i) log[i] = 0;
+        return VORS_OK;
+    }
+    HIP_TRY(hipMemcpy(log, b->split.pred_log, (size_t)n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost));
     return VORS_OK;
 }
 

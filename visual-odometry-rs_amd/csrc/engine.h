@@ -162,6 +162,11 @@ struct LmSplitState {  // per pair
     int lvl;           // level being solved
     int phase;         // 0 init evaluation pending (full), 1 candidate's energy pending, 4 accepted candidate's g and H pending (full),
                        // 2 all levels finished
+    int pred;          // written by the step kernel with phase 1 / 4, read only then (LmSplitWs::predict). Phase 1: 1 = the candidate was
+                       // predicted to go on and is due a FULL evaluation in a round of energy-only ones, its sums 0 and 1 added in the
+                       // energy-only kernel's order; 3 = it could have been predicted and was not (bookkeeping of LmSplitWs::pred_log
+                       // only). Phase 4: 2 = g and H are in `sums` already (taken from that evaluation): the pair sits
+                       // this round out, so that each of its later evaluations falls in the round it has without the prediction
     int went_well;     // 0: a level failed (the pair skips the remaining levels)
     // FUSED arithmetic: the evaluation context (H = K R K^-1, K t: lm_kernels.hip FusedCtx, 21 floats) of the model the NEXT round
     // evaluates at level `lvl` — formed once per pair and round by whoever sets that model (the step kernel, the coarse-level kernel's
@@ -171,6 +176,10 @@ struct LmSplitState {  // per pair
     int fctx_exact;
 };
 #define VORS_SPLIT_MAX_ROUNDS 62
+// Threshold of the go-on prediction on the promised decrease of the mean energy, in grey levels squared like the 1.0 of stop_criterion's
+// d_energy test (cost-model ESTIMATES from the CPU measurement, profiles/lm_predict_experiments/README.md: 0.75 / 1.0 / 1.25 -> 0.40 / 0.48 /
+// 0.42 ms per step)
+#define VORS_LM_PREDICT_TAU 1.0f
 struct LmSplitWs {
     LmSplitState* state;  // [pairs]
     float* partials;      // [pairs][chunks][32]
@@ -183,6 +192,9 @@ struct LmSplitWs {
     int chunks0;          // chunks per pair at level 0 in this launch (level l: chunks0 >> 2l), <= chunks
     int n_split;          // levels 0 .. n_split-1 are solved this way
     int rounds;
+    int predict;          // 1: level-0 candidates predicted to go on are evaluated in full at once (LmSplitState::pred); 0: never
+    float predict_tau;    // ... those whose step promises a decrease of the mean energy above this (lm_kernels.hip VORS_LM_PREDICT_TAU)
+    int* pred_log;        // [cap] what the prediction did with each pair in the last track (VORS_PREDICT_* bits, include/vors_hip.h); null: off
     // SIDE LANE (large dense batches, two levels solved by rounds): the few pairs still iterating at level 1 once everybody else has moved on
     // to level 0 would get ONE cheap evaluation per round while each round lasts milliseconds (level-0 evaluations of 4096 pairs), and then
     // keep ~20 more rounds alive on their own. After round `side_round` the step kernel hands them to a per-pair kernel on a second stream

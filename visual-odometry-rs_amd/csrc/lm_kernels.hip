@@ -859,7 +859,7 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, LmShared& s);  //
 // triangular solves by the stored reciprocals (6 v_rsq + multiplies instead of 6 IEEE square roots and 33 IEEE divisions, FMAs
 // contracted), and from_quaternion through one v_rsq. The one-lane step is ~40 % of the instructions the per-pair kernel issues in the
 // sparse modes (a few hundred points per evaluation); this form is about half as long. Same pivot rule (a pivot that is not > 0 fails).
-__device__ __forceinline__ bool lm_step_fast(const float* h, const float* g, const Iso& model, float lm_coef, Iso* out) {
+__device__ __forceinline__ bool lm_step_fast(const float* h, const float* g, const Iso& model, float lm_coef, Iso* out, float* delta_out = nullptr) {
     float a[6][6], inv[6];
 #pragma unroll
     for (int r = 0; r < 6; ++r)
@@ -899,6 +899,10 @@ __device__ __forceinline__ bool lm_step_fast(const float* h, const float* g, con
 #pragma unroll
         for (int k = i + 1; k < 6; ++k) acc = fmaf(-a[k][i], b[k], acc);
         b[i] = acc * inv[i];
+    }
+    if (delta_out) {  // (a compile-time fact at every call site)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) delta_out[i] = b[i];
     }
     // se3::exp (se3.rs:65-95) as in lie.h, from_quaternion by reciprocal square root
     const float vx = b[0], vy = b[1], vz = b[2], wx = b[3], wy = b[4], wz = b[5];
@@ -1078,7 +1082,8 @@ __device__ bool solve_level(const Src& src, int n_slots, const ImgCtx& c, Iso* m
     return true;
 }
 
-// Sum of two per-thread values over the workgroup (keyframe test, point counts). Ends with a barrier; result uniform.
+// Sum of two per-thread values over the workgroup (keyframe test, point counts). Result uniform. Its last barrier stands BEFORE the reads of
+// s.misc: a caller that writes s.misc again needs a barrier of its own in between.
 template <int BLOCK>
 __device__ __forceinline__ void block_sum2(float& a, float& b, LmShared& s) {
     a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_to_lane63(a)), 63));
@@ -1435,6 +1440,14 @@ lm_split_eval_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __
         const int chunks = split_chunks(ws, lvl);
         if (chunk >= chunks) continue;  // coarser levels are cut into fewer chunks
         const int phase = __builtin_amdgcn_readfirstlane(st->phase);
+        // A candidate predicted to go on (LmSplitState::pred; ENERGY = false only: such a pair stands in the full list): this evaluation
+        // stands in for the energy-only one the plain schedule runs in this very round, so its sums 0 and 1 are added in THAT kernel's
+        // order (block_sum2; block_reduce adds the 16-lane rows of a wavefront one after the other, block_sum2 pairwise) — per lane they
+        // are the same floats already: same units, same cut, the same expressions. Its g and H are what the plain schedule forms one
+        // round later at the same chunk count. A pair whose g and H were taken from such an evaluation sits this round out.
+        const int pred = ENERGY ? 0 : __builtin_amdgcn_readfirstlane(st->pred);
+        if (!ENERGY && phase == 4 && pred == 2) continue;
+        const bool energy_order = !ENERGY && phase == 1 && pred == 1;
         const Iso model = iso_uniform(iso_load(phase == 1 ? st->cand : st->model));
         const ImgCtx c = level_ctx(g, cur0, curu, pair, lvl);
         float acc[NACC];
@@ -1452,8 +1465,16 @@ lm_split_eval_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __
                 out[1] = cnt;
             }
         } else {
+            float e = acc[0], cnt = acc[1];
+            // (workgroup-uniform. block_sum2 reads s.misc after its last barrier: block_reduce writes s.part and s.sums only, and the barrier that
+            // ends this iteration stands before the next write of s.misc)
+            if (energy_order) block_sum2<SPLIT_BLOCK>(e, cnt, s);
             block_reduce<SPLIT_BLOCK>(acc, s, 0);
             if (threadIdx.x < NACC) out[threadIdx.x] = s.sums[0][threadIdx.x];
+            if (energy_order && threadIdx.x == 0) {
+                out[0] = e;
+                out[1] = cnt;
+            }
         }
         __syncthreads();
     }
@@ -1466,9 +1487,21 @@ lm_split_eval_kernel(Geom g, const uint8_t* __restrict__ cur0, const uint8_t* __
 // STEP_WAVES pairs per workgroup, one wavefront each: their appends to the next round's list share ONE atomic per kind and workgroup —
 // with a workgroup per pair the 4096 same-address atomics of a full round were the kernel (55 us; ~13 ns apiece).
 // (The late rounds concern a handful of pairs and are latency: one pair per workgroup there.)
+// The decrease of the mean energy that the quadratic model of the kept state (g, H: sums over its n inside points) promises for the step
+// delta of lm_step_fast: sum (r - J delta)^2 = sum r^2 - 2 g.delta + delta.H.delta. A NaN compares false: not predicted.
+__device__ __forceinline__ float lm_promised_decrease(const float* h36, const float* g6, const float* delta, float n) {
+    float gd = 0.f, dhd = 0.f;
+    for (int q = 0; q < 6; ++q) {
+        float hd = 0.f;
+        for (int r = 0; r < 6; ++r) hd = fmaf(h36[q * 6 + r], delta[r], hd);
+        gd = fmaf(g6[q], delta[q], gd);
+        dhd = fmaf(delta[q], hd, dhd);
+    }
+    return (2.0f * gd - dhd) / n;
+}
 template <int STEP_WAVES>
 __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, LmSplitWs ws, vors_pair_stats* __restrict__ out_stats, int round, int late,
-                                                                        int next_late) {
+                                                                        int next_late, int predict) {
     __shared__ float red_all[STEP_WAVES][32];
     __shared__ int s_kind[STEP_WAVES], s_base[3];
     const int n_active = split_n_active(ws, round);
@@ -1483,8 +1516,10 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
         const int lvl = st->lvl;
         const int chunks = split_chunks(ws, lvl);
         const int phase = st->phase;
-        const bool have_full = phase != 1 || late;  // an energy-only round wrote the first two sums only
-        const int n_sums = have_full ? NACC : 2;
+        const int pred = (phase == 1 || phase == 4) ? st->pred : 0;  // (LmSplitState::pred: written whenever one of these phases is)
+        const bool held = phase == 4 && pred == 2;                   // no evaluation this round: g and H are in st->sums
+        const bool have_full = phase != 1 || late || pred == 1;      // an energy-only evaluation wrote the first two sums only
+        const int n_sums = held ? 0 : (have_full ? NACC : 2);
         if (live && lane < n_sums) {  // chunks in index order; the loads of a batch of 8 are independent, the additions stay sequential
             const float* pp = ws.partials + (size_t)pair * ws.chunks * 32 + lane;
             float t = 0.f;
@@ -1501,12 +1536,13 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
         }
         __syncthreads();
         if (live && lane == 0) {
-            const float energy = red[0] / red[1];  // energy_sum / residuals.len(): 0/0 = NaN like the reference
+            const float energy = held ? 0.f : red[0] / red[1];  // energy_sum / residuals.len(): 0/0 = NaN like the reference (held: nothing was evaluated)
+            int log_bits = 0;  // (LmSplitWs::pred_log)
             Iso cur_model = iso_load(st->model);
             float lm_coef = st->lm_coef, cur_energy = st->cur_energy;
             int nb_iter = st->nb_iter;
             int n_full = st->n_full;  // the initial evaluation + every accepted candidate of this level so far (statistics)
-            bool take = false, done = false, need_gh = false;
+            bool take = false, done = false, need_gh = false, hold = false;
             if (phase == 0) {  // init: lm_optimizer.rs:113-118
                 take = true;
                 cur_energy = energy;
@@ -1514,7 +1550,7 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
                 nb_iter = 0;
                 n_full = 1;
             } else if (phase == 4) {  // g, H of the candidate accepted one round ago (now the kept model): on to its step()
-                take = true;
+                take = !held;         // (held: they were taken a round ago, with the candidate's energy)
             } else {
                 const LmVerdict v = lm_verdict(energy, cur_energy, nb_iter, lm_coef);  // eval()'s verdict + stop_criterion (lie.h)
                 if (lm_accepted(v)) {
@@ -1523,10 +1559,13 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
                     cur_model = iso_load(st->cand);
                 }
                 if (lm_stops(v)) done = true;
+                else if (lm_accepted(v) && pred == 1) hold = true;  // predicted, and it does go on: g and H are at hand a round early
                 else if (lm_accepted(v) && have_full) take = true;  // the level goes on from this candidate, its g and H are at hand
                 else if (lm_accepted(v)) need_gh = true;            // ... or are the business of the next round
+                if (pred == 1) log_bits |= hold ? VORS_PREDICT_FULL_GO_ON : (lm_accepted(v) ? VORS_PREDICT_FULL_STOP : VORS_PREDICT_FULL_REJECTED);
+                if (pred == 3 && need_gh) log_bits |= VORS_PREDICT_MISSED;
             }
-            bool again = false;
+            bool again = false, go_full = false;
             if (done) {  // level finished
                 if (out_stats) store_level_stats(out_stats, pair, lvl, true, nb_iter, n_full, cur_energy);
                 iso_store(cur_model, st->model);
@@ -1540,11 +1579,18 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
                 } else {
                     st->phase = 2;
                 }
-            } else if (need_gh) {
+            } else if (need_gh || hold) {
+                // hold: the sums are kept now and the step() waits one round, in which the pair is evaluated by nobody (the plain schedule
+                // forms g and H there). Stepping at once would move every later evaluation of the pair one round forward, some of them across
+                // the first late round, where the chunk count — the order of the partial sums — changes: other last bits than without the
+                // prediction. The rounds are bound by throughput, so the round of latency costs a large batch nothing.
+                if (hold)
+                    for (int q = 0; q < NACC; ++q) st->sums[q] = red[q];
                 iso_store(cur_model, st->model);
                 st->cur_energy = cur_energy;
                 st->lm_coef = lm_coef;
                 st->phase = 4;
+                st->pred = hold ? 2 : 0;
                 again = true;
             } else {  // step(): lm_optimizer.rs:123-136 on the kept state's sums
                 if (take) {
@@ -1565,9 +1611,21 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
                         ++k;
                     }
                 Iso cand;
-                if ((g.arith == VORS_ARITH_FUSED && !VORS_ABL_EXACT_STEP) ? lm_step_fast(h, gr, cur_model, lm_coef, &cand) : lm_step(h, gr, cur_model, lm_coef, &cand)) {
+                float delta[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (stays zero on the exact step: nothing is promised, nothing predicted)
+                if ((g.arith == VORS_ARITH_FUSED && !VORS_ABL_EXACT_STEP) ? lm_step_fast(h, gr, cur_model, lm_coef, &cand, delta) : lm_step(h, gr, cur_model, lm_coef, &cand)) {
                     iso_store(cand, st->cand);
                     st->phase = 1;
+                    // What the quadratic model promises this step: a decrease of the mean energy by (2 g.delta - delta.H.delta) / n. A level-0
+                    // candidate that promises more than VORS_LM_PREDICT_TAU was accepted with the level going on (LM_ACCEPTED_GO_ON) in all 135
+                    // cases among 512 pairs of the bench's batch, and 0.985 of the go-ons were such candidates; above level 0 the promise is
+                    // kept in 1 case of 7 and nothing is predicted (profiles/lm_predict_experiments/README.md). A predicted candidate gets its full evaluation at once instead of
+                    // an energy-only one now and the full one a round later. Only the schedule depends on this number, never a result.
+                    // (The iteration-limit test can only bite where VORS_LM_LATE_FROM widens the window below: by default a level-0 candidate
+                    // that may be predicted is the pair's first, second or third.)
+                    const bool may = predict && lvl == 0 && !lm_too_many_iterations(nb_iter);
+                    go_full = may && lm_promised_decrease(h, gr, delta, sm[1]) > ws.predict_tau;
+                    st->pred = go_full ? 1 : (may ? 3 : 0);
+                    if (go_full) log_bits |= VORS_PREDICT_FULL;
                     again = true;
                 } else {  // Cholesky failed: the level's progress is discarded and tracking stops (inverse_compositional.rs:195-199)
                     for (int q = 0; q < 7; ++q) st->model[q] = st->entry[q];
@@ -1578,10 +1636,12 @@ __global__ __launch_bounds__(64 * STEP_WAVES) void lm_split_step_kernel(Geom g, 
             }
             st->nb_iter = nb_iter;
             st->n_full = n_full;
+            if (ws.pred_log && log_bits) ws.pred_log[pair] |= log_bits;  // (this lane alone writes the pair's word)
             // FUSED arithmetic: the context of the evaluation this pair is due next, for all its workgroups (engine.h LmSplitState::fctx)
             if (again && g.arith == VORS_ARITH_FUSED) store_fused_ctx(g, st->lvl, iso_load(st->phase == 1 ? st->cand : st->model), st);
             // a candidate goes to the energy-only launch of the next round, unless that round is a late one (full evaluations only)
-            if (again) append_kind = (round == ws.side_round && st->lvl > 0) ? 2 : ((st->phase == 1 && !next_late) ? 1 : 0);  // 2: side lane
+            // ... or is predicted to go on
+            if (again) append_kind = (round == ws.side_round && st->lvl > 0) ? 2 : ((st->phase == 1 && !next_late && !go_full) ? 1 : 0);  // 2: side lane
         }
         if (lane == 0) s_kind[wave] = append_kind;
         __syncthreads();
@@ -1614,16 +1674,18 @@ __global__ __launch_bounds__(256) void lm_split_merge_kernel(LmSplitWs ws, int r
     for (int i = threadIdx.x; i < n; i += 256) ws.list[round & 1][atomicAdd(&ws.count[round], 1)] = ws.join_list[i];
 }
 void launch_lm_split_merge(LmSplitWs ws, int round, hipStream_t s) { hipLaunchKernelGGL(lm_split_merge_kernel, dim3(1), dim3(256), 0, s, ws, round); }
-void launch_lm_split_step(const Geom& g, LmSplitWs ws, vors_pair_stats* out_stats, int round, int late, int next_late, int grid, hipStream_t s) {
+void launch_lm_split_step(const Geom& g, LmSplitWs ws, vors_pair_stats* out_stats, int round, int late, int next_late, int predict, int grid,
+                          hipStream_t s) {
     if (grid >= 1024 && !late)
-        hipLaunchKernelGGL(lm_split_step_kernel<8>, dim3((grid + 7) / 8), dim3(512), 0, s, g, ws, out_stats, round, late, next_late);
+        hipLaunchKernelGGL(lm_split_step_kernel<8>, dim3((grid + 7) / 8), dim3(512), 0, s, g, ws, out_stats, round, late, next_late, predict);
     else
-        hipLaunchKernelGGL(lm_split_step_kernel<1>, dim3(grid), dim3(64), 0, s, g, ws, out_stats, round, late, next_late);
+        hipLaunchKernelGGL(lm_split_step_kernel<1>, dim3(grid), dim3(64), 0, s, g, ws, out_stats, round, late, next_late, predict);
 }
 #else
 // host-side launchers of the (arithmetic-independent) step and merge kernels, defined in the exact object
 void launch_lm_split_merge(LmSplitWs ws, int round, hipStream_t s);
-void launch_lm_split_step(const Geom& g, LmSplitWs ws, vors_pair_stats* out_stats, int round, int late, int next_late, int grid, hipStream_t s);
+void launch_lm_split_step(const Geom& g, LmSplitWs ws, vors_pair_stats* out_stats, int round, int late, int next_late, int predict, int grid,
+                          hipStream_t s);
 #endif
 
 // `n_groups` workgroups of `block` threads (rounded down to 1024 / 512 / 256 / 128 / 64) of the per-pair kernel
@@ -1793,6 +1855,7 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, const TrackCall& call, int block, Lm
     split.n_split = std::max(1, std::min(split.n_split, g.L));
     split.rounds = std::max(1, std::min(split.rounds, VORS_SPLIT_MAX_ROUNDS));
     (void)hipMemsetAsync(split.count, 0, SPLIT_COUNT_INTS * sizeof(int), s);
+    if (split.pred_log) (void)hipMemsetAsync(split.pred_log, 0, (size_t)n_pairs * sizeof(int), s);
     const int join_round = split.side_round >= 0 ? std::min(split.side_round + 3, split.rounds) : -1;
     launch_lm_track_mode(g, call, n_pairs, block, LM_COARSE_LEVELS, split, s);
     const int base_chunks = std::max(1, split.chunks / 4);
@@ -1813,15 +1876,23 @@ void VORS_LAUNCH_LM_TRACK(const Geom& g_in, const TrackCall& call, int block, Lm
         const int shrink = r < 2 * split.n_split ? 1 : (late ? 16 : 2);
         const int grid = std::max(std::min(full, 256), full / shrink);
         // Until the late rounds the pairs march roughly in step: full evaluations (a level's init, or the g / H of a candidate
-        // that goes on) dominate the even rounds, candidates' energies the odd ones; the other kind gets a small grid.
+        // that goes on) dominate the even rounds, candidates' energies the odd ones; the other kind gets a small grid. (The level-0
+        // candidates predicted to go on, a quarter of the pairs, have their full evaluation in an odd round: 1/8 of the full grid is still
+        // several workgroups per CU, and the grid-stride loop does the rest.)
         const int minor = std::max(std::min(full, 256), grid / 8);
-        const int grid_full = late ? grid : ((r & 1) ? minor : grid), grid_energy = (r & 1) ? grid : minor;
+        static const int pred_div_env = getenv("VORS_LM_PREDICT_GRID_DIV") ? std::max(1, atoi(getenv("VORS_LM_PREDICT_GRID_DIV"))) : 0;  // (development knob)
+        // ... but a quarter of the pairs of an odd round within the prediction's window are due a full evaluation there
+        const int minor_full = (split.predict && r >= 2 && r + 1 < std::min(late_from, split.rounds)) ? std::max(minor, grid / (pred_div_env ? pred_div_env : 8)) : minor;
+        const int grid_full = late ? grid : ((r & 1) ? minor_full : grid), grid_energy = (r & 1) ? grid : minor;
         with_bool(g.huber_delta > 0.f, [&](auto huber) {
             constexpr bool HUBER = decltype(huber)::value;
             launch_on_scene(lm_split_eval_kernel<HUBER, false, kFused>, dim3(grid_full), dim3(SPLIT_BLOCK), 0, s, g, call, split, r);
             if (!late && r > 0) launch_on_scene(lm_split_eval_kernel<HUBER, true, kFused>, dim3(grid_energy), dim3(SPLIT_BLOCK), 0, s, g, call, split, r);
         });
-        launch_lm_split_step(g, split, call.out_stats, r, late, next_late, std::max(1, n_pairs / shrink), s);
+        // A candidate may be predicted (lm_split_step_kernel) where the plain schedule has its energy-only evaluation AND the full one that
+        // follows in rounds before the late ones: the full evaluation that replaces both then runs with their chunk count.
+        const int predict = split.predict && r + 2 < std::min(late_from, split.rounds);
+        launch_lm_split_step(g, split, call.out_stats, r, late, next_late, predict, std::max(1, n_pairs / shrink), s);
         if (r == split.side_round) {  // fork: the pairs still above level 0 finish those levels on the side stream, one workgroup each
             (void)hipEventRecord(split.ev_fork, s);
             (void)hipStreamWaitEvent(split.side_stream, split.ev_fork, 0);

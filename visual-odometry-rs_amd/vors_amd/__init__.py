@@ -103,7 +103,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_create", "vors_batch_create_on", "vors_batch_device", "vors_batch_track_pairs", "vors_batch_prepare_keyframes", "vors_batch_track_current",
     "vors_batch_workspace_bytes", "vors_batch_enable_kernel_timing", "vors_batch_kernel_times", "vors_batch_last_kernel_ms",
     "vors_batch_destroy",
-    "vors_batch_get_keyframe_image", "vors_batch_get_current_image", "vors_batch_get_points", "vors_batch_eval_level",
+    "vors_batch_get_keyframe_image", "vors_batch_get_current_image", "vors_batch_get_points", "vors_batch_eval_level", "vors_batch_lm_predict_log",
     "vors_batch_eval_pairs", "vors_batch_pose_information", "vors_pose_information_from_sums",
     "vors_batch_residual_maps", "vors_residual_scale_from_hist",
     "vors_batch_reproject_depth", "vors_to_depth", "vors_from_depth",
@@ -274,6 +274,7 @@ def lib():
         _lib.vors_batch_get_current_image.argtypes = [vp, i, i, vp, C.POINTER(i), C.POINTER(i)]
         _lib.vors_batch_get_points.argtypes = [vp, i, i, i, vp, vp, vp, vp, C.POINTER(i)]
         _lib.vors_batch_eval_level.argtypes = [vp, i, i, vp, i, vp]
+        _lib.vors_batch_lm_predict_log.argtypes = [vp, i, vp]
         _lib.vors_batch_eval_pairs.argtypes = [vp, i, i, i, vp, C.c_size_t, i, i, vp, vp]
         _lib.vors_batch_pose_information.argtypes = [vp, i, i, vp, C.c_size_t, vp, vp, vp, vp, vp]
         _lib.vors_pose_information_from_sums.argtypes = [vp, vp, vp, C.POINTER(f), C.POINTER(C.c_int32)]
@@ -939,6 +940,12 @@ class Batch:
         _check(lib().vors_batch_track_pairs(self._h, n, self._dp(kf_gray), self._dp(kf_depth), self._dp(cur_gray),
                                             self._dp(prev_poses7), self._dp(out_poses7), self._dp(out_status),
                                             self._dp(out_stats), self._stream()))
+
+    def lm_predict_log(self, n_pairs):
+        """What the go-on prediction of the dense FUSED rounds did with each pair in the last track -> int32[n_pairs] of PREDICT_* bits."""
+        out = np.zeros(n_pairs, np.int32)
+        _check(lib().vors_batch_lm_predict_log(self._h, n_pairs, _ptr(out)))
+        return out
 
     def eval_level(self, pair, level, model7, arithmetic):
         """One evaluation of a level of a pair at `model7` in the given arithmetic -> (sum r^2, n_inside, g[6], H[6,6])."""
