@@ -608,6 +608,10 @@ vors_status vors_batch_create(const vors_config* cfg, int max_pairs, int rows, i
  * VORS_ERR_INVALID_ARGUMENT. Device buffers passed to the handle must live on that device. */
 vors_status vors_batch_create_on(int device, const vors_config* cfg, int max_pairs, int rows, int cols, vors_batch** out);
 vors_status vors_batch_device(const vors_batch* b, int* device);
+/* A dense handle of at least 4096 pairs runs a vors_batch_track_pairs call of at least 4096 pairs as two overlapped halves: pairs [0, h)
+ * on the caller's stream, pairs [h, n_pairs) on an internal stream forked from it at entry and joined before return. The
+ * call stays stream-ordered for the caller and capturable, and every output keeps its bits. VORS_BATCH_HALVES (read when the handle is
+ * created; development and test knob): 0 turns this off, 1 forces it from 2 pairs on. */
 vors_status vors_batch_track_pairs(vors_batch* b, int n_pairs, const uint8_t* d_kf_gray, const uint16_t* d_kf_depth,
                                    const uint8_t* d_cur_gray, const float* d_prev_poses7 /* nullable */,
                                    float* d_out_poses7, int32_t* d_out_status,

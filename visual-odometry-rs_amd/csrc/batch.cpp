@@ -215,10 +215,43 @@ static SplitPlan plan_split(const Geom& g, int max_pairs) {
     return p;
 }
 
+// Dense mode, large batches: one vors_batch_track_pairs call as two overlapped slices (host_common.h HalvesPlan). Decided once per handle,
+// from max_pairs; everything plan_split and plan_lm_block decide stays a function of the handle's max_pairs and never of a slice's size,
+// which is what keeps a pair's bits (tests/test_gpu_large_batches.py pins them against the pair's position and the count of the call).
+// Default threshold: measured at 4096 pairs of 640x480 only (profiles/batch_halves/README.md); smaller handles keep the plain path — among
+// them, by construction, every handle kind that must stay bit-identical to another: vors_tracker and lock-step handles below 512
+// sequences never reach 4096 pairs, and vors_trackers_* never calls vors_batch_track_pairs, the only entry that takes the plan.
+// VORS_BATCH_HALVES=0 turns the plan off, =1 forces it from 2 pairs on (development and test knobs, include/vors_hip.h).
+#ifndef VORS_BATCH_HALVES_FROM
+#define VORS_BATCH_HALVES_FROM 4096
+#endif
+struct HalvesDecision {
+    bool present;
+    int from, align, cap;
+};
+static HalvesDecision plan_halves(const Geom& g, int max_pairs) {
+    HalvesDecision p{};
+    const char* e = getenv("VORS_BATCH_HALVES");
+    p.from = (e && atoi(e) == 1) ? 2 : VORS_BATCH_HALVES_FROM;
+    p.present = g.mode == VORS_CANDIDATES_DENSE && !(e && atoi(e) == 0) && max_pairs >= p.from;
+    // the kernels choose their wide forms from the alignment of the level-0 buffers (kernels.hip launch_pyramid, launch_keyframe;
+    // lm_sources.h launch_geom): a slice that starts h pairs in keeps it when h * S0 is a multiple of 16 (every other per-pair stride is)
+    p.align = 1;
+    while (p.align < 16 && ((long long)g.S0 * p.align) % 16 != 0) p.align *= 2;
+    p.cap = std::max(1, max_pairs / 2);
+    return p;
+}
+// Pairs of the first slice of a call of n_pairs: half of them, rounded up to the alignment; 0 = the call takes the plain path.
+static int halves_cut(const HalvesPlan& hp, int n_pairs) {
+    if (!hp.present || n_pairs < hp.from) return 0;
+    const int h = ((n_pairs + 1) / 2 + hp.align - 1) / hp.align * hp.align;
+    return (h >= 1 && h < n_pairs) ? h : 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // ... and the allocations: one per buffer, recorded by b->own (host_common.h DeviceResources), checked once by the caller
 // ---------------------------------------------------------------------------------------------------------------
-static void allocate_workspaces(vors_batch* b) {
+static void allocate_workspaces(vors_batch* b, bool allow_halves) {
     const Geom& g = b->g;
     DeviceResources& own = b->own;
     const size_t np = (size_t)b->max_pairs;
@@ -296,6 +329,36 @@ static void allocate_workspaces(vors_batch* b) {
             own.event(&ws.ev_join, hipEventDisableTiming);
         }
     }
+    const HalvesDecision hd = plan_halves(g, b->max_pairs);
+    if (hd.present && allow_halves) {  // the second slice's own LM workspace (host_common.h HalvesPlan); with the two side lanes the handle opens three streams
+        HalvesPlan& hp = b->halves;
+        hp.present = true;
+        hp.from = hd.from;
+        hp.align = hd.align;
+        hp.cap = hd.cap;
+        const size_t nb = (size_t)hd.cap;
+        if (sp.present) {
+            LmSplitWs& ws = hp.split;
+            ws = b->split;  // the handle's decisions (chunks, levels, rounds, side round, prediction); pred_log is set per call
+            ws.cap = hd.cap;
+            own.alloc(&ws.state, nb);
+            own.alloc(&ws.partials, nb * sp.slots * 32);
+            own.alloc(&ws.list[0], nb);
+            own.alloc(&ws.list[1], nb);
+            own.alloc(&ws.count, (size_t)SPLIT_COUNT_INTS);
+            if (sp.side_lane) {
+                own.alloc(&ws.side_list, nb);
+                own.alloc(&ws.join_list, nb);
+                own.stream(&ws.side_stream, hipStreamNonBlocking);
+                own.event(&ws.ev_fork, hipEventDisableTiming);
+                own.event(&ws.ev_join, hipEventDisableTiming);
+            }
+        }
+        if (g.arith == VORS_ARITH_REFERENCE) own.alloc(&hp.handoff_counters, 2);
+        own.stream(&hp.stream, hipStreamNonBlocking);
+        own.event(&hp.ev_fork, hipEventDisableTiming);
+        own.event(&hp.ev_join, hipEventDisableTiming);
+    }
     if (g.mode == VORS_CANDIDATES_DENSE) {
         float2* lut = nullptr;
         own.alloc(&lut, (size_t)65536);
@@ -346,6 +409,115 @@ vors_status batch_track_current(vors_batch* b, int n_pairs, const uint8_t* d_cur
     return VORS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// a step as two overlapped slices (host_common.h HalvesPlan)
+// ---------------------------------------------------------------------------------------------------------------
+// What one slice of pairs [p0, p0 + n) of a call runs on: the handle's per-pair buffers advanced by p0 pairs, and the LM workspace of
+// its own. The launches are the plain path's, with the slice's count: a kernel sees pair k of the slice as pair k.
+struct Slice {
+    int p0, n;
+    hipStream_t s;
+    bool second;
+    Pyramid kf, cur;
+    const uint16_t* kf_depth;
+    Records rec;
+    LmSplitWs split;
+};
+static Slice make_slice(const vors_batch* b, int p0, int n, bool second, const uint8_t* kf_gray, const uint16_t* kf_depth, const uint8_t* cur_gray,
+                        hipStream_t s) {
+    const Geom& g = b->g;
+    const size_t p = (size_t)p0;
+    Slice v{p0, n, s, second, Pyramid{kf_gray + p * g.S0, b->kf_upper + p * g.upper_stride}, Pyramid{cur_gray + p * g.S0, b->cur_upper + p * g.upper_stride},
+            kf_depth + p * g.S0, b->rec, second ? b->halves.split : b->split};
+    Records& r = v.rec;
+    r.IZ += p * g.slots_total;
+    r.V += p * g.slots_total;
+    r.n_used += p * VORS_MAX_LEVELS;
+    if (r.dense_t.recs) {
+        r.dense_t.recs += p * ((size_t)g.S0 + g.upper_stride);
+        r.dense_t.n_valid += p * VORS_MAX_LEVELS;
+        r.dense_t.cur0 += p * g.S0;
+        r.dense_t.curu += p * g.upper_stride;
+    }
+    if (r.handoff.state) {
+        r.handoff.state += p;
+        r.handoff.list += p;
+        if (second) r.handoff.counters = b->halves.handoff_counters;
+    }
+    if (second) v.split.pred_log = b->split.pred_log ? b->split.pred_log + p : nullptr;  // the prediction log's slice
+    return v;
+}
+// The stage events of a slice: the first slice's are the plain ring's, the second slice's the ring's second set (StageTimers).
+static vors_status slice_stage_mark(vors_batch* b, const Slice& v, int st, bool end) {
+    StageTimers& t = b->timers;
+    if (t.ring <= 0) return VORS_OK;
+    const long idx = t.count[st] % t.ring;
+    HIP_TRY(hipEventRecord((v.second ? (end ? t.evb1 : t.evb0) : (end ? t.ev1 : t.ev0))[st][idx], v.s));
+    return VORS_OK;
+}
+static vors_status slice_pre_lm(vors_batch* b, const Slice& v) {
+    const Geom& g = b->g;
+    vors_status st;
+    if ((st = slice_stage_mark(b, v, 0, false)) != VORS_OK) return st;
+    launch_pyramid(g, v.kf, v.n, v.s);
+    if ((st = slice_stage_mark(b, v, 0, true)) != VORS_OK) return st;
+    if ((st = slice_stage_mark(b, v, 1, false)) != VORS_OK) return st;
+    launch_keyframe(g, v.kf, v.kf_depth, v.rec, v.n, v.s);
+    if (g.arith == VORS_ARITH_REFERENCE) launch_ref_dense_planes_keyframe(g, v.kf, v.kf_depth, v.rec, v.n, v.s);
+    if ((st = slice_stage_mark(b, v, 1, true)) != VORS_OK) return st;
+    if ((st = slice_stage_mark(b, v, 2, false)) != VORS_OK) return st;
+    launch_pyramid(g, v.cur, v.n, v.s);
+    if (g.arith == VORS_ARITH_REFERENCE) launch_ref_dense_planes_current(g, v.cur, v.rec, v.n, v.s);
+    return slice_stage_mark(b, v, 2, true);
+}
+static vors_status slice_lm(vors_batch* b, const Slice& v, const float* prev_poses7, float* out_poses7, int32_t* out_status, vors_pair_stats* out_stats) {
+    const Geom& g = b->g;
+    vors_status st;
+    if ((st = slice_stage_mark(b, v, 3, false)) != VORS_OK) return st;
+    const TrackCall call{{v.cur, v.kf, v.kf_depth, v.rec}, prev_poses7 ? prev_poses7 + (size_t)v.p0 * 7 : nullptr, nullptr, out_poses7 + (size_t)v.p0 * 7,
+                         out_status + v.p0, out_stats ? out_stats + v.p0 : nullptr, v.n};
+    if (g.arith == VORS_ARITH_REFERENCE) launch_lm_track_reference(g, call, b->ref_device, v.s);
+    else launch_lm_track(g, call, b->lm_block, v.split, v.s);
+    return slice_stage_mark(b, v, 3, true);
+}
+// vors_batch_track_pairs of a handle with the plan, for a call that reaches its threshold: pairs [0, h) on the caller's stream, pairs
+// [h, n_pairs) on the plan's stream, forked from the caller's stream at entry and joined back before return — the call stays purely
+// stream-ordered for the caller and capturable (the side lane's fork-and-join pattern). Order of issue: A's pyramids and keyframe stage,
+// B's, then A's LM stage, then B's.
+static vors_status track_pairs_halves(vors_batch* b, int n_pairs, int h, const uint8_t* d_kf_gray, const uint16_t* d_kf_depth, const uint8_t* d_cur_gray,
+                                      const float* d_prev_poses7, float* d_out_poses7, int32_t* d_out_status, vors_pair_stats* d_out_stats, hipStream_t s) {
+    if (!d_kf_gray || !d_kf_depth) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL image pointer");
+    if (!d_cur_gray || !d_out_poses7 || !d_out_status) return fail(VORS_ERR_INVALID_ARGUMENT, "NULL pointer");
+    DeviceGuard guard(b->device);
+    vors_status st = check_stream(b, s);
+    if (st != VORS_OK) return st;
+    HalvesPlan& hp = b->halves;
+    b->kf_level0 = d_kf_gray;
+    b->kf_depth = d_kf_depth;
+    b->cur_level0 = d_cur_gray;
+    b->prepared_pairs = b->current_pairs = n_pairs;
+    const Slice A = make_slice(b, 0, h, false, d_kf_gray, d_kf_depth, d_cur_gray, s);
+    const Slice B = make_slice(b, h, n_pairs - h, true, d_kf_gray, d_kf_depth, d_cur_gray, hp.stream);
+    HIP_TRY(hipEventRecord(hp.ev_fork, s));
+    HIP_TRY(hipStreamWaitEvent(hp.stream, hp.ev_fork, 0));
+    // (whatever fails below, the join is enqueued: nothing of this call may still run on the plan's stream behind the caller's back)
+    st = slice_pre_lm(b, A);
+    if (st == VORS_OK) st = slice_pre_lm(b, B);
+    if (st == VORS_OK) st = slice_lm(b, A, d_prev_poses7, d_out_poses7, d_out_status, d_out_stats);
+    if (st == VORS_OK) st = slice_lm(b, B, d_prev_poses7, d_out_poses7, d_out_status, d_out_stats);
+    HIP_TRY(hipEventRecord(hp.ev_join, hp.stream));
+    HIP_TRY(hipStreamWaitEvent(s, hp.ev_join, 0));
+    if (st != VORS_OK) return st;
+    StageTimers& t = b->timers;
+    if (t.ring > 0)
+        for (int k = 0; k < 4; ++k) {
+            t.two[k][t.count[k] % t.ring] = 1;
+            t.count[k] += 1;
+        }
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
 extern "C" {
 
 vors_status vors_batch_create(const vors_config* cfg, int max_pairs, int rows, int cols, vors_batch** out) {
@@ -358,6 +530,10 @@ vors_status vors_batch_create(const vors_config* cfg, int max_pairs, int rows, i
 }
 
 vors_status vors_batch_create_on(int device, const vors_config* cfg, int max_pairs, int rows, int cols, vors_batch** out) {
+    return batch_create_on(device, cfg, max_pairs, rows, cols, true, out);
+}
+
+vors_status batch_create_on(int device, const vors_config* cfg, int max_pairs, int rows, int cols, bool allow_halves, vors_batch** out) {
     if (!out) return fail(VORS_ERR_INVALID_ARGUMENT, "out is NULL");
     *out = nullptr;
     if (max_pairs < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "max_pairs must be >= 1");
@@ -378,7 +554,7 @@ vors_status vors_batch_create_on(int device, const vors_config* cfg, int max_pai
         b->ref_device = query_ref_device(device);
         (void)hipGetLastError();  // (an attribute this runtime does not know: the default stands)
     }
-    allocate_workspaces(b.get());
+    allocate_workspaces(b.get(), allow_halves);
     if (b->own.err != hipSuccess) return fail(VORS_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(b->own.err));
     if (b->rec.LUT) launch_build_depth_lut(g.depth_scale, const_cast<float2*>(b->rec.LUT), nullptr);
     if (g.mode == VORS_CANDIDATES_DENSE) b->g.fast_idepth = (!getenv("VORS_NO_FASTDIV") && verify_fast_idepth(g.depth_scale, nullptr)) ? 1 : 0;
@@ -427,9 +603,17 @@ vors_status vors_batch_enable_kernel_timing(vors_batch* b, int ring) {
     for (int st = 0; st < 4; ++st) {
         t.ev0[st].assign(ring, nullptr);
         t.ev1[st].assign(ring, nullptr);
+        t.two[st].assign(ring, 0);
         for (int k = 0; k < ring; ++k) {
             HIP_TRY(hipEventCreate(&t.ev0[st][k]));
             HIP_TRY(hipEventCreate(&t.ev1[st][k]));
+        }
+        if (!b->halves.present) continue;
+        t.evb0[st].assign(ring, nullptr);
+        t.evb1[st].assign(ring, nullptr);
+        for (int k = 0; k < ring; ++k) {
+            HIP_TRY(hipEventCreate(&t.evb0[st][k]));
+            HIP_TRY(hipEventCreate(&t.evb1[st][k]));
         }
     }
     t.ring = ring;
@@ -481,10 +665,37 @@ vors_status vors_batch_track_current(vors_batch* b, int n_pairs, const uint8_t* 
 vors_status vors_batch_track_pairs(vors_batch* b, int n_pairs, const uint8_t* d_kf_gray, const uint16_t* d_kf_depth,
                                    const uint8_t* d_cur_gray, const float* d_prev_poses7, float* d_out_poses7,
                                    int32_t* d_out_status, vors_pair_stats* d_out_stats, void* hip_stream) {
+    if (b && n_pairs >= 1 && n_pairs <= b->max_pairs && halves_cut(b->halves, n_pairs) > 0)
+        return track_pairs_halves(b, n_pairs, halves_cut(b->halves, n_pairs), d_kf_gray, d_kf_depth, d_cur_gray, d_prev_poses7, d_out_poses7,
+                                  d_out_status, d_out_stats, static_cast<hipStream_t>(hip_stream));
     vors_status st = vors_batch_prepare_keyframes(b, n_pairs, d_kf_gray, d_kf_depth, hip_stream);
     if (st != VORS_OK) return st;
     return vors_batch_track_current(b, n_pairs, d_cur_gray, d_prev_poses7, d_out_poses7, d_out_status, d_out_stats, hip_stream);
 }
+
+}  // extern "C"
+// Duration of stage `st` of the step in ring entry `idx`. A step that ran as two halves (host_common.h HalvesPlan): the pyramids and the
+// keyframe stage are the SUM of the two slices' own intervals; the LM stage runs from the first LM start of either slice to the last LM
+// end. The slices overlap, so these figures no longer add up to the step.
+static vors_status stage_ms(vors_batch* b, int st, long idx, float* ms) {
+    StageTimers& t = b->timers;
+    HIP_TRY(hipEventSynchronize(t.ev1[st][idx]));
+    HIP_TRY(hipEventElapsedTime(ms, t.ev0[st][idx], t.ev1[st][idx]));
+    if (!t.two[st][idx]) return VORS_OK;
+    float second = 0.f;
+    HIP_TRY(hipEventSynchronize(t.evb1[st][idx]));
+    HIP_TRY(hipEventElapsedTime(&second, t.evb0[st][idx], t.evb1[st][idx]));
+    if (st != 3) {
+        *ms += second;
+        return VORS_OK;
+    }
+    float a_to_b = 0.f, b_to_a = 0.f;
+    HIP_TRY(hipEventElapsedTime(&a_to_b, t.ev0[st][idx], t.evb1[st][idx]));
+    HIP_TRY(hipEventElapsedTime(&b_to_a, t.evb0[st][idx], t.ev1[st][idx]));
+    *ms = std::max(std::max(*ms, second), std::max(a_to_b, b_to_a));
+    return VORS_OK;
+}
+extern "C" {
 
 vors_status vors_batch_kernel_times(vors_batch* b, int stage, float* ms_out, int capacity, int* n_out) {
     if (!b || !n_out || stage < 0 || stage > 3 || (capacity > 0 && !ms_out)) return fail(VORS_ERR_INVALID_ARGUMENT, "bad argument");
@@ -494,8 +705,8 @@ vors_status vors_batch_kernel_times(vors_batch* b, int stage, float* ms_out, int
     for (int k = 0; k < n && k < capacity; ++k) {
         // oldest first
         const long idx = (b->timers.count[stage] - n + k) % b->timers.ring;
-        HIP_TRY(hipEventSynchronize(b->timers.ev1[stage][idx]));
-        HIP_TRY(hipEventElapsedTime(&ms_out[k], b->timers.ev0[stage][idx], b->timers.ev1[stage][idx]));
+        vors_status st = stage_ms(b, stage, idx, &ms_out[k]);
+        if (st != VORS_OK) return st;
     }
     return VORS_OK;
 }
@@ -507,8 +718,8 @@ vors_status vors_batch_last_kernel_ms(vors_batch* b, float* lm_ms, float* keyfra
     for (int st = 0; st < 4; ++st)
         if (b->timers.ring > 0 && b->timers.count[st] > 0) {
             const long idx = (b->timers.count[st] - 1) % b->timers.ring;
-            HIP_TRY(hipEventSynchronize(b->timers.ev1[st][idx]));
-            HIP_TRY(hipEventElapsedTime(&v[st], b->timers.ev0[st][idx], b->timers.ev1[st][idx]));
+            vors_status rc = stage_ms(b, st, idx, &v[st]);
+            if (rc != VORS_OK) return rc;
         }
     if (lm_ms) *lm_ms = v[3];
     if (keyframe_ms) *keyframe_ms = v[1];

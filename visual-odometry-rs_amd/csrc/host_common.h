@@ -115,9 +115,13 @@ struct DeviceResources {
 
 // Per-stage HIP-event ring (stage: 0 keyframe pyramid, 1 keyframe precompute, 2 current pyramid, 3 LM kernel).
 // Events are only RECORDED on the caller's stream during a step (non-blocking); elapsed times are read afterwards.
+// A step that ran as two halves (HalvesPlan below) has a second interval per stage, the second half's on its own stream (evb0 / evb1, created
+// with the others; `two` marks the ring entries that hold one): vors_batch_kernel_times adds the two intervals of a pre-LM stage and takes
+// the LM stage from the first start of either half to the last end.
 struct StageTimers {
     int ring = 0;
-    std::vector<hipEvent_t> ev0[4], ev1[4];
+    std::vector<hipEvent_t> ev0[4], ev1[4], evb0[4], evb1[4];
+    std::vector<char> two[4];
     long count[4] = {0, 0, 0, 0};
     StageTimers() = default;
     StageTimers(const StageTimers&) = delete;
@@ -126,7 +130,8 @@ struct StageTimers {
     void clear() {  // ring -> 0: no stage is timed
         ring = 0;
         for (int st = 0; st < 4; ++st) {
-            for (auto* ring_events : {&ev0[st], &ev1[st]}) {
+            two[st].clear();
+            for (auto* ring_events : {&ev0[st], &ev1[st], &evb0[st], &evb1[st]}) {
                 for (hipEvent_t e : *ring_events)
                     if (e) (void)hipEventDestroy(e);
                 ring_events->clear();
@@ -143,9 +148,26 @@ struct StageTimers {
     do {                      \
         if ((b)->timers.ring > 0) {  \
             HIP_TRY(hipEventRecord((b)->timers.ev1[st][(b)->timers.count[st] % (b)->timers.ring], s)); \
+            (b)->timers.two[st][(b)->timers.count[st] % (b)->timers.ring] = 0; \
             (b)->timers.count[st] += 1; \
         }                     \
     } while (0)
+
+// One dense vors_batch_track_pairs call as two slices of pairs, [0, h) on the caller's stream and [h, n_pairs) on `stream`, so that each
+// slice's dependent tails (round boundaries, late rounds, stragglers, epilogue) are filled by the other slice; as measured, the two slices'
+// pre-LM stages run side by side from the fork on and the two LM stages side by side after them (batch.cpp plan_halves, track_pairs_halves). Per-pair buffers are shared: a slice addresses them through
+// pointers advanced by h pairs. What an LM stage shares through the handle exists once per slice: `split` (state, partials, lists,
+// counters, side lane with its stream and events; pred_log points into the first slice's) and the REFERENCE hand-over counters.
+struct HalvesPlan {
+    bool present = false;
+    int from = 0;         // calls of at least this many pairs take the plan
+    int align = 1;        // h is a multiple of this many pairs: a slice's level-0 buffers then keep the 16-byte alignment of the caller's
+    int cap = 0;          // most pairs of the second slice
+    vors::LmSplitWs split{};
+    int* handoff_counters = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+};
 
 struct vors_batch {
     vors_config cfg;
@@ -161,6 +183,7 @@ struct vors_batch {
     const uint16_t* kf_depth = nullptr;   // caller's depth buffer of the last prepare_keyframes (read by the dense LM kernel)
     vors::Records rec{};
     vors::LmSplitWs split{};
+    HalvesPlan halves;  // large dense handles: one track_pairs call as two overlapped slices (off: halves.present == false)
     vors::EvalPairsWs eval_pairs{};  // vors_batch_eval_pairs / _pose_information: allocated by the first of those calls (items = 0 until then)
     uint32_t* cloud_counts = nullptr;  // vors_batch_point_cloud: [max_pairs][cloud_chunks] kept points per chunk, allocated by its first call
     int cloud_chunks = 0;
@@ -209,6 +232,11 @@ struct IcpArgs {
 // `who`, then launch_icp_points on s. Internal: hidden, so that the library's dynamic symbols stay the ones it had.
 __attribute__((visibility("hidden"))) vors_status icp_points_device(const char* who, const IcpArgs& args, hipStream_t s);
 }
+// vors_batch_create_on with one more decision: allow_halves = false keeps the handle on the plain path whatever its size (HalvesPlan is
+// then never created). A vors_pipeline slot is created so: its steps already overlap with its neighbours', on the ring's own streams.
+// Internal: hidden, so that the library's dynamic symbols stay the ones it had.
+extern "C" __attribute__((visibility("hidden"))) vors_status batch_create_on(int device, const vors_config* cfg, int max_pairs, int rows, int cols,
+                                                                           bool allow_halves, vors_batch** out);
 // The stream work is enqueued on must belong to the handle's device (a stream of another device would silently run nothing useful).
 vors_status check_stream(const vors_batch* b, hipStream_t s);
 // Tracker::track up to the keyframe test for the prepared keyframes of `b`, with the keyframe poses on the device (batch.cpp;

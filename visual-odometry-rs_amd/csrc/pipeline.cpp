@@ -47,7 +47,9 @@ vors_status vors_pipeline_create(int device, const vors_config* cfg, int depth, 
     p->depth = depth;
     for (int k = 0; k < depth; ++k) {
         vors_batch* b = nullptr;
-        vors_status st = vors_batch_create_on(device, cfg, max_pairs, rows, cols, &b);
+        // (a slot keeps the plain path: the ring already runs a step's memory-bound stages under its neighbour's LM stage, and a plan
+        // per slot would put three more streams per slot on the process's four hardware queues — host_common.h HalvesPlan)
+        vors_status st = batch_create_on(device, cfg, max_pairs, rows, cols, false, &b);
         if (st != VORS_OK) return st;
         // a slot of a ring shares the chip with its neighbours' steps (engine.h Geom::ref_inflight_x2): measured at 512 pairs per step, ring of 3,
         // REFERENCE: coarse-to-fine 0.556 ms per step with the lone step's 5 wavefronts per pair, 0.458 with 4; DSO 0.889 / 0.752
