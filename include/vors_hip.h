@@ -138,7 +138,9 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_tracker_enable_map_voxel_stats, vors_tracker_read_map_voxel_stats, vors_tracker_map_voxel_means,
                               *    vors_voxel_means, vors_voxel_means_host, vors_voxel_stats_host, likewise; + vors_trackers_enable_map_icp_means,
                               *    vors_trackers_map_icp_means, vors_tracker_enable_map_icp_means, vors_tracker_read_map_icp_means,
-                              *    vors_map_icp_means_record, likewise) */
+                              *    vors_map_icp_means_record, likewise; + vors_undistort_frames, vors_undistort_frame_host,
+                              *    vors_undistort_source_host, vors_register_depth, vors_register_depth_host, VORS_UNDISTORT_COUNTS,
+                              *    VORS_REGISTER_COUNTS, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -1241,6 +1243,84 @@ typedef struct vors_map_icp_means_record {
  * Refused: a NULL argument, the verdict fields vors_trackers_enable_map_icp refuses, a dilution bound negative or NaN. */
 vors_status vors_map_icp_verdict_joint_host(const vors_map_icp_joint_params* params, const vors_icp_stats* stats, const float pose_before[7],
                                             const float pose_after[7], float dilution_t, float dilution_r, uint32_t* verdict);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2f. SENSOR FRONT END, device-resident and handle-free (the reference has none and ignores lens distortion): what turns
+ *     a real RGB-D stream into the three things every other entry assumes — an ideal pinhole grey image, a u16 depth map registered to
+ *     it pixel for pixel, and one cu cv fu fv skew for both.
+ *
+ * vors_undistort_frames: n planes of grey u8 and / or depth u16, [n][in_rows * in_cols] row-major (DEVICE, each nullable, one required),
+ *   of the real camera cam_in5 (HOST) with Brown-Conrady coefficients dist5 = k1 k2 p1 p2 k3 (HOST; NULL = all zero), resampled into the
+ *   ideal camera cam_out5 (HOST) of out_rows x out_cols pixels (crops and re-centred cameras are the normal case).
+ * SOURCE COORDINATE of output pixel (x, y), in f32, in the written order, without FMA:
+ *     (X, Y, 1) = back_project(K_out, (float)x, (float)y, 1.0f)        (Y = (y - cv) / fv, X = ((x - cu) - skew * Y) / fu)
+ *     xx = X*X;  yy = Y*Y;  xy = X*Y;  r2 = xx + yy
+ *     rad = 1.0f + r2 * (k1 + r2 * (k2 + r2 * k3))
+ *     Xd = (X * rad + (2.0f * p1) * xy) + p2 * (r2 + 2.0f * xx)
+ *     Yd = (Y * rad + p1 * (r2 + 2.0f * yy)) + (2.0f * p2) * xy
+ *     u = (fu_in * Xd + skew_in * Yd) + cu_in;   v = fv_in * Yd + cv_in
+ * GREY: bilinear in lerp form. x0 = floorf(u), a = u - x0, x1 = min(x0 + 1, in_cols - 1), rows likewise with b; t0 = I00 + a * (I01 - I00),
+ *   t1 = I10 + a * (I11 - I10), val = t0 + b * (t1 - t0), all in f32; the output is floorf(val + 0.5f) clamped to 0..255. A pixel is inside
+ *   iff 0 <= u <= in_cols - 1 and 0 <= v <= in_rows - 1, compared in float before any conversion (NaN fails). border = 0 writes 0
+ *   outside; border = 1 clamps u and v into the plane first (edge replicate); a NaN coordinate still writes 0.
+ * DEPTH: never interpolated. xs = floorf(u + 0.5f), ys = floorf(v + 0.5f) (the landing rule of vors_batch_reproject_depth); the output is
+ *   D[ys][xs] if that pixel lies inside the plane (tested in float), else 0. border does not apply: depth is never invented.
+ * Outputs (DEVICE, each nullable, at least one required; every output pixel is written): d_gray_out / d_depth_out [n][out_rows * out_cols];
+ *   d_map [out_rows * out_cols][2] f32 = (u, v), written once, not per plane; d_counts [n][VORS_UNDISTORT_COUNTS] u32 = {pixels: out_rows *
+ *   out_cols; grey inside: the pixels whose (u, v) lies inside the plane, whatever the border mode and whether or not there is a grey
+ *   plane; depth inside and non-zero: the pixels of d_depth_out that are not 0 (0 without a depth plane)}.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued and nothing written: n < 1; both input planes NULL; d_gray_out without d_gray or
+ *   d_depth_out without d_depth; no output at all; a NULL cam_in5 or cam_out5; a non-finite coefficient or camera value, fu or fv equal
+ *   to 0; border outside 0..1; any of the four sizes < 1 or > 65535, or a plane above 2^28 pixels; a pointer off its natural alignment
+ *   (depth planes: 2 bytes, d_map and d_counts: 4). Enqueued on hip_stream on the calling thread's current device, NOT synchronised, no
+ *   allocation ever: a memset of the counters when they are asked for and one kernel; no workgroup waits for another. The one text
+ *   (lie.h undistort_source, undistort_taps, undistort_gray) runs on the host and on the device: the device results equal
+ *   vors_undistort_frame_host's bit for bit. */
+#define VORS_UNDISTORT_COUNTS 3
+vors_status vors_undistort_frames(int n, const uint8_t* d_gray /* nullable */, const uint16_t* d_depth /* nullable */, int in_rows, int in_cols,
+                                  const float cam_in5[5], const float dist5[5] /* nullable */, const float cam_out5[5], int out_rows,
+                                  int out_cols, int border, uint8_t* d_gray_out /* nullable */, uint16_t* d_depth_out /* nullable */,
+                                  float* d_map /* nullable */, uint32_t* d_counts /* nullable */, void* hip_stream);
+/* The same rule for ONE plane of each kind on the host (host arithmetic, needs no GPU; the text the kernel runs): HOST pointers, counts
+ * [VORS_UNDISTORT_COUNTS]. The refusals above, with nothing written. */
+vors_status vors_undistort_frame_host(const uint8_t* gray /* nullable */, const uint16_t* depth /* nullable */, int in_rows, int in_cols,
+                                      const float cam_in5[5], const float dist5[5] /* nullable */, const float cam_out5[5], int out_rows,
+                                      int out_cols, int border, uint8_t* gray_out /* nullable */, uint16_t* depth_out /* nullable */,
+                                      float* map /* nullable */, uint32_t counts[VORS_UNDISTORT_COUNTS] /* nullable */);
+/* The source coordinates alone, for a list of output pixels on the host: xy [n_pixels][2] int32 (x, y), anywhere — the ideal camera has no
+ * border — -> uv [n_pixels][2] f32. Refused: n_pixels < 0, a NULL xy or uv with n_pixels > 0, and what the above refuse of the cameras
+ * and the coefficients. */
+vors_status vors_undistort_source_host(const float cam_in5[5], const float dist5[5] /* nullable */, const float cam_out5[5], int n_pixels,
+                                       const int32_t* xy, float* uv);
+/* vors_register_depth: n depth planes d_depth [n][d_rows * d_cols] u16 (DEVICE) of a PINHOLE depth camera dcam5 (HOST) with depth_scale_in
+ *   (a distorted depth camera goes through vors_undistort_frames first), seen from the colour camera ccam5 (HOST) of c_rows x c_cols pixels
+ *   with depth_scale_out. pose7 (HOST, nullable): depth camera -> colour camera, tx ty tz qi qj qk qw; NULL = no transform at all.
+ * PER SOURCE PIXEL s = y * d_cols + x with d != 0: z = 1.0f / (depth_scale_in / (float)d), P = back_project(K_d, (float)x, (float)y, z) —
+ *   the camera-frame bits of vors_batch_point_cloud —, c = rotation * P + translation (the point cloud's camera -> world text), then
+ *   exactly vors_render_points' rule for the point c in the camera ccam5 WITHOUT a pose: Z' = c.z, the candidate test, the footprint
+ *   (1..3) and the key (uint64)bits(Z') << 32 | s, entered into d_zkey [n][c_rows * c_cols] (DEVICE, REQUIRED, 8-byte aligned) by an
+ *   unsigned 64-bit minimum; VORS_ZKEY_EMPTY where nothing lands. The nearest surface wins, among equal Z' bits the lowest source index:
+ *   bitwise reproducible whatever the order of arrival.
+ * Outputs (DEVICE, each nullable): d_depth_out [n][c_rows * c_cols] u16 = to_depth(depth_scale_out, 1.0f / Z') of the key, 0 where empty;
+ *   d_src_index [n][c_rows * c_cols] u32 = the winning s, 0xFFFFFFFF where empty (with it a caller carries IR, confidence or the depth
+ *   filter's weight plane across); d_counts [n][VORS_REGISTER_COUNTS] u32 = {with depth: the source pixels with d != 0; in front: those
+ *   with Z' > 0; landed; covered: the colour pixels whose key is not empty}.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued and nothing written: n < 1; a NULL d_depth, dcam5 or ccam5; a NULL or misaligned
+ *   d_zkey; footprint outside 1..3; any of the four sizes < 1 or > 65535, or a plane above 2^28 pixels; a depth scale not > 0; a pointer
+ *   off its natural alignment (depth planes: 2 bytes, d_src_index and d_counts: 4). Enqueued on hip_stream on the calling thread's current
+ *   device, NOT synchronised, no allocation ever: the fill of the key planes, a memset of the counters when they are asked for, the splat
+ *   kernel and — with any of d_depth_out, d_src_index, d_counts — the resolve kernel, ordered by the stream. */
+#define VORS_REGISTER_COUNTS 4
+vors_status vors_register_depth(int n, const uint16_t* d_depth, const float dcam5[5], int d_rows, int d_cols, float depth_scale_in,
+                                const float pose7[7] /* nullable */, const float ccam5[5], int c_rows, int c_cols, float depth_scale_out,
+                                int footprint, uint64_t* d_zkey, uint16_t* d_depth_out /* nullable */, uint32_t* d_src_index /* nullable */,
+                                uint32_t* d_counts /* nullable */, void* hip_stream);
+/* The same rule for ONE plane on the host (host arithmetic, needs no GPU; the text the kernels run): HOST pointers, zkey [c_rows * c_cols]
+ * required here too (it is the z-buffer). The refusals above, with nothing written. */
+vors_status vors_register_depth_host(const uint16_t* depth, const float dcam5[5], int d_rows, int d_cols, float depth_scale_in,
+                                     const float pose7[7] /* nullable */, const float ccam5[5], int c_rows, int c_cols, float depth_scale_out,
+                                     int footprint, uint64_t* zkey, uint16_t* depth_out /* nullable */, uint32_t* src_index /* nullable */,
+                                     uint32_t counts[VORS_REGISTER_COUNTS] /* nullable */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

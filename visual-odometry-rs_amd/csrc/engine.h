@@ -533,6 +533,48 @@ void launch_points_normals(const NormalCall& call, hipStream_t s);
 // dst[i] = src[i] for the n running totals of the keyframe map (the ranks an emission starts from), honouring nothing: every sequence.
 void launch_normals_snapshot(const uint32_t* src, uint32_t* dst, int n, hipStream_t s);
 
+// The sensor front end (vors_undistort_frames, vors_register_depth; frontend_kernels.hip). Handle-free: everything the
+// kernels read is here, the cameras, the coefficients and the pose by value. Every output is nullable (the entries ask for what they need).
+struct UndistortCall {
+    int n;                       // planes
+    const uint8_t* gray;         // [n][in_rows * in_cols], nullable
+    const uint16_t* depth;       // [n][in_rows * in_cols], nullable
+    int in_rows, in_cols;
+    Intr k_in;
+    Dist5 dist;
+    Intr k_out;
+    int out_rows, out_cols;
+    int border;                  // 0 = zero outside, 1 = edge replicate (grey only)
+    uint8_t* gray_out;           // [n][out_rows * out_cols]
+    uint16_t* depth_out;         // [n][out_rows * out_cols]
+    float* map;                  // [out_rows * out_cols][2], written once (by the first plane's workgroups)
+    uint32_t* counts;            // [n][VORS_UNDISTORT_COUNTS]
+};
+struct RegisterCall {
+    int n;                       // planes
+    const uint16_t* depth;       // [n][d_rows * d_cols]
+    Intr k_d;
+    int d_rows, d_cols;
+    float scale_in;
+    bool has_pose;
+    Iso pose;                    // depth camera -> colour camera
+    Intr k_c;
+    int c_rows, c_cols;
+    float scale_out;
+    int footprint;               // 1, 2 or 3
+    uint64_t* zkey;              // [n][c_rows * c_cols]
+    uint16_t* depth_out;         // [n][c_rows * c_cols]
+    uint32_t* src_index;         // [n][c_rows * c_cols]
+    uint32_t* counts;            // [n][VORS_REGISTER_COUNTS]
+};
+#define FRONT_BLOCK 256
+#define FRONT_POINTS 4  // pixels per thread
+// A memset of the counters when they are asked for, then one kernel; enqueued on s, not synchronised, no workspace.
+void launch_undistort(const UndistortCall& call, hipStream_t s);
+// Fill of the key planes, a memset of the counters when they are asked for, the splat and — with any of depth_out, src_index, counts —
+// the resolve: enqueued on s in this order, not synchronised, no workspace.
+void launch_register_depth(const RegisterCall& call, hipStream_t s);
+
 // Point-to-plane ICP of world-frame point lists with normals against depth planes (vors_icp_points, vors_trackers_icp_map;
 // icp_kernels.hip): per point lie.h icp_landing / icp_row, the sums in lie.h's fixed order, the round's verdict lie.h icp_round.
 // Handle-free: everything the kernels read is here; the caller's workspace holds the chunk partials, the chunk counts and the state.

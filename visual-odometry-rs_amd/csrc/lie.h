@@ -575,6 +575,102 @@ VORS_HD DepthNormal depth_normal(const Intr& k, float depth_scale, int step, flo
     return o;
 }
 
+// The sensor front end (the reference has none): undistortion of grey and depth planes into an ideal pinhole camera, and
+// registration of a depth camera's planes into a colour camera. K_in / dist = the real camera and its Brown-Conrady coefficients
+// k1 k2 p1 p2 k3, K_out = the ideal camera of the output plane.
+// SOURCE COORDINATE of output pixel (x, y): (X, Y, 1) = back_project(K_out, (float)x, (float)y, 1.0f), the distorted normalised point
+// (Xd, Yd) and (u, v) = K_in (Xd, Yd, 1), in the written order, no FMA (-ffp-contract=off):
+//   xx = X X, yy = Y Y, xy = X Y, r2 = xx + yy, rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+//   Xd = (X rad + (2 p1) xy) + p2 (r2 + 2 xx),  Yd = (Y rad + p1 (r2 + 2 yy)) + (2 p2) xy
+//   u = (fu Xd + skew Yd) + cu,  v = fv Yd + cv
+// GREY, bilinear in lerp form: inside iff 0 <= u <= cols - 1 and 0 <= v <= rows - 1, compared in float BEFORE any conversion (NaN
+// fails); border 1 clamps u and v into the plane first (edge replicate; a NaN coordinate still fails). x0 = floorf(u), a = u - x0,
+// x1 = min(x0 + 1, cols - 1), rows likewise with b; t0 = I00 + a (I01 - I00), t1 = I10 + a (I11 - I10), val = t0 + b (t1 - t0);
+// the output floorf(val + 0.5f) clamped to 0..255, 0 outside. The taps of a pixel outside alias pixel 0 (a safe address; the value is
+// ignored), so that a kernel issues every load before the first use.
+// DEPTH, never interpolated: xs = floorf(u + 0.5f), ys = floorf(v + 0.5f) (the landing rule of the depth reprojection), D[ys][xs] if
+// that pixel lies inside the plane (in float), else 0; the border mode does not apply.
+// The one text the host entries (vors_undistort_frame_host, vors_undistort_source_host) and the device kernel (frontend_kernels.hip
+// undistort_kernel) both run, bit for bit.
+struct Dist5 {
+    float k1, k2, p1, p2, k3;
+};
+VORS_HD void undistort_source(const Intr& k_out, const Intr& k_in, const Dist5& d, int x, int y, float* u, float* v) {
+    const V3 p = back_project(k_out, (float)x, (float)y, 1.0f);
+    const float X = p.x, Y = p.y;
+    const float xx = X * X, yy = Y * Y, xy = X * Y;
+    const float r2 = xx + yy;
+    const float rad = 1.0f + r2 * (d.k1 + r2 * (d.k2 + r2 * d.k3));
+    const float Xd = (X * rad + (2.0f * d.p1) * xy) + d.p2 * (r2 + 2.0f * xx);
+    const float Yd = (Y * rad + d.p1 * (r2 + 2.0f * yy)) + (2.0f * d.p2) * xy;
+    *u = (k_in.fu * Xd + k_in.skew * Yd) + k_in.cu;
+    *v = k_in.fv * Yd + k_in.cv;
+}
+VORS_HD bool undistort_inside(float u, float v, int cols, int rows) {
+    return u >= 0.0f && u <= (float)(cols - 1) && v >= 0.0f && v <= (float)(rows - 1);
+}
+struct UndistortTaps {
+    int i00, i01, i10, i11;  // flat offsets into the grey plane
+    float a, b;
+    bool ok;     // the output is interpolated (else 0)
+    bool inside; // the coordinate itself lies inside the plane, whatever the border mode (the counter)
+    int depth;   // flat offset of the depth pixel, -1 = outside
+};
+VORS_HD UndistortTaps undistort_taps(float u, float v, int border, int cols, int rows) {
+    UndistortTaps t{0, 0, 0, 0, 0.0f, 0.0f, false, undistort_inside(u, v, cols, rows), -1};
+    const float xs = floorf(u + 0.5f), ys = floorf(v + 0.5f);
+    if (undistort_inside(xs, ys, cols, rows)) t.depth = (int)ys * cols + (int)xs;
+    float uc = u, vc = v;
+    if (border == 1 && u == u && v == v) {  // (NaN stays NaN and fails below)
+        const float cmax = (float)(cols - 1), rmax = (float)(rows - 1);
+        uc = u < 0.0f ? 0.0f : u > cmax ? cmax : u;
+        vc = v < 0.0f ? 0.0f : v > rmax ? rmax : v;
+    }
+    t.ok = undistort_inside(uc, vc, cols, rows);
+    if (t.ok) {
+        const float x0f = floorf(uc), y0f = floorf(vc);
+        const int x0 = (int)x0f, y0 = (int)y0f;
+        const int x1 = x0 + 1 < cols - 1 ? x0 + 1 : cols - 1, y1 = y0 + 1 < rows - 1 ? y0 + 1 : rows - 1;
+        t.a = uc - x0f;
+        t.b = vc - y0f;
+        t.i00 = y0 * cols + x0;
+        t.i01 = y0 * cols + x1;
+        t.i10 = y1 * cols + x0;
+        t.i11 = y1 * cols + x1;
+    }
+    return t;
+}
+VORS_HD uint8_t undistort_gray(const UndistortTaps& t, uint8_t i00, uint8_t i01, uint8_t i10, uint8_t i11) {
+    if (!t.ok) return 0;
+    const float f00 = (float)i00, f01 = (float)i01, f10 = (float)i10, f11 = (float)i11;
+    const float t0 = f00 + t.a * (f01 - f00), t1 = f10 + t.a * (f11 - f10);
+    const float val = t0 + t.b * (t1 - t0);
+    const float r = floorf(val + 0.5f);
+    if (!(r > 0.0f)) return 0;
+    if (r >= 255.0f) return 255;
+    return (uint8_t)(int)r;
+}
+// REGISTRATION of source pixel (x, y) of a pinhole depth camera K_d with d != 0: z = depth_normal_z(scale_in, d),
+// P = back_project(K_d, (float)x, (float)y, z) — the camera-frame bits of the point cloud — carried into the colour camera by the depth
+// camera -> colour camera pose with the point cloud's text (iso_transform_point: rotate, then add the translation; without a pose P
+// untouched). The point then goes through render_point(K_c, no pose, ...), render_footprint and render_key(Z', s), s = y * d_cols + x,
+// unchanged. A key resolves to to_depth(scale_out, 1.0f / Z') and the winning s; an empty key to 0 and 0xFFFFFFFF. The one text the host
+// entry (vors_register_depth_host) and the device kernels (frontend_kernels.hip) both run, bit for bit.
+VORS_HD V3 register_point(const Intr& k_d, float scale_in, bool has_pose, const Iso& pose, int x, int y, uint16_t d) {
+    const V3 p = back_project(k_d, (float)x, (float)y, depth_normal_z(scale_in, d));
+    return has_pose ? iso_transform_point(pose, p) : p;
+}
+struct RegisteredPixel {
+    uint16_t depth;
+    uint32_t src;
+    bool covered;
+};
+VORS_HD RegisteredPixel register_resolve(float scale_out, uint64_t key) {
+    if (key == 0xFFFFFFFFFFFFFFFFull) return RegisteredPixel{0, 0xFFFFFFFFu, false};
+    const float zp = __builtin_bit_cast(float, (uint32_t)(key >> 32));
+    return RegisteredPixel{to_depth(scale_out, 1.0f / zp), (uint32_t)key, true};
+}
+
 // Projective point-to-plane ICP of a world-frame point list with normals against a level-0 depth plane (the reference has
 // none). T = the camera -> world pose being refined, w / nw = a world point and its world normal (three zeros: no normal). Everything in
 // the camera frame, existing texts unchanged: c = extr_project(T, w); the landing pixel (x, y) = render_point's footprint-1 anchor, which

@@ -447,6 +447,198 @@ vors_status vors_depth_normals_host(const uint16_t* depth, const float cam5[5], 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The sensor front end (vors_undistort_frames, vors_undistort_frame_host, vors_undistort_source_host, vors_register_depth,
+// vors_register_depth_host): the refusals each pair shares, the device entries (frontend_kernels.hip) and the host entries, which run the
+// kernels' own texts (lie.h undistort_source, undistort_taps, undistort_gray; register_point, render_point, render_footprint,
+// register_resolve).
+// ---------------------------------------------------------------------------------------------------------------
+static bool plane_size_ok(int rows, int cols) {
+    return rows >= 1 && cols >= 1 && rows <= 65535 && cols <= 65535 && (long long)rows * cols <= (1ll << 28);
+}
+// The cameras and the coefficients of an undistortion: every value finite, no focal length 0
+static vors_status undistort_camera_refusals(const std::string& w, const float* cam_in5, const float* dist5, const float* cam_out5) {
+    if (!cam_in5 || !cam_out5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cam_in5 or cam_out5 is NULL");
+    for (int i = 0; i < 5; ++i)
+        if (!f32_finite(cam_in5[i]) || !f32_finite(cam_out5[i]) || (dist5 && !f32_finite(dist5[i])))
+            return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a camera value or a distortion coefficient is not finite");
+    if (cam_in5[2] == 0.0f || cam_in5[3] == 0.0f || cam_out5[2] == 0.0f || cam_out5[3] == 0.0f)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": fu and fv of both cameras must not be 0");
+    return VORS_OK;
+}
+static Dist5 dist_from_dist5(const float* dist5) {
+    return dist5 ? Dist5{dist5[0], dist5[1], dist5[2], dist5[3], dist5[4]} : Dist5{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+}
+static vors_status undistort_refusals(const char* who, const UndistortCall& c, const float* cam_in5, const float* dist5, const float* cam_out5) {
+    const std::string w(who);
+    if (!c.gray && !c.depth) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the grey and the depth planes are both NULL");
+    if ((c.gray_out && !c.gray) || (c.depth_out && !c.depth))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": an output plane is asked for without its input plane");
+    if (!c.gray_out && !c.depth_out && !c.map && !c.counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": no output at all");
+    vors_status st = undistort_camera_refusals(w, cam_in5, dist5, cam_out5);
+    if (st != VORS_OK) return st;
+    if (c.border < 0 || c.border > 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": border must be 0 (zero) or 1 (edge replicate)");
+    if (!plane_size_ok(c.in_rows, c.in_cols) || !plane_size_ok(c.out_rows, c.out_cols))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must lie in 1..65535 and rows * cols must not exceed 2^28 pixels");
+    if ((uintptr_t)c.depth % 2 != 0 || (uintptr_t)c.depth_out % 2 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the depth planes must be 2-byte aligned");
+    if ((uintptr_t)c.map % 4 != 0 || (uintptr_t)c.counts % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": map and counts must be 4-byte aligned");
+    return VORS_OK;
+}
+static UndistortCall undistort_call(int n, const uint8_t* gray, const uint16_t* depth, int in_rows, int in_cols, int out_rows, int out_cols,
+                                    int border, uint8_t* gray_out, uint16_t* depth_out, float* map, uint32_t* counts) {
+    UndistortCall c{};
+    c.n = n; c.gray = gray; c.depth = depth; c.in_rows = in_rows; c.in_cols = in_cols; c.out_rows = out_rows; c.out_cols = out_cols;
+    c.border = border; c.gray_out = gray_out; c.depth_out = depth_out; c.map = map; c.counts = counts;
+    return c;
+}
+// (after the refusals: the cameras are there)
+static void undistort_cameras(UndistortCall& c, const float* cam_in5, const float* dist5, const float* cam_out5) {
+    c.k_in = intr_from_cam5(cam_in5);
+    c.dist = dist_from_dist5(dist5);
+    c.k_out = intr_from_cam5(cam_out5);
+}
+
+vors_status vors_undistort_frames(int n, const uint8_t* d_gray, const uint16_t* d_depth, int in_rows, int in_cols, const float cam_in5[5],
+                                  const float dist5[5], const float cam_out5[5], int out_rows, int out_cols, int border, uint8_t* d_gray_out,
+                                  uint16_t* d_depth_out, float* d_map, uint32_t* d_counts, void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "undistort_frames: n must be >= 1");
+    UndistortCall call = undistort_call(n, d_gray, d_depth, in_rows, in_cols, out_rows, out_cols, border, d_gray_out, d_depth_out, d_map, d_counts);
+    vors_status st = undistort_refusals("undistort_frames", call, cam_in5, dist5, cam_out5);
+    if (st != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    undistort_cameras(call, cam_in5, dist5, cam_out5);
+    launch_undistort(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_undistort_frame_host(const uint8_t* gray, const uint16_t* depth, int in_rows, int in_cols, const float cam_in5[5],
+                                      const float dist5[5], const float cam_out5[5], int out_rows, int out_cols, int border, uint8_t* gray_out,
+                                      uint16_t* depth_out, float* map, uint32_t counts[VORS_UNDISTORT_COUNTS]) {
+    UndistortCall c = undistort_call(1, gray, depth, in_rows, in_cols, out_rows, out_cols, border, gray_out, depth_out, map, counts);
+    vors_status st = undistort_refusals("undistort_frame_host", c, cam_in5, dist5, cam_out5);
+    if (st != VORS_OK) return st;
+    undistort_cameras(c, cam_in5, dist5, cam_out5);
+    uint32_t n[VORS_UNDISTORT_COUNTS] = {0, 0, 0};
+    for (int y = 0; y < out_rows; ++y)
+        for (int x = 0; x < out_cols; ++x) {
+            const size_t i = (size_t)y * (size_t)out_cols + (size_t)x;
+            float u, v;
+            undistort_source(c.k_out, c.k_in, c.dist, x, y, &u, &v);
+            const UndistortTaps t = undistort_taps(u, v, border, in_cols, in_rows);
+            const uint16_t od = depth && t.depth >= 0 ? depth[t.depth] : (uint16_t)0;
+            if (gray_out) gray_out[i] = undistort_gray(t, gray[t.i00], gray[t.i01], gray[t.i10], gray[t.i11]);
+            if (depth_out) depth_out[i] = od;
+            if (map) {
+                map[2 * i] = u;
+                map[2 * i + 1] = v;
+            }
+            n[0] += 1;
+            n[1] += t.inside ? 1 : 0;
+            n[2] += od != 0 ? 1 : 0;
+        }
+    if (counts)
+        for (int k = 0; k < VORS_UNDISTORT_COUNTS; ++k) counts[k] = n[k];
+    return VORS_OK;
+}
+
+vors_status vors_undistort_source_host(const float cam_in5[5], const float dist5[5], const float cam_out5[5], int n_pixels, const int32_t* xy,
+                                       float* uv) {
+    const std::string w("undistort_source_host");
+    if (n_pixels < 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n_pixels must be >= 0");
+    if (n_pixels > 0 && (!xy || !uv)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": xy or uv is NULL");
+    vors_status st = undistort_camera_refusals(w, cam_in5, dist5, cam_out5);
+    if (st != VORS_OK) return st;
+    const Intr k_in = intr_from_cam5(cam_in5), k_out = intr_from_cam5(cam_out5);
+    const Dist5 dist = dist_from_dist5(dist5);
+    for (int i = 0; i < n_pixels; ++i) undistort_source(k_out, k_in, dist, xy[2 * i], xy[2 * i + 1], &uv[2 * i], &uv[2 * i + 1]);
+    return VORS_OK;
+}
+
+static vors_status register_refusals(const char* who, const RegisterCall& c, const float* dcam5, const float* ccam5) {
+    const std::string w(who);
+    if (!c.depth) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": depth is NULL");
+    if (!dcam5 || !ccam5) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": dcam5 or ccam5 is NULL");
+    if (!c.zkey) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": zkey is NULL (the pass keeps no plane of its own)");
+    if ((uintptr_t)c.zkey % 8 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": zkey must be 8-byte aligned");
+    if (c.footprint < 1 || c.footprint > 3) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": footprint must be 1, 2 or 3");
+    if (!plane_size_ok(c.d_rows, c.d_cols) || !plane_size_ok(c.c_rows, c.c_cols))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must lie in 1..65535 and rows * cols must not exceed 2^28 pixels");
+    if (!(c.scale_in > 0.0f) || !(c.scale_out > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the depth scales must be > 0");
+    if ((uintptr_t)c.depth % 2 != 0 || (uintptr_t)c.depth_out % 2 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the depth planes must be 2-byte aligned");
+    if ((uintptr_t)c.src_index % 4 != 0 || (uintptr_t)c.counts % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": src_index and counts must be 4-byte aligned");
+    return VORS_OK;
+}
+static RegisterCall register_call(int n, const uint16_t* depth, int d_rows, int d_cols, float scale_in, const float* pose7, int c_rows, int c_cols,
+                                  float scale_out, int footprint, uint64_t* zkey, uint16_t* depth_out, uint32_t* src_index, uint32_t* counts) {
+    RegisterCall c{};
+    c.n = n; c.depth = depth; c.d_rows = d_rows; c.d_cols = d_cols; c.scale_in = scale_in; c.has_pose = pose7 != nullptr;
+    c.pose = pose7 ? iso_load(pose7) : iso_identity();
+    c.c_rows = c_rows; c.c_cols = c_cols; c.scale_out = scale_out; c.footprint = footprint;
+    c.zkey = zkey; c.depth_out = depth_out; c.src_index = src_index; c.counts = counts;
+    return c;
+}
+
+vors_status vors_register_depth(int n, const uint16_t* d_depth, const float dcam5[5], int d_rows, int d_cols, float depth_scale_in,
+                                const float pose7[7], const float ccam5[5], int c_rows, int c_cols, float depth_scale_out, int footprint,
+                                uint64_t* d_zkey, uint16_t* d_depth_out, uint32_t* d_src_index, uint32_t* d_counts, void* hip_stream) {
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, "register_depth: n must be >= 1");
+    RegisterCall call = register_call(n, d_depth, d_rows, d_cols, depth_scale_in, pose7, c_rows, c_cols, depth_scale_out, footprint, d_zkey,
+                                      d_depth_out, d_src_index, d_counts);
+    vors_status st = register_refusals("register_depth", call, dcam5, ccam5);
+    if (st != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    call.k_d = intr_from_cam5(dcam5);
+    call.k_c = intr_from_cam5(ccam5);
+    launch_register_depth(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_register_depth_host(const uint16_t* depth, const float dcam5[5], int d_rows, int d_cols, float depth_scale_in,
+                                     const float pose7[7], const float ccam5[5], int c_rows, int c_cols, float depth_scale_out, int footprint,
+                                     uint64_t* zkey, uint16_t* depth_out, uint32_t* src_index, uint32_t counts[VORS_REGISTER_COUNTS]) {
+    RegisterCall c = register_call(1, depth, d_rows, d_cols, depth_scale_in, pose7, c_rows, c_cols, depth_scale_out, footprint, zkey, depth_out,
+                                   src_index, counts);
+    vors_status st = register_refusals("register_depth_host", c, dcam5, ccam5);
+    if (st != VORS_OK) return st;
+    c.k_d = intr_from_cam5(dcam5);
+    c.k_c = intr_from_cam5(ccam5);
+    const size_t c_plane = (size_t)c_rows * (size_t)c_cols;
+    for (size_t q = 0; q < c_plane; ++q) zkey[q] = VORS_ZKEY_EMPTY;
+    uint32_t n[VORS_REGISTER_COUNTS] = {0, 0, 0, 0};
+    for (int y = 0; y < d_rows; ++y)
+        for (int x = 0; x < d_cols; ++x) {
+            const int s = y * d_cols + x;
+            const uint16_t d = depth[s];
+            if (d == 0) continue;
+            const V3 p = register_point(c.k_d, c.scale_in, c.has_pose, c.pose, x, y, d);
+            const RenderPoint rp = render_point(c.k_c, false, c.pose, p, footprint, c_cols, c_rows);
+            bool landed = false;
+            if (rp.candidate) {
+                const uint64_t key = render_key(rp.z, (uint32_t)s);
+                landed = render_footprint(rp, footprint, c_cols, c_rows, [&](int q) {
+                    if (key < zkey[q]) zkey[q] = key;
+                });
+            }
+            n[0] += 1;
+            n[1] += rp.in_front ? 1 : 0;
+            n[2] += landed ? 1 : 0;
+        }
+    for (size_t q = 0; q < c_plane; ++q) {
+        const RegisteredPixel o = register_resolve(c.scale_out, zkey[q]);
+        if (depth_out) depth_out[q] = o.depth;
+        if (src_index) src_index[q] = o.src;
+        n[3] += o.covered ? 1 : 0;
+    }
+    if (counts)
+        for (int k = 0; k < VORS_REGISTER_COUNTS; ++k) counts[k] = n[k];
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Point-to-plane ICP of point lists with normals against depth planes (vors_icp_points, vors_icp_points_host): the refusals both share,
 // the device entry (icp_kernels.hip) and the host entry, which runs the kernels' own texts (lie.h icp_landing, icp_row, icp_products,
 // icp_round) and the order of sums lie.h states.

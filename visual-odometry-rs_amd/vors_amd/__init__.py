@@ -25,6 +25,9 @@ MAX_LEVELS = 8
 RESIDUAL_BINS = 256  # VORS_RESIDUAL_BINS
 RENDER_COUNTS = 4  # VORS_RENDER_COUNTS: considered, in front, landed, covered
 NORMAL_COUNTS = 3  # VORS_NORMAL_COUNTS: considered, with depth, with a normal
+UNDISTORT_COUNTS = 3  # VORS_UNDISTORT_COUNTS: pixels, grey inside, depth inside and non-zero
+REGISTER_COUNTS = 4  # VORS_REGISTER_COUNTS: with depth, in front, landed, covered
+SRC_NONE = 0xFFFFFFFF  # vors_register_depth's source index of a pixel nothing landed on
 ICP_ITERATIONS, ICP_CONVERGED, ICP_TOO_FEW, ICP_SINGULAR = 0, 1, 2, 3  # VORS_ICP_*: vors_icp_stats.status
 
 ROW_MAJOR, COL_MAJOR = 0, 1
@@ -111,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "vors_batch_fuse_depth", "vors_fuse_depth_pixels",
     "vors_render_points", "vors_render_points_host", "vors_trackers_render_map",
     "vors_depth_normals", "vors_points_normals", "vors_depth_normals_host", "vors_trackers_enable_map_normals", "vors_trackers_map_normals",
+    "vors_undistort_frames", "vors_undistort_frame_host", "vors_undistort_source_host", "vors_register_depth", "vors_register_depth_host",
     "vors_icp_workspace_bytes", "vors_icp_points", "vors_icp_points_host", "vors_trackers_icp_map",
     "vors_icp_points_robust", "vors_icp_points_robust_host", "vors_trackers_icp_map_robust",
     "vors_icp_points_joint", "vors_icp_points_joint_host", "vors_trackers_icp_map_joint",
@@ -219,6 +223,11 @@ def lib():
         _lib.vors_trackers_map_normals.argtypes = [vp, C.POINTER(vp)]
         _lib.vors_tracker_enable_map_normals.argtypes = [vp, i, f]
         _lib.vors_tracker_read_map_normals.argtypes = [vp, i, vp]
+        _lib.vors_undistort_frames.argtypes = [i, vp, vp, i, i, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
+        _lib.vors_undistort_frame_host.argtypes = [vp, vp, i, i, vp, vp, vp, i, i, i, vp, vp, vp, vp]
+        _lib.vors_undistort_source_host.argtypes = [vp, vp, vp, i, vp, vp]
+        _lib.vors_register_depth.argtypes = [i, vp, vp, i, i, f, vp, vp, i, i, f, i, vp, vp, vp, vp, vp]
+        _lib.vors_register_depth_host.argtypes = [vp, vp, i, i, f, vp, vp, i, i, f, i, vp, vp, vp, vp]
         _lib.vors_icp_workspace_bytes.argtypes = [i, i]
         _lib.vors_icp_workspace_bytes.restype = C.c_uint64
         # The nine ICP entries (include/vors_hip.h 2e and the handle's forwards) from the pieces their lists share, each counted once:
@@ -1852,6 +1861,145 @@ def depth_normals_host(depth, cam5, depth_scale, step, jump_m, pose7=None, pixel
     _check(lib().vors_depth_normals_host(_ptr(d), _ptr(k), rows, cols, float(depth_scale), int(step), float(jump_m), _ptr(pose), _ptr(px),
                                          cap if count is None else int(count), cap, _ptr(rng), _ptr(normals), _ptr(out["counts"])))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- sensor front end
+def _front_cameras(who, cams, dist5=None, pose7=None):
+    """cam5 arrays, the distortion coefficients and a pose as contiguous float32 (None stays None), shapes checked."""
+    ks = [np.ascontiguousarray(k, np.float32) for k in cams]
+    d = None if dist5 is None else np.ascontiguousarray(dist5, np.float32)
+    p = None if pose7 is None else np.ascontiguousarray(pose7, np.float32)
+    if any(k.shape != (5,) for k in ks) or (d is not None and d.shape != (5,)) or (p is not None and p.shape != (7,)):
+        raise VorsError(f"{who}: a camera is cu cv fu fv skew [5], dist5 k1 k2 p1 p2 k3 [5] or None, pose7 [7] or None")
+    return ks, d, p
+
+
+def _front_planes(who, planes, dtypes):
+    """The input planes of a device pass: each None or a contiguous tensor [n, rows, cols] of its dtype, all of one shape -> that shape
+    and the device (None, None without any plane: the C entry refuses that)."""
+    shape = dev = None
+    for t, dtype in zip(planes, dtypes):
+        if t is None:
+            continue
+        if t.dtype != dtype or t.dim() != 3 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise VorsError(f"{who}: the planes are contiguous tensors [n, rows, cols] of one shape (grey uint8, depth int16)")
+        shape, dev = tuple(t.shape), t.device
+    return shape, dev
+
+
+def _host_out(who, o, shape, dtype, fill=None):
+    """An output argument of a host entry: True = a new array, an array = that one after a check, False / None = not wanted."""
+    if o is True:
+        return np.empty(shape, dtype) if fill is None else np.full(shape, fill, dtype)
+    if not _asked(o):
+        return None
+    if not isinstance(o, np.ndarray) or o.dtype != dtype or o.shape != tuple(shape) or not o.flags.c_contiguous:
+        raise VorsError(f"{who}: expected a contiguous {np.dtype(dtype)} output {tuple(shape)}")
+    return o
+
+
+def undistort_frames(gray, depth, cam_in5, dist5, cam_out5, out_rows, out_cols, border=0, gray_out=None, depth_out=None, map=False,
+                     counts=False):
+    """n grey and / or depth planes of a real camera resampled into an ideal pinhole camera (vors_undistort_frames; handle-free) -> dict
+    of the requested tensors on the current stream, not synchronised: "gray" [n, out_rows, out_cols] uint8 (bilinear), "depth" (int16
+    tensor holding the u16 payload; nearest source pixel, never interpolated, 0 outside), "map" [out_rows, out_cols, 2] float32 (the
+    source coordinate (u, v) of every output pixel), "counts" [n, 3] int32 (pixels, grey inside, depth inside and non-zero). gray uint8 /
+    depth int16 [n, in_rows, in_cols] or None; cam_in5 / cam_out5 = cu cv fu fv skew of the real and of the ideal camera; dist5 = k1 k2 p1
+    p2 k3 (Brown-Conrady) or None; border 0 = zero outside, 1 = edge replicate (grey only). gray_out / depth_out default to "where the
+    input is given"; every output may also be a tensor of its shape to write into."""
+    import torch
+    who = "undistort_frames"
+    (k_in, k_out), d5, _ = _front_cameras(who, (cam_in5, cam_out5), dist5)
+    shape, dev = _front_planes(who, (gray, depth), (torch.uint8, torch.int16))
+    n, in_rows, in_cols = shape if shape else (1, 0, 0)
+    dev = dev if dev is not None else next((t.device for t in (gray_out, depth_out, map, counts) if hasattr(t, "device")), None)
+    gray_out = (gray is not None) if gray_out is None else gray_out
+    depth_out = (depth is not None) if depth_out is None else depth_out
+    oshape = (n, int(out_rows), int(out_cols))
+    bufs = (_out_buf(gray_out, oshape, torch.uint8, dev), _out_buf(depth_out, oshape, torch.int16, dev),
+            _out_buf(map, oshape[1:] + (2,), torch.float32, dev), _out_buf(counts, (n, UNDISTORT_COUNTS), torch.int32, dev))
+    _check(lib().vors_undistort_frames(n, Batch._dp(gray), Batch._dp(depth), in_rows, in_cols, _ptr(k_in), _ptr(d5), _ptr(k_out), oshape[1],
+                                       oshape[2], int(border), *[Batch._dp(t) for t in bufs], Batch._stream()))
+    return _result(*((name, _asked(want), t) for name, want, t in zip(("gray", "depth", "map", "counts"), (gray_out, depth_out, map, counts), bufs)))
+
+
+def undistort_frame_host(gray, depth, cam_in5, dist5, cam_out5, out_rows, out_cols, border=0, gray_out=None, depth_out=None, map=True,
+                         counts=True):
+    """The rule of undistort_frames for ONE plane of each kind on the host (vors_undistort_frame_host; needs no GPU; the text the kernel
+    runs): gray [in_rows, in_cols] uint8 / depth uint16 or None -> dict: "gray", "depth" (where the input is given), "map" [out_rows,
+    out_cols, 2] float32, "counts" [3] uint32. Every output may also be an array of its shape to write into, or False."""
+    who = "undistort_frame_host"
+    (k_in, k_out), d5, _ = _front_cameras(who, (cam_in5, cam_out5), dist5)
+    g = None if gray is None else np.ascontiguousarray(gray, np.uint8)
+    d = None if depth is None else np.ascontiguousarray(depth, np.uint16)
+    shapes = {a.shape for a in (g, d) if a is not None}
+    if len(shapes) > 1 or any(len(sh) != 2 for sh in shapes):
+        raise VorsError(f"{who}: gray and depth [in_rows, in_cols] of one shape (each may be None)")
+    in_rows, in_cols = shapes.pop() if shapes else (0, 0)
+    gray_out = (g is not None) if gray_out is None else gray_out
+    depth_out = (d is not None) if depth_out is None else depth_out
+    oshape = (max(int(out_rows), 0), max(int(out_cols), 0))
+    bufs = (_host_out(who, gray_out, oshape, np.uint8), _host_out(who, depth_out, oshape, np.uint16),
+            _host_out(who, map, oshape + (2,), np.float32), _host_out(who, counts, (UNDISTORT_COUNTS,), np.uint32, fill=0))
+    _check(lib().vors_undistort_frame_host(_ptr(g), _ptr(d), in_rows, in_cols, _ptr(k_in), _ptr(d5), _ptr(k_out), int(out_rows), int(out_cols),
+                                           int(border), *[_ptr(b) for b in bufs]))
+    return _result(*((name, _asked(want), t) for name, want, t in zip(("gray", "depth", "map", "counts"), (gray_out, depth_out, map, counts), bufs)))
+
+
+def undistort_source_host(cam_in5, dist5, cam_out5, xy):
+    """The source coordinate (u, v) in the real camera of output pixels xy [m, 2] int32 (x, y) of the ideal camera
+    (vors_undistort_source_host; needs no GPU; the text the kernel runs) -> [m, 2] float32."""
+    who = "undistort_source_host"
+    (k_in, k_out), d5, _ = _front_cameras(who, (cam_in5, cam_out5), dist5)
+    p = np.ascontiguousarray(xy, np.int32)
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise VorsError(f"{who}: xy [m, 2]")
+    uv = np.empty(p.shape, np.float32)
+    _check(lib().vors_undistort_source_host(_ptr(k_in), _ptr(d5), _ptr(k_out), len(p), _ptr(p), _ptr(uv)))
+    return uv
+
+
+def register_depth(depth, dcam5, depth_scale_in, ccam5, c_rows, c_cols, depth_scale_out, pose7=None, footprint=1, depth_out=True,
+                   src_index=False, counts=False, zkey=False):
+    """n depth planes of a pinhole depth camera registered into a colour camera (vors_register_depth; handle-free) -> dict of the requested
+    tensors on the current stream, not synchronised: "depth" [n, c_rows, c_cols] (int16 tensor holding the u16 payload in units of 1 /
+    depth_scale_out, 0 = nothing landed), "src_index" (int32 tensor holding the u32 payload: y * d_cols + x of the winning source pixel, -1
+    = nothing landed), "zkey" (int64 tensor holding bits(Z') << 32 | source index, -1 = empty), "counts" [n, 4] int32 (with depth, in
+    front, landed, covered). depth [n, d_rows, d_cols] int16 tensor holding the u16 payload in units of 1 / depth_scale_in; dcam5 / ccam5 =
+    cu cv fu fv skew of the depth and of the colour camera; pose7 (host) = depth camera -> colour camera, tx ty tz qi qj qk qw, or None;
+    footprint 1, 2 or 3 pixels wide. Every output may also be a tensor of its shape to write into."""
+    import torch
+    who = "register_depth"
+    (k_d, k_c), _, pose = _front_cameras(who, (dcam5, ccam5), None, pose7)
+    shape, dev = _front_planes(who, (depth,), (torch.int16,))
+    if shape is None:
+        raise VorsError(f"{who}: depth int16 [n, d_rows, d_cols], contiguous")
+    n, d_rows, d_cols = shape
+    oshape = (n, int(c_rows), int(c_cols))
+    bufs = (_out_buf(zkey, oshape, torch.int64, dev, always=True), _out_buf(depth_out, oshape, torch.int16, dev),
+            _out_buf(src_index, oshape, torch.int32, dev), _out_buf(counts, (n, REGISTER_COUNTS), torch.int32, dev))
+    _check(lib().vors_register_depth(n, Batch._dp(depth), _ptr(k_d), d_rows, d_cols, float(depth_scale_in), _ptr(pose), _ptr(k_c), oshape[1],
+                                     oshape[2], float(depth_scale_out), int(footprint), *[Batch._dp(t) for t in bufs], Batch._stream()))
+    return _result(*((name, _asked(want), t) for name, want, t in zip(("zkey", "depth", "src_index", "counts"), (zkey, depth_out, src_index, counts), bufs)))
+
+
+def register_depth_host(depth, dcam5, depth_scale_in, ccam5, c_rows, c_cols, depth_scale_out, pose7=None, footprint=1, depth_out=True,
+                        src_index=True, counts=True, zkey=True):
+    """The rule of register_depth for ONE plane on the host (vors_register_depth_host; needs no GPU; the text the kernels run): depth
+    [d_rows, d_cols] uint16 -> dict: "zkey" [c_rows, c_cols] uint64, "depth" uint16, "src_index" uint32 (SRC_NONE = nothing landed),
+    "counts" [4] uint32. Every output may also be an array of its shape to write into; zkey is made all the same."""
+    who = "register_depth_host"
+    (k_d, k_c), _, pose = _front_cameras(who, (dcam5, ccam5), None, pose7)
+    d = np.ascontiguousarray(depth, np.uint16)
+    if d.ndim != 2:
+        raise VorsError(f"{who}: depth [d_rows, d_cols]")
+    oshape = (max(int(c_rows), 0), max(int(c_cols), 0))
+    bufs = (_host_out(who, zkey if _asked(zkey) else True, oshape, np.uint64), _host_out(who, depth_out, oshape, np.uint16),
+            _host_out(who, src_index, oshape, np.uint32), _host_out(who, counts, (REGISTER_COUNTS,), np.uint32, fill=0))
+    _check(lib().vors_register_depth_host(_ptr(d), _ptr(k_d), d.shape[0], d.shape[1], float(depth_scale_in), _ptr(pose), _ptr(k_c), int(c_rows),
+                                          int(c_cols), float(depth_scale_out), int(footprint), *[_ptr(b) for b in bufs]))
+    return _result(*((name, want, t) for name, want, t in zip(("zkey", "depth", "src_index", "counts"),
+                                                               (True, _asked(depth_out), _asked(src_index), _asked(counts)), bufs)))
 
 
 class vors_icp_stats(C.Structure):
