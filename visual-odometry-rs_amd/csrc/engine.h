@@ -47,7 +47,7 @@ struct Geom {
                           // 3 = a slot of a vors_pipeline ring: the LM stage is ~2/3 of a step, so about 1.5 of them overlap). The workgroup size of
                           // the workgroup-per-pair kernel is chosen for n_pairs x this / 2 RESIDENT pairs (lm_reference.hip refc_waves_per_pair): a
                           // ring wants the thinner workgroups whose LDS lets the LM kernels of consecutive steps share a CU. The sums do not depend on it
-    int wide_loads_ok;  // set per launch: the caller's buffers are 16-byte aligned, so the dense quad source may use wide loads
+    int wide_loads_ok;  // set per launch (lm_sources.h launch_geom): the handle's own planes are 16-byte aligned, so the dense quad source may use wide loads
     // Masked launches of the keyframe stage (vors_trackers: per-sequence keyframe promotion on the device). When sel_list is set, index k
     // of a kernel's pair dimension addresses pair sel_list[k] for k < *sel_count and nothing beyond (device_common.h select_pair).
     const int* sel_list;

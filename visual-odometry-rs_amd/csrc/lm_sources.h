@@ -207,6 +207,14 @@ struct DenseSrc {
     __device__ __forceinline__ int slot(const Raw& r, int g, int n) const { return r.i; }
 };
 
+// A load of T from any address: the planes of the caller's need not be aligned, and gfx950 global loads take any address.
+template <class T>
+__device__ __forceinline__ T load_any(const uint8_t* p) {
+    T v;
+    __builtin_memcpy(&v, p, sizeof(T));
+    return v;
+}
+
 // DenseQuadSrc: FOUR horizontally adjacent pixels per unit (cols % 4 == 0). One dword / dwordx2 / dwordx4 load per image
 // row and plane instead of ~8 byte loads per pixel: coalesced 256 B - 1 KiB per wavefront instruction, 4-way ILP per lane.
 template <bool LEVEL0, bool FAST>
@@ -260,21 +268,24 @@ struct DenseQuadSrc {
         r.y = y;
         // 32-bit unsigned offsets from workgroup-uniform bases (scalar base + vector offset addressing, no 64-bit VALU arithmetic)
         const unsigned ucols = (unsigned)cols, o = (unsigned)y * ucols + (unsigned)x0;
-        r.cw = *reinterpret_cast<const uint32_t*>(kimg + o);
+        // level 0 and the depth map are the CALLER's buffers, which need not be aligned: loads of any address (load_any), the same
+        // dword / dwordx2 instructions, so that a pair's source — and with it the order of the sums — does not depend on where
+        // the caller's buffers start
+        r.cw = load_any<uint32_t>(kimg + o);
         if (LEVEL0) {
             const bool yin = y > 0 && y < rows - 1;
-            r.w1 = *reinterpret_cast<const uint32_t*>(kimg + (o - (yin ? ucols : 0u)));
-            r.w2 = *reinterpret_cast<const uint32_t*>(kimg + (o + (yin ? ucols : 0u)));
+            r.w1 = load_any<uint32_t>(kimg + (o - (yin ? ucols : 0u)));
+            r.w2 = load_any<uint32_t>(kimg + (o + (yin ? ucols : 0u)));
             r.w3 = kimg[o - (x0 > 0 ? 1u : 0u)];
             r.w4 = kimg[o + (x0 + 4 < cols ? 4u : 3u)];
-            const uint2 dzw = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(depth) + (o << 1));
+            const uint2 dzw = load_any<uint2>(reinterpret_cast<const uint8_t*>(depth) + (o << 1));
             r.d0 = dzw.x;
             r.d1 = dzw.y;
             r.d2 = r.d3 = 0;
         } else {
             const unsigned ufc = (unsigned)fcols, fo = (unsigned)(2 * y) * ufc + (unsigned)(2 * x0);
-            const uint2 f0 = *reinterpret_cast<const uint2*>(kfine + fo);
-            const uint2 f1 = *reinterpret_cast<const uint2*>(kfine + (fo + ufc));
+            const uint2 f0 = load_any<uint2>(kfine + fo);  // (level 1: the finer level is the caller's level 0)
+            const uint2 f1 = load_any<uint2>(kfine + (fo + ufc));
             r.w1 = f0.x; r.w2 = f0.y; r.w3 = f1.x; r.w4 = f1.y;
             const uint4 z4 = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(iz) + (o << 2));
             r.d0 = z4.x; r.d1 = z4.y; r.d2 = z4.z; r.d3 = z4.w;
@@ -405,7 +416,7 @@ __device__ __forceinline__ void with_exact_source(const Geom& g, int lvl, int pa
         const uint16_t* depth = kf_depth + (size_t)pair * g.S0;
         const float* iz = lvl > 0 ? rec.IZ + (size_t)pair * g.slots_total + lg.slot_off : nullptr;
         const int fcols = lvl > 0 ? g.lv[lvl - 1].cols : 0;
-        // quads need 4-byte aligned rows in every plane they read (and 16-byte aligned inverse-depth rows)
+        // quads need rows of whole quads in every plane they read (and 16-byte aligned inverse-depth rows)
         const bool quad_ok = QUADS && g.wide_loads_ok && (lg.cols % 4 == 0) && (lvl == 0 ? (g.S0 % 4 == 0) : (fcols % 8 == 0));
         if (lvl == 0) {
             if constexpr (QUADS) {
@@ -478,10 +489,12 @@ __device__ __forceinline__ LevelCut level_cut(int n_units, int chunk, int chunks
     return LevelCut{first, last};
 }
 
-// The geometry of a launch on `call`: wide_loads_ok set iff the caller's buffers are 16-byte aligned (the dense quad source's wide loads)
+// The geometry of a launch on `call`: wide_loads_ok set iff the handle's own planes are 16-byte aligned (the dense quad source's dwordx4
+// loads of the inverse depths). The caller's level 0 and depth map are read with loads of any address (DenseQuadSrc::load): whether a
+// pair takes the quad source, and so the order of its sums, is a matter of the shape alone and never of where the caller's buffers start.
 static inline Geom launch_geom(const Geom& g_in, const LmScene& call) {
     Geom g = g_in;
-    g.wide_loads_ok = (((uintptr_t)call.kf.level0 | (uintptr_t)call.kf.upper | (uintptr_t)call.kf_depth | (uintptr_t)call.rec.IZ) % 16 == 0) ? 1 : 0;
+    g.wide_loads_ok = (((uintptr_t)call.kf.upper | (uintptr_t)call.rec.IZ) % 16 == 0) ? 1 : 0;
     return g;
 }
 
