@@ -140,7 +140,8 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_trackers_map_icp_means, vors_tracker_enable_map_icp_means, vors_tracker_read_map_icp_means,
                               *    vors_map_icp_means_record, likewise; + vors_undistort_frames, vors_undistort_frame_host,
                               *    vors_undistort_source_host, vors_register_depth, vors_register_depth_host, VORS_UNDISTORT_COUNTS,
-                              *    VORS_REGISTER_COUNTS, likewise) */
+                              *    VORS_REGISTER_COUNTS, likewise; + vors_pose_graph_optimize, vors_pose_graph_optimize_host,
+                              *    vors_pose_graph_workspace_bytes, vors_pose_graph_jacobians_host, vors_pose_graph_stats, VORS_PG_*, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -1321,6 +1322,87 @@ vors_status vors_register_depth_host(const uint16_t* depth, const float dcam5[5]
                                      const float pose7[7] /* nullable */, const float ccam5[5], int c_rows, int c_cols, float depth_scale_out,
                                      int footprint, uint64_t* zkey, uint16_t* depth_out /* nullable */, uint32_t* src_index /* nullable */,
                                      uint32_t counts[VORS_REGISTER_COUNTS] /* nullable */);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2g. POSE-GRAPH OPTIMISATION OF KEYFRAME POSES, device-resident and handle-free (the reference has none): given N poses and
+ *     E relative-pose measurements with information matrices, the poses that best satisfy all of them — the consumer of
+ *     vors_batch_track_pairs' lm_model and of vors_batch_pose_information's info36, which go in unchanged.
+ * Graphs: n graphs are solved side by side. DEVICE pointers: d_poses7_in [n][node_capacity] camera -> world poses, pose_stride_bytes apart
+ *   (0 = packed, 28; as in vors_render_points); d_node_counts [n] u32 and d_edge_counts [n] u32 (a count above its capacity is clipped);
+ *   d_edges [n][edge_capacity] {u32 i, j}; d_meas7 [n][edge_capacity][7]; d_info36 [n][edge_capacity][36] row-major (nullable =
+ *   identity); d_edge_weight [n][edge_capacity] f32, multiplies the information (nullable = 1); d_fixed [n][node_capacity] u8, non-zero =
+ *   fixed (nullable = node 0 of every graph is fixed).
+ * MEASUREMENT: M_ij maps coordinates of camera i into camera j — vors_pair_stats.lm_model of keyframe i and frame j; consistent poses
+ *   have T_j = T_i M_ij^-1. Edge error E = T_i^-1 T_j M_ij. Under the LM's parametrisation (true model = model exp(xi)^-1) E = exp(xi)
+ *   exactly, so the residual below is xi to first order and info36 = sum J^T J of the LM is its information WITHOUT an adjoint transport.
+ * RESIDUAL: r = (E.t, 2 s E.q.ijk), s = +1 if E.q.w >= 0 else -1; no transcendental. Energy of an edge: w (r . (Omega r)), Omega r row by
+ *   row left to right, then the six products in ascending order (lie.h pg_edge_energy). With d_info36 = NULL the same arithmetic runs on
+ *   an identity matrix: NULL equals identity matrices bit for bit.
+ * JACOBIANS (exact, closed form; perturbation T_k <- renormalize(T_k se3_exp(d_k))): A(E) = blockdiag(R_E, s (E.q.w I + [E.q.ijk]x)),
+ *   Ad(R, t) = [[R, [t]x R], [0, R]] in se3_exp's (v, w) order: J_j = A(E) Ad(M_ij^-1), J_i = -A(E) Ad(E^-1) (lie.h pg_edge_jacobians).
+ * SKIPPED EDGES, counted, contributing nothing anywhere: i == j; an index >= node_count; a weight that is not finite or not > 0; a
+ *   measurement or information entry that is not finite. A free node without a valid edge is treated as fixed and counted as isolated.
+ * ORDER OF THE SUMS (part of the definition): the graph energy — edges in chunks of 1024 consecutive indices (a skipped edge and a slot
+ *   beyond the count hold +0.0f), inside a chunk vors_icp_points' halving tree in f32, the chunk sums added in ascending order from chunk
+ *   0's. Per node k, g_k and the lower triangle of H_kk: sequential f32 sums over k's incident valid edges in ascending edge index,
+ *   starting from the first edge's term. Per edge W_e = J_i^T (w Omega) J_j, stored once per linearisation. Dot products of the solve:
+ *   nodes in chunks of 1024, the same tree and chunk order IN f64 (a node that is not free holds 0.0).
+ * OUTER LOOP per graph, Levenberg-Marquardt, no host round trip: `iters` rounds of linearise; solve (H + lambda D) delta = -g over the
+ *   free nodes, D = diag(H) (cholesky6_solve's damping: diagonal times 1 + lambda); candidates T_k' = renormalize(T_k se3_exp(delta_k));
+ *   energy at the candidates; ACCEPT iff energy' <= energy (a NaN is rejected): the candidates become the poses and lambda = 0.1f lambda;
+ *   otherwise the poses stay and lambda = 10 lambda (lm_verdict's constants; lie.h pg_accepts / pg_lambda_after). A rejected round keeps
+ *   its linearisation. Then ONE final evaluation at the returned poses, which is what the per-edge outputs and final_energy describe
+ *   (iters = 0: a pure evaluator).
+ * INNER SOLVE: block-Jacobi preconditioned conjugate gradients from delta = 0; the 6x6 blocks H_kk + lambda D_kk are factored by a
+ *   Cholesky per node. Exactly cg_iters iterations unless, before an iteration, r.r <= cg_tol^2 r0.r0 (a NaN ends them too). The product
+ *   is a gather per node: the own block first, then W_e p_j (the node is the edge's i) or W_e^T p_i over its incidence list in ascending
+ *   edge index. THE SCALARS ARE f64 (dot products, alpha, beta; lie.h pg_dot6, pg_cg_alpha, pg_cg_beta); alpha and beta are rounded to
+ *   f32 once and the vectors are f32.
+ * FREEZING: VORS_PG_CONVERGED when an accepted step has max_k dot6(delta_k, delta_k) <= step_eps^2; VORS_PG_SINGULAR when a block has no
+ *   Cholesky factor (poses kept); VORS_PG_TOO_FEW when there is no valid edge or no free node (poses returned as given);
+ *   VORS_PG_ITERATIONS otherwise.
+ * Outputs (DEVICE): d_poses7_out [n][node_capacity][7] packed, exactly the nodes below node_count written (may alias d_poses7_in when
+ *   that is packed; fixed and isolated nodes, and every node of a graph that accepted no step, keep their bits); d_stats [n] (nullable);
+ *   d_edge_residuals [n][edge_capacity][6] and d_edge_energy [n][edge_capacity] (nullable) of the final evaluation, exactly the edges
+ *   below edge_count written, NaN for a skipped edge.
+ * d_workspace (DEVICE, 16-byte aligned): vors_pose_graph_workspace_bytes(n, node_capacity, edge_capacity) bytes; 0 for an argument < 1.
+ * The result of a graph depends neither on the graphs around it, nor on the capacities, the grid or the schedule; the device equals
+ *   vors_pose_graph_optimize_host bit for bit. No floating-point atomic exists; the incidence lists are built with integer atomics and
+ *   then ordered per node.
+ * Refused with VORS_ERR_INVALID_ARGUMENT, nothing enqueued: n < 1; a NULL d_poses7_in, d_node_counts, d_edges, d_edge_counts, d_meas7,
+ *   d_workspace or d_poses7_out; a capacity < 1 or > 2^28; a bad pose stride; lambda0, step_eps or cg_tol negative or NaN; iters outside
+ *   0..64; cg_iters outside 1..256; a pointer off its alignment (d_workspace: 16 bytes, d_fixed: none, the others: 4).
+ * Enqueued on hip_stream on the calling thread's current device, NOT synchronised, no allocation ever. Launches: the incidence build (five)
+ *   and the initial energy (two) once; per round the linearisation, the gather, two per CG iteration (product with partial dots; reduce
+ *   and update), the candidates, their energy, the verdict; then the final evaluation and the launch that writes the outputs. Every
+ *   launch is enqueued unconditionally, graphs freeze by state, no workgroup waits for another. */
+#define VORS_PG_ITERATIONS 0
+#define VORS_PG_CONVERGED 1
+#define VORS_PG_TOO_FEW 2
+#define VORS_PG_SINGULAR 3
+typedef struct vors_pose_graph_stats {
+    uint32_t status, accepted_steps, rejected_steps, cg_iterations;
+    uint32_t valid_edges, skipped_edges, free_nodes, fixed_nodes, isolated_nodes;
+    float initial_energy, final_energy, last_step_norm, final_lambda;
+} vors_pose_graph_stats;
+uint64_t vors_pose_graph_workspace_bytes(int n, int node_capacity, int edge_capacity);
+vors_status vors_pose_graph_optimize(int n, const void* d_poses7_in, size_t pose_stride_bytes, const uint32_t* d_node_counts, int node_capacity,
+                                     const uint32_t* d_edges, const uint32_t* d_edge_counts, int edge_capacity, const float* d_meas7,
+                                     const float* d_info36 /* nullable */, const float* d_edge_weight /* nullable */,
+                                     const uint8_t* d_fixed /* nullable */, float lambda0, float step_eps, float cg_tol, int iters, int cg_iters,
+                                     void* d_workspace, float* d_poses7_out, vors_pose_graph_stats* d_stats /* nullable */,
+                                     float* d_edge_residuals /* nullable */, float* d_edge_energy /* nullable */, void* hip_stream);
+/* The same loop for ONE graph on the host (host arithmetic, needs no GPU; the texts and the order of sums the kernels run): HOST pointers,
+ * poses packed [node_capacity][7], no workspace. The refusals above, with nothing written. */
+vors_status vors_pose_graph_optimize_host(const float* poses7_in, uint32_t node_count, int node_capacity, const uint32_t* edges,
+                                          uint32_t edge_count, int edge_capacity, const float* meas7, const float* info36 /* nullable */,
+                                          const float* edge_weight /* nullable */, const uint8_t* fixed /* nullable */, float lambda0,
+                                          float step_eps, float cg_tol, int iters, int cg_iters, float* poses7_out,
+                                          vors_pose_graph_stats* stats /* nullable */, float* edge_residuals /* nullable */,
+                                          float* edge_energy /* nullable */);
+/* The residual and the two Jacobians of ONE edge at the poses (ti, tj), the kernels' own text (lie.h pg_edge_jacobians), for tests:
+ * r6, ji36 and jj36 row-major (HOST). */
+void vors_pose_graph_jacobians_host(const float ti7[7], const float tj7[7], const float meas7[7], float r6[6], float ji36[36], float jj36[36]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

@@ -646,6 +646,93 @@ struct IcpJoint {
 // photo counts when they are asked for.
 void launch_icp_points(const IcpCall& call, const IcpRobust* robust, hipStream_t s, const IcpJoint* joint = nullptr);
 
+// Pose-graph optimisation of n graphs side by side (vors_pose_graph_optimize; pose_graph_kernels.hip): the per-edge and
+// per-node rules are lie.h pg_*, the order of every sum the one include/vors_hip.h 2g states. Handle-free: everything the kernels read is
+// here; the caller's workspace holds the state, the working poses, the incidence lists, the linearisation and the vectors of the solve.
+struct PgState {  // per graph, in the workspace
+    uint32_t status, frozen, accepted, rejected, cg_spent, valid_edges, skipped_edges, free_nodes, fixed_nodes, isolated_nodes;
+    uint32_t cur;         // which of the two pose buffers holds the kept poses
+    uint32_t lin_ok;      // the stored linearisation is the kept poses' (the last round was rejected)
+    uint32_t singular;    // a block of this round had no factor
+    uint32_t cg_done[2];  // slot t & 1: iteration t found the solve ended; written by iteration t's product launch, read by later launches
+    uint32_t step2_bits;  // max over the free nodes of dot6(delta, delta) >= 0, as its bits (an integer maximum)
+    float lambda, energy, initial_energy, last_step_norm;
+};
+struct PgCall {
+    int n, node_capacity, edge_capacity;
+    const float* poses_in;        // [n][node_capacity] poses, pose_stride floats apart
+    int pose_stride;
+    const uint32_t* node_counts;  // [n]; a count above the capacity is clipped to it
+    const uint32_t* edges;        // [n][edge_capacity][2]
+    const uint32_t* edge_counts;  // [n], clipped likewise
+    const float* meas;            // [n][edge_capacity][7]
+    const float* info;            // [n][edge_capacity][36], nullable = identity
+    const float* weight;          // [n][edge_capacity], nullable = 1
+    const uint8_t* fixed;         // [n][node_capacity], nullable = node 0 of every graph
+    float lambda0, step_eps, cg_tol;
+    int iters, cg_iters;
+    float* poses_out;             // [n][node_capacity][7], may alias poses_in when packed alike
+    vors_pose_graph_stats* stats; // [n], nullable
+    float* edge_residuals;        // [n][edge_capacity][6], nullable
+    float* edge_energy;           // [n][edge_capacity], nullable
+    // the workspace, carved by pg_workspace_carve in this order
+    double* dots;                 // [n][6][node chunks]: p.q, r.z (two slots), r.r (two slots), r0.r0 chunk sums
+    PgState* state;               // [n]
+    float* wmat;                  // [n][edge_capacity][36], 16-byte aligned rows
+    float* lin;                   // [n][edge_capacity][VORS_PG_LIN]
+    float* poses;                 // [n][2][node_capacity][7]
+    float *hd, *fac;              // [n][node_capacity][21]
+    float *x, *r, *z, *q, *p;     // [n][node_capacity][6]; p: [n][2][node_capacity][6]
+    float* energy_part;           // [n][edge chunks]
+    uint32_t *edge_ok;            // [n][edge_capacity]
+    uint32_t *deg, *cursor, *node_class;  // [n][node_capacity]
+    uint32_t* off;                // [n][node_capacity + 1]
+    uint32_t *inc_tmp, *inc;      // [n][2 * edge_capacity]: edge << 1 | (0: the node is the edge's i, 1: its j)
+};
+#define PG_BLOCK 256
+#define PG_MAX_CHUNKS 1024  // cap of a grid's x extent: longer graphs go through the stride loop
+#define PG_NODE_FREE 0u
+#define PG_NODE_FIXED 1u
+#define PG_NODE_ISOLATED 2u
+constexpr size_t pg_chunks(int capacity) { return ((size_t)capacity + VORS_PG_CHUNK - 1) / VORS_PG_CHUNK; }
+// One walk over the workspace's parts for its size and for a call's pointers (call NULL: the size only). Every part is a multiple of 16
+// bytes up to `lin`, of 4 bytes after it.
+inline size_t pg_workspace_carve(PgCall* call, void* workspace, int n, int node_capacity, int edge_capacity) {
+    const size_t g = (size_t)n, N = (size_t)node_capacity, E = (size_t)edge_capacity, nc = pg_chunks(node_capacity), ec = pg_chunks(edge_capacity);
+    size_t at = 0;
+    auto part = [&](auto** p, size_t bytes) {
+        if (call) *p = reinterpret_cast<std::remove_reference_t<decltype(**p)>*>(static_cast<char*>(workspace) + at);
+        at += bytes;
+    };
+    PgCall scratch{};
+    PgCall& c = call ? *call : scratch;
+    part(&c.dots, g * 6 * nc * sizeof(double));
+    part(&c.state, g * sizeof(PgState));
+    part(&c.wmat, g * E * 36 * 4);
+    part(&c.lin, g * E * VORS_PG_LIN * 4);
+    part(&c.poses, g * 2 * N * 7 * 4);
+    part(&c.hd, g * N * 21 * 4);
+    part(&c.fac, g * N * 21 * 4);
+    part(&c.x, g * N * 6 * 4);
+    part(&c.r, g * N * 6 * 4);
+    part(&c.z, g * N * 6 * 4);
+    part(&c.q, g * N * 6 * 4);
+    part(&c.p, g * 2 * N * 6 * 4);
+    part(&c.energy_part, g * ec * 4);
+    part(&c.edge_ok, g * E * 4);
+    part(&c.deg, g * N * 4);
+    part(&c.cursor, g * N * 4);
+    part(&c.node_class, g * N * 4);
+    part(&c.off, g * (N + 1) * 4);
+    part(&c.inc_tmp, g * 2 * E * 4);
+    part(&c.inc, g * 2 * E * 4);
+    return at;
+}
+// The incidence build, the initial energy, per round the linearisation, the gather, 2 cg_iters launches of the solve, the candidates,
+// their energy and the verdict, then the final evaluation and the launch that writes the outputs: enqueued on s in this order, every
+// launch unconditionally, not synchronised, no allocation.
+void launch_pose_graph(const PgCall& call, hipStream_t s);
+
 // The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp; map_icp_kernels.hip): what surrounds
 // launch_icp_points there. Handle-free: everything the kernels read is here.
 struct MapIcpCall {

@@ -1181,4 +1181,264 @@ inline void se3_log(const Iso& iso, float xi[6]) {
     xi[3] = w[0]; xi[4] = w[1]; xi[5] = w[2];
 }
 
+// Pose-graph optimisation (vors_pose_graph_optimize, include/vors_hip.h 2g; the reference has none): the texts the kernels
+// (pose_graph_kernels.hip) and the host twin (operators.cpp vors_pose_graph_optimize_host) both run, bit for bit. No libm transcendental
+// below: the residual needs no logarithm, and the update is se3_exp's (ref_sinf / ref_cosf).
+// An edge (i, j, M, Omega, w), poses camera -> world, M maps coordinates of camera i into camera j: E = T_i^-1 T_j M (the identity when
+// consistent), s = E.q.w >= 0 ? 1 : -1, r = (E.t, 2 s E.q.ijk), energy = w * (r . (Omega r)).
+// Jacobians for T_k <- T_k exp(d_k): T_j exp(d) M = E exp(Ad(M^-1) d) and exp(-d) E = E exp(-Ad(E^-1) d), and E exp(e) has the residual
+// r + A(E) e to first order, A(E) = blockdiag(R_E, s (E.q.w I + [E.q.ijk]x)) — so J_j = A Ad(M^-1), J_i = -A Ad(E^-1), with
+// Ad(R, t) = [[R, [t]x R], [0, R]] in se3_exp's (v, w) order (checked against central differences: tests/test_pose_graph_host.py).
+#define VORS_PG_CHUNK 1024
+#define VORS_PG_LIN 56  // floats of an edge's record beside W: H_ii (21, lower triangle row-wise), H_jj (21), g_i (6), g_j (6), 2 of padding
+enum PgStatus { PG_ITERATIONS = 0, PG_CONVERGED = 1, PG_TOO_FEW = 2, PG_SINGULAR = 3 };
+VORS_HD bool pg_finite(float x) { return x - x == 0.0f; }
+// SKIPPED unless: i != j, both below node_count, w finite and > 0, every entry of the measurement and of the information finite
+VORS_HD bool pg_edge_valid(uint32_t i, uint32_t j, uint32_t node_count, float w, const float* meas7, const float* info36 /* nullable */) {
+    bool ok = i != j && i < node_count && j < node_count && pg_finite(w) && w > 0.0f;
+    for (int k = 0; k < 7; ++k) ok = ok && pg_finite(meas7[k]);
+    if (info36)
+        for (int k = 0; k < 36; ++k) ok = ok && pg_finite(info36[k]);
+    return ok;
+}
+// The information of an edge as the arithmetic reads it: the given matrix, or — none given — the identity, through the SAME arithmetic,
+// so that NULL equals identity matrices bit for bit.
+VORS_HD void pg_load_info(const float* info36 /* nullable */, float om[36]) {
+VORS_UNROLL
+    for (int k = 0; k < 36; ++k) om[k] = info36 ? info36[k] : (k % 7 == 0 ? 1.0f : 0.0f);
+}
+VORS_HD float pg_edge_error(const Iso& ti, const Iso& tj, const Iso& m, Iso* e, float r[6]) {
+    *e = iso_mul(iso_mul(iso_inverse(ti), tj), m);
+    const float s = e->q.w >= 0.0f ? 1.0f : -1.0f;
+    r[0] = e->t.x; r[1] = e->t.y; r[2] = e->t.z;
+    r[3] = (2.0f * s) * e->q.i; r[4] = (2.0f * s) * e->q.j; r[5] = (2.0f * s) * e->q.k;
+    return s;
+}
+// w * (r . (Omega r)): rows of Omega r left to right, then the six products r[a] (Omega r)[a] in ascending a
+VORS_HD float pg_edge_energy(const float r[6], const float om[36], float w) {
+    float e = 0.0f;
+VORS_UNROLL
+    for (int a = 0; a < 6; ++a) {
+        float t = om[a * 6] * r[0];
+VORS_UNROLL
+        for (int b = 1; b < 6; ++b) t = t + om[a * 6 + b] * r[b];
+        e = a == 0 ? r[0] * t : e + r[a] * t;
+    }
+    return w * e;
+}
+VORS_HD void pg_rot(const Quat& q, float m[9]) {
+    const float ii = q.i * q.i, jj = q.j * q.j, kk = q.k * q.k, ij = q.i * q.j, ik = q.i * q.k, jk = q.j * q.k;
+    const float iw = q.i * q.w, jw = q.j * q.w, kw = q.k * q.w;
+    m[0] = 1.0f - 2.0f * (jj + kk); m[1] = 2.0f * (ij - kw); m[2] = 2.0f * (ik + jw);
+    m[3] = 2.0f * (ij + kw); m[4] = 1.0f - 2.0f * (ii + kk); m[5] = 2.0f * (jk - iw);
+    m[6] = 2.0f * (ik - jw); m[7] = 2.0f * (jk + iw); m[8] = 1.0f - 2.0f * (ii + jj);
+}
+VORS_HD void pg_mul3(const float a[9], const float b[9], float c[9]) {
+VORS_UNROLL
+    for (int r = 0; r < 3; ++r)
+VORS_UNROLL
+        for (int q = 0; q < 3; ++q) c[r * 3 + q] = (a[r * 3] * b[q] + a[r * 3 + 1] * b[3 + q]) + a[r * 3 + 2] * b[6 + q];
+}
+// A(E) Ad(T) for T = (rotation matrix rt, translation t), scaled by sign: the 6x6 Jacobian, row-major, its lower-left block exact zeros
+VORS_HD void pg_jacobian(const float re[9], const float qe[9], const float rt[9], const V3& t, float sign, float j[36]) {
+    const float hat[9] = {0.0f, -t.z, t.y, t.z, 0.0f, -t.x, -t.y, t.x, 0.0f};
+    float hr[9], a[9], b[9], c[9];
+    pg_mul3(hat, rt, hr);
+    pg_mul3(re, rt, a);
+    pg_mul3(re, hr, b);
+    pg_mul3(qe, rt, c);
+VORS_UNROLL
+    for (int r = 0; r < 3; ++r)
+VORS_UNROLL
+        for (int q = 0; q < 3; ++q) {
+            j[r * 6 + q] = sign * a[r * 3 + q];
+            j[r * 6 + 3 + q] = sign * b[r * 3 + q];
+            j[(r + 3) * 6 + q] = 0.0f;
+            j[(r + 3) * 6 + 3 + q] = sign * c[r * 3 + q];
+        }
+}
+// The residual and both Jacobians of an edge at the poses (ti, tj)
+VORS_HD void pg_edge_jacobians(const Iso& ti, const Iso& tj, const Iso& m, float r[6], float ji[36], float jj[36]) {
+    Iso e;
+    const float s = pg_edge_error(ti, tj, m, &e, r);
+    float re[9], rm[9], rei[9];
+    pg_rot(e.q, re);
+    const float qe[9] = {s * e.q.w, s * -e.q.k, s * e.q.j, s * e.q.k, s * e.q.w, s * -e.q.i, s * -e.q.j, s * e.q.i, s * e.q.w};
+    const Iso mi = iso_inverse(m), ei = iso_inverse(e);
+    pg_rot(mi.q, rm);
+    pg_rot(ei.q, rei);
+    pg_jacobian(re, qe, rm, mi.t, 1.0f, jj);
+    pg_jacobian(re, qe, rei, ei.t, -1.0f, ji);
+}
+// c = a b, 6x6 row-major, each entry summed left to right; at = true: c = a^T b
+VORS_HD void pg_mul6(const float a[36], bool at, const float b[36], float c[36]) {
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int q = 0; q < 6; ++q) {
+            float t = (at ? a[r] : a[r * 6]) * b[q];
+VORS_UNROLL
+            for (int k = 1; k < 6; ++k) t = t + (at ? a[k * 6 + r] : a[r * 6 + k]) * b[k * 6 + q];
+            c[r * 6 + q] = t;
+        }
+}
+// The linearisation of a valid edge: W = J_i^T (w Omega) J_j (36, row-major), and lin = the lower triangles of J_i^T (w Omega) J_i and
+// J_j^T (w Omega) J_j, g_i = J_i^T (w Omega) r, g_j = J_j^T (w Omega) r. w Omega is formed first, entry by entry.
+VORS_HD void pg_edge_linearise(const Iso& ti, const Iso& tj, const Iso& m, const float om[36], float w, float wmat[36], float lin[VORS_PG_LIN]) {
+    float r[6], ji[36], jj[36], ow[36], bi[36], bj[36], v[6];
+    pg_edge_jacobians(ti, tj, m, r, ji, jj);
+VORS_UNROLL
+    for (int k = 0; k < 36; ++k) ow[k] = w * om[k];
+    pg_mul6(ow, false, ji, bi);
+    pg_mul6(ow, false, jj, bj);
+    pg_mul6(ji, true, bj, wmat);
+VORS_UNROLL
+    for (int a = 0; a < 6; ++a) {
+        float t = ow[a * 6] * r[0];
+VORS_UNROLL
+        for (int b = 1; b < 6; ++b) t = t + ow[a * 6 + b] * r[b];
+        v[a] = t;
+    }
+    int k = 0;
+VORS_UNROLL
+    for (int a = 0; a < 6; ++a)
+VORS_UNROLL
+        for (int b = 0; b <= a; ++b, ++k) {
+            float hi = ji[a] * bi[b], hj = jj[a] * bj[b];
+VORS_UNROLL
+            for (int c = 1; c < 6; ++c) {
+                hi = hi + ji[c * 6 + a] * bi[c * 6 + b];
+                hj = hj + jj[c * 6 + a] * bj[c * 6 + b];
+            }
+            lin[k] = hi;
+            lin[21 + k] = hj;
+        }
+VORS_UNROLL
+    for (int a = 0; a < 6; ++a) {
+        float gi = ji[a] * v[0], gj = jj[a] * v[0];
+VORS_UNROLL
+        for (int c = 1; c < 6; ++c) {
+            gi = gi + ji[c * 6 + a] * v[c];
+            gj = gj + jj[c * 6 + a] * v[c];
+        }
+        lin[42 + a] = gi;
+        lin[48 + a] = gj;
+    }
+    lin[54] = lin[55] = 0.0f;
+}
+// A node's damped block and its factor from the sums over its edges: hd = H_kk with the diagonal times (1 + lambda) — cholesky6_solve's
+// damping, D = diag(H) — and fac = its Cholesky factor (lower, cholesky6_solve's left-looking order). No early exit: a pivot that is not
+// > 0 is remembered and the loops run on. -> whether a factor exists. Lower triangles row-wise: (r, c) at r (r + 1) / 2 + c.
+VORS_HD bool pg_node_factor(const float h21[21], float lambda, float hd[21], float fac[21]) {
+    float a[6][6];
+    const float scale = 1.0f + lambda;
+    int k = 0;
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int c = 0; c <= r; ++c, ++k) {
+            hd[k] = r == c ? h21[k] * scale : h21[k];
+            a[r][c] = hd[k];
+        }
+    bool ok = true;
+VORS_UNROLL
+    for (int j = 0; j < 6; ++j) {
+VORS_UNROLL
+        for (int q = 0; q < j; ++q) {
+            const float factor = -a[j][q];
+VORS_UNROLL
+            for (int i = j; i < 6; ++i) a[i][j] = factor * a[i][q] + a[i][j];
+        }
+        ok = ok && a[j][j] > 0.0f;
+        const float denom = sqrtf(a[j][j]);
+        a[j][j] = denom;
+VORS_UNROLL
+        for (int i = j + 1; i < 6; ++i) a[i][j] /= denom;
+    }
+    k = 0;
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r)
+VORS_UNROLL
+        for (int c = 0; c <= r; ++c, ++k) fac[k] = a[r][c];
+    return ok;
+}
+// x = (L L^T)^-1 b: forward, then backward substitution, cholesky6_solve's order
+VORS_HD void pg_factor_solve(const float fac[21], const float b6[6], float x[6]) {
+    float b[6];
+VORS_UNROLL
+    for (int i = 0; i < 6; ++i) b[i] = b6[i];
+VORS_UNROLL
+    for (int i = 0; i < 6; ++i) {
+        const float coeff = b[i] / fac[i * (i + 1) / 2 + i];
+        b[i] = coeff;
+VORS_UNROLL
+        for (int k = i + 1; k < 6; ++k) b[k] = (-coeff) * fac[k * (k + 1) / 2 + i] + b[k];
+    }
+VORS_UNROLL
+    for (int i = 5; i >= 0; --i) {
+        float dot = 0.0f;
+VORS_UNROLL
+        for (int k = i + 1; k < 6; ++k) dot += fac[k * (k + 1) / 2 + i] * b[k];
+        b[i] = (b[i] - dot) / fac[i * (i + 1) / 2 + i];
+    }
+VORS_UNROLL
+    for (int i = 0; i < 6; ++i) x[i] = b[i];
+}
+// The product (H + lambda D) p at one node: y = hd p first (the lower triangle mirrored, each row left to right), then per incident
+// valid edge in ascending edge index y = y + W p_other (the node is the edge's i) or y + W^T p_other (it is the edge's j).
+VORS_HD void pg_matvec_own(const float hd[21], const float p[6], float y[6]) {
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r) {
+        float t = hd[r * (r + 1) / 2] * p[0];
+VORS_UNROLL
+        for (int c = 1; c < 6; ++c) t = t + (c <= r ? hd[r * (r + 1) / 2 + c] : hd[c * (c + 1) / 2 + r]) * p[c];
+        y[r] = t;
+    }
+}
+VORS_HD void pg_matvec_edge(const float wmat[36], bool transposed, const float po[6], float y[6]) {
+VORS_UNROLL
+    for (int r = 0; r < 6; ++r) {
+        float t = (transposed ? wmat[r] : wmat[r * 6]) * po[0];
+VORS_UNROLL
+        for (int c = 1; c < 6; ++c) t = t + (transposed ? wmat[c * 6 + r] : wmat[r * 6 + c]) * po[c];
+        y[r] = y[r] + t;
+    }
+}
+// THE SCALARS OF THE CONJUGATE GRADIENTS ARE f64: a node's share of a dot product is the f64 sum, left to right, of the exact f64
+// products of its six f32 pairs; the shares go through the chunk tree in f64. alpha and beta are rounded to f32 ONCE, and the vectors
+// are updated in f32.
+VORS_HD double pg_dot6(const float a[6], const float b[6]) {
+    double s = (double)a[0] * (double)b[0];
+VORS_UNROLL
+    for (int k = 1; k < 6; ++k) s = s + (double)a[k] * (double)b[k];
+    return s;
+}
+VORS_HD float pg_cg_alpha(double rz, double pq) { return pq > 0.0 ? (float)(rz / pq) : 0.0f; }
+VORS_HD float pg_cg_beta(double rz, double rz_prev) { return rz_prev > 0.0 ? (float)(rz / rz_prev) : 0.0f; }
+// the iterations end when |r| <= cg_tol |r_0| (a NaN ends them as well)
+VORS_HD bool pg_cg_reached(double rr, double rr0, float cg_tol) { return !(rr > ((double)cg_tol * (double)cg_tol) * rr0); }
+// p_t = z_t + beta_t p_(t-1), the direction a node and its neighbours both form from the stored z and p_(t-1)
+VORS_HD void pg_cg_direction(const float z[6], float beta, const float p_prev[6], float p[6]) {
+VORS_UNROLL
+    for (int k = 0; k < 6; ++k) p[k] = z[k] + beta * p_prev[k];
+}
+VORS_HD float pg_step2(const float d[6]) {
+    float s = d[0] * d[0];
+VORS_UNROLL
+    for (int k = 1; k < 6; ++k) s = s + d[k] * d[k];
+    return s;
+}
+VORS_HD Iso pg_candidate(const Iso& t, const float delta[6]) { return renormalize(iso_mul(t, se3_exp(delta))); }
+// The round's verdict. lm_verdict's constants (accepted: lambda = 0.1f * lambda, rejected: lambda *= 10.0f), not its rule: a NaN energy
+// is REJECTED here, and nothing stops on a small decrease of the energy — the step norm does that.
+VORS_HD bool pg_accepts(float energy, float cur_energy) { return energy <= cur_energy; }
+VORS_HD float pg_lambda_after(bool accepted, float lambda) { return accepted ? 0.1f * lambda : lambda * 10.0f; }
+// The halving tree of a chunk on the host: v[s] = v[s] + v[s + w] for w = 512 .. 1; the chunk's sum is v[0].
+template <class T>
+inline T pg_chunk_tree(T* v) {
+    for (int w = VORS_PG_CHUNK / 2; w >= 1; w /= 2)
+        for (int s = 0; s < w; ++s) v[s] = v[s] + v[s + w];
+    return v[0];
+}
+
 }  // namespace vors

@@ -1,5 +1,6 @@
 // Everything of the C ABI that is not a handle: last error, device queries and self-checks, the LM operators on explicit observations
 // (vors_lm_*), Lie helpers and the synthetic scenes.
+#include <algorithm>
 #include <cstring>
 #include <unordered_map>
 #include <vector>
@@ -970,6 +971,295 @@ vors_status vors_icp_points_joint_host(const float* xyz, const float* normals, c
     return icp_points_host("icp_points_joint_host",
                            icp_args(1, xyz, normals, &count, capacity, range2, 0, pose7_in, 0, depth, cam5, rows, cols, depth_scale, dist_m, damping,
                                     step_eps, iters, min_points, nullptr, pose7_out, stats, sums29, residuals, &robust, &joint));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Pose-graph optimisation (vors_pose_graph_optimize, vors_pose_graph_optimize_host; include/vors_hip.h 2g): the refusals both share, the
+// device entry (pose_graph_kernels.hip) and the host entry, which runs the kernels' own texts (lie.h pg_*) launch by launch, with the
+// order of sums the header states.
+// ---------------------------------------------------------------------------------------------------------------
+static vors_status pg_refusals(const char* who, const PgCall& c) {
+    const std::string w(who);
+    if (!c.poses_in) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the input poses are NULL");
+    if (!c.node_counts || !c.edge_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a count (nodes, edges) is NULL");
+    if (!c.edges || !c.meas) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the edges or their measurements are NULL");
+    if (!c.poses_out) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the output poses are NULL");
+    if (c.node_capacity < 1 || c.edge_capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": node_capacity and edge_capacity must be >= 1");
+    if (c.node_capacity > (1 << 28) || c.edge_capacity > (1 << 28))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": node_capacity and edge_capacity must not exceed 2^28");
+    if (!(c.lambda0 >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": lambda0 must be >= 0 (and not NaN)");
+    if (!(c.step_eps >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": step_eps must be >= 0 (and not NaN)");
+    if (!(c.cg_tol >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cg_tol must be >= 0 (and not NaN)");
+    if (c.iters < 0 || c.iters > 64) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": iters must be in 0..64");
+    if (c.cg_iters < 1 || c.cg_iters > 256) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": cg_iters must be in 1..256");
+    if ((uintptr_t)c.poses_in % 4 != 0 || (uintptr_t)c.node_counts % 4 != 0 || (uintptr_t)c.edge_counts % 4 != 0 || (uintptr_t)c.edges % 4 != 0 ||
+        (uintptr_t)c.meas % 4 != 0 || (uintptr_t)c.info % 4 != 0 || (uintptr_t)c.weight % 4 != 0 || (uintptr_t)c.poses_out % 4 != 0 ||
+        (uintptr_t)c.stats % 4 != 0 || (uintptr_t)c.edge_residuals % 4 != 0 || (uintptr_t)c.edge_energy % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the poses, counts, edges, measurements, information, weights, stats, residuals and energies "
+                                                   "must be 4-byte aligned");
+    return VORS_OK;
+}
+
+static PgCall pg_call(int n, const void* poses7_in, const uint32_t* node_counts, int node_capacity, const uint32_t* edges, const uint32_t* edge_counts,
+                      int edge_capacity, const float* meas7, const float* info36, const float* edge_weight, const uint8_t* fixed, float lambda0,
+                      float step_eps, float cg_tol, int iters, int cg_iters, float* poses7_out, vors_pose_graph_stats* stats, float* edge_residuals,
+                      float* edge_energy) {
+    PgCall c{};
+    c.n = n; c.node_capacity = node_capacity; c.edge_capacity = edge_capacity;
+    c.poses_in = static_cast<const float*>(poses7_in); c.pose_stride = 7;
+    c.node_counts = node_counts; c.edges = edges; c.edge_counts = edge_counts; c.meas = meas7; c.info = info36; c.weight = edge_weight; c.fixed = fixed;
+    c.lambda0 = lambda0; c.step_eps = step_eps; c.cg_tol = cg_tol; c.iters = iters; c.cg_iters = cg_iters;
+    c.poses_out = poses7_out; c.stats = stats; c.edge_residuals = edge_residuals; c.edge_energy = edge_energy;
+    return c;
+}
+
+uint64_t vors_pose_graph_workspace_bytes(int n, int node_capacity, int edge_capacity) {
+    if (n < 1 || node_capacity < 1 || edge_capacity < 1) return 0;
+    return (uint64_t)pg_workspace_carve(nullptr, nullptr, n, node_capacity, edge_capacity);
+}
+
+vors_status vors_pose_graph_optimize(int n, const void* d_poses7_in, size_t pose_stride_bytes, const uint32_t* d_node_counts, int node_capacity,
+                                     const uint32_t* d_edges, const uint32_t* d_edge_counts, int edge_capacity, const float* d_meas7,
+                                     const float* d_info36, const float* d_edge_weight, const uint8_t* d_fixed, float lambda0, float step_eps,
+                                     float cg_tol, int iters, int cg_iters, void* d_workspace, float* d_poses7_out, vors_pose_graph_stats* d_stats,
+                                     float* d_edge_residuals, float* d_edge_energy, void* hip_stream) {
+    const char* who = "pose_graph_optimize";
+    const std::string w(who);
+    PgCall call = pg_call(n, d_poses7_in, d_node_counts, node_capacity, d_edges, d_edge_counts, edge_capacity, d_meas7, d_info36, d_edge_weight,
+                          d_fixed, lambda0, step_eps, cg_tol, iters, cg_iters, d_poses7_out, d_stats, d_edge_residuals, d_edge_energy);
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be >= 1");
+    vors_status st = pg_refusals(who, call);
+    if (st != VORS_OK) return st;
+    if (!d_workspace) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_workspace is NULL (the pass allocates nothing: vors_pose_graph_workspace_bytes)");
+    if ((st = stride_refusal(who, "pose_stride_bytes", pose_stride_bytes, 28, OPERATOR_STRIDE_LIMIT)) != VORS_OK) return st;
+    if ((uintptr_t)d_workspace % 16 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if ((st = require_device()) != VORS_OK) return st;
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
+    pg_workspace_carve(&call, d_workspace, n, node_capacity, edge_capacity);
+    launch_pose_graph(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+// The loop of ONE graph on the host: the kernels of pose_graph_kernels.hip in their launch order, each a plain loop.
+static void pg_host_loop(const PgCall& c) {
+    const uint32_t nodes = std::min<uint32_t>(c.node_counts[0], (uint32_t)c.node_capacity), edges = std::min<uint32_t>(c.edge_counts[0], (uint32_t)c.edge_capacity);
+    const uint32_t nchunks = (nodes + (VORS_PG_CHUNK - 1)) / VORS_PG_CHUNK, echunks = (edges + (VORS_PG_CHUNK - 1)) / VORS_PG_CHUNK;
+    auto weight_of = [&](uint32_t e) { return c.weight ? c.weight[e] : 1.0f; };
+    auto info_of = [&](uint32_t e) { return c.info ? c.info + (size_t)e * 36 : nullptr; };
+    // BEGIN .. RANK: validity, classes, the incidence lists in ascending edge index
+    PgState st{};
+    st.status = PG_ITERATIONS;
+    st.lambda = c.lambda0;
+    std::vector<float> poses[2];
+    poses[0].assign((size_t)nodes * 7, 0.0f);
+    poses[1].assign((size_t)nodes * 7, 0.0f);
+    for (size_t k = 0; k < (size_t)nodes * 7; ++k) poses[0][k] = c.poses_in[k];
+    std::vector<uint8_t> ok(edges);
+    std::vector<std::vector<uint32_t>> inc(nodes);
+    for (uint32_t e = 0; e < edges; ++e) {
+        const uint32_t i = c.edges[2 * (size_t)e], j = c.edges[2 * (size_t)e + 1];
+        ok[e] = pg_edge_valid(i, j, nodes, weight_of(e), c.meas + (size_t)e * 7, info_of(e)) ? 1 : 0;
+        if (!ok[e]) continue;
+        st.valid_edges += 1u;
+        inc[i].push_back(e << 1);
+        inc[j].push_back((e << 1) | 1u);
+    }
+    st.skipped_edges = edges - st.valid_edges;
+    std::vector<uint32_t> cls(nodes);
+    for (uint32_t k = 0; k < nodes; ++k) {
+        const bool fixed = c.fixed ? c.fixed[k] != 0 : k == 0;
+        cls[k] = fixed ? PG_NODE_FIXED : (inc[k].empty() ? PG_NODE_ISOLATED : PG_NODE_FREE);
+        (cls[k] == PG_NODE_FREE ? st.free_nodes : cls[k] == PG_NODE_FIXED ? st.fixed_nodes : st.isolated_nodes) += 1u;
+    }
+    if (st.valid_edges == 0u || st.free_nodes == 0u) {
+        st.status = PG_TOO_FEW;
+        st.frozen = 1u;
+    }
+    // ENERGY at one of the two pose buffers; final: the per-edge outputs as well
+    std::vector<float> slots(VORS_PG_CHUNK);
+    auto energy_at = [&](uint32_t which, bool final) {
+        const float* p = poses[which].data();
+        const float nan = nanf("");
+        float sum = 0.0f;
+        for (uint32_t chunk = 0; chunk < echunks; ++chunk) {
+            for (uint32_t s = 0; s < VORS_PG_CHUNK; ++s) {
+                const uint32_t e = chunk * VORS_PG_CHUNK + s;
+                slots[s] = 0.0f;
+                if (e >= edges) continue;
+                float r[6], energy = 0.0f;
+                if (ok[e]) {
+                    float om[36];
+                    pg_load_info(info_of(e), om);
+                    Iso err;
+                    pg_edge_error(iso_load(p + (size_t)c.edges[2 * (size_t)e] * 7), iso_load(p + (size_t)c.edges[2 * (size_t)e + 1] * 7),
+                                  iso_load(c.meas + (size_t)e * 7), &err, r);
+                    energy = pg_edge_energy(r, om, weight_of(e));
+                    slots[s] = energy;
+                }
+                if (final && c.edge_residuals)
+                    for (int k = 0; k < 6; ++k) c.edge_residuals[(size_t)e * 6 + k] = ok[e] ? r[k] : nan;
+                if (final && c.edge_energy) c.edge_energy[e] = ok[e] ? energy : nan;
+            }
+            const float v = pg_chunk_tree(slots.data());
+            sum = chunk == 0 ? v : sum + v;
+        }
+        return sum;
+    };
+    st.energy = st.initial_energy = energy_at(st.cur, false);
+    std::vector<float> wmat((size_t)edges * 36), lin((size_t)edges * VORS_PG_LIN), hd((size_t)nodes * 21), fac((size_t)nodes * 21);
+    std::vector<float> x((size_t)nodes * 6, 0.0f), r((size_t)nodes * 6, 0.0f), z((size_t)nodes * 6, 0.0f), q((size_t)nodes * 6, 0.0f), p[2];
+    p[0].assign((size_t)nodes * 6, 0.0f);
+    p[1].assign((size_t)nodes * 6, 0.0f);
+    std::vector<double> dslots(VORS_PG_CHUNK), dot_pq(nchunks), dot_rz[2], dot_rr[2], dot_rr0(nchunks);
+    for (int b = 0; b < 2; ++b) {
+        dot_rz[b].assign(nchunks, 0.0);
+        dot_rr[b].assign(nchunks, 0.0);
+    }
+    auto sum_chunks = [&](const std::vector<double>& part) {
+        double s = nchunks > 0 ? part[0] : 0.0;
+        for (uint32_t ch = 1; ch < nchunks; ++ch) s = s + part[ch];
+        return s;
+    };
+    // one dot product's chunk sums: share(k) for the free nodes, 0.0 for the others and beyond the count
+    auto node_dots = [&](std::vector<double>& part, auto share) {
+        for (uint32_t chunk = 0; chunk < nchunks; ++chunk) {
+            for (uint32_t s = 0; s < VORS_PG_CHUNK; ++s) {
+                const uint32_t k = chunk * VORS_PG_CHUNK + s;
+                dslots[s] = k < nodes && cls[k] == PG_NODE_FREE ? share(k) : 0.0;
+            }
+            part[chunk] = pg_chunk_tree(dslots.data());
+        }
+    };
+    for (int it = 0; it < c.iters; ++it) {
+        if (st.frozen) break;
+        const float* cur = poses[st.cur].data();
+        if (!st.lin_ok)  // LINEARISE
+            for (uint32_t e = 0; e < edges; ++e) {
+                if (!ok[e]) continue;
+                float om[36];
+                pg_load_info(info_of(e), om);
+                pg_edge_linearise(iso_load(cur + (size_t)c.edges[2 * (size_t)e] * 7), iso_load(cur + (size_t)c.edges[2 * (size_t)e + 1] * 7),
+                                  iso_load(c.meas + (size_t)e * 7), om, weight_of(e), wmat.data() + (size_t)e * 36, lin.data() + (size_t)e * VORS_PG_LIN);
+            }
+        // GATHER
+        for (uint32_t k = 0; k < nodes; ++k) {
+            if (cls[k] != PG_NODE_FREE) continue;
+            float h[21], gk[6], rk[6];
+            for (size_t s = 0; s < inc[k].size(); ++s) {
+                const uint32_t key = inc[k][s];
+                const float* le = lin.data() + (size_t)(key >> 1) * VORS_PG_LIN + (key & 1u) * 21;
+                const float* ge = lin.data() + (size_t)(key >> 1) * VORS_PG_LIN + 42 + (key & 1u) * 6;
+                for (int m = 0; m < 21; ++m) h[m] = s == 0 ? le[m] : h[m] + le[m];
+                for (int m = 0; m < 6; ++m) gk[m] = s == 0 ? ge[m] : gk[m] + ge[m];
+            }
+            if (!pg_node_factor(h, st.lambda, hd.data() + (size_t)k * 21, fac.data() + (size_t)k * 21)) st.singular = 1u;
+            for (int m = 0; m < 6; ++m) rk[m] = -gk[m];
+            pg_factor_solve(fac.data() + (size_t)k * 21, rk, z.data() + (size_t)k * 6);
+            for (int m = 0; m < 6; ++m) {
+                r[(size_t)k * 6 + m] = rk[m];
+                x[(size_t)k * 6 + m] = 0.0f;
+                p[1][(size_t)k * 6 + m] = 0.0f;
+            }
+        }
+        node_dots(dot_rz[0], [&](uint32_t k) { return pg_dot6(r.data() + (size_t)k * 6, z.data() + (size_t)k * 6); });
+        node_dots(dot_rr[0], [&](uint32_t k) { return pg_dot6(r.data() + (size_t)k * 6, r.data() + (size_t)k * 6); });
+        dot_rr0 = dot_rr[0];
+        if (st.singular) {  // VERDICT's first branch
+            st.status = PG_SINGULAR;
+            st.frozen = 1u;
+            break;
+        }
+        for (int t = 0; t < c.cg_iters; ++t) {
+            const uint32_t tc = (uint32_t)t & 1u, tp = tc ^ 1u;
+            // CG A
+            const bool done = st.cg_done[tp] != 0u || pg_cg_reached(sum_chunks(dot_rr[tc]), sum_chunks(dot_rr0), c.cg_tol);
+            st.cg_done[tc] = done ? 1u : 0u;
+            if (done) continue;
+            const float beta = t > 0 ? pg_cg_beta(sum_chunks(dot_rz[tc]), sum_chunks(dot_rz[tp])) : 0.0f;
+            for (uint32_t k = 0; k < nodes; ++k) {
+                if (cls[k] != PG_NODE_FREE) continue;
+                float pk[6], y[6];
+                pg_cg_direction(z.data() + (size_t)k * 6, beta, p[tp].data() + (size_t)k * 6, pk);
+                for (int m = 0; m < 6; ++m) p[tc][(size_t)k * 6 + m] = pk[m];
+                pg_matvec_own(hd.data() + (size_t)k * 21, pk, y);
+                for (uint32_t key : inc[k]) {
+                    const uint32_t e = key >> 1, side = key & 1u, other = c.edges[2 * (size_t)e + (side ^ 1u)];
+                    float d[6];
+                    pg_cg_direction(z.data() + (size_t)other * 6, beta, p[tp].data() + (size_t)other * 6, d);
+                    pg_matvec_edge(wmat.data() + (size_t)e * 36, side != 0u, d, y);
+                }
+                for (int m = 0; m < 6; ++m) q[(size_t)k * 6 + m] = y[m];
+            }
+            node_dots(dot_pq, [&](uint32_t k) { return pg_dot6(p[tc].data() + (size_t)k * 6, q.data() + (size_t)k * 6); });
+            // CG B
+            const float alpha = pg_cg_alpha(sum_chunks(dot_rz[tc]), sum_chunks(dot_pq));
+            st.cg_spent += 1u;
+            for (uint32_t k = 0; k < nodes; ++k) {
+                if (cls[k] != PG_NODE_FREE) continue;
+                for (int m = 0; m < 6; ++m) {
+                    x[(size_t)k * 6 + m] = x[(size_t)k * 6 + m] + alpha * p[tc][(size_t)k * 6 + m];
+                    r[(size_t)k * 6 + m] = r[(size_t)k * 6 + m] - alpha * q[(size_t)k * 6 + m];
+                }
+                pg_factor_solve(fac.data() + (size_t)k * 21, r.data() + (size_t)k * 6, z.data() + (size_t)k * 6);
+            }
+            node_dots(dot_rz[tp], [&](uint32_t k) { return pg_dot6(r.data() + (size_t)k * 6, z.data() + (size_t)k * 6); });
+            node_dots(dot_rr[tp], [&](uint32_t k) { return pg_dot6(r.data() + (size_t)k * 6, r.data() + (size_t)k * 6); });
+        }
+        // CANDIDATE
+        float* cand = poses[st.cur ^ 1u].data();
+        float d2max = 0.0f;
+        for (uint32_t k = 0; k < nodes; ++k) {
+            if (cls[k] != PG_NODE_FREE) {
+                for (int m = 0; m < 7; ++m) cand[(size_t)k * 7 + m] = cur[(size_t)k * 7 + m];
+                continue;
+            }
+            iso_store(pg_candidate(iso_load(cur + (size_t)k * 7), x.data() + (size_t)k * 6), cand + (size_t)k * 7);
+            const float d2 = pg_step2(x.data() + (size_t)k * 6);
+            if (d2 > d2max) d2max = d2;  // (a NaN is left out)
+        }
+        // ENERGY at the candidates, VERDICT
+        const float energy = energy_at(st.cur ^ 1u, false);
+        const bool accepted = pg_accepts(energy, st.energy);
+        st.lambda = pg_lambda_after(accepted, st.lambda);
+        if (accepted) {
+            st.cur ^= 1u;
+            st.energy = energy;
+            st.accepted += 1u;
+            st.last_step_norm = sqrtf(d2max);
+            st.lin_ok = 0u;
+            if (d2max <= c.step_eps * c.step_eps) {
+                st.status = PG_CONVERGED;
+                st.frozen = 1u;
+            }
+        } else {
+            st.rejected += 1u;
+            st.lin_ok = 1u;
+        }
+        st.cg_done[0] = st.cg_done[1] = 0u;
+    }
+    // the final ENERGY, FINISH
+    const float final_energy = energy_at(st.cur, true);
+    for (size_t k = 0; k < (size_t)nodes * 7; ++k) c.poses_out[k] = poses[st.cur][k];
+    if (c.stats)
+        *c.stats = vors_pose_graph_stats{st.status,     st.accepted,       st.rejected,       st.cg_spent,  st.valid_edges,    st.skipped_edges, st.free_nodes,
+                                         st.fixed_nodes, st.isolated_nodes, st.initial_energy, final_energy, st.last_step_norm, st.lambda};
+}
+
+vors_status vors_pose_graph_optimize_host(const float* poses7_in, uint32_t node_count, int node_capacity, const uint32_t* edges, uint32_t edge_count,
+                                          int edge_capacity, const float* meas7, const float* info36, const float* edge_weight, const uint8_t* fixed,
+                                          float lambda0, float step_eps, float cg_tol, int iters, int cg_iters, float* poses7_out,
+                                          vors_pose_graph_stats* stats, float* edge_residuals, float* edge_energy) {
+    const PgCall call = pg_call(1, poses7_in, &node_count, node_capacity, edges, &edge_count, edge_capacity, meas7, info36, edge_weight, fixed, lambda0,
+                                step_eps, cg_tol, iters, cg_iters, poses7_out, stats, edge_residuals, edge_energy);
+    const vors_status st = pg_refusals("pose_graph_optimize_host", call);
+    if (st != VORS_OK) return st;
+    pg_host_loop(call);
+    return VORS_OK;
+}
+
+void vors_pose_graph_jacobians_host(const float ti7[7], const float tj7[7], const float meas7[7], float r6[6], float ji36[36], float jj36[36]) {
+    pg_edge_jacobians(iso_load(ti7), iso_load(tj7), iso_load(meas7), r6, ji36, jj36);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

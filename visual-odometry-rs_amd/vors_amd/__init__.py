@@ -118,6 +118,7 @@ EXPORTED_SYMBOLS = [
     "vors_icp_workspace_bytes", "vors_icp_points", "vors_icp_points_host", "vors_trackers_icp_map",
     "vors_icp_points_robust", "vors_icp_points_robust_host", "vors_trackers_icp_map_robust",
     "vors_icp_points_joint", "vors_icp_points_joint_host", "vors_trackers_icp_map_joint",
+    "vors_pose_graph_workspace_bytes", "vors_pose_graph_optimize", "vors_pose_graph_optimize_host", "vors_pose_graph_jacobians_host",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_trackers_enable_map_icp", "vors_trackers_map_icp", "vors_tracker_enable_map_icp", "vors_tracker_read_map_icp",
     "vors_map_icp_window_host", "vors_map_icp_verdict_host",
@@ -244,6 +245,13 @@ def lib():
             getattr(_lib, f"vors_icp_points{form}_host").argtypes = ([vp, vp] + gray + [u32, i, vp, vp, vp] + gray + [vp] + plane + scalars + more_in
                                                                      + out + more_out)
             getattr(_lib, f"vors_trackers_icp_map{form}").argtypes = [vp, vp] + gray + scalars + strided + more_in + [vp] + out + more_out + [vp]
+        _lib.vors_pose_graph_workspace_bytes.argtypes = [i, i, i]
+        _lib.vors_pose_graph_workspace_bytes.restype = C.c_uint64
+        pg_scalars = [f, f, f, i, i]  # lambda0, step_eps, cg_tol, iters, cg_iters
+        _lib.vors_pose_graph_optimize.argtypes = [i, vp, sz, vp, i, vp, vp, i, vp, vp, vp, vp] + pg_scalars + [vp, vp, vp, vp, vp, vp]
+        _lib.vors_pose_graph_optimize_host.argtypes = [vp, u32, i, vp, u32, i, vp, vp, vp, vp] + pg_scalars + [vp, vp, vp, vp]
+        _lib.vors_pose_graph_jacobians_host.argtypes = [vp] * 6
+        _lib.vors_pose_graph_jacobians_host.restype = None
         _lib.vors_trackers_enable_map_icp.argtypes = [vp, vp]
         _lib.vors_trackers_map_icp.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_icp.argtypes = [vp, vp]
@@ -2151,6 +2159,113 @@ def _icp_host(who, xyz, normals, depth, cam5, depth_scale, pose7, dist_m, dampin
                                          int(min_points), *more_in, _ptr(out["pose"]), _ptr(stats),
                                          *[_ptr(a) for name, a in out.items() if name not in ("pose", "stats")]))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- pose-graph optimisation
+PG_ITERATIONS, PG_CONVERGED, PG_TOO_FEW, PG_SINGULAR = range(4)  # VORS_PG_*
+PG_STATS_DTYPE = np.dtype([("status", "<u4"), ("accepted_steps", "<u4"), ("rejected_steps", "<u4"), ("cg_iterations", "<u4"),
+                           ("valid_edges", "<u4"), ("skipped_edges", "<u4"), ("free_nodes", "<u4"), ("fixed_nodes", "<u4"),
+                           ("isolated_nodes", "<u4"), ("initial_energy", "<f4"), ("final_energy", "<f4"), ("last_step_norm", "<f4"),
+                           ("final_lambda", "<f4")])
+assert PG_STATS_DTYPE.itemsize == 52
+
+
+def decode_pose_graph_stats(stats):
+    """The "stats" tensor of pose_graph_optimize() ([n, 52] uint8: the vors_pose_graph_stats records as bytes) -> a structured array [n]."""
+    return np.ascontiguousarray(stats.cpu().numpy()).view(PG_STATS_DTYPE).reshape(-1)
+
+
+def pose_graph_workspace_bytes(n, node_capacity, edge_capacity):
+    """Bytes of the workspace pose_graph_optimize() needs (vors_pose_graph_workspace_bytes)."""
+    return int(lib().vors_pose_graph_workspace_bytes(int(n), int(node_capacity), int(edge_capacity)))
+
+
+def pose_graph_optimize(poses, node_counts, edges, edge_counts, meas, info=None, edge_weight=None, fixed=None, lambda0=1e-4, step_eps=1e-6,
+                        cg_tol=1e-6, iters=8, cg_iters=32, workspace=None, stats=True, edge_residuals=False, edge_energy=False, out=None):
+    """Pose-graph optimisation of n graphs side by side (vors_pose_graph_optimize; handle-free) -> dict of tensors on the current stream,
+    not synchronised: "poses" [n, node_capacity, 7] float32 (exactly the nodes of each graph written; a new tensor starts as a copy of the
+    input poses), "stats" [n, 52] uint8 (decode_pose_graph_stats()), "edge_residuals" [n, edge_capacity, 6] and "edge_energy"
+    [n, edge_capacity] float32 of the final evaluation, NaN for a skipped edge (a new tensor is filled with NaN first). poses
+    [n, node_capacity, >= 7] float32 camera -> world, the last dimension's stride 1 and the others those of a contiguous tensor (a wider
+    last dimension is the pose stride); node_counts / edge_counts [n] int32; edges [n, edge_capacity, 2] int32 (i, j); meas
+    [n, edge_capacity, 7] float32: M_ij maps camera i's coordinates into camera j's (a track's lm_model of keyframe i and frame j); info
+    [n, edge_capacity, 36] float32 or None (identity); edge_weight [n, edge_capacity] float32 or None; fixed [n, node_capacity] uint8 or
+    None (node 0 of every graph). iters = 0 evaluates. workspace: a uint8 tensor of pose_graph_workspace_bytes() to reuse; out: a
+    [n, node_capacity, 7] tensor for the poses (may be `poses` itself when that is packed); stats / edge_residuals / edge_energy may also
+    be a tensor of that shape to write into."""
+    import torch
+    who = "pose_graph_optimize"
+    if poses.dtype != torch.float32 or poses.dim() != 3 or poses.shape[2] < 7 or not poses.is_contiguous():
+        raise VorsError(f"{who}: poses float32 [n, node_capacity, >= 7], contiguous")
+    n, ncap, width = poses.shape
+    ecap = edges.shape[1] if edges.dim() == 3 else -1
+    dev = poses.device
+    for name, t, dtype, shape in (("node_counts", node_counts, torch.int32, (n,)), ("edge_counts", edge_counts, torch.int32, (n,)),
+                                  ("edges", edges, torch.int32, (n, ecap, 2)), ("meas", meas, torch.float32, (n, ecap, 7)),
+                                  ("info", info, torch.float32, (n, ecap, 36)), ("edge_weight", edge_weight, torch.float32, (n, ecap)),
+                                  ("fixed", fixed, torch.uint8, (n, ncap))):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise VorsError(f"{who}: {name} must be a contiguous {dtype} tensor {shape} on the poses' device")
+    need = pose_graph_workspace_bytes(n, ncap, ecap)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise VorsError(f"{who}: expected a contiguous uint8 workspace of at least {need} bytes")
+    if out is None:
+        out = poses[:, :, :7].contiguous() if width != 7 else poses.clone()
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, ncap, 7) or not out.is_contiguous():
+        raise VorsError(f"{who}: out must be a contiguous float32 tensor ({n}, {ncap}, 7)")
+    bufs = (_out_buf(stats, (n, PG_STATS_DTYPE.itemsize), torch.uint8, dev), _out_buf(edge_residuals, (n, ecap, 6), torch.float32, dev),
+            _out_buf(edge_energy, (n, ecap), torch.float32, dev))
+    if edge_residuals is True:
+        bufs[1].fill_(float("nan"))
+    if edge_energy is True:
+        bufs[2].fill_(float("nan"))
+    dp = Batch._dp
+    _check(lib().vors_pose_graph_optimize(n, dp(poses), 0 if width == 7 else 4 * width, dp(node_counts), ncap, dp(edges), dp(edge_counts), ecap,
+                                          dp(meas), dp(info), dp(edge_weight), dp(fixed), float(lambda0), float(step_eps), float(cg_tol),
+                                          int(iters), int(cg_iters), dp(workspace), dp(out), dp(bufs[0]), dp(bufs[1]), dp(bufs[2]),
+                                          Batch._stream()))
+    return _result(("poses", True, out), ("stats", _asked(stats), bufs[0]), ("edge_residuals", _asked(edge_residuals), bufs[1]),
+                   ("edge_energy", _asked(edge_energy), bufs[2]))
+
+
+def pose_graph_optimize_host(poses, edges, meas, info=None, edge_weight=None, fixed=None, lambda0=1e-4, step_eps=1e-6, cg_tol=1e-6, iters=8,
+                             cg_iters=32, node_count=None, edge_count=None):
+    """The loop of pose_graph_optimize for ONE graph on the host (vors_pose_graph_optimize_host; needs no GPU; the texts and the order of
+    sums the kernels run): poses [node_capacity, 7], edges [edge_capacity, 2], meas [edge_capacity, 7], info [edge_capacity, 36] or None,
+    edge_weight [edge_capacity] or None, fixed [node_capacity] or None; node_count / edge_count: None = the capacities -> dict: "poses"
+    (starts as a copy of the input), "stats" (a PG_STATS_DTYPE record), "edge_residuals" [edge_capacity, 6] and "edge_energy"
+    [edge_capacity] float32 (NaN where not written or skipped)."""
+    who = "pose_graph_optimize_host"
+    p = np.ascontiguousarray(poses, np.float32)
+    e = np.ascontiguousarray(edges, np.uint32)
+    m = np.ascontiguousarray(meas, np.float32)
+    om = None if info is None else np.ascontiguousarray(info, np.float32)
+    w = None if edge_weight is None else np.ascontiguousarray(edge_weight, np.float32)
+    fx = None if fixed is None else np.ascontiguousarray(fixed, np.uint8)
+    if (p.ndim != 2 or p.shape[1] != 7 or e.ndim != 2 or e.shape[1] != 2 or m.shape != (len(e), 7) or (om is not None and om.shape != (len(e), 36))
+            or (w is not None and w.shape != (len(e),)) or (fx is not None and fx.shape != (len(p),))):
+        raise VorsError(f"{who}: poses [node_capacity, 7], edges [edge_capacity, 2], meas [edge_capacity, 7], info [edge_capacity, 36] or "
+                        "None, edge_weight [edge_capacity] or None, fixed [node_capacity] or None")
+    stats = np.zeros(1, PG_STATS_DTYPE)
+    out = dict(poses=p.copy(), stats=stats[0], edge_residuals=np.full((len(e), 6), np.nan, np.float32),
+               edge_energy=np.full(len(e), np.nan, np.float32))
+    some = lambda a: _ptr(a) if a is not None and a.size else None  # noqa: E731
+    _check(lib().vors_pose_graph_optimize_host(some(p), len(p) if node_count is None else int(node_count), len(p), some(e),
+                                               len(e) if edge_count is None else int(edge_count), len(e), some(m), some(om), some(w), some(fx),
+                                               float(lambda0), float(step_eps), float(cg_tol), int(iters), int(cg_iters), some(out["poses"]),
+                                               _ptr(stats), some(out["edge_residuals"]), some(out["edge_energy"])))
+    return out
+
+
+def pose_graph_jacobians_host(ti7, tj7, meas7):
+    """The residual and the closed-form Jacobians of one edge at the poses (ti, tj) (vors_pose_graph_jacobians_host; the kernels' own text)
+    -> (r [6], J_i [6, 6], J_j [6, 6]) float32, for the perturbation T_k <- T_k exp(d_k), d in se3_exp's (v, w) order."""
+    a = [np.ascontiguousarray(v, np.float32).reshape(7) for v in (ti7, tj7, meas7)]
+    r, ji, jj = np.zeros(6, np.float32), np.zeros((6, 6), np.float32), np.zeros((6, 6), np.float32)
+    lib().vors_pose_graph_jacobians_host(*[_ptr(v) for v in a], _ptr(r), _ptr(ji), _ptr(jj))
+    return r, ji, jj
 
 
 ICP_GATE_COUNTS = 4  # VORS_ICP_GATE_COUNTS: with_depth, within_dist, matched, huber_linear
