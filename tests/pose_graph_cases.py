@@ -1,4 +1,4 @@
-"""What tests/test_pose_graph_host.py and tests/test_pose_graph_gpu.py share: a float64 numpy restatement of the pose-graph definition
+"""What tests/test_pose_graph_host.py and tests/test_gpu_pose_graph.py share: a float64 numpy restatement of the pose-graph definition
 (include/vors_hip.h 2g) and the test graphs. Poses are (t, q) with q = (i, j, k, w), camera -> world; a measurement M_ij maps camera i's
 coordinates into camera j's, so consistent poses have T_j = T_i M_ij^-1 and E = T_i^-1 T_j M_ij is the identity."""
 import numpy as np

@@ -4,12 +4,7 @@ measurement convention against the tracker's own outputs (lm_model and info36 fe
 
 Graphs (tests/pose_graph_cases.py): a 23 x 23 grid with 1032 edges cut at 1000 and at 1025 edges (one and two energy chunks), a 33 x 33
 grid (1089 nodes: two node chunks), the star whose hub has 200 edges with skipped edges of every kind appended, the noisy ring with
-information matrices, and an empty graph.
-
-The file sorts behind every other GPU test on purpose: tests/test_gpu_trackers_map_icp.py compares whole map lists, entries past the
-totals included, between two handles, which holds only while both handles' buffers land on the same addresses; GPU tests that run ahead
-of it change which freed blocks the allocator hands back (seen once: "the map's gray moved"). Behind it, no earlier test sees a
-difference."""
+information matrices, and an empty graph."""
 import numpy as np
 import pytest
 

@@ -21,6 +21,7 @@ if [ -f normal_kernels.hip ]; then listing normal_kernels.hip -o "$OUT/normal_ke
 if [ -f icp_kernels.hip ]; then listing icp_kernels.hip -o "$OUT/icp_kernels.s"; fi   # (absent in parents older than the ICP)
 if [ -f map_icp_kernels.hip ]; then listing map_icp_kernels.hip -o "$OUT/map_icp_kernels.s"; fi   # (absent in parents older than the map ICP stage)
 if [ -f frontend_kernels.hip ]; then listing frontend_kernels.hip -o "$OUT/frontend_kernels.s"; fi   # (absent in parents older than the sensor front end)
+if [ -f pose_graph_kernels.hip ]; then listing pose_graph_kernels.hip -o "$OUT/pose_graph_kernels.s"; fi   # (absent in parents older than the pose graph)
 for p in $PIDS; do wait $p; done
 grep -h '^\s*\.amdhsa_kernel ' "$OUT"/*.s | sort > "$OUT/kernels.txt"
 echo "$(wc -l < "$OUT/kernels.txt") kernels, listings in $OUT"

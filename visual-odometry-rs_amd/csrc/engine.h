@@ -1,5 +1,5 @@
 // Internal interface between the HIP kernels and their launch functions (kernels.hip, lm_kernels.hip, product_kernels.hip, lm_reference.hip, dso_kernels.hip)
-// and the host engine / C ABI (host_common.h; batch.cpp, trackers.cpp, pipeline.cpp, operators.cpp).
+// and the host engine / C ABI (host_common.h; batch.cpp, trackers.cpp, trackers_map.cpp, pipeline.cpp, operators.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

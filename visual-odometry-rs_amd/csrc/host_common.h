@@ -1,4 +1,4 @@
-// What the host sources of libvors_hip.so share (batch.cpp, trackers.cpp, pipeline.cpp, operators.cpp): error plumbing, device and buffer
+// What the host sources of libvors_hip.so share (batch.cpp, trackers.cpp, trackers_map.cpp, pipeline.cpp, operators.cpp): error plumbing, device and buffer
 // guards, and the batch handle every other handle is built on. None of them contains a kernel; no CPU compute path exists here: every
 // compute entry point needs a HIP device and fails loudly (VORS_ERR_NO_DEVICE) without one.
 #pragma once

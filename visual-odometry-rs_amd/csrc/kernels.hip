@@ -1115,7 +1115,7 @@ void launch_trackers_advance(int n_seq, int* frame_counter, const float* out_pos
     hipLaunchKernelGGL(trackers_advance_kernel, dim3(1), dim3(256), 0, s, n_seq, frame_counter, out_poses7, stats, cur_poses7, kf_poses7, kf_frame,
                        promo_list, promo_count);
 }
-// Results of sequence 0 of a lock-step handle as ONE packed record (pose7, status, keyframe index, vors_pair_stats; trackers.cpp TrackerOut),
+// Results of sequence 0 of a lock-step handle as ONE packed record (pose7, status, keyframe index, vors_pair_stats; trackers.h TrackerOut),
 // stored by the device straight into the caller's pinned host memory: the single-sequence tracker reads its frame back without a copy call.
 __global__ __launch_bounds__(64) void tracker_pack_out_kernel(const float* __restrict__ pose7, const int32_t* __restrict__ status,
                                                               const int32_t* __restrict__ kf_frame, const vors_pair_stats* __restrict__ stats,
