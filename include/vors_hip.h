@@ -141,7 +141,9 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    vors_map_icp_means_record, likewise; + vors_undistort_frames, vors_undistort_frame_host,
                               *    vors_undistort_source_host, vors_register_depth, vors_register_depth_host, VORS_UNDISTORT_COUNTS,
                               *    VORS_REGISTER_COUNTS, likewise; + vors_pose_graph_optimize, vors_pose_graph_optimize_host,
-                              *    vors_pose_graph_workspace_bytes, vors_pose_graph_jacobians_host, vors_pose_graph_stats, VORS_PG_*, likewise) */
+                              *    vors_pose_graph_workspace_bytes, vors_pose_graph_jacobians_host, vors_pose_graph_stats, VORS_PG_*, likewise;
+                              *    + vors_loop_signatures, vors_loop_candidates, vors_loop_verify_edges, their _host twins, vors_loop_sig_meta,
+                              *    vors_loop_candidate, VORS_LOOP_*, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -1403,6 +1405,117 @@ vors_status vors_pose_graph_optimize_host(const float* poses7_in, uint32_t node_
 /* The residual and the two Jacobians of ONE edge at the poses (ti, tj), the kernels' own text (lie.h pg_edge_jacobians), for tests:
  * r6, ji36 and jj36 row-major (HOST). */
 void vors_pose_graph_jacobians_host(const float ti7[7], const float tj7[7], const float meas7[7], float r6[6], float ji36[36], float jj36[36]);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2h. LOOP CLOSURE, device-resident and handle-free (the reference has none): which earlier keyframes a keyframe should be
+ *     matched against, and which of the tracked loop pairs may become edges of 2g's graph. Three entries, each with a host twin that the
+ *     device equals bit for bit; the shared texts are csrc/lie.h lc_*. Every entry is enqueued on hip_stream on the calling thread's
+ *     current device, NOT synchronised, allocates nothing; no workgroup waits for another; no floating-point atomic exists. Every refusal
+ *     is VORS_ERR_INVALID_ARGUMENT with nothing enqueued and nothing written.
+ *
+ * (1) vors_loop_signatures: a thumbnail signature per grey plane. d_gray [n][rows * cols] u8 (DEVICE); the thumbnail is tr x tc cells,
+ *   D = tr * tc. Cell (cy, cx) covers rows [cy rows / tr, (cy + 1) rows / tr) and columns [cx cols / tc, (cx + 1) cols / tc) (integer
+ *   division); S = the sum of its pixels, cnt their number, q = (2 S + cnt) / (2 cnt) the rounded mean, s = q - 128 the stored int8. All
+ *   of it is exact integer arithmetic: no order of sums to define. Outputs (DEVICE): d_sig [n][D] i8, cell-major cy * tc + cx, 16-byte
+ *   aligned; d_sig_meta [n] {sum of s, sum of s * s}. Both may point INTO larger [capacity][D] / [capacity] arrays (plain pointer
+ *   arithmetic; D is a multiple of 64, so every row keeps the alignment): keyframes are appended as they are promoted, and nothing
+ *   outside the n rows is written. One launch, a workgroup per plane; the plane is read once, as whole 16-byte words at 16-byte
+ *   aligned addresses: where d_gray or a plane's end is off that alignment, up to 15 bytes BEFORE d_gray and up to 15 bytes PAST the
+ *   last plane are loaded and ignored — they lie in the same aligned 16-byte block as a byte of the planes, so in the same page.
+ *   Refused: n < 1; a NULL pointer; D not a multiple of 64 or outside 64..1024; tr or tc < 1; rows < tr, cols < tc; rows or cols > 65535
+ *   or rows * cols > 2^28; d_sig off 16 bytes, d_sig_meta off 4.
+ * (2) vors_loop_candidates: all pairs of signatures of a set scored, gated, the best k per query. n sets side by side: d_sig
+ *   [n][capacity][D], d_sig_meta [n][capacity], d_counts_in [n] u32 (a count above capacity is clipped); d_poses7 (nullable) the
+ *   keyframes' camera -> world poses [n][capacity], pose_stride_bytes apart (0 = packed, 28); d_query_first [n] u32 (nullable = 0): only
+ *   queries j in [first, count) are answered — the keyframes promoted since the last call.
+ *   DEFINITION. The candidates of query j are every i with i + min_gap <= j. dot = sum_c s_i[c] s_j[c] (exact, i32); num = D dot -
+ *   sum_i sum_j (i64); va = D sumsq - sum^2 (i64) per signature; root = sqrt((double)va); score = (float)((double)num / (root_i *
+ *   root_j)): f64 multiply and divide, no contraction, rounded once to f32. Three gates in this order, a pair counted under the first that
+ *   removes it: FLAT va_i == 0 or va_j == 0; POSE (only with d_poses7; f32): dot3(d, d) <= max_dist_m^2 must hold for d = t_i - t_j,
+ *   and |dot3(q_i.ijk, q_j.ijk) + q_i.w q_j.w| >= min_qdot must hold and be finite — max_dist_m = 0 and min_qdot = 0 switch their half
+ *   off, a NaN fails a half that is on; SCORE not score >= min_score (a NaN fails). Survivors are ordered by (score descending, i
+ *   ascending), a total order: the result depends on no tile, grid or schedule.
+ *   d_sig_meta MUST BE the record of its signature, as vors_loop_signatures writes it. Then |num| <= root_i root_j and |score| <= 1, and
+ *   the kernel relies on it: before the f64 divide it drops a pair whose f32 estimate of the score (error below 1e-6 for |score| <= 1)
+ *   lies more than 1e-4 under min_score, which the exact score would drop as well. With meta records that belong to other signatures
+ *   the device may count a pair as score-gated that the host twin keeps.
+ *   Outputs (DEVICE): d_cand [n][capacity][k] vors_loop_candidate, the first min(k, survivors) of that order, unused slots {0xFFFFFFFF,
+ *   0.0f}; d_cand_counts [n][capacity] u32 = min(k, survivors); exactly the queries in [first, count) are written. d_counts
+ *   [n][VORS_LOOP_COUNTS] u32 (nullable) = {examined, flat, pose-gated, score-gated, survivors} over the answered queries (modulo 2^32),
+ *   integer atomics after a memset that the entry enqueues. One launch (two with d_counts): the dot products are
+ *   v_mfma_i32_32x32x32_i8 tiles of the signature matrix against itself, tiles wholly above the band are skipped.
+ *   Refused: n < 1; a NULL d_sig, d_sig_meta, d_counts_in, d_cand or d_cand_counts; capacity < 1 or > 2^20; D not a multiple of 64 or
+ *   outside 64..1024; min_gap < 1; k outside 1..VORS_LOOP_MAX_K; max_dist_m or min_qdot negative or NaN; a bad pose stride; d_sig off 16
+ *   bytes, another pointer off 4.
+ * (3) vors_loop_verify_edges: from tracked candidate pairs to pose-graph edges. The caller has tracked every candidate both ways with
+ *   the existing entries: keyframe i against frame j gives M_ij, j against i gives M_ji, vors_batch_pose_information gives info36 of the
+ *   forward pair. DEVICE: d_pairs [m] {u32 i, j}; d_model_fwd / d_model_bwd [m] models, fwd / bwd_stride_bytes apart (0 = packed, 28;
+ *   vors_pair_stats.lm_model goes in with sizeof(vors_pair_stats)); d_model_bwd nullable; d_status_fwd / d_status_bwd [m] int32
+ *   (d_status_bwd nullable); d_info36 [m][36] nullable; d_poses7 (nullable) the current estimates of node_count nodes, pose_stride_bytes
+ *   apart.
+ *   VERDICT per candidate, the first rule that applies: VORS_LOOP_STATUS a given status is not VORS_TRACK_OK; VORS_LOOP_INDEX i == j, or —
+ *   with poses — an index >= node_count; VORS_LOOP_NONFINITE an entry of a given model or of the information is not finite;
+ *   VORS_LOOP_CYCLE_TRANS / _ROT (with a backward model) C = M_ji M_ij, r = 2g's residual of C, dot3(r.t) > max_cycle_trans^2 /
+ *   dot3(r.rot) > max_cycle_rot^2; VORS_LOOP_PRIOR_TRANS / _ROT (with poses) the same on 2g's edge error E = T_i^-1 T_j M_ij;
+ *   VORS_LOOP_CAPACITY accepted, but the edge list is full; VORS_LOOP_ACCEPTED. A bound of 0 switches its test off; a NaN residual fails
+ *   a test that is on.
+ *   Outputs (DEVICE), in 2g's formats: the accepted candidates IN CANDIDATE ORDER appended to d_edges, d_meas7 (= M_ij), d_info36_out
+ *   (nullable; identity rows when d_info36 is NULL) and d_edge_weight (nullable; = weight), starting at the in / out d_edge_count[0]
+ *   (where the caller's odometry edges end; a count above edge_capacity is clipped to it) — an ordered compaction, the list is a function
+ *   of the inputs alone; d_verdict [m] u32; d_residuals [m][12] (nullable) the cycle's r6, then the prior's r6, both computed for every
+ *   candidate that passes STATUS, INDEX and NONFINITE, NaN otherwise and where their input is not given; d_counts [VORS_LOOP_VERDICTS]
+ *   u32 (nullable), one per verdict code. One launch of one workgroup.
+ *   Refused: m < 1 or > 2^28; a NULL d_pairs, d_model_fwd, d_status_fwd, d_edges, d_meas7, d_edge_count or d_verdict; edge_capacity < 1 or
+ *   > 2^28; a bad stride; a bound negative or NaN; weight not finite or not > 0; a pointer off 4 bytes. */
+#define VORS_LOOP_MAX_K 8
+#define VORS_LOOP_COUNTS 5
+#define VORS_LOOP_ACCEPTED 0
+#define VORS_LOOP_STATUS 1
+#define VORS_LOOP_INDEX 2
+#define VORS_LOOP_NONFINITE 3
+#define VORS_LOOP_CYCLE_TRANS 4
+#define VORS_LOOP_CYCLE_ROT 5
+#define VORS_LOOP_PRIOR_TRANS 6
+#define VORS_LOOP_PRIOR_ROT 7
+#define VORS_LOOP_CAPACITY 8
+#define VORS_LOOP_VERDICTS 9
+typedef struct vors_loop_sig_meta {
+    int32_t sum;
+    uint32_t sumsq;
+} vors_loop_sig_meta;
+typedef struct vors_loop_candidate {
+    uint32_t i;
+    float score;
+} vors_loop_candidate;
+vors_status vors_loop_signatures(int n, const uint8_t* d_gray, int rows, int cols, int tr, int tc, int8_t* d_sig, vors_loop_sig_meta* d_sig_meta,
+                                 void* hip_stream);
+/* ONE plane on the host (HOST pointers; needs no GPU). The refusals above. */
+vors_status vors_loop_signatures_host(const uint8_t* gray, int rows, int cols, int tr, int tc, int8_t* sig, vors_loop_sig_meta* sig_meta);
+vors_status vors_loop_candidates(int n, const int8_t* d_sig, const vors_loop_sig_meta* d_sig_meta, const uint32_t* d_counts_in, int capacity, int D,
+                                 const void* d_poses7 /* nullable */, size_t pose_stride_bytes, const uint32_t* d_query_first /* nullable */,
+                                 uint32_t min_gap, int k, float min_score, float max_dist_m, float min_qdot, vors_loop_candidate* d_cand,
+                                 uint32_t* d_cand_counts, uint32_t* d_counts /* nullable */, void* hip_stream);
+/* ONE set on the host: HOST pointers, poses packed [capacity][7]. The refusals above. */
+vors_status vors_loop_candidates_host(const int8_t* sig, const vors_loop_sig_meta* sig_meta, uint32_t count, int capacity, int D,
+                                      const float* poses7 /* nullable */, uint32_t query_first, uint32_t min_gap, int k, float min_score,
+                                      float max_dist_m, float min_qdot, vors_loop_candidate* cand, uint32_t* cand_counts,
+                                      uint32_t counts[VORS_LOOP_COUNTS] /* nullable */);
+vors_status vors_loop_verify_edges(uint32_t m, const uint32_t* d_pairs, const void* d_model_fwd, size_t fwd_stride_bytes,
+                                   const void* d_model_bwd /* nullable */, size_t bwd_stride_bytes, const int32_t* d_status_fwd,
+                                   const int32_t* d_status_bwd /* nullable */, const float* d_info36 /* nullable */,
+                                   const void* d_poses7 /* nullable */, size_t pose_stride_bytes, uint32_t node_count, float max_cycle_trans,
+                                   float max_cycle_rot, float max_prior_trans, float max_prior_rot, float weight, uint32_t* d_edges,
+                                   float* d_meas7, float* d_info36_out /* nullable */, float* d_edge_weight /* nullable */,
+                                   uint32_t* d_edge_count, int edge_capacity, uint32_t* d_verdict, float* d_residuals /* nullable */,
+                                   uint32_t* d_counts /* nullable */, void* hip_stream);
+/* The same on the host: HOST pointers, the same strides. The refusals above. */
+vors_status vors_loop_verify_edges_host(uint32_t m, const uint32_t* pairs, const void* model_fwd, size_t fwd_stride_bytes,
+                                        const void* model_bwd /* nullable */, size_t bwd_stride_bytes, const int32_t* status_fwd,
+                                        const int32_t* status_bwd /* nullable */, const float* info36 /* nullable */,
+                                        const void* poses7 /* nullable */, size_t pose_stride_bytes, uint32_t node_count, float max_cycle_trans,
+                                        float max_cycle_rot, float max_prior_trans, float max_prior_rot, float weight, uint32_t* edges,
+                                        float* meas7, float* info36_out /* nullable */, float* edge_weight /* nullable */, uint32_t* edge_count,
+                                        int edge_capacity, uint32_t* verdict, float* residuals /* nullable */, uint32_t* counts /* nullable */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

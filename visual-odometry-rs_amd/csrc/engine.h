@@ -733,6 +733,65 @@ inline size_t pg_workspace_carve(PgCall* call, void* workspace, int n, int node_
 // launch unconditionally, not synchronised, no allocation.
 void launch_pose_graph(const PgCall& call, hipStream_t s);
 
+// Loop closure (vors_loop_signatures, vors_loop_candidates, vors_loop_verify_edges; loop_closure_kernels.hip): the rules are
+// lie.h lc_*. Handle-free: everything the kernels read is here. The host twins fill the same records with host pointers.
+struct LcMeta {  // vors_loop_sig_meta
+    int32_t sum;
+    uint32_t sumsq;
+};
+struct LcCand {  // vors_loop_candidate
+    uint32_t i;
+    float score;
+};
+struct LcSigCall {
+    int n, rows, cols, tr, tc;
+    const uint8_t* gray;  // [n][rows * cols]
+    int8_t* sig;          // [n][tr * tc], 16-byte aligned
+    LcMeta* meta;         // [n]
+};
+struct LcCandCall {
+    int n, capacity, d;
+    const int8_t* sig;          // [n][capacity][d], 16-byte aligned
+    const LcMeta* meta;         // [n][capacity]
+    const uint32_t* counts_in;  // [n]; a count above the capacity is clipped to it
+    const float* poses;         // [n][capacity] poses, pose_stride floats apart; nullable = no pose gate
+    int pose_stride;
+    const uint32_t* query_first;  // [n], nullable = 0
+    uint32_t min_gap, k;
+    float min_score, max_dist_m, min_qdot;
+    LcCand* cand;           // [n][capacity][k]
+    uint32_t* cand_counts;  // [n][capacity]
+    uint32_t* counts;       // [n][VORS_LC_COUNTS], nullable; zeroed by the launch
+};
+struct LcVerifyCall {
+    uint32_t m;
+    const uint32_t* pairs;  // [m] {i, j}
+    const float *fwd, *bwd; // [m] models, fwd_stride / bwd_stride floats apart; bwd nullable
+    int fwd_stride, bwd_stride;
+    const int32_t *status_fwd, *status_bwd;  // [m]; status_bwd nullable
+    const float* info;      // [m][36], nullable = identity rows written
+    const float* poses;     // [node_count] poses, pose_stride floats apart; nullable
+    int pose_stride;
+    uint32_t node_count;
+    float max_cycle_trans, max_cycle_rot, max_prior_trans, max_prior_rot, weight;
+    uint32_t* edges;        // [edge_capacity] {i, j}
+    float* meas;            // [edge_capacity][7]
+    float* info_out;        // [edge_capacity][36], nullable
+    float* edge_weight;     // [edge_capacity], nullable
+    uint32_t* edge_count;   // [1] in / out
+    uint32_t edge_capacity;
+    uint32_t* verdict;      // [m]
+    float* residuals;       // [m][12], nullable
+    uint32_t* counts;       // [VORS_LC_VERDICTS], nullable
+};
+// Each is enqueued on s, not synchronised, no allocation: one launch for the signatures (a workgroup per plane); a memset of the counts
+// (when asked for) and one launch for the candidates (a workgroup per tile of 32 queries and set); one launch of ONE workgroup for the
+// verification, whose ordered compaction is a scan over chunks of 1024 candidates in sequence. launch_loop_candidates -> the memset's
+// error, with nothing launched behind a memset that failed.
+void launch_loop_signatures(const LcSigCall& call, hipStream_t s);
+hipError_t launch_loop_candidates(const LcCandCall& call, hipStream_t s);
+void launch_loop_verify(const LcVerifyCall& call, hipStream_t s);
+
 // The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp; map_icp_kernels.hip): what surrounds
 // launch_icp_points there. Handle-free: everything the kernels read is here.
 struct MapIcpCall {

@@ -1207,12 +1207,16 @@ VORS_HD void pg_load_info(const float* info36 /* nullable */, float om[36]) {
 VORS_UNROLL
     for (int k = 0; k < 36; ++k) om[k] = info36 ? info36[k] : (k % 7 == 0 ? 1.0f : 0.0f);
 }
+// the residual of an error E: r = (E.t, 2 s E.q.ijk) -> s (also what vors_loop_verify_edges measures a cycle and a prior with)
+VORS_HD float pg_error_residual(const Iso& e, float r[6]) {
+    const float s = e.q.w >= 0.0f ? 1.0f : -1.0f;
+    r[0] = e.t.x; r[1] = e.t.y; r[2] = e.t.z;
+    r[3] = (2.0f * s) * e.q.i; r[4] = (2.0f * s) * e.q.j; r[5] = (2.0f * s) * e.q.k;
+    return s;
+}
 VORS_HD float pg_edge_error(const Iso& ti, const Iso& tj, const Iso& m, Iso* e, float r[6]) {
     *e = iso_mul(iso_mul(iso_inverse(ti), tj), m);
-    const float s = e->q.w >= 0.0f ? 1.0f : -1.0f;
-    r[0] = e->t.x; r[1] = e->t.y; r[2] = e->t.z;
-    r[3] = (2.0f * s) * e->q.i; r[4] = (2.0f * s) * e->q.j; r[5] = (2.0f * s) * e->q.k;
-    return s;
+    return pg_error_residual(*e, r);
 }
 // w * (r . (Omega r)): rows of Omega r left to right, then the six products r[a] (Omega r)[a] in ascending a
 VORS_HD float pg_edge_energy(const float r[6], const float om[36], float w) {
@@ -1439,6 +1443,105 @@ inline T pg_chunk_tree(T* v) {
     for (int w = VORS_PG_CHUNK / 2; w >= 1; w /= 2)
         for (int s = 0; s < w; ++s) v[s] = v[s] + v[s + w];
     return v[0];
+}
+
+// Loop closure (vors_loop_signatures, vors_loop_candidates, vors_loop_verify_edges; include/vors_hip.h 2h; the reference has
+// none): the texts the kernels (loop_closure_kernels.hip) and the host twins (operators.cpp) both run, bit for bit. Signatures and dot
+// products are exact integers; the score is ONE f64 divide of an exact numerator by the product of two correctly rounded f64 roots.
+#define VORS_LC_MAX_K 8
+#define VORS_LC_COUNTS 5    // examined, flat, pose-gated, score-gated, survivors
+#define VORS_LC_VERDICTS 9  // LcVerdict
+#define VORS_LC_EMPTY 0xFFFFFFFFu
+enum LcVerdict { LC_ACCEPTED = 0, LC_STATUS = 1, LC_INDEX = 2, LC_NONFINITE = 3, LC_CYCLE_TRANS = 4, LC_CYCLE_ROT = 5, LC_PRIOR_TRANS = 6,
+                 LC_PRIOR_ROT = 7, LC_CAPACITY = 8 };
+// the thumbnail cell that pixel coordinate x of `extent` falls into: cell c covers [c extent / cells, (c + 1) extent / cells)
+// (extent <= 65535 and cells <= 1024, which the entries see to: the products fit 32 bits)
+VORS_HD uint32_t lc_cell_of(uint32_t x, uint32_t extent, uint32_t cells) { return ((x + 1u) * cells - 1u) / extent; }
+VORS_HD uint32_t lc_cell_begin(uint32_t c, uint32_t extent, uint32_t cells) { return (c * extent) / cells; }
+// the stored value of a cell: the rounded mean of its pixels minus 128
+VORS_HD int8_t lc_cell_value(uint64_t sum, uint64_t cnt) { return (int8_t)((int)((2u * sum + cnt) / (2u * cnt)) - 128); }
+// D sumsq - sum^2 of a signature (>= 0; 0 = flat), and its root
+VORS_HD int64_t lc_variance(int d, int32_t sum, uint32_t sumsq) { return (int64_t)d * (int64_t)sumsq - (int64_t)sum * (int64_t)sum; }
+VORS_HD double lc_root(int64_t va) { return sqrt((double)va); }
+VORS_HD int64_t lc_numerator(int d, int32_t dot, int32_t sum_i, int32_t sum_j) { return (int64_t)d * (int64_t)dot - (int64_t)sum_i * (int64_t)sum_j; }
+VORS_HD float lc_score(int64_t num, double root_i, double root_j) { return (float)((double)num / (root_i * root_j)); }
+VORS_HD bool lc_score_passes(float score, float min_score) { return score >= min_score; }  // a NaN fails
+// The pose gate of a pair of camera -> world poses, f32 in this order; a half whose parameter is 0 is off; in a half that is on, a
+// value that is not finite fails.
+VORS_HD bool lc_pose_passes(const float* pi7, const float* pj7, float max_dist_m, float min_qdot) {
+    bool ok = true;
+    if (max_dist_m > 0.0f) {
+        const V3 d{pi7[0] - pj7[0], pi7[1] - pj7[1], pi7[2] - pj7[2]};
+        ok = dot3(d, d) <= max_dist_m * max_dist_m;
+    }
+    if (min_qdot > 0.0f) {
+        const float qd = fabsf(dot3(V3{pi7[3], pi7[4], pi7[5]}, V3{pj7[3], pj7[4], pj7[5]}) + pi7[6] * pj7[6]);
+        ok = ok && pg_finite(qd) && qd >= min_qdot;
+    }
+    return ok;
+}
+// THE ORDER of candidates: score descending, then index ascending — total, since an index occurs once
+VORS_HD bool lc_before(float score_a, uint32_t a, float score_b, uint32_t b) { return score_a > score_b || (score_a == score_b && a < b); }
+// Insertion into a list of at most k <= VORS_LC_MAX_K entries kept in that order; slots [*n, k) are unused. The loop has a fixed trip
+// count and constant indices, so a kernel keeps the list in registers.
+VORS_HD void lc_topk_insert(uint32_t idx[VORS_LC_MAX_K], float score[VORS_LC_MAX_K], uint32_t* n, uint32_t k, uint32_t i, float s) {
+    bool have = true;
+VORS_UNROLL
+    for (uint32_t p = 0; p < VORS_LC_MAX_K; ++p) {
+        if (p < k && have) {
+            if (p >= *n) {
+                idx[p] = i;
+                score[p] = s;
+                have = false;
+            } else if (lc_before(s, i, score[p], idx[p])) {
+                const uint32_t ti = idx[p];
+                const float ts = score[p];
+                idx[p] = i;
+                score[p] = s;
+                i = ti;
+                s = ts;
+            }
+        }
+    }
+    if (*n < k) *n += 1u;
+}
+// The verdict of one tracked loop candidate before the edge list's capacity is looked at, and its residuals r12 = the cycle's r6, then
+// the prior's r6 (NaN where not computed). The first rule that applies wins; both residuals are computed for every candidate that
+// passes STATUS, INDEX and NONFINITE. A bound of 0 switches its test off; the comparisons are written so that a NaN residual FAILS.
+// fwd / bwd: M_ij and M_ji (bwd nullable); poses: camera -> world, pose_stride floats apart (nullable).
+VORS_HD uint32_t lc_verify(uint32_t i, uint32_t j, bool status_ok, const float* fwd7, const float* bwd7, const float* info36, const float* poses,
+                           int pose_stride, uint32_t node_count, float max_cycle_trans, float max_cycle_rot, float max_prior_trans,
+                           float max_prior_rot, float r12[12]) {
+    const float nan = nanf("");
+VORS_UNROLL
+    for (int k = 0; k < 12; ++k) r12[k] = nan;
+    if (!status_ok) return LC_STATUS;
+    if (i == j || (poses && (i >= node_count || j >= node_count))) return LC_INDEX;
+    bool finite = true;
+    for (int k = 0; k < 7; ++k) finite = finite && pg_finite(fwd7[k]) && (!bwd7 || pg_finite(bwd7[k]));
+    if (info36)
+        for (int k = 0; k < 36; ++k) finite = finite && pg_finite(info36[k]);
+    if (!finite) return LC_NONFINITE;
+    const Iso m = iso_load(fwd7);
+    uint32_t verdict = LC_ACCEPTED;
+    if (bwd7) {
+        pg_error_residual(iso_mul(iso_load(bwd7), m), r12);
+        const float t2 = dot3(V3{r12[0], r12[1], r12[2]}, V3{r12[0], r12[1], r12[2]});
+        const float w2 = dot3(V3{r12[3], r12[4], r12[5]}, V3{r12[3], r12[4], r12[5]});
+        if (max_cycle_trans > 0.0f && !(t2 <= max_cycle_trans * max_cycle_trans)) verdict = LC_CYCLE_TRANS;
+        else if (max_cycle_rot > 0.0f && !(w2 <= max_cycle_rot * max_cycle_rot)) verdict = LC_CYCLE_ROT;
+    }
+    if (poses) {
+        Iso e;
+        pg_edge_error(iso_load(poses + (size_t)i * pose_stride), iso_load(poses + (size_t)j * pose_stride), m, &e, r12 + 6);
+        const float t2 = dot3(V3{r12[6], r12[7], r12[8]}, V3{r12[6], r12[7], r12[8]});
+        const float w2 = dot3(V3{r12[9], r12[10], r12[11]}, V3{r12[9], r12[10], r12[11]});
+        if (verdict == LC_ACCEPTED) {
+            if (max_prior_trans > 0.0f && !(t2 <= max_prior_trans * max_prior_trans)) verdict = LC_PRIOR_TRANS;
+            else if (max_prior_rot > 0.0f && !(w2 <= max_prior_rot * max_prior_rot)) verdict = LC_PRIOR_ROT;
+        }
+    }
+    return verdict;
 }
 
 }  // namespace vors

@@ -1263,6 +1263,259 @@ void vors_pose_graph_jacobians_host(const float ti7[7], const float tj7[7], cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Loop closure (vors_loop_signatures, vors_loop_candidates, vors_loop_verify_edges and their host twins; include/vors_hip.h 2h): per
+// entry the refusals both forms share, the device entry (loop_closure_kernels.hip) and the host entry, which runs the kernels' own texts
+// (lie.h lc_*) as plain loops.
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(LcMeta) == sizeof(vors_loop_sig_meta) && sizeof(LcCand) == sizeof(vors_loop_candidate), "records of the C ABI");
+static_assert(VORS_LC_MAX_K == VORS_LOOP_MAX_K && VORS_LC_COUNTS == VORS_LOOP_COUNTS && VORS_LC_VERDICTS == VORS_LOOP_VERDICTS &&
+                  LC_CAPACITY == VORS_LOOP_CAPACITY && LC_PRIOR_ROT == VORS_LOOP_PRIOR_ROT && LC_NONFINITE == VORS_LOOP_NONFINITE,
+              "lie.h and the header state the same codes");
+
+static vors_status lc_thumbnail_refusal(const std::string& w, int d) {
+    if (d < 64 || d > 1024 || d % 64 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": D must be a multiple of 64 in 64..1024");
+    return VORS_OK;
+}
+
+static vors_status lc_sig_refusals(const char* who, const LcSigCall& c) {
+    const std::string w(who);
+    if (!c.gray || !c.sig || !c.meta) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the planes, the signatures or their meta records are NULL");
+    if (c.tr < 1 || c.tc < 1 || c.tr > 1024 || c.tc > 1024) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": tr and tc must be in 1..1024");
+    const vors_status st = lc_thumbnail_refusal(w, c.tr * c.tc);
+    if (st != VORS_OK) return st;
+    if (c.rows < c.tr || c.cols < c.tc) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows >= tr and cols >= tc are required");
+    if (c.rows > 65535 || c.cols > 65535 || (int64_t)c.rows * c.cols > (1 << 28))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": rows and cols must not exceed 65535, rows * cols not 2^28");
+    if ((uintptr_t)c.sig % 16 != 0 || (uintptr_t)c.meta % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the signatures must be 16-byte aligned, their meta records 4-byte aligned");
+    return VORS_OK;
+}
+
+vors_status vors_loop_signatures(int n, const uint8_t* d_gray, int rows, int cols, int tr, int tc, int8_t* d_sig, vors_loop_sig_meta* d_sig_meta,
+                                 void* hip_stream) {
+    const char* who = "loop_signatures";
+    const LcSigCall call{n, rows, cols, tr, tc, d_gray, d_sig, reinterpret_cast<LcMeta*>(d_sig_meta)};
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": n must be >= 1");
+    vors_status st = lc_sig_refusals(who, call);
+    if (st != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    launch_loop_signatures(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_loop_signatures_host(const uint8_t* gray, int rows, int cols, int tr, int tc, int8_t* sig, vors_loop_sig_meta* sig_meta) {
+    const LcSigCall c{1, rows, cols, tr, tc, gray, sig, reinterpret_cast<LcMeta*>(sig_meta)};
+    const vors_status st = lc_sig_refusals("loop_signatures_host", c);
+    if (st != VORS_OK) return st;
+    const uint32_t R = (uint32_t)rows, C = (uint32_t)cols, TR = (uint32_t)tr, TC = (uint32_t)tc;
+    LcMeta meta{0, 0u};
+    for (uint32_t cy = 0; cy < TR; ++cy)
+        for (uint32_t cx = 0; cx < TC; ++cx) {
+            const uint32_t y0 = lc_cell_begin(cy, R, TR), y1 = lc_cell_begin(cy + 1u, R, TR), x0 = lc_cell_begin(cx, C, TC), x1 = lc_cell_begin(cx + 1u, C, TC);
+            uint64_t sum = 0;
+            for (uint32_t y = y0; y < y1; ++y)
+                for (uint32_t x = x0; x < x1; ++x) sum += gray[(size_t)y * C + x];
+            const int8_t s = lc_cell_value(sum, (uint64_t)(y1 - y0) * (x1 - x0));
+            sig[cy * TC + cx] = s;
+            meta.sum += (int32_t)s;
+            meta.sumsq += (uint32_t)((int32_t)s * (int32_t)s);
+        }
+    *c.meta = meta;
+    return VORS_OK;
+}
+
+static vors_status lc_cand_refusals(const char* who, const LcCandCall& c, int k) {
+    const std::string w(who);
+    if (!c.sig || !c.meta || !c.counts_in) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the signatures, their meta records or the counts are NULL");
+    if (!c.cand || !c.cand_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the candidate lists or their counts are NULL");
+    if (c.capacity < 1 || c.capacity > (1 << 20)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be in 1..2^20");
+    const vors_status st = lc_thumbnail_refusal(w, c.d);
+    if (st != VORS_OK) return st;
+    if (c.min_gap < 1u) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": min_gap must be >= 1");
+    if (k < 1 || k > VORS_LOOP_MAX_K) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": k must be in 1..VORS_LOOP_MAX_K (8)");
+    if (!(c.max_dist_m >= 0.0f) || !(c.min_qdot >= 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": max_dist_m and min_qdot must be >= 0 (and not NaN)");
+    if ((uintptr_t)c.sig % 16 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the signatures must be 16-byte aligned");
+    if ((uintptr_t)c.meta % 4 != 0 || (uintptr_t)c.counts_in % 4 != 0 || (uintptr_t)c.poses % 4 != 0 || (uintptr_t)c.query_first % 4 != 0 ||
+        (uintptr_t)c.cand % 4 != 0 || (uintptr_t)c.cand_counts % 4 != 0 || (uintptr_t)c.counts % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the meta records, counts, poses, lists and their counts must be 4-byte aligned");
+    return VORS_OK;
+}
+
+vors_status vors_loop_candidates(int n, const int8_t* d_sig, const vors_loop_sig_meta* d_sig_meta, const uint32_t* d_counts_in, int capacity, int D,
+                                 const void* d_poses7, size_t pose_stride_bytes, const uint32_t* d_query_first, uint32_t min_gap, int k,
+                                 float min_score, float max_dist_m, float min_qdot, vors_loop_candidate* d_cand, uint32_t* d_cand_counts,
+                                 uint32_t* d_counts, void* hip_stream) {
+    const char* who = "loop_candidates";
+    LcCandCall call{n, capacity, D, d_sig, reinterpret_cast<const LcMeta*>(d_sig_meta), d_counts_in, static_cast<const float*>(d_poses7), 7,
+                    d_query_first, min_gap, (uint32_t)k, min_score, max_dist_m, min_qdot, reinterpret_cast<LcCand*>(d_cand), d_cand_counts, d_counts};
+    if (n < 1) return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": n must be >= 1");
+    vors_status st = lc_cand_refusals(who, call, k);
+    if (st != VORS_OK) return st;
+    if ((st = stride_refusal(who, "pose_stride_bytes", pose_stride_bytes, 28, OPERATOR_STRIDE_LIMIT)) != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
+    HIP_TRY(launch_loop_candidates(call, static_cast<hipStream_t>(hip_stream)));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_loop_candidates_host(const int8_t* sig, const vors_loop_sig_meta* sig_meta, uint32_t count, int capacity, int D, const float* poses7,
+                                      uint32_t query_first, uint32_t min_gap, int k, float min_score, float max_dist_m, float min_qdot,
+                                      vors_loop_candidate* cand, uint32_t* cand_counts, uint32_t counts[VORS_LOOP_COUNTS]) {
+    const LcCandCall c{1, capacity, D, sig, reinterpret_cast<const LcMeta*>(sig_meta), &count, poses7, 7, &query_first, min_gap, (uint32_t)k,
+                       min_score, max_dist_m, min_qdot, reinterpret_cast<LcCand*>(cand), cand_counts, counts};
+    const vors_status st = lc_cand_refusals("loop_candidates_host", c, k);
+    if (st != VORS_OK) return st;
+    const uint32_t n = std::min<uint32_t>(count, (uint32_t)capacity);
+    uint32_t tally[VORS_LC_COUNTS] = {0u, 0u, 0u, 0u, 0u};
+    std::vector<int64_t> va(n);
+    std::vector<double> root(n);
+    for (uint32_t r = 0; r < n; ++r) {
+        va[r] = lc_variance(D, c.meta[r].sum, c.meta[r].sumsq);
+        root[r] = lc_root(va[r]);
+    }
+    for (uint32_t j = query_first; j < n; ++j) {
+        uint32_t idx[VORS_LC_MAX_K], have = 0u;
+        float score[VORS_LC_MAX_K];
+        for (int p = 0; p < VORS_LC_MAX_K; ++p) {
+            idx[p] = VORS_LC_EMPTY;
+            score[p] = 0.0f;
+        }
+        for (uint32_t i = 0; (uint64_t)i + min_gap <= (uint64_t)j; ++i) {
+            tally[0] += 1u;
+            if (va[i] == 0 || va[j] == 0) {
+                tally[1] += 1u;
+                continue;
+            }
+            if (poses7 && !lc_pose_passes(poses7 + (size_t)i * 7, poses7 + (size_t)j * 7, max_dist_m, min_qdot)) {
+                tally[2] += 1u;
+                continue;
+            }
+            int32_t dot = 0;
+            for (int e = 0; e < D; ++e) dot += (int32_t)sig[(size_t)i * D + e] * (int32_t)sig[(size_t)j * D + e];
+            const float s = lc_score(lc_numerator(D, dot, c.meta[i].sum, c.meta[j].sum), root[i], root[j]);
+            if (!lc_score_passes(s, min_score)) {
+                tally[3] += 1u;
+                continue;
+            }
+            tally[4] += 1u;
+            lc_topk_insert(idx, score, &have, (uint32_t)k, i, s);
+        }
+        for (int p = 0; p < k; ++p) c.cand[(size_t)j * k + p] = LcCand{idx[p], score[p]};
+        cand_counts[j] = have;
+    }
+    if (counts)
+        for (int p = 0; p < VORS_LC_COUNTS; ++p) counts[p] = tally[p];
+    return VORS_OK;
+}
+
+static vors_status lc_verify_refusals(const char* who, const LcVerifyCall& c, int edge_capacity, size_t fwd_bytes, size_t bwd_bytes, size_t pose_bytes) {
+    const std::string w(who);
+    if (c.m < 1u || c.m > (1u << 28)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": m must be in 1..2^28");
+    if (!c.pairs || !c.fwd || !c.status_fwd) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the pairs, the forward models or their statuses are NULL");
+    if (!c.edges || !c.meas || !c.edge_count || !c.verdict)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the edges, their measurements, the edge count or the verdicts are NULL");
+    if (edge_capacity < 1 || edge_capacity > (1 << 28)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": edge_capacity must be in 1..2^28");
+    vors_status st;
+    if ((st = stride_refusal(who, "fwd_stride_bytes", fwd_bytes, 28, OPERATOR_STRIDE_LIMIT)) != VORS_OK) return st;
+    if ((st = stride_refusal(who, "bwd_stride_bytes", bwd_bytes, 28, OPERATOR_STRIDE_LIMIT)) != VORS_OK) return st;
+    if ((st = stride_refusal(who, "pose_stride_bytes", pose_bytes, 28, OPERATOR_STRIDE_LIMIT)) != VORS_OK) return st;
+    if (!(c.max_cycle_trans >= 0.0f) || !(c.max_cycle_rot >= 0.0f) || !(c.max_prior_trans >= 0.0f) || !(c.max_prior_rot >= 0.0f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the four bounds must be >= 0 (and not NaN)");
+    if (!(pg_finite(c.weight) && c.weight > 0.0f)) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": weight must be finite and > 0");
+    if ((uintptr_t)c.pairs % 4 != 0 || (uintptr_t)c.fwd % 4 != 0 || (uintptr_t)c.bwd % 4 != 0 || (uintptr_t)c.status_fwd % 4 != 0 ||
+        (uintptr_t)c.status_bwd % 4 != 0 || (uintptr_t)c.info % 4 != 0 || (uintptr_t)c.poses % 4 != 0 || (uintptr_t)c.edges % 4 != 0 ||
+        (uintptr_t)c.meas % 4 != 0 || (uintptr_t)c.info_out % 4 != 0 || (uintptr_t)c.edge_weight % 4 != 0 || (uintptr_t)c.edge_count % 4 != 0 ||
+        (uintptr_t)c.verdict % 4 != 0 || (uintptr_t)c.residuals % 4 != 0 || (uintptr_t)c.counts % 4 != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": every pointer must be 4-byte aligned");
+    return VORS_OK;
+}
+
+static LcVerifyCall lc_verify_call(uint32_t m, const uint32_t* pairs, const void* model_fwd, size_t fwd_stride_bytes, const void* model_bwd,
+                                   size_t bwd_stride_bytes, const int32_t* status_fwd, const int32_t* status_bwd, const float* info36,
+                                   const void* poses7, size_t pose_stride_bytes, uint32_t node_count, float max_cycle_trans, float max_cycle_rot,
+                                   float max_prior_trans, float max_prior_rot, float weight, uint32_t* edges, float* meas7, float* info36_out,
+                                   float* edge_weight, uint32_t* edge_count, int edge_capacity, uint32_t* verdict, float* residuals, uint32_t* counts) {
+    LcVerifyCall c{};
+    c.m = m; c.pairs = pairs;
+    c.fwd = static_cast<const float*>(model_fwd); c.bwd = static_cast<const float*>(model_bwd);
+    c.fwd_stride = stride_words(fwd_stride_bytes, 7); c.bwd_stride = stride_words(bwd_stride_bytes, 7);
+    c.status_fwd = status_fwd; c.status_bwd = status_bwd; c.info = info36;
+    c.poses = static_cast<const float*>(poses7); c.pose_stride = stride_words(pose_stride_bytes, 7); c.node_count = node_count;
+    c.max_cycle_trans = max_cycle_trans; c.max_cycle_rot = max_cycle_rot; c.max_prior_trans = max_prior_trans; c.max_prior_rot = max_prior_rot;
+    c.weight = weight;
+    c.edges = edges; c.meas = meas7; c.info_out = info36_out; c.edge_weight = edge_weight; c.edge_count = edge_count;
+    c.edge_capacity = edge_capacity > 0 ? (uint32_t)edge_capacity : 0u;
+    c.verdict = verdict; c.residuals = residuals; c.counts = counts;
+    return c;
+}
+
+vors_status vors_loop_verify_edges(uint32_t m, const uint32_t* d_pairs, const void* d_model_fwd, size_t fwd_stride_bytes, const void* d_model_bwd,
+                                   size_t bwd_stride_bytes, const int32_t* d_status_fwd, const int32_t* d_status_bwd, const float* d_info36,
+                                   const void* d_poses7, size_t pose_stride_bytes, uint32_t node_count, float max_cycle_trans, float max_cycle_rot,
+                                   float max_prior_trans, float max_prior_rot, float weight, uint32_t* d_edges, float* d_meas7, float* d_info36_out,
+                                   float* d_edge_weight, uint32_t* d_edge_count, int edge_capacity, uint32_t* d_verdict, float* d_residuals,
+                                   uint32_t* d_counts, void* hip_stream) {
+    const char* who = "loop_verify_edges";
+    const LcVerifyCall call = lc_verify_call(m, d_pairs, d_model_fwd, fwd_stride_bytes, d_model_bwd, bwd_stride_bytes, d_status_fwd, d_status_bwd,
+                                             d_info36, d_poses7, pose_stride_bytes, node_count, max_cycle_trans, max_cycle_rot, max_prior_trans,
+                                             max_prior_rot, weight, d_edges, d_meas7, d_info36_out, d_edge_weight, d_edge_count, edge_capacity,
+                                             d_verdict, d_residuals, d_counts);
+    vors_status st = lc_verify_refusals(who, call, edge_capacity, fwd_stride_bytes, bwd_stride_bytes, pose_stride_bytes);
+    if (st != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    launch_loop_verify(call, static_cast<hipStream_t>(hip_stream));
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_loop_verify_edges_host(uint32_t m, const uint32_t* pairs, const void* model_fwd, size_t fwd_stride_bytes, const void* model_bwd,
+                                        size_t bwd_stride_bytes, const int32_t* status_fwd, const int32_t* status_bwd, const float* info36,
+                                        const void* poses7, size_t pose_stride_bytes, uint32_t node_count, float max_cycle_trans, float max_cycle_rot,
+                                        float max_prior_trans, float max_prior_rot, float weight, uint32_t* edges, float* meas7, float* info36_out,
+                                        float* edge_weight, uint32_t* edge_count, int edge_capacity, uint32_t* verdict, float* residuals,
+                                        uint32_t* counts) {
+    const LcVerifyCall c = lc_verify_call(m, pairs, model_fwd, fwd_stride_bytes, model_bwd, bwd_stride_bytes, status_fwd, status_bwd, info36, poses7,
+                                          pose_stride_bytes, node_count, max_cycle_trans, max_cycle_rot, max_prior_trans, max_prior_rot, weight, edges,
+                                          meas7, info36_out, edge_weight, edge_count, edge_capacity, verdict, residuals, counts);
+    const vors_status st = lc_verify_refusals("loop_verify_edges_host", c, edge_capacity, fwd_stride_bytes, bwd_stride_bytes, pose_stride_bytes);
+    if (st != VORS_OK) return st;
+    uint32_t tally[VORS_LC_VERDICTS] = {};
+    uint32_t at = std::min<uint32_t>(c.edge_count[0], c.edge_capacity);
+    for (uint32_t e = 0; e < m; ++e) {
+        const uint32_t i = pairs[2 * (size_t)e], j = pairs[2 * (size_t)e + 1];
+        const float* fwd = c.fwd + (size_t)e * c.fwd_stride;
+        const float* info = c.info ? c.info + (size_t)e * 36 : nullptr;
+        const bool status_ok = status_fwd[e] == VORS_TRACK_OK && (!status_bwd || status_bwd[e] == VORS_TRACK_OK);
+        float r12[12];
+        uint32_t v = lc_verify(i, j, status_ok, fwd, c.bwd ? c.bwd + (size_t)e * c.bwd_stride : nullptr, info, c.poses, c.pose_stride, node_count,
+                               max_cycle_trans, max_cycle_rot, max_prior_trans, max_prior_rot, r12);
+        if (v == LC_ACCEPTED) {
+            if (at < c.edge_capacity) {
+                edges[2 * (size_t)at] = i;
+                edges[2 * (size_t)at + 1] = j;
+                for (int k = 0; k < 7; ++k) meas7[(size_t)at * 7 + k] = fwd[k];
+                if (info36_out)
+                    for (int k = 0; k < 36; ++k) info36_out[(size_t)at * 36 + k] = info ? info[k] : (k % 7 == 0 ? 1.0f : 0.0f);
+                if (edge_weight) edge_weight[at] = weight;
+                at += 1u;
+            } else {
+                v = LC_CAPACITY;
+            }
+        }
+        verdict[e] = v;
+        if (residuals)
+            for (int k = 0; k < 12; ++k) residuals[(size_t)e * 12 + k] = r12[k];
+        tally[v] += 1u;
+    }
+    c.edge_count[0] = at;
+    if (counts)
+        for (int k = 0; k < VORS_LC_VERDICTS; ++k) counts[k] = tally[k];
+    return VORS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The map ICP correction at keyframe promotion (vors_trackers_enable_map_icp, trackers.cpp): what it refuses of its parameters — one
 // sentence each, shared by the enable entries and the host twins — the verdict's thresholds as the rule reads them, and the two host
 // twins, which run lie.h map_icp_window / map_icp_verdict, the kernels' own texts.

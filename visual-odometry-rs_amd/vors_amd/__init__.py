@@ -119,6 +119,8 @@ EXPORTED_SYMBOLS = [
     "vors_icp_points_robust", "vors_icp_points_robust_host", "vors_trackers_icp_map_robust",
     "vors_icp_points_joint", "vors_icp_points_joint_host", "vors_trackers_icp_map_joint",
     "vors_pose_graph_workspace_bytes", "vors_pose_graph_optimize", "vors_pose_graph_optimize_host", "vors_pose_graph_jacobians_host",
+    "vors_loop_signatures", "vors_loop_signatures_host", "vors_loop_candidates", "vors_loop_candidates_host",
+    "vors_loop_verify_edges", "vors_loop_verify_edges_host",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_trackers_enable_map_icp", "vors_trackers_map_icp", "vors_tracker_enable_map_icp", "vors_tracker_read_map_icp",
     "vors_map_icp_window_host", "vors_map_icp_verdict_host",
@@ -252,6 +254,14 @@ def lib():
         _lib.vors_pose_graph_optimize_host.argtypes = [vp, u32, i, vp, u32, i, vp, vp, vp, vp] + pg_scalars + [vp, vp, vp, vp]
         _lib.vors_pose_graph_jacobians_host.argtypes = [vp] * 6
         _lib.vors_pose_graph_jacobians_host.restype = None
+        _lib.vors_loop_signatures.argtypes = [i, vp, i, i, i, i, vp, vp, vp]
+        _lib.vors_loop_signatures_host.argtypes = [vp, i, i, i, i, vp, vp]
+        lc_gates = [u32, i, f, f, f]  # min_gap, k, min_score, max_dist_m, min_qdot
+        _lib.vors_loop_candidates.argtypes = [i, vp, vp, vp, i, i, vp, sz, vp] + lc_gates + [vp, vp, vp, vp]
+        _lib.vors_loop_candidates_host.argtypes = [vp, vp, u32, i, i, vp, u32] + lc_gates + [vp, vp, vp]
+        lc_verify = [u32, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, u32, f, f, f, f, f, vp, vp, vp, vp, vp, i, vp, vp, vp]
+        _lib.vors_loop_verify_edges.argtypes = lc_verify + [vp]
+        _lib.vors_loop_verify_edges_host.argtypes = lc_verify
         _lib.vors_trackers_enable_map_icp.argtypes = [vp, vp]
         _lib.vors_trackers_map_icp.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_icp.argtypes = [vp, vp]
@@ -2266,6 +2276,182 @@ def pose_graph_jacobians_host(ti7, tj7, meas7):
     r, ji, jj = np.zeros(6, np.float32), np.zeros((6, 6), np.float32), np.zeros((6, 6), np.float32)
     lib().vors_pose_graph_jacobians_host(*[_ptr(v) for v in a], _ptr(r), _ptr(ji), _ptr(jj))
     return r, ji, jj
+
+
+# ----------------------------------------------------------------------------------------------- loop closure
+LOOP_MAX_K, LOOP_COUNTS, LOOP_VERDICTS = 8, 5, 9  # VORS_LOOP_MAX_K, VORS_LOOP_COUNTS, VORS_LOOP_VERDICTS
+(LOOP_ACCEPTED, LOOP_STATUS, LOOP_INDEX, LOOP_NONFINITE, LOOP_CYCLE_TRANS, LOOP_CYCLE_ROT, LOOP_PRIOR_TRANS, LOOP_PRIOR_ROT,
+ LOOP_CAPACITY) = range(9)  # VORS_LOOP_*
+LOOP_EMPTY = 0xFFFFFFFF
+LOOP_META_DTYPE = np.dtype([("sum", "<i4"), ("sumsq", "<u4")])       # vors_loop_sig_meta
+LOOP_CAND_DTYPE = np.dtype([("i", "<u4"), ("score", "<f4")])         # vors_loop_candidate
+
+
+def loop_signatures(gray, tr, tc, sig=None, meta=None, at=0):
+    """Thumbnail signatures of n grey planes (vors_loop_signatures; handle-free, on the current stream, not synchronised) -> dict: "sig"
+    int8 [n or capacity, tr * tc] and "meta" int32 [n or capacity, 2] (sum, sumsq; the bytes of vors_loop_sig_meta). gray uint8
+    [n, rows, cols] contiguous. sig / meta: existing [capacity, D] / [capacity, 2] tensors to write rows [at, at + n) of — keyframes
+    appended as they are promoted; the other rows keep their bits."""
+    import torch
+    who = "loop_signatures"
+    if gray.dtype != torch.uint8 or gray.dim() != 3 or not gray.is_contiguous():
+        raise VorsError(f"{who}: gray uint8 [n, rows, cols], contiguous")
+    n, rows, cols = gray.shape
+    d = int(tr) * int(tc)
+    if sig is None:
+        sig = torch.empty((at + n, d), dtype=torch.int8, device=gray.device)
+    if meta is None:
+        meta = torch.empty((at + n, 2), dtype=torch.int32, device=gray.device)
+    if (sig.dtype != torch.int8 or sig.dim() != 2 or sig.shape[1] != d or not sig.is_contiguous() or meta.dtype != torch.int32
+            or tuple(meta.shape) != (sig.shape[0], 2) or not meta.is_contiguous() or at < 0 or at + n > sig.shape[0]):
+        raise VorsError(f"{who}: sig int8 [capacity, {d}] and meta int32 [capacity, 2], contiguous, with rows [at, at + n) inside")
+    _check(lib().vors_loop_signatures(n, Batch._dp(gray), rows, cols, int(tr), int(tc), C.c_void_p(sig.data_ptr() + at * d),
+                                      C.c_void_p(meta.data_ptr() + at * 8), Batch._stream()))
+    return dict(sig=sig, meta=meta)
+
+
+def loop_signatures_host(gray, tr, tc):
+    """The signature of ONE plane on the host (vors_loop_signatures_host; needs no GPU) -> (sig int8 [tr * tc], sum, sumsq)."""
+    g = np.ascontiguousarray(gray, np.uint8)
+    if g.ndim != 2:
+        raise VorsError("loop_signatures_host: gray uint8 [rows, cols]")
+    sig = np.zeros(max(int(tr) * int(tc), 1), np.int8)
+    meta = np.zeros(1, LOOP_META_DTYPE)
+    _check(lib().vors_loop_signatures_host(_ptr(g), g.shape[0], g.shape[1], int(tr), int(tc), _ptr(sig), _ptr(meta)))
+    return sig, int(meta[0]["sum"]), int(meta[0]["sumsq"])
+
+
+def loop_candidates(sig, meta, counts_in, min_gap, k, min_score, poses=None, max_dist_m=0.0, min_qdot=0.0, query_first=None, counts=True,
+                    cand=None, cand_counts=None):
+    """All-pairs ZNCC of signatures, gated, the best k per query (vors_loop_candidates; handle-free, on the current stream, not
+    synchronised) -> dict: "cand_i" int32 [n, capacity, k] (-1 = unused) and "cand_score" float32 [n, capacity, k] — views of ONE
+    [n, capacity, k, 2] int32 tensor "cand", the vors_loop_candidate records —, "cand_counts" int32 [n, capacity], "counts" int32 [n, 5]
+    (examined, flat, pose-gated, score-gated, survivors). Only the queries in [query_first, count) of each set are written; new tensors
+    start as unused slots and zero counts. sig int8 [n, capacity, D], meta int32 [n, capacity, 2], counts_in int32 [n]; poses float32
+    [n, capacity, >= 7] camera -> world or None; query_first int32 [n] or None."""
+    import torch
+    who = "loop_candidates"
+    if sig.dtype != torch.int8 or sig.dim() != 3 or not sig.is_contiguous():
+        raise VorsError(f"{who}: sig int8 [n, capacity, D], contiguous")
+    n, cap, d = sig.shape
+    dev = sig.device
+    width = poses.shape[2] if poses is not None and poses.dim() == 3 else 7
+    for name, t, dtype, shape in (("meta", meta, torch.int32, (n, cap, 2)), ("counts_in", counts_in, torch.int32, (n,)),
+                                  ("poses", poses, torch.float32, (n, cap, width)), ("query_first", query_first, torch.int32, (n,))):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise VorsError(f"{who}: {name} must be a contiguous {dtype} tensor {shape} on the signatures' device")
+    kk = max(int(k), 1)
+    if cand is None:
+        cand = torch.zeros((n, cap, kk, 2), dtype=torch.int32, device=dev)
+        cand[..., 0] = -1
+    if cand_counts is None:
+        cand_counts = torch.zeros((n, cap), dtype=torch.int32, device=dev)
+    if (cand.dtype != torch.int32 or tuple(cand.shape) != (n, cap, kk, 2) or not cand.is_contiguous() or cand_counts.dtype != torch.int32
+            or tuple(cand_counts.shape) != (n, cap) or not cand_counts.is_contiguous()):
+        raise VorsError(f"{who}: cand int32 ({n}, {cap}, {kk}, 2) and cand_counts int32 ({n}, {cap}), contiguous")
+    cbuf = _out_buf(counts, (n, LOOP_COUNTS), torch.int32, dev)
+    dp = Batch._dp
+    _check(lib().vors_loop_candidates(n, dp(sig), dp(meta), dp(counts_in), cap, d, dp(poses), 0 if width == 7 else 4 * width, dp(query_first),
+                                      int(min_gap), int(k), float(min_score), float(max_dist_m), float(min_qdot), dp(cand), dp(cand_counts),
+                                      dp(cbuf), Batch._stream()))
+    return _result(("cand", True, cand), ("cand_i", True, cand[..., 0]), ("cand_score", True, cand[..., 1].view(torch.float32)),
+                   ("cand_counts", True, cand_counts), ("counts", _asked(counts), cbuf))
+
+
+def loop_candidates_host(sig, meta, min_gap, k, min_score, poses=None, max_dist_m=0.0, min_qdot=0.0, query_first=0, count=None):
+    """The same for ONE set on the host (vors_loop_candidates_host; needs no GPU): sig int8 [capacity, D], meta [capacity, 2] (sum,
+    sumsq), poses [capacity, 7] or None; count: None = the capacity -> dict: "cand" (a LOOP_CAND_DTYPE array [capacity, k], unused
+    slots (0xFFFFFFFF, 0)), "cand_counts" uint32 [capacity], "counts" uint32 [5]."""
+    s = np.ascontiguousarray(sig, np.int8)
+    m = np.ascontiguousarray(meta, np.int32)
+    p = None if poses is None else np.ascontiguousarray(poses, np.float32)
+    if s.ndim != 2 or m.shape != (len(s), 2) or (p is not None and p.shape != (len(s), 7)):
+        raise VorsError("loop_candidates_host: sig int8 [capacity, D], meta [capacity, 2], poses [capacity, 7] or None")
+    kk = max(int(k), 1)
+    cand = np.zeros((len(s), kk), LOOP_CAND_DTYPE)
+    cand["i"] = LOOP_EMPTY
+    out = dict(cand=cand, cand_counts=np.zeros(len(s), np.uint32), counts=np.zeros(LOOP_COUNTS, np.uint32))
+    _check(lib().vors_loop_candidates_host(_ptr(s), _ptr(m), len(s) if count is None else int(count), len(s), s.shape[1], _ptr(p),
+                                           int(query_first), int(min_gap), int(k), float(min_score), float(max_dist_m), float(min_qdot),
+                                           _ptr(cand), _ptr(out["cand_counts"]), _ptr(out["counts"])))
+    return out
+
+
+def loop_verify_edges(pairs, model_fwd, status_fwd, edges, meas, edge_count, model_bwd=None, status_bwd=None, info=None, poses=None,
+                      max_cycle_trans=0.0, max_cycle_rot=0.0, max_prior_trans=0.0, max_prior_rot=0.0, weight=1.0, info_out=None,
+                      edge_weight=None, residuals=True, counts=True):
+    """From tracked loop candidates to pose-graph edges (vors_loop_verify_edges; handle-free, on the current stream, not synchronised):
+    the accepted candidates are appended in candidate order to edges [edge_capacity, 2] int32, meas [edge_capacity, 7], info_out
+    [edge_capacity, 36] and edge_weight [edge_capacity] float32 (the last two optional) from edge_count[0] (int32 [1], in / out) on —
+    the tensors pose_graph_optimize takes -> dict: "verdict" int32 [m] (LOOP_*), "residuals" float32 [m, 12], "counts" int32 [9].
+    pairs int32 [m, 2]; model_fwd / model_bwd float32 [m, >= 7] (row stride = the width: the lm_model columns of a stats tensor go in
+    as a [m, width] view whose first 7 columns are the model); status_* int32 [m]; info float32 [m, 36]; poses float32
+    [node_count, >= 7] camera -> world."""
+    import torch
+    who = "loop_verify_edges"
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise VorsError(f"{who}: pairs int32 [m, 2], contiguous")
+    m, dev = pairs.shape[0], pairs.device
+
+    def rows(name, t, least):  # a float32 [*, >= least] matrix whose rows are `width` floats apart -> its stride in bytes (0 = packed)
+        if t is None:
+            return 0
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < least or t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.device != dev:
+            raise VorsError(f"{who}: {name} must be a float32 [rows, >= {least}] tensor with unit column stride on the pairs' device")
+        return 0 if t.stride(0) == least else 4 * t.stride(0)
+
+    fwd_bytes, bwd_bytes, pose_bytes = rows("model_fwd", model_fwd, 7), rows("model_bwd", model_bwd, 7), rows("poses", poses, 7)
+    ecap = edges.shape[0]
+    for name, t, dtype, shape in (("status_fwd", status_fwd, torch.int32, (m,)), ("status_bwd", status_bwd, torch.int32, (m,)),
+                                  ("info", info, torch.float32, (m, 36)), ("edges", edges, torch.int32, (ecap, 2)),
+                                  ("meas", meas, torch.float32, (ecap, 7)), ("info_out", info_out, torch.float32, (ecap, 36)),
+                                  ("edge_weight", edge_weight, torch.float32, (ecap,)), ("edge_count", edge_count, torch.int32, (1,))):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise VorsError(f"{who}: {name} must be a contiguous {dtype} tensor {shape} on the pairs' device")
+    if model_fwd.shape[0] != m or (model_bwd is not None and model_bwd.shape[0] != m):
+        raise VorsError(f"{who}: one model per pair")
+    verdict = torch.empty(m, dtype=torch.int32, device=dev)
+    rbuf, cbuf = _out_buf(residuals, (m, 12), torch.float32, dev), _out_buf(counts, (LOOP_VERDICTS,), torch.int32, dev)
+    dp = Batch._dp
+    _check(lib().vors_loop_verify_edges(m, dp(pairs), dp(model_fwd), fwd_bytes, dp(model_bwd), bwd_bytes, dp(status_fwd), dp(status_bwd),
+                                        dp(info), dp(poses), pose_bytes, 0 if poses is None else poses.shape[0], float(max_cycle_trans),
+                                        float(max_cycle_rot), float(max_prior_trans), float(max_prior_rot), float(weight), dp(edges), dp(meas),
+                                        dp(info_out), dp(edge_weight), dp(edge_count), ecap, dp(verdict), dp(rbuf), dp(cbuf), Batch._stream()))
+    return _result(("verdict", True, verdict), ("residuals", _asked(residuals), rbuf), ("counts", _asked(counts), cbuf))
+
+
+def loop_verify_edges_host(pairs, model_fwd, status_fwd, edge_capacity, model_bwd=None, status_bwd=None, info=None, poses=None,
+                           max_cycle_trans=0.0, max_cycle_rot=0.0, max_prior_trans=0.0, max_prior_rot=0.0, weight=1.0, edges=None, meas=None,
+                           info_out=None, edge_weight=None, edge_count=0):
+    """The same on the host (vors_loop_verify_edges_host; needs no GPU): pairs [m, 2], model_* [m, 7], status_* [m], info [m, 36], poses
+    [node_count, 7]; edges / meas / info_out / edge_weight: the lists to append to from edge_count on (None = new ones of edge_capacity
+    rows, filled with 0xFFFFFFFF and NaN) -> dict: "edges", "meas", "info", "edge_weight" (copies, appended to), "edge_count", "verdict"
+    uint32 [m], "residuals" [m, 12], "counts" uint32 [9]."""
+    pr = np.ascontiguousarray(pairs, np.uint32)
+    mf = np.ascontiguousarray(model_fwd, np.float32)
+    mb = None if model_bwd is None else np.ascontiguousarray(model_bwd, np.float32)
+    sf = np.ascontiguousarray(status_fwd, np.int32)
+    sb = None if status_bwd is None else np.ascontiguousarray(status_bwd, np.int32)
+    om = None if info is None else np.ascontiguousarray(info, np.float32)
+    ps = None if poses is None else np.ascontiguousarray(poses, np.float32)
+    m, ecap = len(pr), max(int(edge_capacity), 0)
+    if (pr.ndim != 2 or pr.shape[1] != 2 or mf.shape != (m, 7) or (mb is not None and mb.shape != (m, 7)) or sf.shape != (m,)
+            or (sb is not None and sb.shape != (m,)) or (om is not None and om.shape != (m, 36)) or (ps is not None and (ps.ndim != 2 or ps.shape[1] != 7))):
+        raise VorsError("loop_verify_edges_host: pairs [m, 2], models [m, 7], statuses [m], info [m, 36], poses [node_count, 7]")
+    e = np.full((ecap, 2), LOOP_EMPTY, np.uint32) if edges is None else np.array(edges, np.uint32).reshape(ecap, 2)
+    ms = np.full((ecap, 7), np.nan, np.float32) if meas is None else np.array(meas, np.float32).reshape(ecap, 7)
+    io = np.full((ecap, 36), np.nan, np.float32) if info_out is None else np.array(info_out, np.float32).reshape(ecap, 36)
+    ew = np.full(ecap, np.nan, np.float32) if edge_weight is None else np.array(edge_weight, np.float32).reshape(ecap)
+    ec = np.array([edge_count], np.uint32)
+    out = dict(edges=e, meas=ms, info=io, edge_weight=ew, verdict=np.full(m, 0xFFFFFFFF, np.uint32), residuals=np.full((m, 12), 7.5, np.float32),
+               counts=np.full(LOOP_VERDICTS, 0xFFFFFFFF, np.uint32))
+    some = lambda a: _ptr(a) if a is not None and a.size else None  # noqa: E731
+    _check(lib().vors_loop_verify_edges_host(m, some(pr), some(mf), 0, some(mb), 0, some(sf), some(sb), some(om), some(ps), 0,
+                                             0 if ps is None else len(ps), float(max_cycle_trans), float(max_cycle_rot), float(max_prior_trans),
+                                             float(max_prior_rot), float(weight), some(e), some(ms), some(io), some(ew), _ptr(ec), int(edge_capacity),
+                                             some(out["verdict"]), some(out["residuals"]), some(out["counts"])))
+    out["edge_count"] = int(ec[0])
+    return out
 
 
 ICP_GATE_COUNTS = 4  # VORS_ICP_GATE_COUNTS: with_depth, within_dist, matched, huber_linear
