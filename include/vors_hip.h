@@ -143,7 +143,9 @@ int vors_abi_version(void);  /* 2: vors_config.arithmetic, vors_pair_stats.nb_gr
                               *    VORS_REGISTER_COUNTS, likewise; + vors_pose_graph_optimize, vors_pose_graph_optimize_host,
                               *    vors_pose_graph_workspace_bytes, vors_pose_graph_jacobians_host, vors_pose_graph_stats, VORS_PG_*, likewise;
                               *    + vors_loop_signatures, vors_loop_candidates, vors_loop_verify_edges, their _host twins, vors_loop_sig_meta,
-                              *    vors_loop_candidate, VORS_LOOP_*, likewise) */
+                              *    vors_loop_candidate, VORS_LOOP_*, likewise; + vors_repose_points, vors_repose_points_host,
+                              *    vors_trackers_repose_map, vors_voxel_filter_points, vors_voxel_filter_points_host,
+                              *    vors_voxel_filter_workspace_bytes, VORS_REPOSE_COUNTS, likewise) */
 
 /* ------------------------------------------------------------------------------------------------------------
  * 1. Tracker: one sequence, host buffers.  Replaces
@@ -1516,6 +1518,95 @@ vors_status vors_loop_verify_edges_host(uint32_t m, const uint32_t* pairs, const
                                         float max_cycle_rot, float max_prior_trans, float max_prior_rot, float weight, uint32_t* edges,
                                         float* meas7, float* info36_out /* nullable */, float* edge_weight /* nullable */, uint32_t* edge_count,
                                         int edge_capacity, uint32_t* verdict, float* residuals /* nullable */, uint32_t* counts /* nullable */);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * 2i. THE CORRECTED MAP, device-resident and handle-free (the reference has none): what a caller who closed a loop does with
+ *     the poses vors_pose_graph_optimize returned. RE-POSE moves every point and normal of a list from the pose its keyframe had to the
+ *     pose the optimiser gave it; RE-FILTER restores "one point per occupied voxel, the first in the list's order" on any point list.
+ *     Both are stream-ordered, allocate nothing, use integer atomics only, and equal their host twins bit for bit.
+ * RE-POSE. n lists side by side, the pointers of vors_trackers_map / vors_trackers_map_normals and of vors_pose_graph_optimize:
+ *   d_xyz [n][capacity][3] f32, d_normals likewise (nullable), d_list_counts [n] u32 (unclipped: the ranks treated are those below
+ *   min(count, capacity)); d_segments [n][max_keyframes] with d_n_segments [n] (the first min(n_segments, max_keyframes) records are
+ *   used; their `first` must ascend, as a map's do — otherwise which record a rank takes is unspecified, and every store still stays
+ *   inside its buffers); d_poses7_new, node_capacity poses per list, pose_stride_bytes apart (0 = 28; a multiple of 4 of at least 28),
+ *   d_node_counts [n] (clipped to node_capacity); d_node_of_segment [n][max_keyframes] u32 (nullable = segment k is node k; the value
+ *   0xFFFFFFFF = this keyframe is not in the graph).
+ *   A rank belongs to the LAST record whose `first` is not above it, if it lies below that record's first + count; a zero-count segment
+ *   owns no rank; the ranks at or beyond the end of the last record have NO RECORD (keyframes beyond max_keyframes).
+ *   A recorded segment k with old pose A = segments[k].pose7 and new pose B MOVES iff it has a node (an index below the node count, not
+ *   the sentinel), all seven floats of B are finite and B's bits differ from A's. Otherwise it is KEPT: points, normals and record are
+ *   copied bit for bit — re-posing with the poses the map already has is the identity on bits, and a fixed node never drifts.
+ *   Moved point: c = extrinsics::project(A, p), p' = B * c (the texts of vors_camera_project and vors_camera_back_project, unchanged):
+ *   through the keyframe's camera frame, so p' is what the map would have stored with the keyframe at B, up to rounding. Moved normal:
+ *   n' = B.q * (A.q^-1 * n). A point with a non-finite component (a NaN row of vors_voxel_means) is copied bit for bit wherever it lies,
+ *   likewise a normal, each on its own; a rank without a record is copied. A NaN the arithmetic itself produces is stored as 0x7FC00000.
+ *   Outputs, each nullable, one of the first two required: d_xyz_out, d_normals_out (refused without d_normals) — exactly the ranks below
+ *   min(count, capacity) are written; d_segments_out — exactly the used records, pose7 replaced where the segment moved, frame / first /
+ *   count kept; d_counts_out [n][VORS_REPOSE_COUNTS] u32 = {points moved; kept; non-finite (wherever they lie); without a record;
+ *   segments moved; the largest |p' - p| over the moved points as the bits of a non-negative f32 under an unsigned maximum}. The first
+ *   four add up to min(count, capacity).
+ *   d_xyz_out == d_xyz, d_normals_out == d_normals and d_segments_out == d_segments are legal (a rank is read and written by one lane;
+ *   the records are written by a launch behind the point pass, which reads the old ones). Refused with VORS_ERR_INVALID_ARGUMENT, nothing
+ *   enqueued: a NULL required pointer; n outside 1..65535; capacity, max_keyframes or node_capacity < 1; a bad stride; an array off
+ *   4-byte alignment; any other overlap of an output with an input or with another output; d_normals_out without d_normals; a stream of
+ *   another device than the current one. A 16-byte aligned list is moved with 16-byte accesses, any other point by point: same bits. */
+#define VORS_REPOSE_COUNTS 6
+vors_status vors_repose_points(int n, const float* d_xyz, const float* d_normals /* nullable */, const uint32_t* d_list_counts, int capacity,
+                               const vors_map_segment* d_segments, const uint32_t* d_n_segments, int max_keyframes, const void* d_poses7_new,
+                               size_t pose_stride_bytes, int node_capacity, const uint32_t* d_node_counts,
+                               const uint32_t* d_node_of_segment /* nullable */, float* d_xyz_out /* nullable */,
+                               float* d_normals_out /* nullable */, vors_map_segment* d_segments_out /* nullable */,
+                               uint32_t* d_counts_out /* nullable */, void* hip_stream);
+/* The same for ONE list in HOST memory (no GPU): the text the kernels run, bit for bit; poses7_new packed [node_capacity][7]. Same
+ * refusals. */
+vors_status vors_repose_points_host(const float* xyz, const float* normals /* nullable */, uint32_t count, int capacity,
+                                    const vors_map_segment* segments, uint32_t n_segments, int max_keyframes, const float* poses7_new,
+                                    uint32_t node_count, int node_capacity, const uint32_t* node_of_segment /* nullable */,
+                                    float* xyz_out /* nullable */, float* normals_out /* nullable */, vors_map_segment* segments_out /* nullable */,
+                                    uint32_t counts_out[VORS_REPOSE_COUNTS] /* nullable */);
+/* vors_repose_points on a sequence handle's own map: its lists, its normals (when vors_trackers_enable_map_normals is on), its counters
+ * and its segments are the inputs, the CALLER's arrays the outputs. The handle is read only: its map, voxel table, statistics and poses
+ * stay as tracking left them (feeding corrected poses back into a running tracker is not done here). Refused like
+ * vors_trackers_render_map — no enabled map, a call before vors_trackers_init, a stream of another device — and with every refusal of
+ * vors_repose_points; an output that IS one of the handle's arrays is refused too. Enqueued on hip_stream, NOT synchronised. */
+vors_status vors_trackers_repose_map(vors_trackers* t, const void* d_poses7_new, size_t pose_stride_bytes, int node_capacity,
+                                     const uint32_t* d_node_counts, const uint32_t* d_node_of_segment /* nullable */,
+                                     float* d_xyz_out /* nullable */, float* d_normals_out /* nullable */,
+                                     vors_map_segment* d_segments_out /* nullable */, uint32_t* d_counts_out /* nullable */, void* hip_stream);
+/* RE-FILTER. Per list of d_xyz [n][capacity][3] / d_list_counts [n]: the ranks r below min(count, capacity) whose voxel key
+ *   (vors_voxel_keys with voxel_m, section 4) is not VORS_VOXEL_NONE and occurs at no lower rank, in ascending order — the definition of
+ *   vors_trackers_enable_map_voxels, for a list that already exists.
+ *   d_index [n][capacity] u32: the source rank of every kept entry; d_counts_out [n] u32: their number; d_overflow [n] u32 (all three
+ *   required). Gathered copies through the index, each pair nullable: d_xyz_out; d_pixel -> d_pixel_out (u32); d_gray -> d_gray_out (u8);
+ *   d_normals -> d_normals_out. With d_segments / d_n_segments / max_keyframes and d_segments_out: the used records for the filtered
+ *   list — first = the kept ranks below the old first, count = the kept ranks in [first, first + count) of the source, frame and pose7
+ *   kept. Entries at or beyond a list's kept count are not written.
+ *   d_workspace: vors_voxel_filter_workspace_bytes(n, capacity, table_slots) bytes, 16-byte aligned — per list a table of table_slots (a
+ *   power of two in 64..2^30) entries of 16 bytes, emptied inside the call, and 4 bytes per 1024 ranks of capacity. The probes are the
+ *   keyframe map's (open addressing, linear probing, the owner of a voxel the minimum rank): the result does not depend on scheduling,
+ *   on the other lists, on the stream or on table_slots while a list's distinct voxels are <= table_slots. Beyond that the list's
+ *   overflow word is set and its outputs are unspecified (every store stays inside its buffers, a point probes at most table_slots
+ *   entries); the other lists keep the exact result.
+ *   Six launches: EMPTY, CLAIM, COUNT, SCAN, WRITE, SEGMENTS (the last with d_segments_out only). Refused with VORS_ERR_INVALID_ARGUMENT,
+ *   nothing enqueued: a NULL required pointer; n outside 1..65535; capacity < 1; voxel_m not finite or <= 0; a bad table_slots; a gathered
+ *   output without its input; d_segments_out without the records, their count or max_keyframes >= 1; an array off its alignment; ANY
+ *   overlap of an output or the workspace with an input or another output (nothing may be filtered in place); a stream of another device. */
+uint64_t vors_voxel_filter_workspace_bytes(int n, int capacity, int table_slots);  /* 0 for arguments the pass refuses */
+vors_status vors_voxel_filter_points(int n, const float* d_xyz, const uint32_t* d_list_counts, int capacity, float voxel_m, int table_slots,
+                                     void* d_workspace, const uint32_t* d_pixel /* nullable */, const uint8_t* d_gray /* nullable */,
+                                     const float* d_normals /* nullable */, const vors_map_segment* d_segments /* nullable */,
+                                     const uint32_t* d_n_segments /* nullable */, int max_keyframes, uint32_t* d_index, uint32_t* d_counts_out,
+                                     uint32_t* d_overflow, float* d_xyz_out /* nullable */, uint32_t* d_pixel_out /* nullable */,
+                                     uint8_t* d_gray_out /* nullable */, float* d_normals_out /* nullable */,
+                                     vors_map_segment* d_segments_out /* nullable */, void* hip_stream);
+/* The same for ONE list in HOST memory (no GPU): the first occurrence of every key of vors_voxel_keys. No workspace; *overflow is 1
+ * when the list's distinct voxels exceed table_slots — where the device's result is unspecified — and the result is exact all the same. */
+vors_status vors_voxel_filter_points_host(const float* xyz, uint32_t count, int capacity, float voxel_m, int table_slots,
+                                          const uint32_t* pixel /* nullable */, const uint8_t* gray /* nullable */,
+                                          const float* normals /* nullable */, const vors_map_segment* segments /* nullable */,
+                                          uint32_t n_segments, int max_keyframes, uint32_t* index, uint32_t* count_out, uint32_t* overflow,
+                                          float* xyz_out /* nullable */, uint32_t* pixel_out /* nullable */, uint8_t* gray_out /* nullable */,
+                                          float* normals_out /* nullable */, vors_map_segment* segments_out /* nullable */);
 
 /* ------------------------------------------------------------------------------------------------------------
  * 3. Operator level — the optimizer trait's pieces for one pyramid level.  Replaces, for

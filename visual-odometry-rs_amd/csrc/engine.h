@@ -977,6 +977,63 @@ struct VoxelMeansCall {
 void launch_voxel_means(const VoxelMeansCall& call, hipStream_t s);
 // The windowed form: the clear of `records` and one launch over call.n lists; ranges, records, segments, xyz_mean and gray_mean required.
 void launch_voxel_means_window(const VoxelMeansCall& call, hipStream_t s);
+// Re-posing of point lists after pose-graph optimisation (vors_repose_points, vors_trackers_repose_map; repose_kernels.hip
+// repose_points_kernel, repose_segments_kernel): per rank lie.h repose_point / repose_normal with the two poses of its segment.
+// Handle-free: everything the kernels read is here. xyz_out / normals_out / segments_out may be exactly xyz / normals / segments.
+struct ReposeCall {
+    int n;                             // lists
+    const float* xyz;                  // [n][capacity][3]
+    const float* normals;              // [n][capacity][3], nullable
+    const uint32_t* list_counts;       // [n]; a count above capacity is clipped to it
+    int capacity;
+    const vors_map_segment* segments;  // [n][max_keyframes]
+    const uint32_t* n_segments;        // [n]; clipped to max_keyframes
+    int max_keyframes;
+    const float* poses_new;            // [n][node_capacity] poses, pose_stride floats apart
+    int pose_stride, node_capacity;
+    const uint32_t* node_counts;       // [n]; clipped to node_capacity
+    const uint32_t* node_of_segment;   // [n][max_keyframes], nullable = segment k is node k
+    float* xyz_out;                    // nullable
+    float* normals_out;                // nullable
+    vors_map_segment* segments_out;    // nullable
+    uint32_t* counts_out;              // [n][VORS_REPOSE_COUNTS], nullable
+};
+// The clear of counts_out, the point pass and, with segments_out or counts_out, the record pass behind it: enqueued on s, not
+// synchronised, no workspace.
+void launch_repose_points(const ReposeCall& call, hipStream_t s);
+// The voxel filter of plain point lists (vors_voxel_filter_points; repose_kernels.hip voxel_filter_*_kernel): EMPTY, CLAIM, COUNT, SCAN,
+// WRITE and, with segments_out, SEGMENTS, through voxel_table_device.h's probes with the rank as the tag. table / chunk_counts /
+// occupied are carved from the caller's workspace (voxel_filter_workspace_carve).
+#define VORS_VFILTER_CHUNK 1024
+struct VoxelFilterCall {
+    int n;
+    const float* xyz;                  // [n][capacity][3]
+    const uint32_t* list_counts;       // [n]
+    int capacity;
+    float voxel_m;
+    int table_slots;
+    unsigned long long* table;         // [n][table_slots][2]
+    uint32_t* chunk_counts;            // [n][chunks]
+    uint32_t* occupied;                // [n]
+    int chunks;                        // ceil(capacity / VORS_VFILTER_CHUNK)
+    uint32_t* index;                   // [n][capacity]
+    uint32_t* counts_out;              // [n]
+    uint32_t* overflow;                // [n]
+    const uint32_t* pixel;             // gathers, each pair nullable
+    const uint8_t* gray;
+    const float* normals;
+    float* xyz_out;
+    uint32_t* pixel_out;
+    uint8_t* gray_out;
+    float* normals_out;
+    const vors_map_segment* segments;  // [n][max_keyframes], nullable
+    const uint32_t* n_segments;
+    int max_keyframes;
+    vors_map_segment* segments_out;
+};
+// Bytes of the workspace; with `call` and `workspace` also sets call->table, chunk_counts, occupied and chunks.
+size_t voxel_filter_workspace_carve(VoxelFilterCall* call, void* workspace, int n, int capacity, int table_slots);
+void launch_voxel_filter_points(const VoxelFilterCall& call, hipStream_t s);
 // Operator level on explicit observations of one level (device buffers): eval at `model` -> out29 partial sums layout:
 // [0]=sum r^2 (or Huber loss), [1]=n_inside (as float), [2..7]=g, [8..28]=H upper triangle row-wise.
 void launch_lm_eval_obs(Intr k, int rows, int cols, const uint8_t* image, int n, Records rec, float huber_delta,

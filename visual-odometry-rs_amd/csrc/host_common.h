@@ -231,6 +231,9 @@ struct IcpArgs {
 // The device pass of vors_icp_points, _robust and _joint, and of their forwards on the sequence handle: every refusal in the name of
 // `who`, then launch_icp_points on s. Internal: hidden, so that the library's dynamic symbols stay the ones it had.
 __attribute__((visibility("hidden"))) vors_status icp_points_device(const char* who, const IcpArgs& args, hipStream_t s);
+// The device pass of vors_repose_points and of its forward on the sequence handle (operators.cpp): every refusal in the name of `who` —
+// call.pose_stride is set from pose_stride_bytes here —, then launch_repose_points on s. Hidden likewise.
+__attribute__((visibility("hidden"))) vors_status repose_points_device(const char* who, vors::ReposeCall call, size_t pose_stride_bytes, hipStream_t s);
 }
 // vors_batch_create_on with one more decision: allow_halves = false keeps the handle on the plain path whatever its size (HalvesPlan is
 // then never created). A vors_pipeline slot is created so: its steps already overlap with its neighbours', on the ring's own streams.

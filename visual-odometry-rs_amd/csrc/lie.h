@@ -1544,4 +1544,71 @@ VORS_UNROLL
     return verdict;
 }
 
+// Re-posing of point lists after pose-graph optimisation (vors_repose_points, include/vors_hip.h 2i): the texts the
+// kernels of repose_kernels.hip and the host twin (vors_repose_points_host) both run, bit for bit.
+#define VORS_REPOSE_NO_NODE 0xFFFFFFFFu
+enum { REPOSE_MOVED = 0, REPOSE_KEPT = 1, REPOSE_NONFINITE = 2, REPOSE_NO_RECORD = 3, REPOSE_SEGMENTS_MOVED = 4, REPOSE_MAX_SHIFT = 5 };
+VORS_HD uint32_t repose_bits(float v) { return __builtin_bit_cast(uint32_t, v); }
+// The node of recorded segment k: k itself without a table, the table's word with one; VORS_REPOSE_NO_NODE when the word is the
+// sentinel or the index is not below the graph's node count (itself clipped to node_capacity: no pose beyond it is ever read).
+VORS_HD uint32_t repose_node(uint32_t k, const uint32_t* node_of_segment /* nullable */, uint32_t node_count, int node_capacity) {
+    const uint32_t nodes = node_count < (uint32_t)node_capacity ? node_count : (uint32_t)node_capacity;
+    const uint32_t node = node_of_segment ? node_of_segment[k] : k;
+    return node != VORS_REPOSE_NO_NODE && node < nodes ? node : VORS_REPOSE_NO_NODE;
+}
+// A segment with old pose a7 MOVES to b7 (NULL: it has no node) iff all seven floats of b7 are finite and their bits differ from a7's.
+VORS_HD bool repose_moves(const float* a7, const float* b7 /* nullable */) {
+    if (!b7) return false;
+    bool finite = true, differs = false;
+VORS_UNROLL
+    for (int k = 0; k < 7; ++k) {
+        finite = finite && f32_finite(b7[k]);
+        differs = differs || repose_bits(a7[k]) != repose_bits(b7[k]);
+    }
+    return finite && differs;
+}
+VORS_HD bool repose_finite3(const V3& p) { return f32_finite(p.x) && f32_finite(p.y) && f32_finite(p.z); }
+// A NaN that arithmetic produced (a finite input that overflowed on the way) is stored as ONE bit pattern: what the hardware would
+// put into its payload and sign is not the same on every machine.
+VORS_HD float repose_canonical(float v) { return v != v ? __builtin_bit_cast(float, VORS_VOXEL_MEAN_NAN_BITS) : v; }
+VORS_HD V3 repose_canonical3(const V3& p) { return V3{repose_canonical(p.x), repose_canonical(p.y), repose_canonical(p.z)}; }
+// A point of a moved segment: through the keyframe's camera frame at the old pose, out again at the new one — existing texts, unchanged.
+VORS_HD V3 repose_point(const Iso& a, const Iso& b, const V3& p) { return repose_canonical3(iso_transform_point(b, extr_project(a, p))); }
+// Its normal: the two rotations alone.
+VORS_HD V3 repose_normal(const Iso& a, const Iso& b, const V3& n) {
+    const Quat qi{-a.q.i, -a.q.j, -a.q.k, a.q.w};
+    return repose_canonical3(quat_rotate(b.q, quat_rotate(qi, n)));
+}
+// |p' - p| as the bits of a non-negative f32 (a NaN: the one pattern above, which an unsigned maximum ranks above every length).
+VORS_HD uint32_t repose_shift_bits(const V3& p, const V3& q) {
+    const V3 d{q.x - p.x, q.y - p.y, q.z - p.z};
+    return repose_bits(repose_canonical(sqrtf(dot3(d, d))));
+}
+// The ranks of recorded segment k of a list of `total` ranks, [*lo, *hi) (empty: *lo >= *hi): from its `first` to its own end, to the
+// next record's `first` and to the list's end, whichever comes first — so that with ascending `first`, which a map's records have, a
+// rank belongs to the LAST record whose `first` is not above it, and a zero-count segment owns no rank. words: the list's records as
+// 32-bit words (MAP_SEGMENT_WORDS per record, first at word 1, count at word 2).
+VORS_HD void repose_segment_ranks(const uint32_t* words, uint32_t k, uint32_t n_rec, uint32_t total, uint32_t* lo, uint32_t* hi) {
+    const uint32_t first = words[(size_t)k * MAP_SEGMENT_WORDS + 1], count = words[(size_t)k * MAP_SEGMENT_WORDS + 2];
+    const uint64_t end64 = (uint64_t)first + (uint64_t)count;
+    uint32_t end = end64 < (uint64_t)total ? (uint32_t)end64 : total;
+    if (k + 1u < n_rec) {
+        const uint32_t next = words[(size_t)(k + 1u) * MAP_SEGMENT_WORDS + 1];
+        if (next < end) end = next;
+    }
+    *lo = first;
+    *hi = end;
+}
+// The voxel filter of plain point lists (vors_voxel_filter_points): the number of kept source ranks below x, a lower-bound search in the
+// ascending index list of a filtered list. A segment [first, first + count) of the source becomes [below(first), below(first + count)).
+VORS_HD uint32_t voxel_filter_below(const uint32_t* index, uint32_t kept, uint64_t x) {
+    uint32_t lo = 0, hi = kept;  // the first position in [0, kept] whose entry is >= x
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        if ((uint64_t)index[mid] < x) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace vors

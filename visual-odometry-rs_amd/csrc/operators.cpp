@@ -1772,6 +1772,254 @@ vors_status vors_voxel_means_host(const float* xyz, uint32_t count, int capacity
     return VORS_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Re-posing of point lists and the voxel filter of plain lists (include/vors_hip.h 2i): the refusals the device and the host entries
+// share, the device entries (repose_kernels.hip) and the host twins, which run the kernels' own texts (lie.h repose_*, voxel_key,
+// voxel_filter_below).
+// ---------------------------------------------------------------------------------------------------------------
+// An array of a call as the overlap test sees it. Two arrays overlap when they share a byte; `same` names the one input an output may
+// be — exactly, base and extent — without being refused.
+struct ArgSpan {
+    const char* name;
+    const void* p;
+    size_t bytes;
+    const void* same;
+};
+static bool spans_share(const ArgSpan& a, const ArgSpan& b) {
+    if (!a.p || !b.p || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+static vors_status overlap_refusals(const std::string& w, const std::vector<ArgSpan>& in, const std::vector<ArgSpan>& out) {
+    for (size_t o = 0; o < out.size(); ++o) {
+        for (const ArgSpan& i : in)
+            if (spans_share(out[o], i) && !(out[o].same && out[o].same == i.p && out[o].p == i.p))
+                return fail(VORS_ERR_INVALID_ARGUMENT, w + ": " + out[o].name + " overlaps " + i.name);
+        for (size_t q = 0; q < o; ++q)
+            if (spans_share(out[o], out[q])) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": " + out[o].name + " overlaps " + out[q].name);
+    }
+    return VORS_OK;
+}
+// A handle-free pass runs on the calling thread's current device: a stream of another one is refused (a stream nobody can place: let the
+// launch report).
+static vors_status stream_refusal(const std::string& w, hipStream_t s) {
+    if (!s) return VORS_OK;
+    hipDevice_t of;
+    int cur = -1;
+    if (hipStreamGetDevice(s, &of) != hipSuccess || hipGetDevice(&cur) != hipSuccess) {
+        (void)hipGetLastError();
+        return VORS_OK;
+    }
+    if ((int)of != cur)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the stream belongs to device " + std::to_string((int)of) + " but the current device is " + std::to_string(cur));
+    return VORS_OK;
+}
+
+static vors_status repose_refusals(const char* who, const ReposeCall& c) {
+    const std::string w(who);
+    if (c.n < 1 || c.n > 65535) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be in 1..65535");
+    if (c.capacity < 1 || c.max_keyframes < 1 || c.node_capacity < 1)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity, max_keyframes and node_capacity must be >= 1");
+    if (!c.xyz || !c.list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, list_counts) is NULL");
+    if (!c.segments || !c.n_segments) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the segments or their count are NULL");
+    if (!c.poses_new || !c.node_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": the new poses or their count are NULL");
+    if (!c.xyz_out && !c.normals_out) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": no list output at all (xyz_out and normals_out are NULL)");
+    if (c.normals_out && !c.normals) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": normals_out without normals");
+    for (const void* p : {(const void*)c.xyz, (const void*)c.normals, (const void*)c.list_counts, (const void*)c.segments, (const void*)c.n_segments,
+                          (const void*)c.poses_new, (const void*)c.node_counts, (const void*)c.node_of_segment, (const void*)c.xyz_out,
+                          (const void*)c.normals_out, (const void*)c.segments_out, (const void*)c.counts_out})
+        if ((uintptr_t)p % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": every array must be 4-byte aligned");
+    const size_t lists = (size_t)c.n * (size_t)c.capacity * 12, words = (size_t)c.n * 4, recs = (size_t)c.n * (size_t)c.max_keyframes * sizeof(vors_map_segment);
+    const std::vector<ArgSpan> in{{"xyz", c.xyz, lists, nullptr}, {"normals", c.normals, lists, nullptr}, {"list_counts", c.list_counts, words, nullptr},
+                                  {"segments", c.segments, recs, nullptr}, {"n_segments", c.n_segments, words, nullptr},
+                                  {"poses7_new", c.poses_new, (size_t)c.n * (size_t)c.node_capacity * (size_t)c.pose_stride * 4, nullptr},
+                                  {"node_counts", c.node_counts, words, nullptr},
+                                  {"node_of_segment", c.node_of_segment, (size_t)c.n * (size_t)c.max_keyframes * 4, nullptr}};
+    const std::vector<ArgSpan> out{{"xyz_out", c.xyz_out, lists, c.xyz}, {"normals_out", c.normals_out, lists, c.normals},
+                                   {"segments_out", c.segments_out, recs, c.segments},
+                                   {"counts_out", c.counts_out, (size_t)c.n * VORS_REPOSE_COUNTS * 4, nullptr}};
+    return overlap_refusals(w, in, out);
+}
+
+extern "C" vors_status repose_points_device(const char* who, ReposeCall call, size_t pose_stride_bytes, hipStream_t s) {
+    vors_status st = stride_refusal(who, "pose_stride_bytes", pose_stride_bytes, 28, OPERATOR_STRIDE_LIMIT);
+    if (st != VORS_OK) return st;
+    call.pose_stride = stride_words(pose_stride_bytes, 7);
+    if ((st = repose_refusals(who, call)) != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    if ((st = stream_refusal(who, s)) != VORS_OK) return st;
+    launch_repose_points(call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_repose_points(int n, const float* d_xyz, const float* d_normals, const uint32_t* d_list_counts, int capacity,
+                               const vors_map_segment* d_segments, const uint32_t* d_n_segments, int max_keyframes, const void* d_poses7_new,
+                               size_t pose_stride_bytes, int node_capacity, const uint32_t* d_node_counts, const uint32_t* d_node_of_segment,
+                               float* d_xyz_out, float* d_normals_out, vors_map_segment* d_segments_out, uint32_t* d_counts_out, void* hip_stream) {
+    const ReposeCall call{n, d_xyz, d_normals, d_list_counts, capacity, d_segments, d_n_segments, max_keyframes, static_cast<const float*>(d_poses7_new),
+                          7, node_capacity, d_node_counts, d_node_of_segment, d_xyz_out, d_normals_out, d_segments_out, d_counts_out};
+    return repose_points_device("repose_points", call, pose_stride_bytes, static_cast<hipStream_t>(hip_stream));
+}
+
+vors_status vors_repose_points_host(const float* xyz, const float* normals, uint32_t count, int capacity, const vors_map_segment* segments,
+                                    uint32_t n_segments, int max_keyframes, const float* poses7_new, uint32_t node_count, int node_capacity,
+                                    const uint32_t* node_of_segment, float* xyz_out, float* normals_out, vors_map_segment* segments_out,
+                                    uint32_t counts_out[VORS_REPOSE_COUNTS]) {
+    const ReposeCall c{1, xyz, normals, &count, capacity, segments, &n_segments, max_keyframes, poses7_new, 7, node_capacity, &node_count,
+                       node_of_segment, xyz_out, normals_out, segments_out, counts_out};
+    if (vors_status st = repose_refusals("repose_points_host", c); st != VORS_OK) return st;
+    const uint32_t total = std::min<uint32_t>(count, (uint32_t)capacity), n_rec = std::min<uint32_t>(n_segments, (uint32_t)max_keyframes);
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(segments);
+    // the decision and the two poses of every recorded segment, from the records as they are before anything is written
+    std::vector<uint8_t> moved(n_rec);
+    std::vector<Iso> A(n_rec), B(n_rec);
+    uint32_t counts[VORS_REPOSE_COUNTS] = {0, 0, 0, 0, 0, 0};
+    for (uint32_t k = 0; k < n_rec; ++k) {
+        const uint32_t node = repose_node(k, node_of_segment, node_count, node_capacity);
+        const float* b7 = node != VORS_REPOSE_NO_NODE ? poses7_new + (size_t)node * 7 : nullptr;
+        moved[k] = repose_moves(segments[k].pose7, b7) ? 1 : 0;
+        A[k] = iso_load(segments[k].pose7);
+        B[k] = moved[k] ? iso_load(b7) : A[k];
+        counts[REPOSE_SEGMENTS_MOVED] += moved[k];
+    }
+    uint32_t k = 0;
+    for (uint32_t r = 0; r < total; ++r) {
+        while (k + 1u < n_rec && words[(size_t)(k + 1u) * MAP_SEGMENT_WORDS + 1] <= r) ++k;  // the last record whose first is <= r
+        uint32_t lo = 0, hi = 0;
+        if (n_rec) repose_segment_ranks(words, k, n_rec, total, &lo, &hi);
+        const bool recorded = r >= lo && r < hi;
+        const V3 p{xyz[3 * (size_t)r], xyz[3 * (size_t)r + 1], xyz[3 * (size_t)r + 2]};
+        const bool finite = repose_finite3(p);
+        V3 q = p;
+        if (recorded && moved[k] && finite) {
+            q = repose_point(A[k], B[k], p);
+            counts[REPOSE_MAX_SHIFT] = std::max(counts[REPOSE_MAX_SHIFT], repose_shift_bits(p, q));
+        }
+        counts[!finite ? REPOSE_NONFINITE : !recorded ? REPOSE_NO_RECORD : moved[k] ? REPOSE_MOVED : REPOSE_KEPT] += 1u;
+        if (xyz_out) {
+            float* o = xyz_out + 3 * (size_t)r;
+            o[0] = q.x; o[1] = q.y; o[2] = q.z;
+        }
+        if (normals_out) {
+            V3 m{normals[3 * (size_t)r], normals[3 * (size_t)r + 1], normals[3 * (size_t)r + 2]};
+            if (recorded && moved[k] && repose_finite3(m)) m = repose_normal(A[k], B[k], m);
+            float* o = normals_out + 3 * (size_t)r;
+            o[0] = m.x; o[1] = m.y; o[2] = m.z;
+        }
+    }
+    if (segments_out)
+        for (uint32_t s = 0; s < n_rec; ++s) {
+            vors_map_segment rec = segments[s];
+            if (moved[s]) iso_store(B[s], rec.pose7);
+            segments_out[s] = rec;
+        }
+    if (counts_out) std::memcpy(counts_out, counts, sizeof(counts));
+    return VORS_OK;
+}
+
+static vors_status voxel_filter_refusals(const char* who, const VoxelFilterCall& c, const void* workspace, size_t workspace_bytes) {
+    const std::string w(who);
+    if (c.n < 1 || c.n > 65535) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": n must be in 1..65535");
+    if (c.capacity < 1) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": capacity must be >= 1");
+    if (!c.xyz || !c.list_counts) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a list (xyz, list_counts) is NULL");
+    if (!c.index || !c.counts_out || !c.overflow) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": index, counts_out or overflow is NULL");
+    if (!(c.voxel_m > 0.0f) || !(c.voxel_m <= 3.4028234663852886e38f))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": voxel size voxel_m must be finite and > 0");
+    if (c.table_slots < 64 || c.table_slots > (1 << 30) || (c.table_slots & (c.table_slots - 1)) != 0)
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": table_slots must be a power of two in 64..2^30");
+    if ((c.pixel_out && !c.pixel) || (c.gray_out && !c.gray) || (c.normals_out && !c.normals))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": a gathered output (pixel_out, gray_out, normals_out) without its input");
+    if (c.segments_out && (!c.segments || !c.n_segments || c.max_keyframes < 1))
+        return fail(VORS_ERR_INVALID_ARGUMENT, w + ": segments_out without segments, their count or max_keyframes >= 1");
+    for (const void* p : {(const void*)c.xyz, (const void*)c.list_counts, (const void*)c.index, (const void*)c.counts_out, (const void*)c.overflow,
+                          (const void*)c.pixel, (const void*)c.normals, (const void*)c.xyz_out, (const void*)c.pixel_out, (const void*)c.normals_out,
+                          (const void*)c.segments, (const void*)c.n_segments, (const void*)c.segments_out})
+        if ((uintptr_t)p % 4 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, w + ": every array but the greys must be 4-byte aligned");
+    const size_t ranks = (size_t)c.n * (size_t)c.capacity, words = (size_t)c.n * 4;
+    const size_t recs = c.segments_out ? (size_t)c.n * (size_t)c.max_keyframes * sizeof(vors_map_segment) : 0;
+    const std::vector<ArgSpan> in{{"xyz", c.xyz, ranks * 12, nullptr}, {"list_counts", c.list_counts, words, nullptr}, {"pixel", c.pixel, ranks * 4, nullptr},
+                                  {"gray", c.gray, ranks, nullptr}, {"normals", c.normals, ranks * 12, nullptr}, {"segments", c.segments, recs, nullptr},
+                                  {"n_segments", c.segments_out ? c.n_segments : nullptr, words, nullptr}};
+    const std::vector<ArgSpan> out{{"workspace", workspace, workspace_bytes, nullptr}, {"index", c.index, ranks * 4, nullptr},
+                                   {"counts_out", c.counts_out, words, nullptr}, {"overflow", c.overflow, words, nullptr},
+                                   {"xyz_out", c.xyz_out, ranks * 12, nullptr}, {"pixel_out", c.pixel_out, ranks * 4, nullptr},
+                                   {"gray_out", c.gray_out, ranks, nullptr}, {"normals_out", c.normals_out, ranks * 12, nullptr},
+                                   {"segments_out", c.segments_out, recs, nullptr}};
+    return overlap_refusals(w, in, out);
+}
+
+uint64_t vors_voxel_filter_workspace_bytes(int n, int capacity, int table_slots) {
+    if (n < 1 || capacity < 1 || table_slots < 64 || table_slots > (1 << 30)) return 0;
+    return (uint64_t)voxel_filter_workspace_carve(nullptr, nullptr, n, capacity, table_slots);
+}
+
+vors_status vors_voxel_filter_points(int n, const float* d_xyz, const uint32_t* d_list_counts, int capacity, float voxel_m, int table_slots,
+                                     void* d_workspace, const uint32_t* d_pixel, const uint8_t* d_gray, const float* d_normals,
+                                     const vors_map_segment* d_segments, const uint32_t* d_n_segments, int max_keyframes, uint32_t* d_index,
+                                     uint32_t* d_counts_out, uint32_t* d_overflow, float* d_xyz_out, uint32_t* d_pixel_out, uint8_t* d_gray_out,
+                                     float* d_normals_out, vors_map_segment* d_segments_out, void* hip_stream) {
+    const char* who = "voxel_filter_points";
+    VoxelFilterCall call{};
+    call.n = n; call.xyz = d_xyz; call.list_counts = d_list_counts; call.capacity = capacity; call.voxel_m = voxel_m; call.table_slots = table_slots;
+    call.index = d_index; call.counts_out = d_counts_out; call.overflow = d_overflow;
+    call.pixel = d_pixel; call.gray = d_gray; call.normals = d_normals;
+    call.xyz_out = d_xyz_out; call.pixel_out = d_pixel_out; call.gray_out = d_gray_out; call.normals_out = d_normals_out;
+    call.segments = d_segments; call.n_segments = d_n_segments; call.max_keyframes = max_keyframes; call.segments_out = d_segments_out;
+    if (!d_workspace)
+        return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": d_workspace is NULL (the pass allocates nothing: vors_voxel_filter_workspace_bytes)");
+    if ((uintptr_t)d_workspace % 16 != 0) return fail(VORS_ERR_INVALID_ARGUMENT, std::string(who) + ": d_workspace must be 16-byte aligned");
+    vors_status st = voxel_filter_refusals(who, call, d_workspace, (size_t)vors_voxel_filter_workspace_bytes(n, capacity, table_slots));
+    if (st != VORS_OK) return st;
+    if ((st = require_device()) != VORS_OK) return st;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if ((st = stream_refusal(who, s)) != VORS_OK) return st;
+    voxel_filter_workspace_carve(&call, d_workspace, n, capacity, table_slots);
+    launch_voxel_filter_points(call, s);
+    HIP_TRY(hipGetLastError());
+    return VORS_OK;
+}
+
+vors_status vors_voxel_filter_points_host(const float* xyz, uint32_t count, int capacity, float voxel_m, int table_slots, const uint32_t* pixel,
+                                          const uint8_t* gray, const float* normals, const vors_map_segment* segments, uint32_t n_segments,
+                                          int max_keyframes, uint32_t* index, uint32_t* count_out, uint32_t* overflow, float* xyz_out,
+                                          uint32_t* pixel_out, uint8_t* gray_out, float* normals_out, vors_map_segment* segments_out) {
+    VoxelFilterCall c{};
+    c.n = 1; c.xyz = xyz; c.list_counts = &count; c.capacity = capacity; c.voxel_m = voxel_m; c.table_slots = table_slots;
+    c.index = index; c.counts_out = count_out; c.overflow = overflow; c.pixel = pixel; c.gray = gray; c.normals = normals;
+    c.xyz_out = xyz_out; c.pixel_out = pixel_out; c.gray_out = gray_out; c.normals_out = normals_out;
+    c.segments = segments; c.n_segments = &n_segments; c.max_keyframes = max_keyframes; c.segments_out = segments_out;
+    if (vors_status st = voxel_filter_refusals("voxel_filter_points_host", c, nullptr, 0); st != VORS_OK) return st;
+    const uint32_t total = std::min<uint32_t>(count, (uint32_t)capacity);
+    std::unordered_map<uint64_t, uint32_t> first_of;  // key -> its first rank
+    uint32_t kept = 0;
+    for (uint32_t r = 0; r < total; ++r) {
+        const float* w = xyz + 3 * (size_t)r;
+        const uint64_t key = voxel_key(voxel_m, w[0], w[1], w[2]);
+        if (key == VORS_VOXEL_NONE || !first_of.emplace(key, r).second) continue;
+        index[kept] = r;
+        if (xyz_out) std::memcpy(xyz_out + 3 * (size_t)kept, w, 12);
+        if (pixel_out) pixel_out[kept] = pixel[r];
+        if (gray_out) gray_out[kept] = gray[r];
+        if (normals_out) std::memcpy(normals_out + 3 * (size_t)kept, normals + 3 * (size_t)r, 12);
+        kept += 1;
+    }
+    *count_out = kept;
+    *overflow = first_of.size() > (size_t)table_slots ? 1u : 0u;  // (the device's result is then unspecified; this one stays exact)
+    if (segments_out) {
+        const uint32_t n_rec = std::min<uint32_t>(n_segments, (uint32_t)max_keyframes);
+        for (uint32_t k = 0; k < n_rec; ++k) {
+            vors_map_segment rec = segments[k];
+            const uint32_t lo = voxel_filter_below(index, kept, (uint64_t)rec.first);
+            const uint32_t hi = voxel_filter_below(index, kept, (uint64_t)rec.first + (uint64_t)rec.count);
+            rec.first = lo;
+            rec.count = hi - lo;
+            segments_out[k] = rec;
+        }
+    }
+    return VORS_OK;
+}
+
 void vors_camera_project(const float cam5[5], const float pose7[7], const float* xyz, int n, float* uvw_out) {
     const Intr k = intr_from_cam5(cam5);
     for (int i = 0; i < n; ++i) {

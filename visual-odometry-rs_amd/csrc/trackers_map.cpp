@@ -679,6 +679,25 @@ vors_status vors_trackers_map_voxel_means(vors_trackers* t, uint32_t min_count, 
     return VORS_OK;
 }
 
+vors_status vors_trackers_repose_map(vors_trackers* t, const void* d_poses7_new, size_t pose_stride_bytes, int node_capacity,
+                                     const uint32_t* d_node_counts, const uint32_t* d_node_of_segment, float* d_xyz_out, float* d_normals_out,
+                                     vors_map_segment* d_segments_out, uint32_t* d_counts_out, void* hip_stream) {
+    if (vors_status st = entry_guard("repose_map", t, &MAP); st != VORS_OK) return st;
+    const Map& m = t->map;
+    if (!t->initialised) return fail(VORS_ERR_INVALID_ARGUMENT, "repose_map: called before vors_trackers_init (there is no map yet)");
+    if (d_xyz_out == m.xyz || (d_normals_out && d_normals_out == m.normals.n) || d_segments_out == m.segments)
+        return fail(VORS_ERR_INVALID_ARGUMENT, "repose_map: an output is the handle's own array (the handle's map stays as tracking left it)");
+    vors_batch* b = t->batch;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    DeviceGuard guard(b->device);
+    if (vors_status st = check_stream(b, s); st != VORS_OK) return st;
+    // the handle's own lists, normals (when enabled), counters and segments are the inputs: read only, the caller's arrays are written
+    const ReposeCall call{t->n_seq, m.xyz, m.normals.on ? m.normals.n : nullptr, m.counts, m.capacity, m.segments, m.n_segments, m.max_keyframes,
+                          static_cast<const float*>(d_poses7_new), 7, node_capacity, d_node_counts, d_node_of_segment, d_xyz_out, d_normals_out,
+                          d_segments_out, d_counts_out};
+    return repose_points_device("repose_map", call, pose_stride_bytes, s);
+}
+
 vors_status vors_tracker_enable_map_voxel_stats(vors_tracker* t) {
     if (vors_status st = entry_guard("enable_map_voxel_stats", t); st != VORS_OK) return st;
     if (t->seq->map.normals.on)

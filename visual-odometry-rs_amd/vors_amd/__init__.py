@@ -121,6 +121,8 @@ EXPORTED_SYMBOLS = [
     "vors_pose_graph_workspace_bytes", "vors_pose_graph_optimize", "vors_pose_graph_optimize_host", "vors_pose_graph_jacobians_host",
     "vors_loop_signatures", "vors_loop_signatures_host", "vors_loop_candidates", "vors_loop_candidates_host",
     "vors_loop_verify_edges", "vors_loop_verify_edges_host",
+    "vors_repose_points", "vors_repose_points_host", "vors_trackers_repose_map",
+    "vors_voxel_filter_workspace_bytes", "vors_voxel_filter_points", "vors_voxel_filter_points_host",
     "vors_tracker_enable_map_normals", "vors_tracker_read_map_normals",
     "vors_trackers_enable_map_icp", "vors_trackers_map_icp", "vors_tracker_enable_map_icp", "vors_tracker_read_map_icp",
     "vors_map_icp_window_host", "vors_map_icp_verdict_host",
@@ -262,6 +264,14 @@ def lib():
         lc_verify = [u32, vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, u32, f, f, f, f, f, vp, vp, vp, vp, vp, i, vp, vp, vp]
         _lib.vors_loop_verify_edges.argtypes = lc_verify + [vp]
         _lib.vors_loop_verify_edges_host.argtypes = lc_verify
+        repose_out = [vp, vp, vp, vp]  # xyz, normals, segments, counts
+        _lib.vors_repose_points.argtypes = [i, vp, vp, vp, i, vp, vp, i, vp, sz, i, vp, vp] + repose_out + [vp]
+        _lib.vors_repose_points_host.argtypes = [vp, vp, u32, i, vp, u32, i, vp, u32, i, vp] + repose_out
+        _lib.vors_trackers_repose_map.argtypes = [vp, vp, sz, i, vp, vp] + repose_out + [vp]
+        _lib.vors_voxel_filter_workspace_bytes.argtypes = [i, i, i]
+        _lib.vors_voxel_filter_workspace_bytes.restype = C.c_uint64
+        _lib.vors_voxel_filter_points.argtypes = [i, vp, vp, i, f, i, vp, vp, vp, vp, vp, vp, i] + [vp] * 8 + [vp]
+        _lib.vors_voxel_filter_points_host.argtypes = [vp, u32, i, f, i, vp, vp, vp, vp, u32, i, vp, C.POINTER(u32), C.POINTER(u32)] + [vp] * 5
         _lib.vors_trackers_enable_map_icp.argtypes = [vp, vp]
         _lib.vors_trackers_map_icp.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         _lib.vors_tracker_enable_map_icp.argtypes = [vp, vp]
@@ -1228,6 +1238,7 @@ class Trackers:
     sequence with the whole tracker state machine (poses, keyframe test, per-sequence keyframe promotion) on the device."""
 
     _map = None  # enable_map()'s arguments, once it was accepted
+    _map_normals = None  # enable_map_normals()'s, likewise
 
     def __init__(self, config, n_sequences, rows, cols, device=None):
         self.config, self.n, self.rows, self.cols = config, n_sequences, rows, cols
@@ -1362,6 +1373,7 @@ class Trackers:
         keyframe's pose): central differences `step` pixels wide, neighbours further than jump_m metres in depth left out."""
         args = _map_normals_args((step, jump_m))
         _check(lib().vors_trackers_enable_map_normals(self._h, *args))
+        self._map_normals = args
 
     def map_normals(self, copy=True):
         """-> [n, capacity, 3] float32 tensor (vors_trackers_map_normals), valid in stream order after the last init() / track(): entry r
@@ -1422,6 +1434,32 @@ class Trackers:
         distinct voxels of a sequence so far (== map()["counts"] while it has not overflowed), "overflow" [n] int32, non-zero once a
         sequence's voxels outgrew table_slots. copy=False: views of the handle's own buffers, which die with this object."""
         return self._views(lib().vors_trackers_map_voxels, copy, occupied=((), "<i4"), overflow=((), "<i4"))
+
+    def repose_map(self, poses, node_counts, node_of_segment=None, xyz_out=True, normals_out=None, segments_out=True, counts=True):
+        """The keyframe map re-posed after pose-graph optimisation (vors_trackers_repose_map): repose_points() on the handle's own lists,
+        normals (with enable_map_normals()), counters and segments, written into NEW tensors (or the caller's), on the current stream, not
+        synchronised. The handle is only read: its map stays as tracking left it. poses [n, node_capacity, >= 7] float32, node_counts [n]
+        int32, node_of_segment [n, max_keyframes] int32 or None (segment k is node k). normals_out None = True exactly when the map has
+        normals. The result as in repose_points(); a new tensor starts as a copy of the handle's."""
+        import torch
+        who = "repose_map"
+        _, cap, nkf, _ = self._map or (0, 1, 1, 0)  # (no map: the entry refuses)
+        dev = _torch_device(self._device)
+        _repose_list_args(who, self.n, cap, nkf, dev, (("node_counts", node_counts, torch.int32, ()),
+                                                       ("node_of_segment", node_of_segment, torch.int32, (nkf,))))
+        ncap, stride = _repose_poses(who, poses, self.n)
+        if normals_out is None:
+            normals_out = self._map_normals is not None
+        own = self.map(copy=False) if self._map else {}
+        bufs = (own["xyz"].clone() if xyz_out is True and own else _out_buf(xyz_out, (self.n, cap, 3), torch.float32, dev),
+                self.map_normals() if normals_out is True and self._map_normals else _out_buf(normals_out, (self.n, cap, 3), torch.float32, dev),
+                own["segments"].clone() if segments_out is True and own else _out_buf(segments_out, (self.n, nkf, 40), torch.uint8, dev),
+                _out_buf(counts, (self.n, REPOSE_COUNTS), torch.int32, dev))
+        dp = Batch._dp
+        _check(lib().vors_trackers_repose_map(self._h, dp(poses), stride, ncap, dp(node_counts), dp(node_of_segment), *[dp(t) for t in bufs],
+                                              Batch._stream()))
+        self._repose_refs = (poses, node_counts, node_of_segment)
+        return _repose_result(bufs, xyz_out, normals_out, segments_out, counts)
 
     def render_map(self, level=0, poses=None, ranges=None, footprint=1, depth=True, gray=True, counts=False, zkey=False):
         """The keyframe map seen from one pose per sequence (vors_trackers_render_map): render_points() on the handle's own map with the
@@ -2451,6 +2489,176 @@ def loop_verify_edges_host(pairs, model_fwd, status_fwd, edge_capacity, model_bw
                                              float(max_prior_rot), float(weight), some(e), some(ms), some(io), some(ew), _ptr(ec), int(edge_capacity),
                                              some(out["verdict"]), some(out["residuals"]), some(out["counts"])))
     out["edge_count"] = int(ec[0])
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- the corrected map
+REPOSE_COUNTS = 6  # VORS_REPOSE_COUNTS: points moved, kept, non-finite, without a record; segments moved; bits of the largest shift
+REPOSE_NO_NODE = 0xFFFFFFFF  # a word of node_of_segment: this keyframe is not in the graph
+
+
+def _repose_list_args(who, n, cap, nkf, dev, tensors):
+    """(name, tensor or None, dtype, shape behind [n]) per argument: dtype, shape, contiguity and device, the way pose_graph_optimize
+    checks its own."""
+    for name, t, dtype, shape in tensors:
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != (n,) + shape or not t.is_contiguous() or t.device != dev):
+            raise VorsError(f"{who}: {name} must be a contiguous {dtype} tensor {(n,) + shape} on the lists' device")
+
+
+def _repose_poses(who, poses, n):
+    import torch
+    if poses.dtype != torch.float32 or poses.dim() != 3 or poses.shape[0] != n or poses.shape[2] < 7 or not poses.is_contiguous():
+        raise VorsError(f"{who}: poses float32 [n, node_capacity, >= 7], contiguous")
+    return poses.shape[1], (0 if poses.shape[2] == 7 else 4 * poses.shape[2])
+
+
+def _repose_result(bufs, xyz_out, normals_out, segments_out, counts):
+    return _result(("xyz", _asked(xyz_out), bufs[0]), ("normals", _asked(normals_out), bufs[1]), ("segments", _asked(segments_out), bufs[2]),
+                   ("counts", _asked(counts), bufs[3]))
+
+
+def repose_points(xyz, list_counts, segments, n_segments, poses, node_counts, normals=None, node_of_segment=None, xyz_out=True,
+                  normals_out=None, segments_out=True, counts=True):
+    """Re-pose n point lists after pose-graph optimisation (vors_repose_points; handle-free) -> dict of tensors on the current stream, not
+    synchronised: "xyz" and "normals" [n, capacity, 3] float32 (exactly the ranks below min(count, capacity) written), "segments"
+    [n, max_keyframes, 40] uint8 (the used records, pose7 replaced where the segment moved), "counts" [n, REPOSE_COUNTS] int32. xyz /
+    normals [n, capacity, 3] float32, list_counts / n_segments / node_counts [n] int32, segments [n, max_keyframes, 40] uint8 — the tensors
+    of Trackers.map() and map_normals(); poses [n, node_capacity, >= 7] float32, pose_graph_optimize()'s "poses" (a wider last dimension
+    is the pose stride); node_of_segment [n, max_keyframes] int32 or None (segment k is node k; -1 = REPOSE_NO_NODE). Each output may be
+    True (a new tensor: xyz / normals start as copies of the inputs, segments likewise), a tensor to write into — xyz, normals and
+    segments themselves for in place — or False; normals_out None = True exactly when normals are given."""
+    import torch
+    who = "repose_points"
+    if xyz.dtype != torch.float32 or xyz.dim() != 3 or xyz.shape[2] != 3 or not xyz.is_contiguous():
+        raise VorsError(f"{who}: xyz float32 [n, capacity, 3], contiguous")
+    n, cap, _ = xyz.shape
+    nkf = segments.shape[1] if segments.dim() == 3 else -1
+    dev = xyz.device
+    _repose_list_args(who, n, cap, nkf, dev, (("normals", normals, torch.float32, (cap, 3)), ("list_counts", list_counts, torch.int32, ()),
+                                              ("segments", segments, torch.uint8, (nkf, 40)), ("n_segments", n_segments, torch.int32, ()),
+                                              ("node_counts", node_counts, torch.int32, ()),
+                                              ("node_of_segment", node_of_segment, torch.int32, (nkf,))))
+    ncap, stride = _repose_poses(who, poses, n)
+    if normals_out is None:
+        normals_out = normals is not None
+    bufs = (xyz.clone() if xyz_out is True else _out_buf(xyz_out, (n, cap, 3), torch.float32, dev),
+            normals.clone() if normals_out is True and normals is not None else _out_buf(normals_out, (n, cap, 3), torch.float32, dev),
+            segments.clone() if segments_out is True else _out_buf(segments_out, (n, nkf, 40), torch.uint8, dev),
+            _out_buf(counts, (n, REPOSE_COUNTS), torch.int32, dev))
+    dp = Batch._dp
+    _check(lib().vors_repose_points(n, dp(xyz), dp(normals), dp(list_counts), cap, dp(segments), dp(n_segments), nkf, dp(poses), stride, ncap,
+                                    dp(node_counts), dp(node_of_segment), *[dp(t) for t in bufs], Batch._stream()))
+    return _repose_result(bufs, xyz_out, normals_out, segments_out, counts)
+
+
+def _segments_host(who, segments):
+    """A list's records on the host: a MAP_SEGMENT_DTYPE array [k] or their bytes [k, 40] -> a contiguous structured array [k]."""
+    a = np.asarray(segments)
+    if a.dtype != MAP_SEGMENT_DTYPE:
+        a = np.ascontiguousarray(a, np.uint8)
+        if a.ndim != 2 or a.shape[1] != 40:
+            raise VorsError(f"{who}: segments must be a MAP_SEGMENT_DTYPE array [k] or uint8 [k, 40]")
+        a = a.view(MAP_SEGMENT_DTYPE)[:, 0]
+    return np.ascontiguousarray(a.reshape(-1))
+
+
+def repose_points_host(xyz, segments, poses, normals=None, node_of_segment=None, count=None, n_segments=None, node_count=None):
+    """The rule of repose_points for ONE list on the host (vors_repose_points_host; needs no GPU; the texts the kernels run): xyz /
+    normals [capacity, 3] float32, segments a MAP_SEGMENT_DTYPE array [max_keyframes], poses [node_capacity, 7] float32, node_of_segment
+    [max_keyframes] uint32 or None; count / n_segments / node_count: None = the capacities (above them: clipped) -> dict: "xyz",
+    "normals" (None without normals), "segments" (copies of the inputs, re-posed), "counts" uint32 [REPOSE_COUNTS]."""
+    who = "repose_points_host"
+    p = np.ascontiguousarray(xyz, np.float32)
+    nm = None if normals is None else np.ascontiguousarray(normals, np.float32)
+    sg = _segments_host(who, segments)
+    ps = np.ascontiguousarray(poses, np.float32)
+    nos = None if node_of_segment is None else np.ascontiguousarray(node_of_segment, np.uint32)
+    if (p.ndim != 2 or p.shape[1] != 3 or (nm is not None and nm.shape != p.shape) or ps.ndim != 2 or ps.shape[1] != 7
+            or (nos is not None and nos.shape != (len(sg),))):
+        raise VorsError(f"{who}: xyz / normals [capacity, 3], poses [node_capacity, 7], node_of_segment [max_keyframes] or None")
+    out = dict(xyz=p.copy(), normals=None if nm is None else nm.copy(), segments=sg.copy(), counts=np.zeros(REPOSE_COUNTS, np.uint32))
+    some = lambda a: _ptr(a) if a is not None and a.size else None  # noqa: E731
+    _check(lib().vors_repose_points_host(some(p), some(nm), len(p) if count is None else _u32("count", count), len(p), some(sg),
+                                         len(sg) if n_segments is None else _u32("n_segments", n_segments), len(sg), some(ps),
+                                         len(ps) if node_count is None else _u32("node_count", node_count), len(ps), some(nos),
+                                         some(out["xyz"]), some(out["normals"]), some(out["segments"]), _ptr(out["counts"])))
+    return out
+
+
+def voxel_filter_workspace_bytes(n, capacity, table_slots):
+    """Bytes of the workspace voxel_filter_points() needs (vors_voxel_filter_workspace_bytes); 0 for arguments the pass refuses."""
+    return int(lib().vors_voxel_filter_workspace_bytes(int(n), int(capacity), int(table_slots)))
+
+
+def voxel_filter_points(xyz, list_counts, voxel_m, table_slots, pixel=None, gray=None, normals=None, segments=None, n_segments=None,
+                        workspace=None, xyz_out=True, index=True, counts=True, overflow=True, pixel_out=None, gray_out=None, normals_out=None,
+                        segments_out=None):
+    """One point per occupied voxel of n point lists, the first in each list's order (vors_voxel_filter_points; handle-free) -> dict of
+    tensors on the current stream, not synchronised: "index" [n, capacity] int32 (the source rank of every kept entry), "counts" and
+    "overflow" [n] int32, and the gathered "xyz" [n, capacity, 3], "pixel" [n, capacity] int32, "gray" [n, capacity] uint8, "normals"
+    [n, capacity, 3] and "segments" [n, max_keyframes, 40] uint8 (first / count for the filtered list) of the inputs that are given.
+    Entries at or beyond a list's count are not written. xyz [n, capacity, 3] float32, list_counts [n] int32; table_slots a power of two
+    in 64..2^30 that is at least a list's distinct voxels (otherwise that list's overflow word is set and its outputs are unspecified).
+    workspace: a uint8 tensor of voxel_filter_workspace_bytes() to reuse. An output may be True, a tensor to write into (never an input)
+    or False; the gathered ones default to True exactly when their input is given."""
+    import torch
+    who = "voxel_filter_points"
+    if xyz.dtype != torch.float32 or xyz.dim() != 3 or xyz.shape[2] != 3 or not xyz.is_contiguous():
+        raise VorsError(f"{who}: xyz float32 [n, capacity, 3], contiguous")
+    n, cap, _ = xyz.shape
+    nkf = segments.shape[1] if segments is not None and segments.dim() == 3 else 0
+    dev = xyz.device
+    _repose_list_args(who, n, cap, nkf, dev, (("list_counts", list_counts, torch.int32, ()), ("pixel", pixel, torch.int32, (cap,)),
+                                              ("gray", gray, torch.uint8, (cap,)), ("normals", normals, torch.float32, (cap, 3)),
+                                              ("segments", segments, torch.uint8, (nkf, 40)), ("n_segments", n_segments, torch.int32, ())))
+    pixel_out, gray_out, normals_out, segments_out = [given is not None if o is None else o for o, given in
+                                                      ((pixel_out, pixel), (gray_out, gray), (normals_out, normals), (segments_out, segments))]
+    need = voxel_filter_workspace_bytes(n, cap, int(table_slots))
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise VorsError(f"{who}: expected a contiguous uint8 workspace of at least {need} bytes")
+    bufs = (_out_buf(index, (n, cap), torch.int32, dev, always=True), _out_buf(counts, (n,), torch.int32, dev, always=True),
+            _out_buf(overflow, (n,), torch.int32, dev, always=True), _out_buf(xyz_out, (n, cap, 3), torch.float32, dev),
+            _out_buf(pixel_out, (n, cap), torch.int32, dev), _out_buf(gray_out, (n, cap), torch.uint8, dev),
+            _out_buf(normals_out, (n, cap, 3), torch.float32, dev), _out_buf(segments_out, (n, nkf, 40), torch.uint8, dev))
+    dp = Batch._dp
+    _check(lib().vors_voxel_filter_points(n, dp(xyz), dp(list_counts), cap, float(voxel_m), int(table_slots), dp(workspace), dp(pixel), dp(gray),
+                                          dp(normals), dp(segments), dp(n_segments), nkf, *[dp(t) for t in bufs], Batch._stream()))
+    names = ("index", "counts", "overflow", "xyz", "pixel", "gray", "normals", "segments")
+    asked = (index, counts, overflow, xyz_out, pixel_out, gray_out, normals_out, segments_out)
+    return _result(*[(name, _asked(o), t) for name, o, t in zip(names, asked, bufs)])
+
+
+def voxel_filter_points_host(xyz, voxel_m, table_slots=1 << 30, pixel=None, gray=None, normals=None, segments=None, count=None,
+                             n_segments=None):
+    """The rule of voxel_filter_points for ONE list on the host (vors_voxel_filter_points_host; needs no GPU): the first occurrence of
+    every key of voxel_keys(). xyz [capacity, 3] float32, pixel [capacity] uint32, gray [capacity] uint8, normals [capacity, 3], segments
+    a MAP_SEGMENT_DTYPE array; count / n_segments: None = the capacities -> dict: "count", "overflow" (1 when the distinct voxels exceed
+    table_slots; the result is exact all the same), "index" uint32 [count], and "xyz", "pixel", "gray", "normals" [count, ...],
+    "segments" of the inputs that are given."""
+    who = "voxel_filter_points_host"
+    p = np.ascontiguousarray(xyz, np.float32)
+    px = None if pixel is None else np.ascontiguousarray(pixel, np.uint32)
+    g = None if gray is None else np.ascontiguousarray(gray, np.uint8)
+    nm = None if normals is None else np.ascontiguousarray(normals, np.float32)
+    sg = None if segments is None else _segments_host(who, segments)
+    if (p.ndim != 2 or p.shape[1] != 3 or (px is not None and px.shape != (len(p),)) or (g is not None and g.shape != (len(p),))
+            or (nm is not None and nm.shape != p.shape)):
+        raise VorsError(f"{who}: xyz / normals [capacity, 3], pixel / gray [capacity]")
+    cap = len(p)
+    like = lambda a: None if a is None else np.zeros_like(a)  # noqa: E731
+    out = dict(index=np.zeros(cap, np.uint32), xyz=np.zeros_like(p), pixel=like(px), gray=like(g), normals=like(nm), segments=like(sg))
+    kept, over = C.c_uint32(), C.c_uint32()
+    some = lambda a: _ptr(a) if a is not None and a.size else None  # noqa: E731
+    _check(lib().vors_voxel_filter_points_host(some(p), cap if count is None else _u32("count", count), cap, float(voxel_m), int(table_slots),
+                                               some(px), some(g), some(nm), some(sg),
+                                               0 if sg is None else (len(sg) if n_segments is None else _u32("n_segments", n_segments)),
+                                               0 if sg is None else len(sg), some(out["index"]), C.byref(kept), C.byref(over), some(out["xyz"]),
+                                               some(out["pixel"]), some(out["gray"]), some(out["normals"]), some(out["segments"])))
+    k = kept.value
+    out = {name: (a if name == "segments" else a[:k]) for name, a in out.items() if a is not None}
+    out.update(count=k, overflow=over.value)
     return out
 
 
